@@ -11,17 +11,24 @@ RCCL inside the timed region).  All reference features on (flow-aided masks, Lap
 delayed masks and poses, pose re-sync, depth-render outlier rejection).  One "step" = one camera frame for every object
 = ROFTFilter::filtering_step x n_objects; frames are handed to the engine in batches of --batch frames
 (roft_frames_submit).  Inputs (depth, flow, masks) are resident in HBM before the timed region; the PCIe-inclusive rates
-(HOST inputs) are measured in the same run and reported beside `value`, never as it.
+(HOST inputs) are measured with --full and reported beside `value`, never as it.
+
+A plain run does only what the headline needs: set-up, the rehearsal, the timed windows and the result line.  Everything
+else it can measure or check -- CPU baselines, ADD-S against the CPU path and against ground truth, the PCIe-inclusive
+legs, the cold run, the live latency, the instrumented windows behind the roofline and the per-kernel breakdown -- runs
+with --full.  --dump-outputs DIR writes what the last timed step returned to a caller (seeded inputs: two builds compare
+output for output).
 
 Round 5: the timed region is run --windows times (default 5) in one invocation, every time on a FRESH engine and on the workload's
 streams generated anew into FRESH buffers (W warm-up steps, barrier + synchronize, exactly K timed steps, synchronize + barrier, max over ranks), with
 no timing machinery of any kind inside it; `value` is the MEDIAN window (a real run: its ms_per_step, host time and batch
 trace are the top-level ones), `runs` lists all of them.  A 20-step window is 1.3 ms of GPU time in which one host thread
 enqueues ~70 launches: one window can be hit by anything that happens on the box in that millisecond, five cannot.  The
-roofline kernel is timed (HIP event pair on its own dispatch + device clock span) in one MORE window of the same shape,
+roofline kernel is timed (--full: HIP event pair on its own dispatch + device clock span) in one MORE window of the same shape,
 `instrumented_window`, which is never `value`.
 """
 import argparse
+import copy
 import json
 import os
 import subprocess
@@ -35,6 +42,9 @@ sys.path.insert(0, ROOT)
 import numpy as np
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E datasheet peak (/opt/skills/guides/MI355X_MICROARCH.md)
+DUMP_MASK_PIXELS = 4096   # --dump-outputs: pixels of every object's propagated mask in the fixed sample
+REHEARSAL_FRAMES = 64     # frames of the rehearsal's own (disjoint) stream set
+LOOP_PERIOD = 384         # longer runs cycle through the images of a closed motion of this many frames (synth.make_stream(period=))
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -290,7 +300,22 @@ def parse():
     p.add_argument("--windows", type=int, default=5,
                    help="timed windows per invocation (each: fresh engine, the streams generated anew into fresh buffers, W warm-up + K timed steps); "
                         "`value` is the median window")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also measure and check everything beyond the headline figure: the CPU baselines and ADD-S against the CPU path, "
+                        "the PCIe-inclusive legs, the cold run and the live latency, the instrumented windows (roofline, per-kernel "
+                        "breakdown) and the accuracy against ground truth.  Off: set up, warm up, the timed windows, the result line")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed windows, write what the last timed step of the last window returned to a caller (poses, "
+                        "twists and their covariances, flow point counts, outlier decisions, a fixed sample of the propagated masks) "
+                        "as DIR/<name>.npy, float64 / float32")
+    args = p.parse_args()
+    if not args.full:
+        # a plain run does only what its headline figure needs: the legs below are --full's
+        args.no_cpu_baseline = True
+        args.pcie_frames = 0
+        args.no_extras = True
+        args.no_kernel_timing = True
+    return args
 
 
 def split_batches(first, last, T, ramp=False):
@@ -387,29 +412,45 @@ def main():
     n_extra = 0 if args.no_kernel_timing else int(os.environ.get("ROFT_BENCH_EXTRA_FRAMES", "24"))   # frames behind the instrumented window: per-kernel breakdown
     n_timed_end = args.warmup + args.steps
     n_frames = n_timed_end   # frames of a window's stream set (the instrumented set carries n_extra more)
+    # Up to LOOP_PERIOD + 1 frames every frame is an image of its own.  A longer run -- any number of steps -- tracks streams that
+    # cycle through the LOOP_PERIOD + 1 images of a closed motion (as BASELINE config #5's long runs do): the delivery schedules
+    # (masks, poses, outliers, drops) run on for every frame, the images resident in HBM stay bounded.
+    loop_period = LOOP_PERIOD if (n_timed_end > LOOP_PERIOD + 1 and not args.shared_scene) else None
+    imgs = np.array([synth.loop_index(k, loop_period) if loop_period else k for k in range(n_timed_end + n_extra)])   # image of frame k
     cam = synth.Camera.shape_a() if args.shape == "A" else synth.Camera.shape_b()
     ftype = synth.FLOW_F32C2 if args.flow == "f32" else synth.FLOW_S16C2
 
     # The streams of a window stay resident in HBM while it runs (depth 4 B + mask 1 B per pixel, flow per grid cell): refuse a
-    # K + W that cannot fit instead of running the box out of memory.
+    # set of images that cannot fit instead of running the box out of memory.
     g = 1 if args.flow == "f32" else 4
     flow_frame_bytes = (cam.width // g) * (cam.height // g) * (8 if args.flow == "f32" else 4)
     per_frame = cam.width * cam.height * 5 + flow_frame_bytes
-    # (alive at once: window 0's set, kept for the accuracy figures, + the running window's -- or the instrumented one with its
-    #  n_extra frames; the rehearsal's set is freed before the first window)
-    need = per_frame * (2 * n_timed_end + n_extra) * n_obj
+    # (the workload's set is generated once and stays alive; every other set -- a window's fresh copy, the instrumented window's
+    #  longer set, the cold run's -- is made only where there is room next to it, and the leg uses the workload's set otherwise)
+    def n_images(n_fr):
+        return min(n_fr, loop_period + 1) if loop_period else n_fr
+
+    need = per_frame * n_images(n_timed_end) * n_obj
     free_b, _total_b = torch.cuda.mem_get_info(dev)
     if need > 0.8 * free_b:
-        raise SystemExit("bench.py: %d frames x %d objects of synthetic input (two sets alive) need %.0f GB of HBM, %.0f GB are free; "
-                         "lower --steps / --warmup / --objects" % (n_timed_end, n_obj, need / 1e9, free_b / 1e9))
+        raise SystemExit("bench.py: %d images x %d objects of synthetic input need %.0f GB of HBM, %.0f GB are free; "
+                         "lower --objects" % (n_images(n_timed_end), n_obj, need / 1e9, free_b / 1e9))
+
+    def room_for(n_fr):
+        """A further stream set of n_fr frames fits next to what is alive (torch's cached blocks count as free)."""
+        free_now, _t = torch.cuda.mem_get_info(dev)
+        cached = torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+        return per_frame * n_images(n_fr) * n_obj <= 0.8 * (free_now + cached)
 
     # ---- synthetic streams, generated on the GPU and left resident in HBM
     gen_s = [0.0]
 
-    def make_streams(seed_base, n_fr, zero_remote=True):
+    def make_streams(seed_base, n_fr, zero_remote=True, loop=True):
         """The rank's objects' streams: stream seed = seed_base + global object index (seed_base 4000 = 1000 x config #4:
-        the workload; other bases: same shapes and object models, different motion, noise and images)."""
+        the workload; other bases: same shapes and object models, different motion, noise and images).  loop: the
+        run's looping streams where it has them (loop_period)."""
         t_g = time.time()
+        lp = dict(period=loop_period, n_schedule=n_fr) if (loop and loop_period) else {}
         if args.shared_scene:
             # one scene for every object of every rank: all ranks build the same stream (masks, poses and the mesh stay
             # local), but only the ingest rank keeps its images -- the others receive them batch by batch (broadcast_frames)
@@ -424,10 +465,42 @@ def main():
         for gid in my_objects:
             scale = 0.8 + 0.4 * (((gid % 64) * 7) % 10) / 9.0
             half = tuple(h * scale for h in synth.CRACKER_BOX_HALF_EXTENTS)
-            out.append(synth.make_stream(seed_base + gid, n_fr, cam, flow_type=ftype, half_extents=half, device=dev))
+            out.append(synth.make_stream(seed_base + gid, n_fr, cam, flow_type=ftype, half_extents=half, device=dev, **lp))
         torch.cuda.synchronize()
         gen_s[0] += time.time() - t_g
         return out, None
+
+    def copy_streams(src):
+        """The same bytes in fresh buffers: what generating the set anew gives (the generator is deterministic), in milliseconds
+        instead of seconds -- device-to-device copies, not read by anything before the window that gets them."""
+        sts, scene = src
+        done = {}
+
+        def cp(st):
+            if id(st) not in done:
+                c = copy.copy(st)
+                c.depth, c.flow, c.mask_gt = st.depth.clone(), st.flow.clone(), st.mask_gt.clone()
+                done[id(st)] = c
+            return done[id(st)]
+        out = [cp(st) for st in sts], (cp(scene) if scene is not None else None)
+        torch.cuda.synchronize()
+        return out
+
+    canon = {}                # (seed base, frames) -> the set generated first; later windows get fresh copies of it
+    first_touch = [True]      # every window read buffers nothing had read before it
+
+    def window_streams(seed_base, n_fr):
+        key = (seed_base, n_fr)
+        if key not in canon:
+            out = make_streams(seed_base, n_fr)
+            if not any(k[1] == n_fr for k in canon):   # (one set per length is kept: ROFT_BENCH_WINDOW_SEEDS=1 windows are not)
+                canon[key] = out
+            return out
+        if room_for(n_fr):
+            return copy_streams(canon[key])
+        # (no room for a second set: the window reads the workload's own buffers -- hundreds of GB, far beyond any cache)
+        first_touch[0] = False
+        return canon[key]
 
     def new_engine(max_objects):
         cfg = E.default_config(cam.width, cam.height, ftype, max_objects=max_objects, device=local_rank, max_batch_frames=T)
@@ -445,9 +518,10 @@ def main():
             eng.add_object(d, *st.mesh)
 
     def frame_dict(st, k, src, kind):
-        mi = st.mask_delivery[k]
+        mi = st.mask_delivery[k]    # (an image index already)
+        i = st.image(k)
         pose = (st.pose_meas[k, :3], st.pose_meas[k, 3:]) if st.pose_valid[k] else None
-        return dict(depth=src["depth"][k].data_ptr(), flow=src["flow"][k].data_ptr() if st.flow_valid[k] else None,
+        return dict(depth=src["depth"][i].data_ptr(), flow=src["flow"][i].data_ptr() if st.flow_valid[k] else None,
                     mask=src["mask"][mi].data_ptr() if mi >= 0 else None, pose=pose, dt=st.dt, mem_kind=kind)
 
     def host_copies(sts):   # pinned host copies of the streams: the boundary then pays the PCIe transfer
@@ -508,14 +582,17 @@ def main():
     if args.rehearsal_ms > 0:
         # Process warm-up, once, before the first window: scratch engines track a DISJOINT stream set (seeds 20000 +) of the
         # same shapes and batch cuts -- kernels loaded, allocations sized, the device out of its idle power state under the
-        # tracker's own load.  No frame of any window is read by it.
-        reh_streams, _rs = make_streams(20000, n_timed_end, zero_remote=False)   # (nothing broadcasts in the rehearsal)
+        # tracker's own load.  No frame of any window is read by it.  Its set holds at most REHEARSAL_FRAMES frames: the
+        # batches of the windows' plan that fall within them, repeated on fresh engines for --rehearsal-ms.
+        n_reh = min(n_timed_end, REHEARSAL_FRAMES)
+        reh_plan = [(k0, t) for k0, t in warm_splits + timed_splits if k0 + t <= n_reh] or plan_batches(0, n_reh)
+        reh_streams, _rs = make_streams(20000, n_reh, zero_remote=False, loop=False)   # (nothing broadcasts in the rehearsal)
         reh_host = host_copies(reh_streams)
         t_w = time.perf_counter()
         while True:
             _c, scratch = new_engine(n_obj)
             add_objects(scratch, reh_streams)
-            for k0, t in warm_splits + timed_splits:
+            for k0, t in reh_plan:
                 arr, _keep, tt = build(scratch, k0, t, reh_streams, reh_host)
                 scratch.submit_batch_raw(arr, tt)
                 scratch.step()
@@ -566,7 +643,7 @@ def main():
         steps, engine sync (+ the all-gather of the result rows at N > 1), synchronize + barrier, max over ranks.  instrument:
         roft_engine_enable_timing level (0 for every window that can become `value`).  Returns the record of the window and
         what the caller keeps (engine, streams, gathered rows)."""
-        sts, scene = make_streams(seed_base, n_timed_end + extra)
+        sts, scene = window_streams(seed_base, n_timed_end + extra)
         hst = host_copies(sts)
         cfg, eng = new_engine(n_obj)
         add_objects(eng, sts)
@@ -629,12 +706,36 @@ def main():
         }
         return rec, dict(eng=eng, streams=sts, scene=scene, host=hst, gathered=gathered, cfg=cfg, bcast=bcast_bytes[0])
 
+    mask_sample = np.sort(np.random.default_rng(12345).choice(cam.width * cam.height, DUMP_MASK_PIXELS, replace=False))
+
+    def read_outputs(eng):
+        """What a caller of the tracker holds after the last step, per object of this rank: roft_get_outputs, roft_get_state and
+        a fixed sample (same pixels every run) of the propagated mask of roft_get_mask."""
+        outs = eng.outputs()
+        res = {k: [] for k in ("pose", "pose_cov", "twist", "twist_cov", "n_flow_points", "outlier_selected", "outlier_L",
+                               "mask_pixels", "mask_sample")}
+        for o in range(n_obj):
+            pose, P, tw, Pv = eng.state(o)
+            m = eng.mask(o).reshape(-1)
+            res["pose"].append(np.array(outs[o].pose[:]))
+            res["pose_cov"].append(P)
+            res["twist"].append(np.array(outs[o].twist[:]))
+            res["twist_cov"].append(Pv)
+            res["n_flow_points"].append(float(outs[o].n_flow_points))
+            res["outlier_selected"].append(float(outs[o].outlier_selected))
+            res["outlier_L"].append(np.array(outs[o].outlier_L[:]))
+            res["mask_pixels"].append(float(np.count_nonzero(m)))
+            res["mask_sample"].append(m[mask_sample].astype(np.float32) / 255.0)
+        return {k: np.asarray(v, np.float32 if k == "mask_sample" else np.float64) for k, v in res.items()}
+
     # ---- the timed windows
     windows = []
     keep0 = None
+    dump_local = None
     for w in range(n_windows):
-        # Every window tracks the CANONICAL streams of config #4 (seeds 4000 + object index), generated anew into fresh
-        # buffers: no frame has been read by anything when its window reads it, and all windows measure the SAME workload -- the
+        # Every window tracks the CANONICAL streams of config #4 (seeds 4000 + object index, SURVEY 8d), generated once and copied
+        # into fresh buffers for every later window (window_streams): no frame has been read by anything when its window reads it
+        # (unless no second set fits in HBM), and all windows measure the SAME workload -- the
         # spread of `runs` is the machine's, not the data's.  (Round 5 measured windows on other seeds first: the same generator
         # with seeds 5000 + / 6000 + tracks 15 % slower at 64 objects and 40 % slower at 16 -- different motion, different work --,
         # which made the windows incomparable.  ROFT_BENCH_WINDOW_SEEDS=1: window i on seeds 4000 + 1000 i.)
@@ -644,11 +745,15 @@ def main():
             # window 0 tracks the canonical streams (seeds 4000 +): accuracy figures, --dump-rows.  Its results are read now and the
             # engine is closed like the others' -- a tracker whose run is over does not sit next to the next one
             keep0 = keep
-            pose_log, twist_log, npts_log, sel_log = keep["eng"].get_log(0, n_timed_end)
+            if args.full:
+                pose_log, twist_log, npts_log, sel_log = keep["eng"].get_log(0, n_timed_end)
             rows0 = None if keep["gathered"] is not None else np.ascontiguousarray(keep["eng"].get_log_rows(args.warmup, args.steps).transpose(1, 0, 2))
+        if w == n_windows - 1 and args.dump_outputs:
+            dump_local = read_outputs(keep["eng"])
         keep["eng"].close()
         if w != 0:
             del keep
+    windows_first_touch = first_touch[0]
     order = sorted(range(n_windows), key=lambda i: windows[i]["value"])
     med = windows[order[(n_windows - 1) // 2]]   # the median window (the lower one of an even count): a run that happened
     value = med["value"]
@@ -669,9 +774,11 @@ def main():
         inst_seed = 4000 + (1000 * n_windows if os.environ.get("ROFT_BENCH_WINDOW_SEEDS") == "1" else 0)
         k1_ms = k1_cnt = span_ms = span_cnt = 0
         inst_values = []
+        # the breakdown frames need a longer set of their own: skipped where it does not fit next to the workload's
+        n_breakdown = n_extra if (n_extra > 0 and room_for(n_timed_end + n_extra)) else 0
         for wi in range(n_inst):
             last = wi == n_inst - 1
-            inst, keep_i = timed_window(inst_seed, instrument=(2 if full_marks else 1), extra=n_extra if last else 0)
+            inst, keep_i = timed_window(inst_seed, instrument=(2 if full_marks else 1), extra=n_breakdown if last else 0)
             e_i = keep_i["eng"]
             tm = e_i.timing()
             # the kernel that takes the flow measurements: the mask + measurement chain (one launch per batch), or -- images too large
@@ -692,7 +799,8 @@ def main():
             # the same launches on the device's own 100 MHz clock: first workgroup in -> last workgroup out
             k1_live["span_avg_us"] = 1e3 * span_ms / span_cnt
             k1_live["span_launches"] = span_cnt
-        if n_extra > 0:
+        if n_breakdown > 0:
+            canon.pop((inst_seed, n_timed_end + n_breakdown), None)   # (alive as inst_streams while the legs below need it)
             e_i.enable_timing(2)
             extra_b = [build(e_i, k0, t, keep_i["streams"], keep_i["host"]) for k0, t in extra_splits]
             run(e_i, extra_b, extra_splits, keep_i["scene"])
@@ -722,10 +830,10 @@ def main():
 
     sl = slice(args.warmup, n_timed_end)
     adds_gt_local = []
-    for o in range(n_obj):
+    for o in range(n_obj if args.full else 0):
         st = streams[o]
         est = np.concatenate([pose_log[:, o, 6:9], pose_log[:, o, 9:13]], 1)
-        gt = np.concatenate([st.gt.x, st.gt.q], 1)
+        gt = np.concatenate([st.gt.x, st.gt.q], 1)[imgs[:n_timed_end]]
         adds_gt_local.append(metrics.trajectory_adds(est[sl], gt[sl], model_points(st)))
     n_sample = min(args.cpu_sample_objects, n_obj)
     # ADD-S vs the CPU path at N > 1: every rank runs the oracle on its first ceil(sample / world) objects (25 frames of one
@@ -756,6 +864,15 @@ def main():
         dist.all_reduce(seen)   # one contribution per rank that is really in the communicator
         ranks_info = dict(all=allr, seen=int(seen.item()))
 
+    if args.dump_outputs and world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, dump_local)
+        dump_local = {k: np.concatenate([p_[k] for p_ in parts]) for k in dump_local}   # (block-sharded: rank order = object order)
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for k, v in dump_local.items():
+            np.save(os.path.join(args.dump_outputs, k + ".npy"), v)
+
     if rank != 0:
         if world > 1:
             dist.barrier()  # rank 0 is timing the CPU baseline and the PCIe legs
@@ -773,23 +890,25 @@ def main():
         args.pcie_frames = 0
         args.no_extras = True
 
-    if ranks_info is not None:
-        adds_gt = np.concatenate([np.asarray(a) for r in ranks_info["all"] for a in r["adds_gt"]])
-        adds_gt_objects = sum(len(r["adds_gt"]) for r in ranks_info["all"])
-    else:
-        adds_gt = np.concatenate(adds_gt_local)
-        adds_gt_objects = n_obj
-    # RMSE metrics of evaluation/metrics.py on this rank's sample (position cm, orientation deg, velocities with the
-    # pole moved to the object, evaluate.py:514-521)
-    est_x = np.concatenate([pose_log[sl, o, 6:9] for o in range(n_sample)])
-    est_q = np.concatenate([pose_log[sl, o, 9:13] for o in range(n_sample)])
-    gt_x = np.concatenate([streams[o].gt.x[sl] for o in range(n_sample)])
-    gt_q = np.concatenate([streams[o].gt.q[sl] for o in range(n_sample)])
-    est_tw = metrics.object_velocity_from_twist(np.concatenate([twist_log[sl, o] for o in range(n_sample)]), gt_x)
-    gt_tw = metrics.object_velocity_from_twist(np.concatenate([streams[o].gt.twist[sl] for o in range(n_sample)]), gt_x)
-    rmse = {"position_cm": metrics.rmse_cartesian_3d(gt_x, est_x), "orientation_deg": metrics.rmse_angular(gt_q, est_q),
-            "linear_velocity_cm_s": metrics.rmse_linear_velocity(gt_tw[:, :3], est_tw[:, :3]),
-            "angular_velocity_deg_s": metrics.rmse_angular_velocity(gt_tw[:, 3:], est_tw[:, 3:])}
+    adds_gt, adds_gt_objects, rmse = None, None, None
+    if args.full:
+        if ranks_info is not None:
+            adds_gt = np.concatenate([np.asarray(a) for r in ranks_info["all"] for a in r["adds_gt"]])
+            adds_gt_objects = sum(len(r["adds_gt"]) for r in ranks_info["all"])
+        else:
+            adds_gt = np.concatenate(adds_gt_local)
+            adds_gt_objects = n_obj
+        # RMSE metrics of evaluation/metrics.py on this rank's sample (position cm, orientation deg, velocities with the
+        # pole moved to the object, evaluate.py:514-521)
+        est_x = np.concatenate([pose_log[sl, o, 6:9] for o in range(n_sample)])
+        est_q = np.concatenate([pose_log[sl, o, 9:13] for o in range(n_sample)])
+        gt_x = np.concatenate([streams[o].gt.x[imgs[sl]] for o in range(n_sample)])
+        gt_q = np.concatenate([streams[o].gt.q[imgs[sl]] for o in range(n_sample)])
+        est_tw = metrics.object_velocity_from_twist(np.concatenate([twist_log[sl, o] for o in range(n_sample)]), gt_x)
+        gt_tw = metrics.object_velocity_from_twist(np.concatenate([streams[o].gt.twist[imgs[sl]] for o in range(n_sample)]), gt_x)
+        rmse = {"position_cm": metrics.rmse_cartesian_3d(gt_x, est_x), "orientation_deg": metrics.rmse_angular(gt_q, est_q),
+                "linear_velocity_cm_s": metrics.rmse_linear_velocity(gt_tw[:, :3], est_tw[:, :3]),
+                "angular_velocity_deg_s": metrics.rmse_angular_velocity(gt_tw[:, 3:], est_tw[:, 3:])}
     cpu = None
     cpu_multi = None
     adds_cpu = None
@@ -815,7 +934,7 @@ def main():
                 mi = st.mask_delivery[k]
                 pose = (st.pose_meas[k, :3], st.pose_meas[k, 3:]) if st.pose_valid[k] else None
                 t1 = time.perf_counter()
-                r = trk.step(st.dt, depth[k], flow[k] if st.flow_valid[k] else None, masks[mi] if mi >= 0 else None, pose)
+                r = trk.step(st.dt, depth[imgs[k]], flow[imgs[k]] if st.flow_valid[k] else None, masks[mi] if mi >= 0 else None, pose)
                 cpu_time += time.perf_counter() - t1
                 cpu_frames += 1
                 ref_pose[k, :3] = r.pose[6:9]
@@ -840,7 +959,7 @@ def main():
     pcie = None
     # (on the longest stream set of the run: the instrumented window's, W + K + 24 frames, else window 0's)
     long_streams = inst_streams if (inst is not None and not args.shared_scene) else streams
-    n_long = int(long_streams[0].depth.shape[0])
+    n_long = int(long_streams[0].depth.shape[0]) if long_streams is not None else 0
     if args.pcie_frames > 0 and n_long >= T + 2:
         def pcie_leg(shared, in_place=False):
             n_run = min(n_long, T + args.pcie_frames)
@@ -925,7 +1044,9 @@ def main():
             return time.perf_counter() - t1
         # (the device has idled through the CPU baseline and the host work above: no clock warm-up precedes this run)
         # fresh frames as well: a third stream set (seeds + 2000, same shapes) that nothing has read before this run
-        cold_streams, _cs = make_streams(4000, n_timed_end, zero_remote=False)   # (the canonical workload, generated anew: comparable with `value`)
+        # (the canonical workload in fresh buffers: comparable with `value`; the workload's own set where no second one fits)
+        cold_streams = copy_streams((streams, None))[0] if room_for(n_timed_end) else streams
+        cold_fresh = cold_streams is not streams
         torch.cuda.synchronize()
         time.sleep(1.0)
         _c, e2 = new_engine(n_obj)
@@ -934,6 +1055,7 @@ def main():
         e2.close()
         del cold_streams
         value_cold = dict(value=n_obj * args.steps / dt_cold, ms_per_step=1e3 * dt_cold / args.steps, host_enqueue_ms_per_step=1e3 * cold_host[0] / args.steps,
+                          fresh_frames=cold_fresh,
                           note="a timed sequence of the same shape on a fresh engine and on FRESH frames (the workload's streams generated "
                                "once more into fresh buffers, read by nothing before) after the device has idled (CPU baseline, host work, 1 s sleep), "
                                "no rehearsal of any kind and nothing of this shape run for seconds: what a short burst from an idle GPU gets")
@@ -987,7 +1109,8 @@ def main():
         nl = npts_inst[args.warmup:n_timed_end]   # (of the instrumented window: the launches that were timed)
         ran = nl >= 0
         # mask pixels of the frame the measurement reads (the previous frame's propagated mask ~ its ground-truth mask)
-        mask_px = np.mean([float((st.mask_gt[max(args.warmup - 1, 0):n_timed_end - 1] > 0).sum().item()) / args.steps for st in inst_streams])
+        mask_px = np.mean([float((st.mask_gt[torch.as_tensor(imgs[max(args.warmup - 1, 0):n_timed_end - 1], device=st.mask_gt.device)] > 0).sum().item())
+                           / args.steps for st in inst_streams])
         cand = mask_px / float(int(cfg.subsampling_radius))
         n_kept = float(np.mean(nl[ran])) if ran.any() else 0.0
         # Declared bytes (culled form `mask + rho W H (4 + e / g^2)`, rho = fraction of TILES touched): the tile the
@@ -1094,7 +1217,8 @@ def main():
     if kernels:
         e_b = 8 if ftype == synth.FLOW_F32C2 else 4
         plane_b = cam.width * cam.height // 8
-        mask_px_o = float(np.mean([float((st.mask_gt[:n_timed_end] > 0).sum().item()) / max(n_timed_end, 1) for st in streams]))
+        mask_px_o = float(np.mean([float((st.mask_gt[torch.as_tensor(imgs[:n_timed_end], device=st.mask_gt.device)] > 0).sum().item()) / max(n_timed_end, 1)
+                                   for st in streams]))
         n_feat = mask_px_o / 2.0
         flows_per_frame = (period - 1 + min(period, 6)) / float(period) if period > 0 else 1.0   # one flow per frame, `period` on the frame a mask arrives
         nv = float(np.mean([st.mesh[0].shape[0] for st in streams]))
@@ -1172,11 +1296,14 @@ def main():
         "windows": windows,
         "instrumented_window": inst,
         "inputs": "host (PCIe-inclusive)" if args.host_inputs else "resident in HBM",
-        "timed_frames_first_touch": True,
+        "timed_frames_first_touch": windows_first_touch,
         "method": {"windows": n_windows, "rehearsal_ms": args.rehearsal_ms,
-                   "rehearsal_streams": "disjoint from every window's (seeds 20000 +, same shapes and batch cuts), once, before the first window" if args.rehearsal_ms > 0 else None,
+                   "rehearsal_streams": ("disjoint from every window's (seeds 20000 +, same shapes and batch cuts, at most %d frames), once, before "
+                                         "the first window" % REHEARSAL_FRAMES) if args.rehearsal_ms > 0 else None,
                    "window_streams": "every window (and the instrumented one): the canonical streams of config #4, seeds 4000 + object index "
-                                     "(SURVEY 8d), generated anew into fresh buffers -- first touch by the window, same workload in every window",
+                                     "(SURVEY 8d), generated once; every later window gets a device-to-device copy in fresh buffers (the same "
+                                     "bytes as generating them anew) -- first touch by the window, same workload in every window -- or, where no "
+                                     "second set fits in HBM, the generated set itself (timed_frames_first_touch false)",
                    "host_spin_ms": 3.0, "host_spin": "before the W warm-up steps of every window (the window follows them behind one barrier + synchronize)",
                    "batch_cuts": "explicit --splits" if args.splits else ("full batches" if args.no_align else "batches end with the pose-arrival frame"),
                    "scheduling": "a function of the batch index since the engine was last idle (roft_batch_trace::steady), not of host timing",
@@ -1189,7 +1316,7 @@ def main():
                                (cam.width, cam.height, "CV_32FC2" if ftype == synth.FLOW_F32C2 else "CV_16SC2",
                                 cfg.flow_grid, total_obj,
                                 "%d per GPU" % n_obj if args.scaling == "strong" else "%d per GPU (weak scaling)" % n_obj, T),
-                   "objects_per_gpu": n_obj, "objects_total": total_obj, "width": cam.width, "height": cam.height,
+                   "objects_per_gpu": n_obj, "objects_total": total_obj, "width": cam.width, "height": cam.height, "loop_period": loop_period,
                    "batch_frames": T, "timed_batches": [t for _k0, t in timed_splits], "ranks": world, "backend": backend},
         # ---- N > 1: who was there (one entry per rank of the communicator), what each owned, and each rank's OWN time per window
         #      (before the max over ranks) -- a SCALE line can be checked against the per-GPU points of the object sweep
@@ -1221,8 +1348,8 @@ def main():
         "value_cold": value_cold["value"] if value_cold else None,
         "cold_run": value_cold,
         "live_latency": live,
-        "adds_vs_gt_mm": {"mean": 1e3 * float(adds_gt.mean()), "auc": metrics.auc(adds_gt), "objects": adds_gt_objects,
-                          "note": "window 0 (the canonical streams), every object of every rank"},
+        "adds_vs_gt_mm": ({"mean": 1e3 * float(adds_gt.mean()), "auc": metrics.auc(adds_gt), "objects": adds_gt_objects,
+                           "note": "window 0 (the canonical streams), every object of every rank"} if adds_gt is not None else None),
         "adds_vs_cpu_ref_mm": ({"mean": 1e3 * float(adds_cpu.mean()), "max": 1e3 * float(adds_cpu.max()), "objects_per_rank": adds_cpu_objects}
                                if adds_cpu is not None else None),
         "rmse_vs_gt": rmse,

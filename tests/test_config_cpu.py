@@ -1,17 +1,17 @@
 """Configuration files of the reference -> roft_config / roft_object_desc (roft_amd/config.py): the libconfig subset, the
 `--a::b::c value` overrides of ConfigParser, and every key ROFTFilter's constructor consumes (src/roft/src/main.cpp:43-147,
-:286-325).  The reference's own config/*.cfg are read where the reference checkout is present (the build container)."""
+:286-325).  The reference's own config/*.cfg are stored under tests/golden/ref_config."""
 import ctypes as C
-import glob
 import math
 import os
 
 import pytest
 
+import util
 from roft_amd import _lib as L
 from roft_amd import config as K
 
-REF_CFG = sorted(glob.glob("/root/reference/config/*.cfg"))
+REF_CFG = util.REF_CONFIGS
 
 SMALL = """
 # a file in the reference's format, written for this test
@@ -74,9 +74,9 @@ def test_command_line_overrides():
         K.lookup(cfg, "measurement_model::nothing")
 
 
-@pytest.mark.skipif(not REF_CFG, reason="the reference checkout is not here")
-@pytest.mark.parametrize("path", REF_CFG)
+@pytest.mark.parametrize("path", REF_CFG, ids=os.path.basename)
 def test_reference_config_files(path):
+    assert len(REF_CFG) == 2
     cfg = K.parse_cfg(open(path).read())
     keys = set(K.all_keys(cfg))
     # every setting of the file is one main.cpp reads, and every setting the filter consumes is in the file

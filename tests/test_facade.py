@@ -369,7 +369,7 @@ def test_tracker_tail_logs_match_the_engine(tmp_path):
 
 # ---- the reference's executable sources against the facade ------------------------------------------------------------------
 REF_MAIN = "/root/reference/src/roft/src/main.cpp"
-REF_BIN = os.path.join(ROOT, "tests", "cpp", "_ref_build", "ROFT-tracker")
+REF_BIN = os.path.join(ROOT, "oracle", "_ref", "ROFT-tracker")       # (oracle/ref_build.py)
 
 
 def build_sources_check(tmp_path):
@@ -392,7 +392,8 @@ def test_reference_main_compiles_against_the_facade():
 
 def test_config_parser_cpp_reads_what_the_python_reader_reads(tmp_path):
     """include/compat/ConfigParser.h against roft_amd/config.py on a complete configuration with command-line overrides of
-    every type (as test/test.sh passes them), and -- in the dev container -- on the reference's own configuration files."""
+    every type (as test/test.sh passes them), and on the reference's own configuration files (tests/golden/ref_config)."""
+    import util
     from roft_amd import config as K
     exe = build_sources_check(tmp_path)
     cfg_path = str(tmp_path / "tracker.cfg")
@@ -402,10 +403,8 @@ def test_config_parser_cpp_reads_what_the_python_reader_reads(tmp_path):
             "--log::path", str(tmp_path), "--optical_flow_dataset::set", "nvof_1_slow/", "--measurement_model::pose::cov_q", "0.01,0.02,0.03",
             "--kinematic_model::pose::sigma_angular", "1e-2,0.01,0.01"]
     cases = [(cfg_path, over), (cfg_path, [])]
-    for name in ("config_fast_ycb.cfg", "config_ho3d.cfg"):
-        p = os.path.join("/root/reference/config", name)
-        if os.path.exists(p):
-            cases.append((p, over))
+    assert [os.path.basename(p) for p in util.REF_CONFIGS] == ["config_fast_ycb.cfg", "config_ho3d.cfg"]
+    cases += [(p, over) for p in util.REF_CONFIGS]
     for path, ov in cases:
         out = str(tmp_path / "cfg_out.txt")
         subprocess.check_call([exe, "cfg", out, "ROFT-tracker", "--from", path] + ov)
@@ -573,8 +572,8 @@ def test_file_sources_deliver_on_the_references_schedule(tmp_path):
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape", ["A_f32_grid1", "B_s16_grid4", "A_from_first_detection", "A_internal_mesh_db"])
 def test_reference_tracker_runs_on_this_engine(tmp_path, capsys, shape):
-    """The reference's own src/roft/src/main.cpp -- unmodified, built by __graft_entry__.build() in the dev container against
-    include/ROFT + include/compat and linked with libroft_hip.so -- started the way test/test.sh starts ROFT-tracker on a
+    """The reference's own src/roft/src/main.cpp -- unmodified, built by __graft_entry__.build() where a checkout of the reference is
+    at hand (oracle/ref_build.py) against include/ROFT + include/compat and linked with libroft_hip.so -- started the way test/test.sh starts ROFT-tracker on a
     sequence directory: it must write the five log files, and they must say what tools/run_sequence.py (the Python host over
     the same engine, same files, same configuration and overrides) says, to the six digits bfl::Logger prints."""
     import importlib.util
@@ -583,7 +582,7 @@ def test_reference_tracker_runs_on_this_engine(tmp_path, capsys, shape):
     from roft_amd import config as K
     from roft_amd import io, synth
     if not os.path.exists(REF_BIN):
-        pytest.skip("tests/cpp/_ref_build/ROFT-tracker is built where the reference checkout is (python __graft_entry__.py)")
+        pytest.skip("oracle/_ref/ROFT-tracker is built where a checkout of the reference is at hand (oracle/ref_build.py)")
     import copy
     if shape != "B_s16_grid4":     # config_ho3d.cfg's shape: 640x480 (here halved), CV_32FC2 flow per pixel
         n = 40
@@ -599,10 +598,8 @@ def test_reference_tracker_runs_on_this_engine(tmp_path, capsys, shape):
     if shape == "A_internal_mesh_db":
         # test/test.sh leaves model.use_internal_db = true / internal_db_name = "DOPE" of the configuration file alone and
         # only names the object: the mesh comes from the library's data base -- here the directory ROFT_MESH_DB names, holding
-        # the reference's own 003_cracker_box.obj (copied next to the binary by __graft_entry__.build())
-        db = os.path.join(os.path.dirname(REF_BIN), "meshes")
-        if not os.path.exists(os.path.join(db, "DOPE", "003_cracker_box.obj")):
-            pytest.skip("no mesh data base next to the binary")
+        # the reference's own meshes (fixtures under tests/golden/ref_meshes)
+        db = util.ref_mesh_db(tmp_path / "mesh_db")
         obj_name, env["ROFT_MESH_DB"] = "003_cracker_box", db
         mesh = os.path.join(db, "DOPE", "003_cracker_box.obj")
         for k in range(n):
@@ -770,7 +767,7 @@ def test_stamped_source_facade_equals_the_oracle(tmp_path):
 
 
 REF_DUMPER_MAIN = "/root/reference/tools/nvof/dumper/src/main.cpp"
-REF_DUMPER_BIN = os.path.join(ROOT, "tests", "cpp", "_ref_build", "ROFT-of-dumper")
+REF_DUMPER_BIN = os.path.join(ROOT, "oracle", "_ref", "ROFT-of-dumper")   # (oracle/ref_build.py)
 
 
 def test_reference_flow_dumper_compiles_against_the_facade():
@@ -790,7 +787,7 @@ def test_reference_flow_dumper_runs_on_the_hip_producer(tmp_path, version):
     import util
     from roft_amd import io, ops, synth
     if not os.path.exists(REF_DUMPER_BIN):
-        pytest.skip("tests/cpp/_ref_build/ROFT-of-dumper is built where the reference checkout is (python __graft_entry__.py)")
+        pytest.skip("oracle/_ref/ROFT-of-dumper is built where a checkout of the reference is at hand (oracle/ref_build.py)")
     n = 5
     st = util.stream(712, n, 2, with_gray=True)
     root = str(tmp_path / "seq")
@@ -850,16 +847,16 @@ def test_live_flow_source_with_the_references_constructor(tmp_path, product):
 
 
 def test_the_references_meshes_load(tmp_path):
-    """Dev container only: the seven meshes the reference compiles into its library (src/roft-lib/meshes/DOPE/*.obj, Meshlab
-    output with `vn` lines and `f a//n b//n c//n` faces) through the facade's OBJ reader and through roft_amd.io.load_obj: same
-    vertices and triangles; and the directory IS a valid ROFT_MESH_DB for MeshResource's internal data base."""
+    """The seven meshes the reference compiles into its library (src/roft-lib/meshes/DOPE/*.obj, Meshlab output with `vn` lines
+    and `f a//n b//n c//n` faces; fixtures under tests/golden/ref_meshes) through the facade's OBJ reader and through
+    roft_amd.io.load_obj: same vertices and triangles; and the directory IS a valid ROFT_MESH_DB for MeshResource's internal
+    data base."""
+    import util
     from roft_amd import io
-    db = "/root/reference/src/roft-lib/meshes"
-    if not os.path.isdir(db):
-        pytest.skip("the reference checkout is not here")
+    db = util.ref_mesh_db(tmp_path / "meshes")
     exe = build_sources_check(tmp_path)
     names = sorted(f for f in os.listdir(os.path.join(db, "DOPE")) if f.endswith(".obj"))
-    assert len(names) >= 6
+    assert len(names) == 7
     for name in names:
         path = os.path.join(db, "DOPE", name)
         verts, tris = io.load_obj(path)

@@ -78,11 +78,9 @@ def test_obj_loader(tmp_path):
     assert t.tolist() == [[0, 1, 2], [0, 2, 3], [0, 1, 2], [0, 2, 3], [0, 1, 2]]
 
 
-def test_obj_loader_on_the_reference_mesh():
-    ref = "/root/reference/src/roft-lib/meshes/DOPE/003_cracker_box.obj"
-    if not os.path.exists(ref):
-        pytest.skip("reference checkout not present (GPU box)")
-    v, t = io.load_obj(ref)
+def test_obj_loader_on_the_reference_mesh(tmp_path):
+    import util
+    v, t = io.load_obj(util.ref_cracker_box(tmp_path))       # (the reference's mesh, a fixture under tests/golden/ref_meshes)
     assert 7000 < len(v) < 9000 and 15000 < len(t) < 17000
     assert np.allclose(v.min(0), [-0.080, -0.102, -0.036], atol=2e-3) and np.allclose(v.max(0), [0.084, 0.112, 0.035], atol=2e-3)
     assert t.min() == 0 and t.max() == len(v) - 1

@@ -4,7 +4,6 @@ roft_object_add applies) agree on closed, inside-out, inconsistently wound, open
 multi-component and non-orientable meshes; and the oracle's render of a closed mesh without the triangles that face away is the
 render with them (the nearest surface of a closed mesh seen from outside faces the camera; reference: depth test LESS, no
 culling, src/roft-lib/src/SICAD.cpp:271-272)."""
-import os
 
 import numpy as np
 import pytest
@@ -14,8 +13,6 @@ import util
 from oracle import binding as ob
 from roft_amd import io, ops, synth
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CRACKER = os.path.join(ROOT, "tests", "cpp", "_ref_build", "meshes", "DOPE", "003_cracker_box.obj")
 
 
 @pytest.mark.parametrize("name", sorted(mesh_zoo.zoo()))
@@ -44,14 +41,13 @@ def test_flip_marks_the_triangles_wound_clockwise_seen_from_outside():
     assert np.array_equal(flip[:len(f_box)], f_box) and np.array_equal(flip[len(f_box):], 1 - f_box)
 
 
-def test_the_bench_mesh_and_the_references_cracker_box_are_closed():
+def test_the_bench_mesh_and_the_references_cracker_box_are_closed(tmp_path):
     v, t = synth.box_mesh(synth.CRACKER_BOX_HALF_EXTENTS, 36)
     assert ob.mesh_classify(v, t)[0] and ops.mesh_classify(v, t)[0]
-    if os.path.exists(CRACKER):   # (copied next to the reference build by __graft_entry__.build(): data, not tracked)
-        v, t = io.load_obj(CRACKER)
-        co, fo = ob.mesh_classify(v, t)
-        ce, fe = ops.mesh_classify(v, t)
-        assert co and ce and np.array_equal(fo, fe)
+    v, t = io.load_obj(util.ref_cracker_box(tmp_path))   # (the reference's mesh, a fixture under tests/golden/ref_meshes)
+    co, fo = ob.mesh_classify(v, t)
+    ce, fe = ops.mesh_classify(v, t)
+    assert co and ce and np.array_equal(fo, fe)
 
 
 @pytest.mark.parametrize("name", ["box", "box_reversed", "box_random_windings", "box_unwelded", "two_components", "torus", "hollow_box"])

@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 def run_bench(tmp_path, n_ranks, tag, port, extra=(), launcher=True, cpu_ref=False):
     out = str(tmp_path / ("rows_%s.npy" % tag))
     detail = str(tmp_path / ("detail_%s.json" % tag))
-    args = ["bench.py", "--gpus", str(n_ranks), "--steps", "14", "--warmup", "4", "--objects", "5", "--windows", "3",
+    args = ["bench.py", "--gpus", str(n_ranks), "--steps", "14", "--warmup", "4", "--objects", "5", "--windows", "3", "--full",
             "--pcie-frames", "0", "--no-extras", "--no-kernel-timing", "--rehearsal-ms", "0", "--dump-rows", out, "--json-out", detail] + list(extra)
     if not cpu_ref:
         args.append("--no-cpu-baseline")
@@ -104,13 +104,12 @@ def test_gpus_n_without_a_launcher_starts_the_ranks_itself(tmp_path):
 
 
 def test_the_drivers_command_prints_one_small_parseable_line(tmp_path):
-    """`python3 bench.py --gpus 1 --steps 20 --warmup 5` -- exactly what the driver runs and records as BENCH_rNN.json -- with every
-    leg on (CPU baselines, PCIe legs, cold run, instrumented windows): stdout is ONE line, under 4 KB, strict JSON, with the
-    contract's keys, `roofline` and `cpu_baseline` filled in; the side file holds the rest.  (Round 5's line was 20.7 KB and came
-    back as `parsed: null`.)"""
+    """`python3 bench.py --gpus 1 --steps 20 --warmup 5 --full` -- the driver's command with every leg on (CPU baselines, PCIe
+    legs, cold run, instrumented windows): stdout is ONE line, under 4 KB, strict JSON, with the contract's keys, `roofline` and
+    `cpu_baseline` filled in; the side file holds the rest.  (Round 5's line was 20.7 KB and came back as `parsed: null`.)"""
     detail = str(tmp_path / "detail.json")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--json-out", detail],
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--json-out", detail],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = r.stdout.strip().splitlines()
@@ -133,3 +132,59 @@ def test_the_drivers_command_prints_one_small_parseable_line(tmp_path):
     assert d["adds_vs_cpu_ref_mm"]["max"] < 1e-3
     full = json.load(open(detail))
     assert len(full["windows"]) == 5 and full["roofline"]["note"] and full["cpu_baseline_multicore"]
+
+
+def test_plain_run_times_the_steps_and_dumps_what_the_last_step_returned(tmp_path):
+    """A plain run (no --full): the timed windows and the result line only -- contract keys, exactly --steps timed steps,
+    ms_per_step of the median window, none of --full's legs --, and --dump-outputs writes what the last timed step returned:
+    the poses and twists are the last row of the timed region that --dump-rows saves (every window tracks the same streams)."""
+    rows_path, detail, dump = str(tmp_path / "rows.npy"), str(tmp_path / "detail.json"), str(tmp_path / "dump")
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "14", "--warmup", "4", "--objects", "5", "--windows", "3",
+                        "--dump-rows", rows_path, "--dump-outputs", dump, "--json-out", detail], cwd=ROOT, env=env, capture_output=True,
+                       text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = r.stdout.strip().splitlines()
+    assert len(lines) == 1 and len(lines[0]) < 4096
+    d = json.loads(lines[0], parse_constant=lambda c: pytest.fail("non-strict JSON constant " + c))
+    assert d["metric"] == "tracker frames/sec per object (640x480) + ADD-S vs CPU ref" and d["unit"] == "object-frames/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f64" and d["steps"] == 14 and d["warmup"] == 4
+    assert abs(d["value"] * d["ms_per_step"] - 5e3) < 1e-3 * 5e3 and len(d["runs"]) == 3
+    assert d["roofline"] is None and d["cpu_baseline"] is None
+    full = json.load(open(detail))
+    assert all(sum(b["frames"] for b in w["batches"]) == 14 for w in full["windows"])
+    for k in ("instrumented_window", "pcie_inclusive", "cold_run", "live_latency", "adds_vs_gt_mm", "adds_vs_cpu_ref_mm", "rmse_vs_gt"):
+        assert full[k] is None, k
+    assert full["kernels_post_run_breakdown"] == {}
+    shapes = {"pose": (5, 13), "pose_cov": (5, 12, 12), "twist": (5, 6), "twist_cov": (5, 6, 6), "n_flow_points": (5,),
+              "outlier_selected": (5,), "outlier_L": (5, 2), "mask_pixels": (5,), "mask_sample": (5, 4096)}
+    assert sorted(os.listdir(dump)) == sorted(k + ".npy" for k in shapes)
+    out = {k: np.load(os.path.join(dump, k + ".npy")) for k in shapes}
+    for k, shape in shapes.items():
+        assert out[k].shape == shape and out[k].dtype in (np.float32, np.float64) and np.isfinite(out[k]).all(), k
+    rows = np.load(rows_path)
+    assert np.allclose(out["pose"], rows[:, -1, :13], rtol=1e-12, atol=1e-12) and np.allclose(out["twist"], rows[:, -1, 13:], rtol=1e-12, atol=1e-12)
+    assert set(np.unique(out["mask_sample"])) <= {0.0, 1.0} and (out["mask_pixels"] >= 0).all()
+
+
+def test_a_run_longer_than_the_loop_period_cycles_through_the_images(tmp_path):
+    """More frames than bench.LOOP_PERIOD + 1: the streams cycle through the images of a closed motion (HBM holds the images,
+    not the frames), the timed steps are still exactly --steps, and the outputs of the last step are finite."""
+    sys.path.insert(0, ROOT)
+    import bench
+    steps = bench.LOOP_PERIOD + 40
+    rows_path, detail, dump = str(tmp_path / "rows.npy"), str(tmp_path / "detail.json"), str(tmp_path / "dump")
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", "4", "--objects", "3", "--windows", "2",
+                        "--dump-rows", rows_path, "--dump-outputs", dump, "--json-out", detail], cwd=ROOT, env=env, capture_output=True,
+                       text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    assert d["steps"] == steps and abs(d["value"] * d["ms_per_step"] - 3e3) < 1e-3 * 3e3
+    full = json.load(open(detail))
+    assert full["config"]["loop_period"] == bench.LOOP_PERIOD
+    assert sum(full["config"]["timed_batches"]) == steps      # (the engine's batch trace keeps only its last 64 batches)
+    rows = np.load(rows_path)
+    pose = np.load(os.path.join(dump, "pose.npy"))
+    assert rows.shape == (3, steps, 19) and np.isfinite(rows).all()
+    assert np.allclose(pose, rows[:, -1, :13], rtol=1e-12, atol=1e-12)

@@ -395,17 +395,12 @@ def test_outlier_test_hot_path_kernel(oracle, shape, scale, mesh_n, div):
             assert sel == (1 if ref[0][0] > 2.0 * ref[1][0] else 0) == want_sel, kw
 
 
-def test_render_and_outlier_test_on_a_mesh_of_the_reference(oracle):
-    """The reference's own 003_cracker_box.obj (7 866 vertices, 15 728 triangles of very different sizes, as Meshlab wrote it; copied
-    next to the built tracker by __graft_entry__.build() in the dev container -- data, git-ignored) instead of the synthetic
-    subdivided boxes: depth render bit exact against oracle/ro_render.c at both shapes, and the engine's outlier test in all its
-    launch shapes on a scene rendered from that mesh."""
-    import os
+def test_render_and_outlier_test_on_a_mesh_of_the_reference(oracle, tmp_path):
+    """The reference's own 003_cracker_box.obj (7 866 vertices, 15 728 triangles of very different sizes, as Meshlab wrote it; a
+    fixture under tests/golden/ref_meshes) instead of the synthetic subdivided boxes: depth render bit exact against
+    oracle/ro_render.c at both shapes, and the engine's outlier test in all its launch shapes on a scene rendered from that mesh."""
     from roft_amd import io, synth
-    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "cpp", "_ref_build", "meshes", "DOPE", "003_cracker_box.obj")
-    if not os.path.exists(path):
-        pytest.skip("tests/cpp/_ref_build/meshes is filled where the reference checkout is (python __graft_entry__.py)")
-    verts, tris = io.load_obj(path)
+    verts, tris = io.load_obj(util.ref_cracker_box(tmp_path))
     omesh, mesh = oracle.make_mesh(verts, tris), ops.make_mesh(verts, tris)
     rng = np.random.default_rng(21)
     for cam, div in ((synth.Camera.shape_a(), 2), (synth.Camera.shape_b(), 4)):

@@ -1,9 +1,35 @@
-"""Shared helpers for the tests: cached synthetic streams and oracle/engine drivers."""
+"""Shared helpers for the tests: cached synthetic streams, oracle/engine drivers and the stored fixtures of tests/golden."""
 import functools
+import glob
+import lzma
+import os
 
 import numpy as np
 
 from roft_amd import synth
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+# the reference's configuration files (config/*.cfg: settings only), stored as they are
+REF_CONFIGS = sorted(glob.glob(os.path.join(GOLDEN, "ref_config", "*.cfg")))
+
+
+def ref_mesh_db(dst):
+    """The seven meshes the reference compiles into its library (src/roft-lib/meshes/DOPE/*.obj, Meshlab output; stored
+    xz-compressed under tests/golden/ref_meshes) unpacked byte for byte to dst/DOPE/<name>.obj -- a directory that is a valid
+    ROFT_MESH_DB for MeshResource's internal data base.  Returns dst."""
+    dst = str(dst)
+    os.makedirs(os.path.join(dst, "DOPE"), exist_ok=True)
+    for src in sorted(glob.glob(os.path.join(GOLDEN, "ref_meshes", "DOPE", "*.obj.xz"))):
+        out = os.path.join(dst, "DOPE", os.path.basename(src)[:-3])
+        if not os.path.exists(out):
+            with lzma.open(src) as f, open(out, "wb") as g:
+                g.write(f.read())
+    return dst
+
+
+def ref_cracker_box(dst):
+    """The reference's 003_cracker_box.obj (7 866 vertices, 15 728 triangles), unpacked under dst: its path."""
+    return os.path.join(ref_mesh_db(dst), "DOPE", "003_cracker_box.obj")
 
 
 @functools.lru_cache(maxsize=16)

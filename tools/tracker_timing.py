@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-frame time of the reference's executable (tests/cpp/_ref_build/ROFT-tracker: its own main.cpp over this engine, built by
+"""Per-frame time of the reference's executable (oracle/_ref/ROFT-tracker: its own main.cpp over this engine, built by
 __graft_entry__.build() where the reference checkout is) on a synthetic Fast-YCB-shaped sequence directory, 1280x720 CV_16SC2
 grid 4 (config_fast_ycb.cfg's shape): microseconds per frame outside data loading (ROFT_FILTER_TIMING=1) with the images read in
 place from the pinned pool (the default) and staged through the HOST upload path (ROFT_FACADE_STAGED=1), and the mean of the
@@ -18,10 +18,10 @@ from roft_amd import config as K
 from roft_amd import io, synth
 import util
 
-REF_BIN = os.path.join(ROOT, "tests", "cpp", "_ref_build", "ROFT-tracker")
+REF_BIN = os.path.join(ROOT, "oracle", "_ref", "ROFT-tracker")
 n = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 60
 if not os.path.exists(REF_BIN):
-    raise SystemExit("tests/cpp/_ref_build/ROFT-tracker is built where the reference checkout is (python __graft_entry__.py)")
+    raise SystemExit("oracle/_ref/ROFT-tracker is built where a checkout of the reference is at hand (oracle/ref_build.py)")
 import copy
 st = copy.copy(util.stream(704, n, 1, shape="B", flow_type=synth.FLOW_S16C2, mesh_n=24, with_gray=True, device="cuda"))
 st.pose_meas = st.pose_meas.copy()
@@ -62,7 +62,7 @@ for tag, extra in (("in_place", {}), ("staged", {"ROFT_FACADE_STAGED": "1"})):
 same = res["in_place"]["pose"] == res["staged"]["pose"]
 for v in res.values():
     del v["pose"]
-out = dict(what="tests/cpp/_ref_build/ROFT-tracker (the reference's main.cpp over this engine), 1280x720 CV_16SC2 grid 4, one object, %d frames" % n,
+out = dict(what="oracle/_ref/ROFT-tracker (the reference's main.cpp over this engine), 1280x720 CV_16SC2 grid 4, one object, %d frames" % n,
            in_place=res["in_place"], staged=res["staged"], identical_pose_logs=same)
 print(json.dumps(out, indent=1))
 if "--out" in sys.argv:
