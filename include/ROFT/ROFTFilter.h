@@ -107,6 +107,15 @@ public:
         cfg_.pose_frames_between = pose_measurement_ ? pose_measurement_->get_frames_between_iterations() : 0;
         if (cfg_.pose_frames_between < 0) cfg_.pose_frames_between = 0;
         cfg_.max_objects = 1;
+        // How the outlier test renders (roft_config::render_mode) -- a semantics switch, read from the environment because the
+        // reference's main.cpp has no key for it: ROFT_RENDER_MODE=gl scores the alternatives on the reference's GL numerics,
+        // unset or "contract" keeps the render contract; any other value is an error.
+        if (const char* rm = std::getenv("ROFT_RENDER_MODE")) {
+            const std::string mode(rm);
+            if (mode == "gl") cfg_.render_mode = ROFT_RENDER_GL;
+            else if (mode == "contract" || mode.empty()) cfg_.render_mode = ROFT_RENDER_CONTRACT;
+            else throw std::runtime_error(log_name_ + "::ctor. Error: ROFT_RENDER_MODE must be \"gl\" or \"contract\", not \"" + mode + "\".");
+        }
 
         compat::throw_if(roft_default_object(&obj_), "ROFTFilter::ctor");
         for (int i = 0; i < 13; ++i) obj_.p_mean0[i] = initial_condition_p(i);          // v w x q(w x y z)   (cpp:76-79)

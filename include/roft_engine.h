@@ -43,6 +43,10 @@
 extern "C" {
 #endif
 
+/* Version of the ABI's structs and entry points; roft_abi_version() returns the value the library was built with.  A binding
+ * that mirrors the structs (roft_amd/_lib.py) refuses a library of another version.  2: roft_config::render_mode. */
+#define ROFT_ABI_VERSION 2
+
 #define ROFT_OK 0
 #define ROFT_ERR_INVALID (-1)  /* bad argument */
 #define ROFT_ERR_DEVICE (-2)   /* HIP runtime error / no device */
@@ -67,6 +71,21 @@ extern "C" {
  * faulting on the GPU; later submits trust the caller (the look-up costs microseconds per pointer). */
 #define ROFT_MEM_HOST 0
 #define ROFT_MEM_DEVICE 1
+
+/* How the outlier test renders the object (roft_config::render_mode, roft_render_depth_mode, roft_outlier_test_mode).  Both modes draw
+ * the nearest surface's eye-space depth at the pixel centres; they differ in which triangles they draw and in the arithmetic.
+ *  ROFT_RENDER_CONTRACT (default): the render contract of oracle/ro_render.c -- float arithmetic with one reciprocal per vertex and one
+ *    quotient per pixel, inclusive edges, and a mesh that roft_mesh_classify calls closed drawn without the triangles that face away
+ *    (while every vertex is in front of the near plane).  Limit: a closed mesh that intersects itself (a pocket pushed through another
+ *    face) can lose pixels the reference draws, because a triangle that faces away can then be the nearest surface.
+ *  ROFT_RENDER_GL: the numerics of the reference's OpenGL pipeline (SICAD.cpp:271-272, 1634-1637, shader_model.frag:33-51; oracle mode
+ *    RO_RENDER_GL): every triangle drawn, u = (fx X) / Z + cx, window z interpolated linearly in screen space (double plane equation),
+ *    24-bit depth buffer with GL_LESS (the first triangle in the caller's order wins a tie), the shader's float linearisation with
+ *    near 0.001 / far 1000, the top-left rule.  Not modelled (implementation-defined in GL): sub-pixel vertex snapping and near-plane
+ *    clipping (a triangle with a vertex at Z <= 0.001 is dropped).  Costs more: twice the triangles of a closed mesh, double-precision
+ *    work per covered pixel, an 8-byte LDS window per pixel. */
+#define ROFT_RENDER_CONTRACT 0
+#define ROFT_RENDER_GL 1
 
 /* frames per roft_frames_submit call (roft_config::max_batch_frames) */
 #define ROFT_MAX_BATCH_FRAMES 8
@@ -103,6 +122,8 @@ typedef struct {
 const char* roft_last_error_string(void);
 /* number of visible HIP devices (0 when there is none); never fails */
 int roft_device_count(void);
+/* ROFT_ABI_VERSION of the library; never fails */
+int roft_abi_version(void);
 
 /* ---- (1) operator level: host buffers, device 0 ----------------------------------------- */
 
@@ -174,6 +195,15 @@ int roft_outlier_test(const roft_camera* cam, int divider, const float* depth, c
 int roft_outlier_test_split(const roft_camera* cam, int divider, const float* depth, const uint8_t* mask, const roft_mesh* mesh,
                             const double x[6], const double q[8], int bands, int vertex_cache, int window_pixels, int split,
                             double L_out[2], long samples_out[2], int* selected_out, float* tiles_out);
+/* roft_render_depth / roft_outlier_test_split in render mode `mode` (ROFT_RENDER_*).  ROFT_RENDER_CONTRACT returns exactly what those
+ * two return.  ROFT_RENDER_GL renders with the reference's GL numerics (bit for bit RO_RENDER_GL of oracle/ro_render.c) on the same
+ * kernel: bands, vertex_cache, window_pixels and split change no bit there either (its workgroups always split the rows of the window
+ * only, so split is accepted and has no effect). */
+int roft_render_depth_mode(const roft_mesh* mesh, const double x[3], const double q[4], const roft_camera* cam, int divider, int mode,
+                           float* tile);
+int roft_outlier_test_mode(const roft_camera* cam, int divider, const float* depth, const uint8_t* mask, const roft_mesh* mesh,
+                           const double x[6], const double q[8], int bands, int vertex_cache, int window_pixels, int split, int mode,
+                           double L_out[2], long samples_out[2], int* selected_out, float* tiles_out);
 
 /* ---- (2) batched engine --------------------------------------------------------------------- */
 
@@ -238,6 +268,9 @@ typedef struct {
      * for longer: with 64 objects one band tracks 5 % more object-frames/s in long runs and 2.5 % fewer in a 20-frame burst,
      * DESIGN.md section 4).  The likelihood's sums are exact (integer), so the band count changes no result. */
     int outlier_bands_per_alternative;
+    /* How the outlier test renders (ROFT_RENDER_*; 0, the default, is the render contract): a semantics switch -- ROFT_RENDER_GL
+     * scores the alternatives on the reference's GL numerics, slower.  Other values are refused by roft_engine_create. */
+    int render_mode;
 } roft_config;
 
 typedef struct {

@@ -19,6 +19,8 @@ MEM_HOST, MEM_DEVICE = 0, 1
 RETAIN_FRAMES = 16        # default configuration (roft_engine_retain_frames otherwise)
 MAX_BATCH_FRAMES = 8
 MAX_FLOW_CHASE = 30
+RENDER_CONTRACT, RENDER_GL = 0, 1   # roft_config::render_mode
+ABI_VERSION = 2                     # ROFT_ABI_VERSION: the structs below mirror this version of the header
 
 
 class RoftError(RuntimeError):
@@ -56,7 +58,7 @@ class Config(C.Structure):
                 ("pose_frames_between", C.c_int), ("stamped_masks", C.c_int), ("max_objects", C.c_int), ("ukf_cholesky_guard", C.c_double),
                 ("ukf_cholesky_guard_bilinear", C.c_double),
                 ("device", C.c_int), ("max_batch_frames", C.c_int), ("mask_workgroups_per_object", C.c_int),
-                ("outlier_bands_per_alternative", C.c_int)]
+                ("outlier_bands_per_alternative", C.c_int), ("render_mode", C.c_int)]
 
 
 class ObjectDesc(C.Structure):
@@ -93,9 +95,10 @@ class ObjectOutput(C.Structure):
 
 # every symbol include/roft_engine.h declares
 ABI_SYMBOLS = [
-    "roft_last_error_string", "roft_device_count", "roft_flow_measurement", "roft_kf_predict",
+    "roft_last_error_string", "roft_device_count", "roft_abi_version", "roft_flow_measurement", "roft_kf_predict",
     "roft_skf_correct", "roft_skf_correct_points", "roft_mask_propagate", "roft_pose_process_noise", "roft_ukf_predict",
-    "roft_ukf_correct", "roft_mesh_classify", "roft_render_depth", "roft_depth_likelihood", "roft_outlier_test", "roft_outlier_test_split", "roft_default_config",
+    "roft_ukf_correct", "roft_mesh_classify", "roft_render_depth", "roft_render_depth_mode", "roft_depth_likelihood", "roft_outlier_test",
+    "roft_outlier_test_split", "roft_outlier_test_mode", "roft_default_config",
     "roft_default_object", "roft_engine_create", "roft_engine_destroy", "roft_object_add",
     "roft_frame_submit", "roft_frames_submit", "roft_engine_retain_frames", "roft_engine_get_stats", "roft_step", "roft_sync", "roft_get_state", "roft_get_outputs", "roft_get_mask",
     "roft_engine_enable_log", "roft_engine_get_log", "roft_engine_get_log_rows", "roft_engine_stream", "roft_engine_enable_timing",
@@ -129,6 +132,11 @@ def lib():
     if not os.path.exists(SO):
         build()
     L = C.CDLL(SO)
+    # the structs above mirror one version of the header: a library of another version (or one from before the version was
+    # exported) would read them with another layout
+    version = L.roft_abi_version() if hasattr(L, "roft_abi_version") else None
+    if version != ABI_VERSION:
+        raise RoftError("%s has ABI version %s, this binding mirrors version %d: rebuild the library" % (SO, version, ABI_VERSION))
     vp, ip, dp = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double)
     L.roft_last_error_string.restype = C.c_char_p
     L.roft_device_count.restype = C.c_int
@@ -145,6 +153,10 @@ def lib():
     L.roft_depth_likelihood.argtypes = [C.POINTER(Camera), vp, vp, vp, C.c_int, dp, C.POINTER(C.c_long)]
     L.roft_outlier_test.argtypes = [C.POINTER(Camera), C.c_int, vp, vp, C.POINTER(Mesh), vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, ip, vp]
     L.roft_outlier_test_split.argtypes = [C.POINTER(Camera), C.c_int, vp, vp, C.POINTER(Mesh), vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, ip, vp]
+    L.roft_render_depth_mode.argtypes = [C.POINTER(Mesh), vp, vp, C.POINTER(Camera), C.c_int, C.c_int, vp]
+    L.roft_outlier_test_mode.argtypes = [C.POINTER(Camera), C.c_int, vp, vp, C.POINTER(Mesh), vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         vp, vp, ip, vp]
+    L.roft_abi_version.argtypes = []
     L.roft_engine_get_batch_trace.argtypes = [vp, C.POINTER(BatchTrace), C.c_int, ip]
     L.roft_default_config.argtypes = [C.POINTER(Config), C.c_int, C.c_int, C.c_int]
     L.roft_default_object.argtypes = [C.POINTER(ObjectDesc)]

@@ -129,9 +129,12 @@ def apply_overrides(cfg, argv):
             try:
                 old = lookup(cfg, a[2:])
             except KeyError:
-                rest.append(a)
-                i += 1
-                continue
+                key = ".".join(re.split(r"::|\.", a[2:]))
+                if key not in OPTIONAL_KEYS:
+                    rest.append(a)
+                    i += 1
+                    continue
+                old = OPTIONAL_KEYS[key]   # (a setting the file may leave out: its default's type)
             raw = argv[i + 1]
             if isinstance(old, bool):
                 new = raw.strip().lower() == "true"
@@ -149,7 +152,7 @@ def apply_overrides(cfg, argv):
             parts = re.split(r"::|\.", a[2:])
             node = cfg
             for part in parts[:-1]:
-                node = node[part]
+                node = node.setdefault(part, {})
             node[parts[-1]] = new
             i += 2
         elif a == "--from":
@@ -180,6 +183,26 @@ FILTER_KEYS = [
     "segmentation_dataset.desired_fps", "segmentation_dataset.flow_aided",
     "unscented_transform.alpha", "unscented_transform.beta", "unscented_transform.kappa",
 ]
+
+# settings of this engine that the reference's files do not carry -> their defaults (the value when absent).  Not in FILTER_KEYS:
+# every reference file parses without them; command-line overrides may add them.
+#   outlier_rejection.render_mode: how the outlier test renders, "contract" (the render contract) or "gl" (the reference's GL
+#   numerics, roft_config::render_mode)
+OPTIONAL_KEYS = {"outlier_rejection.render_mode": "contract"}
+RENDER_MODES = {"contract": L.RENDER_CONTRACT, "gl": L.RENDER_GL}
+
+
+def render_mode(cfg):
+    """roft_config::render_mode of a parsed configuration: outlier_rejection.render_mode, "contract" when absent."""
+    try:
+        v = lookup(cfg, "outlier_rejection.render_mode")
+    except KeyError:
+        v = OPTIONAL_KEYS["outlier_rejection.render_mode"]
+    if not isinstance(v, str) or v not in RENDER_MODES:
+        raise ValueError("outlier_rejection.render_mode must be one of %s, not %r" % (", ".join('"%s"' % k for k in RENDER_MODES), v))
+    return RENDER_MODES[v]
+
+
 DATASET_KEYS = [
     "camera_dataset.path", "camera_dataset.data_prefix", "camera_dataset.rgb_prefix", "camera_dataset.depth_prefix",
     "camera_dataset.data_format", "camera_dataset.rgb_format", "camera_dataset.depth_format", "camera_dataset.heading_zeros",
@@ -225,6 +248,7 @@ def to_engine(cfg, flow_type, flow_grid=None, flow_scale=None, max_objects=1, ma
     c.use_pose_resync = int(bool(g("measurement_model.use_pose_resync")))
     c.use_velocity = int(bool(g("measurement_model.use_velocity")))
     c.outlier_rejection = int(bool(g("outlier_rejection.enable")))
+    c.render_mode = render_mode(cfg)
     # outlier_rejection.gain reaches ROFTFilter through a `const bool` parameter (ROFTFilter.h:64): any non-zero value
     # is 1 there, and the decision is a ratio test the gain cancels out of -- read, reported, not used
     c.flow_aided_segmentation = int(bool(g("segmentation_dataset.flow_aided")))
@@ -276,13 +300,16 @@ def load(path, argv=(), **kw):
     return c, o, extras, rest
 
 
-def default_text(width, height, fx, fy, cx, cy):
+def default_text(width, height, fx, fy, cx, cy, render_mode=L.RENDER_CONTRACT):
     """A configuration file in the reference's format holding the defaults of the ABI (roft_default_config /
-    roft_default_object: the filter settings of config/config_fast_ycb.cfg) for the given camera."""
+    roft_default_object: the filter settings of config/config_fast_ycb.cfg) for the given camera.  render_mode: written as
+    outlier_rejection.render_mode only when it is not the default (the file then stays one the reference reads)."""
     import ctypes as C
     c, o = L.Config(), L.ObjectDesc()
     L.check(L.lib().roft_default_config(C.byref(c), int(width), int(height), L.FLOW_F32C2))
     L.check(L.lib().roft_default_object(C.byref(o)))
+    c.render_mode = render_mode
+    mode_text = "".join(' render_mode = "%s";' % k for k, v in RENDER_MODES.items() if v == c.render_mode and v != L.RENDER_CONTRACT)
     arr = lambda a: "[" + ", ".join(repr(float(x)) for x in a) + "]"
     b = lambda v: "true" if v else "false"
     fps = lambda n: "fps_reduction = true; delay = true; original_fps = 30.0; desired_fps = %r;" % (30.0 / max(n, 1))
@@ -298,7 +325,7 @@ def default_text(width, height, fx, fy, cx, cy):
         "measurement_model: { pose: { cov_v = %s; cov_w = %s; cov_x = %s; cov_q = %s; }" % (arr(o.p_meas_cov_v), arr(o.p_meas_cov_w), arr(o.p_meas_cov_x), arr(o.p_meas_cov_q)),
         "  velocity: { cov_flow = %s; depth_maximum = %r; subsampling_radius = %r; weight_flow = %s; }" % (arr(o.v_meas_cov_flow), c.depth_maximum, c.subsampling_radius, b(c.flow_weighting)),
         "  use_pose = %s; use_pose_resync = %s; use_velocity = %s; }" % (b(c.use_pose), b(c.use_pose_resync), b(c.use_velocity)),
-        "outlier_rejection: { enable = %s; gain = 0.01; }" % b(c.outlier_rejection),
+        "outlier_rejection: { enable = %s; gain = 0.01;%s }" % (b(c.outlier_rejection), mode_text),
         "pose_dataset: { %s }" % fps(c.pose_frames_between),
         "segmentation_dataset: { %s flow_aided = %s; }" % (fps(c.mask_frames_between), b(c.flow_aided_segmentation)),
         "unscented_transform: { alpha = %r; beta = %r; kappa = %r; }" % (c.ut.alpha, c.ut.beta, c.ut.kappa), ""])
@@ -340,4 +367,4 @@ def all_keys(cfg, prefix=""):
 
 
 __all__ = ["parse_cfg", "apply_overrides", "lookup", "to_engine", "load", "frames_between", "default_text", "tracker_text", "dump_cfg", "FILTER_KEYS", "DATASET_KEYS",
-           "all_keys"]
+           "OPTIONAL_KEYS", "RENDER_MODES", "render_mode", "all_keys"]

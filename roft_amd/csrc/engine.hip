@@ -147,6 +147,8 @@ int roft_device_count(void)
     return n;
 }
 
+int roft_abi_version(void) { return ROFT_ABI_VERSION; }
+
 // ---- pinned host memory pool (roft_engine.h section 2b) ----
 namespace {
 struct HostPool {
@@ -546,6 +548,8 @@ int roft_engine_create(const roft_config* cfg, roft_engine** out)
         return fail(ROFT_ERR_INVALID, "mask_workgroups_per_object must be 0 (automatic) .. 8");
     if (cfg->outlier_bands_per_alternative < 0 || cfg->outlier_bands_per_alternative > kMaxOutlierParts)
         return fail(ROFT_ERR_INVALID, "outlier_bands_per_alternative must be 0 (automatic) .. 8");
+    if (cfg->render_mode != ROFT_RENDER_CONTRACT && cfg->render_mode != ROFT_RENDER_GL)
+        return fail(ROFT_ERR_INVALID, "render_mode must be ROFT_RENDER_CONTRACT (0) or ROFT_RENDER_GL (1)");
     if ((int)(size_t)cfg->subsampling_radius <= 0) return fail(ROFT_ERR_INVALID, "subsampling_radius must be >= 1");
     const int T = std::max(cfg->max_batch_frames, 1);
     // batches in flight: enough that the host never runs out of enqueued work while it waits for the oldest one -- a
@@ -640,9 +644,10 @@ int roft_object_add(roft_engine* e, const roft_object_desc* d, int* obj_id)
                 return bail(ROFT_ERR_INVALID, "mesh: triangle " + std::to_string(i / 3) + " refers to vertex " + std::to_string(d->mesh.tris[i]) +
                                                   " of " + std::to_string(d->mesh.n_verts));
         // closed orientable surface?  Then the outlier test's render leaves the triangles that face away out (the render
-        // contract, oracle/ro_render.c) and walks the triangles in an order that keeps alike-facing ones together
+        // contract, oracle/ro_render.c) and walks the triangles in an order that keeps alike-facing ones together.  The GL render
+        // mode draws every triangle and breaks depth ties on the caller's triangle order: the mesh goes up as it is.
         PreparedMesh pm;
-        prepare_mesh(d->mesh.verts, d->mesh.n_verts, d->mesh.tris, d->mesh.n_tris, pm);
+        if (e->cfg.render_mode == ROFT_RENDER_CONTRACT) prepare_mesh(d->mesh.verts, d->mesh.n_verts, d->mesh.tris, d->mesh.n_tris, pm);
         hipError_t err = o->verts.ensure((size_t)3 * d->mesh.n_verts);
         if (err == hipSuccess) err = o->tris.ensure((size_t)3 * d->mesh.n_tris);
         if (err == hipSuccess && pm.closed) err = o->tri_flip.ensure((size_t)d->mesh.n_tris);

@@ -395,8 +395,8 @@ static int op_outlier(const roft_camera* cam, int divider, const float* depth, c
     };
     for (size_t i = 0; i < (size_t)3 * mesh->n_tris; ++i)
         if (mesh->tris[i] < 0 || mesh->tris[i] >= mesh->n_verts) return fail(ROFT_ERR_INVALID, "mesh: a triangle refers to a vertex outside the vertex array");
-    PreparedMesh pm;
-    prepare_mesh(mesh->verts, mesh->n_verts, mesh->tris, mesh->n_tris, pm);
+    PreparedMesh pm;   // (GL render mode: the caller's triangles as they are, every one drawn -- roft_object_add does the same)
+    if (o_in.render_mode == ROFT_RENDER_CONTRACT) prepare_mesh(mesh->verts, mesh->n_verts, mesh->tris, mesh->n_tris, pm);
     if (int rc = to_dev(c.b0, mesh->verts, (size_t)3 * mesh->n_verts, c.stream)) return rc;
     if (int rc = to_dev(c.b1, pm.tris(mesh->tris), (size_t)3 * mesh->n_tris, c.stream)) return rc;
     if (pm.closed)
@@ -485,13 +485,21 @@ int roft_mesh_classify(const roft_mesh* mesh, uint8_t* flip_out, int* closed_out
 int roft_render_depth(const roft_mesh* mesh, const double x[3], const double q[4], const roft_camera* cam, int divider,
                       float* tile)
 {
+    return roft_render_depth_mode(mesh, x, q, cam, divider, ROFT_RENDER_CONTRACT, tile);
+}
+
+int roft_render_depth_mode(const roft_mesh* mesh, const double x[3], const double q[4], const roft_camera* cam, int divider, int mode,
+                           float* tile)
+{
     if (!mesh || !mesh->verts || !mesh->tris || mesh->n_verts <= 0 || mesh->n_tris <= 0 || !x || !q || !cam || !tile || divider <= 0)
         return fail(ROFT_ERR_INVALID, "bad argument");
+    if (mode != ROFT_RENDER_CONTRACT && mode != ROFT_RENDER_GL) return fail(ROFT_ERR_INVALID, "bad render mode");
     const size_t tpix = (size_t)(cam->width / divider) * (cam->height / divider);
     std::vector<float> tiles(2 * tpix);
     const double x2[6] = {x[0], x[1], x[2], x[0], x[1], x[2]};
     const double q2[8] = {q[0], q[1], q[2], q[3], q[0], q[1], q[2], q[3]};
     OutlierLaunchOpts o;
+    o.render_mode = mode;
     if (int rc = op_outlier(cam, divider, nullptr, nullptr, mesh, x2, q2, o, nullptr, nullptr, nullptr, tiles.data())) return rc;
     std::memcpy(tile, tiles.data(), sizeof(float) * tpix);
     return ROFT_OK;
@@ -511,14 +519,24 @@ int roft_outlier_test_split(const roft_camera* cam, int divider, const float* de
                             const double x[6], const double q[8], int bands, int vertex_cache, int window_pixels, int split, double L_out[2],
                             long samples_out[2], int* selected_out, float* tiles_out)
 {
+    return roft_outlier_test_mode(cam, divider, depth, mask, mesh, x, q, bands, vertex_cache, window_pixels, split, ROFT_RENDER_CONTRACT,
+                                  L_out, samples_out, selected_out, tiles_out);
+}
+
+int roft_outlier_test_mode(const roft_camera* cam, int divider, const float* depth, const uint8_t* mask, const roft_mesh* mesh,
+                           const double x[6], const double q[8], int bands, int vertex_cache, int window_pixels, int split, int mode,
+                           double L_out[2], long samples_out[2], int* selected_out, float* tiles_out)
+{
     if (!cam || !depth || !mask || !mesh || !mesh->verts || !mesh->tris || mesh->n_verts <= 0 || mesh->n_tris <= 0 || !x || !q ||
         divider <= 0 || bands < 0 || bands > kMaxOutlierParts || window_pixels < 0)
         return fail(ROFT_ERR_INVALID, "bad argument");
+    if (mode != ROFT_RENDER_CONTRACT && mode != ROFT_RENDER_GL) return fail(ROFT_ERR_INVALID, "bad render mode");
     OutlierLaunchOpts o;
     o.parts = bands;
     o.no_vertex_cache = vertex_cache ? 0 : 1;
     o.window_pixels = window_pixels;
     o.split = split < 0 ? -1 : (split ? 1 : 0);   // (this call only: nothing process-wide changes)
+    o.render_mode = mode;
     return op_outlier(cam, divider, depth, mask, mesh, x, q, o, L_out, samples_out, selected_out, tiles_out);
 }
 

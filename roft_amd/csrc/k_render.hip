@@ -228,6 +228,104 @@ __device__ __forceinline__ void raster_projected(float x0, float y0, float z0, f
     }
 }
 
+// ---- render mode ROFT_RENDER_GL: the numerics of the reference's OpenGL pipeline (RO_RENDER_GL of oracle/ro_render.c) -------
+// Every triangle is drawn (depth test LESS, no culling: SICAD.cpp:271-272), window z is interpolated linearly in screen space
+// (plane equation in double), quantised to the 24-bit depth buffer, the first fragment in the caller's triangle order wins a tie,
+// and the fragment shader linearises the winner's window z in float (shader_model.frag:33-51).  Coverage follows the top-left rule.
+constexpr float kGlNear = 0.001f, kGlFar = 1000.0f;
+constexpr uint32_t kGlDepthClear = 0xFFFFFFu;                                  // glClear: depth 1.0 in 24 bits
+constexpr uint64_t kGlKeyClear = ((uint64_t)kGlDepthClear << 32) | 0xFFFFFFFFu;  // (qz << 32 | triangle): nothing drawn
+
+// u = (fx X) / Z + cx: a division per vertex (the contract multiplies by one reciprocal)
+__device__ __forceinline__ void project_vertex_gl(const float* v, const RenderPose& P, float fx, float fy, float cx,
+                                                  float cy, float& sx, float& sy, float& z)
+{
+    const float X = ((P.R[0] * v[0] + P.R[1] * v[1]) + P.R[2] * v[2]) + P.t[0];
+    const float Y = ((P.R[3] * v[0] + P.R[4] * v[1]) + P.R[5] * v[2]) + P.t[1];
+    z = ((P.R[6] * v[0] + P.R[7] * v[1]) + P.R[8] * v[2]) + P.t[2];
+    if (z > 0.001f) {
+        sx = (fx * X) / z + cx;
+        sy = (fy * Y) / z + cy;
+    } else {
+        sx = sy = 0.0f;
+    }
+}
+
+// window z of a vertex at eye depth Z > near: the third row of the projection (SICAD.cpp:1634-1637), the perspective divide and the
+// depth range [0, 1]
+__device__ __forceinline__ float gl_vertex_window_z(float Z)
+{
+    const float gl_a = (kGlFar + kGlNear) / (kGlFar - kGlNear), gl_b = (2.0f * (kGlFar * kGlNear)) / (kGlFar - kGlNear);
+    const float z_ndc = (gl_a * Z - gl_b) / Z;
+    return 0.5f * z_ndc + 0.5f;
+}
+
+// window z of the pixel centre (px, py) inside the triangle: its plane equation in double, handed on as a float gl_FragCoord.z
+__device__ __forceinline__ float gl_pixel_window_z(float x0, float y0, float x1, float y1, float x2, float y2, float zw0, float zw1,
+                                                   float zw2, float px, float py)
+{
+    const double dw0 = ((double)x2 - x1) * ((double)py - y1) - ((double)y2 - y1) * ((double)px - x1);
+    const double dw1 = ((double)x0 - x2) * ((double)py - y2) - ((double)y0 - y2) * ((double)px - x2);
+    const double dw2 = ((double)x1 - x0) * ((double)py - y0) - ((double)y1 - y0) * ((double)px - x0);
+    return (float)((dw0 * zw0 + dw1 * zw1 + dw2 * zw2) / (dw0 + dw1 + dw2));
+}
+
+// the fragment shader's output: eye-space depth of window z
+__device__ __forceinline__ float gl_linear_depth(float z_w)
+{
+    const float zn = z_w * 2.0f - 1.0f;
+    return (2.0f * kGlNear * kGlFar) / (kGlFar + kGlNear - zn * (kGlFar - kGlNear));
+}
+
+// raster_projected under the GL numerics: `store(i, j, qz)` receives every fragment that survives the depth range and can pass
+// GL_LESS against a cleared buffer, with its quantised window z.  The vertices are projected by project_vertex_gl.
+template <class Store>
+__device__ __forceinline__ void raster_projected_gl(float x0, float y0, float z0, float x1, float y1, float z1, float x2, float y2,
+                                                    float z2, int w, int h, int j_lo, int j_hi, Store store)
+{
+    if (!(z0 > 0.001f && z1 > 0.001f && z2 > 0.001f)) return;
+    const float area = (x1 - x0) * (y2 - y0) - (x2 - x0) * (y1 - y0);
+    if (area == 0.0f || !(area == area)) return;
+    const float minx = fminf(x0, fminf(x1, x2)), maxx = fmaxf(x0, fmaxf(x1, x2));
+    const float miny = fminf(y0, fminf(y1, y2)), maxy = fmaxf(y0, fmaxf(y1, y2));
+    float fi0 = ceilf(minx - 0.5f), fi1 = floorf(maxx - 0.5f);
+    float fj0 = ceilf(miny - 0.5f), fj1 = floorf(maxy - 0.5f);
+    if (fi0 < 0.0f) fi0 = 0.0f;
+    if (fj0 < 0.0f) fj0 = 0.0f;
+    if (fi1 > (float)(w - 1)) fi1 = (float)(w - 1);
+    if (fj1 > (float)(h - 1)) fj1 = (float)(h - 1);
+    if (!(fi0 <= fi1) || !(fj0 <= fj1)) return;
+    const int ia = (int)fi0, ib = (int)fi1, ja = max((int)fj0, j_lo), jb = min((int)fj1, j_hi);
+    if (jb < ja) return;
+    // top-left rule: with the weights oriented so that the interior is w > 0, edge k is w_k = a_k px + b_k py + c_k; a centre ON
+    // the edge is covered iff a_k > 0 (left edge) or a_k == 0 and b_k > 0 (top edge, image rows grow downwards)
+    const float sgn = (area > 0.0f) ? 1.0f : -1.0f;
+    const float ea0 = -sgn * (y2 - y1), ea1 = -sgn * (y0 - y2), ea2 = -sgn * (y1 - y0);
+    const float eb0 = sgn * (x2 - x1), eb1 = sgn * (x0 - x2), eb2 = sgn * (x1 - x0);
+    const bool own0 = (ea0 > 0.0f) || (ea0 == 0.0f && eb0 > 0.0f);
+    const bool own1 = (ea1 > 0.0f) || (ea1 == 0.0f && eb1 > 0.0f);
+    const bool own2 = (ea2 > 0.0f) || (ea2 == 0.0f && eb2 > 0.0f);
+    const float zw0 = gl_vertex_window_z(z0), zw1 = gl_vertex_window_z(z1), zw2 = gl_vertex_window_z(z2);
+    for (int j = ja; j <= jb; ++j) {
+        const float py = (float)j + 0.5f;
+        for (int i = ia; i <= ib; ++i) {
+            const float px = (float)i + 0.5f;
+            const float w0 = (x2 - x1) * (py - y1) - (y2 - y1) * (px - x1);
+            const float w1 = (x0 - x2) * (py - y2) - (y0 - y2) * (px - x2);
+            const float w2 = (x1 - x0) * (py - y0) - (y1 - y0) * (px - x0);
+            const bool inside = (area > 0.0f) ? (w0 >= 0.0f && w1 >= 0.0f && w2 >= 0.0f)
+                                              : (w0 <= 0.0f && w1 <= 0.0f && w2 <= 0.0f);
+            if (!inside) continue;
+            if ((w0 == 0.0f && !own0) || (w1 == 0.0f && !own1) || (w2 == 0.0f && !own2)) continue;
+            const float z_w = gl_pixel_window_z(x0, y0, x1, y1, x2, y2, zw0, zw1, zw2, px, py);
+            if (!(z_w >= 0.0f && z_w <= 1.0f)) continue;   // clipped by the depth range
+            const uint32_t qz = (uint32_t)floor((double)z_w * 16777215.0 + 0.5);
+            if (qz >= kGlDepthClear) continue;             // never less than the cleared buffer
+            store(i, j, qz);
+        }
+    }
+}
+
 // Operator level (roft_depth_likelihood): likelihood of both alternatives over the buffered features from z-buffers in
 // HBM (EngineArrays::zbuf), decision, and the selected belief becomes the corrected belief (ROFTFilter.cpp:581-583,
 // 670-675).  One workgroup per object.  The engine's own test is outlier_fused_kernel below.
@@ -338,6 +436,10 @@ __global__ __launch_bounds__(kOutlierThreads) void outlier_kernel(EngineArrays a
 // workgroup, which in the row split is the middle band of the largest object (49 - 56 us of triangles at 8 and 16 objects against
 // 25 - 30 with the triangles dealt out: 60 - 66 -> 45 - 46 us per launch).
 // grid: (2 alternatives x parts, n_obj).  dynamic LDS: [3 * vcache_cap floats] | [win_cap z values]
+// GL = true: render mode ROFT_RENDER_GL (raster_projected_gl).  The window is then a visibility buffer: a pixel holds the 64-bit key
+// (quantised window z << 32 | triangle index in the caller's order) resolved with LDS atomicMin -- the nearest fragment, the first
+// drawn among equal depths, whatever order the threads draw in --, and the depth of the winning triangle is evaluated again where it
+// is read (dump, samples).  The workgroups of an alternative split only the rows of its window (launch_outlier passes split_tris 0).
 constexpr int kFusedThreads = 1024;
 // phase stamps (-DROFT_FUSED_PROFILE; PHASES=fused tools/k1_phase_profile.py): 100 MHz ticks -> ObjState::dbg[alt * 8 + phase]
 #ifdef ROFT_FUSED_PROFILE
@@ -346,6 +448,7 @@ constexpr int kFusedThreads = 1024;
 #define UTICK(i) do {} while (0)
 #endif
 
+template <bool GL>
 __global__ __launch_bounds__(kFusedThreads) void outlier_fused_kernel(EngineArrays a, int lin, int vcache_cap, int win_cap, int parts,
                                                                      int split_tris, float* tile_dump)
 {
@@ -376,6 +479,7 @@ __global__ __launch_bounds__(kFusedThreads) void outlier_fused_kernel(EngineArra
     const bool cached = nv <= vcache_cap;
     float* s_v = reinterpret_cast<float*>(smem);
     uint32_t* s_z = reinterpret_cast<uint32_t*>(smem + (((size_t)vcache_cap * 12 + 15) & ~(size_t)15));
+    uint64_t* s_k = reinterpret_cast<uint64_t*>(s_z);   // (GL: the visibility buffer, win_cap keys)
     if (tid < 4) s_box[tid] = (tid < 2) ? INT32_MAX : -1;
     if (tid == 0) s_behind = 0;
 #ifdef ROFT_FUSED_PROFILE
@@ -402,7 +506,8 @@ __global__ __launch_bounds__(kFusedThreads) void outlier_fused_kernel(EngineArra
             const int v = vb + k * kFusedThreads;
             if (v >= nv) break;
             float sx, sy, z;
-            project_vertex(vc[k], P, fx, fy, cx, cy, sx, sy, z);
+            if constexpr (GL) project_vertex_gl(vc[k], P, fx, fy, cx, cy, sx, sy, z);
+            else project_vertex(vc[k], P, fx, fy, cx, cy, sx, sy, z);
             if (cached) { s_v[3 * v] = sx; s_v[3 * v + 1] = sy; s_v[3 * v + 2] = z; }
             if (z > 0.001f) {
                 // (a vertex far outside the target clamps to an empty or full range; float -> int saturates)
@@ -438,7 +543,7 @@ __global__ __launch_bounds__(kFusedThreads) void outlier_fused_kernel(EngineArra
     // projection).  Every workgroup of the alternative sees the same box and decides alike.
     int j0 = min(s_box[1], th - 1), j1 = s_box[3];
     int R = parts;
-    if (split_tris && parts > 1 && i1 >= i0 && j1 >= j0 && i0 >= 0 && j0 >= 0) {
+    if (!GL && split_tris && parts > 1 && i1 >= i0 && j1 >= j0 && i0 >= 0 && j0 >= 0) {
         const long long w_all = i1 - i0 + 1, rows_all = j1 - j0 + 1;
         for (R = 1; R < parts; ++R)
             if (parts % R == 0 && ((rows_all + R - 1) / R) * w_all <= (long long)win_cap) break;
@@ -457,20 +562,46 @@ __global__ __launch_bounds__(kFusedThreads) void outlier_fused_kernel(EngineArra
     const int n = st.n_feat[fslot];
     LikelihoodSum err;
     int cnt = 0;
+    // (GL) eye-space depth at pixel (i, j) of the triangle whose key won it: raster_projected_gl's arithmetic again, so the
+    // window z it drew with
+    auto gl_resolve = [&](uint64_t key, int i, int j) -> float {
+        const int32_t* tri = prm.tris + (size_t)3 * (uint32_t)key;
+        const int v0 = tri[0], v1 = tri[1], v2 = tri[2];
+        float x0, y0, z0, x1, y1, z1, x2, y2, z2;
+        if (cached) {
+            x0 = s_v[3 * v0]; y0 = s_v[3 * v0 + 1]; z0 = s_v[3 * v0 + 2];
+            x1 = s_v[3 * v1]; y1 = s_v[3 * v1 + 1]; z1 = s_v[3 * v1 + 2];
+            x2 = s_v[3 * v2]; y2 = s_v[3 * v2 + 1]; z2 = s_v[3 * v2 + 2];
+        } else {
+            project_vertex_gl(prm.verts + (size_t)3 * v0, P, fx, fy, cx, cy, x0, y0, z0);
+            project_vertex_gl(prm.verts + (size_t)3 * v1, P, fx, fy, cx, cy, x1, y1, z1);
+            project_vertex_gl(prm.verts + (size_t)3 * v2, P, fx, fy, cx, cy, x2, y2, z2);
+        }
+        return gl_linear_depth(gl_pixel_window_z(x0, y0, x1, y1, x2, y2, gl_vertex_window_z(z0), gl_vertex_window_z(z1),
+                                                 gl_vertex_window_z(z2), (float)i + 0.5f, (float)j + 0.5f));
+    };
     if (win_w > 0 && j1 >= j0 && i0 >= 0 && j0 >= 0) {
         const int rows = max(1, win_cap / win_w);   // (win_cap >= the target's width: a strip holds at least one row)
         for (int js = j0; js <= j1; js += rows) {
             const int je = min(j1, js + rows - 1), npx = win_w * (je - js + 1);
-            for (int i = tid; i < npx; i += kFusedThreads) s_z[i] = 0x7F800000u;
+            if constexpr (GL) {
+                for (int i = tid; i < npx; i += kFusedThreads) s_k[i] = kGlKeyClear;
+            } else {
+                for (int i = tid; i < npx; i += kFusedThreads) s_z[i] = 0x7F800000u;
+            }
             __syncthreads();
             UTICK(1);
             ROFT_LDS uint32_t* const zw = pin_lds(s_z);
             auto store = [zw, i0, js, win_w](int i, int j, float z) {
                 (void)__hip_atomic_fetch_min(zw + ((j - js) * win_w + (i - i0)), __float_as_uint(z), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             };
+            ROFT_LDS uint64_t* const zk = (ROFT_LDS uint64_t*)zw;
+            auto store_key = [zk, i0, js, win_w](int i, int j, uint64_t key) {
+                (void)__hip_atomic_fetch_min(zk + ((j - js) * win_w + (i - i0)), key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            };
             constexpr int kTB = 8;   // triangles per thread whose vertex indices are fetched together
             // closed mesh, everything in front of the near plane: triangles that face away are left out (the render contract)
-            const uint8_t* const flips = (prm.tri_flip && !s_behind && nv < (1 << 30)) ? prm.tri_flip : nullptr;   // (the cull code rides in an index's top bits)
+            const uint8_t* const flips = (!GL && prm.tri_flip && !s_behind && nv < (1 << 30)) ? prm.tri_flip : nullptr;   // (the cull code rides in an index's top bits)
             // (split: the triangles are dealt out to the workgroups of the alternative in runs of 64 -- one run per wave and
             //  fetch, so the index loads stay coalesced and neighbouring runs, which cost alike, go to different workgroups)
             const int stride = G, first = grp;
@@ -495,17 +626,28 @@ __global__ __launch_bounds__(kFusedThreads) void outlier_fused_kernel(EngineArra
                     x0 = s_v[3 * v0]; y0 = s_v[3 * v0 + 1]; z0 = s_v[3 * v0 + 2];
                     x1 = s_v[3 * v1]; y1 = s_v[3 * v1 + 1]; z1 = s_v[3 * v1 + 2];
                     x2 = s_v[3 * v2]; y2 = s_v[3 * v2 + 1]; z2 = s_v[3 * v2 + 2];
+                } else if constexpr (GL) {
+                    project_vertex_gl(prm.verts + (size_t)3 * v0, P, fx, fy, cx, cy, x0, y0, z0);
+                    project_vertex_gl(prm.verts + (size_t)3 * v1, P, fx, fy, cx, cy, x1, y1, z1);
+                    project_vertex_gl(prm.verts + (size_t)3 * v2, P, fx, fy, cx, cy, x2, y2, z2);
                 } else {
                     project_vertex(prm.verts + (size_t)3 * v0, P, fx, fy, cx, cy, x0, y0, z0);
                     project_vertex(prm.verts + (size_t)3 * v1, P, fx, fy, cx, cy, x1, y1, z1);
                     project_vertex(prm.verts + (size_t)3 * v2, P, fx, fy, cx, cy, x2, y2, z2);
                 }
-                raster_projected(x0, y0, z0, x1, y1, z1, x2, y2, z2, tw, th, js, je, cull_k, store);
+                if constexpr (GL) {
+                    // the key's low word: the triangle's index in the caller's order (tris are uploaded unsorted in this mode)
+                    const uint64_t t = (uint32_t)tri_of(tb + k * kFusedThreads);
+                    raster_projected_gl(x0, y0, z0, x1, y1, z1, x2, y2, z2, tw, th, js, je,
+                                        [&](int i, int j, uint32_t qz) { store_key(i, j, ((uint64_t)qz << 32) | t); });
+                } else {
+                    raster_projected(x0, y0, z0, x1, y1, z1, x2, y2, z2, tw, th, js, je, cull_k, store);
+                }
               }
             }
             __syncthreads();
             UTICK(2);
-            if (split) {
+            if constexpr (!GL) if (split) {
                 // This workgroup's window -> its slab in memory, written through (agent-coherent stores: the workgroups of an
                 // alternative may sit on different XCDs, each behind an L2 of its own); the workgroup that arrives last reads all
                 // slabs back with agent-coherent loads, keeps the nearest depth of every pixel and goes on alone: dump, samples,
@@ -584,9 +726,17 @@ __global__ __launch_bounds__(kFusedThreads) void outlier_fused_kernel(EngineArra
             // the caller's (zero-filled) render tile of the alternative, 0 = background as the reference reads it back
             if (tile_dump) {
                 float* tile = tile_dump + (size_t)alt * tw * th;
-                for (int i = tid; i < npx; i += kFusedThreads) {
-                    const uint32_t b = s_z[i];
-                    tile[(size_t)(js + i / win_w) * tw + (i0 + i % win_w)] = (b == 0x7F800000u) ? 0.0f : __uint_as_float(b);
+                if constexpr (GL) {
+                    for (int i = tid; i < npx; i += kFusedThreads) {
+                        const uint64_t key = s_k[i];
+                        const int pi = i0 + i % win_w, pj = js + i / win_w;
+                        tile[(size_t)pj * tw + pi] = ((uint32_t)(key >> 32) == kGlDepthClear) ? 0.0f : gl_resolve(key, pi, pj);
+                    }
+                } else {
+                    for (int i = tid; i < npx; i += kFusedThreads) {
+                        const uint32_t b = s_z[i];
+                        tile[(size_t)(js + i / win_w) * tw + (i0 + i % win_w)] = (b == 0x7F800000u) ? 0.0f : __uint_as_float(b);
+                    }
                 }
             }
             // likelihood samples of this strip (feature slots in ascending order per thread, as outlier_kernel adds them)
@@ -606,8 +756,13 @@ __global__ __launch_bounds__(kFusedThreads) void outlier_fused_kernel(EngineArra
                     const int v = (int)(pix[k] >> 16), u = (int)(pix[k] & 0xFFFFu);
                     const int tj = v / d, ti = u / d;
                     if (tj < js || tj > je || ti < i0 || ti > i1) continue;
-                    const uint32_t b = s_z[(tj - js) * win_w + (ti - i0)];
-                    if (b != 0x7F800000u) { err.add(fabsf(dep[k] - __uint_as_float(b))); cnt += 1; }
+                    if constexpr (GL) {
+                        const uint64_t key = s_k[(tj - js) * win_w + (ti - i0)];
+                        if ((uint32_t)(key >> 32) != kGlDepthClear) { err.add(fabsf(dep[k] - gl_resolve(key, ti, tj))); cnt += 1; }
+                    } else {
+                        const uint32_t b = s_z[(tj - js) * win_w + (ti - i0)];
+                        if (b != 0x7F800000u) { err.add(fabsf(dep[k] - __uint_as_float(b))); cnt += 1; }
+                    }
                 }
             }
             __syncthreads();   // the next strip clears the window
@@ -647,13 +802,17 @@ void launch_outlier(const EngineArrays& a, int lin, hipStream_t s, hipEvent_t st
     // pose chain segment that follows (ukf_chain_kernel)
     const size_t lds_total = 160 * 1024 - 4096;
     const size_t vbytes = ((size_t)a.max_verts * 12 + 15) & ~(size_t)15;
+    // render mode: the GL numerics keep an 8-byte key per window pixel (outlier_fused_kernel<true>), the contract a 4-byte depth
+    const bool gl = opts && opts->render_mode == ROFT_RENDER_GL;
+    const size_t zb = gl ? 8 : 4;
     // cache the projected vertices when they leave room for a window of 8 k pixels (a window that large or larger is
     // rendered in strips) and for the widest row of the target
-    const size_t min_win = (size_t)4 * std::max(8192, a.tile_w);
+    const size_t min_win = zb * std::max(8192, a.tile_w);
     const bool cache = vbytes + min_win <= lds_total && !(opts && opts->no_vertex_cache);
     const int vcache_cap = cache ? a.max_verts : 0;
-    int win_cap = (int)((lds_total - (cache ? vbytes : 0)) / 4);
-    (void)set_max_dynamic_lds(reinterpret_cast<const void*>(outlier_fused_kernel), (int)lds_total);
+    int win_cap = (int)((lds_total - (cache ? vbytes : 0)) / zb);
+    (void)set_max_dynamic_lds(gl ? reinterpret_cast<const void*>(outlier_fused_kernel<true>) : reinterpret_cast<const void*>(outlier_fused_kernel<false>),
+                              (int)lds_total);
     // bands per alternative: as many workgroups as the chip has CUs to spare
     int parts = std::max(1, std::min(kMaxOutlierParts, device_cu_count() / (2 * std::max(a.n_obj, 1))));
     if (a.outlier_parts > 0) parts = std::min(a.outlier_parts, kMaxOutlierParts);
@@ -665,15 +824,20 @@ void launch_outlier(const EngineArrays& a, int lin, hipStream_t s, hipEvent_t st
     const int forced = g_outlier_split.load(std::memory_order_relaxed) >= 0 ? g_outlier_split.load(std::memory_order_relaxed) : split_env;
     int split = (opts && opts->split >= 0) ? opts->split : (forced >= 0 ? forced : 1);
     if (parts <= 1 || !a.zmerge || (size_t)a.n_obj * parts > a.zmerge_slabs) split = 0;
+    if (gl) split = 0;   // (GL: the workgroups of an alternative split only the rows of its window; its slabs would be 64-bit)
     // (a band is a fraction of the window: request only the LDS it can need, so that other chains' workgroups fit next to it)
     const int lds_parts = split ? 1 : parts;
-    const size_t win_need = (size_t)4 * std::max((size_t)a.tile_w, ((size_t)a.tile_w * a.tile_h + lds_parts - 1) / lds_parts + (size_t)a.tile_w);
+    const size_t win_need = zb * std::max((size_t)a.tile_w, ((size_t)a.tile_w * a.tile_h + lds_parts - 1) / lds_parts + (size_t)a.tile_w);
     const size_t lds = std::min(lds_total, (((cache ? vbytes : 0) + win_need + 15) & ~(size_t)15));
-    win_cap = std::min(win_cap, (int)((lds - (cache ? vbytes : 0)) / 4));
+    win_cap = std::min(win_cap, (int)((lds - (cache ? vbytes : 0)) / zb));
     // (operator level: a smaller window forces the strip path)
     if (opts && opts->window_pixels > 0) win_cap = std::max(a.tile_w, std::min(win_cap, opts->window_pixels));
-    hipExtLaunchKernelGGL(outlier_fused_kernel, dim3(2 * parts * ((a.n_obj + 7) / 8) * 8), dim3(kFusedThreads), (uint32_t)lds, s, nullptr, stop, 0, a, lin,
-                          vcache_cap, win_cap, parts, split, opts ? opts->tile_dump : nullptr);
+    if (gl)
+        hipExtLaunchKernelGGL(outlier_fused_kernel<true>, dim3(2 * parts * ((a.n_obj + 7) / 8) * 8), dim3(kFusedThreads), (uint32_t)lds, s, nullptr, stop, 0, a,
+                              lin, vcache_cap, win_cap, parts, split, opts ? opts->tile_dump : nullptr);
+    else
+        hipExtLaunchKernelGGL(outlier_fused_kernel<false>, dim3(2 * parts * ((a.n_obj + 7) / 8) * 8), dim3(kFusedThreads), (uint32_t)lds, s, nullptr, stop, 0, a,
+                              lin, vcache_cap, win_cap, parts, split, opts ? opts->tile_dump : nullptr);
 }
 
 void launch_outlier_only(const EngineArrays& a, hipStream_t s)

@@ -415,6 +415,7 @@ struct OutlierLaunchOpts {
     int window_pixels = 0;    // cap of the LDS depth window in pixels (> 0: forces the strip path for larger windows)
     float* tile_dump = nullptr;   // [2][tile_h][tile_w], zero-filled: receives the rendered window of both alternatives
     int split = -1;           // several workgroups per alternative share its TRIANGLES (1) or only its window's rows (0); -1: the default (triangles)
+    int render_mode = ROFT_RENDER_CONTRACT;   // ROFT_RENDER_GL: the reference's GL numerics, every triangle drawn in `tris` order (rows split only)
 };
 // render + likelihood of the pending tests of a lane (the decision is the first thing the next pose chain segment does)
 void launch_outlier(const EngineArrays& a, int lin, hipStream_t s, hipEvent_t stop = nullptr, const OutlierLaunchOpts* opts = nullptr);

@@ -12,12 +12,14 @@ import numpy as np
 from . import _lib as L
 
 
-def default_config(width, height, flow_type=L.FLOW_F32C2, max_objects=64, device=0, max_batch_frames=1):
+def default_config(width, height, flow_type=L.FLOW_F32C2, max_objects=64, device=0, max_batch_frames=1, render_mode=L.RENDER_CONTRACT):
+    """render_mode: how the outlier test renders, L.RENDER_CONTRACT (default) or L.RENDER_GL (the reference's GL numerics)."""
     cfg = L.Config()
     L.check(L.lib().roft_default_config(C.byref(cfg), width, height, flow_type))
     cfg.max_objects = max_objects
     cfg.device = device
     cfg.max_batch_frames = max_batch_frames
+    cfg.render_mode = render_mode
     return cfg
 
 

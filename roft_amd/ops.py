@@ -138,10 +138,14 @@ def mesh_classify(verts, tris):
     return bool(closed.value), flip[:m.n_tris]
 
 
-def render_depth(mesh, x, q, cam, divider):
+def render_depth(mesh, x, q, cam, divider, mode=L.RENDER_CONTRACT):
+    """mode: L.RENDER_CONTRACT (roft_render_depth) or L.RENDER_GL (the reference's GL numerics, roft_render_depth_mode)."""
     x, q = _f64(x), _f64(q)
     tile = np.zeros((cam.height // divider, cam.width // divider), np.float32)
-    L.check(L.lib().roft_render_depth(C.byref(mesh), _p(x), _p(q), C.byref(cam), divider, _p(tile)))
+    if mode == L.RENDER_CONTRACT:
+        L.check(L.lib().roft_render_depth(C.byref(mesh), _p(x), _p(q), C.byref(cam), divider, _p(tile)))
+    else:
+        L.check(L.lib().roft_render_depth_mode(C.byref(mesh), _p(x), _p(q), C.byref(cam), divider, mode, _p(tile)))
     return tile
 
 
@@ -156,10 +160,12 @@ def depth_likelihood(cam, depth, mask, tile, divider):
     return Lv.value, ns.value
 
 
-def outlier_test(cam, divider, depth, mask, mesh, x2, q2, bands=0, vertex_cache=True, window_pixels=0, tiles=True, split=None):
+def outlier_test(cam, divider, depth, mask, mesh, x2, q2, bands=0, vertex_cache=True, window_pixels=0, tiles=True, split=None,
+                 mode=L.RENDER_CONTRACT):
     """ROFTFilter::pick_best_alternative (ROFTFilter.cpp:467-621) on the engine's own kernels (features_kernel,
     outlier_fused_kernel, the deciding pose chain segment).  x2 (2, 3), q2 (2, 4): the two alternatives.
     split: the workgroups of an alternative share its triangles (True) / the rows of its window (False); None: the library's choice.
+    mode: L.RENDER_CONTRACT or L.RENDER_GL (the reference's GL numerics, roft_outlier_test_mode).
     Returns (L[2], samples[2], selected, tiles (2, H/d, W/d) or None)."""
     depth = np.ascontiguousarray(depth, np.float32)
     mask = np.ascontiguousarray(mask, np.uint8)
@@ -169,9 +175,14 @@ def outlier_test(cam, divider, depth, mask, mesh, x2, q2, bands=0, vertex_cache=
     sel = C.c_int(-2)
     t = np.zeros((2, cam.height // divider, cam.width // divider), np.float32) if tiles else None
     # (split travels with the call -- roft_outlier_test_split -- not through a process-wide switch)
-    L.check(L.lib().roft_outlier_test_split(C.byref(cam), divider, _p(depth), _p(mask), C.byref(mesh), _p(x2), _p(q2), bands,
-                                            1 if vertex_cache else 0, window_pixels, -1 if split is None else (1 if split else 0),
-                                            _p(Lv), _p(ns), C.byref(sel), _p(t) if tiles else None))
+    sp = -1 if split is None else (1 if split else 0)
+    if mode == L.RENDER_CONTRACT:
+        L.check(L.lib().roft_outlier_test_split(C.byref(cam), divider, _p(depth), _p(mask), C.byref(mesh), _p(x2), _p(q2), bands,
+                                                1 if vertex_cache else 0, window_pixels, sp, _p(Lv), _p(ns), C.byref(sel), _p(t) if tiles else None))
+    else:
+        L.check(L.lib().roft_outlier_test_mode(C.byref(cam), divider, _p(depth), _p(mask), C.byref(mesh), _p(x2), _p(q2), bands,
+                                               1 if vertex_cache else 0, window_pixels, sp, mode, _p(Lv), _p(ns), C.byref(sel),
+                                               _p(t) if tiles else None))
     return Lv, ns, sel.value, t
 
 
