@@ -125,13 +125,20 @@ __device__ __forceinline__ void quat_diff(const double a[4], const double b[4], 
 // ---- LDS layout -----------------------------------------------------------------------------------
 constexpr int kCols = 50;  // >= 2 * 24 + 1
 
+// Index tables of the algorithm (constants: built at compile time, see g_ukf_tab, and copied into LDS once per launch)
+struct UkfTab {
+    unsigned jtab[11 * 36 * 2];            // Jacobi 12x12: per round and 2x2 block, the four entry offsets (16 bit each, two words)
+    unsigned short tri12[78], tri6[26];    // upper triangles in row-major order: (i << 8 | j), i <= j (tri6: 21 used, padded)
+};
+static_assert(sizeof(UkfTab) % 16 == 0, "copied in 16-byte words");
+constexpr int kUkfTabWords = sizeof(UkfTab) / 16;
+
 struct UkfLds {
+    alignas(16) UkfTab tab;
     double P[144];       // matrix being decomposed (destroyed)
     double V[144];       // its eigenvectors (columns)
     double wP[12];       // its eigenvalues
     double S[144];       // matrix square root the sigma points are drawn from (see decompose_state_cov)
-    uint2 jtab[11 * 36]; // Jacobi 12x12: per round and 2x2 block, the four entry offsets (16 bit each)
-    unsigned short tri12[78], tri6[21];   // upper triangles in row-major order: (i << 8 | j), i <= j
     double cs[2][6][2];  // rotations (c, s) of the current round, double-buffered by round parity
     double Q[100];       // process noise block padded to 10 x 10
     double VQ[100];
@@ -209,7 +216,7 @@ __device__ __forceinline__ void schur_rotation(double app, double aqq, double ap
 constexpr double kJacobiTol = ROFT_JACOBI_TOL;
 
 // pair i (0 <= i < n/2) of round `round` of the round-robin ordering, p < q
-__device__ __forceinline__ void jacobi_pair(int n, int round, int i, int& p, int& q)
+__host__ __device__ __forceinline__ constexpr void jacobi_pair(int n, int round, int i, int& p, int& q)
 {
     if (i == 0) { p = n - 1; q = round; }
     else {
@@ -276,24 +283,28 @@ __device__ __noinline__ void jacobi_wave(double* A, double* V, int n, UkfLds& L)
     wave_sync();
 }
 
-// Entry offsets of the 36 blocks of the 11 rounds of a 12x12 sweep, built once per launch.
-__device__ void jacobi12_table(UkfLds& L)
+// Entry offsets of the 36 blocks of the 11 rounds of a 12x12 sweep and the two triangle enumerations: evaluated by the
+// compiler (they were recomputed by every launch, with integer divisions and a search loop per entry).
+constexpr UkfTab make_ukf_tab()
 {
-    for (int i = threadIdx.x; i < 11 * 36; i += kUkfThreads) {
+    UkfTab t{};
+    for (int i = 0; i < 11 * 36; ++i) {
         const int round = i / 36, l = i % 36;
-        int pa, qa, pb, qb;
+        int pa = 0, qa = 0, pb = 0, qb = 0;
         jacobi_pair(12, round, l / 6, pa, qa);
         jacobi_pair(12, round, l % 6, pb, qb);
-        L.jtab[i] = make_uint2((uint32_t)(pa * 12 + pb) | ((uint32_t)(pa * 12 + qb) << 16),
-                               (uint32_t)(qa * 12 + pb) | ((uint32_t)(qa * 12 + qb) << 16));
+        t.jtab[2 * i] = (unsigned)(pa * 12 + pb) | ((unsigned)(pa * 12 + qb) << 16);
+        t.jtab[2 * i + 1] = (unsigned)(qa * 12 + pb) | ((unsigned)(qa * 12 + qb) << 16);
     }
-    for (int e = threadIdx.x; e < 78 + 21; e += kUkfThreads) {
-        const int m = e < 78 ? 12 : 6;
-        int u = e < 78 ? e : e - 78, i = 0;
-        while (u >= m - i) { u -= m - i; ++i; }
-        (e < 78 ? L.tri12[e] : L.tri6[e - 78]) = (unsigned short)((i << 8) | (i + u));
-    }
+    int e = 0;
+    for (int i = 0; i < 12; ++i)
+        for (int j = i; j < 12; ++j) t.tri12[e++] = (unsigned short)((i << 8) | j);
+    e = 0;
+    for (int i = 0; i < 6; ++i)
+        for (int j = i; j < 6; ++j) t.tri6[e++] = (unsigned short)((i << 8) | j);
+    return t;
 }
+alignas(16) __device__ const UkfTab g_ukf_tab = make_ukf_tab();   // (16-byte words: see the copy at the kernel's start)
 
 // jacobi12(): the 12x12 state covariance, called by the WHOLE workgroup.  Wave 0 owns the 36 blocks of A and
 // computes the six rotations of a round from its diagonal blocks; wave 1 owns the 36 blocks of V.  The rotations
@@ -330,8 +341,8 @@ __device__ __noinline__ void jacobi12(double* A, double* V, UkfLds& L)
             int o00 = 0, o01 = 0, o10 = 0, o11 = 0;
             double x00 = 0, x01 = 0, x10 = 0, x11 = 0;
             if (act) {
-                const uint2 pk = L.jtab[round * 36 + lane];
-                o00 = pk.x & 0xFFFF; o01 = pk.x >> 16; o10 = pk.y & 0xFFFF; o11 = pk.y >> 16;
+                const unsigned pkx = L.tab.jtab[2 * (round * 36 + lane)], pky = L.tab.jtab[2 * (round * 36 + lane) + 1];
+                o00 = pkx & 0xFFFF; o01 = pkx >> 16; o10 = pky & 0xFFFF; o11 = pky >> 16;
                 x00 = M[o00]; x01 = M[o01]; x10 = M[o10]; x11 = M[o11];
                 if (wave == 0 && ba == bb) {   // diagonal block: (app, apq; apq, aqq)
                     double c = 1.0, s = 0.0;
@@ -387,14 +398,20 @@ __device__ __forceinline__ double weighted_dot(const double* ar, const double* b
 }
 
 // The same sum shared by TWO neighbouring lanes (an even / odd pair of one wave): `part` 0 takes the columns [1, mid),
-// part 1 the columns [mid, ncols), the halves meet through a quad_perm swap, and both lanes return the whole sum.  A
+// part 1 the columns [mid, ncols), the halves meet through a quad_perm swap, and both lanes return the whole sum (ncols odd).  A
 // 12 x 12 covariance from 43 sigma columns is 78 distinct sums; one lane each they all take one 43-term chain of LDS
 // reads and dependent FMAs -- two lanes each they take half of it (156 lanes).  Every lane of the wave must call.
 __device__ __forceinline__ double weighted_dot_pair(const double* ar, const double* br, int ncols, double wc0, double wci, int part)
 {
     const int mid = 1 + ((ncols - 1) >> 1);
-    int c = part ? mid : 1;
-    const int end = part ? ncols : mid;
+    // ncols is odd (the mean + plus / minus columns), so both halves hold (ncols - 1) / 2 columns: ONE trip count for the whole
+    // wave and only the base differs.  (With per-lane bounds [1, mid) / [mid, ncols) the loops below were divergent loops to the
+    // compiler: exec-mask bookkeeping around every iteration of a 12-column sum.)
+    const int shift = part ? mid - 1 : 0;
+    ar += shift;
+    br += shift;
+    int c = 1;
+    const int end = mid;
     double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
     for (; c + 7 < end; c += 8) {
         double av[8], bv[8];
@@ -411,8 +428,11 @@ __device__ __forceinline__ double weighted_dot_pair(const double* ar, const doub
     }
     for (; c < end; ++c) s0 = fma(ar[c], br[c], s0);
     double sum = (s0 + s1) + (s2 + s3);
-    sum += __shfl_xor(sum, 1, 64);
-    return fma(ar[0] * br[0], wc0, sum * wci);
+    // the partner's half through a DPP quad_perm [1, 0, 3, 2] swap (two 32-bit moves; __shfl_xor goes through the LDS crossbar:
+    // ds_bpermute, an LDS round trip in front of every entry's store)
+    sum += __hiloint2double(__builtin_amdgcn_update_dpp(0, __double2hiint(sum), 0xB1, 0xF, 0xF, false),
+                            __builtin_amdgcn_update_dpp(0, __double2loint(sum), 0xB1, 0xF, 0xF, false));
+    return fma(ar[-shift] * br[-shift], wc0, sum * wci);
 }
 
 // Weighted means of `nrows` linear rows of Y (row stride kCols), eight lanes per row: lane l of the calling group
@@ -567,8 +587,8 @@ __device__ __forceinline__ void chol_columns(double (&a)[M], double (&rinv)[M], 
     }
 }
 
-// Cholesky factor of the SPD M x M matrix A (ld M) into the lower triangle of Lc (ld M; the strict upper triangle
-// is left untouched) + reciprocal diagonal.  Called by the whole workgroup; the work is done by lanes 0..M-1 of
+// Cholesky factor of the SPD M x M matrix A (ld M) into Lc (ld M; lower triangle, the strict upper triangle is written
+// as zeros) + reciprocal diagonal.  Called by the whole workgroup; the work is done by lanes 0..M-1 of
 // wave 0, lane = row, the row lives in registers and the column being eliminated is broadcast over the row of 16 lanes by DPP row_newbcast
 // (no LDS round trip inside the factorisation).  Returns false if A is not positive definite.
 template <int M>
@@ -576,16 +596,21 @@ __device__ __forceinline__ bool cholesky_rows(const double* A, double* Lc, doubl
 {
     const int lane = threadIdx.x;
     if (lane < 64) {
+        // Rows are read and written WITHOUT a predicate per entry: an `if` around each of the M reads / writes costs a
+        // round trip through the exec mask each (v_cmp -> s_and_saveexec -> ds -> s_or), ~50 cycles apiece on this
+        // one-wave path -- the 12 + 12 of them were a third of a 12 x 12 factorisation.  Lanes >= M work on a copy of
+        // the last row: nothing of theirs is broadcast (the sources are lanes 0 .. M - 1) or stored.
         double a[M];
+        const int row = min(lane, M - 1);
 #pragma unroll
-        for (int k = 0; k < M; ++k) a[k] = (lane < M) ? A[lane * M + k] : 0.0;
+        for (int k = 0; k < M; ++k) a[k] = A[row * M + k];
         double rinv[M];
         int ok = 1;
         static_assert(M <= 16, "the rows of the matrix sit in one DPP row of 16 lanes");
         chol_columns<M, 0>(a, rinv, ok, lane);
         if (lane < M) {
 #pragma unroll
-            for (int k = 0; k < M; ++k) if (k <= lane) Lc[lane * M + k] = a[k];
+            for (int k = 0; k < M; ++k) Lc[lane * M + k] = (k <= lane) ? a[k] : 0.0;
         }
         if (lane == 0) {
 #pragma unroll
@@ -780,14 +805,15 @@ __device__ __noinline__ bool cholesky_state_sqrt(UkfLds& L, bool for_correction,
     const double wv = fmax(L.cov[3 * 13], fmax(L.cov[4 * 13], L.cov[5 * 13]));     // var(omega)
     const double xx = fmax(L.cov[6 * 13], fmax(L.cov[7 * 13], L.cov[8 * 13]));     // var(x)
     // (uniform over the workgroup; comparisons written so that NaN fails them)
-    const bool ok = for_correction ? (th <= guard_rot && wv * xx <= guard_bil) : (th + T * T * wv <= guard_rot);
+    // (the values come from LDS, which the compiler must take for divergent: the vote through readfirstlane makes the branch a
+    //  scalar one instead of a chain of exec-mask updates)
+    const int ok_corr = (int)(th <= guard_rot) & (int)(wv * xx <= guard_bil), ok_pred = (int)(th + T * T * wv <= guard_rot);
+    const bool ok = __builtin_amdgcn_readfirstlane(for_correction ? ok_corr : ok_pred) != 0;
 #ifdef ROFT_UKF_PROFILE
     if (threadIdx.x == 0 && for_correction) { L.dbg[20] = (long long)(th * 1e9); L.dbg[21] = (long long)(wv * 1e9); L.dbg[22] = (long long)(xx * 1e9); }
 #endif
     if (!ok) return false;
-    if (threadIdx.x < 144) L.S[threadIdx.x] = 0.0;
-    __syncthreads();
-    return cholesky_rows<12>(L.cov, L.S, L.rc, L);
+    return cholesky_rows<12>(L.cov, L.S, L.rc, L);   // (writes all of L.S: the factor and the zeros above its diagonal)
 }
 
 // Additive noise in closed form (round 5).  The process noise enters the motion model additively on its linear OUTPUT rows
@@ -874,7 +900,7 @@ __device__ void ukf_predict(UkfLds& L, const ObjParams& prm, double T, const UtT
     }
     __syncthreads();
     if (lane < 192) {   // (whole waves: the pair sum crosses lanes) 78 distinct entries x 2 lanes
-        const int e = min(lane >> 1, 77), ij = L.tri12[e], i = ij >> 8, j = ij & 0xFF;
+        const int e = min(lane >> 1, 77), ij = L.tab.tri12[e], i = ij >> 8, j = ij & 0xFF;
         double v = weighted_dot_pair(L.D + i * kCols, L.D + j * kCols, kPredCols, wc0, w.wi, lane & 1);
         if (j < 9) v += L.Q[i * 10 + j];   // (i <= j: the linear rows carry the process noise)
         if (lane < 156) L.cov[(lane & 1) ? j * 12 + i : i * 12 + j] = v;
@@ -1016,7 +1042,7 @@ __device__ int ukf_correct(UkfLds& L, int type, const UtTable& ut, PoseBelief* o
             double add = 0.0;
             if (e < 72) { ar = L.X + (e / 6) * kCols; br = L.D + (e % 6) * kCols; o0 = e; }
             else {
-                const int ij = L.tri6[e - 72], i = ij >> 8, j = ij & 0xFF;
+                const int ij = L.tab.tri6[e - 72], i = ij >> 8, j = ij & 0xFF;
                 ar = L.D + i * kCols; br = L.D + j * kCols; o0 = i * 6 + j; o1 = j * 6 + i;
                 if (i == j && i < n_add) add = fabs(L.par[r_base + i]);   // |R|: what the sigma columns sqrt(|R|) of rounds 1 - 4 (and the rotation columns above) contribute
             }
@@ -1204,7 +1230,9 @@ __global__ __launch_bounds__(kUkfThreads) void ukf_chain_kernel(EngineArrays a, 
     // table in global memory inside every Jacobi round (two dependent global loads per round)
     ROFT_RESIDENT(a, RK_UKF_CHAIN);
     __shared__ UkfLds L;
-    __shared__ unsigned s_mine;
+    // this thread's 16-byte word of the index tables: in flight while the launch finds out what it has to do
+    uint4 tab_word = make_uint4(0u, 0u, 0u, 0u);
+    if ((int)threadIdx.x < kUkfTabWords) tab_word = reinterpret_cast<const uint4*>(&g_ukf_tab)[threadIdx.x];
     // A pose step is one long chain of dependent instructions on four waves; the CU it runs on is shared with the wide
     // kernels of the other chains (mask walks, rasteriser, flow measurement), whose waves compete for the issue slots of
     // the same SIMDs.  Highest wave priority: the chain's next instruction goes first whenever it is ready.
@@ -1226,12 +1254,10 @@ __global__ __launch_bounds__(kUkfThreads) void ukf_chain_kernel(EngineArrays a, 
     PoseLane& pl = st.lane[lin];
     int t = first_segment ? 0 : pl.pc_frame, step = first_segment ? 0 : pl.pc_step;
     if (t >= a.T) return;   // (this lane's chain of the batch ended in an earlier segment)
-    // frames of the batch that belong to this lane (one load per frame, all in flight together)
-    if (threadIdx.x == 0) s_mine = 0u;
-    __syncthreads();
-    if ((int)threadIdx.x < a.T && frame_ctrl(a, threadIdx.x, obj).lane == lin) atomicOr(&s_mine, 1u << threadIdx.x);
-    __syncthreads();
-    const unsigned mine = s_mine;
+    // frames of the batch that belong to this lane (one load per frame, all in flight together): every wave takes the vote
+    // for itself (a.T <= 32 frames, lane = frame), so the mask is uniform without LDS and without a barrier
+    const int vote_lane = threadIdx.x & 63;
+    const unsigned mine = (unsigned)__ballot(vote_lane < a.T && frame_ctrl(a, vote_lane, obj).lane == lin);
     if ((mine >> t) == 0u) {   // nothing (left) to do for this lane in this batch
         if (threadIdx.x == 0) { pl.pending_frame = -1; pl.pc_frame = a.T; pl.pc_step = 0; }
         return;
@@ -1265,7 +1291,8 @@ __global__ __launch_bounds__(kUkfThreads) void ukf_chain_kernel(EngineArrays a, 
         }
         __syncthreads();   // the next step of this workgroup reads the chosen belief
     }
-    jacobi12_table(L);
+    static_assert(kUkfTabWords <= kUkfThreads, "one 16-byte word of the tables per thread");
+    if ((int)threadIdx.x < kUkfTabWords) reinterpret_cast<uint4*>(&L.tab)[threadIdx.x] = tab_word;
     for (int i = threadIdx.x; i < 100; i += kUkfThreads) L.Q[i] = 0.0;   // see ukf_predict: only the entries of Q(T) are rewritten per step
     __syncthreads();
     bool pending = false;
