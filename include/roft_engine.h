@@ -26,6 +26,7 @@
  *        roft_depth_likelihood   <- ROFTFilter::pick_best_alternative inner loop
  *                                   src/roft-lib/src/ROFTFilter.cpp:553-577
  *        roft_outlier_test       <- ROFTFilter::pick_best_alternative  src/roft-lib/src/ROFTFilter.cpp:467-621
+ *        roft_pose_errors        <- add / adi of tools/third_party/bop_pose_error.py:73-108 (the evaluation's ADD / ADD-S)
  *  (2) the batched engine -- ROFTFilter::filtering_step (src/roft-lib/src/ROFTFilter.cpp:255-452)
  *      for many objects at once with all filter state resident in HBM:
  *        roft_engine_create / roft_object_add / roft_frame_submit | roft_frames_submit / roft_step / roft_get_state.
@@ -205,6 +206,26 @@ int roft_outlier_test_mode(const roft_camera* cam, int divider, const float* dep
                            const double x[6], const double q[8], int bands, int vertex_cache, int window_pixels, int split, int mode,
                            double L_out[2], long samples_out[2], int* selected_out, float* tiles_out);
 
+/* Pose errors of the evaluation (tools/third_party/bop_pose_error.py:73-108, evaluation/metrics.py:303-344) for n_poses pose pairs over
+ * one point set, in double precision, by brute force on the device:
+ *   ROFT_POSE_ERROR_ADD   mean_i |(R_e p_i + t_e) - (R_r p_i + t_r)|
+ *   ROFT_POSE_ERROR_ADDS  mean_i min_j |(R_r p_i + t_r) - (R_e p_j + t_e)|   (BOP "adi": nearest neighbour from the ground-truth
+ *                         cloud into the estimated cloud)
+ * points: n_points x 3 doubles (object frame, metres); est / ref: n_poses x 7 doubles (x y z, q = w x y z); out: n_poses doubles
+ * (metres).  The quaternion is used as it is given, not normalised.
+ * Determinism contract: out[f] is a function of kind, the points and the pose pair f alone -- not of n_poses, of the position of
+ * the pair in the call, of the other pairs or of the run (fixed summation order, no atomics): equal inputs give equal bits.
+ * (ROFT_POSE_ERRORS_FMA=0 in the environment, read once per process, makes the ADD-S search square and add in the oracle's operation
+ * order, 9 instead of 7 operations per pair: an A/B switch of tools/bench_pose_errors.py.  Both orders are inside the 1e-12 m the tests
+ * ask for; their last bits differ, so the contract holds within a process.)
+ * A pose pair with a non-finite component gives a non-finite out[f] (+inf, or NaN) and changes no other entry.
+ * ROFT_ERR_INVALID: unknown kind, NULL pointer, n_points <= 0, n_poses < 0 -- checked before the device is looked for;
+ * n_poses == 0 is ROFT_OK and touches nothing. */
+#define ROFT_POSE_ERROR_ADD  0
+#define ROFT_POSE_ERROR_ADDS 1   /* BOP "adi" */
+int roft_pose_errors(int kind, const double* points, int n_points, const double* est, const double* ref, int n_poses,
+                     double* out);
+
 /* ---- (2) batched engine --------------------------------------------------------------------- */
 
 typedef struct roft_engine roft_engine;
@@ -355,6 +376,15 @@ int roft_engine_get_log(roft_engine* e, int first_frame, int n_frames, roft_obje
 /* the same log as the reference writes it: rows[(f * n_objects + obj) * 19 ..] = pose(13: v w x q) | twist(6)
  * (`pose_estimate` + `velocity_estimate`, ROFTFilter.cpp:386-394) -- the per-object records a multi-GPU job gathers */
 int roft_engine_get_log_rows(roft_engine* e, int first_frame, int n_frames, double* rows);
+/* roft_pose_errors for the poses of one object in the log: the estimates are read in place (pose[6..12] of the records, ring
+ * wrap-around included) and never leave the device; the same device code, so the result equals roft_pose_errors on the rows
+ * roft_engine_get_log_rows returns bit for bit.  ref: n_frames x 7 host doubles for frames first_frame .. first_frame + n_frames - 1;
+ * points NULL (n_points ignored): every vertex of the mesh the object was added with (float -> double is exact).  Syncs the engine.
+ * ROFT_ERR_INVALID: log off, bad obj_id, unknown kind, and a frame range that is not wholly inside what the ring still holds --
+ * valid is first_frame >= 0, n_frames <= the log's capacity, first_frame + n_frames <= frames stepped and
+ * first_frame >= frames stepped - capacity.  n_frames == 0 is ROFT_OK. */
+int roft_engine_score_log(roft_engine* e, int kind, int obj_id, int first_frame, int n_frames, const double* points,
+                          int n_points, const double* ref, double* out);
 
 /* work enqueued since roft_engine_create */
 typedef struct {
@@ -478,6 +508,8 @@ int roft_debug_get_residency(roft_engine* e, unsigned long long out[32]);
  * the LDS in one piece), 0 = they split only the ROWS of its window, -1 = the library's choice (1).  The results do not depend
  * on it (tests/test_parity_gpu.py). */
 int roft_debug_outlier_split(int mode);
+/* device time in milliseconds (HIP events) of the kernels of the calling process's last roft_pose_errors call, without its copies */
+int roft_debug_pose_errors_kernel_ms(double* ms_out);
 /* phase counters of one object's last kernels (only filled by libraries built with a -DROFT_*_PROFILE switch) */
 int roft_debug_get_dbg(roft_engine* e, int obj_id, long long out[32]);
 

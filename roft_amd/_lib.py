@@ -106,7 +106,11 @@ ABI_SYMBOLS = [
     "roft_flow_producer_destroy", "roft_flow_producer_run", "roft_flow_producer_sync", "roft_flow_producer_stream",
     "roft_debug_plan", "roft_debug_get_dbg", "roft_debug_probe_streams", "roft_debug_sector_rate",
     "roft_host_alloc", "roft_host_free", "roft_host_is_pinned", "roft_debug_get_residency", "roft_debug_outlier_split",
+    "roft_pose_errors", "roft_engine_score_log", "roft_debug_pose_errors_kernel_ms",
 ]
+POSE_ERROR_ADD, POSE_ERROR_ADDS = 0, 1   # ROFT_POSE_ERROR_*
+# entry points younger than ABI version 2 itself: a library built before them still loads through ROFT_LIB_SO
+NEWER_SYMBOLS = ("roft_pose_errors", "roft_engine_score_log")
 
 
 def build(force=False):
@@ -193,9 +197,13 @@ def lib():
     L.roft_host_free.restype = None
     L.roft_host_free.argtypes = [vp]
     L.roft_host_is_pinned.argtypes = [vp]
+    if hasattr(L, "roft_pose_errors"):
+        L.roft_pose_errors.argtypes = [C.c_int, vp, C.c_int, vp, vp, C.c_int, vp]
+        L.roft_engine_score_log.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp]
+        L.roft_debug_pose_errors_kernel_ms.argtypes = [dp]
     for name in ABI_SYMBOLS:
-        if name.startswith("roft_debug_") and not hasattr(L, name):
-            continue   # (an older build loaded through ROFT_LIB_SO for an A/B run: diagnostics only; tests/test_abi_cpu.py checks the in-tree library has them all)
+        if (name.startswith("roft_debug_") or name in NEWER_SYMBOLS) and not hasattr(L, name):
+            continue   # (an older build loaded through ROFT_LIB_SO for an A/B run: diagnostics and the pose errors only; tests/test_abi_cpu.py checks the in-tree library has them all)
         f = getattr(L, name)
         if name not in ("roft_last_error_string", "roft_engine_stream", "roft_flow_producer_stream", "roft_host_alloc", "roft_host_free"):
             f.restype = C.c_int

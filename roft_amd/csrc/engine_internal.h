@@ -6,7 +6,7 @@
 //   engine_submit.hip   roft_frames_submit: the frame programs (build_pose_program), HOST staging, the control blocks of a batch
 //   engine_step.hip     roft_step / roft_sync: the four-stream launch graph of a batch (step_batch) and its timing marks
 //   engine_results.hip  state, outputs, log, masks, timing and batch-trace readers
-//   engine_ops.hip      the operator-level entry points (one-object context: roft_flow_measurement ... roft_outlier_test)
+//   engine_ops.hip      the operator-level entry points (one-object context: roft_flow_measurement ... roft_outlier_test, roft_pose_errors)
 //   engine_debug.hip    roft_debug_* (diagnostics and experiments)
 #pragma once
 
@@ -181,6 +181,23 @@ struct Arrays {
         return ROFT_OK;
     }
 };
+
+// Device scratch of the pose-error metrics (roft_pose_errors / roft_engine_score_log): grows on demand, kept between calls.
+struct PoseErrorScratch {
+    DevBuf<double> pts, est, ref, cloud, partial, out;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the kernels of the last call (roft_debug_pose_errors_kernel_ms)
+    bool timed = false;
+    ~PoseErrorScratch()
+    {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+    }
+};
+// ADD / ADD-S of n pose pairs on stream s (engine_ops.hip).  d_pts: P x 3 doubles on the device.  The estimates are est_host
+// (n x 7 host doubles, uploaded) or, when that is null, est_dev (already on the device).  ref_host: n x 7 host doubles;
+// out_host: n doubles.  Returns when the results are in out_host.
+int pose_errors_run(PoseErrorScratch& sc, int kind, const double* d_pts, int P, const double* est_host, PoseView est_dev,
+                    const double* ref_host, int n, double* out_host, hipStream_t s);
 
 inline void init_state(ObjState& st)
 {
@@ -396,6 +413,7 @@ struct roft_engine {
     static constexpr int kSpanLaunches = 64;
     DevBuf<unsigned long long> k1_span;
     std::vector<int> span_wgs;   // workgroups of each stamped launch
+    PoseErrorScratch score;      // roft_engine_score_log
 };
 
 namespace roft {

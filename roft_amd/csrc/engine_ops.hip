@@ -66,6 +66,56 @@ int to_dev(DevBuf<unsigned char>& b, const T* src, size_t count, hipStream_t s)
     return ROFT_OK;
 }
 
+// ROFT_POSE_ERRORS_FMA=0: the nearest-neighbour search squares and adds in the oracle's operation order (9 fp64 operations per
+// pair instead of 7); read once per process
+bool pose_errors_fma()
+{
+    static const bool fma = [] { const char* v = getenv("ROFT_POSE_ERRORS_FMA"); return !(v && v[0] == '0'); }();
+    return fma;
+}
+
+}  // namespace
+
+int roft::host::pose_errors_run(PoseErrorScratch& sc, int kind, const double* d_pts, int P, const double* est_host, PoseView est_dev,
+                                const double* ref_host, int n, double* out_host, hipStream_t s)
+{
+    const int P_pad = pose_error_padded_points(P), waves = pose_error_waves(P);
+    // poses per launch: the estimated clouds of a launch fit 256 MiB of scratch, and the grid's y extent
+    constexpr size_t kCloudBytes = (size_t)256 << 20;
+    const int per_launch = kind == ROFT_POSE_ERROR_ADDS
+                               ? (int)std::min<size_t>(32768, std::max<size_t>(1, kCloudBytes / ((size_t)P_pad * 3 * sizeof(double))))
+                               : 32768;
+    const int chunk = std::min(n, per_launch);
+    if (est_host) {
+        HIP_TRY(sc.est.ensure((size_t)7 * n));
+        HIP_TRY(hipMemcpyAsync(sc.est.p, est_host, sizeof(double) * 7 * n, hipMemcpyHostToDevice, s));
+        est_dev = PoseView{sc.est.p, 7, 0, 0};
+    }
+    HIP_TRY(sc.ref.ensure((size_t)7 * n));
+    HIP_TRY(hipMemcpyAsync(sc.ref.p, ref_host, sizeof(double) * 7 * n, hipMemcpyHostToDevice, s));
+    if (kind == ROFT_POSE_ERROR_ADDS) HIP_TRY(sc.cloud.ensure((size_t)chunk * P_pad * 3));
+    HIP_TRY(sc.partial.ensure((size_t)chunk * waves));
+    HIP_TRY(sc.out.ensure((size_t)n));
+    if (!sc.ev0) { HIP_TRY(hipEventCreate(&sc.ev0)); HIP_TRY(hipEventCreate(&sc.ev1)); }
+    const PoseView ref_dev{sc.ref.p, 7, 0, 0};
+    HIP_TRY(hipEventRecord(sc.ev0, s));
+    for (int f0 = 0; f0 < n; f0 += chunk)   // (in order on one stream: a launch re-uses the scratch of the one before)
+        launch_pose_errors(kind, d_pts, P, est_dev, ref_dev, f0, std::min(chunk, n - f0), sc.cloud.p, sc.partial.p, sc.out.p,
+                           pose_errors_fma(), s);
+    HIP_TRY(hipEventRecord(sc.ev1, s));
+    sc.timed = true;
+    HIP_TRY(hipMemcpyAsync(out_host, sc.out.p, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipGetLastError());
+    return ROFT_OK;
+}
+
+namespace {
+PoseErrorScratch& op_pose_scratch()
+{
+    static PoseErrorScratch sc;
+    return sc;
+}
 }  // namespace
 
 extern "C" {
@@ -602,6 +652,34 @@ int roft_depth_likelihood(const roft_camera* cam, const float* depth, const uint
     c.arr.a.tile_h = cam->height / c.arr.a.cam.divider;
     c.ready = false;  // zbuf may have been re-sized: force a clean re-allocation next time
     HIP_TRY(err);
+    return ROFT_OK;
+}
+
+int roft_pose_errors(int kind, const double* points, int n_points, const double* est, const double* ref, int n_poses, double* out)
+{
+    if (kind != ROFT_POSE_ERROR_ADD && kind != ROFT_POSE_ERROR_ADDS) return fail(ROFT_ERR_INVALID, "unknown pose error kind");
+    if (!points || !est || !ref || !out) return fail(ROFT_ERR_INVALID, "null argument");
+    if (n_points <= 0 || n_poses < 0) return fail(ROFT_ERR_INVALID, "n_points must be > 0 and n_poses >= 0");
+    if (n_poses == 0) return ROFT_OK;
+    OpCtx& c = op();
+    std::lock_guard<std::mutex> lk(c.mu);
+    if (int rc = op_simple_prepare(c)) return rc;
+    PoseErrorScratch& sc = op_pose_scratch();
+    HIP_TRY(sc.pts.ensure((size_t)3 * n_points));
+    HIP_TRY(hipMemcpyAsync(sc.pts.p, points, sizeof(double) * 3 * n_points, hipMemcpyHostToDevice, c.stream));
+    return pose_errors_run(sc, kind, sc.pts.p, n_points, est, PoseView{}, ref, n_poses, out, c.stream);
+}
+
+int roft_debug_pose_errors_kernel_ms(double* ms_out)
+{
+    if (!ms_out) return fail(ROFT_ERR_INVALID, "null argument");
+    OpCtx& c = op();
+    std::lock_guard<std::mutex> lk(c.mu);
+    PoseErrorScratch& sc = op_pose_scratch();
+    if (!sc.timed) return fail(ROFT_ERR_STATE, "no roft_pose_errors call to report");
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, sc.ev0, sc.ev1));
+    *ms_out = ms;
     return ROFT_OK;
 }
 

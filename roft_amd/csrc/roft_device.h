@@ -432,4 +432,20 @@ hipError_t set_max_dynamic_lds(const void* func, int bytes);
 void launch_expand_yh(const FlowRec* recs, const int* n, DevCamera cam, double dt, int32_t* uv, double* y,
                       double* H, int cap, hipStream_t s);
 
+// ---- pose-error metrics (k_metrics.hip) ---------------------------------------------------------------------------
+constexpr int kCandBatch = 8;   // candidates fetched by one group of uniform loads (the padded row length of a cloud is a multiple)
+// n rows of 7 doubles (x y z, q = w x y z) on the device: row f is base + ((first + f) % ring) * stride (ring 0: no wrap-around)
+struct PoseView {
+    const double* base;
+    long stride;   // doubles between two rows
+    int first, ring;
+};
+int pose_error_padded_points(int P);   // candidates per row of the cloud scratch
+int pose_error_waves(int P);           // partial sums per pose
+void launch_float_to_double(const float* in, int n, double* out, hipStream_t s);
+// ADD / ADD-S (kind: ROFT_POSE_ERROR_*) of the pose pairs f0 .. f0 + n - 1 (n <= 65535) of the two views over pts[P][3] -> out[f0 + ..].
+// cloud: n x padded_points x 3 doubles (ADD-S only), partial: n x waves doubles.  fma: 7 instead of 9 operations per pair (ADD-S).
+void launch_pose_errors(int kind, const double* pts, int P, const PoseView& est, const PoseView& ref, int f0, int n, double* cloud,
+                        double* partial, double* out, bool fma, hipStream_t s);
+
 }  // namespace roft

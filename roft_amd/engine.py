@@ -203,6 +203,20 @@ class ROFTFilterBatch:
         L.check(L.lib().roft_engine_get_log_rows(self._h, first, n, rows.ctypes.data))
         return rows
 
+    def score_log(self, kind, obj, first, n, ref, points=None):
+        """ADD ('add') / ADD-S ('adi') of object `obj` over the logged frames first .. first + n - 1 against ref [n, 7] (x y z,
+        q wxyz), on the device: the estimates are read from the log in place (roft_engine_score_log).  points [P, 3]; None:
+        every vertex of the mesh the object was added with.  Returns ndarray[n] (metres)."""
+        from .ops import pose_error_kind
+        ref = np.ascontiguousarray(ref, np.float64).reshape(-1, 7)
+        if ref.shape[0] != n:
+            raise ValueError("ref must hold one pose per scored frame")
+        out = np.zeros(n)
+        pts = None if points is None else np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+        L.check(L.lib().roft_engine_score_log(self._h, pose_error_kind(kind), obj, first, n, None if pts is None else pts.ctypes.data,
+                                              0 if pts is None else pts.shape[0], ref.ctypes.data, out.ctypes.data))
+        return out
+
     def stream(self):
         return L.lib().roft_engine_stream(self._h)
 

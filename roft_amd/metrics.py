@@ -47,12 +47,33 @@ def auc(distances, threshold=0.1):
     return float(np.sum((mrec[i] - mrec[i - 1]) * mpre[i]) * 10.0 * 100.0)
 
 
-def trajectory_adds(pose_est, pose_ref, pts):
-    """pose_*: [F, 7] (x, q wxyz).  Returns the per-frame ADD-S distances."""
+def _trajectory(kind, pose_est, pose_ref, pts, backend):
+    """Per-frame distances of a trajectory.  backend 'cpu': add / adds above, pose by pose; 'hip': the device
+    (ops.pose_errors, no CPU fallback: RoftError without a device); 'auto': the device when there is one."""
+    if backend not in ("cpu", "hip", "auto"):
+        raise ValueError("backend must be 'cpu', 'hip' or 'auto'")
+    if backend == "auto":
+        from . import _lib
+        backend = "hip" if _lib.lib().roft_device_count() > 0 else "cpu"
+    pose_est, pose_ref = np.asarray(pose_est, float), np.asarray(pose_ref, float)
+    if backend == "hip":
+        from . import ops
+        return ops.pose_errors(kind, pts, pose_est, pose_ref)
+    f = add if kind == "add" else adds
     out = np.zeros(len(pose_est))
     for k in range(len(pose_est)):
-        out[k] = adds(quat_to_rot(pose_est[k, 3:]), pose_est[k, :3], quat_to_rot(pose_ref[k, 3:]), pose_ref[k, :3], pts)
+        out[k] = f(quat_to_rot(pose_est[k, 3:]), pose_est[k, :3], quat_to_rot(pose_ref[k, 3:]), pose_ref[k, :3], pts)
     return out
+
+
+def trajectory_adds(pose_est, pose_ref, pts, backend="cpu"):
+    """pose_*: [F, 7] (x, q wxyz).  Returns the per-frame ADD-S distances."""
+    return _trajectory("adi", pose_est, pose_ref, pts, backend)
+
+
+def trajectory_add(pose_est, pose_ref, pts, backend="cpu"):
+    """pose_*: [F, 7] (x, q wxyz).  Returns the per-frame ADD distances."""
+    return _trajectory("add", pose_est, pose_ref, pts, backend)
 
 
 # ---- RMSE metrics of evaluation/metrics.py (the step right after the filtering path) -----------------------
@@ -107,16 +128,18 @@ class Metric:
     arrays whose rows are what evaluation/data_loader.py hands over -- poses `x y z axis angle` (7 columns) for the pose
     metrics, `v w` (6 columns) for the velocity metrics --, `time`: rows `[execution_ms, loading_ms]`; for the object name
     'ALL' all three are dicts name -> array and the rows of all objects are pooled (metrics.py:72-81).  `auc_points`: name ->
-    [P, 3] model points for 'add' / 'adi' (the reference reads YCB_Video_Models/<name>/points.xyz, metrics.py:47-49)."""
+    [P, 3] model points for 'add' / 'adi' (the reference reads YCB_Video_Models/<name>/points.xyz, metrics.py:47-49).
+    `backend`: where the ADD / ADD-S distances are computed, as in trajectory_adds ('cpu' by default)."""
 
     NAMES = ("rmse_cartesian_3d", "rmse_cartesian_x", "rmse_cartesian_y", "rmse_cartesian_z", "rmse_angular", "rmse_linear_velocity",
              "rmse_angular_velocity", "max_linear_velocity", "max_angular_velocity", "add", "adi", "time", "excess_33_ms")
 
-    def __init__(self, name, auc_points=None):
+    def __init__(self, name, auc_points=None, backend="cpu"):
         if name not in self.NAMES:
             raise ValueError("Metric " + name + " does not exist.")
         self.name = name
         self.auc_points = auc_points or {}
+        self.backend = backend
 
     @staticmethod
     def _pool(object_name, x):
@@ -167,11 +190,23 @@ class Metric:
             names = list(signal)
         else:
             names, signal, reference = [object_name], {object_name: signal}, {object_name: reference}
-        dists = []
-        for name in names:
-            pts = np.asarray(self.auc_points[name], float)
-            for r, s in zip(np.asarray(reference[name], float), np.asarray(signal[name], float)):
-                f = add if ad_name == "add" else adds
-                dists.append(f(self._rot(s[3:7]), s[:3], self._rot(r[3:7]), r[:3], pts))
-        dists = np.array(dists)
+        dists = [self.distances(name, reference[name], signal[name], ad_name) for name in names]
+        dists = np.concatenate(dists) if dists else np.zeros(0)
         return dists, auc(dists)
+
+    @staticmethod
+    def _poses(rows):
+        """rows `x y z axis angle` -> [F, 7] `x y z q` (w x y z), converted once per trajectory."""
+        from .io import axis_angle_to_quat
+        rows = np.asarray(rows, float)
+        out = np.empty((len(rows), 7))
+        out[:, :3] = rows[:, :3]
+        for k in range(len(rows)):
+            out[k, 3:] = axis_angle_to_quat(rows[k, 3:6], rows[k, 6])
+        return out
+
+    def distances(self, name, reference, signal, ad_name):
+        """Per-frame ADD ('add') or ADD-S ('adi') of one object's trajectory on auc_points[name]."""
+        pts = np.asarray(self.auc_points[name], float)
+        n = min(len(reference), len(signal))   # (rows are paired as far as both go)
+        return _trajectory(ad_name, self._poses(signal[:n]), self._poses(reference[:n]), pts, self.backend)

@@ -10,6 +10,7 @@ Names follow the reference's classes (hsp-iit/roft `src/roft-lib`):
   render_depth      <- SICAD::superimpose(..., depth)
   depth_likelihood  <- ROFTFilter::pick_best_alternative (inner loop)
   optical_flow      <- ImageOpticalFlowNVOF::step_frame (the product contract; the algorithm is this project's own)
+  pose_errors       <- add / adi of tools/third_party/bop_pose_error.py (the evaluation's ADD / ADD-S)
 All of them run on the GPU; none has a CPU fallback.
 """
 import ctypes as C
@@ -184,6 +185,34 @@ def outlier_test(cam, divider, depth, mask, mesh, x2, q2, bands=0, vertex_cache=
                                                1 if vertex_cache else 0, window_pixels, sp, mode, _p(Lv), _p(ns), C.byref(sel),
                                                _p(t) if tiles else None))
     return Lv, ns, sel.value, t
+
+
+POSE_ERROR_KINDS = {"add": L.POSE_ERROR_ADD, "adi": L.POSE_ERROR_ADDS, "adds": L.POSE_ERROR_ADDS}
+
+
+def pose_error_kind(kind):
+    """'add' | 'adi' | 'adds' or L.POSE_ERROR_ADD | L.POSE_ERROR_ADDS -> the ABI's constant."""
+    return POSE_ERROR_KINDS[kind] if isinstance(kind, str) else int(kind)
+
+
+def pose_errors(kind, points, est, ref):
+    """ADD ('add') or ADD-S ('adi' / 'adds') of F pose pairs over one point set, in double precision on the device
+    (roft_pose_errors).  points [P, 3]; est, ref [F, 7] rows x y z, q = (w, x, y, z), the quaternion used as given.
+    Returns ndarray[F] (metres); a non-finite pose gives a non-finite entry."""
+    points = _f64(points).reshape(-1, 3)
+    est, ref = _f64(est).reshape(-1, 7), _f64(ref).reshape(-1, 7)
+    if est.shape != ref.shape:
+        raise ValueError("est and ref must hold the same number of poses")
+    out = np.zeros(est.shape[0])
+    L.check(L.lib().roft_pose_errors(pose_error_kind(kind), _p(points), points.shape[0], _p(est), _p(ref), est.shape[0], _p(out)))
+    return out
+
+
+def pose_errors_kernel_ms():
+    """Device time (ms, HIP events) of the kernels of the last pose_errors call, without its copies."""
+    ms = C.c_double(0.0)
+    L.check(L.lib().roft_debug_pose_errors_kernel_ms(C.byref(ms)))
+    return ms.value
 
 
 def of_params(levels=3, radius=3, iterations=3, det_min=100.0):

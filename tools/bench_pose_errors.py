@@ -1,0 +1,133 @@
+#!/usr/bin/env python3
+"""Times the ADD-S scoring of trajectories: the CPU path (metrics.trajectory_adds, backend "cpu": one KD-tree per pose on one
+core) against the device path (ops.pose_errors, end to end: upload and read-back included), in one process.
+
+  bench_pose_errors.py [--out profiles/r08_pose_errors.json] [--commit HASH] [--cpu-poses 1000] [--repeats 5]
+
+Cases: P in {500, 2 620, every vertex of synth.box_mesh(CRACKER_BOX_HALF_EXTENTS) = 8 214} x F in {1 000, 48 000} pose pairs.
+The CPU path is run on --cpu-poses poses; for F = 48 000 that time is scaled (its cost per pose does not depend on F).  The
+device path: median of --repeats calls after one warm-up; the kernel-only time comes from HIP events around the call's kernels.
+The achieved fp64 rate counts the nearest-neighbour kernel's own operations per pair (7: 3 sub, 1 mul, 2 fma, 1 min; an fma is
+ONE operation) and is set against the device's peak in the same unit.  The search is also timed once in the oracle's operation
+order (9 operations, ROFT_POSE_ERRORS_FMA=0, in a child process: the switch is read once per process).
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from roft_amd import _lib as L  # noqa: E402
+from roft_amd import metrics, ops, synth  # noqa: E402
+
+# AMD Instinct MI355X data sheet: peak double-precision VECTOR (FP64) performance 78.6 TFLOP/s, an fma counted as two
+# floating-point operations = 256 CUs x 4 SIMDs x 16 lanes x 2.4 GHz = 39.3e12 fp64 VALU operations per second
+PEAK_FP64_VECTOR_TFLOPS = 78.6
+PEAK_FP64_VALU_OPS = PEAK_FP64_VECTOR_TFLOPS * 1e12 / 2.0
+PEAK_SOURCE = "AMD Instinct MI355X data sheet, peak FP64 vector 78.6 TFLOP/s (fma = 2 flop); not measured here"
+
+
+def clouds():
+    rng = np.random.default_rng(8)
+    box = synth.box_mesh(synth.CRACKER_BOX_HALF_EXTENTS)[0].astype(np.float64)
+    return [("500", rng.uniform(-0.1, 0.1, (500, 3))), ("2620", rng.uniform(-0.1, 0.1, (2620, 3))), ("box_8214", box)]
+
+
+def poses(n, seed=1):
+    """Tracker-like pairs: random ground truth within 1.5 m, estimates off by millimetres and a few milliradians."""
+    rng = np.random.default_rng(seed)
+    q = rng.normal(size=(n, 4))
+    q /= np.linalg.norm(q, axis=1, keepdims=True)
+    t = rng.uniform(-0.8, 0.8, (n, 3))
+    dq = np.concatenate([np.ones((n, 1)), rng.normal(0, 5e-3, (n, 3))], 1)
+    qe = np.array([synth.quat_mul(a, b) for a, b in zip(q, dq)])
+    qe /= np.linalg.norm(qe, axis=1, keepdims=True)
+    return np.concatenate([t + rng.normal(0, 3e-3, (n, 3)), qe], 1), np.concatenate([t, q], 1)
+
+
+def time_device(pts, est, ref, repeats):
+    ops.pose_errors("adi", pts, est, ref)   # warm-up: buffers, code object
+    wall, kern = [], []
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        out = ops.pose_errors("adi", pts, est, ref)
+        wall.append(time.perf_counter() - t0)
+        kern.append(ops.pose_errors_kernel_ms() * 1e-3)
+    return float(np.median(wall)), float(np.median(kern)), out
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r08_pose_errors.json"))
+    ap.add_argument("--commit", default=None)
+    ap.add_argument("--cpu-poses", type=int, default=1000)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--kernel-only", action="store_true", help="(the child run) print the kernel time of the full mesh x 1 000 poses")
+    args = ap.parse_args(argv)
+    L.require_device()
+    fma = os.environ.get("ROFT_POSE_ERRORS_FMA", "1")[:1] != "0"
+    ops_per_pair = 7 if fma else 9
+    if args.kernel_only:
+        pts = clouds()[-1][1]
+        est, ref = poses(1000)
+        _, kern, _ = time_device(pts, est, ref, args.repeats)
+        print(json.dumps(dict(kernel_s=kern, ops_per_pair=ops_per_pair)))
+        return 0
+    commit = args.commit
+    if commit is None:
+        try:
+            commit = subprocess.check_output(["git", "-C", ROOT, "rev-parse", "HEAD"], text=True, stderr=subprocess.DEVNULL).strip()
+        except Exception:
+            commit = "unknown"
+    cases = []
+    all_faster = True
+    est_all, ref_all = poses(48000)   # every case scores the leading rows of the same trajectory
+    for name, pts in clouds():
+        P = len(pts)
+        est_c, ref_c = est_all[:args.cpu_poses], ref_all[:args.cpu_poses]
+        t0 = time.perf_counter()
+        cpu_out = metrics.trajectory_adds(est_c, ref_c, pts, backend="cpu")
+        cpu_ms_per_pose = 1e3 * (time.perf_counter() - t0) / args.cpu_poses
+        for F in (1000, 48000):
+            est, ref = est_all[:F], ref_all[:F]
+            wall, kern, out = time_device(pts, est, ref, args.repeats)
+            n_cmp = min(F, args.cpu_poses)
+            pairs = float(F) * P * P
+            rate = pairs * ops_per_pair / kern
+            case = dict(points=P, cloud=name, poses=F, cpu_ms_per_pose=cpu_ms_per_pose, cpu_poses_timed=args.cpu_poses,
+                        cpu_scaled=F != args.cpu_poses, cpu_s=cpu_ms_per_pose * 1e-3 * F,
+                        device_ms_per_pose=1e3 * wall / F, device_s=wall, device_kernel_s=kern, speedup=cpu_ms_per_pose * 1e-3 * F / wall,
+                        pair_distances_per_s=pairs / wall, pair_distances_per_s_kernel=pairs / kern,
+                        fp64_valu_ops_per_s=rate, fraction_of_fp64_vector_peak=rate / PEAK_FP64_VALU_OPS,
+                        max_abs_diff_vs_cpu_m=float(np.abs(out[:n_cmp] - cpu_out[:n_cmp]).max()))
+            all_faster = all_faster and wall < case["cpu_s"]
+            cases.append(case)
+            print(json.dumps(case), flush=True)
+    # the same search in the oracle's operation order, kernel only
+    env = dict(os.environ, ROFT_POSE_ERRORS_FMA="0")
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--kernel-only", "--repeats", str(args.repeats)], env=env,
+                       capture_output=True, text=True, timeout=600)
+    no_fma = json.loads(r.stdout.strip().splitlines()[-1]) if r.returncode == 0 and r.stdout.strip() else dict(error=r.stderr[-500:])
+    with_fma = next(c for c in cases if c["cloud"] == "box_8214" and c["poses"] == 1000)["device_kernel_s"]
+    record = dict(commit=commit, device_count=int(L.lib().roft_device_count()), kind="ADD-S (ROFT_POSE_ERROR_ADDS)",
+                  kernel_ops_per_pair=ops_per_pair, kernel_ops="3 sub, 1 mul, 2 fma, 1 min (an fma is one operation)" if fma else "3 sub, 3 mul, 2 add, 1 min",
+                  peak_fp64_valu_ops_per_s=PEAK_FP64_VALU_OPS, peak_source=PEAK_SOURCE,
+                  cpu_path="metrics.trajectory_adds backend='cpu' (scipy cKDTree, one core); timed on cpu_poses_timed poses, scaled to F where cpu_scaled",
+                  device_path="ops.pose_errors end to end (upload, kernels, read-back): median of %d calls after one warm-up" % args.repeats,
+                  cases=cases, device_faster_in_every_case=bool(all_faster),
+                  operation_order_ab=dict(case="box_8214 x 1000 poses, kernel only", fma_7_ops_kernel_s=with_fma, oracle_order_9_ops=no_fma))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(record, f, indent=1)
+        f.write("\n")
+    print("wrote", args.out, "device faster in every case:", all_faster)
+    return 0 if all_faster else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -3,11 +3,14 @@
 reference computes for its 'ours' entries -- per object and pooled over ALL -- printed as a Markdown table.
 
   evaluate_results.py --results DIR --dataset DIR [--objects NAME ...] [--points DIR] [--metrics m1,m2,...] [--of-ms 0]
+                      [--device] [--all-points]
 
 DIR/<object>/{pose_estimate[_ycb].txt, velocity_estimate.txt, execution_times.txt} are the log files ROFT-tracker (or
 ROFT-tracker-batch, or tools/run_sequence.py with --out DIR/<object>/) leaves; dataset/<object>/gt/poses.txt holds the ground-truth
 poses (x y z axis angle) and, optionally, gt/velocities.txt the ground-truth velocities.  ADD / ADD-S use <points>/<object>/points.xyz
-when --points is given (the reference's YCB_Video_Models layout), else every k-th vertex of dataset/<object>/model.obj.
+when --points is given (the reference's YCB_Video_Models layout), else every k-th vertex of dataset/<object>/model.obj (about 500;
+--all-points: every vertex).  --device computes the ADD / ADD-S distances on the GPU (roft_pose_errors: brute force in double
+precision, the same numbers to 1e-12 m), once per object: the ALL row pools them instead of computing them again.
 As in evaluate.py: the leading six velocity columns of the pose log are dropped (data_loader.py:238-241), the estimates are compared
 with as many ground-truth rows as there are estimates (from the row the run started at: --first-frame), the linear velocity is
 moved from the camera origin to the object position before it is compared (v = v_O + w x r, evaluate.py:514-521), and --of-ms is
@@ -70,6 +73,8 @@ def main(argv=None):
     ap.add_argument("--first-frame", type=int, default=0)
     ap.add_argument("--of-ms", type=float, default=0.0)
     ap.add_argument("--json", default=None, help="also write the numbers to this file")
+    ap.add_argument("--device", action="store_true", help="ADD / ADD-S distances on the GPU (no CPU fallback)")
+    ap.add_argument("--all-points", action="store_true", help="ADD / ADD-S on every vertex of model.obj instead of about 500")
     args = ap.parse_args(argv)
     names = args.objects or sorted(n for n in os.listdir(args.results) if os.path.isdir(os.path.join(args.results, n)))
     data = {n: load_object(args.results, args.dataset, n, args.first_frame, args.of_ms) for n in names}
@@ -81,15 +86,22 @@ def main(argv=None):
             mesh = first_existing(os.path.join(args.dataset, n, "model.obj"), os.path.join(args.dataset, n, n + ".obj"))
             if mesh:
                 v, _ = io.load_obj(mesh)
-                points[n] = v.astype(np.float64)[:: max(1, len(v) // 500)]
+                points[n] = v.astype(np.float64)[:: 1 if args.all_points else max(1, len(v) // 500)]
     wanted = [m for m in args.metrics.split(",") if m]
     table = {}
     for m in wanted:
-        metric = metrics.Metric(m, auc_points=points)
+        metric = metrics.Metric(m, auc_points=points, backend="hip" if args.device else "cpu")
         vel_metric = "velocity" in m
         row = {}
         have = [n for n in names if ("vel" in data[n] if vel_metric else True) and (m not in ("time", "excess_33_ms") or "time" in data[n])
                 and (m not in ("add", "adi") or n in points)]
+        if args.device and m in ("add", "adi"):
+            dist = {n: metric.distances(n, data[n]["gt_pose"], data[n]["pose"], m) for n in have}
+            row = {n: metrics.auc(dist[n]) for n in have}
+            if have:
+                row["ALL"] = metrics.auc(np.concatenate([dist[n] for n in have]))
+            table[m] = row
+            continue
         for n in have:
             ref, sig = (data[n]["gt_vel"], data[n]["vel"]) if vel_metric else (data[n]["gt_pose"], data[n]["pose"])
             row[n] = metric.evaluate(n, ref, sig, data[n].get("time"))

@@ -4,7 +4,7 @@ files (`pose_estimate`, `velocity_estimate`, ROFTFilter.cpp:386-394) -- what `te
 
   run_sequence.py --root DIR --object NAME --mesh model.obj [--flow-set nvof_1_slow] [--mask-set NAME]
                   [--pose-set dope] [--out PREFIX] [--compute-flow nvof1|nvof2] [--no-delay] [--init-pose x y z qw qx qy qz]
-                  [--start-at-first-detection]
+                  [--start-at-first-detection] [--score-on-device]
                   [--from config_fast_ycb.cfg [--group::key value ...]]
 
 --from reads the filter parameters from one of the reference's configuration files (config/config_fast_ycb.cfg,
@@ -13,7 +13,9 @@ config/config_ho3d.cfg) and applies `--a::b::c value` overrides exactly as ROFT-
 
 The camera comes from DIR/cam_K.json (width, height, fx, fy, cx, cy).  --compute-flow first runs tools/flow_dumper.py
 on DIR/rgb (the MI355X replacement of the NVOF dumper) into DIR/optical_flow/<flow-set>.  With DIR/gt/poses.txt present
-the ADD-S / ADD AUC and the RMSE metrics of evaluation/metrics.py are printed as one JSON line.
+the ADD-S / ADD AUC and the RMSE metrics of evaluation/metrics.py are printed as one JSON line.  --score-on-device adds the
+ADD-S and ADD of the same frames on EVERY vertex of the mesh, computed on the GPU from the engine's device-side log
+(roft_engine_score_log: the estimates never leave the device).
 """
 import argparse
 import json
@@ -43,6 +45,8 @@ def main(argv=None):
                          "tools/dataset/dope_pose_finder/pose_finder.py reports for the 5 fps pose source")
     ap.add_argument("--init-pose", type=float, nargs=7, default=None, metavar=("X", "Y", "Z", "QW", "QX", "QY", "QZ"),
                     help="initial_condition.pose (default: the first valid detection)")
+    ap.add_argument("--score-on-device", action="store_true",
+                    help="also score the run on the object's full mesh with roft_engine_score_log (needs gt/poses.txt)")
     ap.add_argument("--from", dest="cfg_file", default=None, help="ROFT configuration file (libconfig), overrides as --a::b::c value")
     args, overrides = ap.parse_known_args(argv)
 
@@ -122,11 +126,16 @@ def main(argv=None):
         eng.submit([seq.frame(k)])
         eng.step()
     pose, twist, npts, sel = eng.get_log(0, n)
+    gt_path = os.path.join(args.root, "gt", "poses.txt")
+    device_scores = {}
+    if args.score_on_device and os.path.exists(gt_path) and n > 12:
+        g = io.read_poses(gt_path)[0][start + 12:start + n]
+        for kind in ("adi", "add"):
+            device_scores[kind] = eng.score_log(kind, 0, 12, len(g), g)
     eng.close()
     prefix = args.out if args.out is not None else os.path.join(args.root, "roft_mi355x_")
     io.write_estimate_logs(prefix, pose[:, 0], twist[:, 0])
     report = dict(frames=n, first_frame=start, logs=[prefix + "pose_estimate", prefix + "velocity_estimate"], flow_type=int(ftype), flow_grid=int(grid))
-    gt_path = os.path.join(args.root, "gt", "poses.txt")
     if os.path.exists(gt_path):
         gt, _ = io.read_poses(gt_path)
         est = np.concatenate([pose[:, 0, 6:9], pose[:, 0, 9:13]], 1)
@@ -136,6 +145,10 @@ def main(argv=None):
         report.update(adds_mm_mean=1e3 * float(dist.mean()), adds_auc=metrics.auc(dist),
                       rmse_position_cm=metrics.rmse_cartesian_3d(g[:, :3], est[12:, :3]),
                       rmse_orientation_deg=metrics.rmse_angular(g[:, 3:], est[12:, 3:]))
+        if device_scores:
+            report.update(full_mesh_points=int(len(verts)), adds_full_mesh_mm_mean=1e3 * float(device_scores["adi"].mean()),
+                          adds_full_mesh_auc=metrics.auc(device_scores["adi"]), add_full_mesh_mm_mean=1e3 * float(device_scores["add"].mean()),
+                          add_full_mesh_auc=metrics.auc(device_scores["add"]))
     print(json.dumps(report))
     return 0
 
