@@ -115,26 +115,27 @@ int wait_batch(roft_engine* e, int b, bool* waited)
 {
     if (waited) *waited = false;
     if (b < e->completed_batches || b >= e->batch_counter) return ROFT_OK;
+    BatchSlot& slot = e->slot_of(b);
     // (with the frame-granular hand-over a pose lane can end before the features kernel behind the velocity filter does)
-    if (e->vel_used[b % roft_engine::kBatchRing]) {
-        if (waited && hipEventQuery(e->ev_vel[b % roft_engine::kBatchRing]) == hipErrorNotReady) *waited = true;
+    if (slot.vel_used) {
+        if (waited && hipEventQuery(slot.ev_vel) == hipErrorNotReady) *waited = true;
         (void)hipGetLastError();
-        HIP_TRY(hipEventSynchronize(e->ev_vel[b % roft_engine::kBatchRing]));
+        HIP_TRY(hipEventSynchronize(slot.ev_vel));
     }
     // (... or before the features kernel behind the batch's mask frames does, which reads the batch's depth images)
-    if (e->feat_used[b % roft_engine::kBatchRing]) HIP_TRY(hipEventSynchronize(e->ev_feat[b % roft_engine::kBatchRing]));
+    if (slot.feat_used) HIP_TRY(hipEventSynchronize(slot.ev_feat));
     for (int l = 0; l < kNumLin; ++l)
-        if (e->done_used[b % roft_engine::kBatchRing][l]) {
-            if (waited && hipEventQuery(e->ev_done[b % roft_engine::kBatchRing][l]) == hipErrorNotReady) *waited = true;
+        if (slot.done_used[l]) {
+            if (waited && hipEventQuery(slot.ev_done[l]) == hipErrorNotReady) *waited = true;
             (void)hipGetLastError();   // (hipErrorNotReady is not an error of this call)
-            HIP_TRY(hipEventSynchronize(e->ev_done[b % roft_engine::kBatchRing][l]));
+            HIP_TRY(hipEventSynchronize(slot.ev_done[l]));
         }
     {
         roft_batch_trace& tr = e->trace[b % roft_engine::kTraceRing];
         if (tr.batch == b && tr.t_done_us == 0.0) tr.t_done_us = host_now_us();
     }
     e->completed_batches = b + 1;
-    e->completed_frames = e->batch_end_frame[b % roft_engine::kBatchRing];
+    e->completed_frames = slot.end_frame;
     return check_dev_error(e);
 }
 
@@ -436,15 +437,13 @@ bool alone_on_device(const StreamSet* mine)
 
 static int engine_setup(roft_engine* e, const roft_config* cfg)
 {
-    constexpr int R = roft_engine::kBatchRing;
+    e->knobs = knobs_from_env();
     // The image chains of batch b+1 do not depend on the pose chain of batch b (only the other way round, through
     // the twist ring and the mask planes), so the chains run on separate HIP streams, ordered by one event per batch
     // and edge.  ROFT_ONE_STREAM=1 serialises everything on one stream (debugging).
-    const char* one = getenv("ROFT_ONE_STREAM");
-    e->multi = !(one && one[0] == '1');
     const char* np = getenv("ROFT_NO_STREAM_PRIORITY");
     if (int rc = acquire_streams(cfg->device, !(np && np[0] == '1'), &e->streams)) return rc;
-    if (e->multi) {
+    if (e->multi()) {
         e->stream = e->streams->mask;
         e->vel_stream = e->streams->vel;
         for (int l = 0; l < kNumLin; ++l) e->pose_stream[l] = e->streams->pose[l];
@@ -452,11 +451,12 @@ static int engine_setup(roft_engine* e, const roft_config* cfg)
     } else {
         e->stream = e->pose_stream[0] = e->pose_stream[1] = e->vel_stream = e->up_stream = e->streams->mask;
     }
-    for (int i = 0; i < R; ++i) {
-        HIP_TRY(e->dctrl[i].ensure((size_t)cfg->max_objects * e->T_max, true));
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->stage[i]), sizeof(FrameCtrl) * cfg->max_objects * e->T_max));
-        for (hipEvent_t* ev : {&e->ev_up[i], &e->ev_ctrl[i], &e->ev_mask[i], &e->ev_part[i], &e->ev_prep[i], &e->ev_feat[i], &e->ev_vel[i], &e->ev_skf[i], &e->ev_done[i][0], &e->ev_done[i][1]})
-            HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+    for (BatchSlot& b : e->ring) {
+        HIP_TRY(b.dctrl.ensure((size_t)cfg->max_objects * e->T_max, true));
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b.stage), sizeof(FrameCtrl) * cfg->max_objects * e->T_max));
+        hipError_t err = hipSuccess;
+        b.each_event([&](hipEvent_t& ev) { if (err == hipSuccess) err = hipEventCreateWithFlags(&ev, hipEventDisableTiming); });
+        HIP_TRY(err);
     }
     DevFlowFmt ff;
     ff.type = cfg->flow_type;
@@ -488,26 +488,28 @@ static int engine_setup(roft_engine* e, const roft_config* cfg)
     // Nothing of a batch may happen for the first time inside a caller's timed region: every event of the batch ring has
     // completed one dispatch on the stream that will carry it (the first use of an event as a kernel's stop event takes a signal
     // from the runtime's pool -- a host call of its own kind), and every stream has queued a wait on an event and on a value.
-    if (e->multi) {
+    if (e->multi()) {
         int* flag = reinterpret_cast<int*>(e->arr.skf_started.p);   // (a word that stays 0 until the first batch; the probe kernel writes 1 ... reset below)
-        for (int i = 0; i < R; ++i) {
-            hipExtLaunchKernelGGL(probe_tiny_kernel, dim3(1), dim3(64), 0, e->stream, nullptr, e->ev_ctrl[i], 0, flag);
-            hipExtLaunchKernelGGL(probe_tiny_kernel, dim3(1), dim3(64), 0, e->stream, nullptr, e->ev_mask[i], 0, flag);
-            hipExtLaunchKernelGGL(probe_tiny_kernel, dim3(1), dim3(64), 0, e->stream, nullptr, e->ev_part[i], 0, flag);
-            HIP_TRY(hipStreamWaitEvent(e->vel_stream, e->ev_part[i], 0));
-            hipExtLaunchKernelGGL(probe_tiny_kernel, dim3(1), dim3(64), 0, e->stream, nullptr, e->ev_feat[i], 0, flag);
-            HIP_TRY(hipStreamWaitEvent(e->vel_stream, e->ev_mask[i], 0));
-            hipExtLaunchKernelGGL(probe_tiny_kernel, dim3(1), dim3(64), 0, e->vel_stream, nullptr, e->ev_vel[i], 0, flag);
-            hipExtLaunchKernelGGL(probe_tiny_kernel, dim3(1), dim3(64), 0, e->vel_stream, nullptr, e->ev_skf[i], 0, flag);
-            HIP_TRY(hipStreamWaitEvent(e->pose_stream[i & 1], e->ev_skf[i], 0));
+        auto signal = [&](hipStream_t q, hipEvent_t ev) { hipExtLaunchKernelGGL(probe_tiny_kernel, dim3(1), dim3(64), 0, q, nullptr, ev, 0, flag); };
+        for (int i = 0; i < roft_engine::kBatchRing; ++i) {
+            BatchSlot& b = e->ring[i];
+            signal(e->stream, b.ev_ctrl);
+            signal(e->stream, b.ev_mask);
+            signal(e->stream, b.ev_part);
+            HIP_TRY(hipStreamWaitEvent(e->vel_stream, b.ev_part, 0));
+            signal(e->stream, b.ev_feat);
+            HIP_TRY(hipStreamWaitEvent(e->vel_stream, b.ev_mask, 0));
+            signal(e->vel_stream, b.ev_vel);
+            signal(e->vel_stream, b.ev_skf);
+            HIP_TRY(hipStreamWaitEvent(e->pose_stream[i & 1], b.ev_skf, 0));
             for (int l = 0; l < kNumLin; ++l) {
-                HIP_TRY(hipStreamWaitEvent(e->pose_stream[l], (i & 1) ? e->ev_vel[i] : e->ev_ctrl[i], 0));
-                hipExtLaunchKernelGGL(probe_tiny_kernel, dim3(1), dim3(64), 0, e->pose_stream[l], nullptr, e->ev_done[i][l], 0, flag);
+                HIP_TRY(hipStreamWaitEvent(e->pose_stream[l], (i & 1) ? b.ev_vel : b.ev_ctrl, 0));
+                signal(e->pose_stream[l], b.ev_done[l]);
             }
-            HIP_TRY(hipEventRecord(e->ev_up[i], e->up_stream));
-            HIP_TRY(hipStreamWaitEvent(e->up_stream, e->ev_mask[i], 0));
-            hipExtLaunchKernelGGL(probe_tiny_kernel, dim3(1), dim3(64), 0, e->up_stream, nullptr, e->ev_prep[i], 0, flag);
-            HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_prep[i], 0));
+            HIP_TRY(hipEventRecord(b.ev_up, e->up_stream));
+            HIP_TRY(hipStreamWaitEvent(e->up_stream, b.ev_mask, 0));
+            signal(e->up_stream, b.ev_prep);
+            HIP_TRY(hipStreamWaitEvent(e->stream, b.ev_prep, 0));
         }
         HIP_TRY(hipGetLastError());
         for (hipStream_t q : {e->stream, e->vel_stream, e->pose_stream[0], e->pose_stream[1], e->up_stream}) HIP_TRY(hipStreamSynchronize(q));
@@ -517,17 +519,7 @@ static int engine_setup(roft_engine* e, const roft_config* cfg)
                 HIP_TRY(hipStreamWaitValue64(e->pose_stream[l], e->arr.skf_started.p, 0ull, hipStreamWaitValueGte, ~0ull));   // (satisfied at once)
         for (int l = 0; l < kNumLin; ++l) HIP_TRY(hipStreamSynchronize(e->pose_stream[l]));
     }
-    if (const char* hm = getenv("ROFT_HANDOFF")) e->handoff_mode = atoi(hm);
-    if (const char* pm = getenv("ROFT_PREP_AHEAD")) e->prep_mode = atoi(pm);
-    if (const char* pm = getenv("ROFT_MASK_PART_GATE")) e->part_mode = atoi(pm);
-    if (const char* pm = getenv("ROFT_FEAT_ON_MASK")) e->feat_mask_mode = atoi(pm);
-    if (const char* pm = getenv("ROFT_LANES_WAIT_SKF")) e->lanes_wait_skf = atoi(pm);
-    // A tool that lets only ONE kernel run at a time (rocprofv3 --pmc: counter collection serialises the dispatches) cannot run a
-    // lane next to the velocity filter it waits for -- the runtime's stream-wait itself is a kernel that spins: off under it.
-    else if (getenv("ROCPROF_COUNTER_COLLECTION")) e->handoff_mode = 0;
     e->feat_batch.assign((size_t)cfg->max_objects * kFeatRing, -1);
-    const char* hpf = getenv("ROFT_HOST_PROF");
-    e->host_prof = hpf && hpf[0] == '1';
     return ROFT_OK;
 }
 
@@ -584,20 +576,18 @@ int roft_engine_create(const roft_config* cfg, roft_engine** out)
 int roft_engine_destroy(roft_engine* e)
 {
     if (!e) return ROFT_OK;
-    constexpr int R = roft_engine::kBatchRing;
     (void)hipSetDevice(e->cfg.device);
-    if (e->host_prof && e->hp_batches > 0) {
+    if (e->knobs.host_prof && e->hp_batches > 0) {
         static const char* names[7] = {"submit: wait in-flight bound", "submit: frame programs + uploads", "submit: wait uploads",
                                        "step: FrameCtrl upload", "step: mask chain", "step: velocity chain", "step: pose chain"};
         for (int i = 0; i < 7; ++i) std::fprintf(stderr, "[roft host] %-36s %7.2f us/batch\n", names[i], e->hp_acc[i] / e->hp_batches);
     }
     for (hipStream_t s : {e->stream, e->vel_stream, e->pose_stream[0], e->pose_stream[1], e->up_stream})
         if (s) (void)hipStreamSynchronize(s);
-    for (int i = 0; i < R; ++i) {
-        for (hipEvent_t ev : {e->ev_up[i], e->ev_ctrl[i], e->ev_mask[i], e->ev_part[i], e->ev_prep[i], e->ev_feat[i], e->ev_vel[i], e->ev_skf[i], e->ev_done[i][0], e->ev_done[i][1]})
-            if (ev) (void)hipEventDestroy(ev);
-        if (e->stage[i]) (void)hipHostFree(e->stage[i]);
-        if (e->gather_tab[i]) (void)hipHostFree(e->gather_tab[i]);
+    for (BatchSlot& b : e->ring) {
+        b.each_event([](hipEvent_t& ev) { if (ev) (void)hipEventDestroy(ev); });
+        if (b.stage) (void)hipHostFree(b.stage);
+        if (b.gather_tab) (void)hipHostFree(b.gather_tab);
     }
     release_streams(e->streams);   // (idle: synchronised above)
     for (auto* o : e->objs) delete o;

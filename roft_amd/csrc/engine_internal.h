@@ -4,7 +4,9 @@
 //
 //   engine.hip          error string, pinned host pool, defaults, stream sets, roft_engine_create / destroy, roft_object_add
 //   engine_submit.hip   roft_frames_submit: the frame programs (build_pose_program), HOST staging, the control blocks of a batch
-//   engine_step.hip     roft_step / roft_sync: the four-stream launch graph of a batch (step_batch) and its timing marks
+//   batch_plan.h        SchedKnobs (the engine's switches, read at creation) and plan_batch: what a batch's launch graph will be, decided
+//                       from counters before anything is enqueued (host-only C++, tested without a GPU)
+//   engine_step.hip     roft_step / roft_sync: step_batch enqueues a BatchPlan on the engine's four streams; the timing marks
 //   engine_results.hip  state, outputs, log, masks, timing and batch-trace readers
 //   engine_ops.hip      the operator-level entry points (one-object context: roft_flow_measurement ... roft_outlier_test, roft_pose_errors)
 //   engine_debug.hip    roft_debug_* (diagnostics and experiments)
@@ -27,6 +29,9 @@
 
 #include "roft_device.h"
 #include "mesh_class.h"
+#include "batch_plan.h"
+
+static_assert(roft::host::kPlanLanes == roft::kNumLin, "batch_plan.h plans for the engine's pose lanes");
 
 
 namespace roft {
@@ -304,6 +309,28 @@ struct GatherItem { const void* src; void* dst; size_t bytes; };   // one small 
 constexpr int kGatherCap = 8192;                                    // items per batch (8 frames x 1024 objects)
 constexpr size_t kGatherMaxBytes = (size_t)2 << 20;                 // larger images go through the copy engine
 
+// What one batch in flight owns: a slot of the batch ring.
+struct BatchSlot {
+    hipEvent_t ev_up = nullptr;     // uploads of the batch on the device
+    hipEvent_t ev_ctrl = nullptr;   // FrameCtrl blocks of the batch on the device (and the mask chain of the batch before)
+    hipEvent_t ev_mask = nullptr;   // mask chain kernel of the batch complete
+    hipEvent_t ev_part = nullptr;   // the masks of the batch's frames 0 .. T - 2 complete (what its flow measurements read)
+    hipEvent_t ev_prep = nullptr;   // control blocks + ingested masks of the batch on the device (prepared on the upload stream)
+    hipEvent_t ev_feat = nullptr;   // features of the batch complete (a feature kernel on the mask stream)
+    hipEvent_t ev_vel = nullptr;    // the batch's velocity chain complete (velocity filter AND the feature kernel behind it)
+    hipEvent_t ev_skf = nullptr;    // twists of the batch complete (the velocity filter alone: what a pose lane waits for)
+    hipEvent_t ev_done[kNumLin] = {nullptr, nullptr};   // pose chain of the batch complete (per lane)
+    template <class F> void each_event(F&& f) { for (hipEvent_t* ev : {&ev_up, &ev_ctrl, &ev_mask, &ev_part, &ev_prep, &ev_feat, &ev_vel, &ev_skf, &ev_done[0], &ev_done[1]}) f(*ev); }
+    DevBuf<FrameCtrl> dctrl;             // control blocks on the device
+    FrameCtrl* stage = nullptr;          // ... and their pinned staging block
+    GatherItem* gather_tab = nullptr;    // pinned table gather_copy_kernel reads (kGatherCap entries; allocated on first use)
+    // written by step_batch for wait_batch: which of the events the batch signals
+    bool done_used[kNumLin] = {false, false};   // the lane had work
+    bool vel_used = false;               // the velocity chain ended with ev_vel
+    bool feat_used = false;              // a feature kernel ran on the mask stream and ended with ev_feat
+    int end_frame = 0;                   // frame counter behind the batch
+};
+
 struct roft_engine {
     roft_config cfg{};
     Arrays arr;
@@ -325,25 +352,14 @@ struct roft_engine {
     int lead = 6;         // batches
     int hist_cap = 6;     // flows kept per object
     int retain = ROFT_RETAIN_FRAMES;
-    DevBuf<FrameCtrl> dctrl[kBatchRing];
-    FrameCtrl* stage[kBatchRing] = {};     // pinned staging blocks
     // Small HOST images in PINNED memory (the per-object masks of a delivery: 64 buffers of 300 KB) are not copied one
     // hipMemcpyAsync each but fetched by ONE kernel over the bus (engine_submit.hip, gather_copy_kernel): what to fetch, per batch
     std::vector<GatherItem> gather;                    // collected by stage_host during a submit
-    GatherItem* gather_tab[kBatchRing] = {};           // pinned tables the kernel reads (kGatherCap entries each; allocated on first use)
-    hipEvent_t ev_up[kBatchRing] = {};     // uploads of the batch on the device
-    hipEvent_t ev_ctrl[kBatchRing] = {};   // FrameCtrl blocks of the batch on the device (and the mask chain of the batch before)
-    hipEvent_t ev_mask[kBatchRing] = {};   // mask chain kernel of the batch complete
-    hipEvent_t ev_part[kBatchRing] = {};   // the masks of the batch's frames 0 .. T - 2 complete (what its flow measurements read)
-    hipEvent_t ev_prep[kBatchRing] = {};   // control blocks + ingested masks of the batch on the device (prepared on the upload stream)
-    hipEvent_t ev_feat[kBatchRing] = {};   // features of the batch complete
-    hipEvent_t ev_vel[kBatchRing] = {};    // the batch's velocity chain complete (velocity filter AND the feature kernel behind it)
-    hipEvent_t ev_skf[kBatchRing] = {};    // twists of the batch complete (the velocity filter alone: what a pose lane waits for)
-    hipEvent_t ev_done[kBatchRing][kNumLin] = {};   // pose chain of the batch complete (per lane)
-    bool done_used[kBatchRing][kNumLin] = {};       // ... the lane had work in that batch
-    bool multi = false;
+    BatchSlot ring[kBatchRing];                        // batch b lives in ring[b % kBatchRing]
+    BatchSlot& slot_of(int b) { return ring[b % kBatchRing]; }
+    SchedKnobs knobs;                                  // the switches, read when the engine is created
+    bool multi() const { return !knobs.one_stream; }
     // ROFT_HOST_PROF=1: host time of the sections of the submit call / roft_step, printed by roft_engine_destroy
-    bool host_prof = false;
     double hp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     long hp_batches = 0;
     std::vector<HostObject*> objs;
@@ -368,35 +384,20 @@ struct roft_engine {
     int prev_T = 0;                 // frames of the batch stepped before
     int batch_counter = 0, frame_counter = 0;
     int completed_batches = 0, completed_frames = 0;
-    int batch_end_frame[kBatchRing] = {};
     roft_engine_stats stats{};
     bool device_pointers_checked = false;   // ROFT_MEM_DEVICE inputs are looked up once, on the first submit
     bool throttled = false;   // MEASURED, diagnostics only (roft_batch_trace): the submit of the current batch had to wait for the in-flight bound
-    // Scheduling mode of a batch, a function of the batch INDEX alone (round 5; rounds 3 - 4 keyed it on `throttled`, a host
-    // timing, so that the launch graph itself differed from run to run): a batch is "steady" when at least `lead` batches have
-    // been stepped since the engine was last idle (creation, roft_sync and everything that calls it), i.e. from the batch on
-    // whose submit call may have to wait for the in-flight bound.  Bursts (fewer batches between two syncs) favour latency:
-    // lanes released early, outlier tests on all the CUs to spare; steady batches favour occupancy.
+    // A batch is "steady" when at least `lead` batches have been stepped since the engine was last idle (creation, roft_sync and
+    // everything that calls it), a burst otherwise: plan_batch.
     int idle_mark = 0;        // batch_counter when the engine was last known idle
-    bool steady = false;      // mode of the batch being stepped
-    bool alone_on_device = true;   // no other engine of this process holds a stream set on the device (asked at every submit: a count, not a timing)
+    bool alone_on_device = true;   // no other engine of this process holds a stream set on the device (asked by a plan that would release a lane early: a count, not a timing)
     bool wait_value_ok = true;     // hipDeviceAttributeCanUseStreamWaitValue
     // trace of the last kTraceRing batches (roft_engine_get_batch_trace)
     static constexpr int kTraceRing = 64;
     roft_batch_trace trace[kTraceRing] = {};
     double cur_submit_t0 = 0.0, cur_submit_us = 0.0, cur_wait_us = 0.0;
-    // Frame-granular hand-over velocity filter -> pose lanes (EngineArrays::handoff).  handoff_mode: 0 never, 1 while the host is
-    // not throttled by the in-flight bound (bursts: the pipeline is filling or draining and latency is what counts), 2 always.
-    int handoff_mode = 1;
-    // ROFT_PREP_AHEAD / ROFT_MASK_PART_GATE, read when the engine is created: 0 never, 1 the default rule (a function of batch index
-    // and object count: step_batch), 2 always, 3 whenever the batch index allows it whatever the object count.  No setting changes a result.
-    int prep_mode = 1, part_mode = 1;
-    int feat_mask_mode = 1;     // features kernel on the mask stream: 0 never, 1 at most one object per sixteen CUs, 2 always (ROFT_FEAT_ON_MASK)
-    int lanes_wait_skf = 1;     // pose lanes without hand-over wait for the velocity filter's own event (ROFT_LANES_WAIT_SKF=0: for the features too)
     bool feat_dep_in_batch = false;        // an outlier test of the batch reads features buffered by a frame of the same batch
     unsigned long long skf_total = 0;      // velocity-filter workgroups launched so far (the value the lanes' gates wait for)
-    bool vel_used[kBatchRing] = {};        // the batch's velocity chain ended with ev_vel (wait_batch waits for it as well)
-    bool feat_used[kBatchRing] = {};       // the batch's feature kernel ran on the mask stream and ended with ev_feat (wait_batch waits for it as well)
     std::vector<int> feat_batch;           // [objects][kFeatRing] batch that last wrote each feature set (-1: none)
     // timing
     bool timing = false;
@@ -423,7 +424,7 @@ inline double host_now_us()
 {
     return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
-#define HP_MARK(e, slot, t) do { if ((e)->host_prof) { const double _n = host_now_us(); (e)->hp_acc[slot] += _n - (t); (t) = _n; } } while (0)
+#define HP_MARK(e, slot, t) do { if ((e)->knobs.host_prof) { const double _n = host_now_us(); (e)->hp_acc[slot] += _n - (t); (t) = _n; } } while (0)
 
 
 }  // namespace host

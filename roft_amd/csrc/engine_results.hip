@@ -21,7 +21,7 @@ int roft_get_state(roft_engine* e, int id, double pose13[13], double P12[144], d
     constexpr size_t kHead = offsetof(ObjState, belief) + kNumLin * sizeof(PoseBelief);
     if (!e->state_host) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->state_host), sizeof(ObjState)));
     const int lin = e->objs[id]->stepped_slot;
-    hipStream_t last = e->multi ? e->pose_stream[e->objs[id]->stepped_lane] : e->stream;
+    hipStream_t last = e->multi() ? e->pose_stream[e->objs[id]->stepped_lane] : e->stream;
     HIP_TRY(hipMemcpyAsync(e->state_host, e->arr.state.p + id, kHead, hipMemcpyDeviceToHost, last));
     if (int rc = roft_sync(e)) return rc;
     const ObjState* st = e->state_host;

@@ -150,14 +150,14 @@ __global__ __launch_bounds__(256) void gather_copy_kernel(const GatherItem* __re
 static int flush_gather(roft_engine* e)
 {
     if (e->gather.empty()) return ROFT_OK;
-    const int slot = e->batch_counter % roft_engine::kBatchRing;
-    if (!e->gather_tab[slot]) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->gather_tab[slot]), sizeof(GatherItem) * kGatherCap, hipHostMallocMapped));
+    GatherItem*& tab = e->slot_of(e->batch_counter).gather_tab;
+    if (!tab) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&tab), sizeof(GatherItem) * kGatherCap, hipHostMallocMapped));
     const size_t n = e->gather.size();
-    std::memcpy(e->gather_tab[slot], e->gather.data(), sizeof(GatherItem) * n);
+    std::memcpy(tab, e->gather.data(), sizeof(GatherItem) * n);
     size_t largest = 0;
     for (const GatherItem& g : e->gather) largest = std::max(largest, g.bytes);
     const unsigned gx = (unsigned)std::max<size_t>(1, std::min<size_t>(32, (largest / 16 + 2047) / 2048));   // ~8 units per thread
-    hipLaunchKernelGGL(gather_copy_kernel, dim3(gx, (unsigned)n), dim3(256), 0, e->up_stream, e->gather_tab[slot]);
+    hipLaunchKernelGGL(gather_copy_kernel, dim3(gx, (unsigned)n), dim3(256), 0, e->up_stream, tab);
     e->gather.clear();
     if (hipError_t le = hipGetLastError()) return fail(ROFT_ERR_DEVICE, std::string("gather copy of HOST inputs: ") + hipGetErrorString(le));
     e->stats.h2d_copies++;
@@ -183,9 +183,8 @@ static int stage_host(roft_engine* e, int frame, const void* host, size_t bytes,
         if (pr.first == host) { *dev = pr.second; return ROFT_OK; }
     unsigned char* d = nullptr;
     if (int rc = stage_alloc(e, frame, bytes, &d)) return rc;
-    static const int gather_env = getenv("ROFT_GATHER_COPY") ? atoi(getenv("ROFT_GATHER_COPY")) : 1;   // (experiments: 0 = one copy per image)
     const void* dp = nullptr;
-    if (gather_env && bytes <= kGatherMaxBytes && (bytes & 15) == 0 && (reinterpret_cast<uintptr_t>(host) & 15) == 0 &&
+    if (e->knobs.gather_copy && bytes <= kGatherMaxBytes && (bytes & 15) == 0 && (reinterpret_cast<uintptr_t>(host) & 15) == 0 &&
         (int)e->gather.size() < kGatherCap && (dp = pinned_device_pointer(host)) != nullptr) {
         e->gather.push_back(GatherItem{dp, d, bytes});   // fetched by flush_gather's one launch
         e->stats.h2d_bytes += (long long)bytes;
@@ -257,7 +256,7 @@ static int submit_frames(roft_engine* e, const roft_frame_input* inputs, int n_o
     const size_t npix = (size_t)cfg.cam.width * cfg.cam.height;
     const size_t fbytes = flow_bytes(e->arr.a.ffmt);
     const int b = e->batch_counter;
-    FrameCtrl* blk = e->stage[b % roft_engine::kBatchRing];
+    FrameCtrl* blk = e->slot_of(b).stage;
     int max_outliers[kNumLin] = {0, 0};
     std::vector<int> n_outliers((size_t)n_obj * kNumLin, 0);
     e->lin_any[0] = e->lin_any[1] = false;
@@ -472,7 +471,7 @@ int roft_frames_submit(roft_engine* e, const roft_frame_input* inputs, int n_obj
     if (n_frames < 1 || n_frames > e->T_max) return fail(ROFT_ERR_INVALID, "n_frames must be 1 .. roft_config::max_batch_frames");
     if (e->submitted) return fail(ROFT_ERR_STATE, "previous batch not stepped yet");
     HIP_TRY(hipSetDevice(e->cfg.device));
-    double hp_t = e->host_prof ? host_now_us() : 0.0;
+    double hp_t = e->knobs.host_prof ? host_now_us() : 0.0;
     e->cur_submit_t0 = host_now_us();
     // bound the batches in flight (see roft_engine::lead); this also frees the batch ring slot
     if (int rc = wait_batch(e, e->batch_counter - e->lead, &e->throttled)) return rc;
@@ -492,9 +491,9 @@ int roft_frames_submit(roft_engine* e, const roft_frame_input* inputs, int n_obj
     int rc2 = ROFT_OK;
     if (e->had_uploads) {
         // HOST buffers belong to the caller again when this call returns
-        const int slot = e->batch_counter % roft_engine::kBatchRing;
-        hipError_t err = hipEventRecord(e->ev_up[slot], e->up_stream);
-        if (err == hipSuccess) err = hipEventSynchronize(e->ev_up[slot]);
+        const hipEvent_t ev_up = e->slot_of(e->batch_counter).ev_up;
+        hipError_t err = hipEventRecord(ev_up, e->up_stream);
+        if (err == hipSuccess) err = hipEventSynchronize(ev_up);
         if (err != hipSuccess) rc2 = fail(ROFT_ERR_DEVICE, std::string("input upload: ") + hipGetErrorString(err));
     }
     HP_MARK(e, 2, hp_t);

@@ -483,6 +483,46 @@ def test_lanes_are_released_early_only_by_the_only_engine_of_the_device():
         assert np.array_equal(x, y)
 
 
+def test_every_engine_reads_its_switches_when_it_is_created(monkeypatch):
+    """ROFT_EARLY_LANES, ROFT_CTRL_INGEST and ROFT_OUTLIER_STEADY_DIV belong to the engine (SchedKnobs, batch_plan.h), like the other
+    debugging switches: an engine created while they are set obeys them, the next one created without them does not -- whatever
+    engines this process has run before.  The batch trace shows each: no lane released early; control blocks and mask ingest in two
+    launches (a 6-frame batch of these streams delivers masks in one frame, which the single launch never declines), so no batch
+    has fewer launches and the run has more; no steady batch with a divided band count -- `outlier_parts_halved` reports what
+    was launched.  No switch changes a result."""
+    n = 60
+    streams = [util.to_device(util.stream(570 + i, n, scale=2, device="cuda")) for i in range(3)]
+
+    def run():
+        eng = make_engine(streams, max_batch_frames=6)
+        eng.enable_log(n)
+        for k0 in range(0, n, 6):
+            eng.submit_batch([[util.device_frame(st, k0 + j) for st in streams] for j in range(6)])
+            eng.step()
+        log, tr = eng.get_log(0, n), eng.batch_trace()
+        eng.close()
+        return log, tr
+
+    keys = ("steady", "handoff", "early_lanes", "outlier_parts_halved", "launches", "event_ops")
+    log_a, tr_a = run()
+    assert [b["outlier_parts_halved"] for b in tr_a] == [b["steady"] for b in tr_a] == [0] * 5 + [1] * 5
+    monkeypatch.setenv("ROFT_EARLY_LANES", "0")
+    monkeypatch.setenv("ROFT_CTRL_INGEST", "0")
+    monkeypatch.setenv("ROFT_OUTLIER_STEADY_DIV", "1")
+    log_b, tr_b = run()
+    monkeypatch.delenv("ROFT_EARLY_LANES")
+    monkeypatch.delenv("ROFT_CTRL_INGEST")
+    monkeypatch.delenv("ROFT_OUTLIER_STEADY_DIV")
+    log_c, tr_c = run()
+    assert not any(b["early_lanes"] for b in tr_b)
+    assert not any(b["outlier_parts_halved"] for b in tr_b) and [b["steady"] for b in tr_b] == [0] * 5 + [1] * 5
+    assert all(y["launches"] >= x["launches"] for x, y in zip(tr_a, tr_b))
+    assert sum(b["launches"] for b in tr_b) > sum(b["launches"] for b in tr_a)
+    assert [[b[k] for k in keys] for b in tr_c] == [[b[k] for k in keys] for b in tr_a]
+    for x, y, z in zip(log_a, log_b, log_c):
+        assert np.array_equal(x, y) and np.array_equal(x, z)
+
+
 def test_a_mesh_whose_triangles_point_outside_its_vertices_is_refused():
     """roft_object_add / roft_render_depth: the rasteriser indexes the vertex array with the triangles' entries -- an index outside
     of it is refused at the boundary (ROFT_ERR_INVALID with the triangle named), not read."""
