@@ -27,6 +27,8 @@
  *                                   src/roft-lib/src/ROFTFilter.cpp:553-577
  *        roft_outlier_test       <- ROFTFilter::pick_best_alternative  src/roft-lib/src/ROFTFilter.cpp:467-621
  *        roft_pose_errors        <- add / adi of tools/third_party/bop_pose_error.py:73-108 (the evaluation's ADD / ADD-S)
+ *        roft_render_scene       <- the evaluation's video / thumbnail renders: evaluation/results_renderer.py:591-778 over
+ *                                   tools/object_renderer/src/renderer.cpp (section 3b)
  *  (2) the batched engine -- ROFTFilter::filtering_step (src/roft-lib/src/ROFTFilter.cpp:255-452)
  *      for many objects at once with all filter state resident in HBM:
  *        roft_engine_create / roft_object_add / roft_frame_submit | roft_frames_submit / roft_step / roft_get_state.
@@ -480,6 +482,64 @@ int roft_flow_producer_run(roft_flow_producer* fp, const uint8_t* const* prev, c
 int roft_flow_producer_sync(roft_flow_producer* fp);
 void* roft_flow_producer_stream(roft_flow_producer* fp);
 
+/* ---- (3b) scene renderer: tracked poses drawn over the camera frames ----------------------------------------------
+ * The reference's evaluation draws the mesh at every estimated pose over the grayed camera frame (evaluation/results_renderer.py:
+ * 591-778 through tools/object_renderer/src/renderer.cpp).  This is that stage for many frames and several objects per frame:
+ * n_instances meshes per frame, each at its own pose, hiding each other; per pixel the nearest surface's eye-space depth, the
+ * instance and the triangle (in the caller's triangle order) it belongs to, and a flat-shaded overlay on the camera image.
+ *
+ * Geometry is the render contract (ROFT_RENDER_CONTRACT above, oracle/ro_render.c) at full resolution, operation for operation:
+ * the depth map of a scene is the per-pixel minimum of what roft_render_depth(mesh, x, q, cam, 1, ...) draws for its instances.
+ * Among equal depths the lower instance wins, then the lower triangle index.  The quaternion is used as given (not normalised),
+ * as in roft_pose_errors.  A pose with a non-finite component, or valid[...] == 0, draws nothing for that instance.
+ *
+ * Colour (float arithmetic, this operation order, no contraction): P_k = the triangle's corners in the camera frame as the contract
+ * computes them, n = (P1 - P0) x (P2 - P0), s = |n_z| / sqrt((n_x^2 + n_y^2) + n_z^2) (0 when the length is 0 or not finite: a head
+ * light, two-sided), level = ambient + (1 - ambient) s, per channel c = opacity (tint_c level) + (1 - opacity) background_c,
+ * out = (uint8) min(max(floorf(c + 0.5f), 0), 255).  The background is the camera image, RGB; with gray_background each pixel
+ * becomes (R 4899 + G 9617 + B 1868 + 8192) >> 14 in all three channels (the reference applies COLOR_RGB2GRAY to a BGR image,
+ * which swaps the weights of R and B; these are the weights of the channels as named).  No background: zeros.
+ *
+ * Determinism contract: the outputs of frame f are a function of that frame's poses, validity flags and background, of the meshes,
+ * the styles and the camera.  They do not depend on n_frames, on the frame's position in the call, on other frames, on
+ * window_pixels or on the run: every pixel is the minimum of a fixed set of 64-bit keys, whatever order they are produced in.
+ *
+ * Every buffer is host memory.  Without a HIP device: ROFT_ERR_INVALID for a bad argument, ROFT_ERR_DEVICE otherwise. */
+typedef struct {
+    float tint[3];  /* colour of the lit surface, 0..255 per channel (R, G, B) */
+    float opacity;  /* 0..1: weight of the surface over the background */
+    float ambient;  /* 0..1: level of a surface seen edge-on */
+} roft_scene_style;
+
+#define ROFT_SCENE_MAX_INSTANCES 256
+
+typedef struct {
+    int n_frames;            /* 0: nothing is done, ROFT_OK */
+    int n_instances;         /* 0 .. ROFT_SCENE_MAX_INSTANCES objects per frame (0: the background alone) */
+    const int* mesh_index;   /* [n_instances] index into the renderer's meshes */
+    const double* poses;     /* [n_frames][n_instances][7]: x y z, q = w x y z */
+    const uint8_t* valid;    /* [n_frames][n_instances], 0 = not drawn; NULL: all drawn */
+    const uint8_t* background; /* [background_frames][H][W][3] RGB, or NULL */
+    int background_frames;   /* n_frames, or 1: the same image under every frame */
+    int gray_background;     /* != 0: the background is converted to gray first */
+    const roft_scene_style* styles; /* [n_instances], or NULL: ambient 0.35, opacity 0.75, tint from a palette of eight by instance % 8 */
+    int window_pixels;       /* 0: the library's choice; > 0: at most this many pixels per on-chip window (tests: forces strips).  Changes no bit. */
+} roft_scene_desc;
+
+typedef struct roft_scene_renderer roft_scene_renderer;
+/* Uploads the meshes once, in the caller's order (each non-empty, fewer than 2^24 triangles).  Any width, height >= 1 with
+ * width * height < 2^24.  max_frames_per_call 1 .. 65536 sizes the resident buffers. */
+int roft_scene_renderer_create(const roft_camera* cam, const roft_mesh* meshes, int n_meshes, int max_frames_per_call, int device,
+                               roft_scene_renderer** out);
+int roft_scene_renderer_destroy(roft_scene_renderer* r);
+/* Any output may be NULL.  rgb_out [n_frames][H][W][3] u8; depth_out [n_frames][H][W] float, 0 = background;
+ * instance_out / triangle_out [n_frames][H][W] int32, -1 = background. */
+int roft_scene_render(roft_scene_renderer* r, const roft_scene_desc* desc, uint8_t* rgb_out, float* depth_out, int32_t* instance_out,
+                      int32_t* triangle_out);
+/* create + render + destroy on device 0 */
+int roft_render_scene(const roft_camera* cam, const roft_mesh* meshes, int n_meshes, const roft_scene_desc* desc, uint8_t* rgb_out,
+                      float* depth_out, int32_t* instance_out, int32_t* triangle_out);
+
 /* ---- (4) diagnostics (tests and profiling tools; not needed by an integration) --------------------------------- */
 /* The per-frame program builder without a device: the host-side mirror of CartesianQuaternionMeasurement::freeze's
  * Standard / PopBufferedMeasurement / RepeatOnlyVelocity state machine (cpp:92-348) and of the re-sync loop of
@@ -510,6 +570,9 @@ int roft_debug_get_residency(roft_engine* e, unsigned long long out[32]);
 int roft_debug_outlier_split(int mode);
 /* device time in milliseconds (HIP events) of the kernels of the calling process's last roft_pose_errors call, without its copies */
 int roft_debug_pose_errors_kernel_ms(double* ms_out);
+/* device time in milliseconds (HIP events) of the renderer's last roft_scene_render call, without its copies: ms_out[0] the visibility
+ * pass (with the clear of its key buffer), ms_out[1] the resolve pass */
+int roft_debug_scene_kernel_ms(roft_scene_renderer* r, double ms_out[2]);
 /* phase counters of one object's last kernels (only filled by libraries built with a -DROFT_*_PROFILE switch) */
 int roft_debug_get_dbg(roft_engine* e, int obj_id, long long out[32]);
 

@@ -93,6 +93,18 @@ class ObjectOutput(C.Structure):
                 ("outlier_selected", C.c_int), ("outlier_L", C.c_double * 2)]
 
 
+class SceneStyle(C.Structure):
+    _fields_ = [("tint", C.c_float * 3), ("opacity", C.c_float), ("ambient", C.c_float)]
+
+
+class SceneDesc(C.Structure):
+    _fields_ = [("n_frames", C.c_int), ("n_instances", C.c_int), ("mesh_index", C.c_void_p), ("poses", C.c_void_p),
+                ("valid", C.c_void_p), ("background", C.c_void_p), ("background_frames", C.c_int), ("gray_background", C.c_int),
+                ("styles", C.c_void_p), ("window_pixels", C.c_int)]
+
+
+SCENE_MAX_INSTANCES = 256   # ROFT_SCENE_MAX_INSTANCES
+
 # every symbol include/roft_engine.h declares
 ABI_SYMBOLS = [
     "roft_last_error_string", "roft_device_count", "roft_abi_version", "roft_flow_measurement", "roft_kf_predict",
@@ -107,10 +119,12 @@ ABI_SYMBOLS = [
     "roft_debug_plan", "roft_debug_get_dbg", "roft_debug_probe_streams", "roft_debug_sector_rate",
     "roft_host_alloc", "roft_host_free", "roft_host_is_pinned", "roft_debug_get_residency", "roft_debug_outlier_split",
     "roft_pose_errors", "roft_engine_score_log", "roft_debug_pose_errors_kernel_ms",
+    "roft_scene_renderer_create", "roft_scene_renderer_destroy", "roft_scene_render", "roft_render_scene", "roft_debug_scene_kernel_ms",
 ]
 POSE_ERROR_ADD, POSE_ERROR_ADDS = 0, 1   # ROFT_POSE_ERROR_*
 # entry points younger than ABI version 2 itself: a library built before them still loads through ROFT_LIB_SO
-NEWER_SYMBOLS = ("roft_pose_errors", "roft_engine_score_log")
+NEWER_SYMBOLS = ("roft_pose_errors", "roft_engine_score_log", "roft_scene_renderer_create", "roft_scene_renderer_destroy", "roft_scene_render",
+                 "roft_render_scene")
 
 
 def build(force=False):
@@ -201,6 +215,12 @@ def lib():
         L.roft_pose_errors.argtypes = [C.c_int, vp, C.c_int, vp, vp, C.c_int, vp]
         L.roft_engine_score_log.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp]
         L.roft_debug_pose_errors_kernel_ms.argtypes = [dp]
+    if hasattr(L, "roft_render_scene"):
+        L.roft_scene_renderer_create.argtypes = [C.POINTER(Camera), C.POINTER(Mesh), C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+        L.roft_scene_renderer_destroy.argtypes = [vp]
+        L.roft_scene_render.argtypes = [vp, C.POINTER(SceneDesc), vp, vp, vp, vp]
+        L.roft_render_scene.argtypes = [C.POINTER(Camera), C.POINTER(Mesh), C.c_int, C.POINTER(SceneDesc), vp, vp, vp, vp]
+        L.roft_debug_scene_kernel_ms.argtypes = [vp, dp]
     for name in ABI_SYMBOLS:
         if (name.startswith("roft_debug_") or name in NEWER_SYMBOLS) and not hasattr(L, name):
             continue   # (an older build loaded through ROFT_LIB_SO for an A/B run: diagnostics and the pose errors only; tests/test_abi_cpu.py checks the in-tree library has them all)

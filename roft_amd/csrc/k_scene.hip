@@ -1,0 +1,225 @@
+// k_scene.hip -- batched scene renderer (gfx950): the meshes of a scene drawn at the poses of many frames, several instances
+// per frame hiding each other, into per-pixel depth / instance / triangle maps and a flat-shaded overlay on the camera image.
+//
+// Reference (behaviour only): the evaluation's `video` and `thumbnail` heads, evaluation/results_renderer.py:591-778, and the
+// renderer they call, tools/object_renderer/src/renderer.cpp (the mesh at every estimated pose over the grayed camera frame).
+//
+// Two passes over a visibility buffer of 64-bit keys, one buffer per frame of the call (scene.h states the contract):
+//   scene_visibility_kernel   one workgroup per (frame, instance, part).  It projects the instance's vertices (kept in LDS
+//       when they fit), takes their pixel bounding box as the instance's window, and walks the window in strips of at most
+//       win_cap pixels: a strip is a window of keys in LDS, every thread draws triangles into it with raster_projected and an
+//       LDS 64-bit min, and the keys that were drawn are merged into the frame's buffer in memory with a 64-bit atomic min
+//       (global_atomic_umin_x2, a vector instruction).  The `parts` workgroups of an instance deal the strips out in turn.
+//   scene_resolve_kernel      streams the keys once, four pixels per thread, and writes the outputs that were asked for:
+//       16-byte stores for the maps, three dwords of RGB.  A covered pixel is shaded from its key: the winning triangle's
+//       corners are transformed again with the float pose the visibility pass left in the pose table.
+// Determinism: a pixel's key is the minimum over a set of fragments that depends on the frame's poses, flags and meshes only.
+// Which workgroup draws a fragment, in which strip, and when it reaches memory changes the order of the min operations and
+// nothing else; the resolve pass is a pure function of a pixel's key, its background pixel and the tables.  No other atomic
+// touches a pixel.
+#include "raster.h"
+#include "scene.h"
+
+namespace roft {
+
+// the eye-space point project_vertex divides: the same three expressions
+__device__ __forceinline__ void eye_vertex(const float* v, const ScenePose& P, float& X, float& Y, float& Z)
+{
+    X = ((P.R[0] * v[0] + P.R[1] * v[1]) + P.R[2] * v[2]) + P.t[0];
+    Y = ((P.R[3] * v[0] + P.R[4] * v[1]) + P.R[5] * v[2]) + P.t[1];
+    Z = ((P.R[6] * v[0] + P.R[7] * v[1]) + P.R[8] * v[2]) + P.t[2];
+}
+
+// grid: n_frames * n_instances * parts.  dynamic LDS: [3 * vcache_cap floats] | [win_cap keys]
+__global__ __launch_bounds__(kSceneThreads) void scene_visibility_kernel(SceneArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __shared__ int s_box[4];
+    __shared__ int s_behind;   // some vertex is not in front of the near plane: a closed mesh is then drawn whole too
+    const int tid = threadIdx.x;
+    const int part = (int)(blockIdx.x % (unsigned)a.parts), fi = (int)(blockIdx.x / (unsigned)a.parts);   // fi = frame * n_instances + instance
+    const int inst = fi % a.n_instances, frame = fi / a.n_instances;
+    if (a.valid && !a.valid[fi]) return;
+    const double* pose = a.poses + (size_t)fi * 7;
+    bool finite = true;
+    for (int i = 0; i < 7; ++i) finite = finite && (fabs(pose[i]) < INFINITY);   // (uniform over the workgroup)
+    if (!finite) return;   // draws nothing; its triangles would fail raster_projected's own tests one by one
+    const RenderPose P = make_pose(pose, pose + 3);
+    if (part == 0 && tid == 0) {
+        ScenePose& o = a.pose_table[fi];
+        for (int i = 0; i < 9; ++i) o.R[i] = P.R[i];
+        for (int i = 0; i < 3; ++i) o.t[i] = P.t[i];
+    }
+    const SceneMesh m = a.meshes[a.mesh_index[inst]];
+    const int nv = m.n_verts, nt = m.n_tris, W = a.W, H = a.H;
+    const bool cached = nv <= a.vcache_cap;
+    float* s_v = reinterpret_cast<float*>(smem);
+    uint64_t* s_k = reinterpret_cast<uint64_t*>(smem + (((size_t)a.vcache_cap * 12 + 15) & ~(size_t)15));
+    if (tid < 4) s_box[tid] = (tid < 2) ? INT32_MAX : -1;
+    if (tid == 0) s_behind = 0;
+    __syncthreads();
+    // vertices -> screen; pixel bounding box of the triangles that can be drawn (as outlier_fused_kernel takes it: the pixel
+    // ranges raster_projected clips to are monotone in the coordinates, so the box of the vertices covers every triangle)
+    {
+        int bi0 = INT32_MAX, bj0 = INT32_MAX, bi1 = -1, bj1 = -1;
+        bool behind = false;
+        for (int v = tid; v < nv; v += kSceneThreads) {
+            float sx, sy, z;
+            project_vertex(m.verts + (size_t)3 * v, P, a.fx, a.fy, a.cx, a.cy, sx, sy, z);
+            if (cached) { s_v[3 * v] = sx; s_v[3 * v + 1] = sy; s_v[3 * v + 2] = z; }
+            if (z > 0.001f) {
+                const float lo_i = fminf(fmaxf(ceilf(sx - 0.5f), 0.0f), (float)W), hi_i = fminf(fmaxf(floorf(sx - 0.5f), -1.0f), (float)(W - 1));
+                const float lo_j = fminf(fmaxf(ceilf(sy - 0.5f), 0.0f), (float)H), hi_j = fminf(fmaxf(floorf(sy - 0.5f), -1.0f), (float)(H - 1));
+                bi0 = min(bi0, (int)lo_i); bi1 = max(bi1, (int)hi_i);
+                bj0 = min(bj0, (int)lo_j); bj1 = max(bj1, (int)hi_j);
+            } else {
+                behind = true;
+            }
+        }
+        if (__any(behind) && (tid & 63) == 0) atomicOr(&s_behind, 1);
+        for (int off = 32; off > 0; off >>= 1) {
+            bi0 = min(bi0, __shfl_xor(bi0, off, 64)); bj0 = min(bj0, __shfl_xor(bj0, off, 64));
+            bi1 = max(bi1, __shfl_xor(bi1, off, 64)); bj1 = max(bj1, __shfl_xor(bj1, off, 64));
+        }
+        if ((tid & 63) == 0) {
+            atomicMin(&s_box[0], bi0); atomicMin(&s_box[1], bj0);
+            atomicMax(&s_box[2], bi1); atomicMax(&s_box[3], bj1);
+        }
+    }
+    __syncthreads();
+    const int i0 = min(s_box[0], W - 1), i1 = s_box[2], j0 = min(s_box[1], H - 1), j1 = s_box[3];
+    if (i1 < i0 || j1 < j0 || i0 < 0 || j0 < 0) return;   // nothing on the screen
+    // strips of the window: whole rows while a row fits the LDS window, else a row is cut into column runs as well
+    const int win_w = i1 - i0 + 1, cw = min(win_w, a.win_cap), rows = max(1, a.win_cap / cw);
+    const int n_cols = (win_w + cw - 1) / cw, n_rows = (j1 - j0 + rows) / rows;
+    const uint8_t* const flips = (m.flip && !s_behind) ? m.flip : nullptr;   // closed, all in front: the back-face rule applies
+    ROFT_LDS uint64_t* const zk = (ROFT_LDS uint64_t*)pin_lds(reinterpret_cast<uint32_t*>(s_k));
+    uint64_t* const keys = a.keys + (size_t)frame * W * H;
+    for (int strip = part; strip < n_cols * n_rows; strip += a.parts) {
+        const int is = i0 + (strip % n_cols) * cw, ie = min(i1, is + cw - 1);
+        const int js = j0 + (strip / n_cols) * rows, je = min(j1, js + rows - 1);
+        const int sw = ie - is + 1, npx = sw * (je - js + 1);   // <= win_cap
+        for (int i = tid; i < npx; i += kSceneThreads) s_k[i] = kSceneKeyEmpty;
+        __syncthreads();
+        for (int t = tid; t < nt; t += kSceneThreads) {
+            const int32_t* tri = m.tris + (size_t)3 * t;
+            const int v0 = tri[0], v1 = tri[1], v2 = tri[2];
+            const int cull = flips ? 1 + (int)flips[t] : 0;
+            float x0, y0, z0, x1, y1, z1, x2, y2, z2;
+            if (cached) {
+                x0 = s_v[3 * v0]; y0 = s_v[3 * v0 + 1]; z0 = s_v[3 * v0 + 2];
+                x1 = s_v[3 * v1]; y1 = s_v[3 * v1 + 1]; z1 = s_v[3 * v1 + 2];
+                x2 = s_v[3 * v2]; y2 = s_v[3 * v2 + 1]; z2 = s_v[3 * v2 + 2];
+            } else {
+                project_vertex(m.verts + (size_t)3 * v0, P, a.fx, a.fy, a.cx, a.cy, x0, y0, z0);
+                project_vertex(m.verts + (size_t)3 * v1, P, a.fx, a.fy, a.cx, a.cy, x1, y1, z1);
+                project_vertex(m.verts + (size_t)3 * v2, P, a.fx, a.fy, a.cx, a.cy, x2, y2, z2);
+            }
+            const uint64_t low = ((uint64_t)(uint32_t)inst << 24) | (uint32_t)t;
+            raster_projected(x0, y0, z0, x1, y1, z1, x2, y2, z2, W, H, js, je, cull, [zk, is, js, sw, low](int i, int j, float z) {
+                const unsigned ci = (unsigned)(i - is);
+                if (ci < (unsigned)sw)
+                    (void)__hip_atomic_fetch_min(zk + ((j - js) * sw + (int)ci), ((uint64_t)__float_as_uint(z) << 32) | low, __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_WORKGROUP);
+            });
+        }
+        __syncthreads();
+        // the strip's drawn keys -> the frame's buffer (other instances and other strips of this one merge into the same buffer)
+        for (int i = tid; i < npx; i += kSceneThreads) {
+            const uint64_t key = s_k[i];
+            if (key != kSceneKeyEmpty)
+                (void)__hip_atomic_fetch_min(keys + ((size_t)(js + i / sw) * W + (is + i % sw)), key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        __syncthreads();   // the next strip clears the window
+    }
+}
+
+// shade of the key's triangle: scene.h, operation by operation
+__device__ __forceinline__ float scene_shade(const SceneArgs& a, int frame, int inst, int tri_id)
+{
+    const SceneMesh& m = a.meshes[a.mesh_index[inst]];
+    const ScenePose& P = a.pose_table[(size_t)frame * a.n_instances + inst];
+    const int32_t* tri = m.tris + (size_t)3 * tri_id;
+    float p[3][3];
+    for (int k = 0; k < 3; ++k) eye_vertex(m.verts + (size_t)3 * tri[k], P, p[k][0], p[k][1], p[k][2]);
+    const float ax = p[1][0] - p[0][0], ay = p[1][1] - p[0][1], az = p[1][2] - p[0][2];
+    const float bx = p[2][0] - p[0][0], by = p[2][1] - p[0][1], bz = p[2][2] - p[0][2];
+    const float nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
+    const float len = sqrtf((nx * nx + ny * ny) + nz * nz);
+    return (len > 0.0f && len < INFINITY) ? fabsf(nz) / len : 0.0f;
+}
+
+__device__ __forceinline__ uint32_t scene_level(float c)
+{
+    return (uint32_t)fminf(fmaxf(floorf(c + 0.5f), 0.0f), 255.0f);
+}
+
+// grid: ceil(n_frames * W * H / (kResolvePixels * 256)); the pixels of the call as one flat array (a thread's four may span
+// two frames).  Every array is padded to a multiple of kResolvePixels pixels.
+__global__ __launch_bounds__(256) void scene_resolve_kernel(SceneArgs a)
+{
+    const size_t WH = (size_t)a.W * a.H, total = WH * a.n_frames;
+    const size_t g0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * kResolvePixels;
+    if (g0 >= total) return;
+    const ulonglong2 k01 = *reinterpret_cast<const ulonglong2*>(a.keys + g0), k23 = *reinterpret_cast<const ulonglong2*>(a.keys + g0 + 2);
+    const uint64_t key[kResolvePixels] = {k01.x, k01.y, k23.x, k23.y};
+    int frame = (int)(g0 / WH);
+    size_t p = g0 - (size_t)frame * WH;
+    float dep[kResolvePixels];
+    int ins[kResolvePixels], tri[kResolvePixels];
+    uint32_t bytes[3 * kResolvePixels];
+#pragma unroll
+    for (int k = 0; k < kResolvePixels; ++k) {
+        const bool in_range = g0 + k < total;
+        const uint32_t zb = (uint32_t)(key[k] >> 32);
+        const bool covered = in_range && zb < 0x7F800000u;   // (an infinite depth is background, as the contract's `z < +inf`)
+        dep[k] = covered ? __uint_as_float(zb) : 0.0f;
+        ins[k] = covered ? (int)((key[k] >> 24) & 0xFFu) : -1;
+        tri[k] = covered ? (int)(key[k] & 0xFFFFFFu) : -1;
+        if (a.rgb) {
+            uint32_t r = 0, g = 0, b = 0;
+            if (a.background && in_range) {
+                const uint8_t* px = a.background + ((a.background_frames == 1 ? 0 : (size_t)frame * WH) + p) * 3;
+                r = px[0]; g = px[1]; b = px[2];
+                if (a.gray_background) r = g = b = (r * 4899u + g * 9617u + b * 1868u + 8192u) >> 14;
+            }
+            if (covered) {
+                const SceneStyle st = a.styles[ins[k]];
+                const float s = scene_shade(a, frame, ins[k], tri[k]);
+                const float level = st.ambient + (1.0f - st.ambient) * s;
+                r = scene_level(st.opacity * (st.tint[0] * level) + (1.0f - st.opacity) * (float)r);
+                g = scene_level(st.opacity * (st.tint[1] * level) + (1.0f - st.opacity) * (float)g);
+                b = scene_level(st.opacity * (st.tint[2] * level) + (1.0f - st.opacity) * (float)b);
+            }
+            bytes[3 * k] = r; bytes[3 * k + 1] = g; bytes[3 * k + 2] = b;
+        }
+        if (++p == WH) { p = 0; ++frame; }
+    }
+    if (a.rgb) {
+        uint32_t* out = reinterpret_cast<uint32_t*>(a.rgb) + 3 * (g0 / kResolvePixels);
+#pragma unroll
+        for (int d = 0; d < 3; ++d)
+            out[d] = bytes[4 * d] | (bytes[4 * d + 1] << 8) | (bytes[4 * d + 2] << 16) | (bytes[4 * d + 3] << 24);
+    }
+    if (a.depth) *reinterpret_cast<float4*>(a.depth + g0) = make_float4(dep[0], dep[1], dep[2], dep[3]);
+    if (a.instance) *reinterpret_cast<int4*>(a.instance + g0) = make_int4(ins[0], ins[1], ins[2], ins[3]);
+    if (a.triangle) *reinterpret_cast<int4*>(a.triangle + g0) = make_int4(tri[0], tri[1], tri[2], tri[3]);
+}
+
+size_t scene_lds_budget() { return 160 * 1024 - 4096; }
+
+void launch_scene_visibility(const SceneArgs& a, size_t lds_bytes, hipStream_t s)
+{
+    (void)set_max_dynamic_lds(reinterpret_cast<const void*>(scene_visibility_kernel), (int)scene_lds_budget());
+    const size_t groups = (size_t)a.n_frames * a.n_instances * a.parts;
+    hipLaunchKernelGGL(scene_visibility_kernel, dim3((unsigned)groups), dim3(kSceneThreads), (uint32_t)lds_bytes, s, a);
+}
+
+void launch_scene_resolve(const SceneArgs& a, hipStream_t s)
+{
+    const size_t total = (size_t)a.W * a.H * a.n_frames;
+    const size_t threads = (total + kResolvePixels - 1) / kResolvePixels;
+    hipLaunchKernelGGL(scene_resolve_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, a);
+}
+
+}  // namespace roft

@@ -68,6 +68,7 @@ class ROFTFilterBatch:
         L.check(L.lib().roft_object_add(self._h, C.byref(desc), C.byref(oid)))
         self.n_objects += 1
         self._inputs = (L.FrameInput * self.n_objects)()
+        self._meshes = getattr(self, "_meshes", []) + [(verts, tris)]   # render_log draws them
         return oid.value
 
     def submit(self, frames):
@@ -216,6 +217,28 @@ class ROFTFilterBatch:
         L.check(L.lib().roft_engine_score_log(self._h, pose_error_kind(kind), obj, first, n, None if pts is None else pts.ctypes.data,
                                               0 if pts is None else pts.shape[0], ref.ctypes.data, out.ctypes.data))
         return out
+
+    def render_log(self, first_frame, n_frames, background=None, gray_background=True, styles=None, outputs=("rgb",),
+                   frames_per_call=16):
+        """The logged estimates of frames first_frame .. first_frame + n_frames - 1 drawn over the camera frames: get_log_rows
+        followed by ops.render_scene over the engine's own meshes, all objects in one scene (object o is instance o).
+        background: [H, W, 3] or [n_frames, H, W, 3] uint8 RGB, or None.  Returns the dict of ops.SceneRenderer.render."""
+        from .ops import SceneRenderer
+        rows = self.get_log_rows(first_frame, n_frames)
+        poses = np.ascontiguousarray(rows[:, :, 6:13])
+        bg = None if background is None else np.asarray(background, np.uint8)
+        per_frame = bg is not None and bg.ndim == 4 and bg.shape[0] != 1
+        renderer = SceneRenderer(self.cfg.cam, getattr(self, "_meshes", []), max_frames_per_call=min(max(n_frames, 1), frames_per_call),
+                                 device=self.cfg.device)
+        parts = []
+        try:
+            for k in range(0, n_frames, renderer.max_frames_per_call):
+                sl = slice(k, min(n_frames, k + renderer.max_frames_per_call))
+                parts.append(renderer.render(np.arange(self.n_objects), poses[sl], background=bg[sl] if per_frame else bg,
+                                             gray_background=gray_background, styles=styles, outputs=outputs))
+        finally:
+            renderer.close()
+        return {key: np.concatenate([p[key] for p in parts]) for key in outputs}
 
     def stream(self):
         return L.lib().roft_engine_stream(self._h)

@@ -11,6 +11,7 @@ Names follow the reference's classes (hsp-iit/roft `src/roft-lib`):
   depth_likelihood  <- ROFTFilter::pick_best_alternative (inner loop)
   optical_flow      <- ImageOpticalFlowNVOF::step_frame (the product contract; the algorithm is this project's own)
   pose_errors       <- add / adi of tools/third_party/bop_pose_error.py (the evaluation's ADD / ADD-S)
+  render_scene      <- the evaluation's video / thumbnail renders (evaluation/results_renderer.py, tools/object_renderer)
 All of them run on the GPU; none has a CPU fallback.
 """
 import ctypes as C
@@ -267,3 +268,120 @@ class FlowProducer:
             self.close()
         except Exception:
             pass
+
+
+# ---- scene renderer (roft_scene_renderer_*, roft_render_scene) --------------------------------------------------
+SCENE_OUTPUTS = ("rgb", "depth", "instance", "triangle")
+
+
+def _mesh_array(meshes):
+    """[(verts, tris), ...] -> (Mesh array, the arrays it points into)."""
+    keep = [(np.ascontiguousarray(v, np.float32).reshape(-1, 3), np.ascontiguousarray(t, np.int32).reshape(-1, 3)) for v, t in meshes]
+    arr = (L.Mesh * max(len(keep), 1))()
+    for k, (v, t) in enumerate(keep):
+        arr[k] = L.Mesh(v.ctypes.data, v.shape[0], t.ctypes.data, t.shape[0])
+    return arr, keep
+
+
+def _scene_desc(width, height, mesh_index, poses, valid, background, gray_background, styles, window_pixels):
+    """The description of a call and the arrays it points into.  poses [F, I, 7] (or [F, 7] with one instance)."""
+    mesh_index = np.ascontiguousarray(mesh_index, np.int32).reshape(-1)
+    n_inst = mesh_index.shape[0]
+    poses = _f64(poses)
+    poses = poses.reshape(-1, n_inst, 7) if n_inst else poses.reshape(poses.shape[0] if poses.ndim else 0, 0, 7)
+    n_frames = poses.shape[0]
+    d = L.SceneDesc()
+    d.n_frames, d.n_instances = n_frames, n_inst
+    d.mesh_index, d.poses = mesh_index.ctypes.data, poses.ctypes.data
+    keep = [mesh_index, poses]
+    if valid is not None:
+        valid = np.ascontiguousarray(np.asarray(valid) != 0, np.uint8).reshape(n_frames, n_inst)
+        d.valid = valid.ctypes.data
+        keep.append(valid)
+    if background is not None:
+        background = np.ascontiguousarray(background, np.uint8)
+        if background.ndim == 3:
+            background = background[None]
+        if background.shape[1:] != (height, width, 3) or background.shape[0] not in (1, n_frames):
+            raise ValueError("background must be [H, W, 3] or [n_frames, H, W, 3] uint8")
+        d.background, d.background_frames = background.ctypes.data, background.shape[0]
+        keep.append(background)
+    d.gray_background = 1 if gray_background else 0
+    if styles is not None:
+        if len(styles) != n_inst:
+            raise ValueError("one style per instance")
+        arr = (L.SceneStyle * max(n_inst, 1))()
+        for i, (tint, opacity, ambient) in enumerate(styles):
+            arr[i].tint[:] = [float(c) for c in tint]
+            arr[i].opacity, arr[i].ambient = float(opacity), float(ambient)
+        d.styles = C.cast(arr, C.c_void_p)
+        keep.append(arr)
+    d.window_pixels = int(window_pixels)
+    return d, keep
+
+
+def _scene_outputs(outputs, n_frames, height, width):
+    unknown = set(outputs) - set(SCENE_OUTPUTS)
+    if unknown:
+        raise ValueError("unknown outputs: %s" % sorted(unknown))
+    shape = (n_frames, height, width)
+    out = {}
+    if "rgb" in outputs:
+        out["rgb"] = np.zeros(shape + (3,), np.uint8)
+    if "depth" in outputs:
+        out["depth"] = np.zeros(shape, np.float32)
+    if "instance" in outputs:
+        out["instance"] = np.zeros(shape, np.int32)
+    if "triangle" in outputs:
+        out["triangle"] = np.zeros(shape, np.int32)
+    return out, [(_p(out[k]) if k in out else None) for k in SCENE_OUTPUTS]
+
+
+class SceneRenderer:
+    """Resident scene renderer (roft_scene_renderer_*): the meshes are uploaded once, `render` draws up to
+    max_frames_per_call frames per call.  cam: L.Camera; meshes: [(verts [n, 3], tris [m, 3]), ...]."""
+
+    def __init__(self, cam, meshes, max_frames_per_call=16, device=0):
+        self._h = C.c_void_p()
+        self.width, self.height, self.max_frames_per_call = cam.width, cam.height, int(max_frames_per_call)
+        arr, keep = _mesh_array(meshes)
+        L.check(L.lib().roft_scene_renderer_create(C.byref(cam), arr, len(keep), self.max_frames_per_call, device, C.byref(self._h)))
+
+    def render(self, mesh_index, poses, valid=None, background=None, gray_background=False, styles=None, window_pixels=0,
+               outputs=SCENE_OUTPUTS):
+        """mesh_index [I]; poses [F, I, 7] rows x y z, q = (w, x, y, z); valid [F, I] or None; background [H, W, 3] or [F, H, W, 3]
+        uint8 RGB or None; styles: one (tint rgb 0..255, opacity, ambient) per instance or None.  Returns a dict with the
+        requested outputs: rgb [F, H, W, 3] u8, depth [F, H, W] f32 (0 = background), instance / triangle [F, H, W] i32 (-1)."""
+        d, keep = _scene_desc(self.width, self.height, mesh_index, poses, valid, background, gray_background, styles, window_pixels)
+        out, ptrs = _scene_outputs(outputs, d.n_frames, self.height, self.width)
+        L.check(L.lib().roft_scene_render(self._h, C.byref(d), *ptrs))
+        del keep
+        return out
+
+    def kernel_ms(self):
+        """Device time (ms, HIP events) of the last render: (visibility pass, resolve pass), without the copies."""
+        ms = (C.c_double * 2)()
+        L.check(L.lib().roft_debug_scene_kernel_ms(self._h, ms))
+        return ms[0], ms[1]
+
+    def close(self):
+        if self._h:
+            L.lib().roft_scene_renderer_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def render_scene(cam, meshes, mesh_index, poses, valid=None, background=None, gray_background=False, styles=None, window_pixels=0,
+                 outputs=SCENE_OUTPUTS):
+    """One-shot roft_render_scene: SceneRenderer(cam, meshes).render(...) without a resident handle."""
+    arr, keep_m = _mesh_array(meshes)
+    d, keep = _scene_desc(cam.width, cam.height, mesh_index, poses, valid, background, gray_background, styles, window_pixels)
+    out, ptrs = _scene_outputs(outputs, d.n_frames, cam.height, cam.width)
+    L.check(L.lib().roft_render_scene(C.byref(cam), arr, len(keep_m), C.byref(d), *ptrs))
+    del keep, keep_m
+    return out

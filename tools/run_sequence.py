@@ -4,7 +4,7 @@ files (`pose_estimate`, `velocity_estimate`, ROFTFilter.cpp:386-394) -- what `te
 
   run_sequence.py --root DIR --object NAME --mesh model.obj [--flow-set nvof_1_slow] [--mask-set NAME]
                   [--pose-set dope] [--out PREFIX] [--compute-flow nvof1|nvof2] [--no-delay] [--init-pose x y z qw qx qy qz]
-                  [--start-at-first-detection] [--score-on-device]
+                  [--start-at-first-detection] [--score-on-device] [--render-overlay DIR]
                   [--from config_fast_ycb.cfg [--group::key value ...]]
 
 --from reads the filter parameters from one of the reference's configuration files (config/config_fast_ycb.cfg,
@@ -15,7 +15,8 @@ The camera comes from DIR/cam_K.json (width, height, fx, fy, cx, cy).  --compute
 on DIR/rgb (the MI355X replacement of the NVOF dumper) into DIR/optical_flow/<flow-set>.  With DIR/gt/poses.txt present
 the ADD-S / ADD AUC and the RMSE metrics of evaluation/metrics.py are printed as one JSON line.  --score-on-device adds the
 ADD-S and ADD of the same frames on EVERY vertex of the mesh, computed on the GPU from the engine's device-side log
-(roft_engine_score_log: the estimates never leave the device).
+(roft_engine_score_log: the estimates never leave the device).  --render-overlay DIR draws the estimate over the sequence's
+grayed RGB frames (DIR/<frame>.png) with tools/render_results.py once the logs are written.
 """
 import argparse
 import json
@@ -47,6 +48,8 @@ def main(argv=None):
                     help="initial_condition.pose (default: the first valid detection)")
     ap.add_argument("--score-on-device", action="store_true",
                     help="also score the run on the object's full mesh with roft_engine_score_log (needs gt/poses.txt)")
+    ap.add_argument("--render-overlay", default=None, metavar="DIR",
+                    help="after the run, draw the estimate over SEQ/rgb/<i>.png into DIR/<i>.png (tools/render_results.py)")
     ap.add_argument("--from", dest="cfg_file", default=None, help="ROFT configuration file (libconfig), overrides as --a::b::c value")
     args, overrides = ap.parse_known_args(argv)
 
@@ -149,6 +152,14 @@ def main(argv=None):
             report.update(full_mesh_points=int(len(verts)), adds_full_mesh_mm_mean=1e3 * float(device_scores["adi"].mean()),
                           adds_full_mesh_auc=metrics.auc(device_scores["adi"]), add_full_mesh_mm_mean=1e3 * float(device_scores["add"].mean()),
                           add_full_mesh_auc=metrics.auc(device_scores["add"]))
+    if args.render_overlay:
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        import render_results
+        rc = render_results.main(["--root", args.root, "--mesh", args.mesh, "--poses", prefix + "pose_estimate", "--out", args.render_overlay,
+                                  "--first-frame", str(start)])
+        if rc != 0:
+            return rc
+        report["overlay"] = args.render_overlay
     print(json.dumps(report))
     return 0
 
