@@ -357,6 +357,37 @@ int roft_object_add(roft_engine* e, const roft_object_desc* desc, int* obj_id);
 int roft_frame_submit(roft_engine* e, const roft_frame_input* inputs, int n_inputs);
 /* A batch of n_frames consecutive frames (1 .. roft_config::max_batch_frames): inputs[t * n_objects + obj]. */
 int roft_frames_submit(roft_engine* e, const roft_frame_input* inputs, int n_objects, int n_frames);
+
+/* Label-image masks: ONE segmentation image per camera frame (a network's output, YCB-Video's -label.png) instead of one H x W
+ * byte mask per object.  An object whose entry names a label image behaves, bit for bit, as if it had been handed the mask
+ * M(p) = (L(p) == label) ? 255 : 0 through roft_frame_input::mask: schedule, first-mask rule, the "new but empty mask is
+ * ignored" rule (ImageSegmentationOFAidedSource.hpp:186-198) when the value does not occur in the image, mask_stamp,
+ * propagation, features and the outlier test.
+ *  - Membership is EQUALITY with `label`, not a threshold: value 3 selects the pixels that are 3, not those >= 3.
+ *  - A label image gives every pixel to at most one value, so it cannot express OVERLAPPING instance masks (nor the
+ *    three-valued {0, 1, 255} masks): the per-object form, roft_frame_input::mask, remains for those.
+ * Two objects may name the same value, the objects of one frame may name different images, and objects with and without labels
+ * may be mixed within a frame.  HOST images are uploaded once per distinct host pointer and frame however many objects name them
+ * (roft_engine_stats counts them once); DEVICE images are read in place under the retention contract of roft_frame_input and
+ * must be 16-byte aligned.  The engine makes one pass over each distinct image of a delivering frame for all objects that name it.
+ * ROFT_ERR_INVALID, with nothing of the batch consumed: labels != NULL together with inputs[].mask != NULL; label 0 (background
+ * by convention); a label outside the type's range; an unknown label_type; a misaligned DEVICE image. */
+#define ROFT_LABEL_U8  1
+#define ROFT_LABEL_U16 2
+typedef struct {
+    const void* labels;  /* H x W label image (HOST or DEVICE like the frame's other images: inputs[].mem_kind),
+                            NULL: this object takes inputs[].mask as before */
+    int label_type;      /* ROFT_LABEL_* */
+    int label;           /* the object's pixels are those EQUAL to this value; 1 .. 255 / 65535 */
+} roft_label_mask;
+/* roft_frames_submit with masks taken from label images: labels[t * n_objects + obj], or labels == NULL (then exactly
+ * roft_frames_submit) */
+int roft_frames_submit_labels(roft_engine* e, const roft_frame_input* inputs, const roft_label_mask* labels, int n_objects, int n_frames);
+/* Stand-alone operator (tests, tools): the n masks {0, 255} (masks_out: n x H x W bytes, optional) and their pixel counts
+ * (counts_out: n ints, optional) of the values[0..n) in one HOST label image, by the engine's own ingest kernel.  Values may
+ * repeat and may be absent from the image (count 0, all-zero mask); 0 and values outside the type's range are refused. */
+int roft_labels_to_masks(const void* labels, int label_type, int W, int H, const int* values, int n, uint8_t* masks_out, int* counts_out);
+
 /* Enqueues every kernel of ROFTFilter::filtering_step for all objects and all submitted frames; returns without
  * waiting. */
 int roft_step(roft_engine* e);

@@ -76,6 +76,13 @@ class FrameInput(C.Structure):
                 ("mem_kind", C.c_int), ("stamp", C.c_double), ("mask_stamp", C.c_double)]
 
 
+LABEL_U8, LABEL_U16 = 1, 2          # ROFT_LABEL_*
+
+
+class LabelMask(C.Structure):
+    _fields_ = [("labels", C.c_void_p), ("label_type", C.c_int), ("label", C.c_int)]
+
+
 class EngineStats(C.Structure):
     _fields_ = [("frames", C.c_longlong), ("batches", C.c_longlong), ("launches", C.c_longlong),
                 ("event_ops", C.c_longlong), ("h2d_bytes", C.c_longlong), ("h2d_copies", C.c_longlong)]
@@ -120,11 +127,12 @@ ABI_SYMBOLS = [
     "roft_host_alloc", "roft_host_free", "roft_host_is_pinned", "roft_debug_get_residency", "roft_debug_outlier_split",
     "roft_pose_errors", "roft_engine_score_log", "roft_debug_pose_errors_kernel_ms",
     "roft_scene_renderer_create", "roft_scene_renderer_destroy", "roft_scene_render", "roft_render_scene", "roft_debug_scene_kernel_ms",
+    "roft_frames_submit_labels", "roft_labels_to_masks",
 ]
 POSE_ERROR_ADD, POSE_ERROR_ADDS = 0, 1   # ROFT_POSE_ERROR_*
 # entry points younger than ABI version 2 itself: a library built before them still loads through ROFT_LIB_SO
 NEWER_SYMBOLS = ("roft_pose_errors", "roft_engine_score_log", "roft_scene_renderer_create", "roft_scene_renderer_destroy", "roft_scene_render",
-                 "roft_render_scene")
+                 "roft_render_scene", "roft_frames_submit_labels", "roft_labels_to_masks")
 
 
 def build(force=False):
@@ -221,6 +229,9 @@ def lib():
         L.roft_scene_render.argtypes = [vp, C.POINTER(SceneDesc), vp, vp, vp, vp]
         L.roft_render_scene.argtypes = [C.POINTER(Camera), C.POINTER(Mesh), C.c_int, C.POINTER(SceneDesc), vp, vp, vp, vp]
         L.roft_debug_scene_kernel_ms.argtypes = [vp, dp]
+    if hasattr(L, "roft_frames_submit_labels"):
+        L.roft_frames_submit_labels.argtypes = [vp, C.POINTER(FrameInput), C.POINTER(LabelMask), C.c_int, C.c_int]
+        L.roft_labels_to_masks.argtypes = [vp, C.c_int, C.c_int, C.c_int, ip, C.c_int, vp, ip]
     for name in ABI_SYMBOLS:
         if (name.startswith("roft_debug_") or name in NEWER_SYMBOLS) and not hasattr(L, name):
             continue   # (an older build loaded through ROFT_LIB_SO for an A/B run: diagnostics and the pose errors only; tests/test_abi_cpu.py checks the in-tree library has them all)

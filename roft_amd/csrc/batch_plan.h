@@ -64,7 +64,8 @@ struct PlanInputs {
     int batch_counter = 0, idle_mark = 0, lead = 6, completed_batches = 0;
     // what the submit left
     bool had_uploads = false;
-    unsigned new_mask_frames = 0;
+    unsigned new_mask_frames = 0;   // bit t: frame t delivers a per-object byte mask (what the ingest of the control-block launch converts)
+    int label_sets = 0;             // distinct (frame, label image) pairs of the batch: masks delivered as label images
     bool any_feat = false, any_feat_now = false, feat_dep_in_batch = false;
     int n_segments[kPlanLanes] = {1, 1};
     bool lin_any[kPlanLanes] = {false, false};
@@ -114,6 +115,7 @@ struct BatchPlan {
     bool prep_waits_mask = false, prep_waits_feat = false;   // ... behind ev_mask (and ev_feat) of batch b - 2
     bool wait_up = false;       // the mask stream waits for ev_up
     bool try_fused = false;     // control blocks + ingest in one launch, if the launcher accepts
+    bool label_ingest = false;  // one more launch behind them: every label image of the batch, all of its objects (the preparation's last)
     Signal ev_ctrl = Signal::none, ev_prep = Signal::none;
     // mask frames and features
     bool part_gate = false;     // the mask chain signals ev_part with the masks of frames 0 .. T - 2
@@ -204,7 +206,11 @@ BatchPlan plan_batch(const PlanInputs& in, AloneFn&& alone)
     // frame were three dependent launches (27 - 35 us in front of the frame).  Not under timing: the marks name the two kernels.
     p.try_fused = k.ctrl_ingest != 0 && !p.prep && in.new_mask_frames != 0 && !in.timing;
     p.ev_ctrl = (multi && (in.T == 1 || any_early)) ? Signal::stop : Signal::none;
-    p.ev_prep = !p.prep ? Signal::none : (full || in.new_mask_frames == 0) ? Signal::record : Signal::stop;   // (no ingest: no kernel to end with it)
+    // Masks that arrive as label images: ONE launch for all of them, whatever the number of objects, frames and images, behind the
+    // control blocks (it reads the table that travels with them) and whatever ingest there is of per-object masks; a batch
+    // without label images enqueues what it always did.
+    p.label_ingest = in.label_sets > 0;
+    p.ev_prep = !p.prep ? Signal::none : (full || (in.new_mask_frames == 0 && !p.label_ingest)) ? Signal::record : Signal::stop;   // (no ingest: no kernel to end with it)
 
     // In a burst the velocity chain is released when the masks its flow measurements read are complete -- frames 0 .. T - 2: the
     // measurement of frame t is taken inside the mask of frame t - 1 --, one mask frame (the one that chases a delivered mask

@@ -452,8 +452,8 @@ static int engine_setup(roft_engine* e, const roft_config* cfg)
         e->stream = e->pose_stream[0] = e->pose_stream[1] = e->vel_stream = e->up_stream = e->streams->mask;
     }
     for (BatchSlot& b : e->ring) {
-        HIP_TRY(b.dctrl.ensure((size_t)cfg->max_objects * e->T_max, true));
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b.stage), sizeof(FrameCtrl) * cfg->max_objects * e->T_max));
+        HIP_TRY(b.dctrl.ensure(ctrl_block_count((size_t)cfg->max_objects * e->T_max), true));
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b.stage), sizeof(FrameCtrl) * ctrl_block_count((size_t)cfg->max_objects * e->T_max)));
         hipError_t err = hipSuccess;
         b.each_event([&](hipEvent_t& ev) { if (err == hipSuccess) err = hipEventCreateWithFlags(&ev, hipEventDisableTiming); });
         HIP_TRY(err);

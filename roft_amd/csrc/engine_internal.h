@@ -283,6 +283,11 @@ struct StageFrame {
 };
 constexpr size_t kStageChunk = (size_t)32 << 20;
 
+// Room behind the control blocks of a batch (staging block and device copy) for its label table: at most one set and one member
+// per object and frame, the member array 16-byte aligned behind the sets.
+inline size_t label_table_cap(size_t objs_x_frames) { return (sizeof(LabelSet) + sizeof(LabelMember)) * objs_x_frames + 16; }
+inline size_t ctrl_block_count(size_t objs_x_frames) { return objs_x_frames + (label_table_cap(objs_x_frames) + sizeof(FrameCtrl) - 1) / sizeof(FrameCtrl); }
+
 
 }  // namespace host
 }  // namespace roft
@@ -380,7 +385,13 @@ struct roft_engine {
     int relabel_wait[kNumLin] = {-1, -1};     // batch of the OTHER lane this lane's launches must follow (slots that changed lanes)
     bool any_feat = false, any_feat_now = false, had_uploads = false;
     unsigned feat_frames = 0;              // bit t: some object buffers outlier-rejection features in frame t of the batch
-    unsigned new_mask_frames = 0;   // bit t: some object receives a mask in frame t of the batch
+    unsigned new_mask_frames = 0;   // bit t: some object receives a mask in frame t of the batch (of either form)
+    unsigned plain_mask_frames = 0; // bit t: ... a per-object byte mask (what mask_ingest_kernel / ctrl_ingest_kernel convert)
+    // ... from a label image (roft_frames_submit_labels): the batch's objects grouped by (frame, device image); written behind the
+    // control blocks of the staging block by the submit, copied to the device with them (label_table_bytes, a multiple of 16)
+    std::vector<LabelSet> label_sets;
+    std::vector<std::vector<LabelMember>> label_members;   // per set
+    size_t label_table_bytes = 0;
     int prev_T = 0;                 // frames of the batch stepped before
     int batch_counter = 0, frame_counter = 0;
     int completed_batches = 0, completed_frames = 0;

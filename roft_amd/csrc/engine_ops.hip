@@ -321,6 +321,68 @@ int roft_mask_propagate(uint8_t* mask, int W, int H, const roft_flow* flows, int
     return ROFT_OK;
 }
 
+int roft_labels_to_masks(const void* labels, int label_type, int W, int H, const int* values, int n, uint8_t* masks_out, int* counts_out)
+{
+    if (!labels || !values || n <= 0) return fail(ROFT_ERR_INVALID, "null argument, or no value");
+    if (label_type != ROFT_LABEL_U8 && label_type != ROFT_LABEL_U16) return fail(ROFT_ERR_INVALID, "label_type must be ROFT_LABEL_U8 or ROFT_LABEL_U16");
+    for (int i = 0; i < n; ++i)
+        if (values[i] <= 0 || values[i] > (label_type == ROFT_LABEL_U8 ? 255 : 65535))
+            return fail(ROFT_ERR_INVALID, "label " + std::to_string(values[i]) + ": 0 is the background, and the value must fit the label type");
+    if (roft_device_count() <= 0) return fail(ROFT_ERR_DEVICE, "no HIP device (libroft_hip has no CPU path)");
+    if (int rc = check_geometry(W, H)) return rc;
+    OpCtx& c = op();
+    std::lock_guard<std::mutex> lk(c.mu);
+    HIP_TRY(hipSetDevice(0));
+    (void)hipGetLastError();
+    if (!c.stream) HIP_TRY(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
+    const size_t npix = (size_t)W * H, plane_words = npix / 32;
+    // the engine's kernel on a compact layout: object i = value i, one ingest slot, one set
+    DevBuf<unsigned char> d_img, d_tab, d_masks;
+    DevBuf<uint32_t> d_planes;
+    DevBuf<MaskRec> d_rec;
+    HIP_TRY(d_img.ensure(npix * (label_type == ROFT_LABEL_U8 ? 1 : 2)));
+    HIP_TRY(hipMemcpyAsync(d_img.p, labels, npix * (label_type == ROFT_LABEL_U8 ? 1 : 2), hipMemcpyHostToDevice, c.stream));
+    std::vector<unsigned char> tab(sizeof(LabelSet) + sizeof(LabelMember) * (size_t)n);
+    LabelSet set{};
+    set.img = d_img.p; set.type = label_type; set.t = 0; set.first = 0; set.n = n;
+    std::memcpy(tab.data(), &set, sizeof(set));
+    for (int i = 0; i < n; ++i) {
+        const LabelMember m{i, values[i]};
+        std::memcpy(tab.data() + sizeof(LabelSet) + sizeof(LabelMember) * (size_t)i, &m, sizeof(m));
+    }
+    HIP_TRY(d_tab.ensure(tab.size()));
+    HIP_TRY(hipMemcpyAsync(d_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice, c.stream));
+    HIP_TRY(d_planes.ensure((size_t)n * 2 * plane_words));
+    HIP_TRY(d_rec.ensure((size_t)2 * n));
+    HIP_TRY(hipMemsetAsync(d_rec.p, 0, sizeof(MaskRec) * 2 * (size_t)n, c.stream));
+    LabelIngestArgs la;
+    la.sets = reinterpret_cast<const LabelSet*>(d_tab.p);
+    la.members = reinterpret_cast<const LabelMember*>(d_tab.p + sizeof(LabelSet));
+    la.planes = d_planes.p;
+    la.plane_words = plane_words;
+    la.obj_stride = 2 * plane_words;
+    la.slot0 = 0;
+    la.mrec = d_rec.p;
+    la.n_obj = n;
+    la.n_grp = (int)(npix / 64);
+    launch_label_ingest(la, 1, c.stream);
+    HIP_TRY(hipGetLastError());
+    if (masks_out) {
+        HIP_TRY(d_masks.ensure(npix * (size_t)n));
+        for (int i = 0; i < n; ++i)
+            launch_planes_to_mask(d_planes.p + (size_t)i * 2 * plane_words, d_planes.p + (size_t)i * 2 * plane_words + plane_words, (int)npix,
+                                  d_masks.p + npix * (size_t)i, c.stream);
+        HIP_TRY(hipMemcpyAsync(masks_out, d_masks.p, npix * (size_t)n, hipMemcpyDeviceToHost, c.stream));
+    }
+    std::vector<MaskRec> rec((size_t)2 * n);
+    HIP_TRY(hipMemcpyAsync(rec.data(), d_rec.p, sizeof(MaskRec) * 2 * (size_t)n, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    HIP_TRY(hipGetLastError());
+    if (counts_out)
+        for (int i = 0; i < n; ++i) counts_out[i] = rec[(size_t)n + i].new_count;   // (row t + 1 = 1)
+    return ROFT_OK;
+}
+
 int roft_pose_process_noise(const double psd[3], const double sig_w[3], double T, double Q[81])
 {
     if (!psd || !sig_w || !Q) return fail(ROFT_ERR_INVALID, "null argument");

@@ -128,12 +128,30 @@ static int enqueue_preparation(Enqueue& q)
     }
     tmark(e, nullptr, p.prep ? 4 : 0);
     static_assert(sizeof(FrameCtrl) % 16 == 0, "FrameCtrl is copied in 16-byte units");
-    const size_t n16 = sizeof(FrameCtrl) * (size_t)a.n_obj * a.T / 16;
+    // (the label table of the batch lies behind its control blocks and is copied with them)
+    const size_t n16 = (sizeof(FrameCtrl) * (size_t)a.n_obj * a.T + (p.label_ingest ? e->label_table_bytes : 0)) / 16;
     const hipEvent_t ctrl_stop = Enqueue::stop(p.ev_ctrl, q.cur.ev_ctrl);
-    if (p.try_fused && launch_ctrl_ingest(q.cur.stage, a, n16, e->new_mask_frames, sp, ctrl_stop)) {
+    // masks delivered as label images: one launch, the preparation's last (it ends with ev_prep where the plan has one)
+    auto label_ingest = [&]() -> int {
+        LabelIngestArgs la;
+        la.sets = reinterpret_cast<const LabelSet*>(a.ctrl + (size_t)a.n_obj * a.T);
+        la.members = reinterpret_cast<const LabelMember*>(la.sets + e->label_sets.size());
+        la.planes = a.planes;
+        la.plane_words = a.plane_words;
+        la.obj_stride = (size_t)kPlaneSlotsTotal * 2 * a.plane_words;
+        la.slot0 = a.slot_new;
+        la.mrec = a.mrec;
+        la.n_obj = a.n_obj;
+        la.n_grp = a.cam.W * a.cam.H / 64;
+        launch_label_ingest(la, (int)e->label_sets.size(), sp, Enqueue::stop(p.ev_prep, q.cur.ev_prep));
+        ++q.launches;
+        CHECK_LAUNCH("label image ingest");
+        return ROFT_OK;
+    };
+    if (p.try_fused && launch_ctrl_ingest(q.cur.stage, a, n16, e->plain_mask_frames, sp, ctrl_stop)) {
         ++q.launches;
         CHECK_LAUNCH("FrameCtrl upload + mask ingest");
-        return ROFT_OK;
+        return p.label_ingest ? label_ingest() : ROFT_OK;
     }
     hipExtLaunchKernelGGL(ctrl_upload_kernel, dim3((unsigned)std::min<size_t>((n16 + 255) / 256, 64)), dim3(256), 0, sp, nullptr, ctrl_stop, 0,
                           reinterpret_cast<const uint4*>(q.cur.stage), a, n16, 1);
@@ -141,10 +159,14 @@ static int enqueue_preparation(Enqueue& q)
     CHECK_LAUNCH("FrameCtrl upload");
     int last = -1;
     for (int t = 0; t < a.T; ++t)
-        if (e->new_mask_frames & (1u << t)) last = t;
+        if (e->plain_mask_frames & (1u << t)) last = t;
     for (int t = 0; t <= last; ++t)
-        if (e->new_mask_frames & (1u << t)) { launch_mask_ingest(a, t, sp, t == last ? Enqueue::stop(p.ev_prep, q.cur.ev_prep) : nullptr); ++q.launches; }
+        if (e->plain_mask_frames & (1u << t)) {
+            launch_mask_ingest(a, t, sp, (t == last && !p.label_ingest) ? Enqueue::stop(p.ev_prep, q.cur.ev_prep) : nullptr);
+            ++q.launches;
+        }
     CHECK_LAUNCH("mask ingest");
+    if (p.label_ingest) TRY(label_ingest());
     if (p.prep) {
         TRY(q.signalled(p.ev_prep, q.cur.ev_prep, sp));
         tmark(e, "mask_prepare", 4);
@@ -287,7 +309,8 @@ static PlanInputs plan_inputs(roft_engine* e)
     in.cus = device_cu_count();
     in.batch_counter = e->batch_counter; in.idle_mark = e->idle_mark; in.lead = e->lead; in.completed_batches = e->completed_batches;
     in.had_uploads = e->had_uploads;
-    in.new_mask_frames = e->new_mask_frames;
+    in.new_mask_frames = e->plain_mask_frames;
+    in.label_sets = (int)e->label_sets.size();
     in.any_feat = e->any_feat; in.any_feat_now = e->any_feat_now; in.feat_dep_in_batch = e->feat_dep_in_batch;
     in.outlier_bands_per_alternative = e->cfg.outlier_bands_per_alternative;
     in.conflict_free = e->streams && e->streams->conflicts == 0;

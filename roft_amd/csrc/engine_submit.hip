@@ -250,7 +250,7 @@ static int stage_host_runs(roft_engine* e, const roft_frame_input* inputs, int n
     return ROFT_OK;
 }
 
-static int submit_frames(roft_engine* e, const roft_frame_input* inputs, int n_obj, int T)
+static int submit_frames(roft_engine* e, const roft_frame_input* inputs, const roft_label_mask* labels, int n_obj, int T)
 {
     const roft_config& cfg = e->cfg;
     const size_t npix = (size_t)cfg.cam.width * cfg.cam.height;
@@ -304,16 +304,28 @@ static int submit_frames(roft_engine* e, const roft_frame_input* inputs, int n_o
             const float* d_depth;
             const void* d_flow = nullptr;
             const uint8_t* d_mask = nullptr;
+            // the mask as the pixels of a label image equal to a value (roft_frames_submit_labels)
+            const roft_label_mask* lm = (labels && labels[(size_t)t * n_obj + id].labels) ? &labels[(size_t)t * n_obj + id] : nullptr;
+            const void* d_labels = nullptr;
+            if (lm) {
+                if (in.mask) return fail(ROFT_ERR_INVALID, "object " + std::to_string(id) + ": a label image AND a mask for one frame (one of the two)");
+                if (lm->label_type != ROFT_LABEL_U8 && lm->label_type != ROFT_LABEL_U16)
+                    return fail(ROFT_ERR_INVALID, "object " + std::to_string(id) + ": label_type must be ROFT_LABEL_U8 or ROFT_LABEL_U16");
+                if (lm->label == 0) return fail(ROFT_ERR_INVALID, "object " + std::to_string(id) + ": label 0 is the background");
+                if (lm->label < 0 || lm->label > (lm->label_type == ROFT_LABEL_U8 ? 255 : 65535))
+                    return fail(ROFT_ERR_INVALID, "object " + std::to_string(id) + ": label " + std::to_string(lm->label) + " is outside the range of the label type");
+            }
             if (in.mem_kind == ROFT_MEM_DEVICE) {
                 d_depth = in.depth;
                 d_flow = in.flow;
                 d_mask = in.mask;
+                if (lm) d_labels = lm->labels;
                 // the first call of an engine only: a host pointer declared as device memory is a GPU page fault that takes
                 // the process down at the first kernel -- the commonest mistake of a new binding is refused here instead
                 if (!e->device_pointers_checked) {
-                    const void* ptrs[3] = {in.depth, in.flow, in.mask};
-                    static const char* const what[3] = {"depth", "flow", "mask"};
-                    for (int q = 0; q < 3; ++q) {
+                    const void* ptrs[4] = {in.depth, in.flow, in.mask, d_labels};
+                    static const char* const what[4] = {"depth", "flow", "mask", "label image"};
+                    for (int q = 0; q < 4; ++q) {
                         if (!ptrs[q]) continue;
                         // device or managed memory, or host memory the GPU can address as it is (hipHostMalloc / hipHostRegister:
                         // pinned and mapped -- zero-copy over the bus); unregistered pageable memory is what is refused
@@ -335,6 +347,7 @@ static int submit_frames(roft_engine* e, const roft_frame_input* inputs, int n_o
                 if ((reinterpret_cast<uintptr_t>(d_mask) & 15) || (reinterpret_cast<uintptr_t>(d_flow) & 7) ||
                     (reinterpret_cast<uintptr_t>(d_depth) & 3))
                     return fail(ROFT_ERR_INVALID, "device buffers must be aligned: mask 16 B, flow 8 B, depth 4 B");
+                if (reinterpret_cast<uintptr_t>(d_labels) & 15) return fail(ROFT_ERR_INVALID, "device buffers must be aligned: label image 16 B");
             } else if (in.mem_kind == ROFT_MEM_HOST) {
                 const void* p = nullptr;
                 if (int rc = stage_host(e, frame, in.depth, npix * sizeof(float), &p)) return rc;
@@ -344,6 +357,7 @@ static int submit_frames(roft_engine* e, const roft_frame_input* inputs, int n_o
                     if (int rc = stage_host(e, frame, in.mask, npix, &p)) return rc;
                     d_mask = static_cast<const uint8_t*>(p);
                 }
+                if (lm) { if (int rc = stage_host(e, frame, lm->labels, npix * (lm->label_type == ROFT_LABEL_U8 ? 1 : 2), &d_labels)) return rc; }
             } else {
                 return fail(ROFT_ERR_INVALID, "mem_kind must be ROFT_MEM_HOST or ROFT_MEM_DEVICE");
             }
@@ -351,11 +365,29 @@ static int submit_frames(roft_engine* e, const roft_frame_input* inputs, int n_o
             // ---- ImageSegmentationOFAidedSource::step_frame (hpp:127-231), schedule part
             c.slot_prev = (o.frame_idx + kPlaneSlots - 1) % kPlaneSlots;
             c.slot_cur = o.frame_idx % kPlaneSlots;
-            c.has_new_mask = d_mask ? 1 : 0;
+            const bool has_mask = d_mask || d_labels;
+            c.has_new_mask = has_mask ? 1 : 0;
             c.new_mask = d_mask;
-            if (d_mask) e->new_mask_frames |= 1u << t;
+            if (has_mask) e->new_mask_frames |= 1u << t;
+            if (d_mask) e->plain_mask_frames |= 1u << t;
+            if (d_labels) {
+                c.label = lm->label;
+                c.label_type = lm->label_type;
+                // the set of this frame's objects that name this image (few distinct images per frame: a linear search)
+                int si = -1;
+                for (size_t i = e->label_sets.size(); i-- > 0 && e->label_sets[i].t == t;)
+                    if (e->label_sets[i].img == d_labels && e->label_sets[i].type == lm->label_type) { si = (int)i; break; }
+                if (si < 0) {
+                    LabelSet ls{};
+                    ls.img = d_labels; ls.type = lm->label_type; ls.t = t;
+                    e->label_sets.push_back(ls);
+                    e->label_members.emplace_back();
+                    si = (int)e->label_sets.size() - 1;
+                }
+                e->label_members[si].push_back(LabelMember{id, lm->label});
+            }
             c.first_mask = 0;
-            if (d_mask && !o.seg_available) { o.seg_available = true; c.first_mask = 1; }
+            if (has_mask && !o.seg_available) { o.seg_available = true; c.first_mask = 1; }
             if (!o.seg_available)
                 return fail(ROFT_ERR_STATE, "no segmentation mask delivered yet: the first frame must carry one");
             const bool valid_flow = d_flow && !o.of_first_frame;
@@ -395,10 +427,10 @@ static int submit_frames(roft_engine* e, const roft_frame_input* inputs, int n_o
                     o.stamps[o.n_stamps++] = in.stamp;
                 }
                 c.n_region = 0;
-                if (d_mask)
+                if (has_mask)
                     for (int i = 0; i < o.n_stamps; ++i)
                         if (std::fabs(o.stamps[i] - in.mask_stamp) < 1e-3) { c.n_region = o.n_stamps - (i + 1); break; }
-            } else if (d_mask && !c.first_mask) {
+            } else if (has_mask && !c.first_mask) {
                 // a delivered mask consumes (or, when empty and the number of frames between masks is unknown, drops)
                 // the buffered flows; with that number unknown ALL of them are chased (hpp:239-245)
                 if (cfg.mask_frames_between <= 0 && o.flows_since_mask > kMaxFlowHist)
@@ -461,10 +493,31 @@ static int submit_frames(roft_engine* e, const roft_frame_input* inputs, int n_o
         }
     }
     for (int l = 0; l < kNumLin; ++l) e->n_segments[l] = 1 + max_outliers[l];
+    // the label table behind the batch's control blocks: the sets, then (16-byte aligned) the members set by set
+    e->label_table_bytes = 0;
+    if (!e->label_sets.empty()) {
+        unsigned char* tab = reinterpret_cast<unsigned char*>(blk + (size_t)T * n_obj);
+        const size_t sets_bytes = sizeof(LabelSet) * e->label_sets.size();
+        LabelMember* mem = reinterpret_cast<LabelMember*>(tab + sets_bytes);
+        int first = 0;
+        for (size_t i = 0; i < e->label_sets.size(); ++i) {
+            e->label_sets[i].first = first;
+            e->label_sets[i].n = (int)e->label_members[i].size();
+            std::memcpy(mem + first, e->label_members[i].data(), sizeof(LabelMember) * e->label_members[i].size());
+            first += e->label_sets[i].n;
+        }
+        std::memcpy(tab, e->label_sets.data(), sets_bytes);
+        e->label_table_bytes = (sets_bytes + sizeof(LabelMember) * (size_t)first + 15) & ~(size_t)15;
+    }
     return ROFT_OK;
 }
 
 int roft_frames_submit(roft_engine* e, const roft_frame_input* inputs, int n_objects, int n_frames)
+{
+    return roft_frames_submit_labels(e, inputs, nullptr, n_objects, n_frames);
+}
+
+int roft_frames_submit_labels(roft_engine* e, const roft_frame_input* inputs, const roft_label_mask* labels, int n_objects, int n_frames)
 {
     if (!e || !inputs) return fail(ROFT_ERR_INVALID, "null argument");
     if (n_objects != (int)e->objs.size() || n_objects <= 0) return fail(ROFT_ERR_INVALID, "one input per object and frame required");
@@ -482,9 +535,12 @@ int roft_frames_submit(roft_engine* e, const roft_frame_input* inputs, int n_obj
     e->any_feat = e->any_feat_now = e->had_uploads = false;
     e->feat_frames = 0;
     e->feat_dep_in_batch = false;
-    e->new_mask_frames = 0;
+    e->new_mask_frames = e->plain_mask_frames = 0;
+    e->label_sets.clear();
+    e->label_members.clear();
+    e->label_table_bytes = 0;
     e->gather.clear();
-    int rc = submit_frames(e, inputs, n_objects, n_frames);
+    int rc = submit_frames(e, inputs, labels, n_objects, n_frames);
     if (rc == ROFT_OK) rc = flush_gather(e);
     e->gather.clear();
     HP_MARK(e, 1, hp_t);

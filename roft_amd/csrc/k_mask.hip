@@ -111,7 +111,7 @@ __global__ __launch_bounds__(256) void mask_ingest_kernel(EngineArrays a, int t)
     ROFT_RESIDENT(a, RK_MASK_INGEST);
     const int obj = blockIdx.y;
     const FrameCtrl& c = frame_ctrl(a, t, obj);
-    if (!c.has_new_mask) return;
+    if (!c.has_new_mask || c.label_type) return;   // (masks from a label image: label_ingest_kernel)
     const int n_grp = (a.cam.W * a.cam.H) >> 6;
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     int count = 0, ones = 0;
@@ -148,7 +148,7 @@ __global__ __launch_bounds__(256) void ctrl_ingest_kernel(const uint4* __restric
     const int chunk = w % chunks, rest = w / chunks, obj = rest % a.n_obj, fi = rest / a.n_obj;
     const int t = (int)((frames_packed >> (4 * fi)) & 15u);   // the fi-th delivering frame of the batch
     const FrameCtrl& c = reinterpret_cast<const FrameCtrl*>(src)[(size_t)t * a.n_obj + obj];
-    if (!c.has_new_mask) return;
+    if (!c.has_new_mask || c.label_type) return;   // (masks from a label image: label_ingest_kernel)
     const int n_grp = (a.cam.W * a.cam.H) >> 6;
     const int g = chunk * blockDim.x + threadIdx.x;
     int count = 0, ones = 0;
@@ -186,6 +186,92 @@ void launch_mask_ingest(const EngineArrays& a, int t, hipStream_t s, hipEvent_t 
 {
     const int n_grp = a.cam.W * a.cam.H / 64;
     hipExtLaunchKernelGGL(mask_ingest_kernel, dim3((n_grp + 255) / 256, a.n_obj), dim3(256), 0, s, nullptr, stop, 0, a, t);
+}
+
+// ---- ingest of label-image masks -------------------------------------------------------------------------------------
+// One segmentation image per camera frame instead of one byte mask per object (roft_frames_submit_labels): the mask of a member
+// object is M(p) = (L(p) == label) ? 255 : 0.  One workgroup = 256 groups of 64 pixels of ONE image (a label set); a thread
+// loads its 64 pixels ONCE -- four 16-byte loads for 8-bit labels, eight for 16-bit ones -- and then, for every member of the
+// set, forms the 64-bit membership word in registers, writes it to BOTH planes of the member's ingest slot (a label mask has no
+// pixel of value 1: nz == obj, new_ones stays 0) and adds its population count to the member's counter behind a wave
+// reduction, as ingest_group does.  Every plane word of every member is written, zeros included (the slot holds stale words).
+// The comparison is byte-parallel: x = pixels ^ label replicated; a byte of x is zero iff
+// ~(((x & 0x7F..) + 0x7F..) | x | 0x7F..) has its top bit set (no carry crosses a byte: 0x7F + 0x7F < 0x100), and one multiply
+// gathers the four top bits: with y = bits 0, 8, 16, 24, y * (2^24 + 2^17 + 2^10 + 2^3) has bit 8 i of y at 24 + i and every
+// other partial product at a position of its own (3, 10, 11, 17, 18, 19 and 25, 26, 27 -- the wanted ones), so nothing carries.
+__device__ __forceinline__ uint32_t eq_bits_u8(uint32_t w, uint32_t rep)   // 4 pixels -> 4 bits
+{
+    const uint32_t x = w ^ rep;
+    const uint32_t z = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);
+    return ((z >> 7) * 0x01020408u) >> 24;
+}
+__device__ __forceinline__ uint32_t eq_bits_u16(uint32_t w, uint32_t rep)   // 2 pixels -> 2 bits
+{
+    const uint32_t x = w ^ rep;
+    const uint32_t z = ~(((x & 0x7FFF7FFFu) + 0x7FFF7FFFu) | x | 0x7FFF7FFFu);   // bits 15 and 31
+    return ((z >> 15) | (z >> 30)) & 3u;
+}
+
+template <int NQ>   // 16-byte loads per thread: 4 (8-bit labels), 8 (16-bit)
+__device__ __forceinline__ void label_ingest_group(const LabelIngestArgs& la, const LabelSet& set, LabelMember* s_mem, int g)
+{
+    const bool in = g < la.n_grp;
+    uint4 v[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) v[q] = in ? reinterpret_cast<const uint4*>(set.img)[(size_t)g * NQ + q] : make_uint4(0u, 0u, 0u, 0u);
+    const size_t slot_off = (size_t)(la.slot0 + set.t) * 2 * la.plane_words;
+    for (int m0 = 0; m0 < set.n; m0 += 256) {
+        __syncthreads();   // (the members of the chunk before have been read)
+        if (m0 + (int)threadIdx.x < set.n) s_mem[threadIdx.x] = la.members[set.first + m0 + threadIdx.x];
+        __syncthreads();
+        const int n_here = min(256, set.n - m0);
+        for (int m = 0; m < n_here; ++m) {
+            const LabelMember mem = s_mem[m];   // (workgroup-uniform)
+            if ((unsigned)mem.obj >= (unsigned)la.n_obj) continue;
+            unsigned long long bits = 0ull;
+            if (NQ == 4) {
+                const uint32_t rep = (uint32_t)mem.label * 0x01010101u;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const uint32_t b = eq_bits_u8(v[q].x, rep) | (eq_bits_u8(v[q].y, rep) << 4) | (eq_bits_u8(v[q].z, rep) << 8) |
+                                       (eq_bits_u8(v[q].w, rep) << 12);
+                    bits |= (unsigned long long)b << (16 * q);
+                }
+            } else {
+                const uint32_t rep = (uint32_t)mem.label * 0x00010001u;
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    const uint32_t b = eq_bits_u16(v[q].x, rep) | (eq_bits_u16(v[q].y, rep) << 2) | (eq_bits_u16(v[q].z, rep) << 4) |
+                                       (eq_bits_u16(v[q].w, rep) << 6);
+                    bits |= (unsigned long long)b << (8 * q);
+                }
+            }
+            if (in) {
+                uint32_t* base = la.planes + (size_t)mem.obj * la.obj_stride + slot_off;
+                const uint2 w = make_uint2((uint32_t)bits, (uint32_t)(bits >> 32));
+                reinterpret_cast<uint2*>(base)[g] = w;
+                reinterpret_cast<uint2*>(base + la.plane_words)[g] = w;
+            }
+            int count = in ? __popcll(bits) : 0;
+            for (int off = 32; off > 0; off >>= 1) count += __shfl_xor(count, off, 64);
+            if ((threadIdx.x & 63) == 0 && count) atomicAdd(&la.mrec[(size_t)(set.t + 1) * la.n_obj + mem.obj].new_count, count);
+        }
+    }
+}
+
+// grid: (ceil(W*H/64/256), label sets of the batch)
+__global__ __launch_bounds__(256) void label_ingest_kernel(LabelIngestArgs la)
+{
+    __shared__ LabelMember s_mem[256];
+    const LabelSet set = la.sets[blockIdx.y];
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (set.type == ROFT_LABEL_U8) label_ingest_group<4>(la, set, s_mem, g);
+    else label_ingest_group<8>(la, set, s_mem, g);
+}
+
+void launch_label_ingest(const LabelIngestArgs& la, int n_sets, hipStream_t s, hipEvent_t stop)
+{
+    hipExtLaunchKernelGGL(label_ingest_kernel, dim3((la.n_grp + 255) / 256, n_sets), dim3(256), 0, s, nullptr, stop, 0, la);
 }
 
 __global__ void mask_reset_kernel(EngineArrays a)

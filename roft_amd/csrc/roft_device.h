@@ -156,7 +156,8 @@ struct alignas(16) FrameCtrl {
     int frame_idx;                   // engine frame counter (row of the output log)
     int lane;                        // pose chain lane (stream) that walks this frame's steps (see BeliefSlot)
     int cur_slot;                    // B_LIN0 / B_LIN1: slot of p_corr_belief_ during this frame
-    int pad_[2];
+    int label;                       // the delivered mask is the pixels of a LABEL IMAGE equal to this value (label_ingest_kernel
+    int label_type;                  // writes its planes; the ordinary ingest skips the object): ROFT_LABEL_*, 0: new_mask as before
 };
 
 // Mask chain record of one frame of the batch and one object (k_mask.hip).  Row t + 1 of EngineArrays::mrec belongs to
@@ -367,6 +368,28 @@ void launch_mask_ingest(const EngineArrays& a, int t, hipStream_t s, hipEvent_t 
 // the batch's control blocks (pinned staging -> a.ctrl) and the ingest of every mask it delivers in ONE launch; the ingest counters
 // must be zero (they are: mask_general_kernel's final launch leaves them so).  false: not launched (too many delivering frames)
 bool launch_ctrl_ingest(const void* staging, const EngineArrays& a, size_t n16, unsigned new_mask_frames, hipStream_t s, hipEvent_t stop = nullptr);
+// Label-image masks: the delivering frames' objects grouped by the image they name.  One set = one image of one frame; its
+// members are members[first .. first + n).  The table travels behind the batch's control blocks (staging and device copy).
+struct alignas(16) LabelSet {
+    const void* img;   // H x W labels on the device
+    int type;          // ROFT_LABEL_*
+    int t;             // frame of the batch
+    int first, n;      // its members
+};
+struct LabelMember { int obj, label; };
+// where label_ingest_kernel writes: planes of (object, slot0 + t) at planes + obj * obj_stride + (slot0 + t) * 2 * plane_words,
+// counters at mrec[(t + 1) * n_obj + obj] -- the engine's layout (plane_offset, EngineArrays::mrec), or a compact one (operator)
+struct LabelIngestArgs {
+    const LabelSet* sets;
+    const LabelMember* members;
+    uint32_t* planes;
+    size_t obj_stride, plane_words;
+    int slot0;
+    MaskRec* mrec;
+    int n_obj, n_grp;   // objects (bound of LabelMember::obj), 64-pixel groups of an image
+};
+// every label set of a batch in ONE launch (grid: chunks of 256 groups x sets): planes and counts of all members, one pass per image
+void launch_label_ingest(const LabelIngestArgs& la, int n_sets, hipStream_t s, hipEvent_t stop = nullptr);
 // Zeroes what the ingest kernels accumulate into: the counters of mrec rows 1 .. T (mask_general is cleared by its only
 // reader, mask_general_kernel: this reset may run while the chain before still sets bits).
 // (Inside the engine the control block upload kernel does this; the operator-level entry points call it.)

@@ -68,20 +68,46 @@ class ROFTFilterBatch:
         L.check(L.lib().roft_object_add(self._h, C.byref(desc), C.byref(oid)))
         self.n_objects += 1
         self._inputs = (L.FrameInput * self.n_objects)()
+        self._labels = (L.LabelMask * self.n_objects)()
         self._meshes = getattr(self, "_meshes", []) + [(verts, tris)]   # render_log draws them
         return oid.value
 
     def submit(self, frames):
         """frames: one dict per object with keys depth, flow, mask, pose (None or (x, q)), dt,
-        mem_kind; depth/flow/mask are numpy arrays (HOST) or integer device addresses (DEVICE)."""
-        self._fill(frames)
-        L.check(L.lib().roft_frame_submit(self._h, self._inputs, self.n_objects))
+        mem_kind; depth/flow/mask are numpy arrays (HOST) or integer device addresses (DEVICE).
+        Instead of `mask`: `labels` (one H x W uint8 / uint16 label image, typically the same array for every object of the
+        frame; or an address, then with `label_type` L.LABEL_U8 / L.LABEL_U16) and `label`: the object's mask is the pixels
+        EQUAL to that value (roft_frames_submit_labels)."""
+        if self._fill(frames):
+            L.check(L.lib().roft_frames_submit_labels(self._h, self._inputs, self._labels, self.n_objects, 1))
+        else:
+            L.check(L.lib().roft_frame_submit(self._h, self._inputs, self.n_objects))
 
     def _fill(self, frames):
+        """Fills self._inputs and self._labels; returns whether an object of the frame takes its mask from a label image."""
         assert len(frames) == self.n_objects
         keep = []
+        shared = {}   # one contiguous copy per distinct label array of the frame: the engine uploads a host pointer once
+        any_labels = False
         for i, f in enumerate(frames):
             fi = self._inputs[i]
+            lm = self._labels[i]
+            lab = f.get("labels")
+            if lab is None:
+                lm.labels, lm.label_type, lm.label = None, 0, 0
+            else:
+                any_labels = True
+                lm.label = int(f["label"])
+                if isinstance(lab, int):
+                    lm.labels, lm.label_type = lab, int(f["label_type"])
+                else:
+                    if lab.dtype not in (np.uint8, np.uint16):
+                        raise TypeError("a label image is uint8 or uint16, not %s" % lab.dtype)
+                    v = shared.get(id(lab))
+                    if v is None:
+                        v = shared[id(lab)] = np.ascontiguousarray(lab)
+                        keep.append(v)
+                    lm.labels, lm.label_type = v.ctypes.data, (L.LABEL_U8 if v.dtype == np.uint8 else L.LABEL_U16)
             kind = f.get("mem_kind", L.MEM_HOST)
             fi.mem_kind = kind
             fi.dt = f.get("dt", 0.0)
@@ -105,42 +131,61 @@ class ROFTFilterBatch:
             else:
                 fi.pose_valid = 0
         self._keep = keep
+        return any_labels
 
     def build_inputs(self, frames):
         """Pre-build the ctypes input array of one frame (see submit) for submit_raw."""
-        saved = self._inputs
+        saved = self._inputs, self._labels
         self._inputs = (L.FrameInput * self.n_objects)()
-        self._fill(frames)
+        self._labels = (L.LabelMask * self.n_objects)()
+        if self._fill(frames):
+            raise ValueError("label images go through build_batch / submit_batch_raw(..., labels=...)")
         arr, keep = self._inputs, self._keep
-        self._inputs = saved
+        self._inputs, self._labels = saved
         return arr, keep
 
     def submit_raw(self, inputs):
         L.check(L.lib().roft_frame_submit(self._h, inputs, self.n_objects))
 
     def build_batch(self, frames_list):
-        """ctypes input array of a batch: frames_list[t] = one dict per object (see submit), t = 0 .. T-1."""
+        """ctypes input array of a batch: frames_list[t] = one dict per object (see submit), t = 0 .. T-1.  When a frame uses
+        label images the returned `keep` ends with the batch's L.LabelMask array: see batch_labels."""
         T = len(frames_list)
         arr = (L.FrameInput * (self.n_objects * T))()
+        lab = (L.LabelMask * (self.n_objects * T))()
         keep = []
-        saved = self._inputs
+        saved = self._inputs, self._labels
+        any_labels = False
         for t, frames in enumerate(frames_list):
             self._inputs = (L.FrameInput * self.n_objects)()
-            self._fill(frames)
+            self._labels = (L.LabelMask * self.n_objects)()
+            any_labels = self._fill(frames) or any_labels
             for i in range(self.n_objects):
                 arr[t * self.n_objects + i] = self._inputs[i]
+                lab[t * self.n_objects + i] = self._labels[i]
             keep.append(self._keep)
-        self._inputs = saved
+        self._inputs, self._labels = saved
+        if any_labels:
+            keep.append(lab)
         return arr, keep, T
 
+    @staticmethod
+    def batch_labels(keep):
+        """The L.LabelMask array of a batch built by build_batch, or None when no frame of it uses label images."""
+        return keep[-1] if keep and isinstance(keep[-1], C.Array) and keep[-1]._type_ is L.LabelMask else None
+
     def submit_batch(self, frames_list):
-        """A batch of consecutive frames (at most cfg.max_batch_frames), roft_frames_submit."""
+        """A batch of consecutive frames (at most cfg.max_batch_frames): roft_frames_submit, or roft_frames_submit_labels when a
+        frame takes masks from label images."""
         arr, keep, T = self.build_batch(frames_list)
         self._keep = keep
-        L.check(L.lib().roft_frames_submit(self._h, arr, self.n_objects, T))
+        self.submit_batch_raw(arr, T, self.batch_labels(keep))
 
-    def submit_batch_raw(self, arr, T):
-        L.check(L.lib().roft_frames_submit(self._h, arr, self.n_objects, T))
+    def submit_batch_raw(self, arr, T, labels=None):
+        if labels is None:
+            L.check(L.lib().roft_frames_submit(self._h, arr, self.n_objects, T))
+        else:
+            L.check(L.lib().roft_frames_submit_labels(self._h, arr, labels, self.n_objects, T))
 
     def retain_frames(self):
         return L.lib().roft_engine_retain_frames(self._h)

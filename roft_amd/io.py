@@ -370,6 +370,19 @@ class Sequence:
 
 
 # ---- writing a stream in the Fast-YCB layout (synthetic data on disk, closes the loop with Sequence / the dumper) ----
+def labels_from_instances(instance_map):
+    """The scene renderer's instance map (int32, -1 background, instance i) as a label image for the engine's label-image masks
+    (ROFTFilterBatch.submit, `labels` / `label`): value i + 1 for instance i, 0 for the background; uint8 while the values fit,
+    uint16 otherwise."""
+    inst = np.asarray(instance_map)
+    top = int(inst.max()) + 1 if inst.size else 0
+    if inst.size and int(inst.min()) < -1:
+        raise ValueError("an instance map holds -1 (background) or instance indices")
+    if top > 65535:
+        raise ValueError("more than 65535 instances do not fit a 16-bit label image")
+    return (inst + 1).astype(np.uint8 if top <= 255 else np.uint16)
+
+
 def write_obj(path, verts, tris):
     with open(path, "w") as f:
         for v in np.asarray(verts, np.float64):

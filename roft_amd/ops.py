@@ -98,6 +98,23 @@ def mask_propagate(mask, flow_arrs, frames_between=6):
     return mask
 
 
+def labels_to_masks(labels, values):
+    """The masks {0, 255} [n, H, W] and pixel counts [n] of `values` in one label image (uint8 or uint16): mask i is
+    (labels == values[i]) * 255, by the engine's own label ingest kernel (roft_labels_to_masks).  Values may repeat or be
+    absent from the image; 0 (the background) is refused."""
+    L.require_device()
+    labels = np.ascontiguousarray(labels)
+    if labels.dtype not in (np.uint8, np.uint16) or labels.ndim != 2:
+        raise TypeError("a label image is a 2-D uint8 or uint16 array")
+    H, W = labels.shape
+    vals = np.ascontiguousarray(values, np.int32).reshape(-1)
+    masks = np.zeros((len(vals), H, W), np.uint8)
+    counts = np.zeros(len(vals), np.int32)
+    L.check(L.lib().roft_labels_to_masks(_p(labels), L.LABEL_U8 if labels.dtype == np.uint8 else L.LABEL_U16, W, H,
+                                         vals.ctypes.data_as(C.POINTER(C.c_int)), len(vals), _p(masks), counts.ctypes.data_as(C.POINTER(C.c_int))))
+    return masks, counts
+
+
 def process_noise(psd, sig_w, T):
     Q = np.zeros((9, 9))
     L.check(L.lib().roft_pose_process_noise(_p(_f64(psd)), _p(_f64(sig_w)), T, _p(Q)))

@@ -1,0 +1,100 @@
+// label_plan_check.cpp -- the case plan_batch (roft_amd/csrc/batch_plan.h) gained with label-image masks, against what
+// include/roft_engine.h and DESIGN.md promise for it.  Built with g++ against batch_plan.h alone (tests/test_label_plan_cpu.py).
+//   (1) a batch without label images (label_sets == 0) has no label launch, and its plan is the plan of the same inputs before
+//       the case existed -- checked as: label_sets changes NOTHING of a plan but label_ingest and, in one situation, ev_prep;
+//   (2) the label launch is ONE launch, decided by label_sets > 0 alone: not by how many sets, objects or frames there are;
+//   (3) it is the preparation's last launch: where the preparation runs ahead on the upload stream and no per-object mask is
+//       ingested, ev_prep ends with that launch (stop) instead of being recorded behind a preparation without an ingest kernel;
+//   (4) it never rides in the fused control-block launch: try_fused does not depend on it.
+// Prints the number of plan pairs compared.
+#include "batch_plan.h"
+
+#include <cstdio>
+#include <cstdlib>
+#include <initializer_list>
+#include <cstring>
+
+using namespace roft::host;
+
+#define RULE(cond)                                                                                \
+    do {                                                                                          \
+        if (!(cond)) {                                                                            \
+            std::fprintf(stderr, "rule broken (line %d): %s\n", __LINE__, #cond);               \
+            std::exit(1);                                                                         \
+        }                                                                                         \
+    } while (0)
+
+static bool same_lane(const LanePlan& a, const LanePlan& b)
+{
+    return a.early == b.early && a.wait_relabel == b.wait_relabel && a.release == b.release && a.wait_feat == b.wait_feat &&
+           a.wait_prev_vel == b.wait_prev_vel && a.gate_second == b.gate_second && a.ev_done == b.ev_done;
+}
+
+// everything of a plan but label_ingest and ev_prep
+static bool same_but_label(const BatchPlan& a, const BatchPlan& b)
+{
+    return a.steady == b.steady && a.handoff == b.handoff && a.early_lanes == b.early_lanes && a.prep == b.prep &&
+           a.prep_waits_mask == b.prep_waits_mask && a.prep_waits_feat == b.prep_waits_feat && a.wait_up == b.wait_up &&
+           a.try_fused == b.try_fused && a.ev_ctrl == b.ev_ctrl && a.part_gate == b.part_gate && a.ev_mask == b.ev_mask && a.feat == b.feat &&
+           a.ev_feat == b.ev_feat && a.vel_waits == b.vel_waits && a.feat_waits_mask == b.feat_waits_mask && a.ev_skf == b.ev_skf &&
+           a.ev_vel == b.ev_vel && same_lane(a.lane[0], b.lane[0]) && same_lane(a.lane[1], b.lane[1]) && a.outlier_div == b.outlier_div;
+}
+
+int main()
+{
+    long pairs = 0, seen_stop_by_label = 0, seen_prep = 0, seen_fused = 0;
+    for (int prep_mode = 0; prep_mode <= 3; ++prep_mode)
+    for (int ctrl_ingest = 0; ctrl_ingest <= 1; ++ctrl_ingest)
+    for (int multi = 0; multi <= 1; ++multi)
+    for (int timing = 0; timing <= 2; ++timing)            // off, level 1, level 2
+    for (int T : {1, 2, 6, 8})
+    for (int n_obj : {1, 3, 16, 32, 33, 64, 1024})
+    for (int batch_counter : {0, 1, 2, 5, 6, 40})
+    for (unsigned masks : {0u, 1u, 0x21u, 0xFFu})
+    for (int uploads = 0; uploads <= 1; ++uploads)
+    for (int up_distinct = 0; up_distinct <= 1; ++up_distinct)
+    for (int feat = 0; feat <= 1; ++feat)
+    for (int alone = 0; alone <= 1; ++alone) {
+        PlanInputs in;
+        in.knobs.prep_mode = prep_mode;
+        in.knobs.ctrl_ingest = ctrl_ingest;
+        in.multi = multi != 0;
+        in.timing = timing != 0;
+        in.timing_level = timing == 1 ? 1 : 2;
+        in.T = T; in.n_obj = n_obj; in.cus = 256;
+        in.batch_counter = batch_counter; in.lead = T > 1 ? 5 : 6;
+        in.new_mask_frames = masks & ((1u << T) - 1u);
+        in.had_uploads = uploads != 0;
+        in.up_stream_distinct = up_distinct != 0;
+        in.any_feat = feat != 0;
+        in.conflict_free = true;
+        in.lin_any[0] = in.lin_any[1] = true;
+        in.lane_objs[0] = in.lane_objs[1] = n_obj;
+        in.n_segments[1] = 2;
+        in.lane_old_first[1] = n_obj;
+        auto plan = [&](int sets) { PlanInputs i2 = in; i2.label_sets = sets; return plan_batch(i2, [&] { return alone != 0; }); };
+        const BatchPlan none = plan(0), one = plan(1), many = plan(T * n_obj);
+        const bool full = in.timing && in.timing_level > 1;
+        // (1)
+        RULE(!none.label_ingest);
+        RULE(same_but_label(none, one) && same_but_label(none, many));
+        // (2)
+        RULE(one.label_ingest && many.label_ingest);
+        RULE(one.ev_prep == many.ev_prep);
+        // (3)
+        RULE((none.ev_prep == Signal::none) == !none.prep && (one.ev_prep == Signal::none) == !one.prep);
+        if (one.prep) {
+            ++seen_prep;
+            RULE(one.ev_prep == (full ? Signal::record : Signal::stop));
+            if (in.new_mask_frames == 0 && !full) { RULE(none.ev_prep == Signal::record); ++seen_stop_by_label; }
+            else RULE(none.ev_prep == one.ev_prep);
+        }
+        // (4)
+        RULE(one.try_fused == (ctrl_ingest != 0 && !one.prep && in.new_mask_frames != 0 && !in.timing));
+        seen_fused += one.try_fused;
+        pairs += 2;
+    }
+    RULE(seen_prep > 0 && seen_stop_by_label > 0 && seen_fused > 0);
+    std::printf("%ld\n", pairs);
+    return 0;
+}

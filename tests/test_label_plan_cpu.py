@@ -1,0 +1,16 @@
+"""The case plan_batch (roft_amd/csrc/batch_plan.h) has for masks delivered as label images: one more launch behind the control
+blocks, decided from a count before anything is enqueued.  tests/cpp/label_plan_check.cpp states the rules and sweeps them; it is
+built against the host-only header alone and run here, without a GPU."""
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "roft_amd", "csrc")
+
+
+def test_label_ingest_is_one_launch_and_changes_nothing_else(tmp_path):
+    exe = str(tmp_path / "label_plan_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", "-I", CSRC, os.path.join(ROOT, "tests", "cpp", "label_plan_check.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    assert int(r.stdout) > 100000
