@@ -139,14 +139,16 @@ int roft_flow_measurement(const roft_camera* cam, const uint8_t* prev_mask, cons
 int roft_kf_predict(const double x[6], const double P[36], const double Qdiag[6], double x_out[6],
                     double P_out[36]);
 
-/* *status_out: 0 corrected, 1 measurement empty (corr = pred, SKFCorrection.cpp:61-69) */
+/* *status_out: 0 corrected, 1 measurement empty (corr = pred, SKFCorrection.cpp:61-69), 3 P_pred or the information matrix
+ * P_pred^-1 + sum l H' R^-1 H is not positive definite (a pivot <= 0 or NaN): x_out / P_out are x_pred / P_pred bit for bit.
+ * The call itself returns ROFT_OK in all three cases. */
 int roft_skf_correct(const double x_pred[6], const double P_pred[36], int N, const double* y,
                      const double* H, const double Rdiag[2], int reweight, double x_out[6],
                      double P_out[36], int* status_out);
 
 /* The same correction fed with the kept flow points themselves -- the form the engine's velocity filter consumes (H rows
  * rebuilt on the device from pixel, depth and camera): uv 2N ints (u, v), z N floats, flow_xy 2N floats (pixels, i.e.
- * already divided by the flow scale). */
+ * already divided by the flow scale).  *status_out as for roft_skf_correct: 0, 1 or 3. */
 int roft_skf_correct_points(const roft_camera* cam, double dt, const double x_pred[6], const double P_pred[36], int N,
                             const int32_t* uv, const float* z, const float* flow_xy, const double Rdiag[2],
                             int reweight, double x_out[6], double P_out[36], int* status_out);

@@ -128,8 +128,10 @@ def test_skf_correct_parity(oracle, reweight):
     assert worst < 1e-6  # mean differs by far less than its own standard deviation
 
 
-def test_skf_correct_large_n_uses_radix_select(oracle):
-    """N > 1024 leaves the LDS counting-rank path and takes the radix-select median."""
+def test_skf_correct_large_n_bucket_select(oracle):
+    """N of 1024 .. 2 500 and more on an ordinary stream: the median through the 1024-bin bucket select (several values per
+    bucket, ranked by counting).  N does not choose the median's route, the clustering of the norms does: the radix-select
+    fallback, N > 4096 and the other branches are aimed at in test_skf_paths_gpu.py."""
     st = util.stream(13, 3, scale=1)
     ocam = util.oracle_camera(oracle, st.camera)
     n, uv, y, Hm = oracle.flow_measurement(ocam, st.mask_gt[1].numpy(), st.depth[1].numpy(), st.flow[2].numpy(), st.dt,
