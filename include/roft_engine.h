@@ -515,6 +515,50 @@ int roft_flow_producer_run(roft_flow_producer* fp, const uint8_t* const* prev, c
 int roft_flow_producer_sync(roft_flow_producer* fp);
 void* roft_flow_producer_stream(roft_flow_producer* fp);
 
+/* ---- (3a) camera images on the engine --------------------------------------------------------------------------- *
+ * Camera images instead of flow frames: the engine computes the optical flow itself (the producer of section 3) and the flow
+ * never leaves the device.  Let G_k be the gray image of an object's frame k: a GRAY8 image as it is, a colour image through
+ * OpenCV's 8-bit COLOR_BGR2GRAY, (R 4899 + G 9617 + B 1868 + 8192) >> 14, computed on the device.  An object whose entries
+ * carry images behaves, bit for bit, as if inputs[].flow of frame k had been a HOST buffer holding
+ * roft_optical_flow(G_{k-1}, G_k, W, H, p, roft_config::flow_type) when frames k - 1 and k both carried an image, and NULL
+ * otherwise.  So the object's first frame has no flow, a frame without an image has none, and the image after it STARTS OVER:
+ * no flow ever spans more than one sample time (ImageOpticalFlowNVOF keeps its last frame across an invalid camera frame; this
+ * does not).  An object may still hand a flow directly (image NULL) for any frame, and both forms mix within a frame.
+ *  - Images are HOST or DEVICE like the frame's other images (inputs[].mem_kind).  HOST images are uploaded once per distinct
+ *    pointer and frame, so the objects of a shared scene name one image; DEVICE images (4-byte aligned) are read in place,
+ *    during the submit call's own enqueued work, under the retention contract of roft_frame_input.
+ *  - One pyramid is built per distinct image and one flow per distinct (previous, current) pair of a frame, however many objects
+ *    name them: roft_engine_flow_stats.
+ *  - ROFT_ERR_INVALID, nothing consumed: an entry with image AND flow, an unknown image_type, a misaligned DEVICE image.
+ *    ROFT_ERR_STATE: images on an engine without roft_engine_enable_flow. */
+#define ROFT_IMAGE_GRAY8 1   /* H x W bytes */
+#define ROFT_IMAGE_BGR8  2   /* H x W x 3, OpenCV order: what the reference's camera delivers */
+#define ROFT_IMAGE_RGB8  3   /* H x W x 3, PNG order */
+typedef struct {
+    const void* image;   /* NULL: no camera image for this object and frame */
+    int image_type;      /* ROFT_IMAGE_* */
+} roft_frame_image;
+/* Before the first frame (ROFT_ERR_STATE afterwards); p NULL: roft_default_of_params.  ROFT_ERR_INVALID, with the reason in
+ * roft_last_error_string, for a configuration the producer cannot serve -- flow_type F32C2 needs flow_grid 1 and flow_scale 1,
+ * S16C2 grid 4 and scale 32; the width a multiple of 4 * 2^(levels-1), the height of 2^(levels-1) and of 4 -- and for parameters
+ * outside roft_flow_producer_create's ranges. */
+int roft_engine_enable_flow(roft_engine* e, const roft_of_params* p);
+/* images[t * n_objects + obj]; images NULL: exactly roft_frames_submit_labels; labels may be NULL */
+int roft_frames_submit_images(roft_engine* e, const roft_frame_input* inputs, const roft_label_mask* labels,
+                              const roft_frame_image* images, int n_objects, int n_frames);
+/* the flow the engine produced for obj's last stepped frame, in the engine's flow type (H / grid x W / grid x 2) -> host buffer;
+ * syncs; ROFT_ERR_STATE when that frame had none */
+int roft_engine_get_flow(roft_engine* e, int obj_id, void* flow_out);
+typedef struct {
+    long long images;       /* distinct images taken in */
+    long long image_bytes;  /* ... their bytes uploaded (a DEVICE image adds none) */
+    long long pyramids;     /* pyramids built */
+    long long pairs;        /* flows produced */
+} roft_engine_flow_stats;   /* since roft_engine_create */
+int roft_engine_get_flow_stats(roft_engine* e, roft_engine_flow_stats* out);
+/* Stand-alone operator (tests, tools): the gray image (W x H bytes) of a HOST image, any W, H >= 1, by the device's conversion. */
+int roft_image_to_gray(const void* image, int image_type, int W, int H, uint8_t* gray_out);
+
 /* ---- (3b) scene renderer: tracked poses drawn over the camera frames ----------------------------------------------
  * The reference's evaluation draws the mesh at every estimated pose over the grayed camera frame (evaluation/results_renderer.py:
  * 591-778 through tools/object_renderer/src/renderer.cpp).  This is that stage for many frames and several objects per frame:

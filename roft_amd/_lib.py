@@ -83,6 +83,17 @@ class LabelMask(C.Structure):
     _fields_ = [("labels", C.c_void_p), ("label_type", C.c_int), ("label", C.c_int)]
 
 
+IMAGE_GRAY8, IMAGE_BGR8, IMAGE_RGB8 = 1, 2, 3   # ROFT_IMAGE_*
+
+
+class FrameImage(C.Structure):
+    _fields_ = [("image", C.c_void_p), ("image_type", C.c_int)]
+
+
+class EngineFlowStats(C.Structure):
+    _fields_ = [("images", C.c_longlong), ("image_bytes", C.c_longlong), ("pyramids", C.c_longlong), ("pairs", C.c_longlong)]
+
+
 class EngineStats(C.Structure):
     _fields_ = [("frames", C.c_longlong), ("batches", C.c_longlong), ("launches", C.c_longlong),
                 ("event_ops", C.c_longlong), ("h2d_bytes", C.c_longlong), ("h2d_copies", C.c_longlong)]
@@ -128,11 +139,13 @@ ABI_SYMBOLS = [
     "roft_pose_errors", "roft_engine_score_log", "roft_debug_pose_errors_kernel_ms",
     "roft_scene_renderer_create", "roft_scene_renderer_destroy", "roft_scene_render", "roft_render_scene", "roft_debug_scene_kernel_ms",
     "roft_frames_submit_labels", "roft_labels_to_masks",
+    "roft_engine_enable_flow", "roft_frames_submit_images", "roft_engine_get_flow", "roft_engine_get_flow_stats", "roft_image_to_gray",
 ]
 POSE_ERROR_ADD, POSE_ERROR_ADDS = 0, 1   # ROFT_POSE_ERROR_*
 # entry points younger than ABI version 2 itself: a library built before them still loads through ROFT_LIB_SO
 NEWER_SYMBOLS = ("roft_pose_errors", "roft_engine_score_log", "roft_scene_renderer_create", "roft_scene_renderer_destroy", "roft_scene_render",
-                 "roft_render_scene", "roft_frames_submit_labels", "roft_labels_to_masks")
+                 "roft_render_scene", "roft_frames_submit_labels", "roft_labels_to_masks",
+                 "roft_engine_enable_flow", "roft_frames_submit_images", "roft_engine_get_flow", "roft_engine_get_flow_stats", "roft_image_to_gray")
 
 
 def build(force=False):
@@ -232,6 +245,12 @@ def lib():
     if hasattr(L, "roft_frames_submit_labels"):
         L.roft_frames_submit_labels.argtypes = [vp, C.POINTER(FrameInput), C.POINTER(LabelMask), C.c_int, C.c_int]
         L.roft_labels_to_masks.argtypes = [vp, C.c_int, C.c_int, C.c_int, ip, C.c_int, vp, ip]
+    if hasattr(L, "roft_frames_submit_images"):
+        L.roft_engine_enable_flow.argtypes = [vp, C.POINTER(OFParams)]
+        L.roft_frames_submit_images.argtypes = [vp, C.POINTER(FrameInput), C.POINTER(LabelMask), C.POINTER(FrameImage), C.c_int, C.c_int]
+        L.roft_engine_get_flow.argtypes = [vp, C.c_int, vp]
+        L.roft_engine_get_flow_stats.argtypes = [vp, C.POINTER(EngineFlowStats)]
+        L.roft_image_to_gray.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
     for name in ABI_SYMBOLS:
         if (name.startswith("roft_debug_") or name in NEWER_SYMBOLS) and not hasattr(L, name):
             continue   # (an older build loaded through ROFT_LIB_SO for an A/B run: diagnostics and the pose errors only; tests/test_abi_cpu.py checks the in-tree library has them all)

@@ -79,6 +79,8 @@ struct PlanInputs {
     bool feat_used_two_back = false;    // batch b - 2 ran a feature kernel on the mask stream
     bool vel_used_prev = false;         // batch b - 1 ended its velocity chain with ev_vel
     bool done_used_relabel[kPlanLanes] = {false, false};   // the other lane had work in batch relabel_wait[lane]
+    // camera images: the submit produced flows on the upload stream (ev_up is recorded behind them, uploads or not)
+    bool produced_flows = false;
 };
 
 // how a span (a launch group on one stream) signals its event
@@ -201,7 +203,7 @@ BatchPlan plan_batch(const PlanInputs& in, AloneFn&& alone)
     p.prep = batch && in.up_stream_distinct && by_mode(k.prep_mode, p.steady, !cus_to_spare);
     p.prep_waits_mask = p.prep && in.batch_counter >= 2;
     p.prep_waits_feat = p.prep_waits_mask && in.feat_used_two_back;
-    p.wait_up = multi && in.had_uploads && !p.prep;   // (prep: same stream as the uploads)
+    p.wait_up = multi && (in.had_uploads || in.produced_flows) && !p.prep;   // (prep: same stream as the uploads and the flow production)
     // Otherwise control blocks and the ingest of the delivered masks in ONE launch -- on the mask stream they and the first mask
     // frame were three dependent launches (27 - 35 us in front of the frame).  Not under timing: the marks name the two kernels.
     p.try_fused = k.ctrl_ingest != 0 && !p.prep && in.new_mask_frames != 0 && !in.timing;

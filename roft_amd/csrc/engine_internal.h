@@ -30,6 +30,7 @@
 #include "roft_device.h"
 #include "mesh_class.h"
 #include "batch_plan.h"
+#include "opticalflow.h"
 
 static_assert(roft::host::kPlanLanes == roft::kNumLin, "batch_plan.h plans for the engine's pose lanes");
 
@@ -250,6 +251,10 @@ struct Sched {
     int last_touch[kNumLin] = {-1, -1};   // last batch whose pose chain reads or writes each slot
     int flows_since_mask = 0;          // upper bound of the flows buffered since the last delivered mask
     const float* depth_prev = nullptr;
+    // camera images (roft_frames_submit_images): the pyramid slot of the image the frame before carried, in that frame's
+    // generation (EngineFlow::pyr; -1: it carried none), and the flow the engine produced for the last frame (null: none)
+    int pyr_prev = -1;
+    const void* flow_made = nullptr;
     Sched() { for (int& u : feat_use) u = -1; }
 };
 
@@ -261,11 +266,38 @@ struct OwnedFlow {
 struct HostObject {
     Sched s;
     int stepped_slot = 0, stepped_lane = 0;   // slot holding p_corr_belief_ after the last stepped frame, and its lane
+    const void* stepped_flow = nullptr;       // the flow produced for the last stepped frame (roft_engine_get_flow), or null
     std::vector<OwnedFlow*> owned;   // engine copies of flows that outlived the zero-copy retention window
     DevBuf<float> verts;
     DevBuf<int32_t> tris;
     DevBuf<uint8_t> tri_flip;   // closed meshes only (mesh_class.h)
     ~HostObject() { for (auto* o : owned) delete o; }
+};
+
+// Camera images on the engine (roft_engine_enable_flow): what a submit call enqueues on the upload stream, frame by frame, behind
+// the copies of its HOST inputs.  Built by submit_frames on the host only; enqueued when the whole batch has been accepted, so a
+// refused submit leaves the pyramids on the device as they were (the per-object side, Sched::pyr_prev, rolls back with Sched).
+struct FlowImageJob { const void* dev; int type; };            // a distinct image of a frame; its index is its pyramid slot
+struct FlowPairJob { int pyr0, pyr1; unsigned char* out; };    // slots in the generations of frame - 1 and frame; the product's place
+struct FlowCloneJob { void* dst; const void* src; };           // a flow that outlived the retention window (OwnedFlow), copied behind the batch's production
+struct FlowFrameJobs {
+    std::vector<FlowImageJob> images;
+    std::vector<FlowPairJob> pairs;
+    std::vector<FlowCloneJob> clones;
+};
+struct EngineFlow {
+    bool enabled = false;
+    roft_of_params prm{};
+    OfGeom geom{};
+    // One pyramid per distinct image of a frame, kept until the next frame's pairs have used it: a ring of max_batch_frames + 1
+    // generations indexed by frame, so that the pyramids of ALL frames of a batch are built in one go while the last one of the
+    // batch before is still there (a later batch overwrites a generation behind its readers in stream order); a generation
+    // grows to the largest number of distinct images a frame ever brought.
+    std::vector<std::vector<DevBuf<float>*>> pyr;
+    DevBuf<float> coarse, field;        // workspace of ONE chunk of kOfChunk pairs, reused chunk after chunk in stream order
+    std::vector<FlowFrameJobs> jobs;    // of the submit call under way
+    roft_engine_flow_stats stats{}, stats_backup{};
+    ~EngineFlow() { for (auto& g : pyr) for (auto* b : g) delete b; }
 };
 
 // Device copies of HOST inputs: a ring of `retain` frame slots, each a bump allocator over chunks of device memory that
@@ -316,7 +348,8 @@ constexpr size_t kGatherMaxBytes = (size_t)2 << 20;                 // larger im
 
 // What one batch in flight owns: a slot of the batch ring.
 struct BatchSlot {
-    hipEvent_t ev_up = nullptr;     // uploads of the batch on the device
+    hipEvent_t ev_up = nullptr;     // uploads of the batch on the device, and the flows the submit produced from camera images behind them
+    hipEvent_t ev_host = nullptr;   // ... the copies alone, where production follows them: what the HOST waits for (its buffers are its own again)
     hipEvent_t ev_ctrl = nullptr;   // FrameCtrl blocks of the batch on the device (and the mask chain of the batch before)
     hipEvent_t ev_mask = nullptr;   // mask chain kernel of the batch complete
     hipEvent_t ev_part = nullptr;   // the masks of the batch's frames 0 .. T - 2 complete (what its flow measurements read)
@@ -325,7 +358,7 @@ struct BatchSlot {
     hipEvent_t ev_vel = nullptr;    // the batch's velocity chain complete (velocity filter AND the feature kernel behind it)
     hipEvent_t ev_skf = nullptr;    // twists of the batch complete (the velocity filter alone: what a pose lane waits for)
     hipEvent_t ev_done[kNumLin] = {nullptr, nullptr};   // pose chain of the batch complete (per lane)
-    template <class F> void each_event(F&& f) { for (hipEvent_t* ev : {&ev_up, &ev_ctrl, &ev_mask, &ev_part, &ev_prep, &ev_feat, &ev_vel, &ev_skf, &ev_done[0], &ev_done[1]}) f(*ev); }
+    template <class F> void each_event(F&& f) { for (hipEvent_t* ev : {&ev_up, &ev_host, &ev_ctrl, &ev_mask, &ev_part, &ev_prep, &ev_feat, &ev_vel, &ev_skf, &ev_done[0], &ev_done[1]}) f(*ev); }
     DevBuf<FrameCtrl> dctrl;             // control blocks on the device
     FrameCtrl* stage = nullptr;          // ... and their pinned staging block
     GatherItem* gather_tab = nullptr;    // pinned table gather_copy_kernel reads (kGatherCap entries; allocated on first use)
@@ -384,6 +417,8 @@ struct roft_engine {
     int lane_objs[kNumLin] = {0, 0}, lane_old_first[kNumLin] = {0, 0};
     int relabel_wait[kNumLin] = {-1, -1};     // batch of the OTHER lane this lane's launches must follow (slots that changed lanes)
     bool any_feat = false, any_feat_now = false, had_uploads = false;
+    bool produced_flows = false;           // the submit enqueued flow production (pyramids, flows, deferred flow clones) behind its copies: ev_up covers it
+    EngineFlow flow;                       // camera images -> flows (roft_engine_enable_flow)
     unsigned feat_frames = 0;              // bit t: some object buffers outlier-rejection features in frame t of the batch
     unsigned new_mask_frames = 0;   // bit t: some object receives a mask in frame t of the batch (of either form)
     unsigned plain_mask_frames = 0; // bit t: ... a per-object byte mask (what mask_ingest_kernel / ctrl_ingest_kernel convert)

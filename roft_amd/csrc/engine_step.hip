@@ -13,6 +13,13 @@
 //      sets, the preparation ahead two batches on (it rewrites the control blocks that kernel reads), the host; ev_done[lane] -> host
 //      (in-flight bound, roft_sync).  Events only point from work enqueued EARLIER to work enqueued later, batch by batch and chain by chain in the
 //      fixed order of step_batch: the wait-for graph is acyclic by construction.
+//      Camera images (roft_frames_submit_images): the submit call enqueues the flow production -- pyramids, Lucas-Kanade levels, the
+//      clones of aged-out flows -- on the UPLOAD stream behind its copies and records ev_up behind the production, so ev_up -> mask /
+//      velocity stream covers the produced flows exactly as it covers a copied flow; it is recorded, and waited for, also when every
+//      input was DEVICE memory and nothing was copied (PlanInputs::produced_flows).  With the preparation on the upload stream the
+//      control blocks follow the production in stream order and ev_prep carries it.  The velocity stream reads flows only behind an
+//      event of this batch's mask stream (ev_ctrl / ev_part / ev_mask), which has waited.  The HOST waits for ev_host, recorded
+//      behind the copies and BEFORE the production: no kernel is waited for, and no kernel waits in memory.
 //  (2) The pose lanes' waits inside their kernels, and the three ways a lane is released: batch_plan.h.
 //  (3) The outlier test's workgroups that share an alternative (k_render.hip) never wait for each other: each writes its slab,
 //      counts itself in and EXITS unless it is the last to arrive; the last one merges.  No co-residency is needed.
@@ -309,6 +316,7 @@ static PlanInputs plan_inputs(roft_engine* e)
     in.cus = device_cu_count();
     in.batch_counter = e->batch_counter; in.idle_mark = e->idle_mark; in.lead = e->lead; in.completed_batches = e->completed_batches;
     in.had_uploads = e->had_uploads;
+    in.produced_flows = e->produced_flows;
     in.new_mask_frames = e->plain_mask_frames;
     in.label_sets = (int)e->label_sets.size();
     in.any_feat = e->any_feat; in.any_feat_now = e->any_feat_now; in.feat_dep_in_batch = e->feat_dep_in_batch;
@@ -409,7 +417,7 @@ int roft_step(roft_engine* e)
         roft_batch_trace& tr = e->trace[e->batch_counter % roft_engine::kTraceRing];
         if (tr.batch == e->batch_counter) tr.step_us = host_now_us() - t_step0;
     }
-    for (HostObject* ho : e->objs) { ho->stepped_slot = ho->s.cur_slot; ho->stepped_lane = ho->s.own[ho->s.cur_slot]; }
+    for (HostObject* ho : e->objs) { ho->stepped_slot = ho->s.cur_slot; ho->stepped_lane = ho->s.own[ho->s.cur_slot]; ho->stepped_flow = ho->s.flow_made; }
     // (a failed step leaves the engine consistent as far as the host can tell: the batch counts as enqueued)
     e->frame_counter += e->cur_T;
     e->prev_T = e->cur_T;

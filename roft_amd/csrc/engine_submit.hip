@@ -250,7 +250,52 @@ static int stage_host_runs(roft_engine* e, const roft_frame_input* inputs, int n
     return ROFT_OK;
 }
 
-static int submit_frames(roft_engine* e, const roft_frame_input* inputs, const roft_label_mask* labels, int n_obj, int T)
+namespace roft { int of_check_params(int W, int H, const roft_of_params* p); }   // flow_producer.hip
+
+static size_t image_bytes(int type, size_t npix) { return type == ROFT_IMAGE_GRAY8 ? npix : 3 * npix; }
+
+// The flow production of the accepted batch -> upload stream: a pyramid for each distinct image of each of its frames, then a flow
+// for each distinct pair, then the clones of flows that aged out in the batch (they may read its products) -- the images and the
+// pairs of ALL its frames in chunks of kOfChunk, whose pointers travel in the kernel arguments and whose workspace the next chunk
+// reuses in stream order.  A batch of eight frames of a shared scene is one chunk of each: seven launches, not seven per frame.
+static int enqueue_flow_production(roft_engine* e, int T)
+{
+    EngineFlow& f = e->flow;
+    const size_t fbytes = flow_bytes(e->arr.a.ffmt);
+    const size_t field_floats = (size_t)2 * e->cfg.cam.width * e->cfg.cam.height;
+    const bool s16 = e->cfg.flow_type == ROFT_FLOW_S16C2;
+    const int G = (int)f.pyr.size();
+    OfImages im{};
+    for (int t = 0; t < T; ++t) {
+        const int gen = (e->frame_counter + t) % G;
+        for (size_t i = 0; i < f.jobs[t].images.size(); ++i) {
+            const int k = im.n++;
+            im.type[k] = f.jobs[t].images[i].type; im.src[k] = f.jobs[t].images[i].dev; im.pyr[k] = f.pyr[gen][i]->p;
+            if (im.n == kOfChunk) { launch_of_pyramids(f.geom, im, e->up_stream); im.n = 0; }
+        }
+    }
+    if (im.n) launch_of_pyramids(f.geom, im, e->up_stream);
+    OfPairs pr{};
+    for (int t = 0; t < T; ++t) {
+        const int gen = (e->frame_counter + t) % G, gen_prev = (e->frame_counter + t + G - 1) % G;
+        for (const FlowPairJob& pj : f.jobs[t].pairs) {
+            const int k = pr.n++;
+            pr.pyr0[k] = f.pyr[gen_prev][pj.pyr0]->p;
+            pr.pyr1[k] = f.pyr[gen][pj.pyr1]->p;
+            pr.coarse[k] = f.coarse.p + (size_t)k * f.geom.flow_stride;
+            pr.field[k] = s16 ? f.field.p + (size_t)k * field_floats : reinterpret_cast<float*>(pj.out);
+            pr.out_s16[k] = s16 ? reinterpret_cast<int16_t*>(pj.out) : nullptr;
+            if (pr.n == kOfChunk) { launch_of_pairs(f.geom, pr, e->up_stream); pr.n = 0; }
+        }
+    }
+    if (pr.n) launch_of_pairs(f.geom, pr, e->up_stream);
+    if (hipError_t le = hipGetLastError()) return fail(ROFT_ERR_DEVICE, std::string("flow production: ") + hipGetErrorString(le));
+    for (int t = 0; t < T; ++t)
+        for (const FlowCloneJob& c : f.jobs[t].clones) HIP_TRY(hipMemcpyAsync(c.dst, c.src, fbytes, hipMemcpyDeviceToDevice, e->up_stream));
+    return ROFT_OK;
+}
+
+static int submit_frames(roft_engine* e, const roft_frame_input* inputs, const roft_label_mask* labels, const roft_frame_image* images, int n_obj, int T)
 {
     const roft_config& cfg = e->cfg;
     const size_t npix = (size_t)cfg.cam.width * cfg.cam.height;
@@ -315,17 +360,27 @@ static int submit_frames(roft_engine* e, const roft_frame_input* inputs, const r
                 if (lm->label < 0 || lm->label > (lm->label_type == ROFT_LABEL_U8 ? 255 : 65535))
                     return fail(ROFT_ERR_INVALID, "object " + std::to_string(id) + ": label " + std::to_string(lm->label) + " is outside the range of the label type");
             }
+            // a camera image instead of a flow frame (roft_frames_submit_images)
+            const roft_frame_image* fim = (images && images[(size_t)t * n_obj + id].image) ? &images[(size_t)t * n_obj + id] : nullptr;
+            const void* d_image = nullptr;
+            if (fim) {
+                if (!e->flow.enabled) return fail(ROFT_ERR_STATE, "camera images need roft_engine_enable_flow before the first frame");
+                if (in.flow) return fail(ROFT_ERR_INVALID, "object " + std::to_string(id) + ": a camera image AND a flow for one frame (one of the two)");
+                if (fim->image_type != ROFT_IMAGE_GRAY8 && fim->image_type != ROFT_IMAGE_BGR8 && fim->image_type != ROFT_IMAGE_RGB8)
+                    return fail(ROFT_ERR_INVALID, "object " + std::to_string(id) + ": image_type must be ROFT_IMAGE_GRAY8, ROFT_IMAGE_BGR8 or ROFT_IMAGE_RGB8");
+            }
             if (in.mem_kind == ROFT_MEM_DEVICE) {
                 d_depth = in.depth;
+                if (fim) d_image = fim->image;
                 d_flow = in.flow;
                 d_mask = in.mask;
                 if (lm) d_labels = lm->labels;
                 // the first call of an engine only: a host pointer declared as device memory is a GPU page fault that takes
                 // the process down at the first kernel -- the commonest mistake of a new binding is refused here instead
                 if (!e->device_pointers_checked) {
-                    const void* ptrs[4] = {in.depth, in.flow, in.mask, d_labels};
-                    static const char* const what[4] = {"depth", "flow", "mask", "label image"};
-                    for (int q = 0; q < 4; ++q) {
+                    const void* ptrs[5] = {in.depth, in.flow, in.mask, d_labels, d_image};
+                    static const char* const what[5] = {"depth", "flow", "mask", "label image", "camera image"};
+                    for (int q = 0; q < 5; ++q) {
                         if (!ptrs[q]) continue;
                         // device or managed memory, or host memory the GPU can address as it is (hipHostMalloc / hipHostRegister:
                         // pinned and mapped -- zero-copy over the bus); unregistered pageable memory is what is refused
@@ -348,6 +403,7 @@ static int submit_frames(roft_engine* e, const roft_frame_input* inputs, const r
                     (reinterpret_cast<uintptr_t>(d_depth) & 3))
                     return fail(ROFT_ERR_INVALID, "device buffers must be aligned: mask 16 B, flow 8 B, depth 4 B");
                 if (reinterpret_cast<uintptr_t>(d_labels) & 15) return fail(ROFT_ERR_INVALID, "device buffers must be aligned: label image 16 B");
+                if (reinterpret_cast<uintptr_t>(d_image) & 3) return fail(ROFT_ERR_INVALID, "device buffers must be aligned: camera image 4 B");
             } else if (in.mem_kind == ROFT_MEM_HOST) {
                 const void* p = nullptr;
                 if (int rc = stage_host(e, frame, in.depth, npix * sizeof(float), &p)) return rc;
@@ -358,9 +414,51 @@ static int submit_frames(roft_engine* e, const roft_frame_input* inputs, const r
                     d_mask = static_cast<const uint8_t*>(p);
                 }
                 if (lm) { if (int rc = stage_host(e, frame, lm->labels, npix * (lm->label_type == ROFT_LABEL_U8 ? 1 : 2), &d_labels)) return rc; }
+                if (fim) {
+                    const long long before = e->stats.h2d_bytes;   // (the objects of a shared scene name one image: uploaded, and counted, once)
+                    if (int rc = stage_host(e, frame, fim->image, image_bytes(fim->image_type, npix), &d_image)) return rc;
+                    e->flow.stats.image_bytes += e->stats.h2d_bytes - before;
+                }
             } else {
                 return fail(ROFT_ERR_INVALID, "mem_kind must be ROFT_MEM_HOST or ROFT_MEM_DEVICE");
             }
+
+            // ---- the flow of a camera image: produced where a staged HOST flow of the frame would have been copied, one pyramid per
+            // distinct image and one flow per distinct (previous, current) pair of the frame; none without an image the frame before
+            int pyr_cur = -1;
+            if (fim) {
+                EngineFlow& f = e->flow;
+                FlowFrameJobs& fj = f.jobs[t];
+                for (size_t i = 0; i < fj.images.size() && pyr_cur < 0; ++i)
+                    if (fj.images[i].dev == d_image && fj.images[i].type == fim->image_type) pyr_cur = (int)i;
+                if (pyr_cur < 0) {
+                    pyr_cur = (int)fj.images.size();
+                    fj.images.push_back(FlowImageJob{d_image, fim->image_type});
+                    std::vector<DevBuf<float>*>& gen = f.pyr[(size_t)frame % f.pyr.size()];
+                    if ((int)gen.size() <= pyr_cur) {
+                        auto* pb = new DevBuf<float>();
+                        gen.push_back(pb);
+                        HIP_TRY(pb->ensure(f.geom.pyr_stride));
+                    }
+                    f.stats.images++;
+                    f.stats.pyramids++;
+                    e->produced_flows = true;   // (a pyramid to build, also where no pair follows in this batch)
+                }
+                if (o.pyr_prev >= 0) {
+                    for (const FlowPairJob& pj : fj.pairs)
+                        if (pj.pyr0 == o.pyr_prev && pj.pyr1 == pyr_cur) { d_flow = pj.out; break; }
+                    if (!d_flow) {
+                        unsigned char* out = nullptr;
+                        if (int rc = stage_alloc(e, frame, fbytes, &out)) return rc;
+                        fj.pairs.push_back(FlowPairJob{o.pyr_prev, pyr_cur, out});
+                        f.stats.pairs++;
+                        d_flow = out;
+                        e->produced_flows = true;
+                    }
+                }
+            }
+            o.pyr_prev = pyr_cur;
+            o.flow_made = fim ? d_flow : nullptr;
 
             // ---- ImageSegmentationOFAidedSource::step_frame (hpp:127-231), schedule part
             c.slot_prev = (o.frame_idx + kPlaneSlots - 1) % kPlaneSlots;
@@ -412,8 +510,14 @@ static int submit_frames(roft_engine* e, const roft_frame_input* inputs, const r
                 }
                 if (k < 0) { ho.owned.push_back(new OwnedFlow()); k = (int)ho.owned.size() - 1; }
                 HIP_TRY(ho.owned[k]->buf.ensure(fbytes));
-                HIP_TRY(hipMemcpyAsync(ho.owned[k]->buf.p, fe.ptr, fbytes, hipMemcpyDeviceToDevice, e->up_stream));
-                e->had_uploads = true;
+                if (e->flow.enabled) {
+                    // (the flow may be one this very submit produces: the copy goes behind that production, in stream order)
+                    e->flow.jobs[t].clones.push_back(FlowCloneJob{ho.owned[k]->buf.p, fe.ptr});
+                    e->produced_flows = true;
+                } else {
+                    HIP_TRY(hipMemcpyAsync(ho.owned[k]->buf.p, fe.ptr, fbytes, hipMemcpyDeviceToDevice, e->up_stream));
+                    e->had_uploads = true;
+                }
                 fe.ptr = ho.owned[k]->buf.p;
                 fe.owned = k;
             }
@@ -519,6 +623,12 @@ int roft_frames_submit(roft_engine* e, const roft_frame_input* inputs, int n_obj
 
 int roft_frames_submit_labels(roft_engine* e, const roft_frame_input* inputs, const roft_label_mask* labels, int n_objects, int n_frames)
 {
+    return roft_frames_submit_images(e, inputs, labels, nullptr, n_objects, n_frames);
+}
+
+int roft_frames_submit_images(roft_engine* e, const roft_frame_input* inputs, const roft_label_mask* labels, const roft_frame_image* images,
+                              int n_objects, int n_frames)
+{
     if (!e || !inputs) return fail(ROFT_ERR_INVALID, "null argument");
     if (n_objects != (int)e->objs.size() || n_objects <= 0) return fail(ROFT_ERR_INVALID, "one input per object and frame required");
     if (n_frames < 1 || n_frames > e->T_max) return fail(ROFT_ERR_INVALID, "n_frames must be 1 .. roft_config::max_batch_frames");
@@ -532,7 +642,11 @@ int roft_frames_submit_labels(roft_engine* e, const roft_frame_input* inputs, co
     HP_MARK(e, 0, hp_t);   // time blocked on the GPU
     e->backup.resize(e->objs.size());
     for (size_t i = 0; i < e->objs.size(); ++i) e->backup[i] = e->objs[i]->s;
-    e->any_feat = e->any_feat_now = e->had_uploads = false;
+    e->any_feat = e->any_feat_now = e->had_uploads = e->produced_flows = false;
+    if (e->flow.enabled) {
+        e->flow.jobs.assign((size_t)n_frames, FlowFrameJobs{});
+        e->flow.stats_backup = e->flow.stats;
+    }
     e->feat_frames = 0;
     e->feat_dep_in_batch = false;
     e->new_mask_frames = e->plain_mask_frames = 0;
@@ -540,22 +654,36 @@ int roft_frames_submit_labels(roft_engine* e, const roft_frame_input* inputs, co
     e->label_members.clear();
     e->label_table_bytes = 0;
     e->gather.clear();
-    int rc = submit_frames(e, inputs, labels, n_objects, n_frames);
+    int rc = submit_frames(e, inputs, labels, images, n_objects, n_frames);
     if (rc == ROFT_OK) rc = flush_gather(e);
     e->gather.clear();
     HP_MARK(e, 1, hp_t);
     int rc2 = ROFT_OK;
-    if (e->had_uploads) {
+    BatchSlot& bs = e->slot_of(e->batch_counter);
+    hipEvent_t ev_wait = nullptr;   // what the host waits for: the copies
+    if (rc == ROFT_OK && e->produced_flows) {
+        // Camera images: the production follows the copies on the upload stream.  The streams wait for ev_up, recorded behind the
+        // production; the host for ev_host, recorded behind the copies alone -- and for nothing when nothing was copied.
+        hipError_t err = hipSuccess;
+        if (e->had_uploads) { err = hipEventRecord(bs.ev_host, e->up_stream); ev_wait = bs.ev_host; }
+        if (err == hipSuccess) rc = enqueue_flow_production(e, n_frames);
+        if (err == hipSuccess && rc == ROFT_OK) err = hipEventRecord(bs.ev_up, e->up_stream);
+        if (err != hipSuccess) rc2 = fail(ROFT_ERR_DEVICE, std::string("flow production: ") + hipGetErrorString(err));
+    } else if (e->had_uploads) {
+        hipError_t err = hipEventRecord(bs.ev_up, e->up_stream);
+        if (err != hipSuccess) rc2 = fail(ROFT_ERR_DEVICE, std::string("input upload: ") + hipGetErrorString(err));
+        ev_wait = bs.ev_up;
+    }
+    if (ev_wait && rc2 == ROFT_OK) {
         // HOST buffers belong to the caller again when this call returns
-        const hipEvent_t ev_up = e->slot_of(e->batch_counter).ev_up;
-        hipError_t err = hipEventRecord(ev_up, e->up_stream);
-        if (err == hipSuccess) err = hipEventSynchronize(ev_up);
+        const hipError_t err = hipEventSynchronize(ev_wait);
         if (err != hipSuccess) rc2 = fail(ROFT_ERR_DEVICE, std::string("input upload: ") + hipGetErrorString(err));
     }
     HP_MARK(e, 2, hp_t);
     if (rc != ROFT_OK || rc2 != ROFT_OK) {
         const std::string msg = last_error();
         for (size_t i = 0; i < e->objs.size(); ++i) e->objs[i]->s = e->backup[i];
+        if (e->flow.enabled) e->flow.stats = e->flow.stats_backup;
         return fail(rc != ROFT_OK ? rc : rc2, msg);
     }
     e->cur_T = n_frames;
@@ -570,5 +698,46 @@ int roft_frame_submit(roft_engine* e, const roft_frame_input* inputs, int n_inpu
     return roft_frames_submit(e, inputs, n_inputs, 1);
 }
 
+// The configurations the producer serves are the two products of the reference's flow source: CV_32FC2 on the pixel grid, CV_16SC2
+// S10.5 on a grid of 4 (ImageOpticalFlowNVOF.cpp:19-80).
+int roft_engine_enable_flow(roft_engine* e, const roft_of_params* p)
+{
+    if (!e) return fail(ROFT_ERR_INVALID, "null engine");
+    if (e->frame_counter > 0 || e->submitted) return fail(ROFT_ERR_STATE, "roft_engine_enable_flow must precede the first frame");
+    roft_of_params prm;
+    if (p) prm = *p; else (void)roft_default_of_params(&prm);
+    const roft_config& cfg = e->cfg;
+    if (cfg.flow_type == ROFT_FLOW_F32C2 && (cfg.flow_grid != 1 || cfg.flow_scale != 1.0f))
+        return fail(ROFT_ERR_INVALID, "the producer's CV_32FC2 flow has flow_grid 1 and flow_scale 1");
+    if (cfg.flow_type == ROFT_FLOW_S16C2 && (cfg.flow_grid != 4 || cfg.flow_scale != 32.0f))
+        return fail(ROFT_ERR_INVALID, "the producer's CV_16SC2 flow has flow_grid 4 and flow_scale 32");
+    if (int rc = roft::of_check_params(cfg.cam.width, cfg.cam.height, &prm)) return rc;
+    HIP_TRY(hipSetDevice(cfg.device));
+    EngineFlow& f = e->flow;
+    of_geometry(f.geom, cfg.cam.width, cfg.cam.height, prm.levels, prm.radius, prm.iterations, prm.det_min);
+    HIP_TRY(f.coarse.ensure((size_t)kOfChunk * f.geom.flow_stride));
+    if (cfg.flow_type == ROFT_FLOW_S16C2) HIP_TRY(f.field.ensure((size_t)kOfChunk * 2 * cfg.cam.width * cfg.cam.height));
+    for (auto& g : f.pyr) for (auto* b : g) delete b;   // (enabled again with other levels: another pyramid size)
+    f.pyr.assign((size_t)e->T_max + 1, std::vector<DevBuf<float>*>());
+    f.prm = prm;
+    f.enabled = true;
+    return ROFT_OK;
+}
 
+int roft_engine_get_flow(roft_engine* e, int obj_id, void* flow_out)
+{
+    if (!e || !flow_out) return fail(ROFT_ERR_INVALID, "null argument");
+    if (obj_id < 0 || obj_id >= (int)e->objs.size()) return fail(ROFT_ERR_INVALID, "bad obj_id");
+    const void* src = e->objs[obj_id]->stepped_flow;
+    if (!src) return fail(ROFT_ERR_STATE, "the engine produced no flow for the object's last stepped frame");
+    if (int rc = roft_sync(e)) return rc;
+    HIP_TRY(hipMemcpy(flow_out, src, flow_bytes(e->arr.a.ffmt), hipMemcpyDeviceToHost));
+    return ROFT_OK;
+}
 
+int roft_engine_get_flow_stats(roft_engine* e, roft_engine_flow_stats* out)
+{
+    if (!e || !out) return fail(ROFT_ERR_INVALID, "null argument");
+    *out = e->flow.stats;
+    return ROFT_OK;
+}

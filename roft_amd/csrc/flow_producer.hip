@@ -13,7 +13,7 @@
 using namespace roft;
 
 extern "C" const char* roft_last_error_string(void);
-namespace roft { int set_last_error(int code, const std::string& msg); }
+namespace roft { int set_last_error(int code, const std::string& msg); int of_check_params(int W, int H, const roft_of_params* p); }
 
 #define OF_TRY(expr)                                                                                       \
     do {                                                                                                   \
@@ -25,13 +25,21 @@ struct roft_flow_producer {
     int W = 0, H = 0, max_pairs = 0, out_type = 0, device = 0;
     roft_of_params prm{};
     hipStream_t stream = nullptr;
-    OfArgs args{};
-    float* pyr = nullptr;
-    float* coarse = nullptr;
+    OfGeom geom{};
+    float* pyr = nullptr;               // [2 * max_pairs][pyr_stride]: one pyramid per DISTINCT image of a call
+    float* coarse = nullptr;            // [max_pairs][flow_stride]
     float* field = nullptr;             // [max_pairs][H*W*2] level-0 fields when the product is CV_16SC2
-    void** d_ptrs = nullptr;            // device copy of the pointer tables: prev | cur | out_f32 | out_s16
-    void** h_ptrs = nullptr;            // pinned staging of the same
 };
+
+// the ranges roft_flow_producer_create accepts (roft_engine_enable_flow asks the same question)
+int roft::of_check_params(int W, int H, const roft_of_params* p)
+{
+    if (p->levels < 1 || p->levels > 6 || p->radius < 1 || p->radius > 7 || p->iterations < 0)
+        return roft::set_last_error(ROFT_ERR_INVALID, "levels 1..6, radius 1..7");
+    if (W <= 0 || H <= 0 || (W % (4 << (p->levels - 1))) || (H % (1 << (p->levels - 1))) || (W % 4) || (H % 4))
+        return roft::set_last_error(ROFT_ERR_INVALID, "width must be a multiple of 4 * 2^(levels-1), height of 2^(levels-1) and of 4");
+    return ROFT_OK;
+}
 
 extern "C" {
 
@@ -49,10 +57,7 @@ int roft_flow_producer_create(int W, int H, int max_pairs, const roft_of_params*
                               roft_flow_producer** out)
 {
     if (!p || !out || max_pairs <= 0) return roft::set_last_error(ROFT_ERR_INVALID, "bad argument");
-    if (p->levels < 1 || p->levels > 6 || p->radius < 1 || p->radius > 7 || p->iterations < 0)
-        return roft::set_last_error(ROFT_ERR_INVALID, "levels 1..6, radius 1..7");
-    if (W <= 0 || H <= 0 || (W % (4 << (p->levels - 1))) || (H % (1 << (p->levels - 1))) || (W % 4) || (H % 4))
-        return roft::set_last_error(ROFT_ERR_INVALID, "width must be a multiple of 4 * 2^(levels-1), height of 2^(levels-1) and of 4");
+    if (int rc = roft::of_check_params(W, H, p)) return rc;
     if (out_type != ROFT_FLOW_F32C2 && out_type != ROFT_FLOW_S16C2) return roft::set_last_error(ROFT_ERR_INVALID, "bad out_type");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device)
@@ -61,24 +66,11 @@ int roft_flow_producer_create(int W, int H, int max_pairs, const roft_of_params*
     roft_flow_producer* fp = new roft_flow_producer();
     fp->W = W; fp->H = H; fp->max_pairs = max_pairs; fp->out_type = out_type; fp->device = device; fp->prm = *p;
     OF_TRY(hipStreamCreateWithFlags(&fp->stream, hipStreamNonBlocking));
-    OfArgs& a = fp->args;
-    a.levels = p->levels; a.radius = p->radius; a.iterations = p->iterations; a.det_min = p->det_min;
-    size_t off = 0, foff = 0;
-    for (int l = 0; l < p->levels; ++l) {
-        a.lv[l].w = W >> l; a.lv[l].h = H >> l; a.lv[l].off = off;
-        off += (size_t)a.lv[l].w * a.lv[l].h;
-        off = (off + 3) & ~(size_t)3;
-        a.flow_off[l] = foff;
-        if (l >= 1) foff += 2 * (size_t)a.lv[l].w * a.lv[l].h;
-    }
-    a.pyr_stride = off;
-    a.flow_stride = std::max<size_t>(foff, 2);
+    OfGeom& a = fp->geom;
+    of_geometry(a, W, H, p->levels, p->radius, p->iterations, p->det_min);
     OF_TRY(hipMalloc(reinterpret_cast<void**>(&fp->pyr), sizeof(float) * 2 * a.pyr_stride * max_pairs));
     OF_TRY(hipMalloc(reinterpret_cast<void**>(&fp->coarse), sizeof(float) * a.flow_stride * max_pairs));
     if (out_type == ROFT_FLOW_S16C2) OF_TRY(hipMalloc(reinterpret_cast<void**>(&fp->field), sizeof(float) * 2 * W * H * max_pairs));
-    OF_TRY(hipMalloc(reinterpret_cast<void**>(&fp->d_ptrs), sizeof(void*) * 4 * max_pairs));
-    OF_TRY(hipHostMalloc(reinterpret_cast<void**>(&fp->h_ptrs), sizeof(void*) * 4 * max_pairs));
-    a.pyr = fp->pyr; a.coarse = fp->coarse;
     *out = fp;
     return ROFT_OK;
 }
@@ -91,8 +83,6 @@ int roft_flow_producer_destroy(roft_flow_producer* fp)
     if (fp->pyr) (void)hipFree(fp->pyr);
     if (fp->coarse) (void)hipFree(fp->coarse);
     if (fp->field) (void)hipFree(fp->field);
-    if (fp->d_ptrs) (void)hipFree(fp->d_ptrs);
-    if (fp->h_ptrs) (void)hipHostFree(fp->h_ptrs);
     if (fp->stream) (void)hipStreamDestroy(fp->stream);
     delete fp;
     return ROFT_OK;
@@ -103,27 +93,37 @@ int roft_flow_producer_run(roft_flow_producer* fp, const uint8_t* const* prev, c
 {
     if (!fp || !prev || !cur || !out || n <= 0 || n > fp->max_pairs) return roft::set_last_error(ROFT_ERR_INVALID, "bad argument");
     OF_TRY(hipSetDevice(fp->device));
-    OF_TRY(hipStreamSynchronize(fp->stream));   // the pinned pointer table is reused
-    const int m = fp->max_pairs;
-    for (int i = 0; i < n; ++i) {
+    for (int i = 0; i < n; ++i)
         if (!prev[i] || !cur[i] || !out[i] || (reinterpret_cast<uintptr_t>(prev[i]) & 3) || (reinterpret_cast<uintptr_t>(cur[i]) & 3) ||
             (reinterpret_cast<uintptr_t>(out[i]) & 7))
             return roft::set_last_error(ROFT_ERR_INVALID, "null or misaligned image / flow pointer (images 4 B, flow 8 B)");
-        fp->h_ptrs[i] = const_cast<uint8_t*>(prev[i]);
-        fp->h_ptrs[m + i] = const_cast<uint8_t*>(cur[i]);
-        fp->h_ptrs[2 * m + i] = (fp->out_type == ROFT_FLOW_F32C2) ? out[i] : (void*)(fp->field + (size_t)i * 2 * fp->W * fp->H);
-        fp->h_ptrs[3 * m + i] = out[i];
+    // one pyramid per distinct image of the call (the frames of a stream are each the `cur` of one pair and the `prev` of the next)
+    const OfGeom& g = fp->geom;
+    std::vector<const uint8_t*> images;
+    auto pyramid_of = [&](const uint8_t* img) -> float* {
+        size_t k = std::find(images.begin(), images.end(), img) - images.begin();
+        if (k == images.size()) images.push_back(img);
+        return fp->pyr + k * g.pyr_stride;
+    };
+    std::vector<OfPairs> chunks((size_t)(n + kOfChunk - 1) / kOfChunk, OfPairs{});
+    for (int i = 0; i < n; ++i) {
+        OfPairs& c = chunks[(size_t)i / kOfChunk];
+        const int k = c.n++;
+        c.pyr0[k] = pyramid_of(prev[i]);
+        c.pyr1[k] = pyramid_of(cur[i]);
+        c.coarse[k] = fp->coarse + (size_t)i * g.flow_stride;
+        c.field[k] = (fp->out_type == ROFT_FLOW_F32C2) ? static_cast<float*>(out[i]) : fp->field + (size_t)i * 2 * fp->W * fp->H;
+        c.out_s16[k] = (fp->out_type == ROFT_FLOW_S16C2) ? static_cast<int16_t*>(out[i]) : nullptr;
     }
-    OF_TRY(hipMemcpyAsync(fp->d_ptrs, fp->h_ptrs, sizeof(void*) * 4 * m, hipMemcpyHostToDevice, fp->stream));
-    OfArgs a = fp->args;
-    a.n = n;
-    a.prev = reinterpret_cast<const uint8_t* const*>(fp->d_ptrs);
-    a.cur = reinterpret_cast<const uint8_t* const*>(fp->d_ptrs + m);
-    a.out_f32 = reinterpret_cast<float* const*>(fp->d_ptrs + 2 * m);
-    launch_optical_flow(a, fp->stream);
-    if (fp->out_type == ROFT_FLOW_S16C2)
-        launch_flow_quantise(reinterpret_cast<const float* const*>(fp->d_ptrs + 2 * m),
-                             reinterpret_cast<int16_t* const*>(fp->d_ptrs + 3 * m), n, fp->W, fp->H, fp->stream);
+    for (size_t i0 = 0; i0 < images.size(); i0 += kOfChunk) {
+        OfImages im{};
+        for (size_t i = i0; i < std::min(images.size(), i0 + kOfChunk); ++i) {
+            const int k = im.n++;
+            im.type[k] = kOfGray8; im.src[k] = images[i]; im.pyr[k] = fp->pyr + i * g.pyr_stride;
+        }
+        launch_of_pyramids(g, im, fp->stream);
+    }
+    for (const OfPairs& c : chunks) launch_of_pairs(g, c, fp->stream);
     OF_TRY(hipGetLastError());
     return ROFT_OK;
 }
@@ -167,6 +167,33 @@ int roft_optical_flow(const uint8_t* prev, const uint8_t* cur, int W, int H, con
     roft_flow_producer_destroy(fp);
     if (e != hipSuccess) return roft::set_last_error(ROFT_ERR_DEVICE, hipGetErrorString(e));
     return rc;
+}
+
+int roft_image_to_gray(const void* image, int image_type, int W, int H, uint8_t* gray_out)
+{
+    if (!image || !gray_out) return roft::set_last_error(ROFT_ERR_INVALID, "null argument");
+    if (image_type != ROFT_IMAGE_GRAY8 && image_type != ROFT_IMAGE_BGR8 && image_type != ROFT_IMAGE_RGB8)
+        return roft::set_last_error(ROFT_ERR_INVALID, "image_type must be ROFT_IMAGE_GRAY8, ROFT_IMAGE_BGR8 or ROFT_IMAGE_RGB8");
+    if (W < 1 || H < 1) return roft::set_last_error(ROFT_ERR_INVALID, "width and height must be at least 1");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        (void)hipGetLastError();
+        return roft::set_last_error(ROFT_ERR_DEVICE, "no HIP device (the conversion has no CPU path)");
+    }
+    const size_t npix = (size_t)W * H, ibytes = npix * (image_type == ROFT_IMAGE_GRAY8 ? 1 : 3);
+    uint8_t *d_in = nullptr, *d_out = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_in), ibytes);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_out), npix);
+    if (e == hipSuccess) e = hipMemcpy(d_in, image, ibytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        launch_image_to_gray(d_in, image_type, npix, d_out, nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(gray_out, d_out, npix, hipMemcpyDeviceToHost);
+    if (d_in) (void)hipFree(d_in);
+    if (d_out) (void)hipFree(d_out);
+    if (e != hipSuccess) return roft::set_last_error(ROFT_ERR_DEVICE, hipGetErrorString(e));
+    return ROFT_OK;
 }
 
 }  // extern "C"

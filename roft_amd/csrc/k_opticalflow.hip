@@ -12,6 +12,10 @@
 // tile with an (r + 1)-pixel halo and its gradient tile (Ix, Iy interleaved) are staged in LDS once and serve the G-matrix and the
 // residual taps of all 256 pixels; only the pixels of the current image under the warped window (whose position
 // depends on the evolving flow) go to the vector cache.  Batched over image pairs in blockIdx.z.
+//
+// Two stages (opticalflow.h): the pyramid of an IMAGE -- level 0 from the 8-bit image, gray or colour, and the means below it -- is
+// built once, by of_convert_kernel / of_down_kernel; the Lucas-Kanade levels of a PAIR read two pyramids by pointer.  In a camera
+// stream every image is the `cur` of one pair and the `prev` of the next: its pyramid serves both.
 #include <algorithm>
 
 #include "opticalflow.h"
@@ -21,23 +25,41 @@ namespace roft {
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-// level 0: u8 -> float, four pixels per thread
-__global__ __launch_bounds__(256) void of_convert_kernel(OfArgs a)
+// OpenCV's 8-bit COLOR_BGR2GRAY (fixed point, 14 fractional bits); `type` says which of c0, c2 is red
+__device__ __forceinline__ unsigned of_gray(unsigned c0, unsigned c1, unsigned c2, int type)
 {
-    const int pair = blockIdx.z, which = blockIdx.y;
-    const uint8_t* src = which ? a.cur[pair] : a.prev[pair];
-    float* dst = a.pyr + ((size_t)pair * 2 + which) * a.pyr_stride;
+    const unsigned r = type == kOfBgr8 ? c2 : c0, b = type == kOfBgr8 ? c0 : c2;
+    return (r * 4899u + c1 * 9617u + b * 1868u + 8192u) >> 14;
+}
+
+// level 0 of one image's pyramid: u8 -> float, four pixels per thread.  A colour image is converted on the way (twelve bytes in
+// three aligned words): the integer gray value is what a separate conversion pass would have stored as a byte.
+__global__ __launch_bounds__(256) void of_convert_kernel(OfGeom a, OfImages im)
+{
+    const int img = blockIdx.y, type = im.type[img];
+    float4* dst = reinterpret_cast<float4*>(im.pyr[img]);
     const int n4 = a.lv[0].w * a.lv[0].h / 4;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += gridDim.x * blockDim.x) {
-        const uchar4 v = reinterpret_cast<const uchar4*>(src)[i];
-        reinterpret_cast<float4*>(dst)[i] = make_float4((float)v.x, (float)v.y, (float)v.z, (float)v.w);
+    if (type == kOfGray8) {
+        const uchar4* src = reinterpret_cast<const uchar4*>(im.src[img]);
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += gridDim.x * blockDim.x) {
+            const uchar4 v = src[i];
+            dst[i] = make_float4((float)v.x, (float)v.y, (float)v.z, (float)v.w);
+        }
+    } else {
+        const unsigned* src = reinterpret_cast<const unsigned*>(im.src[img]);
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += gridDim.x * blockDim.x) {
+            const unsigned w0 = src[3 * (size_t)i], w1 = src[3 * (size_t)i + 1], w2 = src[3 * (size_t)i + 2];
+            dst[i] = make_float4((float)of_gray(w0 & 255u, (w0 >> 8) & 255u, (w0 >> 16) & 255u, type),
+                                 (float)of_gray(w0 >> 24, w1 & 255u, (w1 >> 8) & 255u, type),
+                                 (float)of_gray((w1 >> 16) & 255u, w1 >> 24, w2 & 255u, type),
+                                 (float)of_gray((w2 >> 8) & 255u, (w2 >> 16) & 255u, w2 >> 24, type));
+        }
     }
 }
 
-__global__ __launch_bounds__(256) void of_down_kernel(OfArgs a, int l)
+__global__ __launch_bounds__(256) void of_down_kernel(OfGeom a, OfImages im, int l)
 {
-    const int pair = blockIdx.z, which = blockIdx.y;
-    float* base = a.pyr + ((size_t)pair * 2 + which) * a.pyr_stride;
+    float* base = im.pyr[blockIdx.y];
     const float* src = base + a.lv[l - 1].off;
     float* dst = base + a.lv[l].off;
     const int w = a.lv[l].w, h = a.lv[l].h, ws = a.lv[l - 1].w;
@@ -46,6 +68,14 @@ __global__ __launch_bounds__(256) void of_down_kernel(OfArgs a, int l)
         const size_t i0 = (size_t)(2 * y) * ws + 2 * x, i1 = i0 + ws;
         dst[i] = 0.25f * (((src[i0] + src[i0 + 1]) + src[i1]) + src[i1 + 1]);
     }
+}
+
+// the stand-alone colour conversion: one pixel per thread, any size
+__global__ __launch_bounds__(256) void image_to_gray_kernel(const uint8_t* __restrict__ src, int type, size_t npix, uint8_t* __restrict__ dst)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npix) return;
+    dst[i] = type == kOfGray8 ? src[i] : (uint8_t)of_gray(src[3 * i], src[3 * i + 1], src[3 * i + 2], type);
 }
 
 __device__ __forceinline__ float at_g(const float* I, int w, int h, int x, int y)
@@ -62,7 +92,7 @@ constexpr int kOfTx = 32, kOfTy = 8;
 // row by row (horizontal pass in registers, vertical pass against the previous row) -- 64 cached loads per iteration
 // at r = 3 instead of 4 per tap.
 template <int RT>
-__global__ __launch_bounds__(kOfTx * kOfTy) void of_lk_kernel(OfArgs a, int l)
+__global__ __launch_bounds__(kOfTx * kOfTy) void of_lk_kernel(OfGeom a, OfPairs pr, int l)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int r = RT ? RT : a.radius, R = r + 1;
@@ -72,8 +102,8 @@ __global__ __launch_bounds__(kOfTx * kOfTy) void of_lk_kernel(OfArgs a, int l)
     float2* grad = reinterpret_cast<float2*>(tile + ((tw * th + 1) & ~1));   // (Ix, Iy) interleaved: one 8-byte LDS read per tap
     const int pair = blockIdx.z;
     const int w = a.lv[l].w, h = a.lv[l].h;
-    const float* I0 = a.pyr + ((size_t)pair * 2 + 0) * a.pyr_stride + a.lv[l].off;
-    const float* I1 = a.pyr + ((size_t)pair * 2 + 1) * a.pyr_stride + a.lv[l].off;
+    const float* I0 = pr.pyr0[pair] + a.lv[l].off;
+    const float* I1 = pr.pyr1[pair] + a.lv[l].off;
     const int x0 = blockIdx.x * kOfTx, y0 = blockIdx.y * kOfTy;
     const int tid = threadIdx.y * kOfTx + threadIdx.x;
     for (int i = tid; i < tw * th; i += kOfTx * kOfTy) {
@@ -92,8 +122,7 @@ __global__ __launch_bounds__(kOfTx * kOfTy) void of_lk_kernel(OfArgs a, int l)
 
     float dx = 0.0f, dy = 0.0f;
     if (l < a.levels - 1) {
-        const float* c = a.coarse + (size_t)pair * a.flow_stride + a.flow_off[l + 1] +
-                         2 * ((size_t)(y >> 1) * a.lv[l + 1].w + (x >> 1));
+        const float* c = pr.coarse[pair] + a.flow_off[l + 1] + 2 * ((size_t)(y >> 1) * a.lv[l + 1].w + (x >> 1));
         dx = 2.0f * c[0];
         dy = 2.0f * c[1];
     }
@@ -148,49 +177,57 @@ __global__ __launch_bounds__(kOfTx * kOfTy) void of_lk_kernel(OfArgs a, int l)
             dy -= (g11 * b2 - g12 * b1) * inv;
         }
     }
-    float* dst = (l == 0) ? a.out_f32[pair] : a.coarse + (size_t)pair * a.flow_stride + a.flow_off[l];
+    float* dst = (l == 0) ? pr.field[pair] : pr.coarse[pair] + a.flow_off[l];
     reinterpret_cast<float2*>(dst)[(size_t)y * w + x] = make_float2(dx, dy);
 }
 
 // CV_16SC2 grid 4: block-centre sample, S10.5, saturated
-__global__ __launch_bounds__(256) void of_quantise_kernel(const float* const* field, int16_t* const* out, int W, int H)
+__global__ __launch_bounds__(256) void of_quantise_kernel(OfPairs pr, int W, int H)
 {
     const int pair = blockIdx.y;
     const int gw = W / 4, gh = H / 4;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= gw * gh) return;
     const int gy = i / gw, gx = i - gy * gw;
-    const float2 v = reinterpret_cast<const float2*>(field[pair])[(size_t)(4 * gy + 2) * W + (4 * gx + 2)];
+    const float2 v = reinterpret_cast<const float2*>(pr.field[pair])[(size_t)(4 * gy + 2) * W + (4 * gx + 2)];
     const float qx = fminf(fmaxf(rintf(v.x * 32.0f), -32768.0f), 32767.0f);
     const float qy = fminf(fmaxf(rintf(v.y * 32.0f), -32768.0f), 32767.0f);
-    reinterpret_cast<short2*>(out[pair])[i] = make_short2((short)qx, (short)qy);
+    reinterpret_cast<short2*>(pr.out_s16[pair])[i] = make_short2((short)qx, (short)qy);
 }
 
-void launch_optical_flow(const OfArgs& a, hipStream_t s)
+void launch_of_pyramids(const OfGeom& a, const OfImages& im, hipStream_t s)
 {
     const int n4 = a.lv[0].w * a.lv[0].h / 4;
-    hipLaunchKernelGGL(of_convert_kernel, dim3(std::min((n4 + 255) / 256, 256), 2, a.n), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(of_convert_kernel, dim3(std::min((n4 + 255) / 256, 256), im.n), dim3(256), 0, s, a, im);
     for (int l = 1; l < a.levels; ++l) {
         const int npx = a.lv[l].w * a.lv[l].h;
-        hipLaunchKernelGGL(of_down_kernel, dim3(std::min((npx + 255) / 256, 256), 2, a.n), dim3(256), 0, s, a, l);
+        hipLaunchKernelGGL(of_down_kernel, dim3(std::min((npx + 255) / 256, 256), im.n), dim3(256), 0, s, a, im, l);
     }
+}
+
+void launch_of_pairs(const OfGeom& a, const OfPairs& pr, hipStream_t s)
+{
     const int r = a.radius, R = r + 1;
     const size_t lds = ((((size_t)(kOfTx + 2 * R) * (kOfTy + 2 * R) + 1) & ~(size_t)1) + 2 * (size_t)(kOfTx + 2 * r) * (kOfTy + 2 * r)) * sizeof(float);
     for (int l = a.levels - 1; l >= 0; --l) {
-        const dim3 grid((a.lv[l].w + kOfTx - 1) / kOfTx, (a.lv[l].h + kOfTy - 1) / kOfTy, a.n), block(kOfTx, kOfTy);
+        const dim3 grid((a.lv[l].w + kOfTx - 1) / kOfTx, (a.lv[l].h + kOfTy - 1) / kOfTy, pr.n), block(kOfTx, kOfTy);
         switch (r) {
-            case 1: hipLaunchKernelGGL(of_lk_kernel<1>, grid, block, lds, s, a, l); break;
-            case 2: hipLaunchKernelGGL(of_lk_kernel<2>, grid, block, lds, s, a, l); break;
-            case 3: hipLaunchKernelGGL(of_lk_kernel<3>, grid, block, lds, s, a, l); break;
-            case 4: hipLaunchKernelGGL(of_lk_kernel<4>, grid, block, lds, s, a, l); break;
-            default: hipLaunchKernelGGL(of_lk_kernel<0>, grid, block, lds, s, a, l); break;
+            case 1: hipLaunchKernelGGL(of_lk_kernel<1>, grid, block, lds, s, a, pr, l); break;
+            case 2: hipLaunchKernelGGL(of_lk_kernel<2>, grid, block, lds, s, a, pr, l); break;
+            case 3: hipLaunchKernelGGL(of_lk_kernel<3>, grid, block, lds, s, a, pr, l); break;
+            case 4: hipLaunchKernelGGL(of_lk_kernel<4>, grid, block, lds, s, a, pr, l); break;
+            default: hipLaunchKernelGGL(of_lk_kernel<0>, grid, block, lds, s, a, pr, l); break;
         }
+    }
+    if (pr.out_s16[0]) {
+        const int W = a.lv[0].w, H = a.lv[0].h;
+        hipLaunchKernelGGL(of_quantise_kernel, dim3(((W / 4) * (H / 4) + 255) / 256, pr.n), dim3(256), 0, s, pr, W, H);
     }
 }
 
-void launch_flow_quantise(const float* const* field, int16_t* const* out, int n, int W, int H, hipStream_t s)
+void launch_image_to_gray(const uint8_t* src, int type, size_t npix, uint8_t* dst, hipStream_t s)
 {
-    hipLaunchKernelGGL(of_quantise_kernel, dim3(((W / 4) * (H / 4) + 255) / 256, n), dim3(256), 0, s, field, out, W, H);
+    hipLaunchKernelGGL(image_to_gray_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, src, type, npix, dst);
 }
 
 }  // namespace roft

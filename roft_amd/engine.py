@@ -69,6 +69,7 @@ class ROFTFilterBatch:
         self.n_objects += 1
         self._inputs = (L.FrameInput * self.n_objects)()
         self._labels = (L.LabelMask * self.n_objects)()
+        self._images = (L.FrameImage * self.n_objects)()
         self._meshes = getattr(self, "_meshes", []) + [(verts, tris)]   # render_log draws them
         return oid.value
 
@@ -77,21 +78,46 @@ class ROFTFilterBatch:
         mem_kind; depth/flow/mask are numpy arrays (HOST) or integer device addresses (DEVICE).
         Instead of `mask`: `labels` (one H x W uint8 / uint16 label image, typically the same array for every object of the
         frame; or an address, then with `label_type` L.LABEL_U8 / L.LABEL_U16) and `label`: the object's mask is the pixels
-        EQUAL to that value (roft_frames_submit_labels)."""
-        if self._fill(frames):
+        EQUAL to that value (roft_frames_submit_labels).
+        Instead of `flow`, on an engine with enable_flow(): `image`, the camera image of the frame (numpy [H, W] gray or
+        [H, W, 3]; or an address, then with `image_type` L.IMAGE_GRAY8 / IMAGE_BGR8 / IMAGE_RGB8; a 3-channel array is RGB8
+        unless `image_type` says BGR8): the engine computes the flow from it and the frame before (roft_frames_submit_images)."""
+        any_labels = self._fill(frames)
+        if self._any_images:
+            L.check(L.lib().roft_frames_submit_images(self._h, self._inputs, self._labels if any_labels else None, self._images,
+                                                      self.n_objects, 1))
+        elif any_labels:
             L.check(L.lib().roft_frames_submit_labels(self._h, self._inputs, self._labels, self.n_objects, 1))
         else:
             L.check(L.lib().roft_frame_submit(self._h, self._inputs, self.n_objects))
 
     def _fill(self, frames):
-        """Fills self._inputs and self._labels; returns whether an object of the frame takes its mask from a label image."""
+        """Fills self._inputs, self._labels and self._images (self._any_images: an object of the frame brings a camera image);
+        returns whether an object of the frame takes its mask from a label image."""
         assert len(frames) == self.n_objects
         keep = []
-        shared = {}   # one contiguous copy per distinct label array of the frame: the engine uploads a host pointer once
+        shared = {}   # one contiguous copy per distinct label / camera image array of the frame: the engine uploads a host pointer once
         any_labels = False
+        self._any_images = False
         for i, f in enumerate(frames):
             fi = self._inputs[i]
             lm = self._labels[i]
+            im = self._images[i]
+            img = f.get("image")
+            if img is None:
+                im.image, im.image_type = None, 0
+            else:
+                self._any_images = True
+                if isinstance(img, int):
+                    im.image, im.image_type = img, int(f["image_type"])
+                else:
+                    if img.dtype != np.uint8 or not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] == 3)):
+                        raise TypeError("a camera image is [H, W] or [H, W, 3] uint8")
+                    v = shared.get(id(img))
+                    if v is None:
+                        v = shared[id(img)] = np.ascontiguousarray(img)
+                        keep.append(v)
+                    im.image, im.image_type = v.ctypes.data, int(f.get("image_type", L.IMAGE_GRAY8 if v.ndim == 2 else L.IMAGE_RGB8))
             lab = f.get("labels")
             if lab is None:
                 lm.labels, lm.label_type, lm.label = None, 0, 0
@@ -135,13 +161,14 @@ class ROFTFilterBatch:
 
     def build_inputs(self, frames):
         """Pre-build the ctypes input array of one frame (see submit) for submit_raw."""
-        saved = self._inputs, self._labels
+        saved = self._inputs, self._labels, self._images
         self._inputs = (L.FrameInput * self.n_objects)()
         self._labels = (L.LabelMask * self.n_objects)()
-        if self._fill(frames):
-            raise ValueError("label images go through build_batch / submit_batch_raw(..., labels=...)")
+        self._images = (L.FrameImage * self.n_objects)()
+        if self._fill(frames) or self._any_images:
+            raise ValueError("label and camera images go through build_batch / submit_batch_raw(..., labels=..., images=...)")
         arr, keep = self._inputs, self._keep
-        self._inputs, self._labels = saved
+        self._inputs, self._labels, self._images = saved
         return arr, keep
 
     def submit_raw(self, inputs):
@@ -149,22 +176,29 @@ class ROFTFilterBatch:
 
     def build_batch(self, frames_list):
         """ctypes input array of a batch: frames_list[t] = one dict per object (see submit), t = 0 .. T-1.  When a frame uses
-        label images the returned `keep` ends with the batch's L.LabelMask array: see batch_labels."""
+        label images the returned `keep` ends with the batch's L.LabelMask array (see batch_labels); when one brings camera images,
+        the batch's L.FrameImage array comes before it (see batch_images)."""
         T = len(frames_list)
         arr = (L.FrameInput * (self.n_objects * T))()
         lab = (L.LabelMask * (self.n_objects * T))()
+        img = (L.FrameImage * (self.n_objects * T))()
         keep = []
-        saved = self._inputs, self._labels
-        any_labels = False
+        saved = self._inputs, self._labels, self._images
+        any_labels = any_images = False
         for t, frames in enumerate(frames_list):
             self._inputs = (L.FrameInput * self.n_objects)()
             self._labels = (L.LabelMask * self.n_objects)()
+            self._images = (L.FrameImage * self.n_objects)()
             any_labels = self._fill(frames) or any_labels
+            any_images = any_images or self._any_images
             for i in range(self.n_objects):
                 arr[t * self.n_objects + i] = self._inputs[i]
                 lab[t * self.n_objects + i] = self._labels[i]
+                img[t * self.n_objects + i] = self._images[i]
             keep.append(self._keep)
-        self._inputs, self._labels = saved
+        self._inputs, self._labels, self._images = saved
+        if any_images:
+            keep.append(img)
         if any_labels:
             keep.append(lab)
         return arr, keep, T
@@ -174,18 +208,49 @@ class ROFTFilterBatch:
         """The L.LabelMask array of a batch built by build_batch, or None when no frame of it uses label images."""
         return keep[-1] if keep and isinstance(keep[-1], C.Array) and keep[-1]._type_ is L.LabelMask else None
 
+    @staticmethod
+    def batch_images(keep):
+        """The L.FrameImage array of a batch built by build_batch, or None when no frame of it brings camera images."""
+        for v in keep[-2:]:
+            if isinstance(v, C.Array) and v._type_ is L.FrameImage:
+                return v
+        return None
+
     def submit_batch(self, frames_list):
-        """A batch of consecutive frames (at most cfg.max_batch_frames): roft_frames_submit, or roft_frames_submit_labels when a
-        frame takes masks from label images."""
+        """A batch of consecutive frames (at most cfg.max_batch_frames): roft_frames_submit, roft_frames_submit_labels when a
+        frame takes masks from label images, roft_frames_submit_images when one brings camera images."""
         arr, keep, T = self.build_batch(frames_list)
         self._keep = keep
-        self.submit_batch_raw(arr, T, self.batch_labels(keep))
+        self.submit_batch_raw(arr, T, self.batch_labels(keep), self.batch_images(keep))
 
-    def submit_batch_raw(self, arr, T, labels=None):
-        if labels is None:
+    def submit_batch_raw(self, arr, T, labels=None, images=None):
+        if images is not None:
+            L.check(L.lib().roft_frames_submit_images(self._h, arr, labels, images, self.n_objects, T))
+        elif labels is None:
             L.check(L.lib().roft_frames_submit(self._h, arr, self.n_objects, T))
         else:
             L.check(L.lib().roft_frames_submit_labels(self._h, arr, labels, self.n_objects, T))
+
+    def enable_flow(self, **of_params):
+        """Camera images instead of flow frames (frame key `image`): the engine computes the optical flow itself, with the
+        parameters of ops.of_params (levels, radius, iterations, det_min).  Before the first frame."""
+        from .ops import of_params as make
+        p = make(**of_params)
+        L.check(L.lib().roft_engine_enable_flow(self._h, C.byref(p)))
+
+    def flow_stats(self):
+        """images / image_bytes taken in, pyramids built, pairs (flows) produced since the engine was created."""
+        st = L.EngineFlowStats()
+        L.check(L.lib().roft_engine_get_flow_stats(self._h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in L.EngineFlowStats._fields_}
+
+    def produced_flow(self, obj):
+        """The flow the engine produced for object `obj`'s last stepped frame, in the engine's flow type: float32 [H, W, 2] or
+        int16 [H / 4, W / 4, 2].  Syncs; raises when that frame had none."""
+        g = self.cfg.flow_grid
+        out = np.zeros((self.H // g, self.W // g, 2), np.float32 if self.cfg.flow_type == L.FLOW_F32C2 else np.int16)
+        L.check(L.lib().roft_engine_get_flow(self._h, obj, out.ctypes.data))
+        return out
 
     def retain_frames(self):
         return L.lib().roft_engine_retain_frames(self._h)

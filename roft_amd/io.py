@@ -354,8 +354,14 @@ class Sequence:
     def __len__(self):
         return self.n
 
-    def frame(self, k):
-        ok, flow = read_flow(os.path.join(self.flow_dir, "%d.float" % k))
+    def frame(self, k, with_image=False):
+        """with_image: the camera frame rgb/<k>.png as `image` (RGB8, or GRAY8 for a one-channel file) in place of the flow
+        frame -- for an engine that computes the flow itself (ROFTFilterBatch.enable_flow); no flow file is read."""
+        if with_image:
+            img = read_png(os.path.join(self.root, "rgb", "%d.png" % k))
+            ok, flow = False, None
+        else:
+            ok, flow = read_flow(os.path.join(self.flow_dir, "%d.float" % k))
         mi, pi = self.mask_src[k], self.pose_src[k]
         mask = None
         if mi >= 0:
@@ -365,8 +371,11 @@ class Sequence:
         if pi >= 0 and self.pose_ok[pi]:
             pose = (self.poses[pi, :3], self.poses[pi, 3:])
         dt = float(self.stamp[k] - self.stamp[k - 1]) if k > 0 else 0.0
-        return dict(depth=read_depth(os.path.join(self.depth_dir, "%d.float" % k)), flow=flow if ok else None,
-                    mask=mask, pose=pose, dt=dt)
+        out = dict(depth=read_depth(os.path.join(self.depth_dir, "%d.float" % k)), flow=flow if ok else None,
+                   mask=mask, pose=pose, dt=dt)
+        if with_image:
+            out["image"] = img if img.ndim == 2 else np.ascontiguousarray(img[..., :3])
+        return out
 
 
 # ---- writing a stream in the Fast-YCB layout (synthetic data on disk, closes the loop with Sequence / the dumper) ----

@@ -254,6 +254,23 @@ def optical_flow(prev_gray, cur_gray, flow_type=L.FLOW_F32C2, **kw):
     return out
 
 
+def image_to_gray(image, image_type=None):
+    """The gray image (H x W uint8) of an 8-bit camera image by the device's conversion (roft_image_to_gray): OpenCV's fixed-point
+    COLOR_BGR2GRAY.  image: [H, W] (gray, passes through) or [H, W, 3]; image_type L.IMAGE_BGR8 / L.IMAGE_RGB8 (default RGB8,
+    the order PNG stores)."""
+    img = np.ascontiguousarray(image, np.uint8)
+    if img.ndim == 2:
+        image_type = L.IMAGE_GRAY8 if image_type is None else image_type
+    elif img.ndim == 3 and img.shape[2] == 3:
+        image_type = L.IMAGE_RGB8 if image_type is None else image_type
+    else:
+        raise ValueError("an [H, W] or [H, W, 3] uint8 image expected")
+    H, W = img.shape[:2]
+    out = np.zeros((H, W), np.uint8)
+    L.check(L.lib().roft_image_to_gray(_p(img), image_type, W, H, _p(out)))
+    return out
+
+
 class FlowProducer:
     """Batched device-resident producer (roft_flow_producer_*): `run` takes lists of device pointers."""
 

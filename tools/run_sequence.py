@@ -3,7 +3,8 @@
 files (`pose_estimate`, `velocity_estimate`, ROFTFilter.cpp:386-394) -- what `test/test.sh` does with `ROFT-tracker`.
 
   run_sequence.py --root DIR --object NAME --mesh model.obj [--flow-set nvof_1_slow] [--mask-set NAME]
-                  [--pose-set dope] [--out PREFIX] [--compute-flow nvof1|nvof2] [--no-delay] [--init-pose x y z qw qx qy qz]
+                  [--pose-set dope] [--out PREFIX] [--compute-flow nvof1|nvof2 | --flow-on-engine nvof1|nvof2] [--no-delay]
+                  [--init-pose x y z qw qx qy qz]
                   [--start-at-first-detection] [--score-on-device] [--render-overlay DIR]
                   [--from config_fast_ycb.cfg [--group::key value ...]]
 
@@ -12,7 +13,9 @@ config/config_ho3d.cfg) and applies `--a::b::c value` overrides exactly as ROFT-
 (roft_amd/config.py); without it the defaults of those files are used (roft_default_config / roft_default_object).
 
 The camera comes from DIR/cam_K.json (width, height, fx, fy, cx, cy).  --compute-flow first runs tools/flow_dumper.py
-on DIR/rgb (the MI355X replacement of the NVOF dumper) into DIR/optical_flow/<flow-set>.  With DIR/gt/poses.txt present
+on DIR/rgb (the MI355X replacement of the NVOF dumper) into DIR/optical_flow/<flow-set>.  --flow-on-engine hands the frames
+DIR/rgb/<i>.png to the engine instead, which computes the same flow itself (roft_frames_submit_images: the flow never leaves the
+device, no flow directory is read or written) -- the logs are those of --compute-flow, byte for byte.  With DIR/gt/poses.txt present
 the ADD-S / ADD AUC and the RMSE metrics of evaluation/metrics.py are printed as one JSON line.  --score-on-device adds the
 ADD-S and ADD of the same frames on EVERY vertex of the mesh, computed on the GPU from the engine's device-side log
 (roft_engine_score_log: the estimates never leave the device).  --render-overlay DIR draws the estimate over the sequence's
@@ -40,6 +43,8 @@ def main(argv=None):
     ap.add_argument("--pose-set", default="dope")
     ap.add_argument("--out", default=None)
     ap.add_argument("--compute-flow", choices=["nvof1", "nvof2"], default=None)
+    ap.add_argument("--flow-on-engine", choices=["nvof1", "nvof2"], default=None,
+                    help="hand the camera frames rgb/<i>.png to the engine, which computes the flow (nvof1: CV_16SC2 grid 4, nvof2: CV_32FC2)")
     ap.add_argument("--no-delay", action="store_true")
     ap.add_argument("--start-at-first-detection", action="store_true",
                     help="start where test/test_ho3d.sh:68-80 starts the tracker: at the frame and with the pose "
@@ -57,6 +62,8 @@ def main(argv=None):
     from roft_amd import engine as E
     from roft_amd import io, metrics
 
+    if args.compute_flow and args.flow_on_engine:
+        ap.error("--compute-flow and --flow-on-engine exclude each other")
     L.require_device()
     cam = json.load(open(os.path.join(args.root, "cam_K.json")))
     W, H = int(cam["width"]), int(cam["height"])
@@ -78,15 +85,18 @@ def main(argv=None):
             args.init_pose = aa[:3] + list(io.axis_angle_to_quat(np.array(aa[3:6]), aa[6]))
     seq = io.Sequence(args.root, args.object, flow_set=args.flow_set, mask_set=args.mask_set, pose_set=args.pose_set,
                       width=W, height=H, delayed=not args.no_delay, first_frame=start)
-    first = None
-    for k in range(len(seq)):
-        ok, first = io.read_flow(os.path.join(seq.flow_dir, "%d.float" % k))
-        if ok:
-            break
-    if first is None:
-        sys.stderr.write("no optical flow frames in %s\n" % seq.flow_dir)
-        return 1
-    ftype, grid, scale = io.flow_format(first, W)
+    if args.flow_on_engine:
+        ftype, grid, scale = (L.FLOW_S16C2, 4, 32.0) if args.flow_on_engine == "nvof1" else (L.FLOW_F32C2, 1, 1.0)
+    else:
+        first = None
+        for k in range(len(seq)):
+            ok, first = io.read_flow(os.path.join(seq.flow_dir, "%d.float" % k))
+            if ok:
+                break
+        if first is None:
+            sys.stderr.write("no optical flow frames in %s\n" % seq.flow_dir)
+            return 1
+        ftype, grid, scale = io.flow_format(first, W)
     init_from_cfg = False
     if args.cfg_file:
         from roft_amd import config as K
@@ -125,8 +135,10 @@ def main(argv=None):
         sys.stderr.write("the first detection arrives after the last frame\n")
         return 1
     eng.enable_log(n)
+    if args.flow_on_engine:
+        eng.enable_flow()
     for k in range(start, len(seq)):
-        eng.submit([seq.frame(k)])
+        eng.submit([seq.frame(k, with_image=bool(args.flow_on_engine))])
         eng.step()
     pose, twist, npts, sel = eng.get_log(0, n)
     gt_path = os.path.join(args.root, "gt", "poses.txt")
