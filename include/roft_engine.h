@@ -328,7 +328,8 @@ typedef struct {
 #define ROFT_RETAIN_FRAMES 16
 typedef struct {
     double dt;            /* RGB stamp delta; <= 0 means cfg.sample_time */
-    const float* depth;   /* H x W metres, 0 = invalid; required */
+    const float* depth;   /* H x W metres, 0 = invalid; required.  On an engine with roft_engine_enable_raw_depth (section 3c): a
+                             const uint16_t* image of the depth source's size instead, HOST or DEVICE like the others */
     const void* flow;     /* flow frame or NULL when absent (first frame) */
     const uint8_t* mask;  /* newly delivered mask or NULL */
     int pose_valid;       /* newly delivered pose measurement? */
@@ -559,6 +560,72 @@ int roft_engine_get_flow_stats(roft_engine* e, roft_engine_flow_stats* out);
 /* Stand-alone operator (tests, tools): the gray image (W x H bytes) of a HOST image, any W, H >= 1, by the device's conversion. */
 int roft_image_to_gray(const void* image, int image_type, int W, int H, uint8_t* gray_out);
 
+/* ---- (3c) raw sensor depth on the engine -------------------------------------------------------------------------- *
+ * No sensor delivers H x W floats in metres registered to the colour camera.  The reference's capture tool reads Z16 frames,
+ * registers them to the colour stream with rs2::align and calls convertTo(CV_32FC1, 0.001) on every frame, on the host
+ * (tools/rs-capture/src/main.cpp:23-67); YCB-Video and HO-3D store depth as 16-bit images too
+ * (tools/dataset/conversion/ho3d_utils.py:35-46, 82-83).  On an engine with roft_engine_enable_raw_depth the caller hands over the
+ * sensor's 16-bit frame: inputs[].depth then carries a `const uint16_t*` image of the depth source's size -- for every object and
+ * every submit call (roft_frames_submit, _labels, _images), HOST or DEVICE memory as mem_kind says -- and the float depth the
+ * kernels read is made on the device and never exists on the host.
+ *
+ * Equivalence that defines the feature: the engine behaves, bit for bit, as if inputs[].depth had been a HOST float image --
+ * roft_depth_convert(raw) with align == 0, roft_depth_align(raw) otherwise.  HOST images are uploaded once per distinct pointer and
+ * frame (two bytes per reading), DEVICE images (4-byte aligned) are read in place under the retention contract of roft_frame_input;
+ * one product is made per distinct raw image and frame however many objects name it, and it lives exactly as long as a staged HOST
+ * depth of that frame would (the next frame's flow measurement reads it as the previous depth).
+ *
+ * CONVERT: out = (float)d * scale, one float multiply; 0 stays 0, the engine's "invalid".
+ *
+ * ALIGN: float arithmetic in exactly this operation order, without contraction; the cameras' doubles are converted to float once.
+ * For every depth pixel (x, y) with d != 0:  z = (float)d * scale;  for the two corners s in {-0.5f, +0.5f}:
+ *     px = (float)x + s,  py = (float)y + s
+ *     X = ((px - cx_d) / fx_d) * z,  Y = ((py - cy_d) / fy_d) * z
+ *     P_i = ((R[i][0] * X + R[i][1] * Y) + R[i][2] * z) + t[i]        the pixel is skipped unless P_2 > 0
+ *     u = (P_0 / P_2) * fx_c + cx_c,  v = (P_1 / P_2) * fy_c + cy_c
+ * The pixel is skipped unless u0, v0, u1, v1 are all finite.  Its targets are the colour pixels whose CENTRES lie in the half-open
+ * footprint, computed in float: x0 = max(ceilf(u0), 0), x1 = min(ceilf(u1) - 1, W_c - 1), rows likewise; empty when x1 < x0 or
+ * y1 < y0; the pixel is skipped when x1 - x0 >= ROFT_DEPTH_ALIGN_MAX_SPAN or y1 - y0 >= ROFT_DEPTH_ALIGN_MAX_SPAN after clipping.
+ * Every target keeps the MINIMUM RAW VALUE d of all source pixels that cover it; the output is (float)d_min * scale, and 0 where
+ * nobody covers.  The value written is the sensor's reading, not P_2 (the two cameras of such a sensor are coplanar to a fraction of
+ * a millimetre).  The minimum is over integers: the result depends neither on the execution order nor on the run.  Two consequences:
+ * identity extrinsics with equal cameras give roft_depth_convert bit for bit, and an exact x2 camera replicates every reading into a
+ * 2 x 2 block without holes or overlaps.
+ * Deviation from librealsense, on purpose: rs2::align rounds both corners to nearest and fills inclusively, which takes a 2 x 2
+ * minimum even under identity and drops footprints that are partly outside the image; this contract uses centres in a half-open
+ * footprint and clips.  (librealsense was not at hand when this was written: that description of it is RECALLED, not read.)
+ * Not modelled: lens distortion, colour aligned to depth, per-object depth formats.
+ *
+ * Refusals, all on the host before anything is enqueued, nothing consumed.  ROFT_ERR_STATE: enabling after the first frame.
+ * ROFT_ERR_INVALID: a NULL argument; an unknown type; a scale that is not finite or not > 0; align == 0 with a size other than
+ * roft_config::cam; a non-finite R or t; a focal length <= 0 or not finite; width * height >= 2^24; a DEVICE raw image that is
+ * not 4-byte aligned. */
+#define ROFT_DEPTH_Z16 1            /* H x W uint16, 0 = no reading */
+#define ROFT_DEPTH_ALIGN_MAX_SPAN 16
+typedef struct {
+    int   type;        /* ROFT_DEPTH_* */
+    float scale;       /* metres per unit (RealSense: 0.001f); finite, > 0 */
+    int   align;       /* 0: the frame is already in the engine's camera (size must equal roft_config::cam; cam/R/t ignored) */
+    roft_camera cam;   /* align != 0: the DEPTH camera, any width, height >= 1, pinhole, no distortion */
+    float R[9];        /* row-major; P_colour = R * P_depth + t */
+    float t[3];        /* metres */
+} roft_depth_source;
+/* before the first frame */
+int roft_engine_enable_raw_depth(roft_engine* e, const roft_depth_source* src);
+/* the float depth (roft_config::cam: H x W) the engine made for obj's last stepped frame -> host buffer; syncs; ROFT_ERR_STATE on an
+ * engine without raw depth or before the first step */
+int roft_engine_get_depth(roft_engine* e, int obj_id, float* depth_out);
+typedef struct {
+    long long images;       /* distinct raw images taken in */
+    long long image_bytes;  /* ... their bytes uploaded (a DEVICE image adds none) */
+    long long products;     /* float depth images made */
+} roft_engine_depth_stats;  /* since roft_engine_create */
+int roft_engine_get_depth_stats(roft_engine* e, roft_engine_depth_stats* out);
+/* stand-alone operators (tests, tools): HOST buffers, device 0.  raw: H x W; out: H x W floats (roft_depth_align: the colour
+ * camera's size; src->align is not looked at, src->cam / R / t always are).  Any W, H >= 1. */
+int roft_depth_convert(const uint16_t* raw, int W, int H, float scale, float* out);
+int roft_depth_align(const uint16_t* raw, const roft_depth_source* src, const roft_camera* colour, float* out);
+
 /* ---- (3b) scene renderer: tracked poses drawn over the camera frames ----------------------------------------------
  * The reference's evaluation draws the mesh at every estimated pose over the grayed camera frame (evaluation/results_renderer.py:
  * 591-778 through tools/object_renderer/src/renderer.cpp).  This is that stage for many frames and several objects per frame:
@@ -650,6 +717,9 @@ int roft_debug_pose_errors_kernel_ms(double* ms_out);
 /* device time in milliseconds (HIP events) of the renderer's last roft_scene_render call, without its copies: ms_out[0] the visibility
  * pass (with the clear of its key buffer), ms_out[1] the resolve pass */
 int roft_debug_scene_kernel_ms(roft_scene_renderer* r, double ms_out[2]);
+/* device time in milliseconds (HIP events) of the raw-depth kernels the engine's last submit call enqueued (section 3c), without its
+ * copies; waits for them.  ROFT_ERR_STATE when that call made no depth product. */
+int roft_debug_depth_kernel_ms(roft_engine* e, double* ms_out);
 /* phase counters of one object's last kernels (only filled by libraries built with a -DROFT_*_PROFILE switch) */
 int roft_debug_get_dbg(roft_engine* e, int obj_id, long long out[32]);
 

@@ -94,6 +94,18 @@ class EngineFlowStats(C.Structure):
     _fields_ = [("images", C.c_longlong), ("image_bytes", C.c_longlong), ("pyramids", C.c_longlong), ("pairs", C.c_longlong)]
 
 
+DEPTH_Z16 = 1                       # ROFT_DEPTH_*
+DEPTH_ALIGN_MAX_SPAN = 16           # ROFT_DEPTH_ALIGN_MAX_SPAN
+
+
+class DepthSource(C.Structure):
+    _fields_ = [("type", C.c_int), ("scale", C.c_float), ("align", C.c_int), ("cam", Camera), ("R", C.c_float * 9), ("t", C.c_float * 3)]
+
+
+class EngineDepthStats(C.Structure):
+    _fields_ = [("images", C.c_longlong), ("image_bytes", C.c_longlong), ("products", C.c_longlong)]
+
+
 class EngineStats(C.Structure):
     _fields_ = [("frames", C.c_longlong), ("batches", C.c_longlong), ("launches", C.c_longlong),
                 ("event_ops", C.c_longlong), ("h2d_bytes", C.c_longlong), ("h2d_copies", C.c_longlong)]
@@ -140,12 +152,15 @@ ABI_SYMBOLS = [
     "roft_scene_renderer_create", "roft_scene_renderer_destroy", "roft_scene_render", "roft_render_scene", "roft_debug_scene_kernel_ms",
     "roft_frames_submit_labels", "roft_labels_to_masks",
     "roft_engine_enable_flow", "roft_frames_submit_images", "roft_engine_get_flow", "roft_engine_get_flow_stats", "roft_image_to_gray",
+    "roft_engine_enable_raw_depth", "roft_engine_get_depth", "roft_engine_get_depth_stats", "roft_depth_convert", "roft_depth_align",
+    "roft_debug_depth_kernel_ms",
 ]
 POSE_ERROR_ADD, POSE_ERROR_ADDS = 0, 1   # ROFT_POSE_ERROR_*
 # entry points younger than ABI version 2 itself: a library built before them still loads through ROFT_LIB_SO
 NEWER_SYMBOLS = ("roft_pose_errors", "roft_engine_score_log", "roft_scene_renderer_create", "roft_scene_renderer_destroy", "roft_scene_render",
                  "roft_render_scene", "roft_frames_submit_labels", "roft_labels_to_masks",
-                 "roft_engine_enable_flow", "roft_frames_submit_images", "roft_engine_get_flow", "roft_engine_get_flow_stats", "roft_image_to_gray")
+                 "roft_engine_enable_flow", "roft_frames_submit_images", "roft_engine_get_flow", "roft_engine_get_flow_stats", "roft_image_to_gray",
+                 "roft_engine_enable_raw_depth", "roft_engine_get_depth", "roft_engine_get_depth_stats", "roft_depth_convert", "roft_depth_align")
 
 
 def build(force=False):
@@ -251,6 +266,13 @@ def lib():
         L.roft_engine_get_flow.argtypes = [vp, C.c_int, vp]
         L.roft_engine_get_flow_stats.argtypes = [vp, C.POINTER(EngineFlowStats)]
         L.roft_image_to_gray.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
+    if hasattr(L, "roft_engine_enable_raw_depth"):
+        L.roft_engine_enable_raw_depth.argtypes = [vp, C.POINTER(DepthSource)]
+        L.roft_engine_get_depth.argtypes = [vp, C.c_int, vp]
+        L.roft_engine_get_depth_stats.argtypes = [vp, C.POINTER(EngineDepthStats)]
+        L.roft_depth_convert.argtypes = [vp, C.c_int, C.c_int, C.c_float, vp]
+        L.roft_depth_align.argtypes = [vp, C.POINTER(DepthSource), C.POINTER(Camera), vp]
+        L.roft_debug_depth_kernel_ms.argtypes = [vp, dp]
     for name in ABI_SYMBOLS:
         if (name.startswith("roft_debug_") or name in NEWER_SYMBOLS) and not hasattr(L, name):
             continue   # (an older build loaded through ROFT_LIB_SO for an A/B run: diagnostics and the pose errors only; tests/test_abi_cpu.py checks the in-tree library has them all)

@@ -31,6 +31,7 @@
 #include "mesh_class.h"
 #include "batch_plan.h"
 #include "opticalflow.h"
+#include "depth.h"
 
 static_assert(roft::host::kPlanLanes == roft::kNumLin, "batch_plan.h plans for the engine's pose lanes");
 
@@ -267,6 +268,7 @@ struct HostObject {
     Sched s;
     int stepped_slot = 0, stepped_lane = 0;   // slot holding p_corr_belief_ after the last stepped frame, and its lane
     const void* stepped_flow = nullptr;       // the flow produced for the last stepped frame (roft_engine_get_flow), or null
+    const float* stepped_depth = nullptr;     // the depth of the last stepped frame (roft_engine_get_depth reads it on a raw-depth engine)
     std::vector<OwnedFlow*> owned;   // engine copies of flows that outlived the zero-copy retention window
     DevBuf<float> verts;
     DevBuf<int32_t> tris;
@@ -298,6 +300,27 @@ struct EngineFlow {
     std::vector<FlowFrameJobs> jobs;    // of the submit call under way
     roft_engine_flow_stats stats{}, stats_backup{};
     ~EngineFlow() { for (auto& g : pyr) for (auto* b : g) delete b; }
+};
+
+// Raw sensor depth on the engine (roft_engine_enable_raw_depth): inputs[].depth carries the sensor's 16-bit frame; the float depth
+// the kernels read is made on the upload stream behind the copies, where a staged HOST depth of the frame would have been copied
+// (stage_alloc in the frame's staging slot: it lives exactly as long as one).  Built by submit_frames on the host only and enqueued
+// when the whole batch has been accepted, like the flow production: a refused submit leaves the device untouched.
+struct DepthJob { int t; const uint16_t* raw; float* out; };   // a distinct raw image of frame t of the batch and its product's place
+struct EngineDepth {
+    bool enabled = false;
+    roft_depth_source src{};
+    size_t raw_pixels = 0;            // readings per raw image (the depth source's size)
+    DepthAlignGeom geom{};            // src.align != 0
+    std::vector<DepthJob> jobs;       // of the submit call under way
+    roft_engine_depth_stats stats{}, stats_backup{};
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the depth kernels of the last submit (roft_debug_depth_kernel_ms)
+    bool timed = false;
+    ~EngineDepth()
+    {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+    }
 };
 
 // Device copies of HOST inputs: a ring of `retain` frame slots, each a bump allocator over chunks of device memory that
@@ -417,8 +440,9 @@ struct roft_engine {
     int lane_objs[kNumLin] = {0, 0}, lane_old_first[kNumLin] = {0, 0};
     int relabel_wait[kNumLin] = {-1, -1};     // batch of the OTHER lane this lane's launches must follow (slots that changed lanes)
     bool any_feat = false, any_feat_now = false, had_uploads = false;
-    bool produced_flows = false;           // the submit enqueued flow production (pyramids, flows, deferred flow clones) behind its copies: ev_up covers it
+    bool produced_flows = false;           // the submit enqueued production (flows: pyramids, flows, deferred flow clones; raw depth: its products) behind its copies: ev_up covers it
     EngineFlow flow;                       // camera images -> flows (roft_engine_enable_flow)
+    EngineDepth depth;                     // raw sensor depth -> float depth (roft_engine_enable_raw_depth); its products ride on produced_flows
     unsigned feat_frames = 0;              // bit t: some object buffers outlier-rejection features in frame t of the batch
     unsigned new_mask_frames = 0;   // bit t: some object receives a mask in frame t of the batch (of either form)
     unsigned plain_mask_frames = 0; // bit t: ... a per-object byte mask (what mask_ingest_kernel / ctrl_ingest_kernel convert)

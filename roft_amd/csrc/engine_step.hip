@@ -417,7 +417,7 @@ int roft_step(roft_engine* e)
         roft_batch_trace& tr = e->trace[e->batch_counter % roft_engine::kTraceRing];
         if (tr.batch == e->batch_counter) tr.step_us = host_now_us() - t_step0;
     }
-    for (HostObject* ho : e->objs) { ho->stepped_slot = ho->s.cur_slot; ho->stepped_lane = ho->s.own[ho->s.cur_slot]; ho->stepped_flow = ho->s.flow_made; }
+    for (HostObject* ho : e->objs) { ho->stepped_slot = ho->s.cur_slot; ho->stepped_lane = ho->s.own[ho->s.cur_slot]; ho->stepped_flow = ho->s.flow_made; ho->stepped_depth = ho->s.depth_prev; }
     // (a failed step leaves the engine consistent as far as the host can tell: the batch counts as enqueued)
     e->frame_counter += e->cur_T;
     e->prev_T = e->cur_T;

@@ -239,6 +239,7 @@ static int stage_host_runs(roft_engine* e, const roft_frame_input* inputs, int n
                         e->stats.h2d_bytes += (long long)((size_t)len * bytes);
                         e->stats.h2d_copies++;
                         e->had_uploads = true;
+                        if (kind == 0 && e->depth.enabled) e->depth.stats.image_bytes += (long long)((size_t)len * bytes);   // (raw frames)
                         for (int t = t0; t <= t1; ++t)
                             e->staging[(frame0 + t) % e->retain].seen.emplace_back(p0 + (size_t)(t - t0) * bytes, d + (size_t)(t - t0) * bytes);
                     }
@@ -295,11 +296,39 @@ static int enqueue_flow_production(roft_engine* e, int T)
     return ROFT_OK;
 }
 
+// The depth products of the accepted batch -> upload stream, behind the copies: all distinct raw images of the batch in one launch
+// per phase (one for a conversion, three for an alignment), their pointers in the kernel arguments in chunks of kDepthChunk.
+static int enqueue_depth_production(roft_engine* e)
+{
+    EngineDepth& d = e->depth;
+    const size_t npix = (size_t)e->cfg.cam.width * e->cfg.cam.height;
+    if (!d.ev0) { HIP_TRY(hipEventCreate(&d.ev0)); HIP_TRY(hipEventCreate(&d.ev1)); }
+    HIP_TRY(hipEventRecord(d.ev0, e->up_stream));
+    DepthJobs jobs{};
+    auto launch = [&]() {
+        if (d.src.align) launch_depth_align(jobs, d.geom, e->up_stream);
+        else launch_depth_convert(jobs, npix, d.src.scale, e->up_stream);
+        jobs.n = 0;
+    };
+    for (const DepthJob& j : d.jobs) {
+        jobs.raw[jobs.n] = j.raw; jobs.out[jobs.n] = j.out;
+        if (++jobs.n == kDepthChunk) launch();
+    }
+    if (jobs.n) launch();
+    if (hipError_t le = hipGetLastError()) return fail(ROFT_ERR_DEVICE, std::string("depth production: ") + hipGetErrorString(le));
+    HIP_TRY(hipEventRecord(d.ev1, e->up_stream));
+    d.timed = true;
+    return ROFT_OK;
+}
+
 static int submit_frames(roft_engine* e, const roft_frame_input* inputs, const roft_label_mask* labels, const roft_frame_image* images, int n_obj, int T)
 {
     const roft_config& cfg = e->cfg;
     const size_t npix = (size_t)cfg.cam.width * cfg.cam.height;
     const size_t fbytes = flow_bytes(e->arr.a.ffmt);
+    // what inputs[].depth carries: H x W floats, or on a raw-depth engine the sensor's 16-bit frame of the depth source's size
+    const bool raw_depth = e->depth.enabled;
+    const size_t depth_bytes = raw_depth ? e->depth.raw_pixels * sizeof(uint16_t) : npix * sizeof(float);
     const int b = e->batch_counter;
     FrameCtrl* blk = e->slot_of(b).stage;
     int max_outliers[kNumLin] = {0, 0};
@@ -333,7 +362,7 @@ static int submit_frames(roft_engine* e, const roft_frame_input* inputs, const r
         sf.used = 0;
         sf.seen.clear();
     }
-    if (int rc = stage_host_runs(e, inputs, n_obj, T, npix * sizeof(float), fbytes)) return rc;
+    if (int rc = stage_host_runs(e, inputs, n_obj, T, depth_bytes, fbytes)) return rc;
     for (int t = 0; t < T; ++t) {
         const int frame = e->frame_counter + t;
         for (int id = 0; id < n_obj; ++id) {
@@ -406,7 +435,9 @@ static int submit_frames(roft_engine* e, const roft_frame_input* inputs, const r
                 if (reinterpret_cast<uintptr_t>(d_image) & 3) return fail(ROFT_ERR_INVALID, "device buffers must be aligned: camera image 4 B");
             } else if (in.mem_kind == ROFT_MEM_HOST) {
                 const void* p = nullptr;
-                if (int rc = stage_host(e, frame, in.depth, npix * sizeof(float), &p)) return rc;
+                const long long before_depth = e->stats.h2d_bytes;
+                if (int rc = stage_host(e, frame, in.depth, depth_bytes, &p)) return rc;
+                if (raw_depth) e->depth.stats.image_bytes += e->stats.h2d_bytes - before_depth;   // (uploaded, and counted, once per distinct pointer)
                 d_depth = static_cast<const float*>(p);
                 if (in.flow) { if (int rc = stage_host(e, frame, in.flow, fbytes, &d_flow)) return rc; }
                 if (in.mask) {
@@ -421,6 +452,25 @@ static int submit_frames(roft_engine* e, const roft_frame_input* inputs, const r
                 }
             } else {
                 return fail(ROFT_ERR_INVALID, "mem_kind must be ROFT_MEM_HOST or ROFT_MEM_DEVICE");
+            }
+
+            // ---- raw depth: d_depth is the device address of the 16-bit frame so far.  Its float product goes where a staged HOST depth
+            // of the frame would have been copied, one per distinct raw image and frame however many objects name it.
+            if (raw_depth) {
+                const uint16_t* d_raw = reinterpret_cast<const uint16_t*>(d_depth);
+                float* made = nullptr;
+                for (size_t i = e->depth.jobs.size(); i-- > 0 && e->depth.jobs[i].t == t;)
+                    if (e->depth.jobs[i].raw == d_raw) { made = e->depth.jobs[i].out; break; }
+                if (!made) {
+                    unsigned char* out = nullptr;
+                    if (int rc = stage_alloc(e, frame, npix * sizeof(float), &out)) return rc;
+                    made = reinterpret_cast<float*>(out);
+                    e->depth.jobs.push_back(DepthJob{t, d_raw, made});
+                    e->depth.stats.images++;
+                    e->depth.stats.products++;
+                    e->produced_flows = true;   // (production behind the copies: ev_up is recorded behind it)
+                }
+                d_depth = made;
             }
 
             // ---- the flow of a camera image: produced where a staged HOST flow of the frame would have been copied, one pyramid per
@@ -647,6 +697,11 @@ int roft_frames_submit_images(roft_engine* e, const roft_frame_input* inputs, co
         e->flow.jobs.assign((size_t)n_frames, FlowFrameJobs{});
         e->flow.stats_backup = e->flow.stats;
     }
+    if (e->depth.enabled) {
+        e->depth.jobs.clear();
+        e->depth.stats_backup = e->depth.stats;
+        e->depth.timed = false;
+    }
     e->feat_frames = 0;
     e->feat_dep_in_batch = false;
     e->new_mask_frames = e->plain_mask_frames = 0;
@@ -662,11 +717,12 @@ int roft_frames_submit_images(roft_engine* e, const roft_frame_input* inputs, co
     BatchSlot& bs = e->slot_of(e->batch_counter);
     hipEvent_t ev_wait = nullptr;   // what the host waits for: the copies
     if (rc == ROFT_OK && e->produced_flows) {
-        // Camera images: the production follows the copies on the upload stream.  The streams wait for ev_up, recorded behind the
+        // Camera images and raw depth: the production follows the copies on the upload stream.  The streams wait for ev_up, recorded behind the
         // production; the host for ev_host, recorded behind the copies alone -- and for nothing when nothing was copied.
         hipError_t err = hipSuccess;
         if (e->had_uploads) { err = hipEventRecord(bs.ev_host, e->up_stream); ev_wait = bs.ev_host; }
-        if (err == hipSuccess) rc = enqueue_flow_production(e, n_frames);
+        if (err == hipSuccess && !e->depth.jobs.empty()) rc = enqueue_depth_production(e);
+        if (err == hipSuccess && rc == ROFT_OK && e->flow.enabled) rc = enqueue_flow_production(e, n_frames);
         if (err == hipSuccess && rc == ROFT_OK) err = hipEventRecord(bs.ev_up, e->up_stream);
         if (err != hipSuccess) rc2 = fail(ROFT_ERR_DEVICE, std::string("flow production: ") + hipGetErrorString(err));
     } else if (e->had_uploads) {
@@ -684,6 +740,7 @@ int roft_frames_submit_images(roft_engine* e, const roft_frame_input* inputs, co
         const std::string msg = last_error();
         for (size_t i = 0; i < e->objs.size(); ++i) e->objs[i]->s = e->backup[i];
         if (e->flow.enabled) e->flow.stats = e->flow.stats_backup;
+        if (e->depth.enabled) { e->depth.stats = e->depth.stats_backup; e->depth.jobs.clear(); }
         return fail(rc != ROFT_OK ? rc : rc2, msg);
     }
     e->cur_T = n_frames;
@@ -739,5 +796,60 @@ int roft_engine_get_flow_stats(roft_engine* e, roft_engine_flow_stats* out)
 {
     if (!e || !out) return fail(ROFT_ERR_INVALID, "null argument");
     *out = e->flow.stats;
+    return ROFT_OK;
+}
+
+// ---- raw sensor depth (include/roft_engine.h section 3c) -------------------------------------------------------------------------
+int roft_engine_enable_raw_depth(roft_engine* e, const roft_depth_source* src)
+{
+    if (!e || !src) return fail(ROFT_ERR_INVALID, "null argument");
+    if (e->frame_counter > 0 || e->submitted) return fail(ROFT_ERR_STATE, "roft_engine_enable_raw_depth must precede the first frame");
+    if (src->type != ROFT_DEPTH_Z16) return fail(ROFT_ERR_INVALID, "the depth source's type must be ROFT_DEPTH_Z16");
+    if (int rc = depth_check_scale(src->scale)) return rc;
+    const roft_camera& cam = e->cfg.cam;
+    EngineDepth& d = e->depth;
+    if (src->align) {
+        if (int rc = depth_check_camera(src->cam, "depth")) return rc;
+        if (int rc = depth_check_transform(*src)) return rc;
+        depth_align_geometry(d.geom, *src, cam);
+        d.raw_pixels = (size_t)src->cam.width * src->cam.height;
+    } else {
+        if (src->cam.width != cam.width || src->cam.height != cam.height)
+            return fail(ROFT_ERR_INVALID, "a depth source that is not aligned on the device (align 0) must have the size of roft_config::cam");
+        d.raw_pixels = (size_t)cam.width * cam.height;
+    }
+    d.src = *src;
+    d.enabled = true;
+    return ROFT_OK;
+}
+
+int roft_engine_get_depth(roft_engine* e, int obj_id, float* depth_out)
+{
+    if (!e || !depth_out) return fail(ROFT_ERR_INVALID, "null argument");
+    if (obj_id < 0 || obj_id >= (int)e->objs.size()) return fail(ROFT_ERR_INVALID, "bad obj_id");
+    if (!e->depth.enabled) return fail(ROFT_ERR_STATE, "the engine makes no depth: roft_engine_enable_raw_depth was not called");
+    const float* src = e->objs[obj_id]->stepped_depth;
+    if (!src) return fail(ROFT_ERR_STATE, "no frame stepped yet");
+    if (int rc = roft_sync(e)) return rc;
+    HIP_TRY(hipMemcpy(depth_out, src, (size_t)e->cfg.cam.width * e->cfg.cam.height * sizeof(float), hipMemcpyDeviceToHost));
+    return ROFT_OK;
+}
+
+int roft_engine_get_depth_stats(roft_engine* e, roft_engine_depth_stats* out)
+{
+    if (!e || !out) return fail(ROFT_ERR_INVALID, "null argument");
+    *out = e->depth.stats;
+    return ROFT_OK;
+}
+
+int roft_debug_depth_kernel_ms(roft_engine* e, double* ms_out)
+{
+    if (!e || !ms_out) return fail(ROFT_ERR_INVALID, "null argument");
+    if (!e->depth.timed) return fail(ROFT_ERR_STATE, "the engine's last submit call made no depth product");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(hipEventSynchronize(e->depth.ev1));
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, e->depth.ev0, e->depth.ev1));
+    *ms_out = (double)ms;
     return ROFT_OK;
 }

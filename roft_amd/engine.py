@@ -76,6 +76,7 @@ class ROFTFilterBatch:
     def submit(self, frames):
         """frames: one dict per object with keys depth, flow, mask, pose (None or (x, q)), dt,
         mem_kind; depth/flow/mask are numpy arrays (HOST) or integer device addresses (DEVICE).
+        After enable_raw_depth(): `depth` is the sensor's uint16 frame.
         Instead of `mask`: `labels` (one H x W uint8 / uint16 label image, typically the same array for every object of the
         frame; or an address, then with `label_type` L.LABEL_U8 / L.LABEL_U16) and `label`: the object's mask is the pixels
         EQUAL to that value (roft_frames_submit_labels).
@@ -251,6 +252,34 @@ class ROFTFilterBatch:
         out = np.zeros((self.H // g, self.W // g, 2), np.float32 if self.cfg.flow_type == L.FLOW_F32C2 else np.int16)
         L.check(L.lib().roft_engine_get_flow(self._h, obj, out.ctypes.data))
         return out
+
+    def enable_raw_depth(self, scale=0.001, cam=None, R=None, t=None):
+        """The frame key `depth` carries the sensor's 16-bit frame ([H, W] uint16, or an address) from now on, for every object:
+        the float depth is made on the device (roft_engine_enable_raw_depth).  cam None: the frames are in the engine's camera;
+        otherwise cam is the DEPTH camera and P_colour = R P_depth + t (ops.depth_source).  Before the first frame."""
+        from .ops import depth_source
+        src = depth_source(scale, cam, R, t)
+        if cam is None:
+            src.cam.width, src.cam.height = self.W, self.H
+        L.check(L.lib().roft_engine_enable_raw_depth(self._h, C.byref(src)))
+
+    def depth(self, obj):
+        """The float depth [H, W] the engine made for object `obj`'s last stepped frame (raw-depth engines).  Syncs."""
+        out = np.zeros((self.H, self.W), np.float32)
+        L.check(L.lib().roft_engine_get_depth(self._h, obj, out.ctypes.data))
+        return out
+
+    def depth_stats(self):
+        """distinct raw images / their uploaded image_bytes taken in, float products made since the engine was created."""
+        st = L.EngineDepthStats()
+        L.check(L.lib().roft_engine_get_depth_stats(self._h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in L.EngineDepthStats._fields_}
+
+    def depth_kernel_ms(self):
+        """Device time (ms, HIP events) of the depth kernels of the last submit call."""
+        ms = C.c_double(0.0)
+        L.check(L.lib().roft_debug_depth_kernel_ms(self._h, C.byref(ms)))
+        return ms.value
 
     def retain_frames(self):
         return L.lib().roft_engine_retain_frames(self._h)

@@ -232,9 +232,10 @@ def load_obj(path):
     return np.array(verts, np.float32).reshape(-1, 3), np.array(tris, np.int32).reshape(-1, 3)
 
 
-# ---- PNG (8-bit, non-interlaced; gray, gray+alpha, RGB, RGBA, palette) ------------------------------------
+# ---- PNG (non-interlaced; 8-bit gray, gray+alpha, RGB, RGBA, palette; 16-bit gray) -------------------------
 def read_png(path):
-    """Decodes to uint8 [H, W] (gray / palette index) or [H, W, C]."""
+    """Decodes to uint8 [H, W] (gray / palette index) or [H, W, C]; a 16-bit gray PNG -- the form YCB-Video and HO-3D ship depth
+    in, samples big-endian -- to uint16 [H, W]."""
     with open(path, "rb") as f:
         data = f.read()
     if data[:8] != b"\x89PNG\r\n\x1a\n":
@@ -252,9 +253,12 @@ def read_png(path):
         elif ctype == b"IEND":
             break
     w, h, depth, ctype, _, _, interlace = hdr
-    if depth != 8 or interlace != 0:
-        raise ValueError("only 8-bit non-interlaced PNGs are supported")
+    wide = depth == 16 and ctype == 0
+    if (depth != 8 and not wide) or interlace != 0:
+        raise ValueError("only 8-bit and 16-bit gray non-interlaced PNGs are supported")
     ch = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}[ctype]
+    if wide:
+        ch = 2   # (the filters work on bytes, one pixel back: two bytes)
     raw = np.frombuffer(zlib.decompress(b"".join(idat)), np.uint8)
     stride = w * ch
     raw = raw.reshape(h, stride + 1)
@@ -287,23 +291,38 @@ def read_png(path):
                 cur[x] = (line[x] + pr) & 255
         out[y] = cur
         prev = cur
+    if wide:
+        return out.reshape(h, w, 2).view(">u2").reshape(h, w).astype(np.uint16)
     return out.reshape(h, w) if ch == 1 else out.reshape(h, w, ch)
 
 
 def write_png(path, img):
-    """8-bit gray [H, W] or RGB(A) [H, W, C] PNG, filter 0 (used by the synthetic dataset writer and the tests)."""
+    """8-bit gray [H, W] or RGB(A) [H, W, C] PNG, filter 0 (used by the synthetic dataset writer and the tests); a uint16 [H, W]
+    array is written as a 16-bit gray PNG, samples big-endian."""
+    if np.asarray(img).dtype == np.uint16:
+        img = np.asarray(img)
+        if img.ndim != 2:
+            raise ValueError("a 16-bit PNG is gray: [H, W]")
+        h, w = img.shape
+        raw = np.zeros((h, 2 * w + 1), np.uint8)
+        raw[:, 1:] = np.ascontiguousarray(img.astype(">u2")).view(np.uint8).reshape(h, 2 * w)
+        _write_png_chunks(path, w, h, 16, 0, raw)
+        return
     img = np.ascontiguousarray(img, np.uint8)
     h, w = img.shape[:2]
     ch = 1 if img.ndim == 2 else img.shape[2]
     ctype = {1: 0, 2: 4, 3: 2, 4: 6}[ch]
     raw = np.zeros((h, w * ch + 1), np.uint8)
     raw[:, 1:] = img.reshape(h, w * ch)
+    _write_png_chunks(path, w, h, 8, ctype, raw)
 
+
+def _write_png_chunks(path, w, h, depth, ctype, raw):
     def chunk(t, b):
         return struct.pack(">I", len(b)) + t + b + struct.pack(">I", zlib.crc32(t + b) & 0xFFFFFFFF)
 
     with open(path, "wb") as f:
-        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, ctype, 0, 0, 0)) +
+        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, depth, ctype, 0, 0, 0)) +
                 chunk(b"IDAT", zlib.compress(raw.tobytes(), 3)) + chunk(b"IEND", b""))
 
 
@@ -354,8 +373,10 @@ class Sequence:
     def __len__(self):
         return self.n
 
-    def frame(self, k, with_image=False):
-        """with_image: the camera frame rgb/<k>.png as `image` (RGB8, or GRAY8 for a one-channel file) in place of the flow
+    def frame(self, k, with_image=False, depth_raw=False):
+        """depth_raw: `depth` is the 16-bit frame depth/<k>.png as it is stored (uint16, for an engine with enable_raw_depth) and no
+        float copy is made; otherwise depth/<k>.float.
+        with_image: the camera frame rgb/<k>.png as `image` (RGB8, or GRAY8 for a one-channel file) in place of the flow
         frame -- for an engine that computes the flow itself (ROFTFilterBatch.enable_flow); no flow file is read."""
         if with_image:
             img = read_png(os.path.join(self.root, "rgb", "%d.png" % k))
@@ -371,7 +392,13 @@ class Sequence:
         if pi >= 0 and self.pose_ok[pi]:
             pose = (self.poses[pi, :3], self.poses[pi, 3:])
         dt = float(self.stamp[k] - self.stamp[k - 1]) if k > 0 else 0.0
-        out = dict(depth=read_depth(os.path.join(self.depth_dir, "%d.float" % k)), flow=flow if ok else None,
+        if depth_raw:
+            depth = read_png(os.path.join(self.depth_dir, "%d.png" % k))
+            if depth.dtype != np.uint16:
+                raise ValueError("depth/%d.png is not a 16-bit gray PNG" % k)
+        else:
+            depth = read_depth(os.path.join(self.depth_dir, "%d.float" % k))
+        out = dict(depth=depth, flow=flow if ok else None,
                    mask=mask, pose=pose, dt=dt)
         if with_image:
             out["image"] = img if img.ndim == 2 else np.ascontiguousarray(img[..., :3])

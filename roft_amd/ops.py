@@ -271,6 +271,48 @@ def image_to_gray(image, image_type=None):
     return out
 
 
+def depth_source(scale=0.001, cam=None, R=None, t=None):
+    """L.DepthSource of a Z16 sensor: `scale` metres per unit.  cam None: the frames are already in the colour camera (align 0).
+    Otherwise cam is the DEPTH camera (L.Camera, or anything with width, height, fx, fy, cx, cy) and P_colour = R P_depth + t
+    (R [3, 3] row-major, default identity; t metres, default 0)."""
+    src = L.DepthSource()
+    src.type, src.scale, src.align = L.DEPTH_Z16, float(scale), 0 if cam is None else 1
+    if cam is not None:
+        src.cam = L.Camera(int(cam.width), int(cam.height), float(cam.fx), float(cam.fy), float(cam.cx), float(cam.cy))
+    src.R = (C.c_float * 9)(*np.asarray(np.eye(3) if R is None else R, np.float32).reshape(9))
+    src.t = (C.c_float * 3)(*np.asarray(np.zeros(3) if t is None else t, np.float32).reshape(3))
+    return src
+
+
+def _raw_depth(raw):
+    raw = np.ascontiguousarray(raw)
+    if raw.dtype != np.uint16 or raw.ndim != 2:
+        raise TypeError("a raw depth frame is [H, W] uint16")
+    return raw
+
+
+def depth_convert(raw, scale=0.001):
+    """The float depth image (metres, [H, W] float32) of a 16-bit depth frame by the device's conversion (roft_depth_convert):
+    (float)raw * scale, 0 stays 0."""
+    raw = _raw_depth(raw)
+    out = np.zeros(raw.shape, np.float32)
+    L.check(L.lib().roft_depth_convert(_p(raw), raw.shape[1], raw.shape[0], float(scale), _p(out)))
+    return out
+
+
+def depth_align(raw, depth_cam, colour_cam, scale=0.001, R=None, t=None):
+    """A 16-bit frame of the depth camera registered to the colour camera (roft_depth_align; the contract is in
+    include/roft_engine.h section 3c): [colour H, colour W] float32 metres, 0 where no reading lands."""
+    raw = _raw_depth(raw)
+    if raw.shape != (depth_cam.height, depth_cam.width):
+        raise ValueError("the raw frame does not have the depth camera's size")
+    src = depth_source(scale, depth_cam, R, t)
+    col = L.Camera(int(colour_cam.width), int(colour_cam.height), float(colour_cam.fx), float(colour_cam.fy), float(colour_cam.cx), float(colour_cam.cy))
+    out = np.zeros((col.height, col.width), np.float32)
+    L.check(L.lib().roft_depth_align(_p(raw), C.byref(src), C.byref(col), _p(out)))
+    return out
+
+
 class FlowProducer:
     """Batched device-resident producer (roft_flow_producer_*): `run` takes lists of device pointers."""
 

@@ -4,7 +4,7 @@ files (`pose_estimate`, `velocity_estimate`, ROFTFilter.cpp:386-394) -- what `te
 
   run_sequence.py --root DIR --object NAME --mesh model.obj [--flow-set nvof_1_slow] [--mask-set NAME]
                   [--pose-set dope] [--out PREFIX] [--compute-flow nvof1|nvof2 | --flow-on-engine nvof1|nvof2] [--no-delay]
-                  [--init-pose x y z qw qx qy qz]
+                  [--init-pose x y z qw qx qy qz] [--raw-depth SCALE]
                   [--start-at-first-detection] [--score-on-device] [--render-overlay DIR]
                   [--from config_fast_ycb.cfg [--group::key value ...]]
 
@@ -15,7 +15,9 @@ config/config_ho3d.cfg) and applies `--a::b::c value` overrides exactly as ROFT-
 The camera comes from DIR/cam_K.json (width, height, fx, fy, cx, cy).  --compute-flow first runs tools/flow_dumper.py
 on DIR/rgb (the MI355X replacement of the NVOF dumper) into DIR/optical_flow/<flow-set>.  --flow-on-engine hands the frames
 DIR/rgb/<i>.png to the engine instead, which computes the same flow itself (roft_frames_submit_images: the flow never leaves the
-device, no flow directory is read or written) -- the logs are those of --compute-flow, byte for byte.  With DIR/gt/poses.txt present
+device, no flow directory is read or written) -- the logs are those of --compute-flow, byte for byte.  --raw-depth SCALE
+tracks from the 16-bit frames DIR/depth/<i>.png (the form YCB-Video and HO-3D ship; SCALE metres per unit, 0.001 for millimetres)
+without a float copy: the engine converts them on the device (roft_engine_enable_raw_depth).  With DIR/gt/poses.txt present
 the ADD-S / ADD AUC and the RMSE metrics of evaluation/metrics.py are printed as one JSON line.  --score-on-device adds the
 ADD-S and ADD of the same frames on EVERY vertex of the mesh, computed on the GPU from the engine's device-side log
 (roft_engine_score_log: the estimates never leave the device).  --render-overlay DIR draws the estimate over the sequence's
@@ -45,6 +47,8 @@ def main(argv=None):
     ap.add_argument("--compute-flow", choices=["nvof1", "nvof2"], default=None)
     ap.add_argument("--flow-on-engine", choices=["nvof1", "nvof2"], default=None,
                     help="hand the camera frames rgb/<i>.png to the engine, which computes the flow (nvof1: CV_16SC2 grid 4, nvof2: CV_32FC2)")
+    ap.add_argument("--raw-depth", type=float, default=None, metavar="SCALE",
+                    help="read depth/<i>.png (16-bit gray, SCALE metres per unit) and let the engine convert it on the device")
     ap.add_argument("--no-delay", action="store_true")
     ap.add_argument("--start-at-first-detection", action="store_true",
                     help="start where test/test_ho3d.sh:68-80 starts the tracker: at the frame and with the pose "
@@ -137,8 +141,10 @@ def main(argv=None):
     eng.enable_log(n)
     if args.flow_on_engine:
         eng.enable_flow()
+    if args.raw_depth is not None:
+        eng.enable_raw_depth(args.raw_depth)
     for k in range(start, len(seq)):
-        eng.submit([seq.frame(k, with_image=bool(args.flow_on_engine))])
+        eng.submit([seq.frame(k, with_image=bool(args.flow_on_engine), depth_raw=args.raw_depth is not None)])
         eng.step()
     pose, twist, npts, sel = eng.get_log(0, n)
     gt_path = os.path.join(args.root, "gt", "poses.txt")
