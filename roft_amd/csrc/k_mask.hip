@@ -332,7 +332,9 @@ __host__ __device__ inline ChaseGeo make_chase_geo(const DevCamera& cam, const D
 // INT_MIN there (cvttss2si), i.e. "out of the image"; here NaN -> -2 and the value is clamped to [-2, 2^24] before the
 // conversion, which is out of the image as well (W*H < 2^24) and exact in between, (-1, 0) -> 0 included.
 // (v_med3_f32 returns min3 of its operands when one of them is a NaN, and v_min_f32 returns the other operand: a NaN
-//  becomes -2 without a separate test; the NaN-flow cases of tests/test_parity_gpu.py pin this.)
+//  becomes -2 without a separate test.  Pinned on both kernels: tests/test_parity_gpu.py::test_mask_propagate_* (NaN flows through the
+//  two-wave kernel of delivering frames) and the poison, three_valued and formats cases of tests/test_mask_paths_gpu.py (the four-wave
+//  every-frame kernel: walk_single, walk_single_aligned, chase_groups in MODE 0, and the map kernel of three-valued masks).)
 __device__ __forceinline__ int trunc_clamped(float x)
 {
     return (int)__builtin_amdgcn_fmed3f(x, -2.0f, 16777216.0f);
