@@ -626,6 +626,80 @@ int roft_engine_get_depth_stats(roft_engine* e, roft_engine_depth_stats* out);
 int roft_depth_convert(const uint16_t* raw, int W, int H, float scale, float* out);
 int roft_depth_align(const uint16_t* raw, const roft_depth_source* src, const roft_camera* colour, float* out);
 
+/* ---- (3d) track quality: silhouette overlap and depth residual of every estimate --------------------------------------- *
+ * The outlier test scores two alternatives, on frames where a delayed pose arrives, against features buffered earlier.  Track
+ * quality scores the estimate the engine RETURNS, on every frame (or every `every`-th), against that frame's own mask and depth,
+ * on the device: one record per (frame, object).  It is opt-in, reads engine state, writes only its records and changes no result.
+ * What a caller does with the numbers (thresholds, "lost", "occluded") is the caller's.
+ *
+ * Symbols.  (x, q): the frame's final estimate, pose[6..12] of its log row (roft_engine_get_log).  M: the frame's propagated,
+ * binarised mask -- what roft_get_mask returns after the frame.  D: the frame's float depth as the engine used it (with raw depth
+ * enabled: the converted / aligned product, roft_engine_get_depth).  d: the engine's render divider (2 when the image is 640 wide,
+ * else 4; roft_track_quality: the argument).  w = W / d, h = H / d (integer division).  R: the h x w depth tile of the mesh at
+ * (x, q) under ROFT_RENDER_CONTRACT -- bit for bit roft_render_depth(mesh, x, q, cam, d): the back-face rule for closed meshes,
+ * 0 = background.  An object added without a mesh has R = 0 everywhere.
+ * Every sum runs over the image pixels (u, v), 0 <= u < W, 0 <= v < H, with u / d < w and v / d < h; the render value of a pixel is
+ * r = R[v / d][u / d] (the mapping of the outlier test's likelihood); pixels with u / d >= w or v / d >= h (H or W not a multiple
+ * of d) have no render value: they count for n_mask only.
+ *
+ * Operation by operation:
+ *   n_mask    pixels of the WHOLE image with M != 0
+ *   n_render  pixels with r != 0
+ *   n_both    pixels with M != 0 and r != 0
+ *   n_depth   pixels of n_both whose D is valid: D > 0 and (double)D < depth_maximum; a NaN fails both comparisons
+ *   for those: e = D - r, ONE float subtraction;  n_front counts e < -depth_tolerance, n_behind counts e > +depth_tolerance
+ *              (float comparisons; e == -+depth_tolerance exactly is neither)
+ *   S         the sum of |e| over n_depth, exact: each term t = min((double)|e|, 256.0) is split into two integers
+ *                 hi = floor(t * 2^32),   lo = (integer part of) (t * 2^32 - hi) * 2^32
+ *             -- units of 2^-32 m and 2^-64 m; for every float t >= 2^-41 both products are exact and hi 2^-32 + lo 2^-64 == t;
+ *             a smaller t loses what lies below 2^-64 --, and HI = sum of hi, LO = sum of lo are 64-bit integer sums: they depend
+ *             neither on the order of the terms nor on how the device spreads them over threads
+ *   depth_err value(HI, LO) / (double)n_depth with
+ *                 value(HI, LO) = (double)HI * 2^-32 + (double)LO * 2^-64
+ *             in double arithmetic exactly as written: two conversions (round to nearest even), two multiplications by powers of
+ *             two (exact), one addition, one division.  DBL_MAX when n_depth == 0.
+ * So a record is a function of (x, q), M, D, the mesh, the camera, d, depth_tolerance and depth_maximum alone: equal inputs give
+ * equal bits, whatever the batch shape, the stream layout or the launch shape.
+ *
+ * Engine.  roft_engine_enable_quality: before the first frame (else ROFT_ERR_STATE); the output log must be enabled first
+ * (ROFT_ERR_STATE) -- the kernel reads the estimates where the step wrote them --, with a capacity of at least the frames that can
+ * be in flight, (batches in flight) x max_batch_frames = 6 for one-frame engines and 5 x max_batch_frames otherwise: a smaller log
+ * is refused with ROFT_ERR_INVALID and the error string names the least capacity.  The quality ring has the log's capacity; while
+ * quality is on, roft_engine_enable_log with another capacity is ROFT_ERR_STATE.  every >= 1, depth_tolerance finite and >= 0, else
+ * ROFT_ERR_INVALID.  An engine with render_mode == ROFT_RENDER_GL is refused with ROFT_ERR_INVALID: it keeps its meshes unsorted
+ * and without the flip bits of the back-face rule, so the contract's render does not exist there.  depth_maximum is
+ * roft_config::depth_maximum.  A frame gets records when frame % every == 0 (frame: the engine's frame counter, from 0); the rows
+ * of other frames carry frame = -1 and zeros.
+ * roft_engine_get_quality: syncs; out[n_frames][n_objects]; it accepts exactly the frame ranges roft_engine_score_log accepts --
+ * first_frame >= 0, n_frames >= 0, the range stepped and still in the ring -- else ROFT_ERR_INVALID.
+ * roft_track_quality: the engine's kernel on HOST buffers for one object (device 0): depth, mask H x W; M is the object plane the
+ * engine's ingest makes of the byte mask, the pixels of value > 1 (a delivered mask's 0 and 1 are not the object); mesh may have 0
+ * triangles;
+ * window_pixels > 0 caps the kernel's LDS depth window (a larger window is drawn in strips: no bit changes), 0: the engine's shape.
+ * out->frame is 0.  ROFT_ERR_INVALID before any device is looked for: a NULL pointer, divider <= 0, a negative or NaN
+ * depth_tolerance, window_pixels < 0. */
+typedef struct {
+    int32_t frame;     /* engine frame counter of the record; -1: no record for this (frame, object) */
+    int32_t n_mask;    /* pixels with M != 0 (over the WHOLE image, also outside the render's window) */
+    int32_t n_render;  /* pixels with r != 0 */
+    int32_t n_both;    /* both: overlap = n_both / (n_mask + n_render - n_both) is the caller's to form */
+    int32_t n_depth;   /* pixels of n_both with D > 0 and (double)D < depth_maximum (NaN fails both) */
+    int32_t n_front;   /* of those, e = D - r (float) < -depth_tolerance: something stands in front of the object */
+    int32_t n_behind;  /* of those, e > +depth_tolerance: the surface is not where the estimate puts it */
+    int32_t reserved;  /* 0 */
+    double  depth_err; /* (sum of |e| over n_depth) / n_depth, DBL_MAX when n_depth == 0 */
+} roft_quality_record;  /* 40 bytes */
+typedef struct {
+    int   every;            /* records on frames with frame % every == 0; default 1 */
+    float depth_tolerance;  /* metres; default 0.01f */
+} roft_quality_params;
+int roft_default_quality_params(roft_quality_params* p);
+int roft_engine_enable_quality(roft_engine* e, const roft_quality_params* p);   /* NULL = defaults */
+int roft_engine_get_quality(roft_engine* e, int first_frame, int n_frames, roft_quality_record* out);
+int roft_track_quality(const roft_camera* cam, int divider, const float* depth, const uint8_t* mask, const roft_mesh* mesh,
+                       const double x[3], const double q[4], float depth_tolerance, double depth_maximum, int window_pixels,
+                       roft_quality_record* out);
+
 /* ---- (3b) scene renderer: tracked poses drawn over the camera frames ----------------------------------------------
  * The reference's evaluation draws the mesh at every estimated pose over the grayed camera frame (evaluation/results_renderer.py:
  * 591-778 through tools/object_renderer/src/renderer.cpp).  This is that stage for many frames and several objects per frame:
@@ -720,6 +794,9 @@ int roft_debug_scene_kernel_ms(roft_scene_renderer* r, double ms_out[2]);
 /* device time in milliseconds (HIP events) of the raw-depth kernels the engine's last submit call enqueued (section 3c), without its
  * copies; waits for them.  ROFT_ERR_STATE when that call made no depth product. */
 int roft_debug_depth_kernel_ms(roft_engine* e, double* ms_out);
+/* device time in milliseconds (the HIP events bound to its dispatch) of the engine's last quality launch (section 3d); waits for it.
+ * ROFT_ERR_STATE when there was none. */
+int roft_debug_quality_kernel_ms(roft_engine* e, double* ms_out);
 /* phase counters of one object's last kernels (only filled by libraries built with a -DROFT_*_PROFILE switch) */
 int roft_debug_get_dbg(roft_engine* e, int obj_id, long long out[32]);
 

@@ -106,6 +106,15 @@ class EngineDepthStats(C.Structure):
     _fields_ = [("images", C.c_longlong), ("image_bytes", C.c_longlong), ("products", C.c_longlong)]
 
 
+class QualityRecord(C.Structure):
+    _fields_ = [("frame", C.c_int32), ("n_mask", C.c_int32), ("n_render", C.c_int32), ("n_both", C.c_int32), ("n_depth", C.c_int32),
+                ("n_front", C.c_int32), ("n_behind", C.c_int32), ("reserved", C.c_int32), ("depth_err", C.c_double)]
+
+
+class QualityParams(C.Structure):
+    _fields_ = [("every", C.c_int), ("depth_tolerance", C.c_float)]
+
+
 class EngineStats(C.Structure):
     _fields_ = [("frames", C.c_longlong), ("batches", C.c_longlong), ("launches", C.c_longlong),
                 ("event_ops", C.c_longlong), ("h2d_bytes", C.c_longlong), ("h2d_copies", C.c_longlong)]
@@ -154,13 +163,15 @@ ABI_SYMBOLS = [
     "roft_engine_enable_flow", "roft_frames_submit_images", "roft_engine_get_flow", "roft_engine_get_flow_stats", "roft_image_to_gray",
     "roft_engine_enable_raw_depth", "roft_engine_get_depth", "roft_engine_get_depth_stats", "roft_depth_convert", "roft_depth_align",
     "roft_debug_depth_kernel_ms",
+    "roft_default_quality_params", "roft_engine_enable_quality", "roft_engine_get_quality", "roft_track_quality", "roft_debug_quality_kernel_ms",
 ]
 POSE_ERROR_ADD, POSE_ERROR_ADDS = 0, 1   # ROFT_POSE_ERROR_*
 # entry points younger than ABI version 2 itself: a library built before them still loads through ROFT_LIB_SO
 NEWER_SYMBOLS = ("roft_pose_errors", "roft_engine_score_log", "roft_scene_renderer_create", "roft_scene_renderer_destroy", "roft_scene_render",
                  "roft_render_scene", "roft_frames_submit_labels", "roft_labels_to_masks",
                  "roft_engine_enable_flow", "roft_frames_submit_images", "roft_engine_get_flow", "roft_engine_get_flow_stats", "roft_image_to_gray",
-                 "roft_engine_enable_raw_depth", "roft_engine_get_depth", "roft_engine_get_depth_stats", "roft_depth_convert", "roft_depth_align")
+                 "roft_engine_enable_raw_depth", "roft_engine_get_depth", "roft_engine_get_depth_stats", "roft_depth_convert", "roft_depth_align",
+                 "roft_default_quality_params", "roft_engine_enable_quality", "roft_engine_get_quality", "roft_track_quality")
 
 
 def build(force=False):
@@ -273,6 +284,13 @@ def lib():
         L.roft_depth_convert.argtypes = [vp, C.c_int, C.c_int, C.c_float, vp]
         L.roft_depth_align.argtypes = [vp, C.POINTER(DepthSource), C.POINTER(Camera), vp]
         L.roft_debug_depth_kernel_ms.argtypes = [vp, dp]
+    if hasattr(L, "roft_track_quality"):
+        L.roft_default_quality_params.argtypes = [C.POINTER(QualityParams)]
+        L.roft_engine_enable_quality.argtypes = [vp, C.POINTER(QualityParams)]
+        L.roft_engine_get_quality.argtypes = [vp, C.c_int, C.c_int, vp]
+        L.roft_track_quality.argtypes = [C.POINTER(Camera), C.c_int, vp, vp, C.POINTER(Mesh), vp, vp, C.c_float, C.c_double, C.c_int,
+                                         C.POINTER(QualityRecord)]
+        L.roft_debug_quality_kernel_ms.argtypes = [vp, dp]
     for name in ABI_SYMBOLS:
         if (name.startswith("roft_debug_") or name in NEWER_SYMBOLS) and not hasattr(L, name):
             continue   # (an older build loaded through ROFT_LIB_SO for an A/B run: diagnostics and the pose errors only; tests/test_abi_cpu.py checks the in-tree library has them all)

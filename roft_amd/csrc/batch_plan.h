@@ -81,6 +81,8 @@ struct PlanInputs {
     bool done_used_relabel[kPlanLanes] = {false, false};   // the other lane had work in batch relabel_wait[lane]
     // camera images: the submit produced flows on the upload stream (ev_up is recorded behind them, uploads or not)
     bool produced_flows = false;
+    // track quality (roft_engine_enable_quality): frames of the batch that get a record (0: quality off, or no frame of the batch is due)
+    int quality_frames = 0;
 };
 
 // how a span (a launch group on one stream) signals its event
@@ -130,6 +132,12 @@ struct BatchPlan {
     Signal ev_skf = Signal::none, ev_vel = Signal::none;
     LanePlan lane[kPlanLanes];
     int outlier_div = 1;        // the automatic band count of an outlier test is divided by this
+    // track quality: ONE launch for every (frame, object) of the batch that gets a record, behind the last segment of the LAST pose
+    // lane on that lane's stream (frames of one batch belong to either lineage: it reads the log rows of both lanes)
+    bool quality = false;
+    bool quality_waits_mask = false;    // ... behind ev_mask of the batch (a lane released early may run before the batch's last mask)
+    bool quality_waits_lane = false;    // ... and behind ev_done of the other lane, where that lane had work
+    Signal ev_quality = Signal::none;   // what the host waits for (in-flight bound, roft_sync)
 };
 
 // PROGRESS -- why no wait INSIDE a kernel can hang.  (Ordering, i.e. the waits between streams: engine_step.hip.)
@@ -269,6 +277,15 @@ BatchPlan plan_batch(const PlanInputs& in, AloneFn&& alone)
             lp.wait_feat = lanes_wait_feat && tests;
         }
     }
+
+    // Track quality.  Nothing of this exists in the plan of a batch without records -- no launch, no event, no wait.  The launch
+    // reads the batch's log rows (both lanes: it follows the last lane's last segment in stream order and waits for the other
+    // lane's ev_done), the batch's mask planes and, through the planes' producer, its depth (ev_mask: the mask stream waited for the
+    // uploads; a lane released at the gate or behind the control blocks alone does not imply the batch's last mask frame).
+    p.quality = in.quality_frames > 0;
+    p.quality_waits_mask = p.quality && multi;
+    p.quality_waits_lane = p.quality && multi && in.lin_any[0];
+    p.ev_quality = ends(p.quality);   // (on one stream too: the in-flight bound waits for it)
 
     // Bands per alternative of an outlier test: the caller's number, else by the CUs to spare -- and a fraction of that in the
     // steady state (fewer, longer workgroups leave more CUs to the chains; 64 objects: +5 %, and -2.5 % if a 20-frame burst did

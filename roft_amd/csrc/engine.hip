@@ -130,6 +130,8 @@ int wait_batch(roft_engine* e, int b, bool* waited)
             (void)hipGetLastError();   // (hipErrorNotReady is not an error of this call)
             HIP_TRY(hipEventSynchronize(slot.ev_done[l]));
         }
+    // (the quality launch follows both lanes: what it reads -- plane slots, staged depth, the caller's DEVICE buffers -- lives until here)
+    if (slot.quality_used) HIP_TRY(hipEventSynchronize(e->quality.ev_done[b % roft_engine::kBatchRing]));
     {
         roft_batch_trace& tr = e->trace[b % roft_engine::kTraceRing];
         if (tr.batch == b && tr.t_done_us == 0.0) tr.t_done_us = host_now_us();

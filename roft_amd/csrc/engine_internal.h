@@ -9,6 +9,7 @@
 //   engine_step.hip     roft_step / roft_sync: step_batch enqueues a BatchPlan on the engine's four streams; the timing marks
 //   engine_results.hip  state, outputs, log, masks, timing and batch-trace readers
 //   engine_ops.hip      the operator-level entry points (one-object context: roft_flow_measurement ... roft_outlier_test, roft_pose_errors)
+//   engine_quality.hip  track quality: roft_engine_enable_quality / _get_quality, roft_track_quality, the batch's quality launch
 //   engine_debug.hip    roft_debug_* (diagnostics and experiments)
 #pragma once
 
@@ -32,6 +33,7 @@
 #include "batch_plan.h"
 #include "opticalflow.h"
 #include "depth.h"
+#include "quality.h"
 
 static_assert(roft::host::kPlanLanes == roft::kNumLin, "batch_plan.h plans for the engine's pose lanes");
 
@@ -323,6 +325,23 @@ struct EngineDepth {
     }
 };
 
+// Track quality on the engine (roft_engine_enable_quality): one record per (frame, object) in a ring of the log's capacity, written by
+// one launch per batch behind both pose lanes (engine_step.hip).  The launch's events live here, one pair per slot of the batch
+// ring, created when quality is enabled (with timing: roft_debug_quality_kernel_ms reads the pair of the last launch).
+struct EngineQuality {
+    bool enabled = false;
+    roft_quality_params prm{};
+    DevBuf<QualityRaw> ring;             // [cap][objects]
+    int cap = 0;
+    hipEvent_t ev_start[8] = {}, ev_done[8] = {};   // per batch-ring slot: bound to the launch's dispatch; ev_done is what the host waits for
+    int last_slot = -1;                  // batch-ring slot of the last launch
+    ~EngineQuality()
+    {
+        for (hipEvent_t ev : ev_start) if (ev) (void)hipEventDestroy(ev);
+        for (hipEvent_t ev : ev_done) if (ev) (void)hipEventDestroy(ev);
+    }
+};
+
 // Device copies of HOST inputs: a ring of `retain` frame slots, each a bump allocator over chunks of device memory that
 // are allocated when a frame first needs them and kept (a slot grows to the largest frame it ever held: 64 objects with
 // their own 640x480 depth + CV_32FC2 flow + mask streams need 239 MB per slot, a shared scene 7 MB + the masks); identical
@@ -389,6 +408,7 @@ struct BatchSlot {
     bool done_used[kNumLin] = {false, false};   // the lane had work
     bool vel_used = false;               // the velocity chain ended with ev_vel
     bool feat_used = false;              // a feature kernel ran on the mask stream and ended with ev_feat
+    bool quality_used = false;           // the batch launched the quality kernel: it ends with EngineQuality::ev_done of this slot
     int end_frame = 0;                   // frame counter behind the batch
 };
 
@@ -443,6 +463,7 @@ struct roft_engine {
     bool produced_flows = false;           // the submit enqueued production (flows: pyramids, flows, deferred flow clones; raw depth: its products) behind its copies: ev_up covers it
     EngineFlow flow;                       // camera images -> flows (roft_engine_enable_flow)
     EngineDepth depth;                     // raw sensor depth -> float depth (roft_engine_enable_raw_depth); its products ride on produced_flows
+    EngineQuality quality;                 // track quality (roft_engine_enable_quality)
     unsigned feat_frames = 0;              // bit t: some object buffers outlier-rejection features in frame t of the batch
     unsigned new_mask_frames = 0;   // bit t: some object receives a mask in frame t of the batch (of either form)
     unsigned plain_mask_frames = 0; // bit t: ... a per-object byte mask (what mask_ingest_kernel / ctrl_ingest_kernel convert)
@@ -513,3 +534,5 @@ __global__ void probe_sectors_kernel(const unsigned* buf, unsigned sector_mask, 
 bool build_pose_program(const roft_config& cfg, Sched& o, const roft_frame_input& in, FrameCtrl& c);
 // engine_step.hip
 int step_batch(roft_engine* e);
+// engine_quality.hip
+unsigned quality_frames_of_batch(const roft_engine* e, int* n_out);   // four bits per frame of the submitted batch that gets a record

@@ -53,6 +53,8 @@ int roft_get_outputs(roft_engine* e, roft_object_output* outs, int n_outs)
 int roft_engine_enable_log(roft_engine* e, int n_frames)
 {
     if (!e || n_frames <= 0) return fail(ROFT_ERR_INVALID, "bad arguments");
+    if (e->quality.enabled && n_frames != e->arr.a.log_cap)
+        return fail(ROFT_ERR_STATE, "track quality is on: its ring has the log's capacity (" + std::to_string(e->arr.a.log_cap) + " frames), which cannot change any more");
     if (int rc = roft_sync(e)) return rc;
     HIP_TRY(e->arr.log.ensure((size_t)n_frames * e->cfg.max_objects, true));
     e->arr.a.out_log = e->arr.log.p;

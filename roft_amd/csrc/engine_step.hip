@@ -24,8 +24,20 @@
 //  (3) The outlier test's workgroups that share an alternative (k_render.hip) never wait for each other: each writes its slab,
 //      counts itself in and EXITS unless it is the last to arrive; the last one merges.  No co-residency is needed.
 //  (4) The mask frames hand over through kernel boundaries only (one launch per frame): no barrier among workgroups in memory.
-//  (5) The host blocks in exactly two places: roft_frames_submit on ev_done / ev_vel / ev_feat of batch b - lead (the in-flight bound that
-//      sizes every ring), and roft_sync.  Both wait for events of work already enqueued.
+//  (5) The host blocks in exactly two places: roft_frames_submit on ev_done / ev_vel / ev_feat / ev_quality of batch b - lead (the in-flight
+//      bound that sizes every ring), and roft_sync.  Both wait for events of work already enqueued.
+//  (6) Track quality (roft_engine_enable_quality; a batch without records enqueues none of this).  The launch of batch b is the LAST
+//      thing the batch enqueues: on the stream of the last pose lane behind that lane's last segment, behind ev_done of the other
+//      lane (its log rows) and ev_mask of the batch (its planes; the mask stream waited for the uploads, so its depth too) -- both
+//      recorded earlier in this very step_batch, so (1) holds.  No fifth stream: a stream of its own would share a hardware queue
+//      with one of the four chains and its event wait would block that chain.  It ends with ev_quality, which joins the events
+//      wait_batch and roft_sync wait for.  Two lifetimes hang on that host wait.  (a) What the kernel reads outlives it: plane ring
+//      slots, staged HOST depth and the caller's DEVICE buffers are re-used only by a batch whose submit has waited for batch
+//      b (the in-flight bound); log rows and quality records lie in rings of at least lead x max_batch_frames rows -- the frames
+//      that can be in flight --, which roft_engine_enable_quality enforces.  (b) The control blocks it reads are those of the batch's
+//      own slot of the batch ring (BatchSlot::dctrl, kBatchRing slots > lead): rewritten by batch b + kBatchRing, whose submit has
+//      waited for batch b + kBatchRing - lead > b.  It reads NOTHING from the two mask tables that alternate by batch parity
+//      (EngineArrays::mrec), which the preparation of batch b + 2 resets -- the reason for prep_waits_feat.
 #include "engine_internal.h"
 
 // Control blocks of a batch: pinned (device-visible) host staging -> device by a kernel, so that they travel in-order on the
@@ -301,6 +313,29 @@ static int enqueue_lane(Enqueue& q, int lin)
     return q.signalled(lp.ev_done, q.cur.ev_done[lin], sp);
 }
 
+// Track quality: every (frame, object) of the batch that gets a record in one launch, behind both lanes.
+static int enqueue_quality(Enqueue& q)
+{
+    roft_engine* e = q.e;
+    const BatchPlan& p = q.p;
+    q.cur.quality_used = p.ev_quality != Signal::none;
+    if (!p.quality) return ROFT_OK;
+    const int slot = e->batch_counter % roft_engine::kBatchRing;
+    hipStream_t sp = e->pose_stream[kNumLin - 1];
+    if (p.quality_waits_mask) TRY(q.wait(sp, q.cur.ev_mask));
+    if (p.quality_waits_lane) TRY(q.wait(sp, q.cur.ev_done[0]));
+    int n_frames = 0;
+    const unsigned packed = quality_frames_of_batch(e, &n_frames);
+    EngineQuality& eq = e->quality;
+    launch_quality(q.a, eq.ring.p, eq.cap, packed, n_frames, eq.prm.depth_tolerance, e->cfg.depth_maximum, 0, sp, eq.ev_start[slot],
+                   Enqueue::stop(p.ev_quality, eq.ev_done[slot]));
+    ++q.launches;
+    CHECK_LAUNCH("track quality");
+    tmark(e, "track_quality", 3);
+    eq.last_slot = slot;
+    return q.signalled(p.ev_quality, eq.ev_done[slot], sp);
+}
+
 // everything plan_batch may read, from the engine as the submit left it
 static PlanInputs plan_inputs(roft_engine* e)
 {
@@ -323,6 +358,7 @@ static PlanInputs plan_inputs(roft_engine* e)
     in.outlier_bands_per_alternative = e->cfg.outlier_bands_per_alternative;
     in.conflict_free = e->streams && e->streams->conflicts == 0;
     in.up_stream_distinct = e->up_stream != e->stream;
+    if (e->quality.enabled) (void)quality_frames_of_batch(e, &in.quality_frames);
     in.feat_used_two_back = e->batch_counter >= 2 && e->slot_of(e->batch_counter - 2).feat_used;
     in.vel_used_prev = e->batch_counter >= 1 && e->slot_of(e->batch_counter - 1).vel_used;
     for (int l = 0; l < kNumLin; ++l) {
@@ -366,6 +402,7 @@ int step_batch(roft_engine* e)
     TRY(enqueue_velocity(q));
     HP_MARK(e, 5, hp_t);
     for (int lin = 0; lin < kNumLin; ++lin) TRY(enqueue_lane(q, lin));
+    TRY(enqueue_quality(q));
     HP_MARK(e, 6, hp_t);
     if (e->knobs.host_prof) {
         e->hp_batches++;

@@ -281,6 +281,27 @@ class ROFTFilterBatch:
         L.check(L.lib().roft_debug_depth_kernel_ms(self._h, C.byref(ms)))
         return ms.value
 
+    def enable_quality(self, every=1, depth_tolerance=0.01):
+        """Track quality (roft_engine_enable_quality): from now on every frame with frame % every == 0 leaves one record per object
+        -- silhouette overlap and depth residual of its final estimate against its own mask and depth.  After enable_log (whose
+        capacity is the quality ring's), before the first frame."""
+        prm = L.QualityParams(int(every), float(depth_tolerance))
+        L.check(L.lib().roft_engine_enable_quality(self._h, C.byref(prm)))
+
+    def quality(self, first, n):
+        """The quality records of frames first .. first + n - 1: a structured array [n, n_objects] (ops.QUALITY_DTYPE; frame == -1:
+        no record).  ops.quality_overlap(records) forms the intersection over union.  Syncs."""
+        from .ops import QUALITY_DTYPE
+        out = np.zeros((n, self.n_objects), QUALITY_DTYPE)
+        L.check(L.lib().roft_engine_get_quality(self._h, first, n, out.ctypes.data))
+        return out
+
+    def quality_kernel_ms(self):
+        """Device time (ms, HIP events on its dispatch) of the last quality launch."""
+        ms = C.c_double(0.0)
+        L.check(L.lib().roft_debug_quality_kernel_ms(self._h, C.byref(ms)))
+        return ms.value
+
     def retain_frames(self):
         return L.lib().roft_engine_retain_frames(self._h)
 

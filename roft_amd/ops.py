@@ -205,6 +205,33 @@ def outlier_test(cam, divider, depth, mask, mesh, x2, q2, bands=0, vertex_cache=
     return Lv, ns, sel.value, t
 
 
+# numpy mirror of roft_quality_record (40 bytes)
+QUALITY_DTYPE = np.dtype([("frame", np.int32), ("n_mask", np.int32), ("n_render", np.int32), ("n_both", np.int32), ("n_depth", np.int32),
+                          ("n_front", np.int32), ("n_behind", np.int32), ("reserved", np.int32), ("depth_err", np.float64)])
+
+
+def quality_overlap(rec):
+    """Intersection over union of mask and render silhouette, n_both / (n_mask + n_render - n_both), of quality records (a structured
+    array or one record); NaN where both are empty or there is no record."""
+    rec = np.asarray(rec)
+    union = rec["n_mask"].astype(np.float64) + rec["n_render"] - rec["n_both"]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where((union > 0) & (rec["frame"] >= 0), rec["n_both"] / union, np.nan)
+
+
+def track_quality(cam, divider, depth, mask, mesh, x, q, depth_tolerance=0.01, depth_maximum=2.0, window_pixels=0):
+    """Silhouette overlap and depth residual of the pose (x, q) of `mesh` against a mask and a depth image, by the engine's own
+    kernel on host buffers (roft_track_quality; the contract: include/roft_engine.h, section 3d).  mask: the pixels of value > 1 are
+    the object.  window_pixels > 0 caps the kernel's LDS depth window (strips; no bit changes).  Returns one QUALITY_DTYPE record."""
+    depth = np.ascontiguousarray(depth, np.float32)
+    mask = np.ascontiguousarray(mask, np.uint8)
+    x, q = _f64(np.asarray(x).reshape(3)), _f64(np.asarray(q).reshape(4))
+    rec = L.QualityRecord()
+    L.check(L.lib().roft_track_quality(C.byref(cam), divider, _p(depth), _p(mask), C.byref(mesh), _p(x), _p(q), float(depth_tolerance),
+                                       float(depth_maximum), window_pixels, C.byref(rec)))
+    return np.frombuffer(bytes(rec), QUALITY_DTYPE)[0].copy()
+
+
 POSE_ERROR_KINDS = {"add": L.POSE_ERROR_ADD, "adi": L.POSE_ERROR_ADDS, "adds": L.POSE_ERROR_ADDS}
 
 

@@ -5,7 +5,7 @@ files (`pose_estimate`, `velocity_estimate`, ROFTFilter.cpp:386-394) -- what `te
   run_sequence.py --root DIR --object NAME --mesh model.obj [--flow-set nvof_1_slow] [--mask-set NAME]
                   [--pose-set dope] [--out PREFIX] [--compute-flow nvof1|nvof2 | --flow-on-engine nvof1|nvof2] [--no-delay]
                   [--init-pose x y z qw qx qy qz] [--raw-depth SCALE]
-                  [--start-at-first-detection] [--score-on-device] [--render-overlay DIR]
+                  [--start-at-first-detection] [--score-on-device] [--render-overlay DIR] [--quality FILE]
                   [--from config_fast_ycb.cfg [--group::key value ...]]
 
 --from reads the filter parameters from one of the reference's configuration files (config/config_fast_ycb.cfg,
@@ -21,7 +21,9 @@ without a float copy: the engine converts them on the device (roft_engine_enable
 the ADD-S / ADD AUC and the RMSE metrics of evaluation/metrics.py are printed as one JSON line.  --score-on-device adds the
 ADD-S and ADD of the same frames on EVERY vertex of the mesh, computed on the GPU from the engine's device-side log
 (roft_engine_score_log: the estimates never leave the device).  --render-overlay DIR draws the estimate over the sequence's
-grayed RGB frames (DIR/<frame>.png) with tools/render_results.py once the logs are written.
+grayed RGB frames (DIR/<frame>.png) with tools/render_results.py once the logs are written.  --quality FILE turns track quality on
+(roft_engine_enable_quality) and writes one row per frame: frame, the seven counts of roft_quality_record, depth_err and the overlap
+n_both / (n_mask + n_render - n_both), space separated under a header line.
 """
 import argparse
 import json
@@ -59,6 +61,8 @@ def main(argv=None):
                     help="also score the run on the object's full mesh with roft_engine_score_log (needs gt/poses.txt)")
     ap.add_argument("--render-overlay", default=None, metavar="DIR",
                     help="after the run, draw the estimate over SEQ/rgb/<i>.png into DIR/<i>.png (tools/render_results.py)")
+    ap.add_argument("--quality", default=None, metavar="FILE",
+                    help="score every estimate against its frame's mask and depth on the device; one row per frame into FILE")
     ap.add_argument("--from", dest="cfg_file", default=None, help="ROFT configuration file (libconfig), overrides as --a::b::c value")
     args, overrides = ap.parse_known_args(argv)
 
@@ -138,7 +142,9 @@ def main(argv=None):
     if n <= 0:
         sys.stderr.write("the first detection arrives after the last frame\n")
         return 1
-    eng.enable_log(n)
+    eng.enable_log(max(n, 6) if args.quality else n)   # (the quality ring: at least the six one-frame batches that can be in flight)
+    if args.quality:
+        eng.enable_quality()
     if args.flow_on_engine:
         eng.enable_flow()
     if args.raw_depth is not None:
@@ -153,6 +159,15 @@ def main(argv=None):
         g = io.read_poses(gt_path)[0][start + 12:start + n]
         for kind in ("adi", "add"):
             device_scores[kind] = eng.score_log(kind, 0, 12, len(g), g)
+    if args.quality:
+        from roft_amd.ops import quality_overlap
+        rec = eng.quality(0, n)[:, 0]
+        iou = quality_overlap(rec)
+        with open(args.quality, "w") as f:
+            f.write("# frame n_mask n_render n_both n_depth n_front n_behind depth_err overlap\n")
+            for r, o in zip(rec, iou):
+                f.write("%d %d %d %d %d %d %d %.17g %.6f\n" % (start + r["frame"], r["n_mask"], r["n_render"], r["n_both"], r["n_depth"],
+                                                              r["n_front"], r["n_behind"], r["depth_err"], o))
     eng.close()
     prefix = args.out if args.out is not None else os.path.join(args.root, "roft_mi355x_")
     io.write_estimate_logs(prefix, pose[:, 0], twist[:, 0])
@@ -178,6 +193,8 @@ def main(argv=None):
         if rc != 0:
             return rc
         report["overlay"] = args.render_overlay
+    if args.quality:
+        report["quality"] = args.quality
     print(json.dumps(report))
     return 0
 
