@@ -52,25 +52,37 @@ inline SchedKnobs knobs_from_env()
     return k;
 }
 
+// What a submit call leaves behind for the plan of its batch: declared once, kept by the engine (PendingBatch in engine_internal.h)
+// and read by plan_batch as part of its PlanInputs.
+struct SubmitFacts {
+    int T = 1;                      // frames of the batch
+    bool had_uploads = false;       // HOST inputs were copied
+    // camera images / raw depth: the submit enqueued production (pyramids, flows, deferred flow clones; depth products) on the upload
+    // stream behind its copies (ev_up is recorded behind it, uploads or not)
+    bool produced_flows = false;
+    unsigned plain_mask_frames = 0; // bit t: frame t delivers a per-object byte mask (what the ingest of the control-block launch converts)
+    int label_sets = 0;             // distinct (frame, label image) pairs of the batch: masks delivered as label images
+    bool any_feat = false, any_feat_now = false;
+    bool feat_dep_in_batch = false; // an outlier test of the batch reads features buffered by a frame of the same batch
+    int n_segments[kPlanLanes] = {1, 1};          // pose chain segments per lane (1 + outlier tests of the busiest object)
+    bool lin_any[kPlanLanes] = {false, false};    // some object has a frame on the lane in the batch
+    // per lane: objects with a frame on the lane, and how many of them START with a step whose twist was published by an EARLIER batch
+    // (the first step of a re-sync replay reads the twist of pose_frames_between frames ago): such a lane can run its first segment --
+    // and the outlier test behind it -- before this batch's velocity filter exists
+    int lane_objs[kPlanLanes] = {0, 0}, lane_old_first[kPlanLanes] = {0, 0};
+    int relabel_wait[kPlanLanes] = {-1, -1};      // batch of the OTHER lane this lane's launches must follow (slots that changed lanes)
+};
+
 // Everything a batch's plan depends on.  Counters and counts only -- never a timing (the launch graph of a run is reproducible).
-struct PlanInputs {
+struct PlanInputs : SubmitFacts {
     SchedKnobs knobs;
     bool multi = true;              // the chains have streams of their own (!knobs.one_stream)
     bool timing = false;            // roft_engine_enable_timing
     int timing_level = 2;           // 2: markers between the launch groups
     bool wait_value_ok = true;      // the device can make a stream wait for a value in memory
     bool have_skf_started = true;   // the counter the resident-workgroup gate waits on exists
-    int T = 1, n_obj = 0, cus = 256;
+    int n_obj = 0, cus = 256;
     int batch_counter = 0, idle_mark = 0, lead = 6, completed_batches = 0;
-    // what the submit left
-    bool had_uploads = false;
-    unsigned new_mask_frames = 0;   // bit t: frame t delivers a per-object byte mask (what the ingest of the control-block launch converts)
-    int label_sets = 0;             // distinct (frame, label image) pairs of the batch: masks delivered as label images
-    bool any_feat = false, any_feat_now = false, feat_dep_in_batch = false;
-    int n_segments[kPlanLanes] = {1, 1};
-    bool lin_any[kPlanLanes] = {false, false};
-    int lane_objs[kPlanLanes] = {0, 0}, lane_old_first[kPlanLanes] = {0, 0};
-    int relabel_wait[kPlanLanes] = {-1, -1};
     int outlier_bands_per_alternative = 0;
     // the stream set
     bool conflict_free = false;         // probed: no two of its busy streams share a hardware queue
@@ -79,8 +91,6 @@ struct PlanInputs {
     bool feat_used_two_back = false;    // batch b - 2 ran a feature kernel on the mask stream
     bool vel_used_prev = false;         // batch b - 1 ended its velocity chain with ev_vel
     bool done_used_relabel[kPlanLanes] = {false, false};   // the other lane had work in batch relabel_wait[lane]
-    // camera images: the submit produced flows on the upload stream (ev_up is recorded behind them, uploads or not)
-    bool produced_flows = false;
     // track quality (roft_engine_enable_quality): frames of the batch that get a record (0: quality off, or no frame of the batch is due)
     int quality_frames = 0;
 };
@@ -214,13 +224,13 @@ BatchPlan plan_batch(const PlanInputs& in, AloneFn&& alone)
     p.wait_up = multi && (in.had_uploads || in.produced_flows) && !p.prep;   // (prep: same stream as the uploads and the flow production)
     // Otherwise control blocks and the ingest of the delivered masks in ONE launch -- on the mask stream they and the first mask
     // frame were three dependent launches (27 - 35 us in front of the frame).  Not under timing: the marks name the two kernels.
-    p.try_fused = k.ctrl_ingest != 0 && !p.prep && in.new_mask_frames != 0 && !in.timing;
+    p.try_fused = k.ctrl_ingest != 0 && !p.prep && in.plain_mask_frames != 0 && !in.timing;
     p.ev_ctrl = (multi && (in.T == 1 || any_early)) ? Signal::stop : Signal::none;
     // Masks that arrive as label images: ONE launch for all of them, whatever the number of objects, frames and images, behind the
     // control blocks (it reads the table that travels with them) and whatever ingest there is of per-object masks; a batch
     // without label images enqueues what it always did.
     p.label_ingest = in.label_sets > 0;
-    p.ev_prep = !p.prep ? Signal::none : (full || (in.new_mask_frames == 0 && !p.label_ingest)) ? Signal::record : Signal::stop;   // (no ingest: no kernel to end with it)
+    p.ev_prep = !p.prep ? Signal::none : (full || (in.plain_mask_frames == 0 && !p.label_ingest)) ? Signal::record : Signal::stop;   // (no ingest: no kernel to end with it)
 
     // In a burst the velocity chain is released when the masks its flow measurements read are complete -- frames 0 .. T - 2: the
     // measurement of frame t is taken inside the mask of frame t - 1 --, one mask frame (the one that chases a delivered mask

@@ -521,7 +521,6 @@ static int engine_setup(roft_engine* e, const roft_config* cfg)
                 HIP_TRY(hipStreamWaitValue64(e->pose_stream[l], e->arr.skf_started.p, 0ull, hipStreamWaitValueGte, ~0ull));   // (satisfied at once)
         for (int l = 0; l < kNumLin; ++l) HIP_TRY(hipStreamSynchronize(e->pose_stream[l]));
     }
-    e->feat_batch.assign((size_t)cfg->max_objects * kFeatRing, -1);
     return ROFT_OK;
 }
 

@@ -51,6 +51,7 @@ int fail(int code, const std::string& msg);
         if (_e != hipSuccess)                                                                              \
             return fail(ROFT_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e));               \
     } while (0)
+#define TRY(call) do { if (int _rc = (call)) return _rc; } while (0)   // (a call that has set the error string itself)
 
 template <class T>
 struct DevBuf {
@@ -242,6 +243,7 @@ struct Sched {
     int feat_slot = 0;                 // feature ring slot holding the buffered outlier-rejection features
     int feat_next = 0;                 // next ring slot to write
     int feat_use[kFeatRing];           // last batch that reads or writes each feature ring slot (-1: never used)
+    int feat_batch[kFeatRing];         // batch that last wrote each feature set (-1: none)
     int n_hist = 0;
     FlowEntry hist[kMaxFlowHist];      // last valid flows, newest first
     int n_stamps = 0;
@@ -258,7 +260,7 @@ struct Sched {
     // generation (EngineFlow::pyr; -1: it carried none), and the flow the engine produced for the last frame (null: none)
     int pyr_prev = -1;
     const void* flow_made = nullptr;
-    Sched() { for (int& u : feat_use) u = -1; }
+    Sched() { for (int i = 0; i < kFeatRing; ++i) feat_use[i] = feat_batch[i] = -1; }
 };
 
 struct OwnedFlow {
@@ -279,8 +281,9 @@ struct HostObject {
 };
 
 // Camera images on the engine (roft_engine_enable_flow): what a submit call enqueues on the upload stream, frame by frame, behind
-// the copies of its HOST inputs.  Built by submit_frames on the host only; enqueued when the whole batch has been accepted, so a
-// refused submit leaves the pyramids on the device as they were (the per-object side, Sched::pyr_prev, rolls back with Sched).
+// the copies of its HOST inputs.  Built by submit_frames on the host only (PendingBatch::flow_jobs); enqueued when the whole batch has
+// been accepted, so a refused submit leaves the pyramids on the device as they were (the per-object side, Sched::pyr_prev, rolls back
+// with Sched).
 struct FlowImageJob { const void* dev; int type; };            // a distinct image of a frame; its index is its pyramid slot
 struct FlowPairJob { int pyr0, pyr1; unsigned char* out; };    // slots in the generations of frame - 1 and frame; the product's place
 struct FlowCloneJob { void* dst; const void* src; };           // a flow that outlived the retention window (OwnedFlow), copied behind the batch's production
@@ -299,23 +302,22 @@ struct EngineFlow {
     // grows to the largest number of distinct images a frame ever brought.
     std::vector<std::vector<DevBuf<float>*>> pyr;
     DevBuf<float> coarse, field;        // workspace of ONE chunk of kOfChunk pairs, reused chunk after chunk in stream order
-    std::vector<FlowFrameJobs> jobs;    // of the submit call under way
-    roft_engine_flow_stats stats{}, stats_backup{};
+    roft_engine_flow_stats stats{};
     ~EngineFlow() { for (auto& g : pyr) for (auto* b : g) delete b; }
 };
 
 // Raw sensor depth on the engine (roft_engine_enable_raw_depth): inputs[].depth carries the sensor's 16-bit frame; the float depth
 // the kernels read is made on the upload stream behind the copies, where a staged HOST depth of the frame would have been copied
-// (stage_alloc in the frame's staging slot: it lives exactly as long as one).  Built by submit_frames on the host only and enqueued
-// when the whole batch has been accepted, like the flow production: a refused submit leaves the device untouched.
+// (stage_alloc in the frame's staging slot: it lives exactly as long as one).  Built by submit_frames on the host only
+// (PendingBatch::depth_jobs) and enqueued when the whole batch has been accepted, like the flow production: a refused submit leaves
+// the device untouched.
 struct DepthJob { int t; const uint16_t* raw; float* out; };   // a distinct raw image of frame t of the batch and its product's place
 struct EngineDepth {
     bool enabled = false;
     roft_depth_source src{};
     size_t raw_pixels = 0;            // readings per raw image (the depth source's size)
     DepthAlignGeom geom{};            // src.align != 0
-    std::vector<DepthJob> jobs;       // of the submit call under way
-    roft_engine_depth_stats stats{}, stats_backup{};
+    roft_engine_depth_stats stats{};
     hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the depth kernels of the last submit (roft_debug_depth_kernel_ms)
     bool timed = false;
     ~EngineDepth()
@@ -388,6 +390,51 @@ struct GatherItem { const void* src; void* dst; size_t bytes; };   // one small 
 constexpr int kGatherCap = 8192;                                    // items per batch (8 frames x 1024 objects)
 constexpr size_t kGatherMaxBytes = (size_t)2 << 20;                 // larger images go through the copy engine
 
+// The submitted, not yet stepped batch: everything a submit call leaves behind for roft_step, and what it collects on its way.
+// reset() is the ONE place where a new submit call starts from nothing; the vectors keep their capacity (a frame's flow job lists
+// are built anew, as they always were).
+struct PendingBatch {
+    SubmitFacts facts;                 // what plan_batch reads (batch_plan.h)
+    unsigned feat_frames = 0;          // bit t: some object buffers outlier-rejection features in frame t of the batch
+    unsigned new_mask_frames = 0;      // bit t: some object receives a mask in frame t of the batch, of either form (facts.plain_mask_frames: byte masks)
+    // masks from a label image (roft_frames_submit_labels): the batch's objects grouped by (frame, device image); written behind the
+    // control blocks of the staging block by the submit, copied to the device with them (label_table_bytes, a multiple of 16)
+    std::vector<LabelSet> label_sets;  // (facts.label_sets counts them)
+    std::vector<std::vector<LabelMember>> label_members;   // per set
+    size_t label_table_bytes = 0;
+    std::vector<FlowFrameJobs> flow_jobs;   // [T] camera images: what enqueue_flow_production enqueues, frame by frame
+    std::vector<DepthJob> depth_jobs;       // raw depth: what enqueue_depth_production enqueues
+    // Small HOST images in PINNED memory (the per-object masks of a delivery: 64 buffers of 300 KB) are not copied one
+    // hipMemcpyAsync each but fetched by ONE kernel over the bus (engine_submit.hip, gather_copy_kernel): what to fetch
+    std::vector<GatherItem> gather;         // collected by stage_host, launched by flush_gather
+    double submit_t0 = 0.0, submit_us = 0.0, wait_us = 0.0;   // host times of the submit call (roft_batch_trace); like `throttled`, written by every call
+    bool throttled = false;   // MEASURED, diagnostics only (roft_batch_trace): the submit had to wait for the in-flight bound
+    std::vector<int> lane_tests;            // [objects][kNumLin] outlier tests of the object on the lane so far in the batch (-1: no frame on it yet)
+    void reset(int n_obj, int T)
+    {
+        facts = SubmitFacts{};
+        facts.T = T;
+        feat_frames = new_mask_frames = 0;
+        label_sets.clear();
+        label_members.clear();
+        label_table_bytes = 0;
+        flow_jobs.assign((size_t)T, FlowFrameJobs{});
+        depth_jobs.clear();
+        gather.clear();
+        lane_tests.assign((size_t)n_obj * kNumLin, -1);
+    }
+};
+
+// "A refused submit consumes nothing": what roft_frames_submit_images puts back when it fails.  The schedule mirrors of every object
+// and the counters of the two producers; NOT roft_engine_stats::h2d_bytes / h2d_copies, which count what crossed the bus -- a refused
+// call's copies did.  (What else a submit writes is either the PendingBatch, which the next call resets, or staging memory of the
+// batch's own frames, which the next call recycles.)
+struct SubmitSnapshot {
+    std::vector<Sched> sched;
+    roft_engine_flow_stats flow{};
+    roft_engine_depth_stats depth{};
+};
+
 // What one batch in flight owns: a slot of the batch ring.
 struct BatchSlot {
     hipEvent_t ev_up = nullptr;     // uploads of the batch on the device, and the flows the submit produced from camera images behind them
@@ -433,9 +480,6 @@ struct roft_engine {
     int lead = 6;         // batches
     int hist_cap = 6;     // flows kept per object
     int retain = ROFT_RETAIN_FRAMES;
-    // Small HOST images in PINNED memory (the per-object masks of a delivery: 64 buffers of 300 KB) are not copied one
-    // hipMemcpyAsync each but fetched by ONE kernel over the bus (engine_submit.hip, gather_copy_kernel): what to fetch, per batch
-    std::vector<GatherItem> gather;                    // collected by stage_host during a submit
     BatchSlot ring[kBatchRing];                        // batch b lives in ring[b % kBatchRing]
     BatchSlot& slot_of(int b) { return ring[b % kBatchRing]; }
     SchedKnobs knobs;                                  // the switches, read when the engine is created
@@ -444,40 +488,21 @@ struct roft_engine {
     double hp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     long hp_batches = 0;
     std::vector<HostObject*> objs;
-    std::vector<Sched> backup;
+    SubmitSnapshot snapshot;               // taken when a submit call starts
     std::vector<ObjParams> h_params;
     std::vector<StageFrame> staging;       // [retain]
     ObjState* state_host = nullptr;   // pinned landing block of roft_get_state (velocity belief + corrected pose belief)
     int* dev_error = nullptr;         // pinned word a kernel raises when it gives up (EngineArrays::dev_error)
-    // the submitted, not yet stepped batch
     bool submitted = false;
-    int cur_T = 0;
-    int n_segments[kNumLin] = {1, 1};     // pose chain segments per lane (1 + outlier tests of the busiest object)
-    bool lin_any[kNumLin] = {false, false};   // some object has a frame on the lane in the batch
-    // per lane of the submitted batch: objects with a frame on the lane, and how many of them START with a step whose twist was
-    // published by an EARLIER batch (the first step of a re-sync replay reads the twist of pose_frames_between frames ago): such a
-    // lane can run its first segment -- and the outlier test behind it -- before this batch's velocity filter exists (step_batch)
-    int lane_objs[kNumLin] = {0, 0}, lane_old_first[kNumLin] = {0, 0};
-    int relabel_wait[kNumLin] = {-1, -1};     // batch of the OTHER lane this lane's launches must follow (slots that changed lanes)
-    bool any_feat = false, any_feat_now = false, had_uploads = false;
-    bool produced_flows = false;           // the submit enqueued production (flows: pyramids, flows, deferred flow clones; raw depth: its products) behind its copies: ev_up covers it
+    PendingBatch pending;                  // the submitted (or being submitted), not yet stepped batch
     EngineFlow flow;                       // camera images -> flows (roft_engine_enable_flow)
-    EngineDepth depth;                     // raw sensor depth -> float depth (roft_engine_enable_raw_depth); its products ride on produced_flows
+    EngineDepth depth;                     // raw sensor depth -> float depth (roft_engine_enable_raw_depth); its products ride on SubmitFacts::produced_flows
     EngineQuality quality;                 // track quality (roft_engine_enable_quality)
-    unsigned feat_frames = 0;              // bit t: some object buffers outlier-rejection features in frame t of the batch
-    unsigned new_mask_frames = 0;   // bit t: some object receives a mask in frame t of the batch (of either form)
-    unsigned plain_mask_frames = 0; // bit t: ... a per-object byte mask (what mask_ingest_kernel / ctrl_ingest_kernel convert)
-    // ... from a label image (roft_frames_submit_labels): the batch's objects grouped by (frame, device image); written behind the
-    // control blocks of the staging block by the submit, copied to the device with them (label_table_bytes, a multiple of 16)
-    std::vector<LabelSet> label_sets;
-    std::vector<std::vector<LabelMember>> label_members;   // per set
-    size_t label_table_bytes = 0;
     int prev_T = 0;                 // frames of the batch stepped before
     int batch_counter = 0, frame_counter = 0;
     int completed_batches = 0, completed_frames = 0;
     roft_engine_stats stats{};
     bool device_pointers_checked = false;   // ROFT_MEM_DEVICE inputs are looked up once, on the first submit
-    bool throttled = false;   // MEASURED, diagnostics only (roft_batch_trace): the submit of the current batch had to wait for the in-flight bound
     // A batch is "steady" when at least `lead` batches have been stepped since the engine was last idle (creation, roft_sync and
     // everything that calls it), a burst otherwise: plan_batch.
     int idle_mark = 0;        // batch_counter when the engine was last known idle
@@ -486,10 +511,7 @@ struct roft_engine {
     // trace of the last kTraceRing batches (roft_engine_get_batch_trace)
     static constexpr int kTraceRing = 64;
     roft_batch_trace trace[kTraceRing] = {};
-    double cur_submit_t0 = 0.0, cur_submit_us = 0.0, cur_wait_us = 0.0;
-    bool feat_dep_in_batch = false;        // an outlier test of the batch reads features buffered by a frame of the same batch
     unsigned long long skf_total = 0;      // velocity-filter workgroups launched so far (the value the lanes' gates wait for)
-    std::vector<int> feat_batch;           // [objects][kFeatRing] batch that last wrote each feature set (-1: none)
     // timing
     bool timing = false;
     int timing_level = 2;   // 1: only flow_measure_kernel (two events per batch), 2: every launch group

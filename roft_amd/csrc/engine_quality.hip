@@ -11,7 +11,7 @@ unsigned quality_frames_of_batch(const roft_engine* e, int* n_out)
     unsigned packed = 0;
     int n = 0;
     const int every = std::max(e->quality.prm.every, 1);
-    for (int t = 0; t < e->cur_T && t < 8; ++t)
+    for (int t = 0; t < e->pending.facts.T && t < 8; ++t)
         if ((e->frame_counter + t) % every == 0) packed |= (unsigned)t << (4 * n++);
     if (n_out) *n_out = n;
     return packed;

@@ -16,7 +16,7 @@
 //      Camera images (roft_frames_submit_images): the submit call enqueues the flow production -- pyramids, Lucas-Kanade levels, the
 //      clones of aged-out flows -- on the UPLOAD stream behind its copies and records ev_up behind the production, so ev_up -> mask /
 //      velocity stream covers the produced flows exactly as it covers a copied flow; it is recorded, and waited for, also when every
-//      input was DEVICE memory and nothing was copied (PlanInputs::produced_flows).  With the preparation on the upload stream the
+//      input was DEVICE memory and nothing was copied (SubmitFacts::produced_flows).  With the preparation on the upload stream the
 //      control blocks follow the production in stream order and ev_prep carries it.  The velocity stream reads flows only behind an
 //      event of this batch's mask stream (ev_ctrl / ev_part / ev_mask), which has waited.  The HOST waits for ev_host, recorded
 //      behind the copies and BEFORE the production: no kernel is waited for, and no kernel waits in memory.
@@ -129,13 +129,13 @@ struct Enqueue {
         return ROFT_OK;
     }
 };
-#define TRY(call) do { if (int _rc = (call)) return _rc; } while (0)
 
 // Control blocks of the batch -> device (+ reset of the mask chain's counters), ingest of the masks delivered with the batch
 // (tables and ingest slots of this batch's parity: the carry of the chain before stays readable).
 static int enqueue_preparation(Enqueue& q)
 {
     roft_engine* e = q.e;
+    const PendingBatch& pb = e->pending;
     const BatchPlan& p = q.p;
     const EngineArrays& a = q.a;
     hipStream_t s = e->stream, sp = p.prep ? e->up_stream : s;
@@ -148,13 +148,13 @@ static int enqueue_preparation(Enqueue& q)
     tmark(e, nullptr, p.prep ? 4 : 0);
     static_assert(sizeof(FrameCtrl) % 16 == 0, "FrameCtrl is copied in 16-byte units");
     // (the label table of the batch lies behind its control blocks and is copied with them)
-    const size_t n16 = (sizeof(FrameCtrl) * (size_t)a.n_obj * a.T + (p.label_ingest ? e->label_table_bytes : 0)) / 16;
+    const size_t n16 = (sizeof(FrameCtrl) * (size_t)a.n_obj * a.T + (p.label_ingest ? pb.label_table_bytes : 0)) / 16;
     const hipEvent_t ctrl_stop = Enqueue::stop(p.ev_ctrl, q.cur.ev_ctrl);
     // masks delivered as label images: one launch, the preparation's last (it ends with ev_prep where the plan has one)
     auto label_ingest = [&]() -> int {
         LabelIngestArgs la;
         la.sets = reinterpret_cast<const LabelSet*>(a.ctrl + (size_t)a.n_obj * a.T);
-        la.members = reinterpret_cast<const LabelMember*>(la.sets + e->label_sets.size());
+        la.members = reinterpret_cast<const LabelMember*>(la.sets + pb.label_sets.size());
         la.planes = a.planes;
         la.plane_words = a.plane_words;
         la.obj_stride = (size_t)kPlaneSlotsTotal * 2 * a.plane_words;
@@ -162,12 +162,12 @@ static int enqueue_preparation(Enqueue& q)
         la.mrec = a.mrec;
         la.n_obj = a.n_obj;
         la.n_grp = a.cam.W * a.cam.H / 64;
-        launch_label_ingest(la, (int)e->label_sets.size(), sp, Enqueue::stop(p.ev_prep, q.cur.ev_prep));
+        launch_label_ingest(la, (int)pb.label_sets.size(), sp, Enqueue::stop(p.ev_prep, q.cur.ev_prep));
         ++q.launches;
         CHECK_LAUNCH("label image ingest");
         return ROFT_OK;
     };
-    if (p.try_fused && launch_ctrl_ingest(q.cur.stage, a, n16, e->plain_mask_frames, sp, ctrl_stop)) {
+    if (p.try_fused && launch_ctrl_ingest(q.cur.stage, a, n16, pb.facts.plain_mask_frames, sp, ctrl_stop)) {
         ++q.launches;
         CHECK_LAUNCH("FrameCtrl upload + mask ingest");
         return p.label_ingest ? label_ingest() : ROFT_OK;
@@ -178,9 +178,9 @@ static int enqueue_preparation(Enqueue& q)
     CHECK_LAUNCH("FrameCtrl upload");
     int last = -1;
     for (int t = 0; t < a.T; ++t)
-        if (e->plain_mask_frames & (1u << t)) last = t;
+        if (pb.facts.plain_mask_frames & (1u << t)) last = t;
     for (int t = 0; t <= last; ++t)
-        if (e->plain_mask_frames & (1u << t)) {
+        if (pb.facts.plain_mask_frames & (1u << t)) {
             launch_mask_ingest(a, t, sp, (t == last && !p.label_ingest) ? Enqueue::stop(p.ev_prep, q.cur.ev_prep) : nullptr);
             ++q.launches;
         }
@@ -202,14 +202,14 @@ static int enqueue_mask_frames(Enqueue& q)
     const BatchPlan& p = q.p;
     hipStream_t s = e->stream;
     tmark(e, nullptr, 0);
-    q.launches += launch_mask_chain(q.a, e->cfg.mask_frames_between, e->cfg.flow_aided_segmentation, e->new_mask_frames, s,
+    q.launches += launch_mask_chain(q.a, e->cfg.mask_frames_between, e->cfg.flow_aided_segmentation, e->pending.new_mask_frames, s,
                                     Enqueue::stop(p.ev_mask, q.cur.ev_mask), p.part_gate ? q.cur.ev_part : nullptr);
     CHECK_LAUNCH("mask chain");
     tmark(e, "mask_chain", 0);
     TRY(q.signalled(p.ev_mask, q.cur.ev_mask, s));
     q.cur.feat_used = p.ev_feat != Signal::none;   // (for wait_batch, like vel_used and done_used below)
     if (p.feat == FeatRun::mask_stream) {
-        launch_features(q.a, s, Enqueue::stop(p.ev_feat, q.cur.ev_feat), e->feat_frames);
+        launch_features(q.a, s, Enqueue::stop(p.ev_feat, q.cur.ev_feat), e->pending.feat_frames);
         ++q.launches;
         CHECK_LAUNCH("features");
         tmark(e, "features", 0);
@@ -260,7 +260,7 @@ static int enqueue_velocity(Enqueue& q)
     TRY(q.signalled(skf_how, skf_ev, sv));
     if (feat_behind) {
         if (p.feat_waits_mask) TRY(q.wait(sv, q.cur.ev_mask));
-        launch_features(a, sv, Enqueue::stop(p.ev_vel, q.cur.ev_vel), e->feat_frames);
+        launch_features(a, sv, Enqueue::stop(p.ev_vel, q.cur.ev_vel), e->pending.feat_frames);
         ++q.launches;
         CHECK_LAUNCH("features");
         tmark(e, "features", 2);
@@ -280,8 +280,9 @@ static int enqueue_lane(Enqueue& q, int lin)
     hipStream_t sp = e->pose_stream[lin];
     q.cur.done_used[lin] = lp.ev_done != Signal::none;
     // slots handed over to this lane (submit_frames): behind the other lane's last launch that touched them
-    if (lp.wait_relabel) TRY(q.wait(sp, e->slot_of(e->relabel_wait[lin]).ev_done[1 - lin]));
-    if (!e->lin_any[lin]) return ROFT_OK;
+    const SubmitFacts& facts = e->pending.facts;
+    if (lp.wait_relabel) TRY(q.wait(sp, e->slot_of(facts.relabel_wait[lin]).ev_done[1 - lin]));
+    if (!facts.lin_any[lin]) return ROFT_OK;
     const int which = lin == 0 ? 1 : 3;
     switch (lp.release) {
     case Release::none: break;
@@ -295,7 +296,7 @@ static int enqueue_lane(Enqueue& q, int lin)
     OutlierLaunchOpts oo;
     oo.render_mode = e->cfg.render_mode;
     if (q.p.outlier_div > 1) oo.parts = -q.p.outlier_div;   // (-d: the automatic count / d)
-    const int n_seg = e->n_segments[lin];
+    const int n_seg = facts.n_segments[lin];
     for (int seg = 0; seg < n_seg; ++seg) {
         const bool last = seg == n_seg - 1;
         if (seg == 1 && lp.gate_second) TRY(q.wait_gate(sp));
@@ -340,39 +341,30 @@ static int enqueue_quality(Enqueue& q)
 static PlanInputs plan_inputs(roft_engine* e)
 {
     PlanInputs in;
+    static_cast<SubmitFacts&>(in) = e->pending.facts;
     in.knobs = e->knobs;
     in.multi = e->multi();
     in.timing = e->timing;
     in.timing_level = e->timing_level;
     in.wait_value_ok = e->wait_value_ok;
     in.have_skf_started = e->arr.skf_started.p != nullptr;
-    in.T = e->cur_T;
     in.n_obj = e->arr.a.n_obj;
     in.cus = device_cu_count();
     in.batch_counter = e->batch_counter; in.idle_mark = e->idle_mark; in.lead = e->lead; in.completed_batches = e->completed_batches;
-    in.had_uploads = e->had_uploads;
-    in.produced_flows = e->produced_flows;
-    in.new_mask_frames = e->plain_mask_frames;
-    in.label_sets = (int)e->label_sets.size();
-    in.any_feat = e->any_feat; in.any_feat_now = e->any_feat_now; in.feat_dep_in_batch = e->feat_dep_in_batch;
     in.outlier_bands_per_alternative = e->cfg.outlier_bands_per_alternative;
     in.conflict_free = e->streams && e->streams->conflicts == 0;
     in.up_stream_distinct = e->up_stream != e->stream;
     if (e->quality.enabled) (void)quality_frames_of_batch(e, &in.quality_frames);
     in.feat_used_two_back = e->batch_counter >= 2 && e->slot_of(e->batch_counter - 2).feat_used;
     in.vel_used_prev = e->batch_counter >= 1 && e->slot_of(e->batch_counter - 1).vel_used;
-    for (int l = 0; l < kNumLin; ++l) {
-        in.n_segments[l] = e->n_segments[l]; in.lin_any[l] = e->lin_any[l];
-        in.lane_objs[l] = e->lane_objs[l]; in.lane_old_first[l] = e->lane_old_first[l];
-        in.relabel_wait[l] = e->relabel_wait[l];
-        in.done_used_relabel[l] = e->relabel_wait[l] >= 0 && e->slot_of(e->relabel_wait[l]).done_used[1 - l];
-    }
+    for (int l = 0; l < kNumLin; ++l) in.done_used_relabel[l] = in.relabel_wait[l] >= 0 && e->slot_of(in.relabel_wait[l]).done_used[1 - l];
     return in;
 }
 
 int step_batch(roft_engine* e)
 {
-    const int T = e->cur_T;
+    const PendingBatch& pb = e->pending;
+    const int T = pb.facts.T;
     double hp_t = e->knobs.host_prof ? host_now_us() : 0.0;
     (void)hipGetLastError();   // a stale error of another library on this thread is not this step's
     const BatchPlan p = plan_batch(plan_inputs(e), [e] { return e->alone_on_device = alone_on_device(e->streams); });
@@ -415,12 +407,12 @@ int step_batch(roft_engine* e)
         tr = roft_batch_trace{};
         tr.batch = e->batch_counter;
         tr.frames = T;
-        tr.steady = p.steady; tr.throttled = e->throttled; tr.handoff = p.handoff;
+        tr.steady = p.steady; tr.throttled = pb.throttled; tr.handoff = p.handoff;
         tr.early_lanes = (p.early_lanes ? 4 : 0) | (p.lane[0].early ? 1 : 0) | (p.lane[1].early ? 2 : 0);
         tr.outlier_parts_halved = p.outlier_div > 1 ? 1 : 0;
         tr.launches = (int)(e->stats.launches - launches0);
         tr.event_ops = (int)(e->stats.event_ops - evops0);
-        tr.t_submit_us = e->cur_submit_t0; tr.submit_us = e->cur_submit_us; tr.wait_us = e->cur_wait_us;
+        tr.t_submit_us = pb.submit_t0; tr.submit_us = pb.submit_us; tr.wait_us = pb.wait_us;
     }
     HIP_TRY(hipGetLastError());
     return ROFT_OK;
@@ -456,11 +448,12 @@ int roft_step(roft_engine* e)
     }
     for (HostObject* ho : e->objs) { ho->stepped_slot = ho->s.cur_slot; ho->stepped_lane = ho->s.own[ho->s.cur_slot]; ho->stepped_flow = ho->s.flow_made; ho->stepped_depth = ho->s.depth_prev; }
     // (a failed step leaves the engine consistent as far as the host can tell: the batch counts as enqueued)
-    e->frame_counter += e->cur_T;
-    e->prev_T = e->cur_T;
+    const int T = e->pending.facts.T;
+    e->frame_counter += T;
+    e->prev_T = T;
     e->slot_of(e->batch_counter).end_frame = e->frame_counter;
     e->batch_counter++;
-    e->stats.frames += e->cur_T;
+    e->stats.frames += T;
     e->stats.batches++;
     e->submitted = false;
     return rc;

@@ -7,6 +7,13 @@
 
 // The UKF steps of one frame (ROFTFilter.cpp:327-367 over CartesianQuaternionMeasurement::freeze, cpp:92-348).
 // Returns false when the frame needs more than kMaxSteps steps.
+// the frame writes the next slot of the object's feature ring, if it does not write one yet: the buffered features are there from now on
+static void take_feat_slot(Sched& o, FrameCtrl& c)
+{
+    if (c.feat_write < 0) { c.feat_write = o.feat_next; o.feat_next = (o.feat_next + 1) % kFeatRing; }
+    o.feat_slot = c.feat_write;
+}
+
 bool build_pose_program(const roft_config& cfg, Sched& o, const roft_frame_input& in, FrameCtrl& c)
 {
     const int slot = o.frame_idx % kTwistRing;
@@ -47,6 +54,19 @@ bool build_pose_program(const roft_config& cfg, Sched& o, const roft_frame_input
     sd.src = cur;
     sd.do_predict = 1;
     sd.twist_slot = slot;
+    // the corrections of the step a pose arrives with: under outlier rejection both alternatives, with and without the pose (the test
+    // behind the step chooses), else the pose into the current belief
+    auto pose_corrections = [&](StepDesc& s) {
+        if (cfg.outlier_rejection) {
+            s.n_corr = 2;
+            s.type[0] = ROFT_MEAS_POSE_VELOCITY; s.dst[0] = b_alt(lin, 0);
+            s.type[1] = ROFT_MEAS_VELOCITY;      s.dst[1] = b_alt(lin, 1);
+            c.outlier_step = n;
+        } else {
+            s.n_corr = 1;
+            s.type[0] = ROFT_MEAS_POSE_VELOCITY; s.dst[0] = cur;
+        }
+    };
     if (type == ROFT_MEAS_POSE_VELOCITY) {
         if (cfg.use_pose_resync) {
             // ROFTFilter.cpp:331-354: continue from the belief buffered at the previous pose arrival and
@@ -66,15 +86,7 @@ bool build_pose_program(const roft_config& cfg, Sched& o, const roft_frame_input
                 r.src = cur;
                 if (pose_pending) {
                     pose_pending = false;
-                    if (cfg.outlier_rejection) {
-                        r.n_corr = 2;
-                        r.type[0] = ROFT_MEAS_POSE_VELOCITY; r.dst[0] = b_alt(lin, 0);
-                        r.type[1] = ROFT_MEAS_VELOCITY;      r.dst[1] = b_alt(lin, 1);
-                        c.outlier_step = n;
-                    } else {
-                        r.n_corr = 1;
-                        r.type[0] = ROFT_MEAS_POSE_VELOCITY; r.dst[0] = cur;
-                    }
+                    pose_corrections(r);
                 } else {
                     r.n_corr = 1;
                     r.type[0] = ROFT_MEAS_VELOCITY; r.dst[0] = cur;
@@ -84,21 +96,13 @@ bool build_pose_program(const roft_config& cfg, Sched& o, const roft_frame_input
             // the test reads the features buffered at the previous pose arrival; this frame's are buffered for
             // the next one (ROFTFilter.cpp:353)
             c.feat_read = o.feat_slot;
-            if (c.feat_write < 0) { c.feat_write = o.feat_next; o.feat_next = (o.feat_next + 1) % kFeatRing; }
-            o.feat_slot = c.feat_write;
+            take_feat_slot(o, c);
         } else {
+            pose_corrections(sd);
             if (cfg.outlier_rejection) {
-                sd.n_corr = 2;
-                sd.type[0] = ROFT_MEAS_POSE_VELOCITY; sd.dst[0] = b_alt(lin, 0);
-                sd.type[1] = ROFT_MEAS_VELOCITY;      sd.dst[1] = b_alt(lin, 1);
-                c.outlier_step = n;
                 // without re-sync the test uses the current frame's depth and mask
-                if (c.feat_write < 0) { c.feat_write = o.feat_next; o.feat_next = (o.feat_next + 1) % kFeatRing; }
+                take_feat_slot(o, c);
                 c.feat_read = c.feat_write;
-                o.feat_slot = c.feat_write;
-            } else {
-                sd.n_corr = 1;
-                sd.type[0] = ROFT_MEAS_POSE_VELOCITY; sd.dst[0] = cur;
             }
             add(sd);
         }
@@ -149,16 +153,17 @@ __global__ __launch_bounds__(256) void gather_copy_kernel(const GatherItem* __re
 // the items collected by stage_host during this submit -> one launch on the upload stream (before the submit waits for its uploads)
 static int flush_gather(roft_engine* e)
 {
-    if (e->gather.empty()) return ROFT_OK;
+    std::vector<GatherItem>& gather = e->pending.gather;
+    if (gather.empty()) return ROFT_OK;
     GatherItem*& tab = e->slot_of(e->batch_counter).gather_tab;
     if (!tab) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&tab), sizeof(GatherItem) * kGatherCap, hipHostMallocMapped));
-    const size_t n = e->gather.size();
-    std::memcpy(tab, e->gather.data(), sizeof(GatherItem) * n);
+    const size_t n = gather.size();
+    std::memcpy(tab, gather.data(), sizeof(GatherItem) * n);
     size_t largest = 0;
-    for (const GatherItem& g : e->gather) largest = std::max(largest, g.bytes);
+    for (const GatherItem& g : gather) largest = std::max(largest, g.bytes);
     const unsigned gx = (unsigned)std::max<size_t>(1, std::min<size_t>(32, (largest / 16 + 2047) / 2048));   // ~8 units per thread
     hipLaunchKernelGGL(gather_copy_kernel, dim3(gx, (unsigned)n), dim3(256), 0, e->up_stream, tab);
-    e->gather.clear();
+    gather.clear();
     if (hipError_t le = hipGetLastError()) return fail(ROFT_ERR_DEVICE, std::string("gather copy of HOST inputs: ") + hipGetErrorString(le));
     e->stats.h2d_copies++;
     return ROFT_OK;
@@ -175,6 +180,14 @@ static const void* pinned_device_pointer(const void* host)
     return dp;
 }
 
+// `bytes` of HOST inputs cross the bus for this submit, in `copies` copies of their own (0: fetched by the gather launch)
+static void count_upload(roft_engine* e, size_t bytes, int copies)
+{
+    e->stats.h2d_bytes += (long long)bytes;
+    e->stats.h2d_copies += copies;
+    e->pending.facts.had_uploads = true;
+}
+
 // device copy of one HOST image of `frame` (uploads once per distinct host pointer and frame)
 static int stage_host(roft_engine* e, int frame, const void* host, size_t bytes, const void** dev)
 {
@@ -184,19 +197,11 @@ static int stage_host(roft_engine* e, int frame, const void* host, size_t bytes,
     unsigned char* d = nullptr;
     if (int rc = stage_alloc(e, frame, bytes, &d)) return rc;
     const void* dp = nullptr;
-    if (e->knobs.gather_copy && bytes <= kGatherMaxBytes && (bytes & 15) == 0 && (reinterpret_cast<uintptr_t>(host) & 15) == 0 &&
-        (int)e->gather.size() < kGatherCap && (dp = pinned_device_pointer(host)) != nullptr) {
-        e->gather.push_back(GatherItem{dp, d, bytes});   // fetched by flush_gather's one launch
-        e->stats.h2d_bytes += (long long)bytes;
-        e->had_uploads = true;
-        sf.seen.emplace_back(host, d);
-        *dev = d;
-        return ROFT_OK;
-    }
-    HIP_TRY(hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, e->up_stream));
-    e->stats.h2d_bytes += (long long)bytes;
-    e->stats.h2d_copies++;
-    e->had_uploads = true;
+    const bool gathered = e->knobs.gather_copy && bytes <= kGatherMaxBytes && (bytes & 15) == 0 && (reinterpret_cast<uintptr_t>(host) & 15) == 0 &&
+                          (int)e->pending.gather.size() < kGatherCap && (dp = pinned_device_pointer(host)) != nullptr;
+    if (gathered) e->pending.gather.push_back(GatherItem{dp, d, bytes});   // fetched by flush_gather's one launch
+    else HIP_TRY(hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, e->up_stream));
+    count_upload(e, bytes, gathered ? 0 : 1);
     sf.seen.emplace_back(host, d);
     *dev = d;
     return ROFT_OK;
@@ -236,9 +241,7 @@ static int stage_host_runs(roft_engine* e, const roft_frame_input* inputs, int n
                         unsigned char* d = nullptr;
                         if (int rc = stage_alloc(e, frame0 + t1, (size_t)len * bytes, &d)) return rc;
                         HIP_TRY(hipMemcpyAsync(d, p0, (size_t)len * bytes, hipMemcpyHostToDevice, e->up_stream));
-                        e->stats.h2d_bytes += (long long)((size_t)len * bytes);
-                        e->stats.h2d_copies++;
-                        e->had_uploads = true;
+                        count_upload(e, (size_t)len * bytes, 1);
                         if (kind == 0 && e->depth.enabled) e->depth.stats.image_bytes += (long long)((size_t)len * bytes);   // (raw frames)
                         for (int t = t0; t <= t1; ++t)
                             e->staging[(frame0 + t) % e->retain].seen.emplace_back(p0 + (size_t)(t - t0) * bytes, d + (size_t)(t - t0) * bytes);
@@ -262,6 +265,7 @@ static size_t image_bytes(int type, size_t npix) { return type == ROFT_IMAGE_GRA
 static int enqueue_flow_production(roft_engine* e, int T)
 {
     EngineFlow& f = e->flow;
+    const std::vector<FlowFrameJobs>& jobs = e->pending.flow_jobs;
     const size_t fbytes = flow_bytes(e->arr.a.ffmt);
     const size_t field_floats = (size_t)2 * e->cfg.cam.width * e->cfg.cam.height;
     const bool s16 = e->cfg.flow_type == ROFT_FLOW_S16C2;
@@ -269,9 +273,9 @@ static int enqueue_flow_production(roft_engine* e, int T)
     OfImages im{};
     for (int t = 0; t < T; ++t) {
         const int gen = (e->frame_counter + t) % G;
-        for (size_t i = 0; i < f.jobs[t].images.size(); ++i) {
+        for (size_t i = 0; i < jobs[t].images.size(); ++i) {
             const int k = im.n++;
-            im.type[k] = f.jobs[t].images[i].type; im.src[k] = f.jobs[t].images[i].dev; im.pyr[k] = f.pyr[gen][i]->p;
+            im.type[k] = jobs[t].images[i].type; im.src[k] = jobs[t].images[i].dev; im.pyr[k] = f.pyr[gen][i]->p;
             if (im.n == kOfChunk) { launch_of_pyramids(f.geom, im, e->up_stream); im.n = 0; }
         }
     }
@@ -279,7 +283,7 @@ static int enqueue_flow_production(roft_engine* e, int T)
     OfPairs pr{};
     for (int t = 0; t < T; ++t) {
         const int gen = (e->frame_counter + t) % G, gen_prev = (e->frame_counter + t + G - 1) % G;
-        for (const FlowPairJob& pj : f.jobs[t].pairs) {
+        for (const FlowPairJob& pj : jobs[t].pairs) {
             const int k = pr.n++;
             pr.pyr0[k] = f.pyr[gen_prev][pj.pyr0]->p;
             pr.pyr1[k] = f.pyr[gen][pj.pyr1]->p;
@@ -292,7 +296,7 @@ static int enqueue_flow_production(roft_engine* e, int T)
     if (pr.n) launch_of_pairs(f.geom, pr, e->up_stream);
     if (hipError_t le = hipGetLastError()) return fail(ROFT_ERR_DEVICE, std::string("flow production: ") + hipGetErrorString(le));
     for (int t = 0; t < T; ++t)
-        for (const FlowCloneJob& c : f.jobs[t].clones) HIP_TRY(hipMemcpyAsync(c.dst, c.src, fbytes, hipMemcpyDeviceToDevice, e->up_stream));
+        for (const FlowCloneJob& c : jobs[t].clones) HIP_TRY(hipMemcpyAsync(c.dst, c.src, fbytes, hipMemcpyDeviceToDevice, e->up_stream));
     return ROFT_OK;
 }
 
@@ -310,7 +314,7 @@ static int enqueue_depth_production(roft_engine* e)
         else launch_depth_convert(jobs, npix, d.src.scale, e->up_stream);
         jobs.n = 0;
     };
-    for (const DepthJob& j : d.jobs) {
+    for (const DepthJob& j : e->pending.depth_jobs) {
         jobs.raw[jobs.n] = j.raw; jobs.out[jobs.n] = j.out;
         if (++jobs.n == kDepthChunk) launch();
     }
@@ -321,21 +325,312 @@ static int enqueue_depth_production(roft_engine* e)
     return ROFT_OK;
 }
 
+// ---- submit_frames: one object's frame of the batch at a time, through the stages below in their order --------------------------------
+
+struct ImageSizes {
+    size_t npix, flow;   // pixels of the camera; bytes of a flow frame
+    size_t depth;        // bytes of what inputs[].depth carries: H x W floats, or on a raw-depth engine the sensor's 16-bit frame of the depth source's size
+    explicit ImageSizes(const roft_engine* e)
+        : npix((size_t)e->cfg.cam.width * e->cfg.cam.height), flow(flow_bytes(e->arr.a.ffmt)),
+          depth(e->depth.enabled ? e->depth.raw_pixels * sizeof(uint16_t) : npix * sizeof(float)) {}
+};
+
+struct FrameJob {
+    int t, id, frame;              // frame of the batch, object, the engine's count of that frame
+    const roft_frame_input& in;
+    const roft_label_mask* lm;     // the mask as the pixels of a label image equal to a value (roft_frames_submit_labels), or null
+    const roft_frame_image* fim;   // a camera image instead of a flow frame (roft_frames_submit_images), or null
+    HostObject& ho;
+    FrameCtrl& c;
+};
+
+// the frame's inputs in device memory (depth: floats, or on a raw-depth engine the 16-bit frame until plan_depth_product; mask: bytes)
+struct DevInputs { const void *depth = nullptr, *flow = nullptr, *mask = nullptr, *labels = nullptr, *image = nullptr; };
+
+// device or managed memory, or host memory the GPU can address as it is (hipHostMalloc / hipHostRegister: pinned and mapped --
+// zero-copy over the bus); unregistered pageable memory is what is refused
+static bool device_can_read(const void* p)
+{
+    hipPointerAttribute_t attr{};
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged || pinned_device_pointer(p) == p;
+}
+
+static int check_frame_forms(const roft_engine* e, const FrameJob& j)
+{
+    auto obj = [&] { return "object " + std::to_string(j.id); };
+    if (!j.in.depth) return fail(ROFT_ERR_INVALID, "cannot continue without a continuous depth stream (ROFTFilter.cpp:261-266)");
+    if (const roft_label_mask* lm = j.lm) {
+        if (j.in.mask) return fail(ROFT_ERR_INVALID, obj() + ": a label image AND a mask for one frame (one of the two)");
+        if (lm->label_type != ROFT_LABEL_U8 && lm->label_type != ROFT_LABEL_U16)
+            return fail(ROFT_ERR_INVALID, obj() + ": label_type must be ROFT_LABEL_U8 or ROFT_LABEL_U16");
+        if (lm->label == 0) return fail(ROFT_ERR_INVALID, obj() + ": label 0 is the background");
+        if (lm->label < 0 || lm->label > (lm->label_type == ROFT_LABEL_U8 ? 255 : 65535))
+            return fail(ROFT_ERR_INVALID, obj() + ": label " + std::to_string(lm->label) + " is outside the range of the label type");
+    }
+    if (const roft_frame_image* fim = j.fim) {
+        if (!e->flow.enabled) return fail(ROFT_ERR_STATE, "camera images need roft_engine_enable_flow before the first frame");
+        if (j.in.flow) return fail(ROFT_ERR_INVALID, obj() + ": a camera image AND a flow for one frame (one of the two)");
+        if (fim->image_type != ROFT_IMAGE_GRAY8 && fim->image_type != ROFT_IMAGE_BGR8 && fim->image_type != ROFT_IMAGE_RGB8)
+            return fail(ROFT_ERR_INVALID, obj() + ": image_type must be ROFT_IMAGE_GRAY8, ROFT_IMAGE_BGR8 or ROFT_IMAGE_RGB8");
+    }
+    return ROFT_OK;
+}
+
+// The inputs to device memory: DEVICE pointers as they are (looked up on the engine's first call, and aligned), HOST images staged --
+// depth, flow, mask, labels, image: the order decides their places in the frame's staging slot.
+static int resolve_inputs(roft_engine* e, const FrameJob& j, const ImageSizes& sz, DevInputs& d)
+{
+    const roft_frame_input& in = j.in;
+    if (in.mem_kind == ROFT_MEM_DEVICE) {
+        d.depth = in.depth;
+        d.flow = in.flow;
+        d.mask = in.mask;
+        if (j.lm) d.labels = j.lm->labels;
+        if (j.fim) d.image = j.fim->image;
+        // the first call of an engine only: a host pointer declared as device memory is a GPU page fault that takes
+        // the process down at the first kernel -- the commonest mistake of a new binding is refused here instead
+        if (!e->device_pointers_checked) {
+            const void* ptrs[5] = {d.depth, d.flow, d.mask, d.labels, d.image};
+            static const char* const what[5] = {"depth", "flow", "mask", "label image", "camera image"};
+            for (int q = 0; q < 5; ++q) {
+                if (ptrs[q] && !device_can_read(ptrs[q]))
+                    return fail(ROFT_ERR_INVALID, std::string("mem_kind is ROFT_MEM_DEVICE but the ") + what[q] + " pointer of object " +
+                                                      std::to_string(j.id) + " is neither device memory nor pinned, mapped host memory "
+                                                      "(pass ROFT_MEM_HOST for ordinary host buffers)");
+            }
+        }
+        if ((reinterpret_cast<uintptr_t>(d.mask) & 15) || (reinterpret_cast<uintptr_t>(d.flow) & 7) || (reinterpret_cast<uintptr_t>(d.depth) & 3))
+            return fail(ROFT_ERR_INVALID, "device buffers must be aligned: mask 16 B, flow 8 B, depth 4 B");
+        if (reinterpret_cast<uintptr_t>(d.labels) & 15) return fail(ROFT_ERR_INVALID, "device buffers must be aligned: label image 16 B");
+        if (reinterpret_cast<uintptr_t>(d.image) & 3) return fail(ROFT_ERR_INVALID, "device buffers must be aligned: camera image 4 B");
+        return ROFT_OK;
+    }
+    if (in.mem_kind != ROFT_MEM_HOST) return fail(ROFT_ERR_INVALID, "mem_kind must be ROFT_MEM_HOST or ROFT_MEM_DEVICE");
+    const long long before_depth = e->stats.h2d_bytes;
+    TRY(stage_host(e, j.frame, in.depth, sz.depth, &d.depth));
+    if (e->depth.enabled) e->depth.stats.image_bytes += e->stats.h2d_bytes - before_depth;   // (uploaded, and counted, once per distinct pointer)
+    if (in.flow) TRY(stage_host(e, j.frame, in.flow, sz.flow, &d.flow));
+    if (in.mask) TRY(stage_host(e, j.frame, in.mask, sz.npix, &d.mask));
+    if (j.lm) TRY(stage_host(e, j.frame, j.lm->labels, sz.npix * (j.lm->label_type == ROFT_LABEL_U8 ? 1 : 2), &d.labels));
+    if (j.fim) {
+        const long long before = e->stats.h2d_bytes;   // (the objects of a shared scene name one image: uploaded, and counted, once)
+        TRY(stage_host(e, j.frame, j.fim->image, image_bytes(j.fim->image_type, sz.npix), &d.image));
+        e->flow.stats.image_bytes += e->stats.h2d_bytes - before;
+    }
+    return ROFT_OK;
+}
+
+// Raw depth: d.depth is the device address of the 16-bit frame so far.  Its float product goes where a staged HOST depth of the frame
+// would have been copied, one per distinct raw image and frame however many objects name it.
+static int plan_depth_product(roft_engine* e, const FrameJob& j, const ImageSizes& sz, DevInputs& d)
+{
+    std::vector<DepthJob>& jobs = e->pending.depth_jobs;
+    const uint16_t* d_raw = static_cast<const uint16_t*>(d.depth);
+    float* made = nullptr;
+    for (size_t i = jobs.size(); i-- > 0 && jobs[i].t == j.t;)
+        if (jobs[i].raw == d_raw) { made = jobs[i].out; break; }
+    if (!made) {
+        unsigned char* out = nullptr;
+        TRY(stage_alloc(e, j.frame, sz.npix * sizeof(float), &out));
+        made = reinterpret_cast<float*>(out);
+        jobs.push_back(DepthJob{j.t, d_raw, made});
+        e->depth.stats.images++;
+        e->depth.stats.products++;
+        e->pending.facts.produced_flows = true;   // (production behind the copies: ev_up is recorded behind it)
+    }
+    d.depth = made;
+    return ROFT_OK;
+}
+
+// The flow of a camera image: produced where a staged HOST flow of the frame would have been copied, one pyramid per distinct image
+// and one flow per distinct (previous, current) pair of the frame; none without an image the frame before.
+static int plan_flow_product(roft_engine* e, const FrameJob& j, const ImageSizes& sz, DevInputs& d)
+{
+    Sched& o = j.ho.s;
+    int pyr_cur = -1;
+    if (j.fim) {
+        EngineFlow& f = e->flow;
+        FlowFrameJobs& fj = e->pending.flow_jobs[j.t];
+        for (size_t i = 0; i < fj.images.size() && pyr_cur < 0; ++i)
+            if (fj.images[i].dev == d.image && fj.images[i].type == j.fim->image_type) pyr_cur = (int)i;
+        if (pyr_cur < 0) {
+            pyr_cur = (int)fj.images.size();
+            fj.images.push_back(FlowImageJob{d.image, j.fim->image_type});
+            std::vector<DevBuf<float>*>& gen = f.pyr[(size_t)j.frame % f.pyr.size()];
+            if ((int)gen.size() <= pyr_cur) {
+                auto* pb = new DevBuf<float>();
+                gen.push_back(pb);
+                HIP_TRY(pb->ensure(f.geom.pyr_stride));
+            }
+            f.stats.images++;
+            f.stats.pyramids++;
+            e->pending.facts.produced_flows = true;   // (a pyramid to build, also where no pair follows in this batch)
+        }
+        if (o.pyr_prev >= 0) {
+            for (const FlowPairJob& pj : fj.pairs)
+                if (pj.pyr0 == o.pyr_prev && pj.pyr1 == pyr_cur) { d.flow = pj.out; break; }
+            if (!d.flow) {
+                unsigned char* out = nullptr;
+                TRY(stage_alloc(e, j.frame, sz.flow, &out));
+                fj.pairs.push_back(FlowPairJob{o.pyr_prev, pyr_cur, out});
+                f.stats.pairs++;
+                d.flow = out;
+                e->pending.facts.produced_flows = true;
+            }
+        }
+    }
+    o.pyr_prev = pyr_cur;
+    o.flow_made = j.fim ? d.flow : nullptr;
+    return ROFT_OK;
+}
+
+// ImageSegmentationOFAidedSource::step_frame (hpp:127-231), schedule part: the delivered mask (its label set), the history of valid
+// flows with the clones of those that aged out, the stamped window.
+static int schedule_mask_source(roft_engine* e, const FrameJob& j, const ImageSizes& sz, const DevInputs& d)
+{
+    PendingBatch& pb = e->pending;
+    HostObject& ho = j.ho;
+    Sched& o = ho.s;
+    FrameCtrl& c = j.c;
+    c.slot_prev = (o.frame_idx + kPlaneSlots - 1) % kPlaneSlots;
+    c.slot_cur = o.frame_idx % kPlaneSlots;
+    const bool has_mask = d.mask || d.labels;
+    c.has_new_mask = has_mask ? 1 : 0;
+    c.new_mask = static_cast<const uint8_t*>(d.mask);
+    if (has_mask) pb.new_mask_frames |= 1u << j.t;
+    if (d.mask) pb.facts.plain_mask_frames |= 1u << j.t;
+    if (d.labels) {
+        c.label = j.lm->label;
+        c.label_type = j.lm->label_type;
+        // the set of this frame's objects that name this image (few distinct images per frame: a linear search)
+        int si = -1;
+        for (size_t i = pb.label_sets.size(); i-- > 0 && pb.label_sets[i].t == j.t;)
+            if (pb.label_sets[i].img == d.labels && pb.label_sets[i].type == j.lm->label_type) { si = (int)i; break; }
+        if (si < 0) {
+            LabelSet ls{};
+            ls.img = d.labels; ls.type = j.lm->label_type; ls.t = j.t;
+            pb.label_sets.push_back(ls);
+            pb.label_members.emplace_back();
+            si = pb.facts.label_sets++;
+        }
+        pb.label_members[si].push_back(LabelMember{j.id, j.lm->label});
+    }
+    if (has_mask && !o.seg_available) { o.seg_available = true; c.first_mask = 1; }
+    if (!o.seg_available)
+        return fail(ROFT_ERR_STATE, "no segmentation mask delivered yet: the first frame must carry one");
+    const bool valid_flow = d.flow && !o.of_first_frame;
+    o.of_first_frame = false;
+    if (valid_flow) {
+        const int keep = std::min(o.n_hist, e->hist_cap - 1);
+        std::memmove(o.hist + 1, o.hist, sizeof(FlowEntry) * (size_t)keep);
+        o.hist[0] = FlowEntry{d.flow, o.frame_idx, -1};
+        o.n_hist = keep + 1;
+        o.flows_since_mask++;
+    }
+    // Flows that later flows did not push out of the history in time (dropped flow frames): the caller may
+    // recycle the buffer once the retention window closes, the reference keeps a clone -- so does the engine.
+    for (int k0 = 0; k0 < o.n_hist; ++k0) {
+        FlowEntry& fe = o.hist[k0];
+        if (fe.owned >= 0 || o.frame_idx - fe.frame < e->hist_cap) continue;
+        int k = -1;
+        for (size_t q = 0; q < ho.owned.size(); ++q) {
+            bool referenced = ho.owned[q]->last_ref_frame >= e->completed_frames;
+            for (int j2 = 0; j2 < o.n_hist && !referenced; ++j2) referenced = o.hist[j2].owned == (int)q;
+            if (!referenced) { k = (int)q; break; }
+        }
+        if (k < 0) { ho.owned.push_back(new OwnedFlow()); k = (int)ho.owned.size() - 1; }
+        HIP_TRY(ho.owned[k]->buf.ensure(sz.flow));
+        if (e->flow.enabled) {
+            // (the flow may be one this very submit produces: the copy goes behind that production, in stream order)
+            pb.flow_jobs[j.t].clones.push_back(FlowCloneJob{ho.owned[k]->buf.p, fe.ptr});
+            pb.facts.produced_flows = true;
+        } else {
+            HIP_TRY(hipMemcpyAsync(ho.owned[k]->buf.p, fe.ptr, sz.flow, hipMemcpyDeviceToDevice, e->up_stream));
+            pb.facts.had_uploads = true;
+        }
+        fe.ptr = ho.owned[k]->buf.p;
+        fe.owned = k;
+    }
+    c.flow_valid = valid_flow ? 1 : 0;
+    if (e->cfg.stamped_masks) {
+        // OpticalFlowQueueHandler: window of 30 stamped flows; get_buffer_region(mask stamp) = the flows stored
+        // after the first entry within 1 ms of it (OpticalFlowQueueHandler.cpp:18-58)
+        c.stamped = 1;
+        if (valid_flow) {
+            if (o.n_stamps == 30) std::memmove(o.stamps, o.stamps + 1, sizeof(double) * (size_t)(--o.n_stamps));
+            o.stamps[o.n_stamps++] = j.in.stamp;
+        }
+        if (has_mask)
+            for (int i = 0; i < o.n_stamps; ++i)
+                if (std::fabs(o.stamps[i] - j.in.mask_stamp) < 1e-3) { c.n_region = o.n_stamps - (i + 1); break; }
+    } else if (has_mask && !c.first_mask) {
+        // a delivered mask consumes (or, when empty and the number of frames between masks is unknown, drops)
+        // the buffered flows; with that number unknown ALL of them are chased (hpp:239-245)
+        if (e->cfg.mask_frames_between <= 0 && o.flows_since_mask > kMaxFlowHist)
+            return fail(ROFT_ERR_CAPACITY, "more than ROFT_MAX_FLOW_CHASE flows buffered since the last mask");
+        o.flows_since_mask = valid_flow ? 1 : 0;   // upper bound: 0 after a consumed mask, 1 after an empty one
+    }
+    c.n_hist = o.n_hist;
+    for (int k = 0; k < o.n_hist; ++k) {
+        c.flow[k] = o.hist[k].ptr;
+        if (o.hist[k].owned >= 0) ho.owned[o.hist[k].owned]->last_ref_frame = j.frame;
+    }
+    return ROFT_OK;
+}
+
+// ImageOpticalFlowMeasurement::freeze state machine (hpp:217-229)
+static void schedule_flow_measurement(const FrameJob& j, const DevInputs& d)
+{
+    Sched& o = j.ho.s;
+    const bool data_in = d.flow && !o.flow_first_frame;   // (segmentation is available at this point)
+    o.flow_first_frame = false;
+    j.c.vel_stage = data_in ? 1 : 0;
+    j.c.depth_prev = o.depth_prev;
+    // (data_in implies valid_flow, so c.flow[0] is this frame's flow whenever the velocity stage runs)
+    j.c.depth_cur = o.depth_prev = static_cast<const float*>(d.depth);
+}
+
+// What the frame's pose program means for the batch: its lane, the lane's segments, the feature slots it reads and writes.
+static int account_lanes_and_features(roft_engine* e, const FrameJob& j)
+{
+    PendingBatch& pb = e->pending;
+    SubmitFacts& facts = pb.facts;
+    Sched& o = j.ho.s;
+    const FrameCtrl& c = j.c;
+    const int b = e->batch_counter;
+    const size_t on_lane = (size_t)j.id * kNumLin + c.lane;
+    facts.lin_any[c.lane] = true;
+    if (pb.lane_tests[on_lane] < 0) {
+        // the object's first frame on this lane in the batch: is its first step's twist older than the batch?
+        pb.lane_tests[on_lane] = 0;
+        facts.lane_objs[c.lane]++;
+        const int age = (c.n_steps > 0 && c.steps[0].op) ? ((o.frame_idx - c.steps[0].twist_slot) & (kTwistRing - 1)) : 0;
+        if (age > j.t && c.outlier_step == 0) facts.lane_old_first[c.lane]++;   // (a replay whose first step is the one the outlier test follows)
+    }
+    o.last_touch[o.cur_slot] = b;
+    if (c.outlier_step >= 0) facts.n_segments[c.lane] = std::max(facts.n_segments[c.lane], 1 + ++pb.lane_tests[on_lane]);
+    if (c.outlier_step >= 0 && c.feat_read >= 0 && c.feat_read != c.feat_write && o.feat_batch[c.feat_read] == b) facts.feat_dep_in_batch = true;
+    if (c.feat_write >= 0) {
+        o.feat_batch[c.feat_write] = b;
+        facts.any_feat = true;
+        pb.feat_frames |= 1u << j.t;
+        // a feature set is re-used only when the batch that read or wrote it last has ended
+        const int last = o.feat_use[c.feat_write];
+        if (last >= 0 && last < b) TRY(wait_batch(e, last));
+        o.feat_use[c.feat_write] = b;
+    }
+    if (c.feat_read >= 0 && c.outlier_step >= 0) o.feat_use[c.feat_read] = b;
+    if (c.outlier_step >= 0 && c.feat_read == c.feat_write) facts.any_feat_now = true;
+    return ROFT_OK;
+}
+
 static int submit_frames(roft_engine* e, const roft_frame_input* inputs, const roft_label_mask* labels, const roft_frame_image* images, int n_obj, int T)
 {
     const roft_config& cfg = e->cfg;
-    const size_t npix = (size_t)cfg.cam.width * cfg.cam.height;
-    const size_t fbytes = flow_bytes(e->arr.a.ffmt);
-    // what inputs[].depth carries: H x W floats, or on a raw-depth engine the sensor's 16-bit frame of the depth source's size
-    const bool raw_depth = e->depth.enabled;
-    const size_t depth_bytes = raw_depth ? e->depth.raw_pixels * sizeof(uint16_t) : npix * sizeof(float);
-    const int b = e->batch_counter;
-    FrameCtrl* blk = e->slot_of(b).stage;
-    int max_outliers[kNumLin] = {0, 0};
-    std::vector<int> n_outliers((size_t)n_obj * kNumLin, 0);
-    e->lin_any[0] = e->lin_any[1] = false;
-    e->lane_objs[0] = e->lane_objs[1] = e->lane_old_first[0] = e->lane_old_first[1] = 0;
-    std::vector<unsigned char> lane_seen((size_t)n_obj * kNumLin, 0);
+    const ImageSizes sz(e);
+    PendingBatch& pb = e->pending;
+    FrameCtrl* blk = e->slot_of(e->batch_counter).stage;
     {
         // Balance of the two pose chain lanes.  A lane's launch lasts as long as its busiest object, so the lanes only
         // overlap if, in every batch, the re-sync replays of all objects are on ONE lane and the ordinary steps in
@@ -346,322 +641,63 @@ static int submit_frames(roft_engine* e, const roft_frame_input* inputs, const r
         int cnt[kNumLin] = {0, 0};
         for (int id = 0; id < n_obj; ++id) cnt[e->objs[id]->s.own[e->objs[id]->s.cur_slot]]++;
         const int c = cnt[1] > cnt[0] ? 1 : 0;
-        e->relabel_wait[0] = e->relabel_wait[1] = -1;
+        int* relabel_wait = pb.facts.relabel_wait;
         for (int id = 0; id < n_obj; ++id) {
             Sched& o = e->objs[id]->s;
             if (o.own[o.cur_slot] == c) continue;
-            e->relabel_wait[c] = std::max(e->relabel_wait[c], o.last_touch[o.cur_slot]);
-            e->relabel_wait[1 - c] = std::max(e->relabel_wait[1 - c], o.last_touch[1 - o.cur_slot]);
+            relabel_wait[c] = std::max(relabel_wait[c], o.last_touch[o.cur_slot]);
+            relabel_wait[1 - c] = std::max(relabel_wait[1 - c], o.last_touch[1 - o.cur_slot]);
             std::swap(o.own[0], o.own[1]);
         }
     }
 
     for (int t = 0; t < T; ++t) {   // the staging slots of the batch's frames are free again: every frame that could read them has ended (in-flight bound)
         StageFrame& sf = e->staging[(e->frame_counter + t) % e->retain];
-        sf.cur = 0;
-        sf.used = 0;
+        sf.cur = sf.used = 0;
         sf.seen.clear();
     }
-    if (int rc = stage_host_runs(e, inputs, n_obj, T, depth_bytes, fbytes)) return rc;
+    TRY(stage_host_runs(e, inputs, n_obj, T, sz.depth, sz.flow));
     for (int t = 0; t < T; ++t) {
-        const int frame = e->frame_counter + t;
         for (int id = 0; id < n_obj; ++id) {
-            HostObject& ho = *e->objs[id];
-            Sched& o = ho.s;
-            const roft_frame_input& in = inputs[(size_t)t * n_obj + id];
-            FrameCtrl& c = blk[(size_t)t * n_obj + id];
-            clear_ctrl(c);
-            if (!in.depth) return fail(ROFT_ERR_INVALID, "cannot continue without a continuous depth stream (ROFTFilter.cpp:261-266)");
-            c.dt = (in.dt > 0.0) ? in.dt : cfg.sample_time;
-
-            // ---- inputs to device memory
-            const float* d_depth;
-            const void* d_flow = nullptr;
-            const uint8_t* d_mask = nullptr;
-            // the mask as the pixels of a label image equal to a value (roft_frames_submit_labels)
-            const roft_label_mask* lm = (labels && labels[(size_t)t * n_obj + id].labels) ? &labels[(size_t)t * n_obj + id] : nullptr;
-            const void* d_labels = nullptr;
-            if (lm) {
-                if (in.mask) return fail(ROFT_ERR_INVALID, "object " + std::to_string(id) + ": a label image AND a mask for one frame (one of the two)");
-                if (lm->label_type != ROFT_LABEL_U8 && lm->label_type != ROFT_LABEL_U16)
-                    return fail(ROFT_ERR_INVALID, "object " + std::to_string(id) + ": label_type must be ROFT_LABEL_U8 or ROFT_LABEL_U16");
-                if (lm->label == 0) return fail(ROFT_ERR_INVALID, "object " + std::to_string(id) + ": label 0 is the background");
-                if (lm->label < 0 || lm->label > (lm->label_type == ROFT_LABEL_U8 ? 255 : 65535))
-                    return fail(ROFT_ERR_INVALID, "object " + std::to_string(id) + ": label " + std::to_string(lm->label) + " is outside the range of the label type");
-            }
-            // a camera image instead of a flow frame (roft_frames_submit_images)
-            const roft_frame_image* fim = (images && images[(size_t)t * n_obj + id].image) ? &images[(size_t)t * n_obj + id] : nullptr;
-            const void* d_image = nullptr;
-            if (fim) {
-                if (!e->flow.enabled) return fail(ROFT_ERR_STATE, "camera images need roft_engine_enable_flow before the first frame");
-                if (in.flow) return fail(ROFT_ERR_INVALID, "object " + std::to_string(id) + ": a camera image AND a flow for one frame (one of the two)");
-                if (fim->image_type != ROFT_IMAGE_GRAY8 && fim->image_type != ROFT_IMAGE_BGR8 && fim->image_type != ROFT_IMAGE_RGB8)
-                    return fail(ROFT_ERR_INVALID, "object " + std::to_string(id) + ": image_type must be ROFT_IMAGE_GRAY8, ROFT_IMAGE_BGR8 or ROFT_IMAGE_RGB8");
-            }
-            if (in.mem_kind == ROFT_MEM_DEVICE) {
-                d_depth = in.depth;
-                if (fim) d_image = fim->image;
-                d_flow = in.flow;
-                d_mask = in.mask;
-                if (lm) d_labels = lm->labels;
-                // the first call of an engine only: a host pointer declared as device memory is a GPU page fault that takes
-                // the process down at the first kernel -- the commonest mistake of a new binding is refused here instead
-                if (!e->device_pointers_checked) {
-                    const void* ptrs[5] = {in.depth, in.flow, in.mask, d_labels, d_image};
-                    static const char* const what[5] = {"depth", "flow", "mask", "label image", "camera image"};
-                    for (int q = 0; q < 5; ++q) {
-                        if (!ptrs[q]) continue;
-                        // device or managed memory, or host memory the GPU can address as it is (hipHostMalloc / hipHostRegister:
-                        // pinned and mapped -- zero-copy over the bus); unregistered pageable memory is what is refused
-                        hipPointerAttribute_t attr{};
-                        const hipError_t pe = hipPointerGetAttributes(&attr, ptrs[q]);
-                        if (pe != hipSuccess) (void)hipGetLastError();
-                        bool usable = pe == hipSuccess && (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged);
-                        if (!usable && pe == hipSuccess && attr.type == hipMemoryTypeHost) {
-                            void* dp = nullptr;
-                            usable = hipHostGetDevicePointer(&dp, const_cast<void*>(ptrs[q]), 0) == hipSuccess && dp == ptrs[q];
-                            if (!usable) (void)hipGetLastError();
-                        }
-                        if (!usable)
-                            return fail(ROFT_ERR_INVALID, std::string("mem_kind is ROFT_MEM_DEVICE but the ") + what[q] + " pointer of object " +
-                                                              std::to_string(id) + " is neither device memory nor pinned, mapped host memory "
-                                                              "(pass ROFT_MEM_HOST for ordinary host buffers)");
-                    }
-                }
-                if ((reinterpret_cast<uintptr_t>(d_mask) & 15) || (reinterpret_cast<uintptr_t>(d_flow) & 7) ||
-                    (reinterpret_cast<uintptr_t>(d_depth) & 3))
-                    return fail(ROFT_ERR_INVALID, "device buffers must be aligned: mask 16 B, flow 8 B, depth 4 B");
-                if (reinterpret_cast<uintptr_t>(d_labels) & 15) return fail(ROFT_ERR_INVALID, "device buffers must be aligned: label image 16 B");
-                if (reinterpret_cast<uintptr_t>(d_image) & 3) return fail(ROFT_ERR_INVALID, "device buffers must be aligned: camera image 4 B");
-            } else if (in.mem_kind == ROFT_MEM_HOST) {
-                const void* p = nullptr;
-                const long long before_depth = e->stats.h2d_bytes;
-                if (int rc = stage_host(e, frame, in.depth, depth_bytes, &p)) return rc;
-                if (raw_depth) e->depth.stats.image_bytes += e->stats.h2d_bytes - before_depth;   // (uploaded, and counted, once per distinct pointer)
-                d_depth = static_cast<const float*>(p);
-                if (in.flow) { if (int rc = stage_host(e, frame, in.flow, fbytes, &d_flow)) return rc; }
-                if (in.mask) {
-                    if (int rc = stage_host(e, frame, in.mask, npix, &p)) return rc;
-                    d_mask = static_cast<const uint8_t*>(p);
-                }
-                if (lm) { if (int rc = stage_host(e, frame, lm->labels, npix * (lm->label_type == ROFT_LABEL_U8 ? 1 : 2), &d_labels)) return rc; }
-                if (fim) {
-                    const long long before = e->stats.h2d_bytes;   // (the objects of a shared scene name one image: uploaded, and counted, once)
-                    if (int rc = stage_host(e, frame, fim->image, image_bytes(fim->image_type, npix), &d_image)) return rc;
-                    e->flow.stats.image_bytes += e->stats.h2d_bytes - before;
-                }
-            } else {
-                return fail(ROFT_ERR_INVALID, "mem_kind must be ROFT_MEM_HOST or ROFT_MEM_DEVICE");
-            }
-
-            // ---- raw depth: d_depth is the device address of the 16-bit frame so far.  Its float product goes where a staged HOST depth
-            // of the frame would have been copied, one per distinct raw image and frame however many objects name it.
-            if (raw_depth) {
-                const uint16_t* d_raw = reinterpret_cast<const uint16_t*>(d_depth);
-                float* made = nullptr;
-                for (size_t i = e->depth.jobs.size(); i-- > 0 && e->depth.jobs[i].t == t;)
-                    if (e->depth.jobs[i].raw == d_raw) { made = e->depth.jobs[i].out; break; }
-                if (!made) {
-                    unsigned char* out = nullptr;
-                    if (int rc = stage_alloc(e, frame, npix * sizeof(float), &out)) return rc;
-                    made = reinterpret_cast<float*>(out);
-                    e->depth.jobs.push_back(DepthJob{t, d_raw, made});
-                    e->depth.stats.images++;
-                    e->depth.stats.products++;
-                    e->produced_flows = true;   // (production behind the copies: ev_up is recorded behind it)
-                }
-                d_depth = made;
-            }
-
-            // ---- the flow of a camera image: produced where a staged HOST flow of the frame would have been copied, one pyramid per
-            // distinct image and one flow per distinct (previous, current) pair of the frame; none without an image the frame before
-            int pyr_cur = -1;
-            if (fim) {
-                EngineFlow& f = e->flow;
-                FlowFrameJobs& fj = f.jobs[t];
-                for (size_t i = 0; i < fj.images.size() && pyr_cur < 0; ++i)
-                    if (fj.images[i].dev == d_image && fj.images[i].type == fim->image_type) pyr_cur = (int)i;
-                if (pyr_cur < 0) {
-                    pyr_cur = (int)fj.images.size();
-                    fj.images.push_back(FlowImageJob{d_image, fim->image_type});
-                    std::vector<DevBuf<float>*>& gen = f.pyr[(size_t)frame % f.pyr.size()];
-                    if ((int)gen.size() <= pyr_cur) {
-                        auto* pb = new DevBuf<float>();
-                        gen.push_back(pb);
-                        HIP_TRY(pb->ensure(f.geom.pyr_stride));
-                    }
-                    f.stats.images++;
-                    f.stats.pyramids++;
-                    e->produced_flows = true;   // (a pyramid to build, also where no pair follows in this batch)
-                }
-                if (o.pyr_prev >= 0) {
-                    for (const FlowPairJob& pj : fj.pairs)
-                        if (pj.pyr0 == o.pyr_prev && pj.pyr1 == pyr_cur) { d_flow = pj.out; break; }
-                    if (!d_flow) {
-                        unsigned char* out = nullptr;
-                        if (int rc = stage_alloc(e, frame, fbytes, &out)) return rc;
-                        fj.pairs.push_back(FlowPairJob{o.pyr_prev, pyr_cur, out});
-                        f.stats.pairs++;
-                        d_flow = out;
-                        e->produced_flows = true;
-                    }
-                }
-            }
-            o.pyr_prev = pyr_cur;
-            o.flow_made = fim ? d_flow : nullptr;
-
-            // ---- ImageSegmentationOFAidedSource::step_frame (hpp:127-231), schedule part
-            c.slot_prev = (o.frame_idx + kPlaneSlots - 1) % kPlaneSlots;
-            c.slot_cur = o.frame_idx % kPlaneSlots;
-            const bool has_mask = d_mask || d_labels;
-            c.has_new_mask = has_mask ? 1 : 0;
-            c.new_mask = d_mask;
-            if (has_mask) e->new_mask_frames |= 1u << t;
-            if (d_mask) e->plain_mask_frames |= 1u << t;
-            if (d_labels) {
-                c.label = lm->label;
-                c.label_type = lm->label_type;
-                // the set of this frame's objects that name this image (few distinct images per frame: a linear search)
-                int si = -1;
-                for (size_t i = e->label_sets.size(); i-- > 0 && e->label_sets[i].t == t;)
-                    if (e->label_sets[i].img == d_labels && e->label_sets[i].type == lm->label_type) { si = (int)i; break; }
-                if (si < 0) {
-                    LabelSet ls{};
-                    ls.img = d_labels; ls.type = lm->label_type; ls.t = t;
-                    e->label_sets.push_back(ls);
-                    e->label_members.emplace_back();
-                    si = (int)e->label_sets.size() - 1;
-                }
-                e->label_members[si].push_back(LabelMember{id, lm->label});
-            }
-            c.first_mask = 0;
-            if (has_mask && !o.seg_available) { o.seg_available = true; c.first_mask = 1; }
-            if (!o.seg_available)
-                return fail(ROFT_ERR_STATE, "no segmentation mask delivered yet: the first frame must carry one");
-            const bool valid_flow = d_flow && !o.of_first_frame;
-            o.of_first_frame = false;
-            if (valid_flow) {
-                const int keep = std::min(o.n_hist, e->hist_cap - 1);
-                std::memmove(o.hist + 1, o.hist, sizeof(FlowEntry) * (size_t)keep);
-                o.hist[0] = FlowEntry{d_flow, o.frame_idx, -1};
-                o.n_hist = keep + 1;
-                o.flows_since_mask++;
-            }
-            // Flows that later flows did not push out of the history in time (dropped flow frames): the caller may
-            // recycle the buffer once the retention window closes, the reference keeps a clone -- so does the engine.
-            for (int j = 0; j < o.n_hist; ++j) {
-                FlowEntry& fe = o.hist[j];
-                if (fe.owned >= 0 || o.frame_idx - fe.frame < e->hist_cap) continue;
-                int k = -1;
-                for (size_t q = 0; q < ho.owned.size(); ++q) {
-                    bool referenced = ho.owned[q]->last_ref_frame >= e->completed_frames;
-                    for (int j2 = 0; j2 < o.n_hist && !referenced; ++j2) referenced = o.hist[j2].owned == (int)q;
-                    if (!referenced) { k = (int)q; break; }
-                }
-                if (k < 0) { ho.owned.push_back(new OwnedFlow()); k = (int)ho.owned.size() - 1; }
-                HIP_TRY(ho.owned[k]->buf.ensure(fbytes));
-                if (e->flow.enabled) {
-                    // (the flow may be one this very submit produces: the copy goes behind that production, in stream order)
-                    e->flow.jobs[t].clones.push_back(FlowCloneJob{ho.owned[k]->buf.p, fe.ptr});
-                    e->produced_flows = true;
-                } else {
-                    HIP_TRY(hipMemcpyAsync(ho.owned[k]->buf.p, fe.ptr, fbytes, hipMemcpyDeviceToDevice, e->up_stream));
-                    e->had_uploads = true;
-                }
-                fe.ptr = ho.owned[k]->buf.p;
-                fe.owned = k;
-            }
-            c.flow_valid = valid_flow ? 1 : 0;
-            if (cfg.stamped_masks) {
-                // OpticalFlowQueueHandler: window of 30 stamped flows; get_buffer_region(mask stamp) = the flows stored
-                // after the first entry within 1 ms of it (OpticalFlowQueueHandler.cpp:18-58)
-                c.stamped = 1;
-                if (valid_flow) {
-                    if (o.n_stamps == 30) std::memmove(o.stamps, o.stamps + 1, sizeof(double) * (size_t)(--o.n_stamps));
-                    o.stamps[o.n_stamps++] = in.stamp;
-                }
-                c.n_region = 0;
-                if (has_mask)
-                    for (int i = 0; i < o.n_stamps; ++i)
-                        if (std::fabs(o.stamps[i] - in.mask_stamp) < 1e-3) { c.n_region = o.n_stamps - (i + 1); break; }
-            } else if (has_mask && !c.first_mask) {
-                // a delivered mask consumes (or, when empty and the number of frames between masks is unknown, drops)
-                // the buffered flows; with that number unknown ALL of them are chased (hpp:239-245)
-                if (cfg.mask_frames_between <= 0 && o.flows_since_mask > kMaxFlowHist)
-                    return fail(ROFT_ERR_CAPACITY, "more than ROFT_MAX_FLOW_CHASE flows buffered since the last mask");
-                o.flows_since_mask = valid_flow ? 1 : 0;   // upper bound: 0 after a consumed mask, 1 after an empty one
-            }
-            c.n_hist = o.n_hist;
-            for (int j = 0; j < o.n_hist; ++j) {
-                c.flow[j] = o.hist[j].ptr;
-                if (o.hist[j].owned >= 0) ho.owned[o.hist[j].owned]->last_ref_frame = frame;
-            }
-
-            // ---- ImageOpticalFlowMeasurement::freeze state machine (hpp:217-229)
-            bool data_in = true;  // segmentation is available at this point
-            if (!d_flow || o.flow_first_frame) {
-                o.flow_first_frame = false;
-                data_in = false;
-            }
-            c.vel_stage = data_in ? 1 : 0;
-            c.depth_prev = o.depth_prev;
-            c.depth_cur = d_depth;
-            // (data_in implies valid_flow, so c.flow[0] is this frame's flow whenever the velocity stage runs)
-            o.depth_prev = d_depth;
-
-            // ---- outlier-rejection features on the first frame (ROFTFilter.cpp:313-322)
+            const size_t k = (size_t)t * n_obj + id;
+            const FrameJob j{t, id, e->frame_counter + t, inputs[k], (labels && labels[k].labels) ? &labels[k] : nullptr,
+                             (images && images[k].image) ? &images[k] : nullptr, *e->objs[id], blk[k]};
+            Sched& o = j.ho.s;
+            DevInputs d;
+            clear_ctrl(j.c);
+            TRY(check_frame_forms(e, j));
+            j.c.dt = (j.in.dt > 0.0) ? j.in.dt : cfg.sample_time;
+            TRY(resolve_inputs(e, j, sz, d));
+            if (e->depth.enabled) TRY(plan_depth_product(e, j, sz, d));
+            TRY(plan_flow_product(e, j, sz, d));
+            TRY(schedule_mask_source(e, j, sz, d));
+            schedule_flow_measurement(j, d);
+            // outlier-rejection features on the first frame (ROFTFilter.cpp:313-322)
             if (cfg.use_pose_resync && !o.features_initialized) {
-                c.feat_write = o.feat_next;
-                o.feat_next = (o.feat_next + 1) % kFeatRing;
-                o.feat_slot = c.feat_write;
+                take_feat_slot(o, j.c);
                 o.features_initialized = true;
             }
-            c.frame_idx = frame;
-            if (!build_pose_program(cfg, o, in, c))
+            j.c.frame_idx = j.frame;
+            if (!build_pose_program(cfg, o, j.in, j.c))
                 return fail(ROFT_ERR_CAPACITY, "more buffered velocities to replay than one frame's program holds (kMaxSteps)");
-            e->lin_any[c.lane] = true;
-            if (!lane_seen[(size_t)id * kNumLin + c.lane]) {
-                // the object's first frame on this lane in the batch: is its first step's twist older than the batch?
-                lane_seen[(size_t)id * kNumLin + c.lane] = 1;
-                e->lane_objs[c.lane]++;
-                const int age = (c.n_steps > 0 && c.steps[0].op) ? ((o.frame_idx - c.steps[0].twist_slot) & (kTwistRing - 1)) : 0;
-                if (age > t && c.outlier_step == 0) e->lane_old_first[c.lane]++;   // (a replay whose first step is the one the outlier test follows)
-            }
-            o.last_touch[o.cur_slot] = b;
-            if (c.outlier_step >= 0)
-                max_outliers[c.lane] = std::max(max_outliers[c.lane], ++n_outliers[(size_t)id * kNumLin + c.lane]);
-            if (c.outlier_step >= 0 && c.feat_read >= 0 && c.feat_read != c.feat_write &&
-                e->feat_batch[(size_t)id * kFeatRing + c.feat_read] == b) e->feat_dep_in_batch = true;
-            if (c.feat_write >= 0) {
-                e->feat_batch[(size_t)id * kFeatRing + c.feat_write] = b;
-                e->any_feat = true;
-                e->feat_frames |= 1u << t;
-                // a feature set is re-used only when the batch that read or wrote it last has ended
-                const int last = o.feat_use[c.feat_write];
-                if (last >= 0 && last < b) { if (int rc = wait_batch(e, last)) return rc; }
-                o.feat_use[c.feat_write] = b;
-            }
-            if (c.feat_read >= 0 && c.outlier_step >= 0) o.feat_use[c.feat_read] = b;
-            if (c.outlier_step >= 0 && c.feat_read == c.feat_write) e->any_feat_now = true;
+            TRY(account_lanes_and_features(e, j));
             o.frame_idx++;
         }
     }
-    for (int l = 0; l < kNumLin; ++l) e->n_segments[l] = 1 + max_outliers[l];
     // the label table behind the batch's control blocks: the sets, then (16-byte aligned) the members set by set
-    e->label_table_bytes = 0;
-    if (!e->label_sets.empty()) {
+    if (!pb.label_sets.empty()) {
         unsigned char* tab = reinterpret_cast<unsigned char*>(blk + (size_t)T * n_obj);
-        const size_t sets_bytes = sizeof(LabelSet) * e->label_sets.size();
+        const size_t sets_bytes = sizeof(LabelSet) * pb.label_sets.size();
         LabelMember* mem = reinterpret_cast<LabelMember*>(tab + sets_bytes);
         int first = 0;
-        for (size_t i = 0; i < e->label_sets.size(); ++i) {
-            e->label_sets[i].first = first;
-            e->label_sets[i].n = (int)e->label_members[i].size();
-            std::memcpy(mem + first, e->label_members[i].data(), sizeof(LabelMember) * e->label_members[i].size());
-            first += e->label_sets[i].n;
+        for (size_t i = 0; i < pb.label_sets.size(); ++i) {
+            pb.label_sets[i].first = first;
+            pb.label_sets[i].n = (int)pb.label_members[i].size();
+            std::memcpy(mem + first, pb.label_members[i].data(), sizeof(LabelMember) * pb.label_members[i].size());
+            first += pb.label_sets[i].n;
         }
-        std::memcpy(tab, e->label_sets.data(), sets_bytes);
-        e->label_table_bytes = (sets_bytes + sizeof(LabelMember) * (size_t)first + 15) & ~(size_t)15;
+        std::memcpy(tab, pb.label_sets.data(), sets_bytes);
+        pb.label_table_bytes = (sets_bytes + sizeof(LabelMember) * (size_t)first + 15) & ~(size_t)15;
     }
     return ROFT_OK;
 }
@@ -684,48 +720,37 @@ int roft_frames_submit_images(roft_engine* e, const roft_frame_input* inputs, co
     if (n_frames < 1 || n_frames > e->T_max) return fail(ROFT_ERR_INVALID, "n_frames must be 1 .. roft_config::max_batch_frames");
     if (e->submitted) return fail(ROFT_ERR_STATE, "previous batch not stepped yet");
     HIP_TRY(hipSetDevice(e->cfg.device));
+    PendingBatch& pb = e->pending;
     double hp_t = e->knobs.host_prof ? host_now_us() : 0.0;
-    e->cur_submit_t0 = host_now_us();
+    pb.submit_t0 = host_now_us();
     // bound the batches in flight (see roft_engine::lead); this also frees the batch ring slot
-    if (int rc = wait_batch(e, e->batch_counter - e->lead, &e->throttled)) return rc;
-    e->cur_wait_us = host_now_us() - e->cur_submit_t0;
+    TRY(wait_batch(e, e->batch_counter - e->lead, &pb.throttled));
+    pb.wait_us = host_now_us() - pb.submit_t0;
     HP_MARK(e, 0, hp_t);   // time blocked on the GPU
-    e->backup.resize(e->objs.size());
-    for (size_t i = 0; i < e->objs.size(); ++i) e->backup[i] = e->objs[i]->s;
-    e->any_feat = e->any_feat_now = e->had_uploads = e->produced_flows = false;
-    if (e->flow.enabled) {
-        e->flow.jobs.assign((size_t)n_frames, FlowFrameJobs{});
-        e->flow.stats_backup = e->flow.stats;
-    }
-    if (e->depth.enabled) {
-        e->depth.jobs.clear();
-        e->depth.stats_backup = e->depth.stats;
-        e->depth.timed = false;
-    }
-    e->feat_frames = 0;
-    e->feat_dep_in_batch = false;
-    e->new_mask_frames = e->plain_mask_frames = 0;
-    e->label_sets.clear();
-    e->label_members.clear();
-    e->label_table_bytes = 0;
-    e->gather.clear();
+    // what a refused call puts back (SubmitSnapshot: not the h2d counters of roft_engine_stats, which count what crossed the bus)
+    SubmitSnapshot& snap = e->snapshot;
+    snap.sched.resize(e->objs.size());
+    for (size_t i = 0; i < e->objs.size(); ++i) snap.sched[i] = e->objs[i]->s;
+    snap.flow = e->flow.stats;
+    snap.depth = e->depth.stats;
+    pb.reset(n_objects, n_frames);
+    e->depth.timed = false;
     int rc = submit_frames(e, inputs, labels, images, n_objects, n_frames);
     if (rc == ROFT_OK) rc = flush_gather(e);
-    e->gather.clear();
     HP_MARK(e, 1, hp_t);
     int rc2 = ROFT_OK;
     BatchSlot& bs = e->slot_of(e->batch_counter);
     hipEvent_t ev_wait = nullptr;   // what the host waits for: the copies
-    if (rc == ROFT_OK && e->produced_flows) {
+    if (rc == ROFT_OK && pb.facts.produced_flows) {
         // Camera images and raw depth: the production follows the copies on the upload stream.  The streams wait for ev_up, recorded behind the
         // production; the host for ev_host, recorded behind the copies alone -- and for nothing when nothing was copied.
         hipError_t err = hipSuccess;
-        if (e->had_uploads) { err = hipEventRecord(bs.ev_host, e->up_stream); ev_wait = bs.ev_host; }
-        if (err == hipSuccess && !e->depth.jobs.empty()) rc = enqueue_depth_production(e);
+        if (pb.facts.had_uploads) { err = hipEventRecord(bs.ev_host, e->up_stream); ev_wait = bs.ev_host; }
+        if (err == hipSuccess && !pb.depth_jobs.empty()) rc = enqueue_depth_production(e);
         if (err == hipSuccess && rc == ROFT_OK && e->flow.enabled) rc = enqueue_flow_production(e, n_frames);
         if (err == hipSuccess && rc == ROFT_OK) err = hipEventRecord(bs.ev_up, e->up_stream);
         if (err != hipSuccess) rc2 = fail(ROFT_ERR_DEVICE, std::string("flow production: ") + hipGetErrorString(err));
-    } else if (e->had_uploads) {
+    } else if (pb.facts.had_uploads) {
         hipError_t err = hipEventRecord(bs.ev_up, e->up_stream);
         if (err != hipSuccess) rc2 = fail(ROFT_ERR_DEVICE, std::string("input upload: ") + hipGetErrorString(err));
         ev_wait = bs.ev_up;
@@ -738,15 +763,14 @@ int roft_frames_submit_images(roft_engine* e, const roft_frame_input* inputs, co
     HP_MARK(e, 2, hp_t);
     if (rc != ROFT_OK || rc2 != ROFT_OK) {
         const std::string msg = last_error();
-        for (size_t i = 0; i < e->objs.size(); ++i) e->objs[i]->s = e->backup[i];
-        if (e->flow.enabled) e->flow.stats = e->flow.stats_backup;
-        if (e->depth.enabled) { e->depth.stats = e->depth.stats_backup; e->depth.jobs.clear(); }
+        for (size_t i = 0; i < e->objs.size(); ++i) e->objs[i]->s = snap.sched[i];
+        e->flow.stats = snap.flow;
+        e->depth.stats = snap.depth;
         return fail(rc != ROFT_OK ? rc : rc2, msg);
     }
-    e->cur_T = n_frames;
     e->submitted = true;
     e->device_pointers_checked = true;
-    e->cur_submit_us = host_now_us() - e->cur_submit_t0;
+    pb.submit_us = host_now_us() - pb.submit_t0;
     return ROFT_OK;
 }
 

@@ -49,6 +49,96 @@ def aligned_batches(first, last, T, period, phase=0):
 
 
 
+def frame_arrays(n):
+    return (L.FrameInput * n)(), (L.LabelMask * n)(), (L.FrameImage * n)()
+
+
+def fill_frame(frames, inputs, labels, images, base=0):
+    """One frame -- one dict per object, see ROFTFilterBatch.submit -- into entries base .. base + len(frames) - 1 of the caller's
+    L.FrameInput, L.LabelMask and L.FrameImage arrays.  Returns (keep, any_labels, any_images): the numpy arrays the entries point
+    into, whether an object takes its mask from a label image, whether one brings a camera image."""
+    keep = []
+    shared = {}   # one contiguous copy per distinct label / camera image array of the frame: the engine uploads a host pointer once
+    any_labels = any_images = False
+
+    def shared_pointer(a):
+        v = shared.get(id(a))
+        if v is None:
+            v = shared[id(a)] = np.ascontiguousarray(a)
+            keep.append(v)
+        return v
+
+    for i, f in enumerate(frames):
+        fi, lm, im = inputs[base + i], labels[base + i], images[base + i]
+        img = f.get("image")
+        if img is None:
+            im.image, im.image_type = None, 0
+        elif isinstance(img, int):
+            im.image, im.image_type = img, int(f["image_type"])
+        else:
+            if img.dtype != np.uint8 or not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] == 3)):
+                raise TypeError("a camera image is [H, W] or [H, W, 3] uint8")
+            v = shared_pointer(img)
+            im.image, im.image_type = v.ctypes.data, int(f.get("image_type", L.IMAGE_GRAY8 if v.ndim == 2 else L.IMAGE_RGB8))
+        any_images = any_images or img is not None
+        lab = f.get("labels")
+        if lab is None:
+            lm.labels, lm.label_type, lm.label = None, 0, 0
+        elif isinstance(lab, int):
+            lm.labels, lm.label_type, lm.label = lab, int(f["label_type"]), int(f["label"])
+        else:
+            if lab.dtype not in (np.uint8, np.uint16):
+                raise TypeError("a label image is uint8 or uint16, not %s" % lab.dtype)
+            v = shared_pointer(lab)
+            lm.labels, lm.label_type, lm.label = v.ctypes.data, (L.LABEL_U8 if v.dtype == np.uint8 else L.LABEL_U16), int(f["label"])
+        any_labels = any_labels or lab is not None
+        kind = f.get("mem_kind", L.MEM_HOST)
+        fi.mem_kind = kind
+        fi.dt = f.get("dt", 0.0)
+        fi.stamp = f.get("stamp", 0.0)            # only read with cfg.stamped_masks
+        fi.mask_stamp = f.get("mask_stamp", 0.0)
+        for key in ("depth", "flow", "mask"):
+            v = f.get(key)
+            if v is None:
+                setattr(fi, key, None)
+            elif kind == L.MEM_DEVICE or isinstance(v, int):
+                setattr(fi, key, int(v))   # raw address (device pointer, or a host pointer kept alive by the caller)
+            else:
+                v = np.ascontiguousarray(v)
+                keep.append(v)
+                setattr(fi, key, v.ctypes.data)
+        pose = f.get("pose")
+        if pose is not None:
+            fi.pose_valid = 1
+            fi.pose_x = (C.c_double * 3)(*pose[0])
+            fi.pose_q = (C.c_double * 4)(*pose[1])
+        else:
+            fi.pose_valid = 0
+    return keep, any_labels, any_images
+
+
+class BatchKeep(list):
+    """What a batch built by assemble_batch points into, frame by frame; and its L.LabelMask / L.FrameImage arrays (None: no frame
+    of the batch uses that form)."""
+    labels = images = None
+
+
+def assemble_batch(frames_list, n_objects):
+    """ROFTFilterBatch.build_batch for n_objects objects."""
+    T = len(frames_list)
+    arr, lab, img = frame_arrays(n_objects * T)
+    keep = BatchKeep()
+    for t, frames in enumerate(frames_list):
+        assert len(frames) == n_objects
+        frame_keep, any_labels, any_images = fill_frame(frames, arr, lab, img, t * n_objects)
+        keep.append(frame_keep)
+        if any_labels:
+            keep.labels = lab
+        if any_images:
+            keep.images = img
+    return arr, keep, T
+
+
 class ROFTFilterBatch:
     def __init__(self, cfg):
         L.require_device()
@@ -67,9 +157,7 @@ class ROFTFilterBatch:
         oid = C.c_int(-1)
         L.check(L.lib().roft_object_add(self._h, C.byref(desc), C.byref(oid)))
         self.n_objects += 1
-        self._inputs = (L.FrameInput * self.n_objects)()
-        self._labels = (L.LabelMask * self.n_objects)()
-        self._images = (L.FrameImage * self.n_objects)()
+        self._inputs, self._labels, self._images = frame_arrays(self.n_objects)
         self._meshes = getattr(self, "_meshes", []) + [(verts, tris)]   # render_log draws them
         return oid.value
 
@@ -83,154 +171,58 @@ class ROFTFilterBatch:
         Instead of `flow`, on an engine with enable_flow(): `image`, the camera image of the frame (numpy [H, W] gray or
         [H, W, 3]; or an address, then with `image_type` L.IMAGE_GRAY8 / IMAGE_BGR8 / IMAGE_RGB8; a 3-channel array is RGB8
         unless `image_type` says BGR8): the engine computes the flow from it and the frame before (roft_frames_submit_images)."""
-        any_labels = self._fill(frames)
-        if self._any_images:
-            L.check(L.lib().roft_frames_submit_images(self._h, self._inputs, self._labels if any_labels else None, self._images,
-                                                      self.n_objects, 1))
-        elif any_labels:
-            L.check(L.lib().roft_frames_submit_labels(self._h, self._inputs, self._labels, self.n_objects, 1))
-        else:
-            L.check(L.lib().roft_frame_submit(self._h, self._inputs, self.n_objects))
-
-    def _fill(self, frames):
-        """Fills self._inputs, self._labels and self._images (self._any_images: an object of the frame brings a camera image);
-        returns whether an object of the frame takes its mask from a label image."""
         assert len(frames) == self.n_objects
-        keep = []
-        shared = {}   # one contiguous copy per distinct label / camera image array of the frame: the engine uploads a host pointer once
-        any_labels = False
-        self._any_images = False
-        for i, f in enumerate(frames):
-            fi = self._inputs[i]
-            lm = self._labels[i]
-            im = self._images[i]
-            img = f.get("image")
-            if img is None:
-                im.image, im.image_type = None, 0
-            else:
-                self._any_images = True
-                if isinstance(img, int):
-                    im.image, im.image_type = img, int(f["image_type"])
-                else:
-                    if img.dtype != np.uint8 or not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] == 3)):
-                        raise TypeError("a camera image is [H, W] or [H, W, 3] uint8")
-                    v = shared.get(id(img))
-                    if v is None:
-                        v = shared[id(img)] = np.ascontiguousarray(img)
-                        keep.append(v)
-                    im.image, im.image_type = v.ctypes.data, int(f.get("image_type", L.IMAGE_GRAY8 if v.ndim == 2 else L.IMAGE_RGB8))
-            lab = f.get("labels")
-            if lab is None:
-                lm.labels, lm.label_type, lm.label = None, 0, 0
-            else:
-                any_labels = True
-                lm.label = int(f["label"])
-                if isinstance(lab, int):
-                    lm.labels, lm.label_type = lab, int(f["label_type"])
-                else:
-                    if lab.dtype not in (np.uint8, np.uint16):
-                        raise TypeError("a label image is uint8 or uint16, not %s" % lab.dtype)
-                    v = shared.get(id(lab))
-                    if v is None:
-                        v = shared[id(lab)] = np.ascontiguousarray(lab)
-                        keep.append(v)
-                    lm.labels, lm.label_type = v.ctypes.data, (L.LABEL_U8 if v.dtype == np.uint8 else L.LABEL_U16)
-            kind = f.get("mem_kind", L.MEM_HOST)
-            fi.mem_kind = kind
-            fi.dt = f.get("dt", 0.0)
-            fi.stamp = f.get("stamp", 0.0)            # only read with cfg.stamped_masks
-            fi.mask_stamp = f.get("mask_stamp", 0.0)
-            for key in ("depth", "flow", "mask"):
-                v = f.get(key)
-                if v is None:
-                    setattr(fi, key, None)
-                elif kind == L.MEM_DEVICE or isinstance(v, int):
-                    setattr(fi, key, int(v))   # raw address (device pointer, or a host pointer kept alive by the caller)
-                else:
-                    v = np.ascontiguousarray(v)
-                    keep.append(v)
-                    setattr(fi, key, v.ctypes.data)
-            pose = f.get("pose")
-            if pose is not None:
-                fi.pose_valid = 1
-                fi.pose_x = (C.c_double * 3)(*pose[0])
-                fi.pose_q = (C.c_double * 4)(*pose[1])
-            else:
-                fi.pose_valid = 0
-        self._keep = keep
-        return any_labels
+        self._keep, any_labels, any_images = fill_frame(frames, self._inputs, self._labels, self._images)
+        self._submit(self._inputs, None, self._labels if any_labels else None, self._images if any_images else None)
+
+    def _submit(self, arr, T, labels=None, images=None):
+        """T None: one frame through the one-frame entry point (where the frame has neither label nor camera images)."""
+        if images is not None:
+            L.check(L.lib().roft_frames_submit_images(self._h, arr, labels, images, self.n_objects, T or 1))
+        elif labels is not None:
+            L.check(L.lib().roft_frames_submit_labels(self._h, arr, labels, self.n_objects, T or 1))
+        elif T is None:
+            L.check(L.lib().roft_frame_submit(self._h, arr, self.n_objects))
+        else:
+            L.check(L.lib().roft_frames_submit(self._h, arr, self.n_objects, T))
 
     def build_inputs(self, frames):
         """Pre-build the ctypes input array of one frame (see submit) for submit_raw."""
-        saved = self._inputs, self._labels, self._images
-        self._inputs = (L.FrameInput * self.n_objects)()
-        self._labels = (L.LabelMask * self.n_objects)()
-        self._images = (L.FrameImage * self.n_objects)()
-        if self._fill(frames) or self._any_images:
+        assert len(frames) == self.n_objects
+        arr, lab, img = frame_arrays(self.n_objects)
+        keep, any_labels, any_images = fill_frame(frames, arr, lab, img)
+        if any_labels or any_images:
             raise ValueError("label and camera images go through build_batch / submit_batch_raw(..., labels=..., images=...)")
-        arr, keep = self._inputs, self._keep
-        self._inputs, self._labels, self._images = saved
         return arr, keep
 
     def submit_raw(self, inputs):
-        L.check(L.lib().roft_frame_submit(self._h, inputs, self.n_objects))
+        self._submit(inputs, None)
 
     def build_batch(self, frames_list):
-        """ctypes input array of a batch: frames_list[t] = one dict per object (see submit), t = 0 .. T-1.  When a frame uses
-        label images the returned `keep` ends with the batch's L.LabelMask array (see batch_labels); when one brings camera images,
-        the batch's L.FrameImage array comes before it (see batch_images)."""
-        T = len(frames_list)
-        arr = (L.FrameInput * (self.n_objects * T))()
-        lab = (L.LabelMask * (self.n_objects * T))()
-        img = (L.FrameImage * (self.n_objects * T))()
-        keep = []
-        saved = self._inputs, self._labels, self._images
-        any_labels = any_images = False
-        for t, frames in enumerate(frames_list):
-            self._inputs = (L.FrameInput * self.n_objects)()
-            self._labels = (L.LabelMask * self.n_objects)()
-            self._images = (L.FrameImage * self.n_objects)()
-            any_labels = self._fill(frames) or any_labels
-            any_images = any_images or self._any_images
-            for i in range(self.n_objects):
-                arr[t * self.n_objects + i] = self._inputs[i]
-                lab[t * self.n_objects + i] = self._labels[i]
-                img[t * self.n_objects + i] = self._images[i]
-            keep.append(self._keep)
-        self._inputs, self._labels, self._images = saved
-        if any_images:
-            keep.append(img)
-        if any_labels:
-            keep.append(lab)
-        return arr, keep, T
+        """ctypes input array of a batch: frames_list[t] = one dict per object (see submit), t = 0 .. T-1.  The returned `keep`
+        holds what the array points into, and the batch's L.LabelMask / L.FrameImage arrays where a frame uses label images /
+        brings camera images (see batch_labels, batch_images)."""
+        return assemble_batch(frames_list, self.n_objects)
 
     @staticmethod
     def batch_labels(keep):
         """The L.LabelMask array of a batch built by build_batch, or None when no frame of it uses label images."""
-        return keep[-1] if keep and isinstance(keep[-1], C.Array) and keep[-1]._type_ is L.LabelMask else None
+        return getattr(keep, "labels", None)
 
     @staticmethod
     def batch_images(keep):
         """The L.FrameImage array of a batch built by build_batch, or None when no frame of it brings camera images."""
-        for v in keep[-2:]:
-            if isinstance(v, C.Array) and v._type_ is L.FrameImage:
-                return v
-        return None
+        return getattr(keep, "images", None)
 
     def submit_batch(self, frames_list):
         """A batch of consecutive frames (at most cfg.max_batch_frames): roft_frames_submit, roft_frames_submit_labels when a
         frame takes masks from label images, roft_frames_submit_images when one brings camera images."""
         arr, keep, T = self.build_batch(frames_list)
         self._keep = keep
-        self.submit_batch_raw(arr, T, self.batch_labels(keep), self.batch_images(keep))
+        self._submit(arr, T, keep.labels, keep.images)
 
     def submit_batch_raw(self, arr, T, labels=None, images=None):
-        if images is not None:
-            L.check(L.lib().roft_frames_submit_images(self._h, arr, labels, images, self.n_objects, T))
-        elif labels is None:
-            L.check(L.lib().roft_frames_submit(self._h, arr, self.n_objects, T))
-        else:
-            L.check(L.lib().roft_frames_submit_labels(self._h, arr, labels, self.n_objects, T))
+        self._submit(arr, T, labels, images)
 
     def enable_flow(self, **of_params):
         """Camera images instead of flow frames (frame key `image`): the engine computes the optical flow itself, with the

@@ -26,7 +26,7 @@ static std::string describe(const PlanInputs& in, bool alone)
                   "feat_used-2 %d vel_used-1 %d done_used %d %d",
                   k.handoff_mode, k.prep_mode, k.part_mode, k.feat_mask_mode, k.lanes_wait_skf, k.early_lanes, k.ctrl_ingest, k.outlier_steady_div,
                   in.multi, in.timing, in.timing_level, in.wait_value_ok, in.have_skf_started, in.T, in.n_obj, in.cus, in.batch_counter, in.idle_mark,
-                  in.lead, in.completed_batches, in.had_uploads, in.new_mask_frames, in.any_feat, in.any_feat_now, in.feat_dep_in_batch,
+                  in.lead, in.completed_batches, in.had_uploads, in.plain_mask_frames, in.any_feat, in.any_feat_now, in.feat_dep_in_batch,
                   in.n_segments[0], in.n_segments[1], in.lin_any[0], in.lin_any[1], in.lane_objs[0], in.lane_objs[1], in.lane_old_first[0],
                   in.lane_old_first[1], in.relabel_wait[0], in.relabel_wait[1], in.outlier_bands_per_alternative, in.conflict_free,
                   in.up_stream_distinct, alone, in.feat_used_two_back, in.vel_used_prev, in.done_used_relabel[0], in.done_used_relabel[1]);
@@ -128,8 +128,8 @@ static void check_rules(const PlanInputs& in, bool alone)
     RULE(implies(in.multi && in.had_uploads && !p.prep, p.wait_up));
 
     // fused control + ingest launch: never under timing or with the preparation ahead
-    RULE(implies(p.try_fused, !in.timing && !p.prep && in.new_mask_frames != 0 && k.ctrl_ingest != 0));
-    RULE(implies(k.ctrl_ingest != 0 && !in.timing && !p.prep && in.new_mask_frames != 0, p.try_fused));
+    RULE(implies(p.try_fused, !in.timing && !p.prep && in.plain_mask_frames != 0 && k.ctrl_ingest != 0));
+    RULE(implies(k.ctrl_ingest != 0 && !in.timing && !p.prep && in.plain_mask_frames != 0, p.try_fused));
 
     // velocity chain released one mask frame early
     RULE(implies(k.part_mode == 0, !p.part_gate));
@@ -178,7 +178,7 @@ static void check_rules(const PlanInputs& in, bool alone)
     // stop event of the span's last kernel, or recorded behind it under full timing (ev_ctrl and ev_part are always stop events; a
     // preparation without a mask to ingest has no kernel to end with ev_prep)
     RULE(p.ev_ctrl != Signal::record);
-    RULE(implies(p.prep, (p.ev_prep == Signal::record) == (full || in.new_mask_frames == 0)));
+    RULE(implies(p.prep, (p.ev_prep == Signal::record) == (full || in.plain_mask_frames == 0)));
     for (Signal s : {p.ev_mask, p.ev_feat, p.ev_skf, p.ev_vel, p.lane[0].ev_done, p.lane[1].ev_done})
         RULE(s == Signal::none || (s == Signal::record) == full);
 
@@ -257,7 +257,7 @@ static long sweep()
                 in.batch_counter = in.idle_mark + pick(since_idle);
                 in.completed_batches = std::max(0, in.batch_counter - (int)rnd(lead + 1));
                 in.had_uploads = rnd(2);
-                in.new_mask_frames = pick({0u, 1u, 0x21u}) & ((1u << in.T) - 1);
+                in.plain_mask_frames = pick({0u, 1u, 0x21u}) & ((1u << in.T) - 1);
                 in.any_feat = rnd(4) != 0;
                 in.any_feat_now = in.any_feat && rnd(6) == 0;
                 in.feat_dep_in_batch = in.any_feat && in.T > 1 && rnd(6) == 0;

@@ -63,7 +63,7 @@ int main()
         in.timing_level = timing == 1 ? 1 : 2;
         in.T = T; in.n_obj = n_obj; in.cus = 256;
         in.batch_counter = batch_counter; in.lead = T > 1 ? 5 : 6;
-        in.new_mask_frames = masks & ((1u << T) - 1u);
+        in.plain_mask_frames = masks & ((1u << T) - 1u);
         in.had_uploads = uploads != 0;
         in.up_stream_distinct = up_distinct != 0;
         in.any_feat = feat != 0;
@@ -86,11 +86,11 @@ int main()
         if (one.prep) {
             ++seen_prep;
             RULE(one.ev_prep == (full ? Signal::record : Signal::stop));
-            if (in.new_mask_frames == 0 && !full) { RULE(none.ev_prep == Signal::record); ++seen_stop_by_label; }
+            if (in.plain_mask_frames == 0 && !full) { RULE(none.ev_prep == Signal::record); ++seen_stop_by_label; }
             else RULE(none.ev_prep == one.ev_prep);
         }
         // (4)
-        RULE(one.try_fused == (ctrl_ingest != 0 && !one.prep && in.new_mask_frames != 0 && !in.timing));
+        RULE(one.try_fused == (ctrl_ingest != 0 && !one.prep && in.plain_mask_frames != 0 && !in.timing));
         seen_fused += one.try_fused;
         pairs += 2;
     }

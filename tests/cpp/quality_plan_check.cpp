@@ -56,7 +56,7 @@ int main()
         in.batch_counter = batch;
         in.completed_batches = batch > 2 ? batch - 2 : 0;
         in.had_uploads = uploads != 0;
-        in.new_mask_frames = uploads ? 1u : 0u;
+        in.plain_mask_frames = uploads ? 1u : 0u;
         in.any_feat = feat != 0;
         in.conflict_free = true;
         in.lin_any[0] = (lanes & 1) != 0;

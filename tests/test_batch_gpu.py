@@ -126,6 +126,59 @@ def test_batch_size_is_checked_and_a_failed_submit_consumes_nothing():
         assert np.array_equal(x, y)
 
 
+TRACE_COUNTED = ("frames", "steady", "handoff", "early_lanes", "outlier_parts_halved", "launches", "event_ops")
+
+
+def run_host_splits(streams, n, splits, refuse):
+    """The streams as HOST numpy inputs in batches of `splits` frames.  refuse: every batch is first submitted with the LAST
+    object's entry of its LAST frame broken (mem_kind 7) -- the call fails when every other object-frame of the batch has been
+    scheduled, staged and given its feature slots and pose program --, then stepped (which must raise), then submitted intact.
+    Returns the log, the final masks and the counted fields of the batch trace."""
+    def host_frame(st, k):
+        depth, flow, mask, pose = util.frame_inputs(st, k)
+        return dict(depth=depth, flow=flow, mask=mask, pose=pose, dt=st.dt, mem_kind=L.MEM_HOST)
+
+    eng = make_engine(streams, max_batch_frames=max(splits))
+    eng.enable_log(n)
+    k = i = 0
+    while k < n:
+        t = min(splits[i % len(splits)], n - k)
+        frames = [[host_frame(st, k + j) for st in streams] for j in range(t)]
+        if refuse:
+            bad = [[dict(f) for f in row] for row in frames]
+            bad[-1][-1]["mem_kind"] = 7
+            with pytest.raises(L.RoftError):
+                eng.submit_batch(bad)
+            with pytest.raises(L.RoftError):
+                eng.step()                                                      # nothing was submitted
+        eng.submit_batch(frames)
+        eng.step()
+        k += t
+        i += 1
+    log = eng.get_log(0, n)
+    masks = [eng.mask(o) for o in range(len(streams))]
+    trace = [{f: b[f] for f in TRACE_COUNTED} for b in eng.batch_trace()]
+    eng.close()
+    return log, masks, trace
+
+
+def test_a_submit_refused_at_its_last_object_frame_consumes_nothing():
+    """The refused attempt has done everything a submit does -- lanes rebalanced (dropped poses), an aged-out flow cloned (a
+    dropped flow frame), an empty and a three-valued mask staged, several pose segments per batch (a pose on every frame), HOST
+    runs and images uploaded into the staging slots -- before its very last object-frame is found broken.  The run must equal the
+    same splits without refusals: log and final masks bit for bit, and per batch the counted fields of the batch trace (host
+    times and `throttled` are measurements and left out; two refusal-free runs agree on every counted field, so none is dropped)."""
+    n, splits = 24, [3, 1, 8, 5]
+    streams = awkward_streams(n)
+    ref, ref_masks, ref_trace = run_host_splits(streams, n, splits, refuse=False)
+    got, masks, trace = run_host_splits(streams, n, splits, refuse=True)
+    for x, y in zip(ref, got):
+        assert np.array_equal(x, y)
+    for x, y in zip(ref_masks, masks):
+        assert np.array_equal(x, y)
+    assert len(trace) == 7 and trace == ref_trace
+
+
 @pytest.mark.parametrize("prep", ["1", "2"])
 def test_host_buffers_may_be_reused_when_submit_returns(prep, monkeypatch):
     """roft_frame_input: HOST buffers are copied before the submit call returns -- a live caller that refills its one
