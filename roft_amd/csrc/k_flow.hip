@@ -18,21 +18,6 @@
 
 namespace roft {
 
-__device__ __forceinline__ void flow_at(const void* data, const DevFlowFmt& f, int row, int col, float& dx,
-                                        float& dy)
-{
-    size_t idx = ((size_t)row * (size_t)f.cols + (size_t)col);
-    if (f.type == ROFT_FLOW_S16C2) {
-        short2 p = reinterpret_cast<const short2*>(data)[idx];
-        dx = (float)p.x / f.scale;
-        dy = (float)p.y / f.scale;
-    } else {
-        float2 p = reinterpret_cast<const float2*>(data)[idx];
-        dx = p.x / f.scale;
-        dy = p.y / f.scale;
-    }
-}
-
 __device__ __forceinline__ bool is_flow_valid(float fx, float fy)
 {
     return !isnan(fx) && !isnan(fy) && fabs((double)fx) < 1e9 && fabs((double)fy) < 1e9;

@@ -24,54 +24,11 @@
 // The per-frame decisions (mode, source, flow count, binary or not) are made by the frame kernels and recorded in
 // MaskRec rows that carry the state from frame to frame and from batch to batch.
 #include <algorithm>
-#include <cstdlib>
+#include <initializer_list>
 
 #include "roft_device.h"
 
 namespace roft {
-
-// (int)float as evaluated by the reference's x86-64 build (cvttss2si): NaN / out of range give
-// INT_MIN, which then fails the `< 0` bounds test.  AMD's v_cvt_i32_f32 would saturate / give 0.
-__device__ __forceinline__ int trunc_int_x86(float x)
-{
-    if (!(x > -2147483904.0f && x < 2147483648.0f)) return INT32_MIN;
-    return (int)x;
-}
-
-__device__ __forceinline__ void flow_at(const void* data, const DevFlowFmt& f, int row, int col, float& dx,
-                                        float& dy)
-{
-    size_t idx = ((size_t)row * (size_t)f.cols + (size_t)col);
-    if (f.type == ROFT_FLOW_S16C2) {
-        short2 p = reinterpret_cast<const short2*>(data)[idx];
-        dx = (float)p.x / f.scale;
-        dy = (float)p.y / f.scale;
-    } else {
-        float2 p = reinterpret_cast<const float2*>(data)[idx];
-        dx = p.x / f.scale;
-        dy = p.y / f.scale;
-    }
-}
-
-// the same element in two steps -- load, then decode -- so that several loads can be in flight before the first use
-template <int FT>
-__device__ __forceinline__ uint2 flow_raw(const void* data, size_t idx)
-{
-    if (FT == ROFT_FLOW_S16C2) return make_uint2(reinterpret_cast<const uint32_t*>(data)[idx], 0u);
-    return reinterpret_cast<const uint2*>(data)[idx];
-}
-
-template <int FT>
-__device__ __forceinline__ void flow_decode(uint2 raw, float scale, float& dx, float& dy)
-{
-    if (FT == ROFT_FLOW_S16C2) {
-        dx = (float)(short)(raw.x & 0xFFFFu) / scale;
-        dy = (float)(short)(raw.x >> 16) / scale;
-    } else {
-        dx = __uint_as_float(raw.x) / scale;
-        dy = __uint_as_float(raw.y) / scale;
-    }
-}
 
 // ---- ingest: raw u8 mask -> (nz, obj) bit planes ---------------------------------------------------
 // One thread converts 64 consecutive pixels: four 16-byte loads, two 64-bit masks built in registers,
@@ -105,15 +62,12 @@ __device__ __forceinline__ void ingest_group(const uint4* src, int g, uint2* nz,
     ones += __popcll(bnz & ~bob);
 }
 
-// grid: (ceil(W*H/64/256), n_obj); frame t of the batch
-__global__ __launch_bounds__(256) void mask_ingest_kernel(EngineArrays a, int t)
+// Chunk `chunk` (one group per thread of the workgroup) of the byte mask that control block c delivers for object obj on frame t
+// of the batch -> its plane words, and each wave's pixel counts added to the frame's record.
+__device__ __forceinline__ void ingest_delivered(const EngineArrays& a, const FrameCtrl& c, int t, int obj, int chunk)
 {
-    ROFT_RESIDENT(a, RK_MASK_INGEST);
-    const int obj = blockIdx.y;
-    const FrameCtrl& c = frame_ctrl(a, t, obj);
-    if (!c.has_new_mask || c.label_type) return;   // (masks from a label image: label_ingest_kernel)
     const int n_grp = (a.cam.W * a.cam.H) >> 6;
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    const int g = chunk * blockDim.x + threadIdx.x;
     int count = 0, ones = 0;
     if (g < n_grp)
         ingest_group(reinterpret_cast<const uint4*>(c.new_mask), g,
@@ -125,6 +79,16 @@ __global__ __launch_bounds__(256) void mask_ingest_kernel(EngineArrays a, int t)
         atomicAdd(&r.new_count, count);
         if (ones) atomicAdd(&r.new_ones, ones);
     }
+}
+
+// grid: (ceil(W*H/64/256), n_obj); frame t of the batch
+__global__ __launch_bounds__(256) void mask_ingest_kernel(EngineArrays a, int t)
+{
+    ROFT_RESIDENT(a, RK_MASK_INGEST);
+    const int obj = blockIdx.y;
+    const FrameCtrl& c = frame_ctrl(a, t, obj);
+    if (!c.has_new_mask || c.label_type) return;   // (masks from a label image: label_ingest_kernel)
+    ingest_delivered(a, c, t, obj, blockIdx.x);
 }
 
 // Control blocks of a batch AND the ingest of the masks it delivers in ONE launch (round 6; bursts: on the mask stream the control
@@ -149,19 +113,7 @@ __global__ __launch_bounds__(256) void ctrl_ingest_kernel(const uint4* __restric
     const int t = (int)((frames_packed >> (4 * fi)) & 15u);   // the fi-th delivering frame of the batch
     const FrameCtrl& c = reinterpret_cast<const FrameCtrl*>(src)[(size_t)t * a.n_obj + obj];
     if (!c.has_new_mask || c.label_type) return;   // (masks from a label image: label_ingest_kernel)
-    const int n_grp = (a.cam.W * a.cam.H) >> 6;
-    const int g = chunk * blockDim.x + threadIdx.x;
-    int count = 0, ones = 0;
-    if (g < n_grp)
-        ingest_group(reinterpret_cast<const uint4*>(c.new_mask), g,
-                     reinterpret_cast<uint2*>(a.planes + plane_offset(a, obj, a.slot_new + t, 0)),
-                     reinterpret_cast<uint2*>(a.planes + plane_offset(a, obj, a.slot_new + t, 1)), count, ones);
-    for (int off = 32; off > 0; off >>= 1) { count += __shfl_xor(count, off, 64); ones += __shfl_xor(ones, off, 64); }
-    if ((threadIdx.x & 63) == 0 && count) {
-        MaskRec& r = a.mrec[(size_t)(t + 1) * a.n_obj + obj];
-        atomicAdd(&r.new_count, count);
-        if (ones) atomicAdd(&r.new_ones, ones);
-    }
+    ingest_delivered(a, c, t, obj, chunk);
 }
 
 // returns false when the batch's delivering frames do not fit the packed argument (more than eight: never with T <= 8)
@@ -292,13 +244,7 @@ void launch_mask_reset(const EngineArrays& a, hipStream_t s)
 // frame: each of them filled the register file of its CU for the whole batch -- 192 of 256 CUs held by a latency-bound
 // kernel, half of the chip's CU time, DESIGN.md section 5.  A workgroup here is four waves with a few KB of LDS: it fits
 // next to the filters' workgroups and is gone after a few microseconds.)
-#ifndef ROFT_FRAME_THREADS
-#define ROFT_FRAME_THREADS 256
-#endif
-constexpr int kFrameThreads = ROFT_FRAME_THREADS;
-constexpr int kFrameWaves = kFrameThreads / 64;
-// (64-pixel groups whose walks through the flows are in flight together in one wave -- chase_groups' NCH: a pixel's
-//  walk is a chain of dependent loads, the chains of different groups are independent)
+constexpr int kFrameThreads = 256, kFreshThreads = 128;   // threads of a workgroup: every frame | a frame that delivers a mask (launch_mask_chain)
 
 struct MaskShared {
     int bbox[4];
@@ -342,6 +288,87 @@ __device__ __forceinline__ int trunc_clamped(float x)
 
 #define ROFT_GLOBAL __attribute__((address_space(1)))
 
+// ---- the vocabulary of the walks ---------------------------------------------------------------------------------------
+// A wave-uniform base pointer in scalar registers: the loads from it need only a 32-bit offset per lane.
+__device__ __forceinline__ const ROFT_GLOBAL unsigned char* uniform_global(const void* p)
+{
+    const unsigned long long bits = (unsigned long long)p;
+    return (const ROFT_GLOBAL unsigned char*)(((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(bits >> 32)) << 32) |
+                                              (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)bits));
+}
+
+// A wave-uniform LDS pointer as such: through a generic pointer every read of the list is a flat load, and a flat load waits
+// for ALL outstanding memory operations -- the flow loads would go out one at a time.
+__device__ __forceinline__ ROFT_LDS uint32_t* uniform_lds(const void* p)
+{
+    return (ROFT_LDS uint32_t*)(uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(const ROFT_LDS void*)p);
+}
+
+// One flow element in two steps -- load, then decode -- so that the loads of several groups are in flight before the first use.
+// NaN carries "dropped" through a walk: it survives every flow addition and trunc_clamped converts it to "out of the image", so a
+// walk tests nothing on the way, and a NaN flow drops the pixel the same way, as cvttss2si does in the reference.
+template <int FT>
+constexpr uint32_t kFlowElem = (FT == ROFT_FLOW_S16C2) ? 4u : 8u;   // bytes: short2 | float2
+
+template <int FT>
+__device__ __forceinline__ uint2 flow_load(const ROFT_GLOBAL unsigned char* p)
+{
+    if (FT == ROFT_FLOW_S16C2) return make_uint2(*(const ROFT_GLOBAL uint32_t*)p, 0u);
+    const unsigned long long w = *(const ROFT_GLOBAL unsigned long long*)p;
+    return make_uint2((uint32_t)w, (uint32_t)(w >> 32));
+}
+
+template <int FT>
+__device__ __forceinline__ void flow_value(uint2 raw, float& dx, float& dy)
+{
+    if (FT == ROFT_FLOW_S16C2) { dx = (float)(short)(raw.x & 0xFFFFu); dy = (float)(short)(raw.x >> 16); }
+    else { dx = __uint_as_float(raw.x); dy = __uint_as_float(raw.y); }
+}
+
+// raw flow -> pixels.  MODE 2: scale 1; MODE 1: a power of two, the reciprocal multiply is the division, bit for bit; MODE 0: divide
+template <int MODE>
+__device__ __forceinline__ void scale_flow(const ChaseGeo& g, float& dx, float& dy)
+{
+    if (MODE == 1) { dx *= g.inv_scale; dy *= g.inv_scale; }
+    else if (MODE == 0) { dx /= g.scale; dy /= g.scale; }
+}
+
+// The pixel of lane `lane` in the 64-pixel group of list entry yx = (row << 16 | column) of its first pixel: a group may straddle
+// rows when W % 64 != 0
+__device__ __forceinline__ void group_pixel(int W, uint32_t yx, int lane, int& px, int& py)
+{
+    px = (int)(yx & 0xFFFFu) + lane;
+    py = (int)(yx >> 16);
+    if (W & 63) {
+        if (px >= W) { px -= W; ++py; }
+        if (px >= W) { px -= W; ++py; }
+    }
+}
+
+// A workgroup's list of non-empty groups (LDS).  An entry is (row << 16 | column) of the group's first pixel.  A wave reserves
+// the entries of its non-empty groups with ONE atomic (`ne`: this thread's group is one); entry() is the thread's own.
+__device__ __forceinline__ uint32_t group_entry(int g, int W)
+{
+    const int p0 = g * 64, y0 = p0 / W;
+    return ((uint32_t)y0 << 16) | (uint32_t)(p0 - y0 * W);
+}
+
+struct ListSlot {
+    int base;
+    unsigned long long wave;   // the wave's lanes with a group to list
+    __device__ __forceinline__ int entry() const { return base + __popcll(wave & ((1ull << (threadIdx.x & 63)) - 1ull)); }
+};
+
+__device__ __forceinline__ ListSlot list_reserve(int& n_list, bool ne)
+{
+    ListSlot s;
+    s.wave = __ballot(ne);
+    s.base = 0;
+    if ((threadIdx.x & 63) == 0 && s.wave) s.base = atomicAdd(&n_list, __popcll(s.wave));
+    s.base = __shfl(s.base, 0, 64);
+    return s;
+}
+
 // Where the target bits of a workgroup go: an LDS window of plane words [off, off + words) -- the rows of the workgroup's
 // source groups and a margin above and below --, and, for the few pixels that fly further, the destination plane itself.
 struct OrTarget {
@@ -357,17 +384,14 @@ struct OrTarget {
     }
 };
 
-// Walks of the source pixels of one frame.  `list` (LDS) holds non-empty 64-pixel groups of the source plane as
-// (row << 16 | column) of their first pixel -- the division by the image width is done once per group by the list
-// pass, one group per thread, instead of by every wave that walks the group; wave w of the NW waves owns entries w, w + NW,
+// Walks of the source pixels of one frame.  `list` (LDS) holds non-empty 64-pixel groups of the source plane (group_entry:
+// one division by the image width per group, not one by every wave that walks it); wave w of the NW waves owns entries w, w + NW,
 // ... (the object's rows spread over all waves), keeps the plane words of up to 64 of them in its lanes (lane i <-> the
 // wave's i-th entry) and chases them NCH at a time: the flow reads of a wave are row-contiguous (64 x 8 B).  A surviving
 // pixel is handed to `hit(target, x, y, source)`.
 // The instruction count per pixel and flow matters as much as the load latency:
 //  * per-group work (row / column of the group) is wave-uniform;
-//  * a pixel that is not set, or left the image, carries t_x = NaN from then on -- NaN survives every flow addition and
-//    converts to "out of the image", so there is no per-walk activity flag to keep (and a NaN flow drops the pixel the
-//    same way, as cvttss2si does in the reference);
+//  * a pixel that is not set, or left the image, carries t_x = NaN from then on (flow_value): no per-walk activity flag to keep;
 //  * the float -> int conversions are clamps; MODE 2: grid 1 and scale 1 (CV_32FC2), the flow element of a pixel is
 //    the pixel itself; MODE 1: grid and scale are powers of two, the divisions are exact reciprocal multiplies;
 //    MODE 0: true divisions.
@@ -410,13 +434,9 @@ __device__ __forceinline__ void chase_groups(const ChaseGeo g, const uint2* plan
                     unsigned long long bits = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)mine.y, it) << 32) |
                                               (uint32_t)__builtin_amdgcn_readlane((int)mine.x, it);
                     if (clear00 && yx == 0u) bits &= ~1ull;                 // mask_.at<uchar>(0,0) = 0
-                    // row / column of the group's first pixel: wave-uniform; a group may straddle rows when W % 64 != 0
-                    const int y0 = (int)(yx >> 16), x0 = (int)(yx & 0xFFFFu);
-                    int px = x0 + lane, py = y0;
-                    if (W & 63) {
-                        if (px >= W) { px -= W; ++py; }
-                        if (px >= W) { px -= W; ++py; }
-                    }
+                    const int y0 = (int)(yx >> 16), x0 = (int)(yx & 0xFFFFu);   // (wave-uniform)
+                    int px, py;
+                    group_pixel(W, yx, lane, px, py);
                     src[u] = y0 * W + x0 + lane;
                     t_x[u] = ((bits >> lane) & 1ull) ? (float)px : nan;
                     t_y[u] = (float)py;
@@ -424,11 +444,7 @@ __device__ __forceinline__ void chase_groups(const ChaseGeo g, const uint2* plan
             }
             // flows in chronological order: oldest buffered first (flows[n_flows-1]) ... current (flows[0])
             for (int j = n_flows - 1; j >= 0; --j) {
-                // (wave-uniform base pointer in scalar registers: the loads need only a 32-bit offset per lane)
-                const unsigned long long fl_bits = (unsigned long long)flows[j];
-                const ROFT_GLOBAL unsigned char* fl = (const ROFT_GLOBAL unsigned char*)(
-                    ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(fl_bits >> 32)) << 32) |
-                    (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)fl_bits));
+                const ROFT_GLOBAL unsigned char* fl = uniform_global(flows[j]);
                 uint2 raw[NCH];
 #pragma unroll
                 for (int u = 0; u < NCH; ++u) {
@@ -440,21 +456,13 @@ __device__ __forceinline__ void chase_groups(const ChaseGeo g, const uint2* plan
                     else if (MODE == 1) { fr = trunc_clamped(t_y[u] * g.inv_grid); fc = trunc_clamped(t_x[u] * g.inv_grid); }
                     else { fr = trunc_clamped(t_y[u] / g.grid_f); fc = trunc_clamped(t_x[u] / g.grid_f); }
                     // dropped pixels read element (0, 0): the loads stay unconditional and in flight together
-                    const uint32_t off = in ? (uint32_t)(fr * g.cols + fc) * (FT == ROFT_FLOW_S16C2 ? 4u : 8u) : 0u;
-                    if (FT == ROFT_FLOW_S16C2) {
-                        raw[u] = make_uint2(*(const ROFT_GLOBAL uint32_t*)(fl + off), 0u);
-                    } else {
-                        const unsigned long long w = *(const ROFT_GLOBAL unsigned long long*)(fl + off);
-                        raw[u] = make_uint2((uint32_t)w, (uint32_t)(w >> 32));
-                    }
+                    raw[u] = flow_load<FT>(fl + (in ? (uint32_t)(fr * g.cols + fc) * kFlowElem<FT> : 0u));
                 }
 #pragma unroll
                 for (int u = 0; u < NCH; ++u) {
                     float dx, dy;
-                    if (FT == ROFT_FLOW_S16C2) { dx = (float)(short)(raw[u].x & 0xFFFFu); dy = (float)(short)(raw[u].x >> 16); }
-                    else { dx = __uint_as_float(raw[u].x); dy = __uint_as_float(raw[u].y); }
-                    if (MODE == 1) { dx *= g.inv_scale; dy *= g.inv_scale; }
-                    else if (MODE == 0) { dx /= g.scale; dy /= g.scale; }
+                    flow_value<FT>(raw[u], dx, dy);
+                    scale_flow<MODE>(g, dx, dy);
                     t_x[u] += dx;
                     t_y[u] += dy;
                 }
@@ -473,27 +481,17 @@ __device__ __forceinline__ void chase_groups(const ChaseGeo g, const uint2* plan
 // VGPRs per group -- and ALL groups of a wave (about a dozen) go out in one round: the frame pays one
 // memory latency for its flow.  Position, bit and target are (re)computed when the data is back.  Same arithmetic as
 // chase_groups with n_flows == 1, operation by operation.  Needs the plane words of the listed groups in LDS (`words`).
-#ifndef ROFT_SINGLE_WALKS
-#define ROFT_SINGLE_WALKS 12
-#endif
-constexpr int kSingleWalks = ROFT_SINGLE_WALKS;   // groups per wave whose flow loads are in flight together
+constexpr int kSingleWalks = 12;   // groups per wave whose flow loads are in flight together
 template <int FT, int MODE, int NW>
 __device__ __forceinline__ void walk_single(const ChaseGeo g, const uint32_t* list_, const uint2* words_, int n_list, bool clear00,
                                             const void* flow, const OrTarget tgt)
 {
     constexpr int NCH = kSingleWalks;
-    // (LDS pointers as such: through generic pointers every read of the list is a flat load, and a flat load waits for
-    //  ALL outstanding memory operations -- the flow loads would go out one at a time)
-    const ROFT_LDS uint32_t* const list = (const ROFT_LDS uint32_t*)(uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane(
-        (int)(uint32_t)(uintptr_t)(const ROFT_LDS uint32_t*)list_);
-    const ROFT_LDS uint32_t* const words = (const ROFT_LDS uint32_t*)(uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane(
-        (int)(uint32_t)(uintptr_t)(const ROFT_LDS uint32_t*)reinterpret_cast<const uint32_t*>(words_));
+    const ROFT_LDS uint32_t* const list = uniform_lds(list_);
+    const ROFT_LDS uint32_t* const words = uniform_lds(words_);
     const int W = g.W, H = g.H;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long fl_bits = (unsigned long long)flow;
-    const ROFT_GLOBAL unsigned char* fl = (const ROFT_GLOBAL unsigned char*)(
-        ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(fl_bits >> 32)) << 32) |
-        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)fl_bits));
+    const ROFT_GLOBAL unsigned char* fl = uniform_global(flow);
     for (int e0 = wave; e0 < n_list; e0 += NCH * NW) {
         uint2 raw[NCH];
 #pragma unroll
@@ -502,21 +500,11 @@ __device__ __forceinline__ void walk_single(const ChaseGeo g, const uint32_t* li
             raw[u] = make_uint2(0u, 0u);
             if (e < n_list) {   // (wave-uniform)
                 const uint32_t yx = (uint32_t)__builtin_amdgcn_readfirstlane((int)list[e]);
-                int px = (int)(yx & 0xFFFFu) + lane, py = (int)(yx >> 16);
-                if (W & 63) {
-                    if (px >= W) { px -= W; ++py; }
-                    if (px >= W) { px -= W; ++py; }
-                }
-                int fr, fc;
+                int px, py, fr, fc;
+                group_pixel(W, yx, lane, px, py);
                 if (MODE == 2) { fr = py; fc = px; }
                 else { fr = trunc_clamped((float)py * g.inv_grid); fc = trunc_clamped((float)px * g.inv_grid); }
-                const uint32_t off = (uint32_t)(fr * g.cols + fc) * (FT == ROFT_FLOW_S16C2 ? 4u : 8u);
-                if (FT == ROFT_FLOW_S16C2) {
-                    raw[u] = make_uint2(*(const ROFT_GLOBAL uint32_t*)(fl + off), 0u);
-                } else {
-                    const unsigned long long w = *(const ROFT_GLOBAL unsigned long long*)(fl + off);
-                    raw[u] = make_uint2((uint32_t)w, (uint32_t)(w >> 32));
-                }
+                raw[u] = flow_load<FT>(fl + (uint32_t)(fr * g.cols + fc) * kFlowElem<FT>);
             }
         }
 #pragma unroll
@@ -527,15 +515,11 @@ __device__ __forceinline__ void walk_single(const ChaseGeo g, const uint32_t* li
                 unsigned long long bits = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)words[2 * e + 1]) << 32) |
                                           (uint32_t)__builtin_amdgcn_readfirstlane((int)words[2 * e]);
                 if (clear00 && yx == 0u) bits &= ~1ull;                 // mask_.at<uchar>(0,0) = 0
-                int px = (int)(yx & 0xFFFFu) + lane, py = (int)(yx >> 16);
-                if (W & 63) {
-                    if (px >= W) { px -= W; ++py; }
-                    if (px >= W) { px -= W; ++py; }
-                }
+                int px, py;
+                group_pixel(W, yx, lane, px, py);
                 float dx, dy;
-                if (FT == ROFT_FLOW_S16C2) { dx = (float)(short)(raw[u].x & 0xFFFFu); dy = (float)(short)(raw[u].x >> 16); }
-                else { dx = __uint_as_float(raw[u].x); dy = __uint_as_float(raw[u].y); }
-                if (MODE == 1) { dx *= g.inv_scale; dy *= g.inv_scale; }
+                flow_value<FT>(raw[u], dx, dy);
+                scale_flow<MODE>(g, dx, dy);
                 const float t_x = (float)px + dx, t_y = (float)py + dy;
                 const int ix = trunc_clamped(t_x), iy = trunc_clamped(t_y);
                 if (((bits >> lane) & 1ull) && (unsigned)ix < (unsigned)W && (unsigned)iy < (unsigned)H) tgt.hit(iy * W + ix);
@@ -559,18 +543,13 @@ __device__ __forceinline__ void walk_single_aligned(const ChaseGeo g, const uint
 {
     static_assert(MODE == 1 || MODE == 2, "power-of-two grid and scale");
     constexpr int NCH = kSingleWalks;
-    const ROFT_LDS uint32_t* const list = (const ROFT_LDS uint32_t*)(uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane(
-        (int)(uint32_t)(uintptr_t)(const ROFT_LDS uint32_t*)list_);
-    const ROFT_LDS uint32_t* const words = (const ROFT_LDS uint32_t*)(uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane(
-        (int)(uint32_t)(uintptr_t)(const ROFT_LDS uint32_t*)reinterpret_cast<const uint32_t*>(words_));
+    const ROFT_LDS uint32_t* const list = uniform_lds(list_);
+    const ROFT_LDS uint32_t* const words = uniform_lds(words_);
     const int W = g.W, H = g.H;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    constexpr uint32_t elem = (FT == ROFT_FLOW_S16C2) ? 4u : 8u;
+    constexpr uint32_t elem = kFlowElem<FT>;
     const int sh = (MODE == 2) ? 0 : __builtin_ctz((unsigned)g.grid);
-    const unsigned long long fl_bits = (unsigned long long)flow;
-    const ROFT_GLOBAL unsigned char* const fl = (const ROFT_GLOBAL unsigned char*)(
-        ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(fl_bits >> 32)) << 32) |
-        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)fl_bits));
+    const ROFT_GLOBAL unsigned char* const fl = uniform_global(flow);
     // per-lane constants
     const uint32_t lane_off = (uint32_t)(lane >> sh) * elem;          // the lane's flow element relative to the group's first
     const uint32_t m_lo = lane < 32 ? 1u << lane : 0u, m_hi = lane < 32 ? 0u : 1u << (lane - 32);   // the lane's bit of a group's two words
@@ -589,13 +568,7 @@ __device__ __forceinline__ void walk_single_aligned(const ChaseGeo g, const uint
                 const uint32_t yx = (uint32_t)__builtin_amdgcn_readlane((int)my_yx, u0 + u);
                 const uint32_t y0 = yx >> 16, x0 = yx & 0xFFFFu;
                 const uint32_t off = ((y0 >> sh) * (uint32_t)g.cols + (x0 >> sh)) * elem;   // (scalar unit)
-                const ROFT_GLOBAL unsigned char* p = fl + off;
-                if (FT == ROFT_FLOW_S16C2) {
-                    raw[u] = make_uint2(*(const ROFT_GLOBAL uint32_t*)(p + lane_off), 0u);
-                } else {
-                    const unsigned long long w = *(const ROFT_GLOBAL unsigned long long*)(p + lane_off);
-                    raw[u] = make_uint2((uint32_t)w, (uint32_t)(w >> 32));
-                }
+                raw[u] = flow_load<FT>(fl + off + lane_off);
             }
         }
 #pragma unroll
@@ -607,9 +580,8 @@ __device__ __forceinline__ void walk_single_aligned(const ChaseGeo g, const uint
                 if (clear00 && yx == 0u) lo &= ~1u;                      // mask_.at<uchar>(0,0) = 0
                 const float x0f = (float)(int)(yx & 0xFFFFu), y0f = (float)(int)(yx >> 16);   // (wave-uniform)
                 float dx, dy;
-                if (FT == ROFT_FLOW_S16C2) { dx = (float)(short)(raw[u].x & 0xFFFFu); dy = (float)(short)(raw[u].x >> 16); }
-                else { dx = __uint_as_float(raw[u].x); dy = __uint_as_float(raw[u].y); }
-                if (MODE == 1) { dx *= g.inv_scale; dy *= g.inv_scale; }
+                flow_value<FT>(raw[u], dx, dy);
+                scale_flow<MODE>(g, dx, dy);
                 const float t_x = (x0f + lane_f) + dx, t_y = y0f + dy;
                 const int ix = trunc_clamped(t_x), iy = trunc_clamped(t_y);
                 if ((((lo & m_lo) | (hi & m_hi)) != 0u) && (unsigned)ix < (unsigned)W && (unsigned)iy < (unsigned)H) tgt.hit(iy * W + ix);
@@ -716,17 +688,14 @@ __device__ __forceinline__ MaskRec decide_frame(const MaskRec& prev, const MaskR
 #define MTICK(i) do {} while (0)
 #endif
 
-#ifndef ROFT_MASK_WPE
-#define ROFT_MASK_WPE 4   // (experiments: 7 forces 72 registers -- and 36 bytes of scratch in the multi-flow walk)
-#endif
 template <int FT, int THREADS>
-__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(ROFT_MASK_WPE, 8)))
+__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 8)))   // (7 forces 72 registers -- and 36 bytes of scratch in the multi-flow walk)
 void mask_frame_kernel(EngineArrays a, int t, int frames_between, int flow_aided, int grp_per_wg, int margin, int win_cap)
 {
 #ifdef ROFT_MASK_PROFILE
     if (threadIdx.x == 0) atomicMax((unsigned long long*)&a.state[blockIdx.y].dbg[8], (unsigned long long)((1ll << 62) - wall_clock64()));
 #endif
-    ROFT_RESIDENT(a, THREADS == 128 ? RK_MASK_FRESH_EMPTY : RK_MASK_FRAME_EMPTY);
+    ROFT_RESIDENT(a, THREADS == kFreshThreads ? RK_MASK_FRESH_EMPTY : RK_MASK_FRAME_EMPTY);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ MaskShared S;
     __shared__ FrameCtrl s_c;
@@ -737,7 +706,7 @@ void mask_frame_kernel(EngineArrays a, int t, int frames_between, int flow_aided
     uint2* s_words = reinterpret_cast<uint2*>(s_list + THREADS);
     const int obj = blockIdx.y, q = blockIdx.x;
     const int W = a.cam.W, H = a.cam.H, wpr = a.cam.wpr, n_grp = (W * H) >> 6;
-    const int tid = threadIdx.x, lane = tid & 63;
+    const int tid = threadIdx.x;
     const int g0 = q * grp_per_wg, g1 = min(n_grp, g0 + grp_per_wg);
     // the band's rows + margin = the LDS window
     const int r_lo = max(0, (g0 * 64) / W - margin), r_hi = min(H - 1, (g1 * 64 - 1) / W + margin);
@@ -795,7 +764,7 @@ void mask_frame_kernel(EngineArrays a, int t, int frames_between, int flow_aided
     MTICK(6);
     const ChaseGeo geo = make_chase_geo(a.cam, a.ffmt);
     OrTarget tgt;
-    tgt.win = (ROFT_LDS uint32_t*)(uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(ROFT_LDS uint32_t*)s_win);
+    tgt.win = uniform_lds(s_win);
     tgt.off = win_off;
     tgt.words = win_words;
     tgt.dst = dst;
@@ -815,20 +784,15 @@ void mask_frame_kernel(EngineArrays a, int t, int frames_between, int flow_aided
             __syncthreads();
         }
         MTICK(7);
-        const bool ne = ww != 0ull;
-        const unsigned long long b = __ballot(ne);
-        int base = 0;
-        if (lane == 0 && b) base = atomicAdd(&S.n_list, __popcll(b));
-        base = __shfl(base, 0, 64);
-        if (ne) {
-            const int e = base + __popcll(b & ((1ull << lane) - 1ull));
-            const int p0 = g * 64, y0 = p0 / W;
-            s_list[e] = ((uint32_t)y0 << 16) | (uint32_t)(p0 - y0 * W);
+        const ListSlot slot = list_reserve(S.n_list, ww != 0ull);
+        if (ww != 0ull) {
+            const int e = slot.entry();
+            s_list[e] = group_entry(g, W);
             s_words[e] = make_uint2((uint32_t)ww, (uint32_t)(ww >> 32));
         }
         __syncthreads();
         MTICK(1);
-        if (S.n_list > 0) ROFT_RESIDENT_AS(a, THREADS == 128 ? RK_MASK_FRESH : RK_MASK_FRAME);
+        if (S.n_list > 0) ROFT_RESIDENT_AS(a, THREADS == kFreshThreads ? RK_MASK_FRESH : RK_MASK_FRAME);
         propagate_binary<FT, THREADS / 64>(geo, plane2, s_list, S.n_list, r.n_flows, r.mode == 1, S.flows, tgt, s_words);
     }
     __syncthreads();
@@ -895,14 +859,8 @@ __global__ __launch_bounds__(kMaskThreads) void mask_general_kernel(EngineArrays
                     const int g = g0 + tid;
                     bool ne = false;
                     if (g < c1) { const uint2 w = plane2[g]; ne = (w.x | w.y) != 0u; }
-                    const unsigned long long b = __ballot(ne);
-                    int base = 0;
-                    if (lane == 0 && b) base = atomicAdd(&S.n_list, __popcll(b));
-                    base = __shfl(base, 0, 64);
-                    if (ne) {
-                        const int p0 = g * 64, y0 = p0 / W;
-                        s_list[base + __popcll(b & ((1ull << lane) - 1ull))] = ((uint32_t)y0 << 16) | (uint32_t)(p0 - y0 * W);
-                    }
+                    const ListSlot slot = list_reserve(S.n_list, ne);
+                    if (ne) { const uint32_t yx = group_entry(g, W); s_list[slot.entry()] = yx; }
                 }
                 __syncthreads();
                 propagate_general<FT, kMaskWaves>(make_chase_geo(a.cam, a.ffmt), plane2, s_list, S.n_list, r.n_flows, r.mode == 1, S.flows, map, S.bbox);
@@ -944,55 +902,48 @@ int launch_mask_chain(const EngineArrays& a, int frames_between, int flow_aided,
     // (walk_single) -- and a third of that on frames that deliver a mask (the schedule tells the host which: the new mask is
     // chased through up to 30 flows, a chain of dependent reads per group).  roft_config::mask_workgroups_per_object = S > 0
     // splits the plane into exactly S bands instead (1: one workgroup walks the whole object, chunk by chunk).
-    static const int rows_env = getenv("ROFT_MASK_ROWS") ? atoi(getenv("ROFT_MASK_ROWS")) : 0;           // (experiments)
-    static const int rows_new_env = getenv("ROFT_MASK_ROWS_NEW") ? atoi(getenv("ROFT_MASK_ROWS_NEW")) : 0;
-    const int rows_auto = rows_env > 0 ? rows_env : 20, rows_auto_new = rows_new_env > 0 ? rows_new_env : 6;
+    constexpr int kBandRows = 20, kBandRowsFresh = 6;   // (both swept twice against their neighbours: docs/notebook.md)
     auto per_for = [&](bool fresh) {
         if (a.mask_wgs > 0) return (n_grp + a.mask_wgs - 1) / a.mask_wgs;
-        const int per = std::max(1, (fresh ? rows_auto_new : rows_auto) * a.cam.W / 64);
+        const int per = std::max(1, (fresh ? kBandRowsFresh : kBandRows) * a.cam.W / 64);
         return std::min(per, n_grp);
     };
     const size_t lds_cap = 160 * 1024 - 4096;   // (the kernel's static LDS -- control block, records, flow pointers -- is ~1.3 KB)
-    {
-        (void)set_max_dynamic_lds(reinterpret_cast<const void*>(mask_frame_kernel<ROFT_FLOW_S16C2, kFrameThreads>), (int)lds_cap);
-        (void)set_max_dynamic_lds(reinterpret_cast<const void*>(mask_frame_kernel<ROFT_FLOW_F32C2, kFrameThreads>), (int)lds_cap);
-        (void)set_max_dynamic_lds(reinterpret_cast<const void*>(mask_frame_kernel<ROFT_FLOW_S16C2, 128>), (int)lds_cap);
-        (void)set_max_dynamic_lds(reinterpret_cast<const void*>(mask_frame_kernel<ROFT_FLOW_F32C2, 128>), (int)lds_cap);
-    }
+    // the instantiations, each named once: the kernel for a flow format (and a workgroup size)
+    auto frame_kernel = [](bool s16, int threads) {
+        if (threads == kFrameThreads) return s16 ? mask_frame_kernel<ROFT_FLOW_S16C2, kFrameThreads> : mask_frame_kernel<ROFT_FLOW_F32C2, kFrameThreads>;
+        return s16 ? mask_frame_kernel<ROFT_FLOW_S16C2, kFreshThreads> : mask_frame_kernel<ROFT_FLOW_F32C2, kFreshThreads>;
+    };
+    auto general_kernel = [](bool s16) { return s16 ? mask_general_kernel<ROFT_FLOW_S16C2> : mask_general_kernel<ROFT_FLOW_F32C2>; };
+    for (int threads : {kFrameThreads, kFreshThreads})
+        for (bool f16 : {true, false}) (void)set_max_dynamic_lds(reinterpret_cast<const void*>(frame_kernel(f16, threads)), (int)lds_cap);
     int launches = 0;
     const bool s16 = a.ffmt.type == ROFT_FLOW_S16C2;
     // the frames of objects with three-valued masks (none, normally): one workgroup per object behind the frame kernels
     auto launch_general = [&](hipEvent_t ev, int final_launch) {
         const size_t lds_gen = ((size_t)std::min(n_grp, kGeneralList) * 4 + 15) & ~(size_t)15;
-        (void)set_max_dynamic_lds(reinterpret_cast<const void*>(mask_general_kernel<ROFT_FLOW_S16C2>), kGeneralList * 4 + 16);
-        (void)set_max_dynamic_lds(reinterpret_cast<const void*>(mask_general_kernel<ROFT_FLOW_F32C2>), kGeneralList * 4 + 16);
-        if (s16)
-            hipExtLaunchKernelGGL(mask_general_kernel<ROFT_FLOW_S16C2>, dim3(a.n_obj), dim3(kMaskThreads), (uint32_t)lds_gen, s, nullptr, ev, 0, a, final_launch);
-        else
-            hipExtLaunchKernelGGL(mask_general_kernel<ROFT_FLOW_F32C2>, dim3(a.n_obj), dim3(kMaskThreads), (uint32_t)lds_gen, s, nullptr, ev, 0, a, final_launch);
+        for (bool f16 : {true, false}) (void)set_max_dynamic_lds(reinterpret_cast<const void*>(general_kernel(f16)), kGeneralList * 4 + 16);
+        hipExtLaunchKernelGGL(general_kernel(s16), dim3(a.n_obj), dim3(kMaskThreads), (uint32_t)lds_gen, s, nullptr, ev, 0, a, final_launch);
     };
     for (int t = 0; t < a.T; ++t) {
         const bool fresh = (new_mask_frames >> t) & 1u;
         const int per = per_for(fresh);
         // LDS window: the band's rows + a margin of rows above and below (pixels that fly further are ORed into the
         // destination plane directly): 16 rows for one flow step, 48 when a new mask is chased through several
-        const int margin = fresh ? 48 : 16;
+        constexpr int kMargin = 16, kMarginFresh = 48;
+        const int margin = fresh ? kMarginFresh : kMargin;
         // Workgroups of TWO waves on a frame that delivers a mask: its 80 bands x n_obj workgroups exceed what the device holds at once
         // (seven per CU by wave slots at four waves: the last one starts 33 us after the first), more than half of them find no
         // pixel and leave after one round trip, and the others chase their groups through six flows -- six dependent round trips
         // whatever the number of waves.  Half the waves per workgroup = twice the workgroups in flight: +1 - 3 % in runs of 60 steps
-        // and more, nothing in a 20-frame burst.  (ROFT_MASK_FRESH_THREADS=256: four waves as on every other frame.)
-        static const int fresh_threads_env = getenv("ROFT_MASK_FRESH_THREADS") ? atoi(getenv("ROFT_MASK_FRESH_THREADS")) : 128;
-        const int threads = (fresh && fresh_threads_env == 128 && kFrameThreads > 128) ? 128 : kFrameThreads;
+        // and more, nothing in a 20-frame burst.  (kFreshThreads = 128, next to kFrameThreads.)
+        const int threads = fresh ? kFreshThreads : kFrameThreads;
         const size_t fixed = (size_t)threads * 12;
         size_t win_cap = ((size_t)std::min(a.cam.H, (per * 64 + a.cam.W - 1) / a.cam.W + 1 + 2 * margin) * a.cam.wpr + 1) & ~(size_t)1;
         win_cap = std::min(win_cap, ((lds_cap - fixed) / 4) & ~(size_t)1);
         const size_t lds = win_cap * 4 + fixed;
         const dim3 grid((n_grp + per - 1) / per, a.n_obj);
-        auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(threads), (uint32_t)lds, s, a, t, frames_between, flow_aided, per, margin, (int)win_cap); };
-        if (threads == 128) { if (s16) go(mask_frame_kernel<ROFT_FLOW_S16C2, 128>); else go(mask_frame_kernel<ROFT_FLOW_F32C2, 128>); }
-        else if (s16) go(mask_frame_kernel<ROFT_FLOW_S16C2, kFrameThreads>);
-        else go(mask_frame_kernel<ROFT_FLOW_F32C2, kFrameThreads>);
+        hipLaunchKernelGGL(frame_kernel(s16, threads), grid, dim3(threads), (uint32_t)lds, s, a, t, frames_between, flow_aided, per, margin, (int)win_cap);
         ++launches;
         // `stop_early`: the masks up to the batch's LAST BUT ONE frame are complete -- all that the flow measurements of the batch
         // read (frame t measures inside the mask of frame t - 1); the three-valued frames so far are brought up to date for it

@@ -85,18 +85,6 @@ struct ArrayAccessor {
     }
 };
 
-// innovation component k (flat index into the 2N vector) at the predicted mean
-template <class Acc>
-__device__ __forceinline__ double innov_at(const Acc& acc, int k, const double* x)
-{
-    double h[12], y[2];
-    acc.get(k >> 1, h, y);
-    const double* hr = h + 6 * (k & 1);
-    double pred = 0.0;
-    for (int i = 0; i < 6; ++i) pred += hr[i] * x[i];
-    return -(pred - y[k & 1]);
-}
-
 // One workgroup of eight waves per object.  A frame has 700 - 3 000 flow points (640x480 - 1280x720): more waves
 // shorten the passes over the points (a handful of dependent operations per point and thread) but lengthen every
 // reduction and barrier between them.  Measured per frame, chains overlapping: 256 threads 23 / 68 us

@@ -542,16 +542,6 @@ __device__ void quaternion_mean(const double* Y, int qrow, int ncols, double wm0
     for (int i = 0; i < 4; ++i) out[i] = L.w4[i];
 }
 
-// C (ra x rb, leading dim ldc) = A diag(w) B'
-__device__ void weighted_outer(const double* A, int ra, const double* B, int rb, int ncols, double wc0, double wci,
-                               double* C, int ldc)
-{
-    for (int e = threadIdx.x; e < ra * rb; e += kUkfThreads) {
-        const int i = e / rb, j = e % rb;
-        C[i * ldc + j] = weighted_dot(A + i * kCols, B + j * kCols, ncols, wc0, wci);
-    }
-}
-
 // lane SRC of every row of 16 lanes -> all lanes of the row: DPP row_newbcast (gfx90a+).  Two 32-bit DPP moves per double: no
 // SGPR round trip and no hazard wait states as with v_readlane (two of them + an s_nop per use).  (v_fmac_f64_dpp takes the
 // control directly -- one instruction per update -- and is no faster: measured, DESIGN.md App. A.)

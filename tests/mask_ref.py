@@ -194,8 +194,8 @@ class Source:
 # what the launches look like (launch_mask_chain in roft_amd/csrc/k_mask.hip): used by aim() only
 # ---------------------------------------------------------------------------------------------
 Launch = namedtuple("Launch", "band_rows margin threads")
-ORDINARY = Launch(20, 16, 256)       # a frame that delivers no mask: rows_auto, margin, kFrameThreads
-DELIVERING = Launch(6, 48, 128)      # a frame on which some object receives a mask: rows_auto_new, margin, two waves
+ORDINARY = Launch(20, 16, 256)       # a frame that delivers no mask: kBandRows, kMargin, kFrameThreads
+DELIVERING = Launch(6, 48, 128)      # a frame on which some object receives a mask: kBandRowsFresh, kMarginFresh, kFreshThreads
 LDS_CAP = 160 * 1024 - 4096          # lds_cap; a workgroup's list and plane words take 12 bytes per thread of it
 SINGLE_WALKS = 12                    # kSingleWalks: groups per wave whose flow loads are in flight together
 MAX_FLOW_CHASE = 30                  # ROFT_MAX_FLOW_CHASE
