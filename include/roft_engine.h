@@ -700,6 +700,54 @@ int roft_track_quality(const roft_camera* cam, int divider, const float* depth, 
                        const double x[3], const double q[4], float depth_tolerance, double depth_maximum, int window_pixels,
                        roft_quality_record* out);
 
+/* ---- (3e) masks from poses: the silhouette of a delivered pose as the frame's mask ---------------------------------------- *
+ * A caller with a pose estimator and a mesh but no segmentation network (DOPE, the reference's own pose source, delivers no masks)
+ * enrols its objects, and the engine draws the mask itself, on the device, from what the submit call was handed: the object's mesh
+ * is resident, the pose travels with the frame.  The equivalence below DEFINES the feature.
+ *
+ * roft_engine_enable_pose_masks(e, obj_ids, n_ids): after the objects it names were added, before the first frame.  n_ids == 0
+ * (obj_ids may be NULL) enrols every object the engine has at its first frame.  It may be called more than once; the sets add up.
+ *
+ * For an enrolled object and a frame whose entry has mask == NULL and names no label image:
+ *  - if inputs[].pose_valid, the engine behaves BIT FOR BIT as if inputs[].mask had been a HOST buffer holding
+ *        M(p) = roft_render_depth(mesh, pose_x, pose_q, cam, 1)(p) > 0 ? 255 : 0
+ *    -- the render contract at FULL resolution (divider 1), pose_q exactly as submitted (not normalised), the back-face rule for
+ *    closed meshes (a closed mesh is drawn whole as soon as one vertex is not in front of the near plane), and a pixel counts only
+ *    if its computed z > 0.  Whether roft_config::use_pose lets the filter use the pose does not matter;
+ *  - on the object's FIRST frame without pose_valid the pose is roft_object_desc::p_mean0[6..12] (the reference initialises from
+ *    the first detection);
+ *  - otherwise no mask is delivered on that frame.
+ * Everything downstream is what it is for a delivered mask: the first-mask rule; the "new but empty mask is ignored" rule
+ * (ImageSegmentationOFAidedSource.hpp:186-198) for a pose off-screen or behind the camera; the chase through the last
+ * mask_frames_between buffered flows -- a pose computed on an older image is chased like a delayed network mask, so a delayed pose
+ * source wants mask_frames_between == pose_frames_between --; features, outlier test, quality records, roft_get_mask.
+ * A delivered mask or label image takes precedence on any frame, so network masks and silhouettes may alternate for one object;
+ * enrolled objects, plain-mask objects and label-image objects mix within one frame.  An object added without a mesh has an empty
+ * silhouette; with n_ids == 0 such objects are not enrolled.
+ *
+ * LIMIT.  The silhouette is drawn from the pose MEASUREMENT, before any filtering: an outlier pose (the reference's data has them,
+ * 30 degrees off) yields a wrong mask until the next pose arrives.  The UKF's outlier rejection protects the estimate, not the mask.
+ * Objects do not occlude each other's silhouettes, and nothing is dilated.
+ *
+ * Refused on the host, with nothing consumed and the reason in roft_last_error_string: ROFT_ERR_STATE after the first frame;
+ * ROFT_ERR_INVALID for an id that is not an object of the engine, for an object added without a mesh, for an engine with
+ * stamped_masks (a pose carries no stamp), and for an engine with render_mode == ROFT_RENDER_GL (its meshes are uploaded without
+ * the flip bits of the back-face rule: the defining render does not exist there).
+ *
+ * roft_pose_silhouette: the same kernel on HOST buffers, device 0: mask_out H x W bytes {0, 255} (optional), count_out the number
+ * of set pixels (optional).  bands: workgroups (bands of image rows) the image is split into, 0 = the library's choice;
+ * vertex_cache: 1 = the projected vertices are kept in LDS where the mesh fits, 0 = projected per triangle.  Neither changes a
+ * bit (the result is an order-free OR).  ROFT_ERR_INVALID before any device is looked for: a NULL camera, mesh, x or q, bands < 0,
+ * a vertex_cache that is neither 0 nor 1, a triangle that names a vertex outside the vertex array. */
+typedef struct {
+    long long silhouettes;   /* (frame, object) pairs whose mask the engine drew */
+    long long frames;        /* frames in which it drew at least one */
+} roft_engine_pose_mask_stats;
+int roft_engine_enable_pose_masks(roft_engine* e, const int* obj_ids, int n_ids);
+int roft_engine_get_pose_mask_stats(roft_engine* e, roft_engine_pose_mask_stats* out);
+int roft_pose_silhouette(const roft_camera* cam, const roft_mesh* mesh, const double x[3], const double q[4], int bands, int vertex_cache,
+                         uint8_t* mask_out, int* count_out);
+
 /* ---- (3b) scene renderer: tracked poses drawn over the camera frames ----------------------------------------------
  * The reference's evaluation draws the mesh at every estimated pose over the grayed camera frame (evaluation/results_renderer.py:
  * 591-778 through tools/object_renderer/src/renderer.cpp).  This is that stage for many frames and several objects per frame:
@@ -797,6 +845,10 @@ int roft_debug_depth_kernel_ms(roft_engine* e, double* ms_out);
 /* device time in milliseconds (the HIP events bound to its dispatch) of the engine's last quality launch (section 3d); waits for it.
  * ROFT_ERR_STATE when there was none. */
 int roft_debug_quality_kernel_ms(roft_engine* e, double* ms_out);
+/* device time in milliseconds (the HIP events bound to its dispatch) of the engine's last silhouette launch (section 3e); waits for it.
+ * ROFT_ERR_STATE: no launch so far, or the last one ended with the preparation's own event (a steady batch of a full device outside
+ * roft_engine_enable_timing), which takes no time stamps. */
+int roft_debug_pose_mask_kernel_ms(roft_engine* e, double* ms_out);
 /* phase counters of one object's last kernels (only filled by libraries built with a -DROFT_*_PROFILE switch) */
 int roft_debug_get_dbg(roft_engine* e, int obj_id, long long out[32]);
 

@@ -115,6 +115,10 @@ class QualityParams(C.Structure):
     _fields_ = [("every", C.c_int), ("depth_tolerance", C.c_float)]
 
 
+class EnginePoseMaskStats(C.Structure):
+    _fields_ = [("silhouettes", C.c_longlong), ("frames", C.c_longlong)]
+
+
 class EngineStats(C.Structure):
     _fields_ = [("frames", C.c_longlong), ("batches", C.c_longlong), ("launches", C.c_longlong),
                 ("event_ops", C.c_longlong), ("h2d_bytes", C.c_longlong), ("h2d_copies", C.c_longlong)]
@@ -164,6 +168,7 @@ ABI_SYMBOLS = [
     "roft_engine_enable_raw_depth", "roft_engine_get_depth", "roft_engine_get_depth_stats", "roft_depth_convert", "roft_depth_align",
     "roft_debug_depth_kernel_ms",
     "roft_default_quality_params", "roft_engine_enable_quality", "roft_engine_get_quality", "roft_track_quality", "roft_debug_quality_kernel_ms",
+    "roft_engine_enable_pose_masks", "roft_engine_get_pose_mask_stats", "roft_pose_silhouette", "roft_debug_pose_mask_kernel_ms",
 ]
 POSE_ERROR_ADD, POSE_ERROR_ADDS = 0, 1   # ROFT_POSE_ERROR_*
 # entry points younger than ABI version 2 itself: a library built before them still loads through ROFT_LIB_SO
@@ -171,7 +176,8 @@ NEWER_SYMBOLS = ("roft_pose_errors", "roft_engine_score_log", "roft_scene_render
                  "roft_render_scene", "roft_frames_submit_labels", "roft_labels_to_masks",
                  "roft_engine_enable_flow", "roft_frames_submit_images", "roft_engine_get_flow", "roft_engine_get_flow_stats", "roft_image_to_gray",
                  "roft_engine_enable_raw_depth", "roft_engine_get_depth", "roft_engine_get_depth_stats", "roft_depth_convert", "roft_depth_align",
-                 "roft_default_quality_params", "roft_engine_enable_quality", "roft_engine_get_quality", "roft_track_quality")
+                 "roft_default_quality_params", "roft_engine_enable_quality", "roft_engine_get_quality", "roft_track_quality",
+                 "roft_engine_enable_pose_masks", "roft_engine_get_pose_mask_stats", "roft_pose_silhouette")
 
 
 def build(force=False):
@@ -291,6 +297,11 @@ def lib():
         L.roft_track_quality.argtypes = [C.POINTER(Camera), C.c_int, vp, vp, C.POINTER(Mesh), vp, vp, C.c_float, C.c_double, C.c_int,
                                          C.POINTER(QualityRecord)]
         L.roft_debug_quality_kernel_ms.argtypes = [vp, dp]
+    if hasattr(L, "roft_pose_silhouette"):
+        L.roft_engine_enable_pose_masks.argtypes = [vp, ip, C.c_int]
+        L.roft_engine_get_pose_mask_stats.argtypes = [vp, C.POINTER(EnginePoseMaskStats)]
+        L.roft_pose_silhouette.argtypes = [C.POINTER(Camera), C.POINTER(Mesh), vp, vp, C.c_int, C.c_int, vp, ip]
+        L.roft_debug_pose_mask_kernel_ms.argtypes = [vp, dp]
     for name in ABI_SYMBOLS:
         if (name.startswith("roft_debug_") or name in NEWER_SYMBOLS) and not hasattr(L, name):
             continue   # (an older build loaded through ROFT_LIB_SO for an A/B run: diagnostics and the pose errors only; tests/test_abi_cpu.py checks the in-tree library has them all)

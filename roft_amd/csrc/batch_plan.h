@@ -62,6 +62,7 @@ struct SubmitFacts {
     bool produced_flows = false;
     unsigned plain_mask_frames = 0; // bit t: frame t delivers a per-object byte mask (what the ingest of the control-block launch converts)
     int label_sets = 0;             // distinct (frame, label image) pairs of the batch: masks delivered as label images
+    int pose_masks = 0;             // (frame, object) pairs of the batch whose mask is the silhouette of a delivered pose (masks from poses)
     bool any_feat = false, any_feat_now = false;
     bool feat_dep_in_batch = false; // an outlier test of the batch reads features buffered by a frame of the same batch
     int n_segments[kPlanLanes] = {1, 1};          // pose chain segments per lane (1 + outlier tests of the busiest object)
@@ -129,7 +130,8 @@ struct BatchPlan {
     bool prep_waits_mask = false, prep_waits_feat = false;   // ... behind ev_mask (and ev_feat) of batch b - 2
     bool wait_up = false;       // the mask stream waits for ev_up
     bool try_fused = false;     // control blocks + ingest in one launch, if the launcher accepts
-    bool label_ingest = false;  // one more launch behind them: every label image of the batch, all of its objects (the preparation's last)
+    bool label_ingest = false;  // one more launch behind them: every label image of the batch, all of its objects
+    bool pose_silhouettes = false;   // one more launch behind those: every silhouette of the batch (the preparation's last launch is the last of these that exists)
     Signal ev_ctrl = Signal::none, ev_prep = Signal::none;
     // mask frames and features
     bool part_gate = false;     // the mask chain signals ev_part with the masks of frames 0 .. T - 2
@@ -230,7 +232,12 @@ BatchPlan plan_batch(const PlanInputs& in, AloneFn&& alone)
     // control blocks (it reads the table that travels with them) and whatever ingest there is of per-object masks; a batch
     // without label images enqueues what it always did.
     p.label_ingest = in.label_sets > 0;
-    p.ev_prep = !p.prep ? Signal::none : (full || (in.plain_mask_frames == 0 && !p.label_ingest)) ? Signal::record : Signal::stop;   // (no ingest: no kernel to end with it)
+    // Masks from poses: ONE launch for every silhouette of the batch, in the same place and by the same rule -- it reads the control
+    // blocks (the poses travel in them) and the resident meshes, nothing the batch computes: on the upload stream when the
+    // preparation runs ahead.  A batch without silhouettes enqueues what it always did.
+    p.pose_silhouettes = in.pose_masks > 0;
+    p.ev_prep = !p.prep ? Signal::none
+                : (full || (in.plain_mask_frames == 0 && !p.label_ingest && !p.pose_silhouettes)) ? Signal::record : Signal::stop;   // (no ingest: no kernel to end with it)
 
     // In a burst the velocity chain is released when the masks its flow measurements read are complete -- frames 0 .. T - 2: the
     // measurement of frame t is taken inside the mask of frame t - 1 --, one mask frame (the one that chases a delivered mask

@@ -668,6 +668,7 @@ int roft_object_add(roft_engine* e, const roft_object_desc* d, int* obj_id)
     if (err != hipSuccess) return bail(ROFT_ERR_DEVICE, std::string("state upload: ") + hipGetErrorString(err));
     e->arr.a.max_tris = std::max(e->arr.a.max_tris, d->mesh.n_tris);
     e->arr.a.max_verts = std::max(e->arr.a.max_verts, d->mesh.n_verts);
+    for (int i = 0; i < 7; ++i) o->pose0[i] = d->p_mean0[6 + i];
     e->objs.push_back(o);
     e->arr.a.n_obj = (int)e->objs.size();
     if (obj_id) *obj_id = id;

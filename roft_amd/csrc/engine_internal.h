@@ -277,6 +277,10 @@ struct HostObject {
     DevBuf<float> verts;
     DevBuf<int32_t> tris;
     DevBuf<uint8_t> tri_flip;   // closed meshes only (mesh_class.h)
+    // masks from poses (roft_engine_enable_pose_masks): the object is enrolled; the pose of roft_object_desc::p_mean0 (x, q = w x y z),
+    // which stands in for a first frame that brings none
+    bool pose_masks = false;
+    double pose0[7] = {0, 0, 0, 1, 0, 0, 0};
     ~HostObject() { for (auto* o : owned) delete o; }
 };
 
@@ -324,6 +328,24 @@ struct EngineDepth {
     {
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
+    }
+};
+
+// Masks from poses on the engine (roft_engine_enable_pose_masks): enrolled objects take the silhouette of a delivered pose as the
+// frame's mask where no mask and no label image arrives.  One launch per delivering batch, part of its preparation (engine_step.hip).
+// The launch's events live here, one pair per slot of the batch ring; where the plan ends the preparation with the launch's stop
+// event (ev_prep of the batch slot, which takes no time stamps) the launch is not timed.
+struct EnginePoseMasks {
+    bool enabled = false;
+    bool all = false;                    // n_ids == 0: every object the engine has at its first frame (and a mesh)
+    roft_engine_pose_mask_stats stats{};
+    hipEvent_t ev_start[8] = {}, ev_stop[8] = {};
+    int last_slot = -1;                  // batch-ring slot of the last launch
+    bool last_timed = false;             // ... and whether it ended with ev_stop of that slot
+    ~EnginePoseMasks()
+    {
+        for (hipEvent_t ev : ev_start) if (ev) (void)hipEventDestroy(ev);
+        for (hipEvent_t ev : ev_stop) if (ev) (void)hipEventDestroy(ev);
     }
 };
 
@@ -402,6 +424,8 @@ struct PendingBatch {
     std::vector<LabelSet> label_sets;  // (facts.label_sets counts them)
     std::vector<std::vector<LabelMember>> label_members;   // per set
     size_t label_table_bytes = 0;
+    // masks from poses: bit t: some enrolled object's mask of frame t is the silhouette of its pose (facts.pose_masks counts the pairs)
+    unsigned pose_mask_frames = 0;
     std::vector<FlowFrameJobs> flow_jobs;   // [T] camera images: what enqueue_flow_production enqueues, frame by frame
     std::vector<DepthJob> depth_jobs;       // raw depth: what enqueue_depth_production enqueues
     // Small HOST images in PINNED memory (the per-object masks of a delivery: 64 buffers of 300 KB) are not copied one
@@ -414,7 +438,7 @@ struct PendingBatch {
     {
         facts = SubmitFacts{};
         facts.T = T;
-        feat_frames = new_mask_frames = 0;
+        feat_frames = new_mask_frames = pose_mask_frames = 0;
         label_sets.clear();
         label_members.clear();
         label_table_bytes = 0;
@@ -498,6 +522,7 @@ struct roft_engine {
     EngineFlow flow;                       // camera images -> flows (roft_engine_enable_flow)
     EngineDepth depth;                     // raw sensor depth -> float depth (roft_engine_enable_raw_depth); its products ride on SubmitFacts::produced_flows
     EngineQuality quality;                 // track quality (roft_engine_enable_quality)
+    EnginePoseMasks pose_masks;            // masks from poses (roft_engine_enable_pose_masks)
     int prev_T = 0;                 // frames of the batch stepped before
     int batch_counter = 0, frame_counter = 0;
     int completed_batches = 0, completed_frames = 0;

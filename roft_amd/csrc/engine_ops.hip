@@ -383,6 +383,89 @@ int roft_labels_to_masks(const void* labels, int label_type, int W, int H, const
     return ROFT_OK;
 }
 
+// Masks from poses, stand-alone: the engine's silhouette kernel on a compact layout -- one object, one ingest slot, one frame.
+int roft_pose_silhouette(const roft_camera* cam, const roft_mesh* mesh, const double x[3], const double q[4], int bands, int vertex_cache,
+                         uint8_t* mask_out, int* count_out)
+{
+    if (!cam || !mesh || !x || !q) return fail(ROFT_ERR_INVALID, "null argument");
+    if (bands < 0) return fail(ROFT_ERR_INVALID, "bands must be >= 0 (0: the library's choice)");
+    if (vertex_cache != 0 && vertex_cache != 1) return fail(ROFT_ERR_INVALID, "vertex_cache must be 0 or 1");
+    const bool has_mesh = mesh->n_verts > 0 && mesh->n_tris > 0;
+    if (has_mesh && (!mesh->verts || !mesh->tris)) return fail(ROFT_ERR_INVALID, "mesh: null vertex or triangle array");
+    if (has_mesh)
+        for (size_t i = 0; i < (size_t)3 * mesh->n_tris; ++i)
+            if (mesh->tris[i] < 0 || mesh->tris[i] >= mesh->n_verts) return fail(ROFT_ERR_INVALID, "mesh: a triangle refers to a vertex outside the vertex array");
+    if (roft_device_count() <= 0) return fail(ROFT_ERR_DEVICE, "no HIP device (libroft_hip has no CPU path)");
+    if (int rc = check_geometry(cam->width, cam->height)) return rc;
+    OpCtx& c = op();
+    std::lock_guard<std::mutex> lk(c.mu);
+    HIP_TRY(hipSetDevice(0));
+    (void)hipGetLastError();
+    if (!c.stream) HIP_TRY(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
+    const DevCamera dc = make_cam(*cam);
+    const size_t npix = (size_t)cam->width * cam->height, plane_words = (size_t)dc.wpr * dc.H;
+    DevBuf<unsigned char> d_verts, d_tris, d_flip, d_mask;
+    DevBuf<uint32_t> d_planes;
+    DevBuf<MaskRec> d_rec;
+    DevBuf<FrameCtrl> d_ctrl;
+    DevBuf<ObjParams> d_prm;
+    ObjParams prm;
+    std::memset(&prm, 0, sizeof(prm));
+    PreparedMesh pm;
+    if (has_mesh) {
+        prepare_mesh(mesh->verts, mesh->n_verts, mesh->tris, mesh->n_tris, pm);
+        if (int rc = to_dev(d_verts, mesh->verts, (size_t)3 * mesh->n_verts, c.stream)) return rc;
+        if (int rc = to_dev(d_tris, pm.tris(mesh->tris), (size_t)3 * mesh->n_tris, c.stream)) return rc;
+        if (pm.closed)
+            if (int rc = to_dev(d_flip, pm.flip.data(), (size_t)mesh->n_tris, c.stream)) return rc;
+        prm.verts = reinterpret_cast<const float*>(d_verts.p);
+        prm.tris = reinterpret_cast<const int32_t*>(d_tris.p);
+        prm.tri_flip = pm.closed ? reinterpret_cast<const uint8_t*>(d_flip.p) : nullptr;
+        prm.n_verts = mesh->n_verts;
+        prm.n_tris = mesh->n_tris;
+    }
+    FrameCtrl fc;
+    clear_ctrl(fc);
+    fc.has_new_mask = 1;
+    fc.label_type = kMaskFromPose;
+    for (int i = 0; i < 3; ++i) fc.pose_x[i] = x[i];
+    for (int i = 0; i < 4; ++i) fc.pose_q[i] = q[i];
+    HIP_TRY(d_ctrl.ensure(1));
+    HIP_TRY(d_prm.ensure(1));
+    HIP_TRY(d_planes.ensure(2 * plane_words));
+    HIP_TRY(d_rec.ensure(2));
+    HIP_TRY(hipMemcpyAsync(d_ctrl.p, &fc, sizeof(fc), hipMemcpyHostToDevice, c.stream));
+    HIP_TRY(hipMemcpyAsync(d_prm.p, &prm, sizeof(prm), hipMemcpyHostToDevice, c.stream));
+    HIP_TRY(hipMemsetAsync(d_planes.p, 0xA5, sizeof(uint32_t) * 2 * plane_words, c.stream));   // (stale words, as an engine's ingest slot holds)
+    HIP_TRY(hipMemsetAsync(d_rec.p, 0, sizeof(MaskRec) * 2, c.stream));
+    SilhouetteArgs sa{};
+    sa.ctrl = d_ctrl.p;
+    sa.params = d_prm.p;
+    sa.planes = d_planes.p;
+    sa.plane_words = plane_words;
+    sa.obj_stride = 2 * plane_words;
+    sa.slot0 = 0;
+    sa.mrec = d_rec.p;
+    sa.n_obj = 1;
+    sa.W = dc.W; sa.H = dc.H; sa.wpr = dc.wpr;
+    sa.fx = (float)dc.fx; sa.fy = (float)dc.fy; sa.cx = (float)dc.cx; sa.cy = (float)dc.cy;   // (divider 1: the camera as it is)
+    sa.frames_packed = 0u;
+    if (!launch_pose_silhouette(sa, 1, prm.n_verts, bands, vertex_cache, c.stream))
+        return fail(ROFT_ERR_INVALID, "pose silhouette: an image row is wider than the kernel's bit window");
+    HIP_TRY(hipGetLastError());
+    if (mask_out) {
+        HIP_TRY(d_mask.ensure(npix));
+        launch_planes_to_mask(d_planes.p, d_planes.p + plane_words, (int)npix, d_mask.p, c.stream);
+        HIP_TRY(hipMemcpyAsync(mask_out, d_mask.p, npix, hipMemcpyDeviceToHost, c.stream));
+    }
+    MaskRec rec[2];
+    HIP_TRY(hipMemcpyAsync(rec, d_rec.p, sizeof(rec), hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));   // (fc, prm and rec live on this stack)
+    HIP_TRY(hipGetLastError());
+    if (count_out) *count_out = rec[1].new_count;   // (row t + 1 = 1)
+    return ROFT_OK;
+}
+
 int roft_pose_process_noise(const double psd[3], const double sig_w[3], double T, double Q[81])
 {
     if (!psd || !sig_w || !Q) return fail(ROFT_ERR_INVALID, "null argument");

@@ -150,7 +150,8 @@ static int enqueue_preparation(Enqueue& q)
     // (the label table of the batch lies behind its control blocks and is copied with them)
     const size_t n16 = (sizeof(FrameCtrl) * (size_t)a.n_obj * a.T + (p.label_ingest ? pb.label_table_bytes : 0)) / 16;
     const hipEvent_t ctrl_stop = Enqueue::stop(p.ev_ctrl, q.cur.ev_ctrl);
-    // masks delivered as label images: one launch, the preparation's last (it ends with ev_prep where the plan has one)
+    // masks delivered as label images: one launch behind the per-object ingest (it ends with ev_prep where the plan has one and no
+    // silhouette launch follows)
     auto label_ingest = [&]() -> int {
         LabelIngestArgs la;
         la.sets = reinterpret_cast<const LabelSet*>(a.ctrl + (size_t)a.n_obj * a.T);
@@ -162,15 +163,46 @@ static int enqueue_preparation(Enqueue& q)
         la.mrec = a.mrec;
         la.n_obj = a.n_obj;
         la.n_grp = a.cam.W * a.cam.H / 64;
-        launch_label_ingest(la, (int)pb.label_sets.size(), sp, Enqueue::stop(p.ev_prep, q.cur.ev_prep));
+        launch_label_ingest(la, (int)pb.label_sets.size(), sp, p.pose_silhouettes ? nullptr : Enqueue::stop(p.ev_prep, q.cur.ev_prep));
         ++q.launches;
         CHECK_LAUNCH("label image ingest");
+        return ROFT_OK;
+    };
+    // masks from poses: one launch for every silhouette of the batch, the preparation's last.  It ends with ev_prep where the plan
+    // has one bound to a launch, else with an event of its own, which takes time stamps (roft_debug_pose_mask_kernel_ms).
+    auto pose_silhouettes = [&]() -> int {
+        EnginePoseMasks& pm = e->pose_masks;
+        SilhouetteArgs sa{};
+        sa.ctrl = a.ctrl;
+        sa.params = a.params;
+        sa.planes = a.planes;
+        sa.plane_words = a.plane_words;
+        sa.obj_stride = (size_t)kPlaneSlotsTotal * 2 * a.plane_words;
+        sa.slot0 = a.slot_new;
+        sa.mrec = a.mrec;
+        sa.n_obj = a.n_obj;
+        sa.W = a.cam.W; sa.H = a.cam.H; sa.wpr = a.cam.wpr;
+        sa.fx = (float)a.cam.fx; sa.fy = (float)a.cam.fy; sa.cx = (float)a.cam.cx; sa.cy = (float)a.cam.cy;   // (divider 1: the camera as it is)
+        int n_frames = 0;
+        for (int t = 0; t < a.T && t < 8; ++t)
+            if (pb.pose_mask_frames & (1u << t)) sa.frames_packed |= (unsigned)t << (4 * n_frames++);
+        const int slot = e->batch_counter % roft_engine::kBatchRing;
+        const hipEvent_t plan_stop = Enqueue::stop(p.ev_prep, q.cur.ev_prep);
+        if (!p.prep) tmark(e, nullptr, 0);   // (timing runs: a mark of its own on the mask stream; ahead on the upload stream it is part of mask_prepare)
+        if (!launch_pose_silhouette(sa, n_frames, a.max_verts, 0, 1, sp, pm.ev_start[slot], plan_stop ? plan_stop : pm.ev_stop[slot]))
+            return fail(ROFT_ERR_INVALID, "pose masks: the image does not fit the kernel's bit window");
+        pm.last_slot = slot;
+        pm.last_timed = plan_stop == nullptr;
+        ++q.launches;
+        CHECK_LAUNCH("pose silhouettes");
+        if (!p.prep) tmark(e, "pose_silhouettes", 0);
         return ROFT_OK;
     };
     if (p.try_fused && launch_ctrl_ingest(q.cur.stage, a, n16, pb.facts.plain_mask_frames, sp, ctrl_stop)) {
         ++q.launches;
         CHECK_LAUNCH("FrameCtrl upload + mask ingest");
-        return p.label_ingest ? label_ingest() : ROFT_OK;
+        if (p.label_ingest) TRY(label_ingest());
+        return p.pose_silhouettes ? pose_silhouettes() : ROFT_OK;
     }
     hipExtLaunchKernelGGL(ctrl_upload_kernel, dim3((unsigned)std::min<size_t>((n16 + 255) / 256, 64)), dim3(256), 0, sp, nullptr, ctrl_stop, 0,
                           reinterpret_cast<const uint4*>(q.cur.stage), a, n16, 1);
@@ -181,11 +213,12 @@ static int enqueue_preparation(Enqueue& q)
         if (pb.facts.plain_mask_frames & (1u << t)) last = t;
     for (int t = 0; t <= last; ++t)
         if (pb.facts.plain_mask_frames & (1u << t)) {
-            launch_mask_ingest(a, t, sp, (t == last && !p.label_ingest) ? Enqueue::stop(p.ev_prep, q.cur.ev_prep) : nullptr);
+            launch_mask_ingest(a, t, sp, (t == last && !p.label_ingest && !p.pose_silhouettes) ? Enqueue::stop(p.ev_prep, q.cur.ev_prep) : nullptr);
             ++q.launches;
         }
     CHECK_LAUNCH("mask ingest");
     if (p.label_ingest) TRY(label_ingest());
+    if (p.pose_silhouettes) TRY(pose_silhouettes());
     if (p.prep) {
         TRY(q.signalled(p.ev_prep, q.cur.ev_prep, sp));
         tmark(e, "mask_prepare", 4);

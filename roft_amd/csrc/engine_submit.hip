@@ -495,7 +495,12 @@ static int schedule_mask_source(roft_engine* e, const FrameJob& j, const ImageSi
     FrameCtrl& c = j.c;
     c.slot_prev = (o.frame_idx + kPlaneSlots - 1) % kPlaneSlots;
     c.slot_cur = o.frame_idx % kPlaneSlots;
-    const bool has_mask = d.mask || d.labels;
+    // masks from poses (roft_engine_enable_pose_masks): an enrolled object whose frame brings neither a mask nor a label image takes
+    // the silhouette of the delivered pose -- on its first frame, without one, of the pose it was added with
+    const EnginePoseMasks& pm = e->pose_masks;
+    const bool enrolled = pm.enabled && (ho.pose_masks || (pm.all && e->h_params[j.id].n_verts > 0 && e->h_params[j.id].n_tris > 0));
+    const bool from_pose = enrolled && !d.mask && !d.labels && (j.in.pose_valid || o.frame_idx == 0);
+    const bool has_mask = d.mask || d.labels || from_pose;
     c.has_new_mask = has_mask ? 1 : 0;
     c.new_mask = static_cast<const uint8_t*>(d.mask);
     if (has_mask) pb.new_mask_frames |= 1u << j.t;
@@ -516,9 +521,14 @@ static int schedule_mask_source(roft_engine* e, const FrameJob& j, const ImageSi
         }
         pb.label_members[si].push_back(LabelMember{j.id, j.lm->label});
     }
+    if (from_pose) {
+        c.label_type = kMaskFromPose;   // (pose_silhouette_kernel draws the planes; the ordinary ingest skips the object)
+        pb.pose_mask_frames |= 1u << j.t;
+        pb.facts.pose_masks++;
+    }
     if (has_mask && !o.seg_available) { o.seg_available = true; c.first_mask = 1; }
     if (!o.seg_available)
-        return fail(ROFT_ERR_STATE, "no segmentation mask delivered yet: the first frame must carry one");
+        return fail(ROFT_ERR_STATE, "no segmentation mask delivered yet: the first frame must carry one (or the object be enrolled with roft_engine_enable_pose_masks)");
     const bool valid_flow = d.flow && !o.of_first_frame;
     o.of_first_frame = false;
     if (valid_flow) {
@@ -680,6 +690,11 @@ static int submit_frames(roft_engine* e, const roft_frame_input* inputs, const r
             j.c.frame_idx = j.frame;
             if (!build_pose_program(cfg, o, j.in, j.c))
                 return fail(ROFT_ERR_CAPACITY, "more buffered velocities to replay than one frame's program holds (kMaxSteps)");
+            if (j.c.label_type == kMaskFromPose && !j.in.pose_valid) {
+                // the silhouette of a first frame without a pose: the initial pose, in the fields no step of the frame reads
+                for (int i = 0; i < 3; ++i) j.c.pose_x[i] = j.ho.pose0[i];
+                for (int i = 0; i < 4; ++i) j.c.pose_q[i] = j.ho.pose0[3 + i];
+            }
             TRY(account_lanes_and_features(e, j));
             o.frame_idx++;
         }
@@ -770,6 +785,8 @@ int roft_frames_submit_images(roft_engine* e, const roft_frame_input* inputs, co
     }
     e->submitted = true;
     e->device_pointers_checked = true;
+    e->pose_masks.stats.silhouettes += pb.facts.pose_masks;
+    e->pose_masks.stats.frames += __builtin_popcount(pb.pose_mask_frames);
     pb.submit_us = host_now_us() - pb.submit_t0;
     return ROFT_OK;
 }
@@ -820,6 +837,64 @@ int roft_engine_get_flow_stats(roft_engine* e, roft_engine_flow_stats* out)
 {
     if (!e || !out) return fail(ROFT_ERR_INVALID, "null argument");
     *out = e->flow.stats;
+    return ROFT_OK;
+}
+
+// ---- masks from poses (include/roft_engine.h section 3e) -------------------------------------------------------------------------
+int roft_engine_enable_pose_masks(roft_engine* e, const int* obj_ids, int n_ids)
+{
+    if (!e) return fail(ROFT_ERR_INVALID, "null engine");
+    if (n_ids < 0 || (n_ids > 0 && !obj_ids)) return fail(ROFT_ERR_INVALID, "pose masks: n_ids object ids required (n_ids 0: every object)");
+    if (e->frame_counter > 0 || e->submitted) return fail(ROFT_ERR_STATE, "roft_engine_enable_pose_masks must precede the first frame");
+    if (e->cfg.stamped_masks) return fail(ROFT_ERR_INVALID, "pose masks: a pose carries no stamp, an engine with stamped_masks cannot place its silhouette in the flow queue");
+    if (e->cfg.render_mode == ROFT_RENDER_GL)
+        return fail(ROFT_ERR_INVALID, "pose masks are drawn under ROFT_RENDER_CONTRACT: an engine with render_mode ROFT_RENDER_GL keeps its meshes "
+                                      "unsorted and without the flip bits of the back-face rule, so the defining render does not exist there");
+    for (int i = 0; i < n_ids; ++i) {
+        const int id = obj_ids[i];
+        if (id < 0 || id >= (int)e->objs.size()) return fail(ROFT_ERR_INVALID, "pose masks: " + std::to_string(id) + " is not an object of the engine");
+        if (e->h_params[id].n_verts <= 0 || e->h_params[id].n_tris <= 0)
+            return fail(ROFT_ERR_INVALID, "pose masks: object " + std::to_string(id) + " was added without a mesh");
+    }
+    if (e->cfg.cam.width / 32 > kSilhouetteWindowWords) return fail(ROFT_ERR_INVALID, "pose masks: an image row is wider than the kernel's bit window");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    EnginePoseMasks& pm = e->pose_masks;
+    // nothing of the launch may happen for the first time inside a caller's timed region (engine_setup): each event pair has completed
+    // one dispatch on the streams that will carry it
+    for (int i = 0; i < roft_engine::kBatchRing; ++i) {
+        if (!pm.ev_start[i]) HIP_TRY(hipEventCreate(&pm.ev_start[i]));
+        if (!pm.ev_stop[i]) HIP_TRY(hipEventCreate(&pm.ev_stop[i]));
+        hipExtLaunchKernelGGL(probe_tiny_kernel, dim3(1), dim3(64), 0, (i & 1) ? e->up_stream : e->stream, pm.ev_start[i], pm.ev_stop[i], 0,
+                              reinterpret_cast<int*>(e->arr.a.mask_general));
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipStreamSynchronize(e->up_stream));
+    HIP_TRY(hipMemset(e->arr.a.mask_general, 0, sizeof(unsigned)));   // (what the probe touched)
+    if (n_ids == 0) pm.all = true;
+    for (int i = 0; i < n_ids; ++i) e->objs[obj_ids[i]]->pose_masks = true;
+    pm.enabled = true;
+    return ROFT_OK;
+}
+
+int roft_engine_get_pose_mask_stats(roft_engine* e, roft_engine_pose_mask_stats* out)
+{
+    if (!e || !out) return fail(ROFT_ERR_INVALID, "null argument");
+    *out = e->pose_masks.stats;
+    return ROFT_OK;
+}
+
+int roft_debug_pose_mask_kernel_ms(roft_engine* e, double* ms_out)
+{
+    if (!e || !ms_out) return fail(ROFT_ERR_INVALID, "null argument");
+    const EnginePoseMasks& pm = e->pose_masks;
+    if (!pm.enabled || pm.last_slot < 0) return fail(ROFT_ERR_STATE, "no silhouette launch so far");
+    if (!pm.last_timed) return fail(ROFT_ERR_STATE, "the last silhouette launch ended with the preparation's event, which takes no time stamps (roft_engine_enable_timing times every launch)");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(hipEventSynchronize(pm.ev_stop[pm.last_slot]));
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, pm.ev_start[pm.last_slot], pm.ev_stop[pm.last_slot]));
+    *ms_out = (double)ms;
     return ROFT_OK;
 }
 

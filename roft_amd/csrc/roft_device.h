@@ -157,7 +157,8 @@ struct alignas(16) FrameCtrl {
     int lane;                        // pose chain lane (stream) that walks this frame's steps (see BeliefSlot)
     int cur_slot;                    // B_LIN0 / B_LIN1: slot of p_corr_belief_ during this frame
     int label;                       // the delivered mask is the pixels of a LABEL IMAGE equal to this value (label_ingest_kernel
-    int label_type;                  // writes its planes; the ordinary ingest skips the object): ROFT_LABEL_*, 0: new_mask as before
+    int label_type;                  // writes its planes; the ordinary ingest skips the object): ROFT_LABEL_*, 0: new_mask as before;
+                                     // kMaskFromPose: the silhouette of the mesh at pose_x / pose_q (pose_silhouette_kernel)
 };
 
 // Mask chain record of one frame of the batch and one object (k_mask.hip).  Row t + 1 of EngineArrays::mrec belongs to
@@ -390,6 +391,30 @@ struct LabelIngestArgs {
 };
 // every label set of a batch in ONE launch (grid: chunks of 256 groups x sets): planes and counts of all members, one pass per image
 void launch_label_ingest(const LabelIngestArgs& la, int n_sets, hipStream_t s, hipEvent_t stop = nullptr);
+// Masks from poses (include/roft_engine.h section 3e): FrameCtrl::label_type of a frame whose mask is the silhouette of the mesh at
+// the frame's pose_x / pose_q (pose_silhouette_kernel, k_silhouette.hip, writes its planes; the ordinary ingest skips the object)
+constexpr int kMaskFromPose = 3;
+constexpr int kSilhouetteCacheVerts = 8192;     // projected vertices a workgroup keeps in LDS (96 KB); a larger mesh is projected per triangle
+constexpr int kSilhouetteWindowWords = 8192;    // words of the LDS bit window (32 KB): a band with more rows is drawn in strips
+// what pose_silhouette_kernel reads and where it writes: like LabelIngestArgs, the engine's layout or a compact one (operator)
+struct SilhouetteArgs {
+    const FrameCtrl* ctrl;       // [T][n_obj]: label_type (kMaskFromPose: the pair is drawn, else its workgroups leave), pose_x, pose_q
+    const ObjParams* params;     // [n_obj]: the meshes
+    uint32_t* planes;
+    size_t obj_stride, plane_words;
+    int slot0;
+    MaskRec* mrec;
+    int n_obj;
+    int W, H, wpr;
+    float fx, fy, cx, cy;        // the camera at full resolution, as roft_render_depth(.., divider 1) rounds it
+    unsigned frames_packed;      // four bits per delivering frame of the batch, lowest first (grid z)
+    int vcache_cap;              // vertices the LDS cache holds (0: project per triangle)
+    int win_rows;                // rows of the LDS bit window
+};
+// every (delivering frame, enrolled object) pair of a batch in ONE launch (grid: bands x objects x delivering frames).  bands 0: one
+// per 64 image rows; vertex_cache 0: project per triangle.  Neither changes a bit.  false: not launched (an image row wider than the window)
+bool launch_pose_silhouette(SilhouetteArgs sa, int n_frames, int max_verts, int bands, int vertex_cache, hipStream_t s,
+                            hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 // Zeroes what the ingest kernels accumulate into: the counters of mrec rows 1 .. T (mask_general is cleared by its only
 // reader, mask_general_kernel: this reset may run while the chain before still sets bits).
 // (Inside the engine the control block upload kernel does this; the operator-level entry points call it.)

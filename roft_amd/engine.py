@@ -294,6 +294,26 @@ class ROFTFilterBatch:
         L.check(L.lib().roft_debug_quality_kernel_ms(self._h, C.byref(ms)))
         return ms.value
 
+    def enable_pose_masks(self, obj_ids=None):
+        """Masks from poses (roft_engine_enable_pose_masks): the listed objects (None: every object the engine has at its first
+        frame) take the silhouette of a delivered pose as the frame's mask wherever the frame brings neither `mask` nor `labels`
+        -- on their first frame, without a pose, the silhouette of the pose they were added with.  After the objects are added,
+        before the first frame."""
+        ids = np.ascontiguousarray([] if obj_ids is None else obj_ids, np.int32).reshape(-1)
+        L.check(L.lib().roft_engine_enable_pose_masks(self._h, ids.ctypes.data_as(C.POINTER(C.c_int)) if len(ids) else None, len(ids)))
+
+    def pose_mask_stats(self):
+        """silhouettes drawn / frames that had any since the engine was created."""
+        st = L.EnginePoseMaskStats()
+        L.check(L.lib().roft_engine_get_pose_mask_stats(self._h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in L.EnginePoseMaskStats._fields_}
+
+    def pose_mask_kernel_ms(self):
+        """Device time (ms, HIP events on its dispatch) of the last silhouette launch."""
+        ms = C.c_double(0.0)
+        L.check(L.lib().roft_debug_pose_mask_kernel_ms(self._h, C.byref(ms)))
+        return ms.value
+
     def retain_frames(self):
         return L.lib().roft_engine_retain_frames(self._h)
 

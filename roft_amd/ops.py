@@ -115,6 +115,25 @@ def labels_to_masks(labels, values):
     return masks, counts
 
 
+def pose_silhouette(cam, mesh, x, q, bands=0, vertex_cache=True):
+    """The mask {0, 255} [H, W] and the pixel count of the silhouette of `mesh` at the pose (x, q = w x y z), by the
+    engine's own kernel (roft_pose_silhouette; the contract: include/roft_engine.h, section 3e): a pixel is set where
+    roft_render_depth at divider 1 is > 0.  bands 0: the library's choice of workgroups per image; vertex_cache False: the
+    vertices are projected per triangle.  Neither changes a bit.
+    mesh: (verts [n, 3], tris [m, 3]) arrays of any layout -- they are made float32 / int32 and C-contiguous here -- or an L.Mesh,
+    whose pointers must name C-contiguous float32 / int32 memory (the address of a transposed or sliced array is not that)."""
+    L.require_device()
+    x, q = _f64(np.asarray(x).reshape(3)), _f64(np.asarray(q).reshape(4))
+    if not isinstance(mesh, L.Mesh):
+        verts = np.ascontiguousarray(mesh[0], np.float32).reshape(-1, 3)
+        tris = np.ascontiguousarray(mesh[1], np.int32).reshape(-1, 3)
+        mesh = L.Mesh(verts.ctypes.data, verts.shape[0], tris.ctypes.data, tris.shape[0])
+    mask = np.zeros((cam.height, cam.width), np.uint8)
+    count = C.c_int(0)
+    L.check(L.lib().roft_pose_silhouette(C.byref(cam), C.byref(mesh), _p(x), _p(q), int(bands), 1 if vertex_cache else 0, _p(mask), C.byref(count)))
+    return mask, count.value
+
+
 def process_noise(psd, sig_w, T):
     Q = np.zeros((9, 9))
     L.check(L.lib().roft_pose_process_noise(_p(_f64(psd)), _p(_f64(sig_w)), T, _p(Q)))

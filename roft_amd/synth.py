@@ -67,7 +67,8 @@ def box_mesh(half_extents, n=36):
             base = sum(v.shape[0] for v in verts)
             verts.append(p * np.array([hx, hy, hz]))
             tris.append(face_tris + base)
-    return np.concatenate(verts).astype(np.float32), np.concatenate(tris).astype(np.int32)
+    # (C-contiguous: the triangle blocks come out of a column selection in Fortran order, and astype keeps that)
+    return np.ascontiguousarray(np.concatenate(verts), np.float32), np.ascontiguousarray(np.concatenate(tris), np.int32)
 
 
 def quat_mul(a, b):

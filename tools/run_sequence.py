@@ -5,7 +5,7 @@ files (`pose_estimate`, `velocity_estimate`, ROFTFilter.cpp:386-394) -- what `te
   run_sequence.py --root DIR --object NAME --mesh model.obj [--flow-set nvof_1_slow] [--mask-set NAME]
                   [--pose-set dope] [--out PREFIX] [--compute-flow nvof1|nvof2 | --flow-on-engine nvof1|nvof2] [--no-delay]
                   [--init-pose x y z qw qx qy qz] [--raw-depth SCALE]
-                  [--start-at-first-detection] [--score-on-device] [--render-overlay DIR] [--quality FILE]
+                  [--start-at-first-detection] [--score-on-device] [--render-overlay DIR] [--quality FILE] [--masks-from-pose]
                   [--from config_fast_ycb.cfg [--group::key value ...]]
 
 --from reads the filter parameters from one of the reference's configuration files (config/config_fast_ycb.cfg,
@@ -23,7 +23,11 @@ ADD-S and ADD of the same frames on EVERY vertex of the mesh, computed on the GP
 (roft_engine_score_log: the estimates never leave the device).  --render-overlay DIR draws the estimate over the sequence's
 grayed RGB frames (DIR/<frame>.png) with tools/render_results.py once the logs are written.  --quality FILE turns track quality on
 (roft_engine_enable_quality) and writes one row per frame: frame, the seven counts of roft_quality_record, depth_err and the overlap
-n_both / (n_mask + n_render - n_both), space separated under a header line.
+n_both / (n_mask + n_render - n_both), space separated under a header line.  --masks-from-pose tracks a directory that has
+<pose-set>/poses.txt and NO masks: the object is enrolled with roft_engine_enable_pose_masks and every delivered pose brings the
+silhouette of the mesh at that pose as the frame's mask, drawn on the device (DIR/masks is not read; the first frame uses the
+initial pose when it brings none).  The pose source's delay is the mask's delay then: keep mask_frames_between equal to
+pose_frames_between.
 """
 import argparse
 import json
@@ -63,6 +67,8 @@ def main(argv=None):
                     help="after the run, draw the estimate over SEQ/rgb/<i>.png into DIR/<i>.png (tools/render_results.py)")
     ap.add_argument("--quality", default=None, metavar="FILE",
                     help="score every estimate against its frame's mask and depth on the device; one row per frame into FILE")
+    ap.add_argument("--masks-from-pose", action="store_true",
+                    help="no segmentation masks: the engine draws the silhouette of every delivered pose on the device and tracks with it")
     ap.add_argument("--from", dest="cfg_file", default=None, help="ROFT configuration file (libconfig), overrides as --a::b::c value")
     args, overrides = ap.parse_known_args(argv)
 
@@ -149,8 +155,16 @@ def main(argv=None):
         eng.enable_flow()
     if args.raw_depth is not None:
         eng.enable_raw_depth(args.raw_depth)
+    if args.masks_from_pose:
+        if cfg.mask_frames_between != cfg.pose_frames_between:
+            sys.stderr.write("note: mask_frames_between %d != pose_frames_between %d: a silhouette is as old as its pose\n" %
+                             (cfg.mask_frames_between, cfg.pose_frames_between))
+        eng.enable_pose_masks([0])
     for k in range(start, len(seq)):
-        eng.submit([seq.frame(k, with_image=bool(args.flow_on_engine), depth_raw=args.raw_depth is not None)])
+        frame = seq.frame(k, with_image=bool(args.flow_on_engine), depth_raw=args.raw_depth is not None)
+        if args.masks_from_pose:
+            frame["mask"] = None
+        eng.submit([frame])
         eng.step()
     pose, twist, npts, sel = eng.get_log(0, n)
     gt_path = os.path.join(args.root, "gt", "poses.txt")
@@ -168,6 +182,7 @@ def main(argv=None):
             for r, o in zip(rec, iou):
                 f.write("%d %d %d %d %d %d %d %.17g %.6f\n" % (start + r["frame"], r["n_mask"], r["n_render"], r["n_both"], r["n_depth"],
                                                               r["n_front"], r["n_behind"], r["depth_err"], o))
+    pose_mask_stats = eng.pose_mask_stats() if args.masks_from_pose else None
     eng.close()
     prefix = args.out if args.out is not None else os.path.join(args.root, "roft_mi355x_")
     io.write_estimate_logs(prefix, pose[:, 0], twist[:, 0])
@@ -195,6 +210,8 @@ def main(argv=None):
         report["overlay"] = args.render_overlay
     if args.quality:
         report["quality"] = args.quality
+    if args.masks_from_pose:
+        report["pose_masks"] = pose_mask_stats
     print(json.dumps(report))
     return 0
 
