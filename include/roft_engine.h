@@ -727,7 +727,7 @@ int roft_track_quality(const roft_camera* cam, int divider, const float* depth, 
  *
  * LIMIT.  The silhouette is drawn from the pose MEASUREMENT, before any filtering: an outlier pose (the reference's data has them,
  * 30 degrees off) yields a wrong mask until the next pose arrives.  The UKF's outlier rejection protects the estimate, not the mask.
- * Objects do not occlude each other's silhouettes, and nothing is dilated.
+ * Nothing is dilated.  Objects hide each other's silhouettes only where the caller says they share a scene (below).
  *
  * Refused on the host, with nothing consumed and the reason in roft_last_error_string: ROFT_ERR_STATE after the first frame;
  * ROFT_ERR_INVALID for an id that is not an object of the engine, for an object added without a mesh, for an engine with
@@ -747,6 +747,59 @@ int roft_engine_enable_pose_masks(roft_engine* e, const int* obj_ids, int n_ids)
 int roft_engine_get_pose_mask_stats(roft_engine* e, roft_engine_pose_mask_stats* out);
 int roft_pose_silhouette(const roft_camera* cam, const roft_mesh* mesh, const double x[3], const double q[4], int bands, int vertex_cache,
                          uint8_t* mask_out, int* count_out);
+
+/* ---- (3e, continued) enrolled objects of one scene hide each other ----------------------------------------------------------- *
+ * Two objects that overlap in the image both own the overlap as plain silhouettes: the rear object's flow samples, features,
+ * outlier likelihood and quality records are then taken on the front object.  Opt-in: objects the caller declares to share a scene
+ * are drawn against a common z-buffer, and each keeps only the pixels where it is the nearest surface.  Off, the engine enqueues
+ * exactly what it does without this call.
+ *
+ * roft_engine_enable_pose_mask_occlusion(e, obj_ids, scene_ids, n_ids): after roft_engine_enable_pose_masks, before the first frame.
+ * scene_ids[i] >= 0 names the scene of obj_ids[i]; n_ids == 0 (NULL arrays allowed) puts every object enrolled at the time of the
+ * call into scene 0 (the shared-scene deployment).  A later call replaces an object's scene.  An enrolled object that is never named
+ * is a scene of its own and is drawn exactly as without the mode.
+ *
+ * THE RESOLVED MASK.  For a frame t and a scene s let D be the objects of s whose mask on frame t is a silhouette (the pairs the
+ * rules above give a silhouette, a first frame drawn from p_mean0 included).  For i in D let
+ *        R_i = roft_render_depth(mesh_i, pose_x_i, pose_q_i, cam, 1)
+ * (the float image, the pose exactly as above).  The engine behaves BIT FOR BIT as if object i had been handed the HOST mask
+ *        M_i(p) = 255  when R_i(p) > 0 and for every other j in D:  R_j(p) == 0,  or R_i(p) < R_j(p),  or R_i(p) == R_j(p) and i < j
+ *        M_i(p) = 0    otherwise
+ * -- float comparisons on the rendered values; on an exact tie the lower object id keeps the pixel.  The masks of D are disjoint
+ * and their union is the union of the plain silhouettes.
+ *  - An object whose mask arrives another way on that frame (a delivered mask, a label image, no pose delivered) is not in D: it
+ *    neither hides nor is hidden.
+ *  - Objects of other scenes do not interact.
+ *  - A silhouette that loses every pixel is a "new but empty mask" and is ignored by the existing rule: the object keeps
+ *    propagating its last mask.
+ *  - Downstream, everything is what it is for a delivered mask.
+ *  - roft_engine_pose_mask_stats keeps its meaning: silhouettes are counted whether hidden or not.
+ * LIMITS.  Only enrolled objects with silhouettes on the same frame hide each other: hands, clutter and plain-mask objects do not.
+ * The silhouettes are not gated against the frame's depth (a delayed pose belongs to an older image than the frame that carries it).
+ * Memory: one z-buffer of width x height x 8 bytes per scene with at least two members, times 2 x ROFT_MAX_BATCH_FRAMES, allocated
+ * by this call; nothing grows on the hot path.
+ *
+ * Refused on the host, with nothing consumed and the reason in roft_last_error_string: ROFT_ERR_STATE after the first frame or
+ * when pose masks are not enabled; ROFT_ERR_INVALID for an id that is not an object of the engine, an id that is not enrolled
+ * (explicitly or through enrol-all), a negative scene id, n_ids < 0, n_ids > 0 with a NULL array.
+ *
+ * roft_engine_get_pose_mask_occlusion_stats: waits for the batches stepped so far (hidden and pixels_removed are counted on the device).
+ *
+ * roft_pose_silhouettes_occluded: the same kernels on HOST buffers, device 0, ONE scene of n meshes (object id = index): masks_out
+ * n x H x W bytes {0, 255} (optional), counts_out n pixel counts (optional).  bands and vertex_cache as for roft_pose_silhouette;
+ * they change no bit (a per-pixel minimum and an equality test are order-free).  With n == 1 it is roft_pose_silhouette.
+ * ROFT_ERR_INVALID before any device is looked for: a NULL cam, meshes, x or q, n < 1 or n > ROFT_SCENE_MAX_INSTANCES (256),
+ * bands < 0, a vertex_cache that is neither 0 nor 1, a triangle that names a vertex outside its mesh. */
+typedef struct {
+    long long resolved;        /* (frame, object) silhouettes drawn against at least one other object of their scene */
+    long long hidden;          /* of those, silhouettes that had pixels and lost every one */
+    long long pixels_removed;  /* pixels the plain silhouettes had and the resolved ones have not */
+} roft_engine_pose_mask_occlusion_stats;
+int roft_engine_enable_pose_mask_occlusion(roft_engine* e, const int* obj_ids, const int* scene_ids, int n_ids);
+int roft_engine_get_pose_mask_occlusion_stats(roft_engine* e, roft_engine_pose_mask_occlusion_stats* out);
+int roft_pose_silhouettes_occluded(const roft_camera* cam, const roft_mesh* meshes, int n, const double* x /* [n][3] */,
+                                   const double* q /* [n][4] */, int bands, int vertex_cache,
+                                   uint8_t* masks_out /* [n][H][W], optional */, int* counts_out /* [n], optional */);
 
 /* ---- (3b) scene renderer: tracked poses drawn over the camera frames ----------------------------------------------
  * The reference's evaluation draws the mesh at every estimated pose over the grayed camera frame (evaluation/results_renderer.py:
@@ -845,7 +898,8 @@ int roft_debug_depth_kernel_ms(roft_engine* e, double* ms_out);
 /* device time in milliseconds (the HIP events bound to its dispatch) of the engine's last quality launch (section 3d); waits for it.
  * ROFT_ERR_STATE when there was none. */
 int roft_debug_quality_kernel_ms(roft_engine* e, double* ms_out);
-/* device time in milliseconds (the HIP events bound to its dispatch) of the engine's last silhouette launch (section 3e); waits for it.
+/* device time in milliseconds (the HIP events bound to its dispatches) of the engine's last silhouette stage (section 3e: the one-pass
+ * launch, or draw to resolve where silhouettes were resolved); waits for it.
  * ROFT_ERR_STATE: no launch so far, or the last one ended with the preparation's own event (a steady batch of a full device outside
  * roft_engine_enable_timing), which takes no time stamps. */
 int roft_debug_pose_mask_kernel_ms(roft_engine* e, double* ms_out);

@@ -119,6 +119,10 @@ class EnginePoseMaskStats(C.Structure):
     _fields_ = [("silhouettes", C.c_longlong), ("frames", C.c_longlong)]
 
 
+class EnginePoseMaskOcclusionStats(C.Structure):
+    _fields_ = [("resolved", C.c_longlong), ("hidden", C.c_longlong), ("pixels_removed", C.c_longlong)]
+
+
 class EngineStats(C.Structure):
     _fields_ = [("frames", C.c_longlong), ("batches", C.c_longlong), ("launches", C.c_longlong),
                 ("event_ops", C.c_longlong), ("h2d_bytes", C.c_longlong), ("h2d_copies", C.c_longlong)]
@@ -169,6 +173,7 @@ ABI_SYMBOLS = [
     "roft_debug_depth_kernel_ms",
     "roft_default_quality_params", "roft_engine_enable_quality", "roft_engine_get_quality", "roft_track_quality", "roft_debug_quality_kernel_ms",
     "roft_engine_enable_pose_masks", "roft_engine_get_pose_mask_stats", "roft_pose_silhouette", "roft_debug_pose_mask_kernel_ms",
+    "roft_engine_enable_pose_mask_occlusion", "roft_engine_get_pose_mask_occlusion_stats", "roft_pose_silhouettes_occluded",
 ]
 POSE_ERROR_ADD, POSE_ERROR_ADDS = 0, 1   # ROFT_POSE_ERROR_*
 # entry points younger than ABI version 2 itself: a library built before them still loads through ROFT_LIB_SO
@@ -177,7 +182,8 @@ NEWER_SYMBOLS = ("roft_pose_errors", "roft_engine_score_log", "roft_scene_render
                  "roft_engine_enable_flow", "roft_frames_submit_images", "roft_engine_get_flow", "roft_engine_get_flow_stats", "roft_image_to_gray",
                  "roft_engine_enable_raw_depth", "roft_engine_get_depth", "roft_engine_get_depth_stats", "roft_depth_convert", "roft_depth_align",
                  "roft_default_quality_params", "roft_engine_enable_quality", "roft_engine_get_quality", "roft_track_quality",
-                 "roft_engine_enable_pose_masks", "roft_engine_get_pose_mask_stats", "roft_pose_silhouette")
+                 "roft_engine_enable_pose_masks", "roft_engine_get_pose_mask_stats", "roft_pose_silhouette",
+                 "roft_engine_enable_pose_mask_occlusion", "roft_engine_get_pose_mask_occlusion_stats", "roft_pose_silhouettes_occluded")
 
 
 def build(force=False):
@@ -302,6 +308,10 @@ def lib():
         L.roft_engine_get_pose_mask_stats.argtypes = [vp, C.POINTER(EnginePoseMaskStats)]
         L.roft_pose_silhouette.argtypes = [C.POINTER(Camera), C.POINTER(Mesh), vp, vp, C.c_int, C.c_int, vp, ip]
         L.roft_debug_pose_mask_kernel_ms.argtypes = [vp, dp]
+    if hasattr(L, "roft_pose_silhouettes_occluded"):
+        L.roft_engine_enable_pose_mask_occlusion.argtypes = [vp, ip, ip, C.c_int]
+        L.roft_engine_get_pose_mask_occlusion_stats.argtypes = [vp, C.POINTER(EnginePoseMaskOcclusionStats)]
+        L.roft_pose_silhouettes_occluded.argtypes = [C.POINTER(Camera), C.POINTER(Mesh), C.c_int, vp, vp, C.c_int, C.c_int, vp, ip]
     for name in ABI_SYMBOLS:
         if (name.startswith("roft_debug_") or name in NEWER_SYMBOLS) and not hasattr(L, name):
             continue   # (an older build loaded through ROFT_LIB_SO for an A/B run: diagnostics and the pose errors only; tests/test_abi_cpu.py checks the in-tree library has them all)

@@ -63,6 +63,7 @@ struct SubmitFacts {
     unsigned plain_mask_frames = 0; // bit t: frame t delivers a per-object byte mask (what the ingest of the control-block launch converts)
     int label_sets = 0;             // distinct (frame, label image) pairs of the batch: masks delivered as label images
     int pose_masks = 0;             // (frame, object) pairs of the batch whose mask is the silhouette of a delivered pose (masks from poses)
+    int pose_resolve = 0;           // ... of those, the pairs drawn against at least one other object of their scene on their frame
     bool any_feat = false, any_feat_now = false;
     bool feat_dep_in_batch = false; // an outlier test of the batch reads features buffered by a frame of the same batch
     int n_segments[kPlanLanes] = {1, 1};          // pose chain segments per lane (1 + outlier tests of the busiest object)
@@ -132,6 +133,7 @@ struct BatchPlan {
     bool try_fused = false;     // control blocks + ingest in one launch, if the launcher accepts
     bool label_ingest = false;  // one more launch behind them: every label image of the batch, all of its objects
     bool pose_silhouettes = false;   // one more launch behind those: every silhouette of the batch (the preparation's last launch is the last of these that exists)
+    bool pose_resolve = false;       // silhouettes to resolve: the silhouette launch draws them against z-buffers, and a resolve launch follows it
     Signal ev_ctrl = Signal::none, ev_prep = Signal::none;
     // mask frames and features
     bool part_gate = false;     // the mask chain signals ev_part with the masks of frames 0 .. T - 2
@@ -236,6 +238,9 @@ BatchPlan plan_batch(const PlanInputs& in, AloneFn&& alone)
     // blocks (the poses travel in them) and the resident meshes, nothing the batch computes: on the upload stream when the
     // preparation runs ahead.  A batch without silhouettes enqueues what it always did.
     p.pose_silhouettes = in.pose_masks > 0;
+    // Silhouettes of one scene that hide each other: the same launch draws them against z-buffers (cleared in front of it) and ONE
+    // resolve launch follows, the preparation's last by the same rule.  A batch with nothing to resolve launches nothing new.
+    p.pose_resolve = p.pose_silhouettes && in.pose_resolve > 0;
     p.ev_prep = !p.prep ? Signal::none
                 : (full || (in.plain_mask_frames == 0 && !p.label_ingest && !p.pose_silhouettes)) ? Signal::record : Signal::stop;   // (no ingest: no kernel to end with it)
 
@@ -310,6 +315,19 @@ BatchPlan plan_batch(const PlanInputs& in, AloneFn&& alone)
     p.outlier_div = (in.outlier_bands_per_alternative == 0 && p.steady && k.outlier_steady_div > 1) ? k.outlier_steady_div : 1;
     return p;
 }
+
+// The launches of a batch's preparation behind its control blocks, in the order they are enqueued.  The last of those that exist
+// ends with ev_prep where the plan binds the event to a launch (Signal::stop).
+enum class PrepLaunch { none, mask_ingest, label_ingest, pose_silhouettes, pose_resolve };
+inline PrepLaunch prep_last_launch(const BatchPlan& p, unsigned plain_mask_frames)
+{
+    return p.pose_resolve ? PrepLaunch::pose_resolve
+           : p.pose_silhouettes ? PrepLaunch::pose_silhouettes
+           : p.label_ingest ? PrepLaunch::label_ingest
+           : plain_mask_frames ? PrepLaunch::mask_ingest : PrepLaunch::none;
+}
+// kernel launches of the silhouette stage: none, the one-pass launch, or draw + resolve
+inline int pose_silhouette_launches(const BatchPlan& p) { return p.pose_resolve ? 2 : p.pose_silhouettes ? 1 : 0; }
 
 }  // namespace host
 }  // namespace roft

@@ -280,6 +280,9 @@ struct HostObject {
     // masks from poses (roft_engine_enable_pose_masks): the object is enrolled; the pose of roft_object_desc::p_mean0 (x, q = w x y z),
     // which stands in for a first frame that brings none
     bool pose_masks = false;
+    // ... and the scene it shares with others (roft_engine_enable_pose_mask_occlusion; -1: a scene of its own), and that scene's
+    // z-buffer where it has at least two members (-1: none, the object is always drawn alone)
+    int pose_scene = -1, pose_zscene = -1;
     double pose0[7] = {0, 0, 0, 1, 0, 0, 0};
     ~HostObject() { for (auto* o : owned) delete o; }
 };
@@ -342,6 +345,14 @@ struct EnginePoseMasks {
     hipEvent_t ev_start[8] = {}, ev_stop[8] = {};
     int last_slot = -1;                  // batch-ring slot of the last launch
     bool last_timed = false;             // ... and whether it ended with ev_stop of that slot
+    // objects of one scene hide each other (roft_engine_enable_pose_mask_occlusion).  Allocated when the mode is enabled: z-buffers
+    // [batch parity][kMaxBatch delivering frames][n_zscenes][H * W] (the parity of the ingest slots: the preparation of batch b + 1
+    // may run next to the chains of batch b), the pair records [batch parity][kMaxBatch][max_objects], the two device counters
+    bool occlusion = false;
+    int n_zscenes = 0;                   // scenes with at least two members
+    roft_engine_pose_mask_occlusion_stats occl_stats{};   // (resolved: counted by submit; the rest is read from zstats)
+    DevBuf<unsigned long long> zbuf, zstats;
+    DevBuf<SilhouettePair> zpairs;
     ~EnginePoseMasks()
     {
         for (hipEvent_t ev : ev_start) if (ev) (void)hipEventDestroy(ev);

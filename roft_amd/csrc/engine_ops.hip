@@ -383,18 +383,23 @@ int roft_labels_to_masks(const void* labels, int label_type, int W, int H, const
     return ROFT_OK;
 }
 
-// Masks from poses, stand-alone: the engine's silhouette kernel on a compact layout -- one object, one ingest slot, one frame.
-int roft_pose_silhouette(const roft_camera* cam, const roft_mesh* mesh, const double x[3], const double q[4], int bands, int vertex_cache,
-                         uint8_t* mask_out, int* count_out)
+// Masks from poses, stand-alone: the engine's silhouette kernels on a compact layout -- n objects of ONE scene, one ingest slot each,
+// one frame.  With one object there is nothing to resolve: the one-pass launch, as in an engine without the occlusion mode.
+static int pose_silhouettes(const char* what, const roft_camera* cam, const roft_mesh* meshes, int n, const double* x, const double* q, int bands,
+                            int vertex_cache, uint8_t* masks_out, int* counts_out)
 {
-    if (!cam || !mesh || !x || !q) return fail(ROFT_ERR_INVALID, "null argument");
+    if (!cam || !meshes || !x || !q) return fail(ROFT_ERR_INVALID, "null argument");
+    if (n < 1 || n > ROFT_SCENE_MAX_INSTANCES) return fail(ROFT_ERR_INVALID, std::string(what) + ": n must be 1 .. ROFT_SCENE_MAX_INSTANCES");
     if (bands < 0) return fail(ROFT_ERR_INVALID, "bands must be >= 0 (0: the library's choice)");
     if (vertex_cache != 0 && vertex_cache != 1) return fail(ROFT_ERR_INVALID, "vertex_cache must be 0 or 1");
-    const bool has_mesh = mesh->n_verts > 0 && mesh->n_tris > 0;
-    if (has_mesh && (!mesh->verts || !mesh->tris)) return fail(ROFT_ERR_INVALID, "mesh: null vertex or triangle array");
-    if (has_mesh)
-        for (size_t i = 0; i < (size_t)3 * mesh->n_tris; ++i)
-            if (mesh->tris[i] < 0 || mesh->tris[i] >= mesh->n_verts) return fail(ROFT_ERR_INVALID, "mesh: a triangle refers to a vertex outside the vertex array");
+    auto has_mesh = [&](int k) { return meshes[k].n_verts > 0 && meshes[k].n_tris > 0; };
+    for (int k = 0; k < n; ++k) {
+        if (!has_mesh(k)) continue;
+        const roft_mesh& m = meshes[k];
+        if (!m.verts || !m.tris) return fail(ROFT_ERR_INVALID, "mesh: null vertex or triangle array");
+        for (size_t i = 0; i < (size_t)3 * m.n_tris; ++i)
+            if (m.tris[i] < 0 || m.tris[i] >= m.n_verts) return fail(ROFT_ERR_INVALID, "mesh: a triangle refers to a vertex outside the vertex array");
+    }
     if (roft_device_count() <= 0) return fail(ROFT_ERR_DEVICE, "no HIP device (libroft_hip has no CPU path)");
     if (int rc = check_geometry(cam->width, cam->height)) return rc;
     OpCtx& c = op();
@@ -404,40 +409,50 @@ int roft_pose_silhouette(const roft_camera* cam, const roft_mesh* mesh, const do
     if (!c.stream) HIP_TRY(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
     const DevCamera dc = make_cam(*cam);
     const size_t npix = (size_t)cam->width * cam->height, plane_words = (size_t)dc.wpr * dc.H;
-    DevBuf<unsigned char> d_verts, d_tris, d_flip, d_mask;
+    std::vector<DevBuf<unsigned char>> d_verts((size_t)n), d_tris((size_t)n), d_flip((size_t)n);
+    DevBuf<unsigned char> d_mask;
     DevBuf<uint32_t> d_planes;
     DevBuf<MaskRec> d_rec;
     DevBuf<FrameCtrl> d_ctrl;
     DevBuf<ObjParams> d_prm;
-    ObjParams prm;
-    std::memset(&prm, 0, sizeof(prm));
-    PreparedMesh pm;
-    if (has_mesh) {
-        prepare_mesh(mesh->verts, mesh->n_verts, mesh->tris, mesh->n_tris, pm);
-        if (int rc = to_dev(d_verts, mesh->verts, (size_t)3 * mesh->n_verts, c.stream)) return rc;
-        if (int rc = to_dev(d_tris, pm.tris(mesh->tris), (size_t)3 * mesh->n_tris, c.stream)) return rc;
-        if (pm.closed)
-            if (int rc = to_dev(d_flip, pm.flip.data(), (size_t)mesh->n_tris, c.stream)) return rc;
-        prm.verts = reinterpret_cast<const float*>(d_verts.p);
-        prm.tris = reinterpret_cast<const int32_t*>(d_tris.p);
-        prm.tri_flip = pm.closed ? reinterpret_cast<const uint8_t*>(d_flip.p) : nullptr;
-        prm.n_verts = mesh->n_verts;
-        prm.n_tris = mesh->n_tris;
+    DevBuf<unsigned long long> d_zbuf, d_zstats;
+    DevBuf<SilhouettePair> d_zpairs;
+    std::vector<ObjParams> prm((size_t)n);
+    std::vector<FrameCtrl> fc((size_t)n);
+    std::memset(prm.data(), 0, sizeof(ObjParams) * prm.size());
+    int max_verts = 0;
+    for (int k = 0; k < n; ++k) {
+        if (has_mesh(k)) {
+            const roft_mesh& m = meshes[k];
+            PreparedMesh pm;
+            prepare_mesh(m.verts, m.n_verts, m.tris, m.n_tris, pm);
+            if (int rc = to_dev(d_verts[k], m.verts, (size_t)3 * m.n_verts, c.stream)) return rc;
+            if (int rc = to_dev(d_tris[k], pm.tris(m.tris), (size_t)3 * m.n_tris, c.stream)) return rc;
+            if (pm.closed)
+                if (int rc = to_dev(d_flip[k], pm.flip.data(), (size_t)m.n_tris, c.stream)) return rc;
+            HIP_TRY(hipStreamSynchronize(c.stream));   // (pm lives in this iteration)
+            prm[k].verts = reinterpret_cast<const float*>(d_verts[k].p);
+            prm[k].tris = reinterpret_cast<const int32_t*>(d_tris[k].p);
+            prm[k].tri_flip = pm.closed ? reinterpret_cast<const uint8_t*>(d_flip[k].p) : nullptr;
+            prm[k].n_verts = m.n_verts;
+            prm[k].n_tris = m.n_tris;
+            max_verts = std::max(max_verts, m.n_verts);
+        }
+        clear_ctrl(fc[k]);
+        fc[k].has_new_mask = 1;
+        fc[k].label_type = kMaskFromPose;
+        fc[k].label = n > 1 ? 1 : 0;   // (z-buffer 0 of the frame)
+        for (int i = 0; i < 3; ++i) fc[k].pose_x[i] = x[3 * k + i];
+        for (int i = 0; i < 4; ++i) fc[k].pose_q[i] = q[4 * k + i];
     }
-    FrameCtrl fc;
-    clear_ctrl(fc);
-    fc.has_new_mask = 1;
-    fc.label_type = kMaskFromPose;
-    for (int i = 0; i < 3; ++i) fc.pose_x[i] = x[i];
-    for (int i = 0; i < 4; ++i) fc.pose_q[i] = q[i];
-    HIP_TRY(d_ctrl.ensure(1));
-    HIP_TRY(d_prm.ensure(1));
-    HIP_TRY(d_planes.ensure(2 * plane_words));
-    HIP_TRY(d_rec.ensure(2));
-    HIP_TRY(hipMemcpyAsync(d_ctrl.p, &fc, sizeof(fc), hipMemcpyHostToDevice, c.stream));
-    HIP_TRY(hipMemcpyAsync(d_prm.p, &prm, sizeof(prm), hipMemcpyHostToDevice, c.stream));
-    HIP_TRY(hipMemsetAsync(d_planes.p, 0xA5, sizeof(uint32_t) * 2 * plane_words, c.stream));   // (stale words, as an engine's ingest slot holds)
-    HIP_TRY(hipMemsetAsync(d_rec.p, 0, sizeof(MaskRec) * 2, c.stream));
+    HIP_TRY(d_ctrl.ensure((size_t)n));
+    HIP_TRY(d_prm.ensure((size_t)n));
+    HIP_TRY(d_planes.ensure((size_t)n * 2 * plane_words));
+    HIP_TRY(d_rec.ensure((size_t)2 * n));
+    HIP_TRY(hipMemcpyAsync(d_ctrl.p, fc.data(), sizeof(FrameCtrl) * n, hipMemcpyHostToDevice, c.stream));
+    HIP_TRY(hipMemcpyAsync(d_prm.p, prm.data(), sizeof(ObjParams) * n, hipMemcpyHostToDevice, c.stream));
+    HIP_TRY(hipMemsetAsync(d_planes.p, 0xA5, sizeof(uint32_t) * (size_t)n * 2 * plane_words, c.stream));   // (stale words, as an engine's ingest slot holds)
+    HIP_TRY(hipMemsetAsync(d_rec.p, 0, sizeof(MaskRec) * 2 * n, c.stream));
     SilhouetteArgs sa{};
     sa.ctrl = d_ctrl.p;
     sa.params = d_prm.p;
@@ -446,24 +461,51 @@ int roft_pose_silhouette(const roft_camera* cam, const roft_mesh* mesh, const do
     sa.obj_stride = 2 * plane_words;
     sa.slot0 = 0;
     sa.mrec = d_rec.p;
-    sa.n_obj = 1;
+    sa.n_obj = n;
     sa.W = dc.W; sa.H = dc.H; sa.wpr = dc.wpr;
     sa.fx = (float)dc.fx; sa.fy = (float)dc.fy; sa.cx = (float)dc.cx; sa.cy = (float)dc.cy;   // (divider 1: the camera as it is)
     sa.frames_packed = 0u;
-    if (!launch_pose_silhouette(sa, 1, prm.n_verts, bands, vertex_cache, c.stream))
+    if (n > 1) {
+        HIP_TRY(d_zbuf.ensure(npix));
+        HIP_TRY(d_zpairs.ensure((size_t)n));
+        HIP_TRY(d_zstats.ensure(2));
+        HIP_TRY(hipMemsetAsync(d_zpairs.p, 0, sizeof(SilhouettePair) * n, c.stream));
+        HIP_TRY(hipMemsetAsync(d_zstats.p, 0, sizeof(unsigned long long) * 2, c.stream));
+        sa.zbuf = d_zbuf.p;
+        sa.n_zscenes = 1;
+        sa.zpairs = d_zpairs.p;
+        sa.zstats = d_zstats.p;
+    }
+    if (!launch_pose_silhouette(sa, 1, max_verts, bands, vertex_cache, c.stream))
         return fail(ROFT_ERR_INVALID, "pose silhouette: an image row is wider than the kernel's bit window");
     HIP_TRY(hipGetLastError());
-    if (mask_out) {
-        HIP_TRY(d_mask.ensure(npix));
-        launch_planes_to_mask(d_planes.p, d_planes.p + plane_words, (int)npix, d_mask.p, c.stream);
-        HIP_TRY(hipMemcpyAsync(mask_out, d_mask.p, npix, hipMemcpyDeviceToHost, c.stream));
+    if (masks_out) {
+        HIP_TRY(d_mask.ensure(npix * n));
+        for (int k = 0; k < n; ++k) {
+            const uint32_t* nz = d_planes.p + (size_t)k * 2 * plane_words;
+            launch_planes_to_mask(nz, nz + plane_words, (int)npix, d_mask.p + (size_t)k * npix, c.stream);
+        }
+        HIP_TRY(hipMemcpyAsync(masks_out, d_mask.p, npix * n, hipMemcpyDeviceToHost, c.stream));
     }
-    MaskRec rec[2];
-    HIP_TRY(hipMemcpyAsync(rec, d_rec.p, sizeof(rec), hipMemcpyDeviceToHost, c.stream));
-    HIP_TRY(hipStreamSynchronize(c.stream));   // (fc, prm and rec live on this stack)
+    std::vector<MaskRec> rec((size_t)2 * n);
+    HIP_TRY(hipMemcpyAsync(rec.data(), d_rec.p, sizeof(MaskRec) * rec.size(), hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));   // (fc, prm and rec live in this call)
     HIP_TRY(hipGetLastError());
-    if (count_out) *count_out = rec[1].new_count;   // (row t + 1 = 1)
+    if (counts_out)
+        for (int k = 0; k < n; ++k) counts_out[k] = rec[(size_t)n + k].new_count;   // (row t + 1 = 1)
     return ROFT_OK;
+}
+
+int roft_pose_silhouette(const roft_camera* cam, const roft_mesh* mesh, const double x[3], const double q[4], int bands, int vertex_cache,
+                         uint8_t* mask_out, int* count_out)
+{
+    return pose_silhouettes("roft_pose_silhouette", cam, mesh, 1, x, q, bands, vertex_cache, mask_out, count_out);
+}
+
+int roft_pose_silhouettes_occluded(const roft_camera* cam, const roft_mesh* meshes, int n, const double* x, const double* q, int bands,
+                                   int vertex_cache, uint8_t* masks_out, int* counts_out)
+{
+    return pose_silhouettes("roft_pose_silhouettes_occluded", cam, meshes, n, x, q, bands, vertex_cache, masks_out, counts_out);
 }
 
 int roft_pose_process_noise(const double psd[3], const double sig_w[3], double T, double Q[81])

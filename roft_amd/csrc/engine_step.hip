@@ -150,6 +150,7 @@ static int enqueue_preparation(Enqueue& q)
     // (the label table of the batch lies behind its control blocks and is copied with them)
     const size_t n16 = (sizeof(FrameCtrl) * (size_t)a.n_obj * a.T + (p.label_ingest ? pb.label_table_bytes : 0)) / 16;
     const hipEvent_t ctrl_stop = Enqueue::stop(p.ev_ctrl, q.cur.ev_ctrl);
+    const PrepLaunch last_launch = prep_last_launch(p, pb.facts.plain_mask_frames);
     // masks delivered as label images: one launch behind the per-object ingest (it ends with ev_prep where the plan has one and no
     // silhouette launch follows)
     auto label_ingest = [&]() -> int {
@@ -163,13 +164,14 @@ static int enqueue_preparation(Enqueue& q)
         la.mrec = a.mrec;
         la.n_obj = a.n_obj;
         la.n_grp = a.cam.W * a.cam.H / 64;
-        launch_label_ingest(la, (int)pb.label_sets.size(), sp, p.pose_silhouettes ? nullptr : Enqueue::stop(p.ev_prep, q.cur.ev_prep));
+        launch_label_ingest(la, (int)pb.label_sets.size(), sp, last_launch == PrepLaunch::label_ingest ? Enqueue::stop(p.ev_prep, q.cur.ev_prep) : nullptr);
         ++q.launches;
         CHECK_LAUNCH("label image ingest");
         return ROFT_OK;
     };
-    // masks from poses: one launch for every silhouette of the batch, the preparation's last.  It ends with ev_prep where the plan
-    // has one bound to a launch, else with an event of its own, which takes time stamps (roft_debug_pose_mask_kernel_ms).
+    // masks from poses: one launch for every silhouette of the batch, the preparation's last -- with silhouettes to resolve, the
+    // clear of this parity's z-buffers, the draw and the resolve.  The stage ends with ev_prep where the plan has one bound to a
+    // launch, else with an event of its own, which takes time stamps (roft_debug_pose_mask_kernel_ms: draw to resolve).
     auto pose_silhouettes = [&]() -> int {
         EnginePoseMasks& pm = e->pose_masks;
         SilhouetteArgs sa{};
@@ -186,15 +188,23 @@ static int enqueue_preparation(Enqueue& q)
         int n_frames = 0;
         for (int t = 0; t < a.T && t < 8; ++t)
             if (pb.pose_mask_frames & (1u << t)) sa.frames_packed |= (unsigned)t << (4 * n_frames++);
+        if (p.pose_resolve) {
+            const int par = e->batch_counter & 1;
+            sa.n_zscenes = pm.n_zscenes;
+            sa.zbuf = pm.zbuf.p + (size_t)par * kMaxBatch * pm.n_zscenes * a.cam.W * a.cam.H;
+            sa.zpairs = pm.zpairs.p + (size_t)par * kMaxBatch * e->cfg.max_objects;
+            sa.zstats = pm.zstats.p;
+        }
         const int slot = e->batch_counter % roft_engine::kBatchRing;
         const hipEvent_t plan_stop = Enqueue::stop(p.ev_prep, q.cur.ev_prep);
         if (!p.prep) tmark(e, nullptr, 0);   // (timing runs: a mark of its own on the mask stream; ahead on the upload stream it is part of mask_prepare)
-        if (!launch_pose_silhouette(sa, n_frames, a.max_verts, 0, 1, sp, pm.ev_start[slot], plan_stop ? plan_stop : pm.ev_stop[slot]))
+        const int launched = launch_pose_silhouette(sa, n_frames, a.max_verts, 0, 1, sp, pm.ev_start[slot], plan_stop ? plan_stop : pm.ev_stop[slot]);
+        if (launched != pose_silhouette_launches(p))
             return fail(ROFT_ERR_INVALID, "pose masks: the image does not fit the kernel's bit window");
         pm.last_slot = slot;
         pm.last_timed = plan_stop == nullptr;
-        ++q.launches;
-        CHECK_LAUNCH("pose silhouettes");
+        q.launches += launched;
+        CHECK_LAUNCH(p.pose_resolve ? "pose silhouettes: clear, draw and resolve" : "pose silhouettes");
         if (!p.prep) tmark(e, "pose_silhouettes", 0);
         return ROFT_OK;
     };
@@ -213,7 +223,7 @@ static int enqueue_preparation(Enqueue& q)
         if (pb.facts.plain_mask_frames & (1u << t)) last = t;
     for (int t = 0; t <= last; ++t)
         if (pb.facts.plain_mask_frames & (1u << t)) {
-            launch_mask_ingest(a, t, sp, (t == last && !p.label_ingest && !p.pose_silhouettes) ? Enqueue::stop(p.ev_prep, q.cur.ev_prep) : nullptr);
+            launch_mask_ingest(a, t, sp, (t == last && last_launch == PrepLaunch::mask_ingest) ? Enqueue::stop(p.ev_prep, q.cur.ev_prep) : nullptr);
             ++q.launches;
         }
     CHECK_LAUNCH("mask ingest");

@@ -699,6 +699,22 @@ static int submit_frames(roft_engine* e, const roft_frame_input* inputs, const r
             o.frame_idx++;
         }
     }
+    // silhouettes of one scene hide each other: a pair that shares its frame with another drawn member of its scene is drawn against
+    // the scene's z-buffer (FrameCtrl::label = 1 + z-buffer); a member drawn alone on its frame stays a plain silhouette
+    if (e->pose_masks.occlusion && e->pose_masks.n_zscenes > 0 && pb.pose_mask_frames) {
+        std::vector<int> drawn((size_t)e->pose_masks.n_zscenes);
+        for (int t = 0; t < T; ++t) {
+            if (!(pb.pose_mask_frames & (1u << t))) continue;
+            std::fill(drawn.begin(), drawn.end(), 0);
+            for (int id = 0; id < n_obj; ++id)
+                if (blk[(size_t)t * n_obj + id].label_type == kMaskFromPose && e->objs[id]->pose_zscene >= 0) drawn[e->objs[id]->pose_zscene]++;
+            for (int id = 0; id < n_obj; ++id) {
+                FrameCtrl& c = blk[(size_t)t * n_obj + id];
+                const int z = e->objs[id]->pose_zscene;
+                if (c.label_type == kMaskFromPose && z >= 0 && drawn[z] >= 2) { c.label = 1 + z; pb.facts.pose_resolve++; }
+            }
+        }
+    }
     // the label table behind the batch's control blocks: the sets, then (16-byte aligned) the members set by set
     if (!pb.label_sets.empty()) {
         unsigned char* tab = reinterpret_cast<unsigned char*>(blk + (size_t)T * n_obj);
@@ -787,6 +803,7 @@ int roft_frames_submit_images(roft_engine* e, const roft_frame_input* inputs, co
     e->device_pointers_checked = true;
     e->pose_masks.stats.silhouettes += pb.facts.pose_masks;
     e->pose_masks.stats.frames += __builtin_popcount(pb.pose_mask_frames);
+    e->pose_masks.occl_stats.resolved += pb.facts.pose_resolve;
     pb.submit_us = host_now_us() - pb.submit_t0;
     return ROFT_OK;
 }
@@ -881,6 +898,69 @@ int roft_engine_get_pose_mask_stats(roft_engine* e, roft_engine_pose_mask_stats*
 {
     if (!e || !out) return fail(ROFT_ERR_INVALID, "null argument");
     *out = e->pose_masks.stats;
+    return ROFT_OK;
+}
+
+// Objects of one scene hide each other.  Scenes with at least two members get a z-buffer each; everything the hot path touches is
+// allocated here.
+int roft_engine_enable_pose_mask_occlusion(roft_engine* e, const int* obj_ids, const int* scene_ids, int n_ids)
+{
+    if (!e) return fail(ROFT_ERR_INVALID, "null engine");
+    if (n_ids < 0 || (n_ids > 0 && (!obj_ids || !scene_ids)))
+        return fail(ROFT_ERR_INVALID, "pose mask occlusion: n_ids object ids and scene ids required (n_ids 0: every enrolled object in scene 0)");
+    if (e->frame_counter > 0 || e->submitted) return fail(ROFT_ERR_STATE, "roft_engine_enable_pose_mask_occlusion must precede the first frame");
+    EnginePoseMasks& pm = e->pose_masks;
+    if (!pm.enabled) return fail(ROFT_ERR_STATE, "pose mask occlusion: roft_engine_enable_pose_masks comes first");
+    auto enrolled = [&](int id) { return e->objs[id]->pose_masks || (pm.all && e->h_params[id].n_verts > 0 && e->h_params[id].n_tris > 0); };
+    for (int i = 0; i < n_ids; ++i) {
+        const int id = obj_ids[i];
+        if (id < 0 || id >= (int)e->objs.size()) return fail(ROFT_ERR_INVALID, "pose mask occlusion: " + std::to_string(id) + " is not an object of the engine");
+        if (!enrolled(id)) return fail(ROFT_ERR_INVALID, "pose mask occlusion: object " + std::to_string(id) + " is not enrolled with roft_engine_enable_pose_masks");
+        if (scene_ids[i] < 0) return fail(ROFT_ERR_INVALID, "pose mask occlusion: scene ids are >= 0");
+    }
+    // the scenes as they will be, and a z-buffer for each that has at least two members
+    const int n = (int)e->objs.size();
+    std::vector<int> scene((size_t)n), zscene((size_t)n, -1);
+    for (int id = 0; id < n; ++id) scene[id] = (n_ids == 0 && enrolled(id)) ? 0 : e->objs[id]->pose_scene;
+    for (int i = 0; i < n_ids; ++i) scene[obj_ids[i]] = scene_ids[i];
+    int n_z = 0;
+    for (int id = 0; id < n; ++id) {
+        if (scene[id] < 0 || zscene[id] >= 0) continue;
+        int members = 0;
+        for (int k = id; k < n; ++k) members += scene[k] == scene[id];
+        if (members < 2) continue;
+        for (int k = id; k < n; ++k)
+            if (scene[k] == scene[id]) zscene[k] = n_z;
+        ++n_z;
+    }
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    if (n_z > 0) {
+        HIP_TRY(pm.zbuf.ensure((size_t)2 * kMaxBatch * n_z * e->cfg.cam.width * e->cfg.cam.height));
+        HIP_TRY(pm.zpairs.ensure((size_t)2 * kMaxBatch * e->cfg.max_objects));
+        HIP_TRY(hipMemset(pm.zpairs.p, 0, sizeof(SilhouettePair) * pm.zpairs.n));
+    }
+    HIP_TRY(pm.zstats.ensure(2, true));
+    for (int id = 0; id < n; ++id) { e->objs[id]->pose_scene = scene[id]; e->objs[id]->pose_zscene = zscene[id]; }
+    pm.n_zscenes = n_z;
+    pm.occlusion = true;
+    return ROFT_OK;
+}
+
+// (hidden and pixels_removed are counted by the resolve on the device: the call waits for the batches stepped so far)
+int roft_engine_get_pose_mask_occlusion_stats(roft_engine* e, roft_engine_pose_mask_occlusion_stats* out)
+{
+    if (!e || !out) return fail(ROFT_ERR_INVALID, "null argument");
+    EnginePoseMasks& pm = e->pose_masks;
+    if (pm.occlusion && pm.zstats.p) {
+        HIP_TRY(hipSetDevice(e->cfg.device));
+        HIP_TRY(hipStreamSynchronize(e->up_stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        unsigned long long h[2] = {0, 0};
+        HIP_TRY(hipMemcpy(h, pm.zstats.p, sizeof(h), hipMemcpyDeviceToHost));
+        pm.occl_stats.hidden = (long long)h[0];
+        pm.occl_stats.pixels_removed = (long long)h[1];
+    }
+    *out = pm.occl_stats;
     return ROFT_OK;
 }
 

@@ -23,6 +23,12 @@ namespace roft {
 
 constexpr int kSilhouetteThreads = 256;
 
+// kZ: the launch of a batch that has silhouettes to resolve (section 3e, "objects of one scene hide each other").  A pair whose
+// FrameCtrl::label names a z-buffer (1 + its index) is DRAWN here and not flushed: every covered pixel sends
+// (float bits of z) << 32 | obj through a 64-bit atomicMin to the z-buffer of its (delivering frame, scene) -- positive floats order
+// like their bit patterns, the low word is the tie rule "lower id" --, the bit window only counts the plain silhouette's pixels, and
+// the pair leaves its row box; pose_resolve_kernel below writes its planes.  Every other pair is drawn and flushed as without kZ.
+template <bool kZ>
 __global__ __launch_bounds__(kSilhouetteThreads) void pose_silhouette_kernel(SilhouetteArgs sa)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -72,6 +78,8 @@ __global__ __launch_bounds__(kSilhouetteThreads) void pose_silhouette_kernel(Sil
     }
     __syncthreads();
     const int box0 = s_rows[0], box1 = s_rows[1];
+    const bool to_z = kZ && c.label > 0;   // (workgroup-uniform)
+    unsigned long long* const zb = to_z ? sa.zbuf + ((size_t)blockIdx.z * sa.n_zscenes + (c.label - 1)) * ((size_t)W * H) : nullptr;
     const uint8_t* const flips = (prm.tri_flip && !s_behind) ? prm.tri_flip : nullptr;
 
     // the band's rows, strip by strip
@@ -86,8 +94,11 @@ __global__ __launch_bounds__(kSilhouetteThreads) void pose_silhouette_kernel(Sil
         const int j_lo = max(js, box0), j_hi = min(je, box1);
         if (j_lo <= j_hi) {
             ROFT_LDS uint32_t* const win = pin_lds(s_win);
-            auto store = [win, js, wpr](int i, int j, float) {
+            auto store = [win, js, wpr, zb, W, obj](int i, int j, float z) {
                 (void)__hip_atomic_fetch_or(win + ((j - js) * wpr + (i >> 5)), 1u << (i & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (kZ && zb)
+                    (void)__hip_atomic_fetch_min(zb + ((size_t)j * W + i), ((unsigned long long)__float_as_uint(z) << 32) | (unsigned)obj,
+                                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             };
             for (int k = tid; k < nt; k += kSilhouetteThreads) {
                 const int32_t* tri = prm.tris + (size_t)3 * k;
@@ -112,23 +123,97 @@ __global__ __launch_bounds__(kSilhouetteThreads) void pose_silhouette_kernel(Sil
         uint32_t* const ob = nz + sa.plane_words;
         for (int i = tid; i < n_words; i += kSilhouetteThreads) {
             const uint32_t w = s_win[i];
-            nz[i] = w;
-            ob[i] = w;
+            if (!to_z) { nz[i] = w; ob[i] = w; }
             count += __popc(w);
         }
         __syncthreads();   // the next strip clears the window
     }
     for (int off = 32; off > 0; off >>= 1) count += __shfl_xor(count, off, 64);
+    if (to_z) {
+        // what the resolve needs of the pair: the rows anything was drawn in, and the plain silhouette's pixels (for the statistics)
+        SilhouettePair& pr = sa.zpairs[(size_t)blockIdx.z * sa.n_obj + obj];
+        if ((tid & 63) == 0 && count) atomicAdd(&pr.raw, count);
+        if (band == 0 && tid == 0) { pr.box0 = box0; pr.box1 = box1; }
+        return;
+    }
     if ((tid & 63) == 0 && count) atomicAdd(&sa.mrec[(size_t)(t + 1) * sa.n_obj + obj].new_count, count);
+}
+
+// The resolve: same grid, behind the draw.  For its band and pair, a workgroup reads the z-buffer inside the pair's row box, sets
+// the bit where the low word is its object id -- the object is the nearest surface there, the lower id on an exact tie -- and
+// writes EVERY word of BOTH planes of slot slot0 + t, zeros included, and the population count to mrec[t + 1][obj].new_count:
+// what the flush above does for a plain silhouette.  A wave takes 64 consecutive pixels -- two plane words, W is a multiple of 32
+// and a band begins on a row -- as one ballot, four of them per round so that four loads are in flight.  The pair's last workgroup
+// (a ticket) adds the pair to the statistics and leaves its record zeroed for the next batch of this parity.
+__global__ __launch_bounds__(kSilhouetteThreads) void pose_resolve_kernel(SilhouetteArgs sa)
+{
+    __shared__ int s_count;
+    const int obj = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int t = (int)((sa.frames_packed >> (4 * blockIdx.z)) & 15u);
+    const FrameCtrl& c = sa.ctrl[(size_t)t * sa.n_obj + obj];
+    if (c.label_type != kMaskFromPose || c.label <= 0) return;   // (workgroup-uniform)
+    const int W = sa.W, H = sa.H;
+    SilhouettePair& pr = sa.zpairs[(size_t)blockIdx.z * sa.n_obj + obj];
+    const unsigned long long* const zb = sa.zbuf + ((size_t)blockIdx.z * sa.n_zscenes + (c.label - 1)) * ((size_t)W * H);
+    const int bands = (int)gridDim.x, band = (int)blockIdx.x;
+    const int r0 = (int)(((long long)band * H) / bands), r1 = (int)(((long long)(band + 1) * H) / bands) - 1;
+    const int p_begin = r0 * W, p_end = (r1 + 1) * W;   // (W * H < 2^24)
+    const int box0 = min(pr.box0, H), box1 = min(pr.box1, H - 1);   // (nothing drawn: INT32_MAX, -1)
+    const int b_begin = max(p_begin, box0 * W), b_end = min(p_end, (box1 + 1) * W);   // the box's pixels of this band
+    uint32_t* const nz = sa.planes + (size_t)obj * sa.obj_stride + (size_t)(sa.slot0 + t) * 2 * sa.plane_words;
+    uint32_t* const ob = nz + sa.plane_words;
+    if (tid == 0) s_count = 0;
+    __syncthreads();
+    int count = 0;
+    constexpr int kRound = 4;
+    for (int p0 = p_begin + wave * (64 * kRound); p0 < p_end; p0 += kSilhouetteThreads * kRound) {
+        unsigned long long v[kRound];
+#pragma unroll
+        for (int u = 0; u < kRound; ++u) {
+            const int p = p0 + 64 * u + lane;
+            v[u] = (p >= b_begin && p < b_end) ? zb[p] : ~0ull;
+        }
+#pragma unroll
+        for (int u = 0; u < kRound; ++u) {
+            const int p = p0 + 64 * u + lane;
+            const unsigned long long mine = __ballot((uint32_t)v[u] == (uint32_t)obj);   // (all-ones: nobody's)
+            if ((lane & 31) == 0 && p < p_end) {
+                const uint32_t w = lane ? (uint32_t)(mine >> 32) : (uint32_t)mine;
+                nz[p >> 5] = w;
+                ob[p >> 5] = w;
+                count += __popc(w);
+            }
+        }
+    }
+    count += __shfl_xor(count, 32, 64);
+    if (lane == 0 && count) atomicAdd(&s_count, count);
+    __syncthreads();
+    if (tid == 0) {
+        const int n = s_count;
+        if (n) {
+            atomicAdd(&sa.mrec[(size_t)(t + 1) * sa.n_obj + obj].new_count, n);
+            atomicAdd(&pr.kept, n);
+        }
+        __threadfence();
+        if (atomicAdd(&pr.done, 1) == bands - 1) {
+            __threadfence();
+            const int raw = atomicAdd(&pr.raw, 0), kept = atomicAdd(&pr.kept, 0);
+            if (raw > 0 && kept == 0) atomicAdd(&sa.zstats[0], 1ull);
+            if (raw > kept) atomicAdd(&sa.zstats[1], (unsigned long long)(raw - kept));
+            pr.raw = 0; pr.kept = 0; pr.done = 0;
+        }
+    }
 }
 
 // LDS of a workgroup: the projected vertices of the largest mesh where the cache is on and they fit it, and the bit window of one
 // strip -- the rows of a band, at most kSilhouetteWindowWords words.  A small mesh on a small image takes a few KB, so that several
 // workgroups share a CU with the chains the launch runs next to.
-bool launch_pose_silhouette(SilhouetteArgs sa, int n_frames, int max_verts, int bands, int vertex_cache, hipStream_t s, hipEvent_t start,
-                            hipEvent_t stop)
+// With a z-buffer (sa.zbuf: the batch has silhouettes to resolve) the stage is the clear of the z-buffers of its delivering frames
+// to all-ones, the draw and the resolve: `start` opens the draw, `stop` ends the resolve.
+int launch_pose_silhouette(SilhouetteArgs sa, int n_frames, int max_verts, int bands, int vertex_cache, hipStream_t s, hipEvent_t start,
+                           hipEvent_t stop)
 {
-    if (sa.wpr <= 0 || sa.wpr > kSilhouetteWindowWords || sa.H <= 0 || n_frames <= 0 || sa.n_obj <= 0) return false;
+    if (sa.wpr <= 0 || sa.wpr > kSilhouetteWindowWords || sa.H <= 0 || n_frames <= 0 || sa.n_obj <= 0) return 0;
     if (bands <= 0) bands = (sa.H + 63) / 64;
     bands = std::min(bands, std::min(sa.H, 1024));
     const int band_rows = (sa.H + bands - 1) / bands;   // (the tallest band)
@@ -136,9 +221,18 @@ bool launch_pose_silhouette(SilhouetteArgs sa, int n_frames, int max_verts, int 
     sa.vcache_cap = (vertex_cache && max_verts <= kSilhouetteCacheVerts) ? std::max(max_verts, 0) : 0;
     const size_t vbytes = ((size_t)sa.vcache_cap * 12 + 15) & ~(size_t)15;
     const size_t lds = vbytes + 4 * (size_t)sa.win_rows * sa.wpr;
-    (void)set_max_dynamic_lds(reinterpret_cast<const void*>(pose_silhouette_kernel), 160 * 1024 - 4096);
-    hipExtLaunchKernelGGL(pose_silhouette_kernel, dim3(bands, sa.n_obj, n_frames), dim3(kSilhouetteThreads), (uint32_t)lds, s, start, stop, 0, sa);
-    return true;
+    const dim3 grid(bands, sa.n_obj, n_frames);
+    if (!sa.zbuf) {
+        (void)set_max_dynamic_lds(reinterpret_cast<const void*>(pose_silhouette_kernel<false>), 160 * 1024 - 4096);
+        hipExtLaunchKernelGGL(pose_silhouette_kernel<false>, grid, dim3(kSilhouetteThreads), (uint32_t)lds, s, start, stop, 0, sa);
+        return 1;
+    }
+    if (sa.n_zscenes <= 0 || !sa.zpairs || !sa.zstats) return 0;
+    (void)hipMemsetAsync(sa.zbuf, 0xFF, sizeof(unsigned long long) * (size_t)n_frames * sa.n_zscenes * sa.W * sa.H, s);
+    (void)set_max_dynamic_lds(reinterpret_cast<const void*>(pose_silhouette_kernel<true>), 160 * 1024 - 4096);
+    hipExtLaunchKernelGGL(pose_silhouette_kernel<true>, grid, dim3(kSilhouetteThreads), (uint32_t)lds, s, start, nullptr, 0, sa);
+    hipExtLaunchKernelGGL(pose_resolve_kernel, grid, dim3(kSilhouetteThreads), 0, s, nullptr, stop, 0, sa);
+    return 2;
 }
 
 }  // namespace roft

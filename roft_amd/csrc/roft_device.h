@@ -158,7 +158,8 @@ struct alignas(16) FrameCtrl {
     int cur_slot;                    // B_LIN0 / B_LIN1: slot of p_corr_belief_ during this frame
     int label;                       // the delivered mask is the pixels of a LABEL IMAGE equal to this value (label_ingest_kernel
     int label_type;                  // writes its planes; the ordinary ingest skips the object): ROFT_LABEL_*, 0: new_mask as before;
-                                     // kMaskFromPose: the silhouette of the mesh at pose_x / pose_q (pose_silhouette_kernel)
+                                     // kMaskFromPose: the silhouette of the mesh at pose_x / pose_q (pose_silhouette_kernel); label is
+                                     // then 0, or 1 + the z-buffer the silhouette is resolved against (SilhouetteArgs)
 };
 
 // Mask chain record of one frame of the batch and one object (k_mask.hip).  Row t + 1 of EngineArrays::mrec belongs to
@@ -396,6 +397,14 @@ void launch_label_ingest(const LabelIngestArgs& la, int n_sets, hipStream_t s, h
 constexpr int kMaskFromPose = 3;
 constexpr int kSilhouetteCacheVerts = 8192;     // projected vertices a workgroup keeps in LDS (96 KB); a larger mesh is projected per triangle
 constexpr int kSilhouetteWindowWords = 8192;    // words of the LDS bit window (32 KB): a band with more rows is drawn in strips
+// Silhouettes of one scene hide each other (section 3e): what a (delivering frame, object) pair that is drawn against a z-buffer
+// leaves between the draw and the resolve.  The resolve's last workgroup zeroes the record again.
+struct SilhouettePair {
+    int box0, box1;              // first and last image row anything of the object can be drawn in
+    int raw;                     // pixels of the plain silhouette
+    int kept;                    // pixels of the resolved one
+    int done;                    // workgroups of the resolve that have finished (a ticket)
+};
 // what pose_silhouette_kernel reads and where it writes: like LabelIngestArgs, the engine's layout or a compact one (operator)
 struct SilhouetteArgs {
     const FrameCtrl* ctrl;       // [T][n_obj]: label_type (kMaskFromPose: the pair is drawn, else its workgroups leave), pose_x, pose_q
@@ -410,10 +419,17 @@ struct SilhouetteArgs {
     unsigned frames_packed;      // four bits per delivering frame of the batch, lowest first (grid z)
     int vcache_cap;              // vertices the LDS cache holds (0: project per triangle)
     int win_rows;                // rows of the LDS bit window
+    // silhouettes to resolve (null / 0: none in this launch).  FrameCtrl::label of a kMaskFromPose pair: 0 = drawn alone,
+    // 1 + z = drawn against z-buffer z of its delivering frame
+    unsigned long long* zbuf;    // [delivering frame (grid z)][n_zscenes][H * W]: (float bits of z) << 32 | obj, all-ones = nothing drawn
+    int n_zscenes;
+    SilhouettePair* zpairs;      // [delivering frame (grid z)][n_obj], zero between launches
+    unsigned long long* zstats;  // [2]: silhouettes that lost every pixel; pixels removed (accumulated)
 };
 // every (delivering frame, enrolled object) pair of a batch in ONE launch (grid: bands x objects x delivering frames).  bands 0: one
-// per 64 image rows; vertex_cache 0: project per triangle.  Neither changes a bit.  false: not launched (an image row wider than the window)
-bool launch_pose_silhouette(SilhouetteArgs sa, int n_frames, int max_verts, int bands, int vertex_cache, hipStream_t s,
+// per 64 image rows; vertex_cache 0: project per triangle.  Neither changes a bit.  With sa.zbuf the clear of the z-buffers, the draw
+// and the resolve.  Returns the number of kernel launches; 0: not launched (an image row wider than the window)
+int launch_pose_silhouette(SilhouetteArgs sa, int n_frames, int max_verts, int bands, int vertex_cache, hipStream_t s,
                             hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 // Zeroes what the ingest kernels accumulate into: the counters of mrec rows 1 .. T (mask_general is cleared by its only
 // reader, mask_general_kernel: this reset may run while the chain before still sets bits).

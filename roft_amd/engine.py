@@ -308,6 +308,27 @@ class ROFTFilterBatch:
         L.check(L.lib().roft_engine_get_pose_mask_stats(self._h, C.byref(st)))
         return {k: getattr(st, k) for k, _ in L.EnginePoseMaskStats._fields_}
 
+    def enable_pose_mask_occlusion(self, scene_of=None):
+        """Enrolled objects of one scene hide each other's silhouettes (roft_engine_enable_pose_mask_occlusion): each keeps the
+        pixels where it is the nearest surface.  scene_of: a dict object id -> scene, or a sequence whose entry i is the scene of
+        object i; None: every enrolled object shares scene 0.  After enable_pose_masks, before the first frame."""
+        if scene_of is None:
+            L.check(L.lib().roft_engine_enable_pose_mask_occlusion(self._h, None, None, 0))
+            return
+        pairs = sorted(scene_of.items()) if isinstance(scene_of, dict) else list(enumerate(scene_of))
+        if not pairs:
+            raise ValueError("scene_of names no object (None: every enrolled object shares scene 0)")
+        ids = np.ascontiguousarray([p[0] for p in pairs], np.int32)
+        scenes = np.ascontiguousarray([p[1] for p in pairs], np.int32)
+        ip = C.POINTER(C.c_int)
+        L.check(L.lib().roft_engine_enable_pose_mask_occlusion(self._h, ids.ctypes.data_as(ip), scenes.ctypes.data_as(ip), len(ids)))
+
+    def pose_mask_occlusion_stats(self):
+        """silhouettes resolved / of those hidden entirely / pixels removed, since the engine was created (waits for the device)."""
+        st = L.EnginePoseMaskOcclusionStats()
+        L.check(L.lib().roft_engine_get_pose_mask_occlusion_stats(self._h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in L.EnginePoseMaskOcclusionStats._fields_}
+
     def pose_mask_kernel_ms(self):
         """Device time (ms, HIP events on its dispatch) of the last silhouette launch."""
         ms = C.c_double(0.0)

@@ -134,6 +134,27 @@ def pose_silhouette(cam, mesh, x, q, bands=0, vertex_cache=True):
     return mask, count.value
 
 
+def pose_silhouettes_occluded(cam, meshes, xs, qs, bands=0, vertex_cache=True):
+    """The masks {0, 255} [n, H, W] and the pixel counts [n] of n meshes of ONE scene at the poses (xs [n, 3], qs [n, 4] = w x y z),
+    each keeping the pixels where it is the nearest surface -- the lower index on an exact tie -- by the engine's own kernels
+    (roft_pose_silhouettes_occluded; the contract: include/roft_engine.h, section 3e).  bands and vertex_cache as for
+    pose_silhouette: neither changes a bit.  meshes: a sequence of (verts, tris) array pairs, as for pose_silhouette."""
+    L.require_device()
+    n = len(meshes)
+    xs, qs = _f64(np.asarray(xs).reshape(n, 3)), _f64(np.asarray(qs).reshape(n, 4))
+    keep, arr = [], (L.Mesh * max(n, 1))()
+    for k, m in enumerate(meshes):
+        verts = np.ascontiguousarray(m[0], np.float32).reshape(-1, 3)
+        tris = np.ascontiguousarray(m[1], np.int32).reshape(-1, 3)
+        keep.append((verts, tris))
+        arr[k] = L.Mesh(verts.ctypes.data, verts.shape[0], tris.ctypes.data, tris.shape[0])
+    masks = np.zeros((n, cam.height, cam.width), np.uint8)
+    counts = np.zeros(n, np.int32)
+    L.check(L.lib().roft_pose_silhouettes_occluded(C.byref(cam), arr, n, _p(xs), _p(qs), int(bands), 1 if vertex_cache else 0, _p(masks),
+                                                   counts.ctypes.data_as(C.POINTER(C.c_int))))
+    return masks, counts
+
+
 def process_noise(psd, sig_w, T):
     Q = np.zeros((9, 9))
     L.check(L.lib().roft_pose_process_noise(_p(_f64(psd)), _p(_f64(sig_w)), T, _p(Q)))

@@ -19,6 +19,17 @@ run, and -- on engines created with ROFT_PREP_AHEAD=2, where the preparation run
 summarised by tools/marks_timeline.py into FILE: where the launch sits in a burst and in the steady state.
 
 Writes profiles/r14_pose_masks.json.
+
+--occlusion: the shared scene with poses laid out so that the objects OVERLAP (an 8-column grid of offsets around the stream's
+pose, staggered in depth), three forms of the host leg alternated in one process, --runs rounds, medians:
+  * occlusion  the objects enrolled and declared one scene (roft_engine_enable_pose_mask_occlusion): each keeps the pixels where it
+               is the nearest surface;
+  * pose       the objects enrolled without the mode (plain silhouettes: other masks, the same work elsewhere);
+  * masks      the RESOLVED silhouettes -- the CPU oracle's renders resolved in numpy by the header's definition -- uploaded as
+               per-object HOST masks: the caller the mode replaces.  Its log must equal the occlusion form's.
+An instrumented pass reads the silhouette stage's device time (roft_debug_pose_mask_kernel_ms: draw + resolve) per delivering batch
+with the mode on and off.  Prints the share of the plain silhouettes' pixels the resolve removed.  Writes
+profiles/r15_pose_mask_occlusion.json.
 """
 import argparse
 import json
@@ -43,7 +54,12 @@ def main():
     p.add_argument("--scale", type=int, default=1, help="divide the 640 x 480 camera (a quick look on a small shape)")
     p.add_argument("--marks", default=os.path.join(ROOT, "profiles", "r14_marks_timeline.txt"))
     p.add_argument("--out", default=os.path.join(ROOT, "profiles", "r14_pose_masks.json"))
+    p.add_argument("--occlusion", action="store_true", help="the three forms of the overlapping shared scene (see above)")
     args = p.parse_args()
+    if args.occlusion:
+        if args.out.endswith("r14_pose_masks.json"):
+            args.out = os.path.join(ROOT, "profiles", "r15_pose_mask_occlusion.json")
+        return occlusion(args)
 
     import torch
     from roft_amd import _lib as L
@@ -230,6 +246,141 @@ def main():
     print("mask_prepare", json.dumps({k: v.get("mask_prepare") for k, v in timing.items() if k.endswith("_prep_ahead")}))
     if not same:
         raise SystemExit("bench_pose_masks.py: the two forms did not track to identical poses")
+
+
+def occlusion(args):
+    import torch
+    from oracle import binding as ob
+    from roft_amd import _lib as L
+    from roft_amd import engine as E
+    from roft_amd import ops, synth
+
+    L.require_device()
+    dev = torch.device("cuda", 0)
+    cam = synth.Camera.shape_a()
+    if args.scale > 1:
+        cam = cam.scaled(args.scale)
+    n_obj, T = args.objects, max(1, min(args.batch, L.MAX_BATCH_FRAMES))
+    n_run = T + args.frames
+    st = synth.make_stream(4000, n_run, cam, flow_type=synth.FLOW_F32C2, device=dev, mesh_n=12)
+    W, H = cam.width, cam.height
+    verts, tris = st.mesh
+    depth_h = st.depth[:n_run].cpu().pin_memory()
+    flow_h = st.flow[:n_run].cpu().pin_memory()
+    deliveries = [k for k in range(n_run) if st.pose_valid[k]]
+    # object o: the stream's pose moved to column o % 8, row o // 8 of a grid whose step is a third of the box, staggered in depth
+    offsets = np.array([[(o % 8 - 3.5) * 0.06, (o // 8 - 3.5) * 0.045, 0.02 * ((o * 37) % 64) / 8.0] for o in range(n_obj)])
+
+    def pose_of(k, o):
+        return st.pose_meas[k, :3] + offsets[o], st.pose_meas[k, 3:]
+
+    o_mesh, o_cam = ob.make_mesh(verts, tris), ob.camera(W, H, cam.fx, cam.fy, cam.cx, cam.cy)
+    resolved, raw_pixels, kept_pixels, hidden = {}, 0, 0, 0
+    for k in deliveries:
+        R = np.stack([np.array(ob.render_depth(o_mesh, *pose_of(k, o), o_cam, 1), np.float32) for o in range(n_obj)])
+        raw = R > 0
+        res = raw & (np.argmin(np.where(raw, R, np.float32(np.inf)), axis=0)[None] == np.arange(n_obj)[:, None, None])
+        resolved[k] = torch.from_numpy(np.ascontiguousarray(res.astype(np.uint8) * 255)).pin_memory()
+        raw_pixels += int(raw.sum())
+        kept_pixels += int(res.sum())
+        hidden += int((raw.any(axis=(1, 2)) & ~res.any(axis=(1, 2))).sum())
+    k0 = deliveries[0]
+    got = ops.pose_silhouettes_occluded(L.Camera(W, H, cam.fx, cam.fy, cam.cx, cam.cy), [(verts, tris)] * n_obj,
+                                        [pose_of(k0, o)[0] for o in range(n_obj)], [pose_of(k0, o)[1] for o in range(n_obj)])[0]
+    operator_agrees = bool(np.array_equal(got, resolved[k0].numpy()))
+    batches_kt = [(b, min(T, n_run - b)) for b in range(0, n_run, T)]
+
+    def leg(form, timing=False):
+        cfg = E.default_config(W, H, st.flow_type, max_objects=n_obj, max_batch_frames=T)
+        cfg.cam.fx, cfg.cam.fy, cfg.cam.cx, cfg.cam.cy = cam.fx, cam.fy, cam.cx, cam.cy
+        eng = E.ROFTFilterBatch(cfg)
+        for o in range(n_obj):
+            d = E.default_object()
+            x0, q0 = pose_of(0, o)
+            for i in range(13):
+                d.p_mean0[i] = 0.0 if i < 6 else (x0[i - 6] if i < 9 else q0[i - 9])
+            eng.add_object(d, verts, tris)
+        if form != "masks":
+            eng.enable_pose_masks()
+        if form == "occlusion":
+            eng.enable_pose_mask_occlusion()
+        eng.enable_log(n_run)
+        batches = []
+        for b, t in batches_kt:
+            fl = []
+            for k in range(b, b + t):
+                row = []
+                for o in range(n_obj):
+                    f = dict(depth=depth_h[k].data_ptr(), flow=flow_h[k].data_ptr() if st.flow_valid[k] else None, mask=None,
+                             pose=pose_of(k, o) if st.pose_valid[k] else None, dt=st.dt, mem_kind=L.MEM_HOST)
+                    if form == "masks" and k in resolved:
+                        f["mask"] = resolved[k][o].data_ptr()
+                    row.append(f)
+                fl.append(row)
+            batches.append(eng.build_batch(fl))
+        eng.submit_batch_raw(batches[0][0], batches[0][2])
+        eng.step()
+        eng.sync()
+        if timing:
+            eng.enable_timing(2)
+        stage_us, last_drawn = [], eng.pose_mask_stats()["silhouettes"]
+        s0 = eng.stats()
+        t1 = time.perf_counter()
+        for arr, _keep, t in batches[1:]:
+            eng.submit_batch_raw(arr, t)
+            eng.step()
+            if timing:
+                drawn = eng.pose_mask_stats()["silhouettes"]
+                if drawn != last_drawn:
+                    last_drawn = drawn
+                    stage_us.append(1e3 * eng.pose_mask_kernel_ms())
+        eng.sync()
+        dt = time.perf_counter() - t1
+        s1 = eng.stats()
+        frames = s1["frames"] - s0["frames"]
+        res = dict(value=n_obj * frames / dt, unit="object-frames/s", ms_per_step=1e3 * dt / frames,
+                   h2d_MB_per_step=(s1["h2d_bytes"] - s0["h2d_bytes"]) / frames / 1e6, launches_per_step=(s1["launches"] - s0["launches"]) / frames,
+                   rows=eng.get_log_rows(0, n_run))
+        if timing:
+            res["stage_us"] = dict(median=float(np.median(stage_us)), min=float(np.min(stage_us)), max=float(np.max(stage_us)), n=len(stage_us))
+        if form == "occlusion":
+            res["occlusion_stats"] = eng.pose_mask_occlusion_stats()
+        eng.close()
+        return res
+
+    forms = ("occlusion", "pose", "masks")
+    runs, rows, stats = {f: [] for f in forms}, {}, None
+    for _ in range(args.runs):
+        for form in forms:
+            r = leg(form)
+            rows.setdefault(form, r.pop("rows"))
+            r.pop("rows", None)
+            stats = r.pop("occlusion_stats", stats)
+            runs[form].append(r)
+    same = bool(np.array_equal(rows["occlusion"], rows["masks"], equal_nan=True))
+    out = dict(config=dict(objects=n_obj, width=W, height=H, batch=T, timed_frames=args.frames, runs=args.runs, flow="CV_32FC2",
+                           mesh_vertices=int(verts.shape[0]), mesh_triangles=int(tris.shape[0]), deliveries=len(deliveries)),
+               oracle=dict(silhouettes=len(deliveries) * n_obj, hidden=hidden, pixels_plain=raw_pixels, pixels_resolved=kept_pixels,
+                           share_removed=1.0 - kept_pixels / max(raw_pixels, 1)),
+               engine_stats=stats, identical_results=same, operator_equals_oracle=operator_agrees)
+    for form in forms:
+        rs = sorted(runs[form], key=lambda r: r["value"])
+        out[form] = dict(rs[len(rs) // 2], runs=[r["value"] for r in runs[form]])
+    out["ratio_occlusion_over_masks"] = out["occlusion"]["value"] / out["masks"]["value"]
+    out["ratio_occlusion_over_pose"] = out["occlusion"]["value"] / out["pose"]["value"]
+    out["stage_us"] = {form: leg(form, timing=True)["stage_us"] for form in ("occlusion", "pose")}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps({k: out[k] for k in ("config", "oracle", "engine_stats", "identical_results", "operator_equals_oracle")}))
+    for form in forms:
+        print(form, json.dumps({k: out[form][k] for k in ("value", "h2d_MB_per_step", "ms_per_step", "launches_per_step", "runs")}))
+    print("ratio occlusion / masks %.3f, occlusion / pose %.3f, share of pixels removed %.3f" %
+          (out["ratio_occlusion_over_masks"], out["ratio_occlusion_over_pose"], out["oracle"]["share_removed"]))
+    print("stage_us", json.dumps(out["stage_us"]))
+    if not same:
+        raise SystemExit("bench_pose_masks.py --occlusion: the occlusion form and the resolved host masks did not track to identical poses")
 
 
 if __name__ == "__main__":
