@@ -25,7 +25,7 @@ __global__ __launch_bounds__(kQualityThreads) void quality_kernel(EngineArrays a
     __shared__ long long s_hi[kQualityThreads / 64], s_lo[kQualityThreads / 64];
     __shared__ int s_cnt[kQualityThreads / 64][kQualityCounts];
     __shared__ int s_box[4];
-    __shared__ int s_behind;   // some vertex is not in front of the near plane: a closed mesh is then drawn whole too
+    __shared__ int s_behind;
     const int obj = blockIdx.x, tid = threadIdx.x;
     const FrameCtrl& c = frame_ctrl(a, (int)((qa.frames_packed >> (4 * blockIdx.y)) & 15u), obj);
     const float* depth = c.depth_cur;
@@ -38,7 +38,7 @@ __global__ __launch_bounds__(kQualityThreads) void quality_kernel(EngineArrays a
     const int nv = prm.n_verts, nt = prm.n_tris;
     const bool cached = nv <= qa.vcache_cap;
     float* s_v = reinterpret_cast<float*>(smem);
-    uint32_t* s_z = reinterpret_cast<uint32_t*>(smem + (((size_t)qa.vcache_cap * 12 + 15) & ~(size_t)15));
+    uint32_t* s_z = reinterpret_cast<uint32_t*>(smem + vertex_cache_bytes(qa.vcache_cap));
     if (tid < 4) s_box[tid] = (tid < 2) ? INT32_MAX : -1;
     if (tid == 0) s_behind = 0;
     __syncthreads();
@@ -55,37 +55,9 @@ __global__ __launch_bounds__(kQualityThreads) void quality_kernel(EngineArrays a
         for (size_t i = n4 * 4 + tid; i < a.plane_words; i += kQualityThreads) n_mask += __popc(plane[i]);
     }
 
-    // vertices -> screen and the pixel box of everything that can be drawn (as outlier_fused_kernel takes it: the pixel ranges
-    // raster_projected clips to are monotone in the coordinates, so the box of the vertices covers every triangle)
-    {
-        int bi0 = INT32_MAX, bj0 = INT32_MAX, bi1 = -1, bj1 = -1;
-        bool behind = false;
-        for (int v = tid; v < nv; v += kQualityThreads) {
-            float vc[3], sx, sy, z;
-#pragma unroll
-            for (int q = 0; q < 3; ++q) vc[q] = prm.verts[(size_t)3 * v + q];
-            project_vertex(vc, P, fx, fy, cx, cy, sx, sy, z);
-            if (cached) { s_v[3 * v] = sx; s_v[3 * v + 1] = sy; s_v[3 * v + 2] = z; }
-            if (z > 0.001f) {
-                // (a vertex far outside the target clamps to an empty or full range; float -> int saturates)
-                const float lo_i = fminf(fmaxf(ceilf(sx - 0.5f), 0.0f), (float)tw), hi_i = fminf(fmaxf(floorf(sx - 0.5f), -1.0f), (float)(tw - 1));
-                const float lo_j = fminf(fmaxf(ceilf(sy - 0.5f), 0.0f), (float)th), hi_j = fminf(fmaxf(floorf(sy - 0.5f), -1.0f), (float)(th - 1));
-                bi0 = min(bi0, (int)lo_i); bi1 = max(bi1, (int)hi_i);
-                bj0 = min(bj0, (int)lo_j); bj1 = max(bj1, (int)hi_j);
-            } else {
-                behind = true;
-            }
-        }
-        if (__any(behind) && (tid & 63) == 0) atomicOr(&s_behind, 1);
-        for (int off = 32; off > 0; off >>= 1) {
-            bi0 = min(bi0, __shfl_xor(bi0, off, 64)); bj0 = min(bj0, __shfl_xor(bj0, off, 64));
-            bi1 = max(bi1, __shfl_xor(bi1, off, 64)); bj1 = max(bj1, __shfl_xor(bj1, off, 64));
-        }
-        if ((tid & 63) == 0) {
-            atomicMin(&s_box[0], bi0); atomicMin(&s_box[1], bj0);
-            atomicMax(&s_box[2], bi1); atomicMax(&s_box[3], bj1);
-        }
-    }
+    // vertices -> screen and the pixel box of everything that can be drawn (raster.h)
+    auto project = [&](const float* v, float& sx, float& sy, float& z) { project_vertex(v, P, fx, fy, cx, cy, sx, sy, z); };
+    project_mesh<kQualityThreads, 1>(prm.verts, nv, cached, s_v, tw, th, s_box, &s_behind, project);
     __syncthreads();
     const int i0 = min(s_box[0], tw - 1), i1 = s_box[2], j0 = min(s_box[1], th - 1), j1 = s_box[3];
     const int win_w = i1 - i0 + 1;
@@ -93,10 +65,10 @@ __global__ __launch_bounds__(kQualityThreads) void quality_kernel(EngineArrays a
     // (the launcher refuses targets wider than the window's capacity: a strip holds at least one row of any window)
     if (win_w > 0 && win_w <= qa.win_cap && j1 >= j0 && i0 >= 0 && j0 >= 0) {
         const int rows = max(1, qa.win_cap / win_w);
-        const uint8_t* const flips = (prm.tri_flip && !s_behind) ? prm.tri_flip : nullptr;
+        const uint8_t* const flips = cull_table(prm.tri_flip, s_behind);
         for (int js = j0; js <= j1; js += rows) {
             const int je = min(j1, js + rows - 1), npx = win_w * (je - js + 1);
-            for (int i = tid; i < npx; i += kQualityThreads) s_z[i] = 0x7F800000u;   // +inf: nothing drawn
+            for (int i = tid; i < npx; i += kQualityThreads) s_z[i] = kDepthEmpty;
             __syncthreads();
             ROFT_LDS uint32_t* const zw = pin_lds(s_z);
             auto store = [zw, i0, js, win_w](int i, int j, float z) {
@@ -105,17 +77,9 @@ __global__ __launch_bounds__(kQualityThreads) void quality_kernel(EngineArrays a
             for (int t = tid; t < nt; t += kQualityThreads) {
                 const int32_t* tri = prm.tris + (size_t)3 * t;
                 const int v0 = tri[0], v1 = tri[1], v2 = tri[2];
-                const int cull = flips ? 1 + (int)flips[t] : 0;
+                const int cull = cull_code(flips, t);
                 float x0, y0, z0, x1, y1, z1, x2, y2, z2;
-                if (cached) {
-                    x0 = s_v[3 * v0]; y0 = s_v[3 * v0 + 1]; z0 = s_v[3 * v0 + 2];
-                    x1 = s_v[3 * v1]; y1 = s_v[3 * v1 + 1]; z1 = s_v[3 * v1 + 2];
-                    x2 = s_v[3 * v2]; y2 = s_v[3 * v2 + 1]; z2 = s_v[3 * v2 + 2];
-                } else {
-                    project_vertex(prm.verts + (size_t)3 * v0, P, fx, fy, cx, cy, x0, y0, z0);
-                    project_vertex(prm.verts + (size_t)3 * v1, P, fx, fy, cx, cy, x1, y1, z1);
-                    project_vertex(prm.verts + (size_t)3 * v2, P, fx, fy, cx, cy, x2, y2, z2);
-                }
+                fetch_triangle(s_v, cached, prm.verts, v0, v1, v2, project, x0, y0, z0, x1, y1, z1, x2, y2, z2);
                 raster_projected(x0, y0, z0, x1, y1, z1, x2, y2, z2, tw, th, js, je, cull, store);
             }
             __syncthreads();
@@ -125,7 +89,7 @@ __global__ __launch_bounds__(kQualityThreads) void quality_kernel(EngineArrays a
             for (int idx = tid; idx < n_img; idx += kQualityThreads) {
                 const int vv = idx / rw, uu = idx - vv * rw;
                 const uint32_t b = s_z[(vv / d) * win_w + uu / d];
-                if (b == 0x7F800000u) continue;
+                if (b == kDepthEmpty) continue;
                 n_render += 1;
                 const int u = i0 * d + uu, v = js * d + vv;
                 if (!((plane[(size_t)v * wpr + (u >> 5)] >> (u & 31)) & 1u)) continue;
@@ -175,8 +139,8 @@ __global__ __launch_bounds__(kQualityThreads) void quality_kernel(EngineArrays a
 // that workgroups of the chains the launch runs next to still find a place on the CU.
 static bool quality_shape(const EngineArrays& a, int window_pixels, int& vcache_cap, int& win_cap, size_t& lds)
 {
-    const size_t lds_total = 160 * 1024 - 4096;
-    const size_t vbytes = ((size_t)a.max_verts * 12 + 15) & ~(size_t)15;
+    const size_t lds_total = kRasterLdsBudget;
+    const size_t vbytes = vertex_cache_bytes(a.max_verts);
     const size_t min_win = 4 * (size_t)std::max(8192, a.tile_w);
     const bool cache = vbytes + min_win <= lds_total;
     vcache_cap = cache ? a.max_verts : 0;
@@ -206,7 +170,7 @@ void launch_quality(const EngineArrays& a, QualityRaw* ring, int cap, unsigned f
     qa.depth_maximum = depth_maximum;
     size_t lds = 0;
     if (!quality_shape(a, window_pixels, qa.vcache_cap, qa.win_cap, lds)) return;   // (callers ask quality_fits first)
-    (void)set_max_dynamic_lds(reinterpret_cast<const void*>(quality_kernel), 160 * 1024 - 4096);
+    (void)set_max_dynamic_lds(reinterpret_cast<const void*>(quality_kernel), (int)kRasterLdsBudget);
     hipExtLaunchKernelGGL(quality_kernel, dim3(a.n_obj, n_frames), dim3(kQualityThreads), (uint32_t)lds, s, start, stop, 0, a, qa);
 }
 

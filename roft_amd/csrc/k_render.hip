@@ -147,7 +147,7 @@ void launch_features(const EngineArrays& a, hipStream_t s, hipEvent_t stop, unsi
 }
 
 // ---- rasteriser ---------------------------------------------------------------------------------
-// RenderPose, make_pose, project_vertex, raster_projected: raster.h
+// RenderPose, make_pose, project_vertex, raster_projected, and the mesh walk around them (project_mesh, fetch_triangle, cull_table): raster.h
 
 // ---- render mode ROFT_RENDER_GL: the numerics of the reference's OpenGL pipeline (RO_RENDER_GL of oracle/ro_render.c) -------
 // Every triangle is drawn (depth test LESS, no culling: SICAD.cpp:271-272), window z is interpolated linearly in screen space
@@ -293,8 +293,8 @@ __global__ __launch_bounds__(kOutlierThreads) void outlier_kernel(EngineArrays a
 #pragma unroll
         for (int k = 0; k < kBatch; ++k) {
             if (!((dep[k] > 0) && ((double)dep[k] < 2.0))) continue;  // hard-coded 2.0 (ROFTFilter.cpp:561)
-            if (b0[k] != 0x7F800000u) { err[0] += (double)fabsf(dep[k] - __uint_as_float(b0[k])); cnt[0] += 1.0; }
-            if (b1[k] != 0x7F800000u) { err[1] += (double)fabsf(dep[k] - __uint_as_float(b1[k])); cnt[1] += 1.0; }
+            if (b0[k] != kDepthEmpty) { err[0] += (double)fabsf(dep[k] - __uint_as_float(b0[k])); cnt[0] += 1.0; }
+            if (b1[k] != kDepthEmpty) { err[1] += (double)fabsf(dep[k] - __uint_as_float(b1[k])); cnt[1] += 1.0; }
         }
     }
     for (int k = 0; k < 2; ++k) {
@@ -378,7 +378,7 @@ __global__ __launch_bounds__(kFusedThreads) void outlier_fused_kernel(EngineArra
     __shared__ long long s_hi[kFusedThreads / 64], s_lo[kFusedThreads / 64];
     __shared__ int s_cnt[kFusedThreads / 64];
     __shared__ int s_box[4];
-    __shared__ int s_behind;   // some vertex is not in front of the near plane: a closed mesh is then drawn whole too
+    __shared__ int s_behind;
     __shared__ int s_last;
     // Workgroups are handed to the XCDs round robin by their linear index; the 2 x parts workgroups of an object read the
     // same mesh (186 KB of indices + 98 KB of vertices at the bench's 15.5 k triangles): with the grid laid out as
@@ -399,7 +399,7 @@ __global__ __launch_bounds__(kFusedThreads) void outlier_fused_kernel(EngineArra
     const int nv = prm.n_verts, nt = prm.n_tris;
     const bool cached = nv <= vcache_cap;
     float* s_v = reinterpret_cast<float*>(smem);
-    uint32_t* s_z = reinterpret_cast<uint32_t*>(smem + (((size_t)vcache_cap * 12 + 15) & ~(size_t)15));
+    uint32_t* s_z = reinterpret_cast<uint32_t*>(smem + vertex_cache_bytes(vcache_cap));
     uint64_t* s_k = reinterpret_cast<uint64_t*>(s_z);   // (GL: the visibility buffer, win_cap keys)
     if (tid < 4) s_box[tid] = (tid < 2) ? INT32_MAX : -1;
     if (tid == 0) s_behind = 0;
@@ -408,52 +408,13 @@ __global__ __launch_bounds__(kFusedThreads) void outlier_fused_kernel(EngineArra
     if (tid < 8 && bx < 4) st.dbg[bx * 8 + tid] = 0;
 #endif
     __syncthreads();
-    // vertices -> screen; pixel bounding box of the triangles that can be drawn (pixel ranges as raster_projected clips
-    // them: ceil(min - 0.5) .. floor(max - 0.5) are monotone, so the box of the vertices covers every triangle)
-    {
-        int bi0 = INT32_MAX, bj0 = INT32_MAX, bi1 = -1, bj1 = -1;
-        bool behind = false;
-        constexpr int kVB = 4;   // vertices per thread whose coordinates are fetched together
-        for (int vb = tid; vb < nv; vb += kVB * kFusedThreads) {
-          float vc[kVB][3];
-#pragma unroll
-          for (int k = 0; k < kVB; ++k) {
-              const int v = min(vb + k * kFusedThreads, nv - 1);
-#pragma unroll
-              for (int q = 0; q < 3; ++q) vc[k][q] = prm.verts[(size_t)3 * v + q];
-          }
-#pragma unroll
-          for (int k = 0; k < kVB; ++k) {
-            const int v = vb + k * kFusedThreads;
-            if (v >= nv) break;
-            float sx, sy, z;
-            if constexpr (GL) project_vertex_gl(vc[k], P, fx, fy, cx, cy, sx, sy, z);
-            else project_vertex(vc[k], P, fx, fy, cx, cy, sx, sy, z);
-            if (cached) { s_v[3 * v] = sx; s_v[3 * v + 1] = sy; s_v[3 * v + 2] = z; }
-            if (z > 0.001f) {
-                // (a vertex far outside the target clamps to an empty or full range; float -> int saturates)
-                const float lo_i = fminf(fmaxf(ceilf(sx - 0.5f), 0.0f), (float)tw), hi_i = fminf(fmaxf(floorf(sx - 0.5f), -1.0f), (float)(tw - 1));
-                const float lo_j = fminf(fmaxf(ceilf(sy - 0.5f), 0.0f), (float)th), hi_j = fminf(fmaxf(floorf(sy - 0.5f), -1.0f), (float)(th - 1));
-                bi0 = min(bi0, (int)lo_i); bi1 = max(bi1, (int)hi_i);
-                bj0 = min(bj0, (int)lo_j); bj1 = max(bj1, (int)hi_j);
-            } else {
-                behind = true;
-            }
-          }
-        }
-        if (__any(behind) && (tid & 63) == 0) atomicOr(&s_behind, 1);
-        for (int off = 32; off > 0; off >>= 1) {
-            bi0 = min(bi0, __shfl_xor(bi0, off, 64)); bj0 = min(bj0, __shfl_xor(bj0, off, 64));
-            bi1 = max(bi1, __shfl_xor(bi1, off, 64)); bj1 = max(bj1, __shfl_xor(bj1, off, 64));
-        }
-        if ((tid & 63) == 0) {
-            atomicMin(&s_box[0], bi0); atomicMin(&s_box[1], bj0);
-            atomicMax(&s_box[2], bi1); atomicMax(&s_box[3], bj1);
-        }
-    }
+    auto project = [&](const float* v, float& sx, float& sy, float& z) {
+        if constexpr (GL) project_vertex_gl(v, P, fx, fy, cx, cy, sx, sy, z);
+        else project_vertex(v, P, fx, fy, cx, cy, sx, sy, z);
+    };
+    // vertices -> screen and the pixel box of everything that can be drawn (raster.h), four vertices per thread fetched together
+    project_mesh<kFusedThreads, 4>(prm.verts, nv, cached, s_v, tw, th, s_box, &s_behind, project);
     __syncthreads();
-    // (a triangle's pixels lie between the smallest lower bound and the largest upper bound of its vertices; vertices
-    //  left or above the target contribute lower bound 0, vertices right or below it the upper bound w - 1 / h - 1)
     UTICK(0);
     const int i0 = min(s_box[0], tw - 1), i1 = s_box[2];
     // The `parts` workgroups of the alternative share its work as R bands of the window's rows x G groups of its triangles
@@ -489,15 +450,7 @@ __global__ __launch_bounds__(kFusedThreads) void outlier_fused_kernel(EngineArra
         const int32_t* tri = prm.tris + (size_t)3 * (uint32_t)key;
         const int v0 = tri[0], v1 = tri[1], v2 = tri[2];
         float x0, y0, z0, x1, y1, z1, x2, y2, z2;
-        if (cached) {
-            x0 = s_v[3 * v0]; y0 = s_v[3 * v0 + 1]; z0 = s_v[3 * v0 + 2];
-            x1 = s_v[3 * v1]; y1 = s_v[3 * v1 + 1]; z1 = s_v[3 * v1 + 2];
-            x2 = s_v[3 * v2]; y2 = s_v[3 * v2 + 1]; z2 = s_v[3 * v2 + 2];
-        } else {
-            project_vertex_gl(prm.verts + (size_t)3 * v0, P, fx, fy, cx, cy, x0, y0, z0);
-            project_vertex_gl(prm.verts + (size_t)3 * v1, P, fx, fy, cx, cy, x1, y1, z1);
-            project_vertex_gl(prm.verts + (size_t)3 * v2, P, fx, fy, cx, cy, x2, y2, z2);
-        }
+        fetch_triangle(s_v, cached, prm.verts, v0, v1, v2, project, x0, y0, z0, x1, y1, z1, x2, y2, z2);
         return gl_linear_depth(gl_pixel_window_z(x0, y0, x1, y1, x2, y2, gl_vertex_window_z(z0), gl_vertex_window_z(z1),
                                                  gl_vertex_window_z(z2), (float)i + 0.5f, (float)j + 0.5f));
     };
@@ -508,7 +461,7 @@ __global__ __launch_bounds__(kFusedThreads) void outlier_fused_kernel(EngineArra
             if constexpr (GL) {
                 for (int i = tid; i < npx; i += kFusedThreads) s_k[i] = kGlKeyClear;
             } else {
-                for (int i = tid; i < npx; i += kFusedThreads) s_z[i] = 0x7F800000u;
+                for (int i = tid; i < npx; i += kFusedThreads) s_z[i] = kDepthEmpty;
             }
             __syncthreads();
             UTICK(1);
@@ -521,8 +474,7 @@ __global__ __launch_bounds__(kFusedThreads) void outlier_fused_kernel(EngineArra
                 (void)__hip_atomic_fetch_min(zk + ((j - js) * win_w + (i - i0)), key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             };
             constexpr int kTB = 8;   // triangles per thread whose vertex indices are fetched together
-            // closed mesh, everything in front of the near plane: triangles that face away are left out (the render contract)
-            const uint8_t* const flips = (!GL && prm.tri_flip && !s_behind && nv < (1 << 30)) ? prm.tri_flip : nullptr;   // (the cull code rides in an index's top bits)
+            const uint8_t* const flips = (!GL && nv < (1 << 30)) ? cull_table(prm.tri_flip, s_behind) : nullptr;   // (the cull code rides in an index's top bits)
             // (split: the triangles are dealt out to the workgroups of the alternative in runs of 64 -- one run per wave and
             //  fetch, so the index loads stay coalesced and neighbouring runs, which cost alike, go to different workgroups)
             const int stride = G, first = grp;
@@ -535,7 +487,7 @@ __global__ __launch_bounds__(kFusedThreads) void outlier_fused_kernel(EngineArra
                   const int t = min(tri_of(min(tb + k * kFusedThreads, n_slots - 1)), nt - 1);
                   const int32_t* tri = prm.tris + (size_t)3 * t;
                   idx[k][0] = tri[0]; idx[k][1] = tri[1]; idx[k][2] = tri[2];
-                  if (flips) idx[k][0] |= (1 + (int)flips[t]) << 30;
+                  if (flips) idx[k][0] |= cull_code(flips, t) << 30;
               }
 #pragma unroll
               for (int k = 0; k < kTB; ++k) {
@@ -543,19 +495,7 @@ __global__ __launch_bounds__(kFusedThreads) void outlier_fused_kernel(EngineArra
                 const int cull_k = (int)((unsigned)idx[k][0] >> 30);
                 const int v0 = idx[k][0] & 0x3FFFFFFF, v1 = idx[k][1], v2 = idx[k][2];
                 float x0, y0, z0, x1, y1, z1, x2, y2, z2;
-                if (cached) {
-                    x0 = s_v[3 * v0]; y0 = s_v[3 * v0 + 1]; z0 = s_v[3 * v0 + 2];
-                    x1 = s_v[3 * v1]; y1 = s_v[3 * v1 + 1]; z1 = s_v[3 * v1 + 2];
-                    x2 = s_v[3 * v2]; y2 = s_v[3 * v2 + 1]; z2 = s_v[3 * v2 + 2];
-                } else if constexpr (GL) {
-                    project_vertex_gl(prm.verts + (size_t)3 * v0, P, fx, fy, cx, cy, x0, y0, z0);
-                    project_vertex_gl(prm.verts + (size_t)3 * v1, P, fx, fy, cx, cy, x1, y1, z1);
-                    project_vertex_gl(prm.verts + (size_t)3 * v2, P, fx, fy, cx, cy, x2, y2, z2);
-                } else {
-                    project_vertex(prm.verts + (size_t)3 * v0, P, fx, fy, cx, cy, x0, y0, z0);
-                    project_vertex(prm.verts + (size_t)3 * v1, P, fx, fy, cx, cy, x1, y1, z1);
-                    project_vertex(prm.verts + (size_t)3 * v2, P, fx, fy, cx, cy, x2, y2, z2);
-                }
+                fetch_triangle(s_v, cached, prm.verts, v0, v1, v2, project, x0, y0, z0, x1, y1, z1, x2, y2, z2);
                 if constexpr (GL) {
                     // the key's low word: the triangle's index in the caller's order (tris are uploaded unsorted in this mode)
                     const uint64_t t = (uint32_t)tri_of(tb + k * kFusedThreads);
@@ -656,7 +596,7 @@ __global__ __launch_bounds__(kFusedThreads) void outlier_fused_kernel(EngineArra
                 } else {
                     for (int i = tid; i < npx; i += kFusedThreads) {
                         const uint32_t b = s_z[i];
-                        tile[(size_t)(js + i / win_w) * tw + (i0 + i % win_w)] = (b == 0x7F800000u) ? 0.0f : __uint_as_float(b);
+                        tile[(size_t)(js + i / win_w) * tw + (i0 + i % win_w)] = (b == kDepthEmpty) ? 0.0f : __uint_as_float(b);
                     }
                 }
             }
@@ -682,7 +622,7 @@ __global__ __launch_bounds__(kFusedThreads) void outlier_fused_kernel(EngineArra
                         if ((uint32_t)(key >> 32) != kGlDepthClear) { err.add(fabsf(dep[k] - gl_resolve(key, ti, tj))); cnt += 1; }
                     } else {
                         const uint32_t b = s_z[(tj - js) * win_w + (ti - i0)];
-                        if (b != 0x7F800000u) { err.add(fabsf(dep[k] - __uint_as_float(b))); cnt += 1; }
+                        if (b != kDepthEmpty) { err.add(fabsf(dep[k] - __uint_as_float(b))); cnt += 1; }
                     }
                 }
             }
@@ -721,8 +661,8 @@ void launch_outlier(const EngineArrays& a, int lin, hipStream_t s, hipEvent_t st
 {
     // objects that do not test this frame return immediately; the decision (ROFTFilter.cpp:581-583) is taken by the
     // pose chain segment that follows (ukf_chain_kernel)
-    const size_t lds_total = 160 * 1024 - 4096;
-    const size_t vbytes = ((size_t)a.max_verts * 12 + 15) & ~(size_t)15;
+    const size_t lds_total = kRasterLdsBudget;
+    const size_t vbytes = vertex_cache_bytes(a.max_verts);
     // render mode: the GL numerics keep an 8-byte key per window pixel (outlier_fused_kernel<true>), the contract a 4-byte depth
     const bool gl = opts && opts->render_mode == ROFT_RENDER_GL;
     const size_t zb = gl ? 8 : 4;

@@ -35,7 +35,7 @@ __global__ __launch_bounds__(kSceneThreads) void scene_visibility_kernel(SceneAr
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ int s_box[4];
-    __shared__ int s_behind;   // some vertex is not in front of the near plane: a closed mesh is then drawn whole too
+    __shared__ int s_behind;
     const int tid = threadIdx.x;
     const int part = (int)(blockIdx.x % (unsigned)a.parts), fi = (int)(blockIdx.x / (unsigned)a.parts);   // fi = frame * n_instances + instance
     const int inst = fi % a.n_instances, frame = fi / a.n_instances;
@@ -54,45 +54,20 @@ __global__ __launch_bounds__(kSceneThreads) void scene_visibility_kernel(SceneAr
     const int nv = m.n_verts, nt = m.n_tris, W = a.W, H = a.H;
     const bool cached = nv <= a.vcache_cap;
     float* s_v = reinterpret_cast<float*>(smem);
-    uint64_t* s_k = reinterpret_cast<uint64_t*>(smem + (((size_t)a.vcache_cap * 12 + 15) & ~(size_t)15));
+    uint64_t* s_k = reinterpret_cast<uint64_t*>(smem + vertex_cache_bytes(a.vcache_cap));
     if (tid < 4) s_box[tid] = (tid < 2) ? INT32_MAX : -1;
     if (tid == 0) s_behind = 0;
     __syncthreads();
-    // vertices -> screen; pixel bounding box of the triangles that can be drawn (as outlier_fused_kernel takes it: the pixel
-    // ranges raster_projected clips to are monotone in the coordinates, so the box of the vertices covers every triangle)
-    {
-        int bi0 = INT32_MAX, bj0 = INT32_MAX, bi1 = -1, bj1 = -1;
-        bool behind = false;
-        for (int v = tid; v < nv; v += kSceneThreads) {
-            float sx, sy, z;
-            project_vertex(m.verts + (size_t)3 * v, P, a.fx, a.fy, a.cx, a.cy, sx, sy, z);
-            if (cached) { s_v[3 * v] = sx; s_v[3 * v + 1] = sy; s_v[3 * v + 2] = z; }
-            if (z > 0.001f) {
-                const float lo_i = fminf(fmaxf(ceilf(sx - 0.5f), 0.0f), (float)W), hi_i = fminf(fmaxf(floorf(sx - 0.5f), -1.0f), (float)(W - 1));
-                const float lo_j = fminf(fmaxf(ceilf(sy - 0.5f), 0.0f), (float)H), hi_j = fminf(fmaxf(floorf(sy - 0.5f), -1.0f), (float)(H - 1));
-                bi0 = min(bi0, (int)lo_i); bi1 = max(bi1, (int)hi_i);
-                bj0 = min(bj0, (int)lo_j); bj1 = max(bj1, (int)hi_j);
-            } else {
-                behind = true;
-            }
-        }
-        if (__any(behind) && (tid & 63) == 0) atomicOr(&s_behind, 1);
-        for (int off = 32; off > 0; off >>= 1) {
-            bi0 = min(bi0, __shfl_xor(bi0, off, 64)); bj0 = min(bj0, __shfl_xor(bj0, off, 64));
-            bi1 = max(bi1, __shfl_xor(bi1, off, 64)); bj1 = max(bj1, __shfl_xor(bj1, off, 64));
-        }
-        if ((tid & 63) == 0) {
-            atomicMin(&s_box[0], bi0); atomicMin(&s_box[1], bj0);
-            atomicMax(&s_box[2], bi1); atomicMax(&s_box[3], bj1);
-        }
-    }
+    // vertices -> screen and the pixel box of everything that can be drawn (raster.h)
+    auto project = [&](const float* v, float& sx, float& sy, float& z) { project_vertex(v, P, a.fx, a.fy, a.cx, a.cy, sx, sy, z); };
+    project_mesh<kSceneThreads, 1>(m.verts, nv, cached, s_v, W, H, s_box, &s_behind, project);
     __syncthreads();
     const int i0 = min(s_box[0], W - 1), i1 = s_box[2], j0 = min(s_box[1], H - 1), j1 = s_box[3];
     if (i1 < i0 || j1 < j0 || i0 < 0 || j0 < 0) return;   // nothing on the screen
     // strips of the window: whole rows while a row fits the LDS window, else a row is cut into column runs as well
     const int win_w = i1 - i0 + 1, cw = min(win_w, a.win_cap), rows = max(1, a.win_cap / cw);
     const int n_cols = (win_w + cw - 1) / cw, n_rows = (j1 - j0 + rows) / rows;
-    const uint8_t* const flips = (m.flip && !s_behind) ? m.flip : nullptr;   // closed, all in front: the back-face rule applies
+    const uint8_t* const flips = cull_table(m.flip, s_behind);
     ROFT_LDS uint64_t* const zk = (ROFT_LDS uint64_t*)pin_lds(reinterpret_cast<uint32_t*>(s_k));
     uint64_t* const keys = a.keys + (size_t)frame * W * H;
     for (int strip = part; strip < n_cols * n_rows; strip += a.parts) {
@@ -104,17 +79,9 @@ __global__ __launch_bounds__(kSceneThreads) void scene_visibility_kernel(SceneAr
         for (int t = tid; t < nt; t += kSceneThreads) {
             const int32_t* tri = m.tris + (size_t)3 * t;
             const int v0 = tri[0], v1 = tri[1], v2 = tri[2];
-            const int cull = flips ? 1 + (int)flips[t] : 0;
+            const int cull = cull_code(flips, t);
             float x0, y0, z0, x1, y1, z1, x2, y2, z2;
-            if (cached) {
-                x0 = s_v[3 * v0]; y0 = s_v[3 * v0 + 1]; z0 = s_v[3 * v0 + 2];
-                x1 = s_v[3 * v1]; y1 = s_v[3 * v1 + 1]; z1 = s_v[3 * v1 + 2];
-                x2 = s_v[3 * v2]; y2 = s_v[3 * v2 + 1]; z2 = s_v[3 * v2 + 2];
-            } else {
-                project_vertex(m.verts + (size_t)3 * v0, P, a.fx, a.fy, a.cx, a.cy, x0, y0, z0);
-                project_vertex(m.verts + (size_t)3 * v1, P, a.fx, a.fy, a.cx, a.cy, x1, y1, z1);
-                project_vertex(m.verts + (size_t)3 * v2, P, a.fx, a.fy, a.cx, a.cy, x2, y2, z2);
-            }
+            fetch_triangle(s_v, cached, m.verts, v0, v1, v2, project, x0, y0, z0, x1, y1, z1, x2, y2, z2);
             const uint64_t low = ((uint64_t)(uint32_t)inst << 24) | (uint32_t)t;
             raster_projected(x0, y0, z0, x1, y1, z1, x2, y2, z2, W, H, js, je, cull, [zk, is, js, sw, low](int i, int j, float z) {
                 const unsigned ci = (unsigned)(i - is);
@@ -172,7 +139,7 @@ __global__ __launch_bounds__(256) void scene_resolve_kernel(SceneArgs a)
     for (int k = 0; k < kResolvePixels; ++k) {
         const bool in_range = g0 + k < total;
         const uint32_t zb = (uint32_t)(key[k] >> 32);
-        const bool covered = in_range && zb < 0x7F800000u;   // (an infinite depth is background, as the contract's `z < +inf`)
+        const bool covered = in_range && zb < kDepthEmpty;   // (an infinite depth is background, as the contract's `z < +inf`)
         dep[k] = covered ? __uint_as_float(zb) : 0.0f;
         ins[k] = covered ? (int)((key[k] >> 24) & 0xFFu) : -1;
         tri[k] = covered ? (int)(key[k] & 0xFFFFFFu) : -1;
@@ -206,11 +173,9 @@ __global__ __launch_bounds__(256) void scene_resolve_kernel(SceneArgs a)
     if (a.triangle) *reinterpret_cast<int4*>(a.triangle + g0) = make_int4(tri[0], tri[1], tri[2], tri[3]);
 }
 
-size_t scene_lds_budget() { return 160 * 1024 - 4096; }
-
 void launch_scene_visibility(const SceneArgs& a, size_t lds_bytes, hipStream_t s)
 {
-    (void)set_max_dynamic_lds(reinterpret_cast<const void*>(scene_visibility_kernel), (int)scene_lds_budget());
+    (void)set_max_dynamic_lds(reinterpret_cast<const void*>(scene_visibility_kernel), (int)kRasterLdsBudget);
     const size_t groups = (size_t)a.n_frames * a.n_instances * a.parts;
     hipLaunchKernelGGL(scene_visibility_kernel, dim3((unsigned)groups), dim3(kSceneThreads), (uint32_t)lds_bytes, s, a);
 }

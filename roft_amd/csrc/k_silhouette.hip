@@ -32,8 +32,8 @@ template <bool kZ>
 __global__ __launch_bounds__(kSilhouetteThreads) void pose_silhouette_kernel(SilhouetteArgs sa)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    __shared__ int s_rows[2];   // first and last image row anything can be drawn in
-    __shared__ int s_behind;    // some vertex is not in front of the near plane: a closed mesh is then drawn whole too
+    __shared__ int s_box[4];   // (of which the rows are used: the first and last image row anything can be drawn in)
+    __shared__ int s_behind;
     const int obj = blockIdx.y, tid = threadIdx.x;
     const int t = (int)((sa.frames_packed >> (4 * blockIdx.z)) & 15u);
     const FrameCtrl& c = sa.ctrl[(size_t)t * sa.n_obj + obj];
@@ -45,42 +45,20 @@ __global__ __launch_bounds__(kSilhouetteThreads) void pose_silhouette_kernel(Sil
     const int nv = prm.n_verts, nt = prm.n_tris;
     const bool cached = nv <= sa.vcache_cap;
     float* s_v = reinterpret_cast<float*>(smem);
-    uint32_t* s_win = reinterpret_cast<uint32_t*>(smem + (((size_t)sa.vcache_cap * 12 + 15) & ~(size_t)15));
-    if (tid == 0) { s_rows[0] = INT32_MAX; s_rows[1] = -1; s_behind = 0; }
+    uint32_t* s_win = reinterpret_cast<uint32_t*>(smem + vertex_cache_bytes(sa.vcache_cap));
+    if (tid < 4) s_box[tid] = (tid < 2) ? INT32_MAX : -1;
+    if (tid == 0) s_behind = 0;
     __syncthreads();
 
-    // vertices -> screen, and the rows of everything that can be drawn (the row range raster_projected clips a triangle to is
-    // monotone in the coordinates of its vertices, so the range of the vertices in front covers every triangle that is drawn)
-    {
-        int bj0 = INT32_MAX, bj1 = -1;
-        bool behind = false;
-        for (int v = tid; v < nv; v += kSilhouetteThreads) {
-            float vc[3], sx, sy, z;
-#pragma unroll
-            for (int q = 0; q < 3; ++q) vc[q] = prm.verts[(size_t)3 * v + q];
-            project_vertex(vc, P, fx, fy, cx, cy, sx, sy, z);
-            if (cached) { s_v[3 * v] = sx; s_v[3 * v + 1] = sy; s_v[3 * v + 2] = z; }
-            if (z > 0.001f) {
-                // (a vertex far outside the image clamps to an empty or full range; NaN coordinates fail every comparison of the
-                //  rasteriser: nothing of such a triangle is drawn, and fminf / fmaxf drop the NaN here)
-                const float lo_j = fminf(fmaxf(ceilf(sy - 0.5f), 0.0f), (float)H), hi_j = fminf(fmaxf(floorf(sy - 0.5f), -1.0f), (float)(H - 1));
-                bj0 = min(bj0, (int)lo_j); bj1 = max(bj1, (int)hi_j);
-            } else {
-                behind = true;
-            }
-        }
-        if (__any(behind) && (tid & 63) == 0) atomicOr(&s_behind, 1);
-        for (int off = 32; off > 0; off >>= 1) {
-            bj0 = min(bj0, __shfl_xor(bj0, off, 64));
-            bj1 = max(bj1, __shfl_xor(bj1, off, 64));
-        }
-        if ((tid & 63) == 0) { atomicMin(&s_rows[0], bj0); atomicMax(&s_rows[1], bj1); }
-    }
+    // vertices -> screen and the rows of everything that can be drawn (raster.h; rows only: the columns, which nothing here reads,
+    // were measured at 1 - 2 % of the launch, docs/notebook.md)
+    auto project = [&](const float* v, float& sx, float& sy, float& z) { project_vertex(v, P, fx, fy, cx, cy, sx, sy, z); };
+    project_mesh<kSilhouetteThreads, 1, true>(prm.verts, nv, cached, s_v, W, H, s_box, &s_behind, project);
     __syncthreads();
-    const int box0 = s_rows[0], box1 = s_rows[1];
+    const int box0 = s_box[1], box1 = s_box[3];
     const bool to_z = kZ && c.label > 0;   // (workgroup-uniform)
     unsigned long long* const zb = to_z ? sa.zbuf + ((size_t)blockIdx.z * sa.n_zscenes + (c.label - 1)) * ((size_t)W * H) : nullptr;
-    const uint8_t* const flips = (prm.tri_flip && !s_behind) ? prm.tri_flip : nullptr;
+    const uint8_t* const flips = cull_table(prm.tri_flip, s_behind);
 
     // the band's rows, strip by strip
     const int bands = (int)gridDim.x, band = (int)blockIdx.x;
@@ -103,17 +81,9 @@ __global__ __launch_bounds__(kSilhouetteThreads) void pose_silhouette_kernel(Sil
             for (int k = tid; k < nt; k += kSilhouetteThreads) {
                 const int32_t* tri = prm.tris + (size_t)3 * k;
                 const int v0 = tri[0], v1 = tri[1], v2 = tri[2];
-                const int cull = flips ? 1 + (int)flips[k] : 0;
+                const int cull = cull_code(flips, k);
                 float x0, y0, z0, x1, y1, z1, x2, y2, z2;
-                if (cached) {
-                    x0 = s_v[3 * v0]; y0 = s_v[3 * v0 + 1]; z0 = s_v[3 * v0 + 2];
-                    x1 = s_v[3 * v1]; y1 = s_v[3 * v1 + 1]; z1 = s_v[3 * v1 + 2];
-                    x2 = s_v[3 * v2]; y2 = s_v[3 * v2 + 1]; z2 = s_v[3 * v2 + 2];
-                } else {
-                    project_vertex(prm.verts + (size_t)3 * v0, P, fx, fy, cx, cy, x0, y0, z0);
-                    project_vertex(prm.verts + (size_t)3 * v1, P, fx, fy, cx, cy, x1, y1, z1);
-                    project_vertex(prm.verts + (size_t)3 * v2, P, fx, fy, cx, cy, x2, y2, z2);
-                }
+                fetch_triangle(s_v, cached, prm.verts, v0, v1, v2, project, x0, y0, z0, x1, y1, z1, x2, y2, z2);
                 raster_projected(x0, y0, z0, x1, y1, z1, x2, y2, z2, W, H, j_lo, j_hi, cull, store);
             }
             __syncthreads();
@@ -219,17 +189,17 @@ int launch_pose_silhouette(SilhouetteArgs sa, int n_frames, int max_verts, int b
     const int band_rows = (sa.H + bands - 1) / bands;   // (the tallest band)
     sa.win_rows = std::max(1, std::min(band_rows, kSilhouetteWindowWords / sa.wpr));
     sa.vcache_cap = (vertex_cache && max_verts <= kSilhouetteCacheVerts) ? std::max(max_verts, 0) : 0;
-    const size_t vbytes = ((size_t)sa.vcache_cap * 12 + 15) & ~(size_t)15;
+    const size_t vbytes = vertex_cache_bytes(sa.vcache_cap);
     const size_t lds = vbytes + 4 * (size_t)sa.win_rows * sa.wpr;
     const dim3 grid(bands, sa.n_obj, n_frames);
     if (!sa.zbuf) {
-        (void)set_max_dynamic_lds(reinterpret_cast<const void*>(pose_silhouette_kernel<false>), 160 * 1024 - 4096);
+        (void)set_max_dynamic_lds(reinterpret_cast<const void*>(pose_silhouette_kernel<false>), (int)kRasterLdsBudget);
         hipExtLaunchKernelGGL(pose_silhouette_kernel<false>, grid, dim3(kSilhouetteThreads), (uint32_t)lds, s, start, stop, 0, sa);
         return 1;
     }
     if (sa.n_zscenes <= 0 || !sa.zpairs || !sa.zstats) return 0;
     (void)hipMemsetAsync(sa.zbuf, 0xFF, sizeof(unsigned long long) * (size_t)n_frames * sa.n_zscenes * sa.W * sa.H, s);
-    (void)set_max_dynamic_lds(reinterpret_cast<const void*>(pose_silhouette_kernel<true>), 160 * 1024 - 4096);
+    (void)set_max_dynamic_lds(reinterpret_cast<const void*>(pose_silhouette_kernel<true>), (int)kRasterLdsBudget);
     hipExtLaunchKernelGGL(pose_silhouette_kernel<true>, grid, dim3(kSilhouetteThreads), (uint32_t)lds, s, start, nullptr, 0, sa);
     hipExtLaunchKernelGGL(pose_resolve_kernel, grid, dim3(kSilhouetteThreads), 0, s, nullptr, stop, 0, sa);
     return 2;

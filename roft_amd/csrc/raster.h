@@ -1,11 +1,19 @@
 // raster.h -- the render contract's rasteriser (oracle/ro_render.c, operation by operation): pose -> float rotation, vertex
-// projection, scan conversion of one projected triangle.  Shared by the outlier test (k_render.hip) and the scene renderer
+// projection, scan conversion of one projected triangle -- and the mesh walk around it: the vertex pass (project_mesh), the corner
+// fetch (fetch_triangle), the back-face rule's guard (cull_table / cull_code) and the LDS arithmetic of a launcher.  Shared by the
+// outlier test (k_render.hip), track quality (k_quality.hip), masks from poses (k_silhouette.hip) and the scene renderer
 // (k_scene.hip); every translation unit that includes it is built with -ffp-contract=off.
 #pragma once
 
 #include "roft_device.h"
 
 namespace roft {
+
+constexpr uint32_t kDepthEmpty = 0x7F800000u;   // +inf: the pixel of a depth window nothing was drawn into
+
+// Dynamic LDS of a workgroup that draws a mesh: [the projected vertices, when they are cached] | [its window].
+constexpr size_t kRasterLdsBudget = 160 * 1024 - 4096;   // what such a kernel may ask for (the rest: its static LDS)
+__host__ __device__ constexpr size_t vertex_cache_bytes(int verts) { return ((size_t)verts * 12 + 15) & ~(size_t)15; }   // = the window's offset
 
 struct RenderPose {
     float R[9];
@@ -43,6 +51,7 @@ __device__ __forceinline__ void project_vertex(const float* v, const RenderPose&
 // skipped (a strip of the target).  cull: 0 = draw; 1 / 2 = the mesh is a closed surface (mesh_class.h) and this triangle is
 // wound counter-clockwise (1) / clockwise (2) seen from outside: it is drawn only if it faces the camera -- a counter-clockwise
 // triangle that does has NEGATIVE screen area under the contract's projection (x right, y down, z forward).
+// (cull_code below makes the code of triangle t from a mesh's flip table.)
 // (The candidate pixels as ONE loop of columns x rows iterations instead of two nested ones -- rounds of a wave = its largest box
 // instead of tallest x widest -- was measured in rounds 5 and 6, with and without the back-face rule: 15.6 against 15.0 us for the
 // triangle phase, the compiler hoists the row terms of the edge functions out of the inner loop.  Nested it stays.)
@@ -86,6 +95,97 @@ __device__ __forceinline__ void raster_projected(float x0, float y0, float z0, f
             if (!(z > 0.0f)) continue;
             store(i, j, z);
         }
+    }
+}
+
+// The back-face rule's guard: the flip table to cull with, or nullptr = every triangle is drawn.  Triangles that face away are
+// left out only while the mesh is closed (it has a flip table) and all of it is in front of the near plane (`behind`: project_mesh's
+// flag): with a vertex behind, the camera may be inside the surface, and what it sees there are back faces.
+__device__ __forceinline__ const uint8_t* cull_table(const uint8_t* tri_flip, int behind)
+{
+    return (tri_flip && !behind) ? tri_flip : nullptr;
+}
+
+// raster_projected's `cull` for triangle t: 1 + its flip bit
+__device__ __forceinline__ int cull_code(const uint8_t* flips, int t) { return flips ? 1 + (int)flips[t] : 0; }
+
+// The vertex pass of a workgroup of kThreads threads that draws a mesh on a w x h target: every vertex goes through
+// `project(const float* v, float& sx, float& sy, float& z)` -- project_vertex with the caller's pose and intrinsics --, is kept in
+// s_v (3 floats per vertex) when `cached`, and widens s_box = {i0, j0, i1, j1}, the pixel box of everything that can be drawn;
+// *s_behind is set when some vertex is not in front of the near plane (cull_table).  kVB: vertices per thread whose coordinates are
+// fetched together.  kRowsOnly: the caller uses the rows of the box only (s_box[1], s_box[3]); the columns are left as it set them.
+// Contract: the caller sets s_box = {INT32_MAX, INT32_MAX, -1, -1} and *s_behind = 0 behind a barrier, and puts a barrier after
+// the call.  It then reads i0 = min(s_box[0], w - 1), i1 = s_box[2], j0 = min(s_box[1], h - 1), j1 = s_box[3]; nothing can be drawn
+// when i1 < i0 or j1 < j0 (every vertex on one side of the target, or none in front: the box is untouched).
+// Why the box of the VERTICES covers every triangle: raster_projected clips a triangle to ceil(min - 0.5) .. floor(max - 0.5)
+// of its corners' coordinates, clamped to the target; both bounds are monotone in the coordinates, so a triangle's range lies
+// between the smallest lower bound and the largest upper bound of its vertices, and only triangles with all three corners in
+// front are drawn.  A vertex left of or above the target contributes the lower bound 0, one right of or below it the upper bound
+// w - 1 / h - 1; its other bound is the empty one, -1 or w / h (hence (float)w against w - 1; the caller's min takes that back).
+// A coordinate far off the target clamps the same way before the conversion (which would saturate anyway).  A NaN coordinate is
+// dropped by fminf / fmaxf, which return their other operand: the vertex counts as one left of and above the target, and the
+// rasteriser draws nothing of its triangles (NaN fails every comparison there).
+template <int kThreads, int kVB, bool kRowsOnly = false, class Project>
+__device__ __forceinline__ void project_mesh(const float* verts, int nv, bool cached, float* s_v, int w, int h, int* s_box,
+                                             int* s_behind, Project project)
+{
+    const int tid = threadIdx.x;
+    int bi0 = INT32_MAX, bj0 = INT32_MAX, bi1 = -1, bj1 = -1;
+    bool behind = false;
+    for (int vb = tid; vb < nv; vb += kVB * kThreads) {
+        float vc[kVB][3];
+#pragma unroll
+        for (int k = 0; k < kVB; ++k) {
+            const int v = min(vb + k * kThreads, nv - 1);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) vc[k][q] = verts[(size_t)3 * v + q];
+        }
+#pragma unroll
+        for (int k = 0; k < kVB; ++k) {
+            const int v = vb + k * kThreads;
+            if (v >= nv) break;
+            float sx, sy, z;
+            project(vc[k], sx, sy, z);
+            if (cached) { s_v[3 * v] = sx; s_v[3 * v + 1] = sy; s_v[3 * v + 2] = z; }
+            if (z > 0.001f) {
+                if constexpr (!kRowsOnly) {
+                    const float lo_i = fminf(fmaxf(ceilf(sx - 0.5f), 0.0f), (float)w), hi_i = fminf(fmaxf(floorf(sx - 0.5f), -1.0f), (float)(w - 1));
+                    bi0 = min(bi0, (int)lo_i); bi1 = max(bi1, (int)hi_i);
+                }
+                const float lo_j = fminf(fmaxf(ceilf(sy - 0.5f), 0.0f), (float)h), hi_j = fminf(fmaxf(floorf(sy - 0.5f), -1.0f), (float)(h - 1));
+                bj0 = min(bj0, (int)lo_j); bj1 = max(bj1, (int)hi_j);
+            } else {
+                behind = true;
+            }
+        }
+    }
+    if (__any(behind) && (tid & 63) == 0) atomicOr(s_behind, 1);
+    for (int off = 32; off > 0; off >>= 1) {
+        if constexpr (!kRowsOnly) { bi0 = min(bi0, __shfl_xor(bi0, off, 64)); bi1 = max(bi1, __shfl_xor(bi1, off, 64)); }
+        bj0 = min(bj0, __shfl_xor(bj0, off, 64)); bj1 = max(bj1, __shfl_xor(bj1, off, 64));
+    }
+    if ((tid & 63) == 0) {
+        if constexpr (!kRowsOnly) { atomicMin(&s_box[0], bi0); atomicMax(&s_box[2], bi1); }
+        atomicMin(&s_box[1], bj0); atomicMax(&s_box[3], bj1);
+    }
+}
+
+// The projected corners of a triangle: from the cache project_mesh filled, else through `project` again.
+// (Callers read cull_code BEFORE the fetch, so that the flip table's load is in flight with the corners': read behind the fetch it
+//  cost quality_kernel and pose_silhouette_kernel 3 us of 135 per launch, docs/notebook.md.)
+template <class Project>
+__device__ __forceinline__ void fetch_triangle(const float* s_v, bool cached, const float* verts, int v0, int v1, int v2, Project project,
+                                               float& x0, float& y0, float& z0, float& x1, float& y1, float& z1, float& x2, float& y2,
+                                               float& z2)
+{
+    if (cached) {
+        x0 = s_v[3 * v0]; y0 = s_v[3 * v0 + 1]; z0 = s_v[3 * v0 + 2];
+        x1 = s_v[3 * v1]; y1 = s_v[3 * v1 + 1]; z1 = s_v[3 * v1 + 2];
+        x2 = s_v[3 * v2]; y2 = s_v[3 * v2 + 1]; z2 = s_v[3 * v2 + 2];
+    } else {
+        project(verts + (size_t)3 * v0, x0, y0, z0);
+        project(verts + (size_t)3 * v1, x1, y1, z1);
+        project(verts + (size_t)3 * v2, x2, y2, z2);
     }
 }
 

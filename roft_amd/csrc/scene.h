@@ -63,6 +63,5 @@ struct SceneArgs {
 
 void launch_scene_visibility(const SceneArgs& a, size_t lds_bytes, hipStream_t s);
 void launch_scene_resolve(const SceneArgs& a, hipStream_t s);
-size_t scene_lds_budget();         // dynamic LDS a visibility workgroup may ask for
 
 }  // namespace roft

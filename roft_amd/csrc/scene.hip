@@ -1,6 +1,7 @@
 // scene.hip -- host side of the scene renderer entry points of include/roft_engine.h (section 3b): argument checks (all of them
 // before the device is looked for), the resident handle with its device buffers, and the two launches of k_scene.hip.
 #include "engine_internal.h"
+#include "raster.h"
 #include "scene.h"
 
 struct roft_scene_renderer {
@@ -143,7 +144,7 @@ int render(roft_scene_renderer* r, const roft_scene_desc* d, uint8_t* rgb_out, f
     // The LDS of a visibility workgroup: the projected vertices when they leave room for a window of 8 k keys, and the window.
     // 8 k keys = 64 KB: two workgroups share a CU.  (A larger window means fewer strips, each of which walks all triangles, but one
     // workgroup per CU; the object of a tracked sequence covers a few tens of thousands of pixels, a handful of strips.)
-    const size_t budget = scene_lds_budget(), vbytes = ((size_t)r->max_verts * 12 + 15) & ~(size_t)15;
+    const size_t budget = kRasterLdsBudget, vbytes = vertex_cache_bytes(r->max_verts);
     size_t win = std::min<size_t>(WH, 8192);
     const bool cache = vbytes + 8 * win <= budget;
     if (d->window_pixels > 0) win = std::min<size_t>(win, (size_t)d->window_pixels);
