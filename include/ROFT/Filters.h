@@ -53,6 +53,13 @@ public:
         compat::throw_if(roft_object_add(e_, &d, &id), "ROFTFilterBatch::add_object");
         return id;
     }
+    // A new track in the same slot (roft_objects_restart): slots ids[i] restart with descs[i] in ONE call, which waits for every stepped
+    // batch like wait(); flags: 0 or ROFT_RESTART_KEEP_MESH (descs[i].mesh is not looked at, the slots keep their meshes).
+    void restart_objects(const std::vector<int>& ids, const std::vector<roft_object_desc>& descs, int flags = 0)
+    {
+        if (ids.size() != descs.size()) throw std::invalid_argument("ROFTFilterBatch::restart_objects: one description per id");
+        compat::throw_if(roft_objects_restart(e_, ids.data(), descs.data(), static_cast<int>(ids.size()), flags), "ROFTFilterBatch::restart_objects");
+    }
     // one frame: inputs[object]
     void filtering_step(const std::vector<roft_frame_input>& inputs)
     {

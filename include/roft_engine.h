@@ -355,6 +355,41 @@ int roft_engine_create(const roft_config* cfg, roft_engine** out);
 int roft_engine_destroy(roft_engine* e);
 int roft_object_add(roft_engine* e, const roft_object_desc* desc, int* obj_id);
 
+/* ---- restart object slots on a running engine: a new track in the same slot ------------------------------------------------------ *
+ * The objects of an engine are fixed before its first frame; roft_objects_restart gives n of them (obj_ids[i], each named once) a new
+ * description descs[i] -- initial pose and covariances, noise parameters, mesh -- while every other object keeps its state: a lost
+ * track is re-initialised (section 3d tells the caller when), or a slot whose sequence has ended takes the next one.
+ *
+ * The contract.  Let the engine have stepped F frames when the call returns ROFT_OK.
+ *  - A NAMED slot: everything the engine returns for it on engine frame F + k -- log row, roft_get_outputs, roft_get_state,
+ *    roft_get_mask, roft_engine_get_flow, roft_engine_get_depth, quality records apart from their `frame` field -- is bit for bit
+ *    what a NEW engine returns on its frame k: an engine with the same roft_config and the same enable calls, whose objects were
+ *    added with the descriptions the slots have now, fed the inputs of frames F, F + 1, ...  Frame F is the slot's first frame in every
+ *    sense the reference gives that word: a flow handed with it is not used, there is no previous depth, the first-mask rule applies
+ *    (frame F must deliver a mask, or the object be enrolled for pose masks), outlier-rejection features are not initialised, the
+ *    velocity buffer and the flow history are empty, the eigen-decomposition starts cold, on an engine with camera images the flow
+ *    starts over, and an enrolled pose-mask object without pose_valid draws the silhouette of the new p_mean0.
+ *  - A slot NOT named: bit for bit what the same engine returns without the call.
+ *  - What persists: the slot id, pose-mask enrolment and scene membership, the quality, log, raw-depth and flow enables.  Log rows and
+ *    quality records of earlier frames stay readable, and records keep the ENGINE's frame numbering (frame % every included): the
+ *    engine's frame count never restarts.  Until the slot's next step roft_get_outputs shows the old track's last row and
+ *    roft_get_mask is ROFT_ERR_STATE, as on a new engine; roft_get_state already returns the new initial belief.  roft_engine_score_log with points == NULL uses the slot's current mesh.
+ *  - THE CALL WAITS for every stepped batch, exactly as roft_sync does, and the engine counts as idle afterwards (the next batches
+ *    are a burst again): restart the slots that are due in ONE call.  Restarts are served on an idle engine by plain copies; the
+ *    launch graph of a batch does not know about them.
+ *  - ROFT_RESTART_KEEP_MESH: descs[i].mesh is not looked at; the slot keeps its resident mesh (no upload, no classification).
+ *  - Refusals, all on the host before anything changes and before any wait, with the reason in roft_last_error_string.
+ *    ROFT_ERR_INVALID, checked before a device is looked for: a NULL engine; n < 0, or n > 0 with a NULL array; an id outside the
+ *    engine's objects; an id named twice; unknown flag bits; every check roft_object_add makes on a description; a description
+ *    without a mesh (without KEEP_MESH) for an object that needs one -- outlier rejection with use_pose, or enrolled for pose masks.
+ *    ROFT_ERR_STATE: a submitted batch that has not been stepped.  n == 0 is ROFT_OK and does not wait.
+ *  - Before the first frame the call is equivalent to having added the object with that description.
+ * Not offered: new slots after the first frame, ended or parked slots, a restart that does not wait. */
+#define ROFT_RESTART_KEEP_MESH 1
+int roft_objects_restart(roft_engine* e, const int* obj_ids, const roft_object_desc* descs, int n, int flags);
+typedef struct { long long calls, objects, meshes_replaced; } roft_engine_restart_stats;   /* successful calls with n > 0, slots restarted, meshes uploaded by them; since roft_engine_create */
+int roft_engine_get_restart_stats(roft_engine* e, roft_engine_restart_stats* out);
+
 /* inputs: one entry per object, in obj_id order.  Enqueues uploads and builds the frame program.  On an error
  * nothing of the frame has been consumed: the call can be repeated with corrected inputs. */
 int roft_frame_submit(roft_engine* e, const roft_frame_input* inputs, int n_inputs);
@@ -867,6 +902,11 @@ int roft_render_scene(const roft_camera* cam, const roft_mesh* meshes, int n_mes
  * (slots: n_frames x 10, -1 padded).  Any output may be NULL. */
 int roft_debug_plan(const roft_config* cfg, const int* pose_valid, int n_frames, int* n_steps, int* n_corrections,
                     int* outlier, int* slots);
+/* The refusals of roft_objects_restart without a device: the same host checks against a DESCRIBED engine -- n_objects objects,
+ * has_mesh[i] / enrolled[i]: object i has a mesh now / was named to roft_engine_enable_pose_masks, enrol_all: that call named nobody
+ * (then every object with a mesh is enrolled).  Returns what the call would return before it looks at the engine's state. */
+int roft_debug_restart_check(const roft_config* cfg, int n_objects, const int* has_mesh, const int* enrolled, int enrol_all,
+                             const int* obj_ids, const roft_object_desc* descs, int n, int flags);
 /* Which of the engine's HIP streams delay each other at the dispatch level (streams that the runtime mapped onto one hardware
  * queue): out[a * 5 + b] = microseconds until a one-workgroup kernel on stream b completes while stream a is placing a grid
  * larger than the device; ~15 = independent, >= 80 = queued behind it.  Order: pose lane 0, pose lane 1, velocity chain, mask

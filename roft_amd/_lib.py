@@ -123,6 +123,13 @@ class EnginePoseMaskOcclusionStats(C.Structure):
     _fields_ = [("resolved", C.c_longlong), ("hidden", C.c_longlong), ("pixels_removed", C.c_longlong)]
 
 
+RESTART_KEEP_MESH = 1               # ROFT_RESTART_KEEP_MESH
+
+
+class EngineRestartStats(C.Structure):
+    _fields_ = [("calls", C.c_longlong), ("objects", C.c_longlong), ("meshes_replaced", C.c_longlong)]
+
+
 class EngineStats(C.Structure):
     _fields_ = [("frames", C.c_longlong), ("batches", C.c_longlong), ("launches", C.c_longlong),
                 ("event_ops", C.c_longlong), ("h2d_bytes", C.c_longlong), ("h2d_copies", C.c_longlong)]
@@ -174,6 +181,7 @@ ABI_SYMBOLS = [
     "roft_default_quality_params", "roft_engine_enable_quality", "roft_engine_get_quality", "roft_track_quality", "roft_debug_quality_kernel_ms",
     "roft_engine_enable_pose_masks", "roft_engine_get_pose_mask_stats", "roft_pose_silhouette", "roft_debug_pose_mask_kernel_ms",
     "roft_engine_enable_pose_mask_occlusion", "roft_engine_get_pose_mask_occlusion_stats", "roft_pose_silhouettes_occluded",
+    "roft_objects_restart", "roft_engine_get_restart_stats", "roft_debug_restart_check",
 ]
 POSE_ERROR_ADD, POSE_ERROR_ADDS = 0, 1   # ROFT_POSE_ERROR_*
 # entry points younger than ABI version 2 itself: a library built before them still loads through ROFT_LIB_SO
@@ -183,7 +191,8 @@ NEWER_SYMBOLS = ("roft_pose_errors", "roft_engine_score_log", "roft_scene_render
                  "roft_engine_enable_raw_depth", "roft_engine_get_depth", "roft_engine_get_depth_stats", "roft_depth_convert", "roft_depth_align",
                  "roft_default_quality_params", "roft_engine_enable_quality", "roft_engine_get_quality", "roft_track_quality",
                  "roft_engine_enable_pose_masks", "roft_engine_get_pose_mask_stats", "roft_pose_silhouette",
-                 "roft_engine_enable_pose_mask_occlusion", "roft_engine_get_pose_mask_occlusion_stats", "roft_pose_silhouettes_occluded")
+                 "roft_engine_enable_pose_mask_occlusion", "roft_engine_get_pose_mask_occlusion_stats", "roft_pose_silhouettes_occluded",
+                 "roft_objects_restart", "roft_engine_get_restart_stats")
 
 
 def build(force=False):
@@ -312,6 +321,10 @@ def lib():
         L.roft_engine_enable_pose_mask_occlusion.argtypes = [vp, ip, ip, C.c_int]
         L.roft_engine_get_pose_mask_occlusion_stats.argtypes = [vp, C.POINTER(EnginePoseMaskOcclusionStats)]
         L.roft_pose_silhouettes_occluded.argtypes = [C.POINTER(Camera), C.POINTER(Mesh), C.c_int, vp, vp, C.c_int, C.c_int, vp, ip]
+    if hasattr(L, "roft_objects_restart"):
+        L.roft_objects_restart.argtypes = [vp, ip, C.POINTER(ObjectDesc), C.c_int, C.c_int]
+        L.roft_engine_get_restart_stats.argtypes = [vp, C.POINTER(EngineRestartStats)]
+        L.roft_debug_restart_check.argtypes = [C.POINTER(Config), C.c_int, ip, ip, C.c_int, ip, C.POINTER(ObjectDesc), C.c_int, C.c_int]
     for name in ABI_SYMBOLS:
         if (name.startswith("roft_debug_") or name in NEWER_SYMBOLS) and not hasattr(L, name):
             continue   # (an older build loaded through ROFT_LIB_SO for an A/B run: diagnostics and the pose errors only; tests/test_abi_cpu.py checks the in-tree library has them all)

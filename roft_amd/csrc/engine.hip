@@ -608,15 +608,41 @@ int roft_engine_get_stats(roft_engine* e, roft_engine_stats* out)
     return ROFT_OK;
 }
 
-int roft_object_add(roft_engine* e, const roft_object_desc* d, int* obj_id)
+// ---- one object from its description: shared by roft_object_add and roft_objects_restart -------------------------------------------
+
+// does the engine draw object `id`'s silhouette for missing masks (roft_engine_enable_pose_masks)?  `has_mesh`: of the mesh it has, or is about to get
+static bool pose_mask_enrolled(const roft_engine* e, int id, bool has_mesh)
 {
-    if (!e || !d) return fail(ROFT_ERR_INVALID, "null argument");
-    if ((int)e->objs.size() >= e->cfg.max_objects) return fail(ROFT_ERR_CAPACITY, "max_objects reached");
-    if (e->frame_counter > 0 || e->submitted) return fail(ROFT_ERR_STATE, "objects must be added before the first frame");
-    HIP_TRY(hipSetDevice(e->cfg.device));
-    const int id = (int)e->objs.size();
-    HostObject* o = new HostObject();
+    const EnginePoseMasks& pm = e->pose_masks;
+    return pm.enabled && ((id < (int)e->objs.size() && e->objs[id]->pose_masks) || (pm.all && has_mesh));
+}
+
+// Every check on a description, on the host (no device is looked for).  keep_mesh: d.mesh is not looked at.  enrolled: the object is
+// enrolled for pose masks by id, so a description without a mesh is refused.
+static int check_object_desc(const roft_config& cfg, const roft_object_desc& d, bool keep_mesh, bool enrolled)
+{
+    if (keep_mesh) return ROFT_OK;
+    if (d.mesh.n_verts > 0 && d.mesh.n_tris > 0) {
+        if (!d.mesh.verts || !d.mesh.tris) return fail(ROFT_ERR_INVALID, "mesh: null vertex or triangle array");
+        for (size_t i = 0; i < (size_t)3 * d.mesh.n_tris; ++i)   // (the rasteriser indexes the vertex array with these)
+            if (d.mesh.tris[i] < 0 || d.mesh.tris[i] >= d.mesh.n_verts)
+                return fail(ROFT_ERR_INVALID, "mesh: triangle " + std::to_string(i / 3) + " refers to vertex " + std::to_string(d.mesh.tris[i]) +
+                                                  " of " + std::to_string(d.mesh.n_verts));
+        return ROFT_OK;
+    }
+    if (cfg.outlier_rejection && cfg.use_pose) return fail(ROFT_ERR_INVALID, "outlier rejection needs a mesh");
+    if (enrolled) return fail(ROFT_ERR_INVALID, "the object is enrolled for pose masks: its description needs a mesh");
+    return ROFT_OK;
+}
+
+// Parameter block, mesh preparation and upload, ObjState from the description, pose0 -> object `id` (its HostObject `o`), on stream s;
+// `st` is the host copy the upload reads: the caller keeps it until the stream has been synchronised.  The description has passed
+// check_object_desc.  keep_mesh: the resident mesh stays.  *mesh_uploaded: a mesh went up.
+static int apply_object_desc(roft_engine* e, int id, HostObject* o, const roft_object_desc* d, bool keep_mesh, ObjState* st, hipStream_t s,
+                             bool* mesh_uploaded)
+{
     ObjParams& p = e->h_params[id];
+    const ObjParams old = p;
     std::memset(&p, 0, sizeof(p));
     for (int i = 0; i < 3; ++i) {
         p.sigma_ang_vel[i] = d->p_sigma_ang_vel[i];
@@ -627,13 +653,11 @@ int roft_object_add(roft_engine* e, const roft_object_desc* d, int* obj_id)
     for (int i = 0; i < 6; ++i) p.v_q[i] = d->v_q_diag[i];
     p.r_flow[0] = d->v_meas_cov_flow[0];
     p.r_flow[1] = d->v_meas_cov_flow[1];
-    auto bail = [&](int code, const std::string& msg) { delete o; return fail(code, msg); };
-    if (d->mesh.n_verts > 0 && d->mesh.n_tris > 0) {
-        if (!d->mesh.verts || !d->mesh.tris) return bail(ROFT_ERR_INVALID, "mesh: null vertex or triangle array");
-        for (size_t i = 0; i < (size_t)3 * d->mesh.n_tris; ++i)   // (the rasteriser indexes the vertex array with these)
-            if (d->mesh.tris[i] < 0 || d->mesh.tris[i] >= d->mesh.n_verts)
-                return bail(ROFT_ERR_INVALID, "mesh: triangle " + std::to_string(i / 3) + " refers to vertex " + std::to_string(d->mesh.tris[i]) +
-                                                  " of " + std::to_string(d->mesh.n_verts));
+    *mesh_uploaded = false;
+    if (keep_mesh) {
+        p.verts = old.verts; p.tris = old.tris; p.tri_flip = old.tri_flip;
+        p.n_verts = old.n_verts; p.n_tris = old.n_tris;
+    } else if (d->mesh.n_verts > 0 && d->mesh.n_tris > 0) {
         // closed orientable surface?  Then the outlier test's render leaves the triangles that face away out (the render
         // contract, oracle/ro_render.c) and walks the triangles in an order that keeps alike-facing ones together.  The GL render
         // mode draws every triangle and breaks depth ties on the caller's triangle order: the mesh goes up as it is.
@@ -642,18 +666,17 @@ int roft_object_add(roft_engine* e, const roft_object_desc* d, int* obj_id)
         hipError_t err = o->verts.ensure((size_t)3 * d->mesh.n_verts);
         if (err == hipSuccess) err = o->tris.ensure((size_t)3 * d->mesh.n_tris);
         if (err == hipSuccess && pm.closed) err = o->tri_flip.ensure((size_t)d->mesh.n_tris);
+        // (synchronous copies: the prepared triangle order and flip bits live in `pm`)
         if (err == hipSuccess) err = hipMemcpy(o->verts.p, d->mesh.verts, sizeof(float) * 3 * d->mesh.n_verts, hipMemcpyHostToDevice);
         if (err == hipSuccess) err = hipMemcpy(o->tris.p, pm.tris(d->mesh.tris), sizeof(int32_t) * 3 * d->mesh.n_tris, hipMemcpyHostToDevice);
         if (err == hipSuccess && pm.closed) err = hipMemcpy(o->tri_flip.p, pm.flip.data(), (size_t)d->mesh.n_tris, hipMemcpyHostToDevice);
-        if (err != hipSuccess) return bail(ROFT_ERR_DEVICE, std::string("mesh upload: ") + hipGetErrorString(err));
+        if (err != hipSuccess) { p = old; return fail(ROFT_ERR_DEVICE, std::string("mesh upload: ") + hipGetErrorString(err)); }
         p.verts = o->verts.p; p.tris = o->tris.p;
         p.tri_flip = pm.closed ? o->tri_flip.p : nullptr;
         p.n_verts = d->mesh.n_verts; p.n_tris = d->mesh.n_tris;
-    } else if (e->cfg.outlier_rejection && e->cfg.use_pose) {
-        return bail(ROFT_ERR_INVALID, "outlier rejection needs a mesh");
+        *mesh_uploaded = true;
     }
     // initialization_step (ROFTFilter.cpp:216-237)
-    ObjState* st = new ObjState();
     init_state(*st);
     for (int i = 0; i < 6; ++i) { st->v_mean[i] = d->v_mean0[i]; st->v_cov[i * 6 + i] = d->v_cov0_diag[i]; }
     PoseBelief b{};
@@ -662,18 +685,151 @@ int roft_object_add(roft_engine* e, const roft_object_desc* d, int* obj_id)
     st->belief[B_LIN0] = b;       // p_corr_belief_
     st->belief[B_LIN1] = b;       // buffered_belief_ = p_corr_belief_ at initialization (ROFTFilter.cpp:231)
     st->belief[B_PRED] = st->belief[B_PRED + 1] = b;
-    hipError_t err = hipMemcpy(e->arr.params.p + id, &p, sizeof(p), hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = hipMemcpy(e->arr.state.p + id, st, sizeof(ObjState), hipMemcpyHostToDevice);
-    delete st;
-    if (err != hipSuccess) return bail(ROFT_ERR_DEVICE, std::string("state upload: ") + hipGetErrorString(err));
-    e->arr.a.max_tris = std::max(e->arr.a.max_tris, d->mesh.n_tris);
-    e->arr.a.max_verts = std::max(e->arr.a.max_verts, d->mesh.n_verts);
+    hipError_t err = hipMemcpyAsync(e->arr.params.p + id, &p, sizeof(p), hipMemcpyHostToDevice, s);
+    if (err == hipSuccess) err = hipMemcpyAsync(e->arr.state.p + id, st, sizeof(ObjState), hipMemcpyHostToDevice, s);
+    if (err != hipSuccess) return fail(ROFT_ERR_DEVICE, std::string("state upload: ") + hipGetErrorString(err));
     for (int i = 0; i < 7; ++i) o->pose0[i] = d->p_mean0[6 + i];
+    return ROFT_OK;
+}
+
+// the largest mesh among the current objects (they only choose the vertex cache of the silhouette and outlier launches: no bit depends on them)
+static void update_mesh_maxima(roft_engine* e, int n_objs)
+{
+    e->arr.a.max_tris = e->arr.a.max_verts = 0;
+    for (int id = 0; id < n_objs; ++id) {
+        e->arr.a.max_tris = std::max(e->arr.a.max_tris, e->h_params[id].n_tris);
+        e->arr.a.max_verts = std::max(e->arr.a.max_verts, e->h_params[id].n_verts);
+    }
+}
+
+int roft_object_add(roft_engine* e, const roft_object_desc* d, int* obj_id)
+{
+    if (!e || !d) return fail(ROFT_ERR_INVALID, "null argument");
+    if ((int)e->objs.size() >= e->cfg.max_objects) return fail(ROFT_ERR_CAPACITY, "max_objects reached");
+    if (e->frame_counter > 0 || e->submitted) return fail(ROFT_ERR_STATE, "objects must be added before the first frame");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    const int id = (int)e->objs.size();
+    TRY(check_object_desc(e->cfg, *d, false, false));
+    HostObject* o = new HostObject();
+    ObjState* st = new ObjState();
+    bool mesh_uploaded = false;
+    int rc = apply_object_desc(e, id, o, d, false, st, e->stream, &mesh_uploaded);
+    if (rc == ROFT_OK && hipStreamSynchronize(e->stream) != hipSuccess) rc = fail(ROFT_ERR_DEVICE, "state upload failed");
+    delete st;
+    if (rc != ROFT_OK) { delete o; return rc; }
     e->objs.push_back(o);
     e->arr.a.n_obj = (int)e->objs.size();
+    update_mesh_maxima(e, e->arr.a.n_obj);
     if (obj_id) *obj_id = id;
     return ROFT_OK;
 }
 
+// ---- roft_objects_restart (include/roft_engine.h; DESIGN.md "Restarting object slots") ---------------------------------------------
 
+// Every refusal of the call that needs no device.  n_objects objects; has_mesh / enrolled_by_id: per object, the mesh it has now and
+// whether roft_engine_enable_pose_masks named it; enrol_all: that call named nobody (every object with a mesh is enrolled).
+static int check_restart_args(const roft_config& cfg, int n_objects, const int* has_mesh, const int* enrolled_by_id, bool pose_masks, bool enrol_all,
+                              const int* obj_ids, const roft_object_desc* descs, int n, int flags)
+{
+    if (n < 0) return fail(ROFT_ERR_INVALID, "restart: n must be >= 0");
+    if (n > 0 && (!obj_ids || !descs)) return fail(ROFT_ERR_INVALID, "restart: n object ids and n descriptions required");
+    if (flags & ~ROFT_RESTART_KEEP_MESH) return fail(ROFT_ERR_INVALID, "restart: unknown flag bits");
+    const bool keep_mesh = (flags & ROFT_RESTART_KEEP_MESH) != 0;
+    for (int i = 0; i < n; ++i) {
+        const int id = obj_ids[i];
+        if (id < 0 || id >= n_objects) return fail(ROFT_ERR_INVALID, "restart: " + std::to_string(id) + " is not an object of the engine");
+        for (int k = 0; k < i; ++k)
+            if (obj_ids[k] == id) return fail(ROFT_ERR_INVALID, "restart: object " + std::to_string(id) + " is named twice");
+        // (under "every object with a mesh is enrolled" an object that had a mesh was drawn so far: it needs one to go on)
+        const bool enrolled = pose_masks && (enrolled_by_id[id] || (enrol_all && has_mesh[id]));
+        if (int rc = check_object_desc(cfg, descs[i], keep_mesh, enrolled)) return fail(rc, "restart: object " + std::to_string(id) + ": " + last_error());
+    }
+    return ROFT_OK;
+}
 
+// the same checks against a described engine: the host logic without a device (tests)
+extern "C" int roft_debug_restart_check(const roft_config* cfg, int n_objects, const int* has_mesh, const int* enrolled, int enrol_all,
+                                        const int* obj_ids, const roft_object_desc* descs, int n, int flags)
+{
+    if (!cfg || n_objects < 0 || (n_objects > 0 && (!has_mesh || !enrolled))) return fail(ROFT_ERR_INVALID, "null argument");
+    bool any = enrol_all != 0;
+    for (int i = 0; i < n_objects; ++i) any = any || enrolled[i];
+    return check_restart_args(*cfg, n_objects, has_mesh, enrolled, any, enrol_all != 0, obj_ids, descs, n, flags);
+}
+
+int roft_objects_restart(roft_engine* e, const int* obj_ids, const roft_object_desc* descs, int n, int flags)
+{
+    if (!e) return fail(ROFT_ERR_INVALID, "null engine");
+    const int n_obj = (int)e->objs.size();
+    {
+        std::vector<int> has_mesh((size_t)n_obj), enrolled((size_t)n_obj);
+        for (int id = 0; id < n_obj; ++id) {
+            has_mesh[id] = e->h_params[id].n_verts > 0 && e->h_params[id].n_tris > 0;
+            enrolled[id] = e->objs[id]->pose_masks;
+        }
+        TRY(check_restart_args(e->cfg, n_obj, has_mesh.data(), enrolled.data(), e->pose_masks.enabled, e->pose_masks.all, obj_ids, descs, n, flags));
+    }
+    if (e->submitted) return fail(ROFT_ERR_STATE, "restart: a submitted batch has not been stepped (roft_step comes first)");
+    if (n == 0) return ROFT_OK;
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    TRY(roft_sync(e));   // every stepped batch has ended: nothing on the device reads or writes what follows
+    const bool keep_mesh = (flags & ROFT_RESTART_KEEP_MESH) != 0;
+    const bool running = e->frame_counter > 0;
+    const EngineArrays& a = e->arr.a;
+    hipStream_t s = e->stream;
+    std::vector<ObjState> fresh((size_t)n), last((size_t)(running ? n : 0));
+    // what roft_get_outputs shows for the tracks that end here: read before their state is overwritten
+    if (running) {
+        for (int i = 0; i < n; ++i)
+            if (e->objs[obj_ids[i]]->s.track_frames > 0)
+                HIP_TRY(hipMemcpyAsync(&last[i], e->arr.state.p + obj_ids[i], sizeof(ObjState), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    long long meshes = 0;
+    for (int i = 0; i < n; ++i) {
+        const int id = obj_ids[i];
+        HostObject* o = e->objs[id];
+        if (running && o->s.track_frames > 0) {
+            const ObjState& st = last[i];
+            roft_object_output& out = o->last_out;
+            std::memcpy(out.pose, st.belief[B_LIN0 + o->stepped_slot].mean, sizeof(double) * 13);
+            std::memcpy(out.twist, st.v_mean, sizeof(double) * 6);
+            out.n_flow_points = st.n_flow_points;
+            out.outlier_selected = st.lane[o->stepped_lane].outlier_selected;
+            out.outlier_L[0] = st.lane[o->stepped_lane].outlier_L[0];
+            out.outlier_L[1] = st.lane[o->stepped_lane].outlier_L[1];
+            o->last_out_valid = true;
+        }
+        bool mesh_uploaded = false;
+        TRY(apply_object_desc(e, id, o, &descs[i], keep_mesh, &fresh[i], s, &mesh_uploaded));
+        meshes += mesh_uploaded ? 1 : 0;
+        // the schedule mirrors of a new object, on the ENGINE's frame numbering (Sched::frame_idx)
+        for (OwnedFlow* of : o->owned) delete of;
+        o->owned.clear();
+        o->s = Sched();
+        o->s.frame_idx = e->frame_counter;
+        o->stepped_slot = o->stepped_lane = 0;
+        o->stepped_flow = nullptr;
+        o->stepped_depth = nullptr;
+        if (!running) continue;   // (before the first frame everything below is as roft_engine_create left it)
+        // what a new engine relies on being zero: the object's plane slots, its rows of both mask tables, its bits for the general
+        // mask kernel, its point counts
+        HIP_TRY(hipMemsetAsync(e->arr.planes.p + plane_offset(a, id, 0, 0), 0, sizeof(uint32_t) * (size_t)kPlaneSlotsTotal * 2 * a.plane_words, s));
+        HIP_TRY(hipMemset2DAsync(e->arr.mrec.p + id, sizeof(MaskRec) * (size_t)a.n_obj, 0, sizeof(MaskRec), (size_t)2 * (kMaxBatch + 1), s));
+        HIP_TRY(hipMemsetAsync(e->arr.mask_general.p + id, 0, sizeof(unsigned), s));
+        HIP_TRY(hipMemset2DAsync(e->arr.npts.p + id, sizeof(int) * (size_t)a.n_obj, 0, sizeof(int), (size_t)e->T_max, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));   // (`fresh` is read by the copies; the engine is idle again)
+    update_mesh_maxima(e, n_obj);
+    e->restart_stats.calls++;
+    e->restart_stats.objects += n;
+    e->restart_stats.meshes_replaced += meshes;
+    return ROFT_OK;
+}
+
+int roft_engine_get_restart_stats(roft_engine* e, roft_engine_restart_stats* out)
+{
+    if (!e || !out) return fail(ROFT_ERR_INVALID, "null argument");
+    *out = e->restart_stats;
+    return ROFT_OK;
+}

@@ -118,6 +118,7 @@ extern "C" int roft_debug_plan(const roft_config* cfg, const int* pose_valid, in
         in.pose_valid = pose_valid[k];
         if (!build_pose_program(*cfg, o, in, c)) return ROFT_ERR_CAPACITY;
         o.frame_idx++;
+        o.track_frames++;
         if (n_steps) n_steps[k] = c.n_steps;
         int nc = 0;
         for (int s = 0; s < c.n_steps; ++s) {

@@ -2,7 +2,8 @@
 // engine, the host-side mirrors of the reference's source / measurement state machines (Sched), the engine object itself and
 // the few functions that cross a file boundary.  Not installed, not part of the ABI (that is include/roft_engine.h).
 //
-//   engine.hip          error string, pinned host pool, defaults, stream sets, roft_engine_create / destroy, roft_object_add
+//   engine.hip          error string, pinned host pool, defaults, stream sets, roft_engine_create / destroy, roft_object_add,
+//                       roft_objects_restart
 //   engine_submit.hip   roft_frames_submit: the frame programs (build_pose_program), HOST staging, the control blocks of a batch
 //   batch_plan.h        SchedKnobs (the engine's switches, read at creation) and plan_batch: what a batch's launch graph will be, decided
 //                       from counters before anything is enqueued (host-only C++, tested without a GPU)
@@ -235,7 +236,12 @@ struct FlowEntry {
 // call works on the live copy and restores the snapshot taken at its start if it fails, so a failed call consumes
 // nothing.
 struct Sched {
+    // TWO frame counters ("Restarting object slots").  frame_idx is the ENGINE's number of the object's next frame: every
+    // ring -- plane slots, twist slots and their tags, hist[].frame, log and quality rows -- is indexed by it, so that the object's
+    // slots agree with what the kernels derive from roft_engine::frame_counter.  track_frames counts the frames since the object's
+    // track started (roft_object_add, roft_objects_restart) and answers the first-frame questions.  They differ after a restart.
     int frame_idx = 0;
+    int track_frames = 0;
     bool seg_available = false;        // ImageSegmentationOFAidedSource::segmentation_available_
     bool of_first_frame = true;        // ...::is_first_frame_
     bool flow_first_frame = true;      // ImageOpticalFlowMeasurement::is_first_frame_
@@ -284,6 +290,9 @@ struct HostObject {
     // z-buffer where it has at least two members (-1: none, the object is always drawn alone)
     int pose_scene = -1, pose_zscene = -1;
     double pose0[7] = {0, 0, 0, 1, 0, 0, 0};
+    // roft_objects_restart: what roft_get_outputs showed for the track that ended, shown until the new track's first step
+    roft_object_output last_out{};
+    bool last_out_valid = false;
     ~HostObject() { for (auto* o : owned) delete o; }
 };
 
@@ -538,6 +547,7 @@ struct roft_engine {
     int batch_counter = 0, frame_counter = 0;
     int completed_batches = 0, completed_frames = 0;
     roft_engine_stats stats{};
+    roft_engine_restart_stats restart_stats{};   // roft_objects_restart
     bool device_pointers_checked = false;   // ROFT_MEM_DEVICE inputs are looked up once, on the first submit
     // A batch is "steady" when at least `lead` batches have been stepped since the engine was last idle (creation, roft_sync and
     // everything that calls it), a burst otherwise: plan_batch.

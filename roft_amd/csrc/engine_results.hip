@@ -39,6 +39,8 @@ int roft_get_outputs(roft_engine* e, roft_object_output* outs, int n_outs)
     std::vector<ObjState> st(n_outs);
     HIP_TRY(hipMemcpy(st.data(), e->arr.state.p, sizeof(ObjState) * n_outs, hipMemcpyDeviceToHost));
     for (int i = 0; i < n_outs; ++i) {
+        // (a restarted slot shows the last row of the track that ended until its new track has stepped)
+        if (e->objs[i]->last_out_valid) { outs[i] = e->objs[i]->last_out; continue; }
         const int lin = e->objs[i]->stepped_lane;
         std::memcpy(outs[i].pose, st[i].belief[B_LIN0 + e->objs[i]->stepped_slot].mean, sizeof(double) * 13);
         std::memcpy(outs[i].twist, st[i].v_mean, sizeof(double) * 6);
@@ -125,7 +127,7 @@ int roft_get_mask(roft_engine* e, int id, uint8_t* mask_out)
 {
     if (!e || !mask_out || id < 0 || id >= (int)e->objs.size()) return fail(ROFT_ERR_INVALID, "bad arguments");
     const Sched& o = e->objs[id]->s;
-    if (o.frame_idx == 0 || e->submitted) return fail(ROFT_ERR_STATE, "no stepped frame to read the mask of");
+    if (o.track_frames == 0 || e->submitted) return fail(ROFT_ERR_STATE, "no stepped frame to read the mask of");
     if (int rc = roft_sync(e)) return rc;
     const EngineArrays& a = e->arr.a;
     const int slot = (o.frame_idx - 1) % kPlaneSlots;

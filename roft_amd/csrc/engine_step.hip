@@ -489,7 +489,7 @@ int roft_step(roft_engine* e)
         roft_batch_trace& tr = e->trace[e->batch_counter % roft_engine::kTraceRing];
         if (tr.batch == e->batch_counter) tr.step_us = host_now_us() - t_step0;
     }
-    for (HostObject* ho : e->objs) { ho->stepped_slot = ho->s.cur_slot; ho->stepped_lane = ho->s.own[ho->s.cur_slot]; ho->stepped_flow = ho->s.flow_made; ho->stepped_depth = ho->s.depth_prev; }
+    for (HostObject* ho : e->objs) { ho->stepped_slot = ho->s.cur_slot; ho->stepped_lane = ho->s.own[ho->s.cur_slot]; ho->stepped_flow = ho->s.flow_made; ho->stepped_depth = ho->s.depth_prev; ho->last_out_valid = false; }
     // (a failed step leaves the engine consistent as far as the host can tell: the batch counts as enqueued)
     const int T = e->pending.facts.T;
     e->frame_counter += T;

@@ -496,10 +496,11 @@ static int schedule_mask_source(roft_engine* e, const FrameJob& j, const ImageSi
     c.slot_prev = (o.frame_idx + kPlaneSlots - 1) % kPlaneSlots;
     c.slot_cur = o.frame_idx % kPlaneSlots;
     // masks from poses (roft_engine_enable_pose_masks): an enrolled object whose frame brings neither a mask nor a label image takes
-    // the silhouette of the delivered pose -- on its first frame, without one, of the pose it was added with
+    // the silhouette of the delivered pose -- on the first frame of its track (Sched::track_frames), without one, of the pose it was
+    // added or restarted with
     const EnginePoseMasks& pm = e->pose_masks;
     const bool enrolled = pm.enabled && (ho.pose_masks || (pm.all && e->h_params[j.id].n_verts > 0 && e->h_params[j.id].n_tris > 0));
-    const bool from_pose = enrolled && !d.mask && !d.labels && (j.in.pose_valid || o.frame_idx == 0);
+    const bool from_pose = enrolled && !d.mask && !d.labels && (j.in.pose_valid || o.track_frames == 0);
     const bool has_mask = d.mask || d.labels || from_pose;
     c.has_new_mask = has_mask ? 1 : 0;
     c.new_mask = static_cast<const uint8_t*>(d.mask);
@@ -697,6 +698,7 @@ static int submit_frames(roft_engine* e, const roft_frame_input* inputs, const r
             }
             TRY(account_lanes_and_features(e, j));
             o.frame_idx++;
+            o.track_frames++;
         }
     }
     // silhouettes of one scene hide each other: a pair that shares its frame with another drawn member of its scene is drawn against

@@ -161,6 +161,39 @@ class ROFTFilterBatch:
         self._meshes = getattr(self, "_meshes", []) + [(verts, tris)]   # render_log draws them
         return oid.value
 
+    def restart_objects(self, items, keep_mesh=False):
+        """A new track in the same slot (roft_objects_restart): items = [(obj_id, desc, verts, tris), ...], all restarted by ONE call,
+        which waits for every stepped batch like sync().  From the engine's next frame on each named slot behaves, bit for bit, like
+        the object of a new engine added with `desc` and that mesh; the other objects are untouched.  keep_mesh: verts / tris are
+        not looked at (None will do) and the slots keep their resident meshes.  Also updates the meshes render_log draws."""
+        items = list(items)
+        n = len(items)
+        ids = (C.c_int * max(n, 1))()
+        descs = (L.ObjectDesc * max(n, 1))()
+        keep = []
+        for i, (oid, desc, verts, tris) in enumerate(items):
+            ids[i] = int(oid)
+            C.memmove(C.byref(descs[i]), C.byref(desc), C.sizeof(L.ObjectDesc))
+            if keep_mesh:
+                descs[i].mesh = L.Mesh(None, 0, None, 0)
+                keep.append(None)
+            else:
+                v = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
+                t = np.ascontiguousarray(tris, np.int32).reshape(-1, 3)
+                descs[i].mesh = L.Mesh(v.ctypes.data, v.shape[0], t.ctypes.data, t.shape[0])
+                keep.append((v, t))
+        L.check(L.lib().roft_objects_restart(self._h, ids, descs, n, L.RESTART_KEEP_MESH if keep_mesh else 0))
+        meshes = getattr(self, "_meshes", [])
+        for (oid, _, _, _), m in zip(items, keep):
+            if m is not None and 0 <= int(oid) < len(meshes):
+                meshes[int(oid)] = m
+
+    def restart_stats(self):
+        """calls / objects restarted / meshes replaced by restart_objects since the engine was created."""
+        st = L.EngineRestartStats()
+        L.check(L.lib().roft_engine_get_restart_stats(self._h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in L.EngineRestartStats._fields_}
+
     def submit(self, frames):
         """frames: one dict per object with keys depth, flow, mask, pose (None or (x, q)), dt,
         mem_kind; depth/flow/mask are numpy arrays (HOST) or integer device addresses (DEVICE).

@@ -4,8 +4,16 @@
 // ROFTFilter::filtering_step, so this is the same computation per object (tests/test_facade.py compares the two).
 //
 //   ROFT-tracker-batch --from config.cfg [--group::key value ...]        the reference's configuration file and overrides
-//                      --log_root DIR [--batch_frames T] [--outlier_bands B] [--device D] [--shard RANK WORLD]
+//                      --log_root DIR [--batch_frames T] [--outlier_bands B] [--device D] [--shard RANK WORLD] [--slots N]
 //                      --object SEQUENCE_DIR NAME [MESH.obj] [--object ...]
+//
+// Without --slots every sequence is an object of the engine and all of them stop when the first source runs dry (sequences of unequal
+// length are cut to the shortest; a line on stderr says so).  `--slots N`: a QUEUE of sequences over min(N, sequences) object slots --
+// every sequence is tracked to its own end, and a slot whose sequence has ended takes the next queued one through
+// roft_objects_restart (new description, new mesh; its first frame must deliver a mask, as today).  A batch ends at the first frame at
+// which any slot's source runs dry, so restarts fall between submits, and all slots that end in one batch restart in one call.  A
+// slot with nothing left to take is fed its last depth image without flow, mask or pose; its rows are discarded.  Logs are written
+// per sequence with that sequence's own frame count; --shard splits the sequence list first.
 //
 // Several GPUs: one process per GPU, each given the same object list, `--device r --shard r G`: process r tracks the r-th block
 // of ceil(n / G) objects (the partition of roft_amd/parallel.py) -- no process talks to another while tracking.
@@ -61,6 +69,7 @@ struct TrackedObject {
     std::vector<std::int32_t> tris;
     double last_stamp = -1.0;
     bool mask_received = false;
+    bool frozen = false;   // --slots: the camera's next frame has been frozen already (the batch it belonged to ended in front of it)
 };
 
 // what one frame of one object hands to the engine, kept alive until the batch has been submitted
@@ -168,7 +177,7 @@ int main(int argc, char** argv)
         // ---- split the command line: what is ours, what is the configuration's
         std::vector<ObjectArgs> objects;
         std::string log_root, gather_id_file;
-        int batch_frames = 6, device = 0, shard_rank = 0, shard_world = 1, outlier_bands = 0;
+        int batch_frames = 6, device = 0, shard_rank = 0, shard_world = 1, outlier_bands = 0, slots = -1;
         std::vector<char*> cfg_argv = {argv[0]};
         for (int i = 1; i < argc; ++i) {
             const std::string a = argv[i];
@@ -184,9 +193,11 @@ int main(int argc, char** argv)
             else if (a == "--outlier_bands" && i + 1 < argc) outlier_bands = std::atoi(argv[++i]);   // roft_config::outlier_bands_per_alternative
             else if (a == "--shard" && i + 2 < argc) { shard_rank = std::atoi(argv[i + 1]); shard_world = std::atoi(argv[i + 2]); i += 2; }
             else if (a == "--gather" && i + 1 < argc) gather_id_file = argv[++i];
+            else if (a == "--slots" && i + 1 < argc) { slots = std::atoi(argv[++i]); if (slots < 1) throw std::runtime_error("--slots N: N >= 1"); }
             else cfg_argv.push_back(argv[i]);
         }
-        if (objects.empty() || log_root.empty()) throw std::runtime_error("usage: ROFT-tracker-batch --from config.cfg [--group::key value ...] --log_root DIR [--batch_frames T] [--outlier_bands B] [--device D] [--shard RANK WORLD] --object SEQUENCE_DIR NAME [MESH.obj] ...");
+        if (objects.empty() || log_root.empty()) throw std::runtime_error("usage: ROFT-tracker-batch --from config.cfg [--group::key value ...] --log_root DIR [--batch_frames T] [--outlier_bands B] [--device D] [--shard RANK WORLD] [--slots N] --object SEQUENCE_DIR NAME [MESH.obj] ...");
+        if (slots > 0 && !gather_id_file.empty()) throw std::runtime_error("--slots and --gather do not combine: with --slots every process writes the logs of its own sequences");
         if (shard_world < 1 || shard_rank < 0 || shard_rank >= shard_world) throw std::runtime_error("--shard RANK WORLD: 0 <= RANK < WORLD");
 #ifndef ROFT_WITH_RCCL
         if (!gather_id_file.empty()) throw std::runtime_error("--gather needs a build with -DROFT_WITH_RCCL (rccl.h / librccl)");
@@ -196,6 +207,7 @@ int main(int argc, char** argv)
             const std::size_t per = (objects.size() + (std::size_t)shard_world - 1) / (std::size_t)shard_world;
             const std::size_t lo = std::min(objects.size(), per * (std::size_t)shard_rank), hi = std::min(objects.size(), lo + per);
             objects = std::vector<ObjectArgs>(objects.begin() + (long)lo, objects.begin() + (long)hi);
+            if (objects.empty() && slots > 0) { std::printf("tracked 0 sequences in 0 slots over 0 engine frames\n"); return EXIT_SUCCESS; }
             if (objects.empty() && gather_id_file.empty()) { std::printf("tracked 0 objects over 0 frames\n"); return EXIT_SUCCESS; }
             if (objects.empty()) throw std::runtime_error("--gather: every process needs at least one object (fewer processes than objects)");
         }
@@ -293,13 +305,15 @@ int main(int argc, char** argv)
         cfg.flow_aided_segmentation = flow_aided;
         cfg.mask_frames_between = tracked[0].segmentation->get_frames_between_iterations();
         cfg.pose_frames_between = std::max(0, tracked[0].pose->get_frames_between_iterations());
-        cfg.max_objects = (int)tracked.size();
+        const int n_slots = slots > 0 ? std::min(slots, (int)tracked.size()) : (int)tracked.size();   // (--slots: the rest of the sequences queue)
+        cfg.max_objects = n_slots;
         cfg.device = device;
         if (batch_frames < 1 || batch_frames > ROFT_MAX_BATCH_FRAMES) throw std::runtime_error("--batch_frames out of range");
         cfg.max_batch_frames = batch_frames;
         cfg.outlier_bands_per_alternative = outlier_bands;   // (0: the engine's choice, which follows the load)
         ROFTFilterBatch engine(cfg);
-        for (TrackedObject& t : tracked) {
+        // the description a sequence's object starts with (its mesh arrays stay with the TrackedObject)
+        auto describe = [&](TrackedObject& t) {
             roft_object_desc d{};
             compat::throw_if(roft_default_object(&d), "roft_default_object");
             // initial pose: the first row of the object's pose file (test/test.sh:120-123)
@@ -317,69 +331,48 @@ int main(int argc, char** argv)
             }
             d.v_meas_cov_flow[0] = m_cov_flow(0); d.v_meas_cov_flow[1] = m_cov_flow(1);
             d.mesh = roft_mesh{t.verts.data(), (int)(t.verts.size() / 3), t.tris.data(), (int)(t.tris.size() / 3)};
-            engine.add_object(d);
-        }
+            return d;
+        };
+        for (int o = 0; o < n_slots; ++o) engine.add_object(describe(tracked[(std::size_t)o]));
 
         // ---- frames: every source polled as ROFTFilter::filtering_step polls it, T frames handed over at a time
-        const int n_obj = (int)tracked.size();
+        const int n_obj = n_slots;
         const int log_capacity = 1 << 16;
         compat::throw_if(roft_engine_enable_log(engine.engine(), log_capacity), "roft_engine_enable_log");
-        int frames = 0;
-        bool more = true;
-        while (more && frames + batch_frames <= log_capacity) {
-            std::vector<FrameBuffers> buffers((std::size_t)batch_frames * n_obj);
-            std::vector<roft_frame_input> inputs((std::size_t)batch_frames * n_obj);
-            int t_in = 0;
-            for (; t_in < batch_frames && more; ++t_in) {
-                for (int o = 0; o < n_obj && more; ++o) {
-                    TrackedObject& t = tracked[o];
-                    FrameBuffers& b = buffers[(std::size_t)t_in * n_obj + o];
-                    roft_frame_input& in = inputs[(std::size_t)t_in * n_obj + o];
-                    in = roft_frame_input{};
-                    if (!t.camera->freeze(CameraMeasurementType::RGBD)) { more = false; break; }
-                    bool valid = false;
-                    bfl::Data cam_data;
-                    std::tie(valid, cam_data) = t.camera->measure();
-                    b.depth = std::get<2>(*bfl::any::any_cast<CameraMeasurement::CameraMeasurementTuple>(&cam_data));
-                    double stamp = 0.0;
-                    bool has_stamp = false;
-                    std::tie(has_stamp, stamp) = t.camera->camera_time_stamp_rgb();
-                    in.dt = (has_stamp && t.last_stamp != -1.0) ? stamp - t.last_stamp : sample_time;
-                    if (has_stamp) t.last_stamp = stamp;
-                    if (t.flow->is_stepping_required()) t.flow->step_frame();
-                    bool valid_flow = false;
-                    std::tie(valid_flow, b.flow) = t.flow->flow(false);
-                    if (t.segmentation->is_stepping_required()) t.segmentation->step_frame();
-                    bool new_mask = false;
-                    std::tie(new_mask, b.mask) = t.segmentation->segmentation(false);
-                    if (!t.mask_received && !new_mask) throw std::runtime_error("the first frame of " + t.args.root + " delivers no mask");
-                    t.mask_received = true;
-                    in.depth = b.depth.data();
-                    in.flow = valid_flow ? b.flow.data : nullptr;
-                    in.mask = new_mask ? b.mask.data : nullptr;
-                    in.mem_kind = ROFT_MEM_HOST;
-                    if (use_pose && t.pose->freeze(false)) {
-                        const auto P = t.pose->transform();
-                        in.pose_valid = 1;
-                        for (int i = 0; i < 3; ++i) in.pose_x[i] = P.translation()[i];
-                        for (int i = 0; i < 4; ++i) in.pose_q[i] = P.quaternion()[i];
-                    }
-                }
-                if (!more) break;
+        // one frame of one sequence whose camera has been frozen: its images into `b`, what the engine takes into `in`
+        auto read_frame = [&](TrackedObject& t, FrameBuffers& b, roft_frame_input& in) {
+            in = roft_frame_input{};
+            bool valid = false;
+            bfl::Data cam_data;
+            std::tie(valid, cam_data) = t.camera->measure();
+            b.depth = std::get<2>(*bfl::any::any_cast<CameraMeasurement::CameraMeasurementTuple>(&cam_data));
+            double stamp = 0.0;
+            bool has_stamp = false;
+            std::tie(has_stamp, stamp) = t.camera->camera_time_stamp_rgb();
+            in.dt = (has_stamp && t.last_stamp != -1.0) ? stamp - t.last_stamp : sample_time;
+            if (has_stamp) t.last_stamp = stamp;
+            if (t.flow->is_stepping_required()) t.flow->step_frame();
+            bool valid_flow = false;
+            std::tie(valid_flow, b.flow) = t.flow->flow(false);
+            if (t.segmentation->is_stepping_required()) t.segmentation->step_frame();
+            bool new_mask = false;
+            std::tie(new_mask, b.mask) = t.segmentation->segmentation(false);
+            if (!t.mask_received && !new_mask) throw std::runtime_error("the first frame of " + t.args.root + " delivers no mask");
+            t.mask_received = true;
+            in.depth = b.depth.data();
+            in.flow = valid_flow ? b.flow.data : nullptr;
+            in.mask = new_mask ? b.mask.data : nullptr;
+            in.mem_kind = ROFT_MEM_HOST;
+            if (use_pose && t.pose->freeze(false)) {
+                const auto P = t.pose->transform();
+                in.pose_valid = 1;
+                for (int i = 0; i < 3; ++i) in.pose_x[i] = P.translation()[i];
+                for (int i = 0; i < 4; ++i) in.pose_q[i] = P.quaternion()[i];
             }
-            if (t_in == 0) break;
-            inputs.resize((std::size_t)t_in * n_obj);
-            engine.filtering_steps(inputs, n_obj, t_in);
-            frames += t_in;
-        }
-        engine.wait();
-
-        // ---- logs in the reference's format (ROFTFilter.cpp:386-394 through bfl::Logger)
-        std::vector<double> rows((std::size_t)frames * n_obj * 19);
-        compat::throw_if(roft_engine_get_log_rows(engine.engine(), 0, frames, rows.data()), "roft_engine_get_log_rows");
-        auto write_logs = [&](const std::vector<double>& rows, int n_obj, int frames, const ObjectArgs* names) {
-        for (int o = 0; o < n_obj; ++o) {
-            const std::string dir = log_root + "/" + names[o].name;
+        };
+        // the logs of one sequence in the reference's format (ROFTFilter.cpp:386-394 through bfl::Logger): rows[f * stride + 0 .. 18]
+        auto write_sequence_logs = [&](const std::string& name, const double* rows, std::size_t stride, int frames) {
+            const std::string dir = log_root + "/" + name;
             std::error_code ec;
             std::filesystem::create_directories(dir, ec);
             if (ec) throw std::runtime_error("cannot create " + dir + ": " + ec.message());
@@ -388,7 +381,7 @@ int main(int argc, char** argv)
             EstimateLog log;
             if (!log.enable_log(dir, "")) throw std::runtime_error("cannot write the logs in " + dir);
             for (int f = 0; f < frames; ++f) {
-                const double* r = &rows[((std::size_t)f * n_obj + o) * 19];
+                const double* r = rows + (std::size_t)f * stride;
                 Eigen::VectorXd p(13), v(6);
                 for (int i = 0; i < 9; ++i) p(i) = r[i];
                 double axis[3], angle;
@@ -398,7 +391,125 @@ int main(int argc, char** argv)
                 for (int i = 0; i < 6; ++i) v(i) = r[13 + i];
                 log.logger(p.transpose(), v.transpose());
             }
+        };
+
+        if (slots > 0) {
+            // ---- a queue of sequences over n_slots slots
+            struct Slot {
+                int seq = -1;              // the sequence the slot tracks (index into `tracked`), -1: nothing left to take
+                int start = 0;             // engine frame of its first frame
+                Eigen::MatrixXf last_depth;   // what an idle slot is fed
+            };
+            std::vector<Slot> slot((std::size_t)n_slots);
+            for (int o = 0; o < n_slots; ++o) slot[(std::size_t)o].seq = o;
+            int next_seq = n_slots, done = 0, frames = 0;
+            const int n_seq = (int)tracked.size();
+            std::vector<double> rows;
+            while (done < n_seq) {
+                std::vector<FrameBuffers> buffers((std::size_t)batch_frames * n_obj);
+                std::vector<roft_frame_input> inputs((std::size_t)batch_frames * n_obj);
+                std::vector<int> ended;   // slots whose source ran dry in front of frame t_in
+                int t_in = 0;
+                for (; t_in < batch_frames; ++t_in) {
+                    // the batch ends in front of the first frame at which any slot's source runs dry; the cameras that did deliver
+                    // keep their frozen frame for the next batch
+                    for (int o = 0; o < n_obj; ++o) {
+                        Slot& sl = slot[(std::size_t)o];
+                        if (sl.seq < 0) continue;
+                        TrackedObject& t = tracked[(std::size_t)sl.seq];
+                        if (!t.frozen && !t.camera->freeze(CameraMeasurementType::RGBD)) ended.push_back(o);
+                        else t.frozen = true;
+                    }
+                    if (!ended.empty()) break;
+                    for (int o = 0; o < n_obj; ++o) {
+                        Slot& sl = slot[(std::size_t)o];
+                        FrameBuffers& b = buffers[(std::size_t)t_in * n_obj + o];
+                        roft_frame_input& in = inputs[(std::size_t)t_in * n_obj + o];
+                        if (sl.seq < 0) {
+                            in = roft_frame_input{};
+                            in.dt = sample_time;
+                            in.depth = sl.last_depth.data();
+                            in.mem_kind = ROFT_MEM_HOST;
+                            continue;
+                        }
+                        TrackedObject& t = tracked[(std::size_t)sl.seq];
+                        t.frozen = false;
+                        read_frame(t, b, in);
+                    }
+                }
+                if (t_in > 0) {
+                    inputs.resize((std::size_t)t_in * n_obj);
+                    engine.filtering_steps(inputs, n_obj, t_in);
+                    frames += t_in;
+                    for (int o = 0; o < n_obj; ++o)
+                        if (slot[(std::size_t)o].seq >= 0) slot[(std::size_t)o].last_depth = buffers[(std::size_t)(t_in - 1) * n_obj + o].depth;
+                }
+                if (ended.empty()) continue;
+                // the sequences that ended: their rows (the read waits for the engine, as the restart below does anyway), then the next
+                // queued sequences into their slots -- all in one call
+                std::vector<int> ids;
+                std::vector<roft_object_desc> descs;
+                for (int o : ended) {
+                    Slot& sl = slot[(std::size_t)o];
+                    const int len = frames - sl.start;
+                    if (len > log_capacity) throw std::runtime_error("sequence " + tracked[(std::size_t)sl.seq].args.root + " is longer than the log");
+                    rows.resize((std::size_t)std::max(len, 1) * n_obj * 19);
+                    compat::throw_if(roft_engine_get_log_rows(engine.engine(), sl.start, len, rows.data()), "roft_engine_get_log_rows");
+                    write_sequence_logs(tracked[(std::size_t)sl.seq].args.name, rows.data() + (std::size_t)o * 19, (std::size_t)n_obj * 19, len);
+                    ++done;
+                    if (next_seq < n_seq) {
+                        sl.seq = next_seq++;
+                        sl.start = frames;
+                        ids.push_back(o);
+                        descs.push_back(describe(tracked[(std::size_t)sl.seq]));
+                    } else {
+                        sl.seq = -1;
+                        if (sl.last_depth.size() == 0) sl.last_depth = Eigen::MatrixXf::Zero(height, width);   // (a sequence without a frame)
+                    }
+                }
+                if (!ids.empty()) engine.restart_objects(ids, descs);
+            }
+            engine.wait();
+            std::printf("tracked %d sequences in %d slots over %d engine frames\n", n_seq, n_slots, frames);
+            return EXIT_SUCCESS;
         }
+
+        int frames = 0;
+        bool more = true;
+        int dry = -1, dry_frame_consumed = 0;   // the source that ran dry first, and how many sources had delivered that frame before it
+        while (more && frames + batch_frames <= log_capacity) {
+            std::vector<FrameBuffers> buffers((std::size_t)batch_frames * n_obj);
+            std::vector<roft_frame_input> inputs((std::size_t)batch_frames * n_obj);
+            int t_in = 0;
+            for (; t_in < batch_frames && more; ++t_in) {
+                for (int o = 0; o < n_obj && more; ++o) {
+                    TrackedObject& t = tracked[o];
+                    if (!t.camera->freeze(CameraMeasurementType::RGBD)) { more = false; dry = o; dry_frame_consumed = o; break; }
+                    read_frame(t, buffers[(std::size_t)t_in * n_obj + o], inputs[(std::size_t)t_in * n_obj + o]);
+                }
+                if (!more) break;
+            }
+            if (t_in == 0) break;
+            inputs.resize((std::size_t)t_in * n_obj);
+            engine.filtering_steps(inputs, n_obj, t_in);
+            frames += t_in;
+        }
+        engine.wait();
+        {
+            // sequences of unequal length are cut to the shortest here: say so
+            int left = dry_frame_consumed;
+            for (int o = dry + 1; o < n_obj && dry >= 0; ++o) left += tracked[(std::size_t)o].camera->freeze(CameraMeasurementType::RGBD) ? 1 : 0;
+            if (dry < 0) for (int o = 0; o < n_obj; ++o) left += tracked[(std::size_t)o].camera->freeze(CameraMeasurementType::RGBD) ? 1 : 0;
+            if (left > 0)
+                std::fprintf(stderr, "ROFT-tracker-batch: stopped after %d frames with %d of %d sources that still had frames (--slots N tracks every sequence to its end)\n",
+                             frames, left, n_obj);
+        }
+
+        // ---- logs in the reference's format (ROFTFilter.cpp:386-394 through bfl::Logger)
+        std::vector<double> rows((std::size_t)frames * n_obj * 19);
+        compat::throw_if(roft_engine_get_log_rows(engine.engine(), 0, frames, rows.data()), "roft_engine_get_log_rows");
+        auto write_logs = [&](const std::vector<double>& rows, int n_obj, int frames, const ObjectArgs* names) {
+            for (int o = 0; o < n_obj; ++o) write_sequence_logs(names[o].name, rows.data() + (std::size_t)o * 19, (std::size_t)n_obj * 19, frames);
         };
 #ifdef ROFT_WITH_RCCL
         if (!gather_id_file.empty()) {
