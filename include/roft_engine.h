@@ -810,7 +810,8 @@ int roft_pose_silhouette(const roft_camera* cam, const roft_mesh* mesh, const do
  *  - Downstream, everything is what it is for a delivered mask.
  *  - roft_engine_pose_mask_stats keeps its meaning: silhouettes are counted whether hidden or not.
  * LIMITS.  Only enrolled objects with silhouettes on the same frame hide each other: hands, clutter and plain-mask objects do not.
- * The silhouettes are not gated against the frame's depth (a delayed pose belongs to an older image than the frame that carries it).
+ * Those are what the depth gate below removes (roft_engine_enable_pose_mask_depth_gate: the silhouettes compared with the depth of
+ * the image the pose was computed on -- a delayed pose belongs to an older image than the frame that carries it).
  * Memory: one z-buffer of width x height x 8 bytes per scene with at least two members, times 2 x ROFT_MAX_BATCH_FRAMES, allocated
  * by this call; nothing grows on the hot path.
  *
@@ -835,6 +836,73 @@ int roft_engine_get_pose_mask_occlusion_stats(roft_engine* e, roft_engine_pose_m
 int roft_pose_silhouettes_occluded(const roft_camera* cam, const roft_mesh* meshes, int n, const double* x /* [n][3] */,
                                    const double* q /* [n][4] */, int bands, int vertex_cache,
                                    uint8_t* masks_out /* [n][H][W], optional */, int* counts_out /* [n], optional */);
+
+/* ---- (3e, continued) silhouettes gated against the depth of the pose's own frame ------------------------------------------------ *
+ * A network mask leaves out the hand that holds the object; a drawn silhouette paints it in, and the engine then samples the hand's
+ * flow and takes features and quality records on it.  Opt-in: every silhouette the engine draws is compared, pixel by pixel, with a
+ * depth image the engine already holds, and loses the pixels where the sensor saw something clearly nearer (or, optionally, clearly
+ * farther) than the rendered surface.  Off, the engine enqueues exactly what it does without this call; on, it adds no launch.
+ *
+ * THE KEEP PREDICATE.  With tf = front_tolerance, tb = behind_tolerance, R a rendered depth and D a sensor depth, all floats,
+ *        keep(R, D) = !(D > 0.0f && D < R - tf) && !(tb > 0.0f && D > R + tb)
+ * -- R - tf and R + tb each rounded once to float, nothing contracted.  A NaN depth keeps the pixel; so does a depth of 0 (the
+ * sensor's "no reading").  No pixel fails both tests; pixels_front counts the first, pixels_behind the second.
+ *
+ * A PAIR DRAWN ALONE.  For an enrolled object and a frame on which its mask is a silhouette (the rules above: a delivered pose, or
+ * p_mean0 on the first frame of a track) the engine behaves BIT FOR BIT as if the object had been handed the HOST mask
+ *        M'(p) = (R(p) > 0 && keep(R(p), D_g(p))) ? 255 : 0,      R = roft_render_depth(mesh, pose_x, pose_q, cam, 1).
+ * A PAIR OF A SCENE (roft_engine_enable_pose_mask_occlusion):
+ *        M'_i(p) = (M_i(p) == 255 && keep(R_i(p), D_g,i(p))) ? 255 : 0
+ * with M_i the resolved mask above.  The resolve is decided by the renders alone: a pixel the gate removes still hides the objects
+ * behind it.  Each object uses the depth of its own gate frame.
+ *
+ * THE GATE FRAME g.  A pose that arrives on frame k was computed on an older image.  Let n be the number of buffered flows the chase
+ * of this new mask uses (the last mask_frames_between of the flows buffered since the mask before, all of them when that number is
+ * not given; 0 under the first-mask rule).  n == 0: g is frame k itself.  Otherwise g is the object's frame just before the frame
+ * that delivered the oldest of those n flows -- frame k - n with a complete flow stream, the image a delayed pose source grabbed;
+ * with dropped flow frames, the frame the chase itself starts from.  D_g is the float image the engine holds for that frame: with
+ * roft_engine_enable_raw_depth the converted or aligned one (roft_depth_convert / roft_depth_align give the same bytes).  The engine
+ * keeps that image as long as the flow (a clone where the flow is cloned); roft_engine_retain_frames() does not change -- the image
+ * is one frame older than its flow, and the window's margin of two frames covers it.
+ * The host counts the buffered flows as if every delivered mask had pixels (it cannot see an empty one): after a silhouette that was
+ * empty, or emptied, on an engine with mask_frames_between > 0 the next chase may use more flows than the gate frame assumes.
+ *
+ * Downstream, everything is what it is for a delivered mask.  A silhouette the gate empties is a "new but empty mask", ignored by the
+ * existing rule: the object goes on with its propagated mask.  roft_engine_pose_mask_stats keeps its meaning.  The gate applies to
+ * every enrolled object of the engine; a delivered mask or label image is never gated.  roft_objects_restart starts a new history: the
+ * first silhouette of the new track is gated against its own frame.
+ *
+ * OUT OF SCOPE.  No verdict and no loss policy: the counts are the caller's to judge.  Delivered masks are not gated.  One pair of
+ * tolerances per engine.  stamped_masks and ROFT_RENDER_GL engines are refused for pose masks already.  The C++ facade has no switch.
+ *
+ * roft_engine_enable_pose_mask_depth_gate(e, g): after roft_engine_enable_pose_masks, before the first frame; g == NULL: the defaults
+ * (0.02, 0).  Refused on the host, with nothing consumed and the reason in roft_last_error_string: ROFT_ERR_STATE after the first frame
+ * or when pose masks are not enabled; ROFT_ERR_INVALID for a front_tolerance that is not finite or not > 0, a behind_tolerance that
+ * is NaN or infinite.
+ * roft_engine_get_pose_mask_gate_stats: waits for the batches stepped so far (all but `gated` are counted on the device).
+ *
+ * roft_pose_silhouettes_gated: the same kernels on HOST buffers, device 0, ONE scene of n meshes and ONE depth image: with n == 1 the
+ * pair drawn alone, with n > 1 the resolve followed by the gate.  removed_out[i] = {front, behind} of object i.  bands and
+ * vertex_cache change no bit.  ROFT_ERR_INVALID before any device is looked for: a NULL cam, meshes, x, q, depth or g, n < 1 or
+ * n > ROFT_SCENE_MAX_INSTANCES, bands < 0, a vertex_cache that is neither 0 nor 1, a triangle that names a vertex outside its mesh,
+ * tolerances as above. */
+typedef struct {
+    float front_tolerance;    /* metres, finite, > 0: a valid depth more than this in FRONT of the rendered surface is an occluder */
+    float behind_tolerance;   /* metres; > 0: a depth more than this BEHIND the rendered surface means the object is not there; <= 0: test off */
+} roft_pose_mask_gate;
+int roft_default_pose_mask_gate(roft_pose_mask_gate* g);                 /* 0.02f, 0.0f */
+int roft_engine_enable_pose_mask_depth_gate(roft_engine* e, const roft_pose_mask_gate* g);
+typedef struct {
+    long long gated;           /* (frame, object) silhouettes compared with a depth image */
+    long long emptied;         /* of those, silhouettes that had pixels and lost every one to the gate */
+    long long pixels_front;    /* pixels removed as occluded */
+    long long pixels_behind;   /* pixels removed by the behind test (and not by the front test) */
+} roft_engine_pose_mask_gate_stats;
+int roft_engine_get_pose_mask_gate_stats(roft_engine* e, roft_engine_pose_mask_gate_stats* out);
+int roft_pose_silhouettes_gated(const roft_camera* cam, const roft_mesh* meshes, int n, const double* x /* [n][3] */,
+                                const double* q /* [n][4] */, const float* depth /* H x W, HOST */, const roft_pose_mask_gate* g,
+                                int bands, int vertex_cache, uint8_t* masks_out /* [n][H][W], optional */,
+                                int* counts_out /* [n], optional */, int* removed_out /* [n][2]: front, behind; optional */);
 
 /* ---- (3b) scene renderer: tracked poses drawn over the camera frames ----------------------------------------------
  * The reference's evaluation draws the mesh at every estimated pose over the grayed camera frame (evaluation/results_renderer.py:

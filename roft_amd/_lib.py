@@ -123,6 +123,14 @@ class EnginePoseMaskOcclusionStats(C.Structure):
     _fields_ = [("resolved", C.c_longlong), ("hidden", C.c_longlong), ("pixels_removed", C.c_longlong)]
 
 
+class PoseMaskGate(C.Structure):
+    _fields_ = [("front_tolerance", C.c_float), ("behind_tolerance", C.c_float)]
+
+
+class EnginePoseMaskGateStats(C.Structure):
+    _fields_ = [("gated", C.c_longlong), ("emptied", C.c_longlong), ("pixels_front", C.c_longlong), ("pixels_behind", C.c_longlong)]
+
+
 RESTART_KEEP_MESH = 1               # ROFT_RESTART_KEEP_MESH
 
 
@@ -182,6 +190,7 @@ ABI_SYMBOLS = [
     "roft_engine_enable_pose_masks", "roft_engine_get_pose_mask_stats", "roft_pose_silhouette", "roft_debug_pose_mask_kernel_ms",
     "roft_engine_enable_pose_mask_occlusion", "roft_engine_get_pose_mask_occlusion_stats", "roft_pose_silhouettes_occluded",
     "roft_objects_restart", "roft_engine_get_restart_stats", "roft_debug_restart_check",
+    "roft_default_pose_mask_gate", "roft_engine_enable_pose_mask_depth_gate", "roft_engine_get_pose_mask_gate_stats", "roft_pose_silhouettes_gated",
 ]
 POSE_ERROR_ADD, POSE_ERROR_ADDS = 0, 1   # ROFT_POSE_ERROR_*
 # entry points younger than ABI version 2 itself: a library built before them still loads through ROFT_LIB_SO
@@ -192,7 +201,9 @@ NEWER_SYMBOLS = ("roft_pose_errors", "roft_engine_score_log", "roft_scene_render
                  "roft_default_quality_params", "roft_engine_enable_quality", "roft_engine_get_quality", "roft_track_quality",
                  "roft_engine_enable_pose_masks", "roft_engine_get_pose_mask_stats", "roft_pose_silhouette",
                  "roft_engine_enable_pose_mask_occlusion", "roft_engine_get_pose_mask_occlusion_stats", "roft_pose_silhouettes_occluded",
-                 "roft_objects_restart", "roft_engine_get_restart_stats")
+                 "roft_objects_restart", "roft_engine_get_restart_stats",
+                 "roft_default_pose_mask_gate", "roft_engine_enable_pose_mask_depth_gate", "roft_engine_get_pose_mask_gate_stats",
+                 "roft_pose_silhouettes_gated")
 
 
 def build(force=False):
@@ -317,6 +328,11 @@ def lib():
         L.roft_engine_get_pose_mask_stats.argtypes = [vp, C.POINTER(EnginePoseMaskStats)]
         L.roft_pose_silhouette.argtypes = [C.POINTER(Camera), C.POINTER(Mesh), vp, vp, C.c_int, C.c_int, vp, ip]
         L.roft_debug_pose_mask_kernel_ms.argtypes = [vp, dp]
+    if hasattr(L, "roft_pose_silhouettes_gated"):
+        L.roft_default_pose_mask_gate.argtypes = [C.POINTER(PoseMaskGate)]
+        L.roft_engine_enable_pose_mask_depth_gate.argtypes = [vp, C.POINTER(PoseMaskGate)]
+        L.roft_engine_get_pose_mask_gate_stats.argtypes = [vp, C.POINTER(EnginePoseMaskGateStats)]
+        L.roft_pose_silhouettes_gated.argtypes = [C.POINTER(Camera), C.POINTER(Mesh), C.c_int, vp, vp, vp, C.POINTER(PoseMaskGate), C.c_int, C.c_int, vp, ip, ip]
     if hasattr(L, "roft_pose_silhouettes_occluded"):
         L.roft_engine_enable_pose_mask_occlusion.argtypes = [vp, ip, ip, C.c_int]
         L.roft_engine_get_pose_mask_occlusion_stats.argtypes = [vp, C.POINTER(EnginePoseMaskOcclusionStats)]

@@ -32,6 +32,7 @@
 #include "roft_device.h"
 #include "mesh_class.h"
 #include "batch_plan.h"
+#include "pose_mask_gate.h"
 #include "opticalflow.h"
 #include "depth.h"
 #include "quality.h"
@@ -230,6 +231,9 @@ struct FlowEntry {
     const void* ptr;
     int frame;   // frame index the flow was delivered with
     int owned;   // index into HostObject::owned when the engine holds its own copy, else -1
+    // the depth of the object's frame before the one that delivered the flow (Sched::depth_prev when the flow was pushed; null: none):
+    // what a silhouette whose chase starts at this flow is gated against (pose_mask_gate.h).  Cloned with the flow (OwnedFlow::depth)
+    const float* depth_before;
 };
 
 // Schedule-driven mirrors of the reference's source / measurement-model state machines.  Trivially copyable: a submit
@@ -261,6 +265,9 @@ struct Sched {
     int own[kNumLin] = {0, 1};         // pose chain lane that walks each of the two slots (always different lanes)
     int last_touch[kNumLin] = {-1, -1};   // last batch whose pose chain reads or writes each slot
     int flows_since_mask = 0;          // upper bound of the flows buffered since the last delivered mask
+    // ... and the number itself where every delivered mask had pixels (the host cannot see an empty one: flow_buffer_ of the OF-aided
+    // source, this frame's flow counted in; 0 again behind a delivered mask): what names the gate frame (pose_mask_gate.h)
+    int flows_buffered = 0;
     const float* depth_prev = nullptr;
     // camera images (roft_frames_submit_images): the pyramid slot of the image the frame before carried, in that frame's
     // generation (EngineFlow::pyr; -1: it carried none), and the flow the engine produced for the last frame (null: none)
@@ -271,6 +278,7 @@ struct Sched {
 
 struct OwnedFlow {
     DevBuf<unsigned char> buf;
+    DevBuf<float> depth;       // engines with the depth gate: the clone of FlowEntry::depth_before
     int last_ref_frame = -1;   // last frame whose control block references the copy
 };
 
@@ -362,6 +370,12 @@ struct EnginePoseMasks {
     roft_engine_pose_mask_occlusion_stats occl_stats{};   // (resolved: counted by submit; the rest is read from zstats)
     DevBuf<unsigned long long> zbuf, zstats;
     DevBuf<SilhouettePair> zpairs;
+    // silhouettes gated against the depth of the pose's own frame (roft_engine_enable_pose_mask_depth_gate).  Allocated when the mode
+    // is enabled: the pair records (zpairs, shared with the occlusion mode: a pair is drawn alone or resolved) and three counters
+    bool gate = false;
+    roft_pose_mask_gate gate_prm{};
+    roft_engine_pose_mask_gate_stats gate_stats{};   // (gated: counted by submit; the rest is read from gstats)
+    DevBuf<unsigned long long> gstats;
     ~EnginePoseMasks()
     {
         for (hipEvent_t ev : ev_start) if (ev) (void)hipEventDestroy(ev);
@@ -446,6 +460,7 @@ struct PendingBatch {
     size_t label_table_bytes = 0;
     // masks from poses: bit t: some enrolled object's mask of frame t is the silhouette of its pose (facts.pose_masks counts the pairs)
     unsigned pose_mask_frames = 0;
+    int gated_pairs = 0;               // ... and the pairs among them that are compared with a depth image (the depth gate)
     std::vector<FlowFrameJobs> flow_jobs;   // [T] camera images: what enqueue_flow_production enqueues, frame by frame
     std::vector<DepthJob> depth_jobs;       // raw depth: what enqueue_depth_production enqueues
     // Small HOST images in PINNED memory (the per-object masks of a delivery: 64 buffers of 300 KB) are not copied one
@@ -459,6 +474,7 @@ struct PendingBatch {
         facts = SubmitFacts{};
         facts.T = T;
         feat_frames = new_mask_frames = pose_mask_frames = 0;
+        gated_pairs = 0;
         label_sets.clear();
         label_members.clear();
         label_table_bytes = 0;
@@ -519,6 +535,10 @@ struct roft_engine {
     //   plane ring kPlaneSlots > lead * T + T + 1;  twist ring kTwistRing > lead * T + pose_frames_between + 2;
     //   feature ring kFeatRing >= T + 2 (re-use is ordered by feat_use);
     //   caller buffers / HOST staging: retain = hist_cap + lead * T + 2 frames.
+    //   The depth gate of masks from poses reads FlowEntry::depth_before, ONE frame older than the oldest flow a frame may name
+    //   (age hist_cap instead of hist_cap - 1; older entries are clones).  The margin covers it: a frame in flight is at most
+    //   (lead - 1) * T behind the counter C of the submit that recycles slots, so the oldest image named is C - (lead - 1) * T -
+    //   hist_cap, and the newest slot recycled is C - retain + T - 1 = C - hist_cap - (lead - 1) * T - 3.  retain stays as it is.
     static constexpr int kBatchRing = 8;
     int T_max = 1;        // cfg.max_batch_frames
     int lead = 6;         // batches

@@ -385,10 +385,15 @@ int roft_labels_to_masks(const void* labels, int label_type, int W, int H, const
 
 // Masks from poses, stand-alone: the engine's silhouette kernels on a compact layout -- n objects of ONE scene, one ingest slot each,
 // one frame.  With one object there is nothing to resolve: the one-pass launch, as in an engine without the occlusion mode.
+// gate: every pair is compared with `depth` (one image: every object's gate frame) -- the pair drawn alone for n == 1, the resolve
+// followed by the gate for n > 1.
 static int pose_silhouettes(const char* what, const roft_camera* cam, const roft_mesh* meshes, int n, const double* x, const double* q, int bands,
-                            int vertex_cache, uint8_t* masks_out, int* counts_out)
+                            int vertex_cache, uint8_t* masks_out, int* counts_out, bool gated = false, const float* depth = nullptr,
+                            const roft_pose_mask_gate* gate = nullptr, int* removed_out = nullptr)
 {
-    if (!cam || !meshes || !x || !q) return fail(ROFT_ERR_INVALID, "null argument");
+    if (!cam || !meshes || !x || !q || (gated && (!depth || !gate))) return fail(ROFT_ERR_INVALID, "null argument");
+    if (gated && !pose_mask_gate_valid(gate->front_tolerance, gate->behind_tolerance))
+        return fail(ROFT_ERR_INVALID, std::string(what) + ": front_tolerance must be finite and > 0, behind_tolerance finite (<= 0: that test is off)");
     if (n < 1 || n > ROFT_SCENE_MAX_INSTANCES) return fail(ROFT_ERR_INVALID, std::string(what) + ": n must be 1 .. ROFT_SCENE_MAX_INSTANCES");
     if (bands < 0) return fail(ROFT_ERR_INVALID, "bands must be >= 0 (0: the library's choice)");
     if (vertex_cache != 0 && vertex_cache != 1) return fail(ROFT_ERR_INVALID, "vertex_cache must be 0 or 1");
@@ -417,6 +422,10 @@ static int pose_silhouettes(const char* what, const roft_camera* cam, const roft
     DevBuf<ObjParams> d_prm;
     DevBuf<unsigned long long> d_zbuf, d_zstats;
     DevBuf<SilhouettePair> d_zpairs;
+    DevBuf<unsigned char> d_depth;
+    DevBuf<int> d_removed;
+    if (gated)
+        if (int rc = to_dev(d_depth, depth, npix, c.stream)) return rc;
     std::vector<ObjParams> prm((size_t)n);
     std::vector<FrameCtrl> fc((size_t)n);
     std::memset(prm.data(), 0, sizeof(ObjParams) * prm.size());
@@ -442,6 +451,7 @@ static int pose_silhouettes(const char* what, const roft_camera* cam, const roft
         fc[k].has_new_mask = 1;
         fc[k].label_type = kMaskFromPose;
         fc[k].label = n > 1 ? 1 : 0;   // (z-buffer 0 of the frame)
+        fc[k].gate_depth = gated ? reinterpret_cast<const float*>(d_depth.p) : nullptr;
         for (int i = 0; i < 3; ++i) fc[k].pose_x[i] = x[3 * k + i];
         for (int i = 0; i < 4; ++i) fc[k].pose_q[i] = q[4 * k + i];
     }
@@ -465,16 +475,27 @@ static int pose_silhouettes(const char* what, const roft_camera* cam, const roft
     sa.W = dc.W; sa.H = dc.H; sa.wpr = dc.wpr;
     sa.fx = (float)dc.fx; sa.fy = (float)dc.fy; sa.cx = (float)dc.cx; sa.cy = (float)dc.cy;   // (divider 1: the camera as it is)
     sa.frames_packed = 0u;
+    if (n > 1 || gated) {
+        HIP_TRY(d_zpairs.ensure((size_t)n));
+        HIP_TRY(d_zstats.ensure(2 + 3));   // (the occlusion counters, then the gate's)
+        HIP_TRY(hipMemsetAsync(d_zpairs.p, 0, sizeof(SilhouettePair) * n, c.stream));
+        HIP_TRY(hipMemsetAsync(d_zstats.p, 0, sizeof(unsigned long long) * 5, c.stream));
+        sa.zpairs = d_zpairs.p;
+    }
     if (n > 1) {
         HIP_TRY(d_zbuf.ensure(npix));
-        HIP_TRY(d_zpairs.ensure((size_t)n));
-        HIP_TRY(d_zstats.ensure(2));
-        HIP_TRY(hipMemsetAsync(d_zpairs.p, 0, sizeof(SilhouettePair) * n, c.stream));
-        HIP_TRY(hipMemsetAsync(d_zstats.p, 0, sizeof(unsigned long long) * 2, c.stream));
         sa.zbuf = d_zbuf.p;
         sa.n_zscenes = 1;
-        sa.zpairs = d_zpairs.p;
         sa.zstats = d_zstats.p;
+    }
+    if (gated) {
+        HIP_TRY(d_removed.ensure((size_t)2 * n));
+        HIP_TRY(hipMemsetAsync(d_removed.p, 0, sizeof(int) * 2 * n, c.stream));   // (an object without a mesh is drawn, and removes nothing)
+        sa.gate = 1;
+        sa.gate_tf = gate->front_tolerance;
+        sa.gate_tb = gate->behind_tolerance;
+        sa.gstats = d_zstats.p + 2;
+        sa.gremoved = d_removed.p;
     }
     if (!launch_pose_silhouette(sa, 1, max_verts, bands, vertex_cache, c.stream))
         return fail(ROFT_ERR_INVALID, "pose silhouette: an image row is wider than the kernel's bit window");
@@ -489,6 +510,7 @@ static int pose_silhouettes(const char* what, const roft_camera* cam, const roft
     }
     std::vector<MaskRec> rec((size_t)2 * n);
     HIP_TRY(hipMemcpyAsync(rec.data(), d_rec.p, sizeof(MaskRec) * rec.size(), hipMemcpyDeviceToHost, c.stream));
+    if (gated && removed_out) HIP_TRY(hipMemcpyAsync(removed_out, d_removed.p, sizeof(int) * 2 * n, hipMemcpyDeviceToHost, c.stream));
     HIP_TRY(hipStreamSynchronize(c.stream));   // (fc, prm and rec live in this call)
     HIP_TRY(hipGetLastError());
     if (counts_out)
@@ -506,6 +528,12 @@ int roft_pose_silhouettes_occluded(const roft_camera* cam, const roft_mesh* mesh
                                    int vertex_cache, uint8_t* masks_out, int* counts_out)
 {
     return pose_silhouettes("roft_pose_silhouettes_occluded", cam, meshes, n, x, q, bands, vertex_cache, masks_out, counts_out);
+}
+
+int roft_pose_silhouettes_gated(const roft_camera* cam, const roft_mesh* meshes, int n, const double* x, const double* q, const float* depth,
+                                const roft_pose_mask_gate* g, int bands, int vertex_cache, uint8_t* masks_out, int* counts_out, int* removed_out)
+{
+    return pose_silhouettes("roft_pose_silhouettes_gated", cam, meshes, n, x, q, bands, vertex_cache, masks_out, counts_out, true, depth, g, removed_out);
 }
 
 int roft_pose_process_noise(const double psd[3], const double sig_w[3], double T, double Q[81])

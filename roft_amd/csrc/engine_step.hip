@@ -195,6 +195,17 @@ static int enqueue_preparation(Enqueue& q)
             sa.zpairs = pm.zpairs.p + (size_t)par * kMaxBatch * e->cfg.max_objects;
             sa.zstats = pm.zstats.p;
         }
+        if (pm.gate) {
+            // the depth gate: same launches, every drawn pair compared with FrameCtrl::gate_depth.  The gate images are resident when
+            // the launch runs -- on the upload stream it follows the batch's copies and production in stream order; on the mask stream
+            // that stream has waited for ev_up of every batch with copies or production, this one included (BatchPlan::wait_up), and
+            // with one stream everything is in order anyway.  No wait is added.
+            sa.gate = 1;
+            sa.gate_tf = pm.gate_prm.front_tolerance;
+            sa.gate_tb = pm.gate_prm.behind_tolerance;
+            sa.gstats = pm.gstats.p;
+            sa.zpairs = pm.zpairs.p + (size_t)(e->batch_counter & 1) * kMaxBatch * e->cfg.max_objects;
+        }
         const int slot = e->batch_counter % roft_engine::kBatchRing;
         const hipEvent_t plan_stop = Enqueue::stop(p.ev_prep, q.cur.ev_prep);
         if (!p.prep) tmark(e, nullptr, 0);   // (timing runs: a mark of its own on the mask stream; ahead on the upload stream it is part of mask_prepare)

@@ -535,9 +535,10 @@ static int schedule_mask_source(roft_engine* e, const FrameJob& j, const ImageSi
     if (valid_flow) {
         const int keep = std::min(o.n_hist, e->hist_cap - 1);
         std::memmove(o.hist + 1, o.hist, sizeof(FlowEntry) * (size_t)keep);
-        o.hist[0] = FlowEntry{d.flow, o.frame_idx, -1};
+        o.hist[0] = FlowEntry{d.flow, o.frame_idx, -1, o.depth_prev};   // (depth_prev: still the frame before, schedule_flow_measurement moves it on)
         o.n_hist = keep + 1;
         o.flows_since_mask++;
+        o.flows_buffered = std::min(o.flows_buffered + 1, kMaxFlowHist);
     }
     // Flows that later flows did not push out of the history in time (dropped flow frames): the caller may
     // recycle the buffer once the retention window closes, the reference keeps a clone -- so does the engine.
@@ -552,6 +553,13 @@ static int schedule_mask_source(roft_engine* e, const FrameJob& j, const ImageSi
         }
         if (k < 0) { ho.owned.push_back(new OwnedFlow()); k = (int)ho.owned.size() - 1; }
         HIP_TRY(ho.owned[k]->buf.ensure(sz.flow));
+        if (pm.gate && fe.depth_before) {
+            // the depth gate: the image the chase from this flow starts on ages out one frame BEFORE its flow; it is older than
+            // anything this submit uploads or produces, so the copy needs no place behind the batch's production
+            HIP_TRY(ho.owned[k]->depth.ensure(sz.npix));   // (the float image, also where the caller's frames are the sensor's)
+            HIP_TRY(hipMemcpyAsync(ho.owned[k]->depth.p, fe.depth_before, sz.npix * sizeof(float), hipMemcpyDeviceToDevice, e->up_stream));
+            fe.depth_before = ho.owned[k]->depth.p;
+        }
         if (e->flow.enabled) {
             // (the flow may be one this very submit produces: the copy goes behind that production, in stream order)
             pb.flow_jobs[j.t].clones.push_back(FlowCloneJob{ho.owned[k]->buf.p, fe.ptr});
@@ -582,6 +590,13 @@ static int schedule_mask_source(roft_engine* e, const FrameJob& j, const ImageSi
             return fail(ROFT_ERR_CAPACITY, "more than ROFT_MAX_FLOW_CHASE flows buffered since the last mask");
         o.flows_since_mask = valid_flow ? 1 : 0;   // upper bound: 0 after a consumed mask, 1 after an empty one
     }
+    if (from_pose && pm.gate) {
+        // the gate image of the silhouette: the frame its chase starts on, or -- nothing to chase -- this frame's own depth
+        const int k = pose_mask_gate_entry(o.n_hist, e->cfg.mask_frames_between, o.flows_buffered, c.first_mask != 0);
+        c.gate_depth = k < 0 ? static_cast<const float*>(d.depth) : o.hist[k].depth_before;
+        pb.gated_pairs++;
+    }
+    if (has_mask && !c.first_mask && !e->cfg.stamped_masks) o.flows_buffered = 0;   // (consumed: flow_buffer_.clear(), hpp:218)
     c.n_hist = o.n_hist;
     for (int k = 0; k < o.n_hist; ++k) {
         c.flow[k] = o.hist[k].ptr;
@@ -806,6 +821,7 @@ int roft_frames_submit_images(roft_engine* e, const roft_frame_input* inputs, co
     e->pose_masks.stats.silhouettes += pb.facts.pose_masks;
     e->pose_masks.stats.frames += __builtin_popcount(pb.pose_mask_frames);
     e->pose_masks.occl_stats.resolved += pb.facts.pose_resolve;
+    e->pose_masks.gate_stats.gated += pb.gated_pairs;
     pb.submit_us = host_now_us() - pb.submit_t0;
     return ROFT_OK;
 }
@@ -963,6 +979,56 @@ int roft_engine_get_pose_mask_occlusion_stats(roft_engine* e, roft_engine_pose_m
         pm.occl_stats.pixels_removed = (long long)h[1];
     }
     *out = pm.occl_stats;
+    return ROFT_OK;
+}
+
+// Silhouettes gated against the depth of the pose's own frame.  Everything the hot path touches is allocated here.
+int roft_default_pose_mask_gate(roft_pose_mask_gate* g)
+{
+    if (!g) return fail(ROFT_ERR_INVALID, "null argument");
+    g->front_tolerance = 0.02f;
+    g->behind_tolerance = 0.0f;
+    return ROFT_OK;
+}
+
+int roft_engine_enable_pose_mask_depth_gate(roft_engine* e, const roft_pose_mask_gate* g)
+{
+    if (!e) return fail(ROFT_ERR_INVALID, "null engine");
+    roft_pose_mask_gate prm;
+    if (g) prm = *g; else (void)roft_default_pose_mask_gate(&prm);
+    if (!pose_mask_gate_valid(prm.front_tolerance, prm.behind_tolerance))
+        return fail(ROFT_ERR_INVALID, "pose mask depth gate: front_tolerance must be finite and > 0, behind_tolerance finite (<= 0: that test is off)");
+    if (e->frame_counter > 0 || e->submitted) return fail(ROFT_ERR_STATE, "roft_engine_enable_pose_mask_depth_gate must precede the first frame");
+    EnginePoseMasks& pm = e->pose_masks;
+    if (!pm.enabled) return fail(ROFT_ERR_STATE, "pose mask depth gate: roft_engine_enable_pose_masks comes first");
+    if (e->cfg.cam.width / 32 > kSilhouetteWindowWords / 3) return fail(ROFT_ERR_INVALID, "pose mask depth gate: an image row is wider than a third of the kernel's bit window");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    if (!pm.zpairs.p) {
+        HIP_TRY(pm.zpairs.ensure((size_t)2 * kMaxBatch * e->cfg.max_objects));
+        HIP_TRY(hipMemset(pm.zpairs.p, 0, sizeof(SilhouettePair) * pm.zpairs.n));
+    }
+    HIP_TRY(pm.gstats.ensure(3, true));
+    pm.gate_prm = prm;
+    pm.gate = true;
+    return ROFT_OK;
+}
+
+// (emptied and the pixel counts are counted on the device: the call waits for the batches stepped so far)
+int roft_engine_get_pose_mask_gate_stats(roft_engine* e, roft_engine_pose_mask_gate_stats* out)
+{
+    if (!e || !out) return fail(ROFT_ERR_INVALID, "null argument");
+    EnginePoseMasks& pm = e->pose_masks;
+    if (pm.gate && pm.gstats.p) {
+        HIP_TRY(hipSetDevice(e->cfg.device));
+        HIP_TRY(hipStreamSynchronize(e->up_stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        unsigned long long h[3] = {0, 0, 0};
+        HIP_TRY(hipMemcpy(h, pm.gstats.p, sizeof(h), hipMemcpyDeviceToHost));
+        pm.gate_stats.emptied = (long long)h[0];
+        pm.gate_stats.pixels_front = (long long)h[1];
+        pm.gate_stats.pixels_behind = (long long)h[2];
+    }
+    *out = pm.gate_stats;
     return ROFT_OK;
 }
 

@@ -160,6 +160,8 @@ struct alignas(16) FrameCtrl {
     int label_type;                  // writes its planes; the ordinary ingest skips the object): ROFT_LABEL_*, 0: new_mask as before;
                                      // kMaskFromPose: the silhouette of the mesh at pose_x / pose_q (pose_silhouette_kernel); label is
                                      // then 0, or 1 + the z-buffer the silhouette is resolved against (SilhouetteArgs)
+    const float* gate_depth;         // kMaskFromPose on an engine with the depth gate: the H x W depth of the pair's gate frame
+                                     // (pose_mask_gate.h), else null
 };
 
 // Mask chain record of one frame of the batch and one object (k_mask.hip).  Row t + 1 of EngineArrays::mrec belongs to
@@ -404,6 +406,7 @@ struct SilhouettePair {
     int raw;                     // pixels of the plain silhouette
     int kept;                    // pixels of the resolved one
     int done;                    // workgroups of the resolve that have finished (a ticket)
+    int front, behind;           // depth gate: pixels it removed as occluded / by the behind test
 };
 // what pose_silhouette_kernel reads and where it writes: like LabelIngestArgs, the engine's layout or a compact one (operator)
 struct SilhouetteArgs {
@@ -425,6 +428,12 @@ struct SilhouetteArgs {
     int n_zscenes;
     SilhouettePair* zpairs;      // [delivering frame (grid z)][n_obj], zero between launches
     unsigned long long* zstats;  // [2]: silhouettes that lost every pixel; pixels removed (accumulated)
+    // the depth gate (0: off, and nothing below is read).  Every drawn pair is compared with FrameCtrl::gate_depth; zpairs is then
+    // needed for pairs drawn alone too (their workgroups' ticket)
+    int gate;
+    float gate_tf, gate_tb;      // front tolerance > 0; behind tolerance, <= 0: that test is off
+    unsigned long long* gstats;  // [3]: silhouettes the gate emptied; pixels removed in front; pixels removed behind (accumulated)
+    int* gremoved;               // [delivering frame (grid z)][n_obj][2]: front, behind of every drawn pair (operator), or null
 };
 // every (delivering frame, enrolled object) pair of a batch in ONE launch (grid: bands x objects x delivering frames).  bands 0: one
 // per 64 image rows; vertex_cache 0: project per triangle.  Neither changes a bit.  With sa.zbuf the clear of the z-buffers, the draw

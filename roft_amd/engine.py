@@ -356,6 +356,20 @@ class ROFTFilterBatch:
         ip = C.POINTER(C.c_int)
         L.check(L.lib().roft_engine_enable_pose_mask_occlusion(self._h, ids.ctypes.data_as(ip), scenes.ctypes.data_as(ip), len(ids)))
 
+    def enable_pose_mask_depth_gate(self, front_tolerance=0.02, behind_tolerance=0.0):
+        """Every silhouette the engine draws is compared with the depth of the image its pose was computed on
+        (roft_engine_enable_pose_mask_depth_gate; include/roft_engine.h, section 3e): it loses the pixels where the sensor saw
+        something more than front_tolerance metres nearer than the rendered surface, or (behind_tolerance > 0) more than
+        behind_tolerance farther.  After enable_pose_masks, before the first frame."""
+        gate = L.PoseMaskGate(front_tolerance, behind_tolerance)
+        L.check(L.lib().roft_engine_enable_pose_mask_depth_gate(self._h, C.byref(gate)))
+
+    def pose_mask_gate_stats(self):
+        """dict(gated, emptied, pixels_front, pixels_behind); waits for the batches stepped so far"""
+        st = L.EnginePoseMaskGateStats()
+        L.check(L.lib().roft_engine_get_pose_mask_gate_stats(self._h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in L.EnginePoseMaskGateStats._fields_}
+
     def pose_mask_occlusion_stats(self):
         """silhouettes resolved / of those hidden entirely / pixels removed, since the engine was created (waits for the device)."""
         st = L.EnginePoseMaskOcclusionStats()

@@ -155,6 +155,33 @@ def pose_silhouettes_occluded(cam, meshes, xs, qs, bands=0, vertex_cache=True):
     return masks, counts
 
 
+def pose_silhouettes_gated(cam, meshes, xs, qs, depth, front_tolerance=0.02, behind_tolerance=0.0, bands=0, vertex_cache=True):
+    """pose_silhouettes_occluded followed by the depth gate (roft_pose_silhouettes_gated; the contract: include/roft_engine.h, section
+    3e): a pixel stays unless `depth` [H, W] float32 has a valid reading more than front_tolerance in front of the rendered surface,
+    or (behind_tolerance > 0) more than behind_tolerance behind it.  With one mesh it is pose_silhouette followed by the gate.
+    Returns masks {0, 255} [n, H, W], kept pixel counts [n] and removed [n, 2] = (front, behind)."""
+    L.require_device()
+    n = len(meshes)
+    xs, qs = _f64(np.asarray(xs).reshape(n, 3)), _f64(np.asarray(qs).reshape(n, 4))
+    depth = np.ascontiguousarray(depth, np.float32)
+    if depth.shape != (cam.height, cam.width):
+        raise ValueError("depth is an H x W image of the camera's size")
+    keep, arr = [], (L.Mesh * max(n, 1))()
+    for k, m in enumerate(meshes):
+        verts = np.ascontiguousarray(m[0], np.float32).reshape(-1, 3)
+        tris = np.ascontiguousarray(m[1], np.int32).reshape(-1, 3)
+        keep.append((verts, tris))
+        arr[k] = L.Mesh(verts.ctypes.data, verts.shape[0], tris.ctypes.data, tris.shape[0])
+    masks = np.zeros((n, cam.height, cam.width), np.uint8)
+    counts = np.zeros(n, np.int32)
+    removed = np.zeros((n, 2), np.int32)
+    gate = L.PoseMaskGate(front_tolerance, behind_tolerance)
+    ip = C.POINTER(C.c_int)
+    L.check(L.lib().roft_pose_silhouettes_gated(C.byref(cam), arr, n, _p(xs), _p(qs), _p(depth), C.byref(gate), int(bands), 1 if vertex_cache else 0,
+                                                _p(masks), counts.ctypes.data_as(ip), removed.ctypes.data_as(ip)))
+    return masks, counts, removed
+
+
 def process_noise(psd, sig_w, T):
     Q = np.zeros((9, 9))
     L.check(L.lib().roft_pose_process_noise(_p(_f64(psd)), _p(_f64(sig_w)), T, _p(Q)))

@@ -30,6 +30,13 @@ pose, staggered in depth), three forms of the host leg alternated in one process
 An instrumented pass reads the silhouette stage's device time (roft_debug_pose_mask_kernel_ms: draw + resolve) per delivering batch
 with the mode on and off.  Prints the share of the plain silhouettes' pixels the resolve removed.  Writes
 profiles/r15_pose_mask_occlusion.json.
+
+--depth-gate: what roft_engine_enable_pose_mask_depth_gate costs.  The shared scene's host leg in the shape of the "pose" form above
+(the plain path: every pair drawn alone) and in the overlapping layout of --occlusion with the mode on (the occlusion path: draw +
+resolve), each with the gate on and off, alternated in one process for --runs rounds (5 unless given): object-frames/s, medians, and
+-- from an instrumented pass -- the silhouette stage's device time per delivering batch (roft_debug_pose_mask_kernel_ms).  The gate
+reads the stream's own depth, with the front tolerance 0.02 and the behind test at 0.05.  Writes
+profiles/r17_pose_mask_depth_gate.json.
 """
 import argparse
 import json
@@ -55,7 +62,14 @@ def main():
     p.add_argument("--marks", default=os.path.join(ROOT, "profiles", "r14_marks_timeline.txt"))
     p.add_argument("--out", default=os.path.join(ROOT, "profiles", "r14_pose_masks.json"))
     p.add_argument("--occlusion", action="store_true", help="the three forms of the overlapping shared scene (see above)")
+    p.add_argument("--depth-gate", action="store_true", help="the depth gate on against off, on the plain and the occlusion path (see above)")
     args = p.parse_args()
+    if args.depth_gate:
+        if args.out.endswith("r14_pose_masks.json"):
+            args.out = os.path.join(ROOT, "profiles", "r17_pose_mask_depth_gate.json")
+        if "--runs" not in sys.argv:
+            args.runs = 5
+        return depth_gate(args)
     if args.occlusion:
         if args.out.endswith("r14_pose_masks.json"):
             args.out = os.path.join(ROOT, "profiles", "r15_pose_mask_occlusion.json")
@@ -381,6 +395,107 @@ def occlusion(args):
     print("stage_us", json.dumps(out["stage_us"]))
     if not same:
         raise SystemExit("bench_pose_masks.py --occlusion: the occlusion form and the resolved host masks did not track to identical poses")
+
+
+def depth_gate(args):
+    import torch
+    from roft_amd import _lib as L
+    from roft_amd import engine as E
+    from roft_amd import synth
+
+    L.require_device()
+    dev = torch.device("cuda", 0)
+    cam = synth.Camera.shape_a()
+    if args.scale > 1:
+        cam = cam.scaled(args.scale)
+    n_obj, T = args.objects, max(1, min(args.batch, L.MAX_BATCH_FRAMES))
+    n_run = T + args.frames
+    st = synth.make_stream(4000, n_run, cam, flow_type=synth.FLOW_F32C2, device=dev, mesh_n=12)
+    W, H = cam.width, cam.height
+    verts, tris = st.mesh
+    depth_h = st.depth[:n_run].cpu().pin_memory()
+    flow_h = st.flow[:n_run].cpu().pin_memory()
+    offsets = np.array([[(o % 8 - 3.5) * 0.06, (o // 8 - 3.5) * 0.045, 0.02 * ((o * 37) % 64) / 8.0] for o in range(n_obj)])
+    batches_kt = [(b, min(T, n_run - b)) for b in range(0, n_run, T)]
+
+    def leg(path, gate, timing=False):
+        off = offsets if path == "occlusion" else np.zeros_like(offsets)
+        pose_of = lambda k, o: (st.pose_meas[k, :3] + off[o], st.pose_meas[k, 3:])
+        cfg = E.default_config(W, H, st.flow_type, max_objects=n_obj, max_batch_frames=T)
+        cfg.cam.fx, cfg.cam.fy, cfg.cam.cx, cfg.cam.cy = cam.fx, cam.fy, cam.cx, cam.cy
+        eng = E.ROFTFilterBatch(cfg)
+        for o in range(n_obj):
+            d = E.default_object()
+            x0, q0 = pose_of(0, o)
+            for i in range(13):
+                d.p_mean0[i] = 0.0 if i < 6 else (x0[i - 6] if i < 9 else q0[i - 9])
+            eng.add_object(d, verts, tris)
+        eng.enable_pose_masks()
+        if path == "occlusion":
+            eng.enable_pose_mask_occlusion()
+        if gate:
+            eng.enable_pose_mask_depth_gate(0.02, 0.05)
+        batches = []
+        for b, t in batches_kt:
+            fl = [[dict(depth=depth_h[k].data_ptr(), flow=flow_h[k].data_ptr() if st.flow_valid[k] else None, mask=None,
+                        pose=pose_of(k, o) if st.pose_valid[k] else None, dt=st.dt, mem_kind=L.MEM_HOST) for o in range(n_obj)]
+                  for k in range(b, b + t)]
+            batches.append(eng.build_batch(fl))
+        eng.submit_batch_raw(batches[0][0], batches[0][2])
+        eng.step()
+        eng.sync()
+        if timing:
+            eng.enable_timing(2)
+        stage_us, last_drawn = [], eng.pose_mask_stats()["silhouettes"]
+        s0 = eng.stats()
+        t1 = time.perf_counter()
+        for arr, _keep, t in batches[1:]:
+            eng.submit_batch_raw(arr, t)
+            eng.step()
+            if timing:
+                drawn = eng.pose_mask_stats()["silhouettes"]
+                if drawn != last_drawn:
+                    last_drawn = drawn
+                    stage_us.append(1e3 * eng.pose_mask_kernel_ms())
+        eng.sync()
+        dt = time.perf_counter() - t1
+        s1 = eng.stats()
+        frames = s1["frames"] - s0["frames"]
+        res = dict(value=n_obj * frames / dt, unit="object-frames/s", ms_per_step=1e3 * dt / frames,
+                   launches_per_step=(s1["launches"] - s0["launches"]) / frames, event_ops_per_step=(s1["event_ops"] - s0["event_ops"]) / frames)
+        if timing:
+            res["stage_us"] = dict(median=float(np.median(stage_us)), min=float(np.min(stage_us)), max=float(np.max(stage_us)), n=len(stage_us))
+        res["gate_stats"] = eng.pose_mask_gate_stats()
+        res["silhouettes"] = eng.pose_mask_stats()["silhouettes"]
+        eng.close()
+        return res
+
+    out = dict(config=dict(objects=n_obj, width=W, height=H, batch=T, timed_frames=args.frames, rounds=args.runs, flow="CV_32FC2",
+                           mesh_vertices=int(verts.shape[0]), mesh_triangles=int(tris.shape[0]), front_tolerance=0.02, behind_tolerance=0.05))
+    for path in ("plain", "occlusion"):
+        runs = {True: [], False: []}
+        for _ in range(args.runs):
+            for gate in (True, False):
+                runs[gate].append(leg(path, gate))
+        res = {}
+        for gate, name in ((True, "gate_on"), (False, "gate_off")):
+            rs = sorted(runs[gate], key=lambda r: r["value"])
+            res[name] = dict(rs[len(rs) // 2], runs=[r["value"] for r in runs[gate]])
+        res["ratio_on_over_off"] = res["gate_on"]["value"] / res["gate_off"]["value"]
+        res["same_launches_and_event_ops"] = bool(res["gate_on"]["launches_per_step"] == res["gate_off"]["launches_per_step"]
+                                                  and res["gate_on"]["event_ops_per_step"] == res["gate_off"]["event_ops_per_step"])
+        res["stage_us"] = {name: leg(path, gate, timing=True)["stage_us"] for gate, name in ((True, "gate_on"), (False, "gate_off"))}
+        out[path] = res
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out["config"]))
+    for path in ("plain", "occlusion"):
+        r = out[path]
+        print(path, "on %.0f off %.0f object-frames/s (ratio %.3f); stage us on %s off %s; gate stats %s" %
+              (r["gate_on"]["value"], r["gate_off"]["value"], r["ratio_on_over_off"], json.dumps(r["stage_us"]["gate_on"]),
+               json.dumps(r["stage_us"]["gate_off"]), json.dumps(r["gate_on"]["gate_stats"])))
 
 
 if __name__ == "__main__":

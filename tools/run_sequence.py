@@ -6,6 +6,7 @@ files (`pose_estimate`, `velocity_estimate`, ROFTFilter.cpp:386-394) -- what `te
                   [--pose-set dope] [--out PREFIX] [--compute-flow nvof1|nvof2 | --flow-on-engine nvof1|nvof2] [--no-delay]
                   [--init-pose x y z qw qx qy qz] [--raw-depth SCALE]
                   [--start-at-first-detection] [--score-on-device] [--render-overlay DIR] [--quality FILE] [--masks-from-pose]
+                  [--pose-mask-depth-gate FRONT[,BEHIND]]
                   [--from config_fast_ycb.cfg [--group::key value ...]]
 
 --from reads the filter parameters from one of the reference's configuration files (config/config_fast_ycb.cfg,
@@ -27,7 +28,10 @@ n_both / (n_mask + n_render - n_both), space separated under a header line.  --m
 <pose-set>/poses.txt and NO masks: the object is enrolled with roft_engine_enable_pose_masks and every delivered pose brings the
 silhouette of the mesh at that pose as the frame's mask, drawn on the device (DIR/masks is not read; the first frame uses the
 initial pose when it brings none).  The pose source's delay is the mask's delay then: keep mask_frames_between equal to
-pose_frames_between.
+pose_frames_between.  --pose-mask-depth-gate FRONT[,BEHIND] (with --masks-from-pose) compares every silhouette with the depth of
+the image its pose was computed on (roft_engine_enable_pose_mask_depth_gate): pixels where the sensor saw something more than
+FRONT metres nearer than the mesh -- a hand, clutter -- are left out, and with BEHIND > 0 those where it saw something more than
+BEHIND metres farther; the report carries the gate's counts.
 """
 import argparse
 import json
@@ -69,6 +73,8 @@ def main(argv=None):
                     help="score every estimate against its frame's mask and depth on the device; one row per frame into FILE")
     ap.add_argument("--masks-from-pose", action="store_true",
                     help="no segmentation masks: the engine draws the silhouette of every delivered pose on the device and tracks with it")
+    ap.add_argument("--pose-mask-depth-gate", default=None, metavar="FRONT[,BEHIND]",
+                    help="with --masks-from-pose: gate the silhouettes against the depth of the pose's own frame (tolerances in metres; BEHIND 0: off)")
     ap.add_argument("--from", dest="cfg_file", default=None, help="ROFT configuration file (libconfig), overrides as --a::b::c value")
     args, overrides = ap.parse_known_args(argv)
 
@@ -78,6 +84,17 @@ def main(argv=None):
 
     if args.compute_flow and args.flow_on_engine:
         ap.error("--compute-flow and --flow-on-engine exclude each other")
+    gate = None
+    if args.pose_mask_depth_gate is not None:
+        if not args.masks_from_pose:
+            ap.error("--pose-mask-depth-gate needs --masks-from-pose")
+        try:
+            gate = [float(v) for v in args.pose_mask_depth_gate.split(",")]
+        except ValueError:
+            gate = []
+        if len(gate) not in (1, 2):
+            ap.error("--pose-mask-depth-gate takes FRONT or FRONT,BEHIND (metres)")
+        gate = (gate + [0.0])[:2]
     L.require_device()
     cam = json.load(open(os.path.join(args.root, "cam_K.json")))
     W, H = int(cam["width"]), int(cam["height"])
@@ -160,6 +177,8 @@ def main(argv=None):
             sys.stderr.write("note: mask_frames_between %d != pose_frames_between %d: a silhouette is as old as its pose\n" %
                              (cfg.mask_frames_between, cfg.pose_frames_between))
         eng.enable_pose_masks([0])
+        if gate:
+            eng.enable_pose_mask_depth_gate(gate[0], gate[1])
     for k in range(start, len(seq)):
         frame = seq.frame(k, with_image=bool(args.flow_on_engine), depth_raw=args.raw_depth is not None)
         if args.masks_from_pose:
@@ -183,6 +202,7 @@ def main(argv=None):
                 f.write("%d %d %d %d %d %d %d %.17g %.6f\n" % (start + r["frame"], r["n_mask"], r["n_render"], r["n_both"], r["n_depth"],
                                                               r["n_front"], r["n_behind"], r["depth_err"], o))
     pose_mask_stats = eng.pose_mask_stats() if args.masks_from_pose else None
+    gate_stats = dict(eng.pose_mask_gate_stats(), front_tolerance=gate[0], behind_tolerance=gate[1]) if gate else None
     eng.close()
     prefix = args.out if args.out is not None else os.path.join(args.root, "roft_mi355x_")
     io.write_estimate_logs(prefix, pose[:, 0], twist[:, 0])
@@ -212,6 +232,8 @@ def main(argv=None):
         report["quality"] = args.quality
     if args.masks_from_pose:
         report["pose_masks"] = pose_mask_stats
+    if gate_stats:
+        report["pose_mask_gate"] = gate_stats
     print(json.dumps(report))
     return 0
 
