@@ -610,26 +610,12 @@ int roft_engine_get_stats(roft_engine* e, roft_engine_stats* out)
 
 // ---- one object from its description: shared by roft_object_add and roft_objects_restart -------------------------------------------
 
-// does the engine draw object `id`'s silhouette for missing masks (roft_engine_enable_pose_masks)?  `has_mesh`: of the mesh it has, or is about to get
-static bool pose_mask_enrolled(const roft_engine* e, int id, bool has_mesh)
-{
-    const EnginePoseMasks& pm = e->pose_masks;
-    return pm.enabled && ((id < (int)e->objs.size() && e->objs[id]->pose_masks) || (pm.all && has_mesh));
-}
-
 // Every check on a description, on the host (no device is looked for).  keep_mesh: d.mesh is not looked at.  enrolled: the object is
 // enrolled for pose masks by id, so a description without a mesh is refused.
 static int check_object_desc(const roft_config& cfg, const roft_object_desc& d, bool keep_mesh, bool enrolled)
 {
     if (keep_mesh) return ROFT_OK;
-    if (d.mesh.n_verts > 0 && d.mesh.n_tris > 0) {
-        if (!d.mesh.verts || !d.mesh.tris) return fail(ROFT_ERR_INVALID, "mesh: null vertex or triangle array");
-        for (size_t i = 0; i < (size_t)3 * d.mesh.n_tris; ++i)   // (the rasteriser indexes the vertex array with these)
-            if (d.mesh.tris[i] < 0 || d.mesh.tris[i] >= d.mesh.n_verts)
-                return fail(ROFT_ERR_INVALID, "mesh: triangle " + std::to_string(i / 3) + " refers to vertex " + std::to_string(d.mesh.tris[i]) +
-                                                  " of " + std::to_string(d.mesh.n_verts));
-        return ROFT_OK;
-    }
+    if (has_mesh(d.mesh)) return check_mesh(d.mesh, "mesh", true);
     if (cfg.outlier_rejection && cfg.use_pose) return fail(ROFT_ERR_INVALID, "outlier rejection needs a mesh");
     if (enrolled) return fail(ROFT_ERR_INVALID, "the object is enrolled for pose masks: its description needs a mesh");
     return ROFT_OK;
@@ -637,12 +623,13 @@ static int check_object_desc(const roft_config& cfg, const roft_object_desc& d, 
 
 // Parameter block, mesh preparation and upload, ObjState from the description, pose0 -> object `id` (its HostObject `o`), on stream s;
 // `st` is the host copy the upload reads: the caller keeps it until the stream has been synchronised.  The description has passed
-// check_object_desc.  keep_mesh: the resident mesh stays.  *mesh_uploaded: a mesh went up.
+// check_object_desc.  keep_mesh: the resident mesh stays.  *mesh_uploaded: a mesh went up.  The new mesh goes up next to the resident
+// one and takes its place only when every step has succeeded: a failed call leaves the object, its parameters and its mesh as they
+// were.  (Nothing on the device reads the mesh that is released: the object is new, or roft_objects_restart has run roft_sync.)
 static int apply_object_desc(roft_engine* e, int id, HostObject* o, const roft_object_desc* d, bool keep_mesh, ObjState* st, hipStream_t s,
                              bool* mesh_uploaded)
 {
-    ObjParams& p = e->h_params[id];
-    const ObjParams old = p;
+    ObjParams p;
     std::memset(&p, 0, sizeof(p));
     for (int i = 0; i < 3; ++i) {
         p.sigma_ang_vel[i] = d->p_sigma_ang_vel[i];
@@ -653,29 +640,11 @@ static int apply_object_desc(roft_engine* e, int id, HostObject* o, const roft_o
     for (int i = 0; i < 6; ++i) p.v_q[i] = d->v_q_diag[i];
     p.r_flow[0] = d->v_meas_cov_flow[0];
     p.r_flow[1] = d->v_meas_cov_flow[1];
-    *mesh_uploaded = false;
-    if (keep_mesh) {
-        p.verts = old.verts; p.tris = old.tris; p.tri_flip = old.tri_flip;
-        p.n_verts = old.n_verts; p.n_tris = old.n_tris;
-    } else if (d->mesh.n_verts > 0 && d->mesh.n_tris > 0) {
-        // closed orientable surface?  Then the outlier test's render leaves the triangles that face away out (the render
-        // contract, oracle/ro_render.c) and walks the triangles in an order that keeps alike-facing ones together.  The GL render
-        // mode draws every triangle and breaks depth ties on the caller's triangle order: the mesh goes up as it is.
-        PreparedMesh pm;
-        if (e->cfg.render_mode == ROFT_RENDER_CONTRACT) prepare_mesh(d->mesh.verts, d->mesh.n_verts, d->mesh.tris, d->mesh.n_tris, pm);
-        hipError_t err = o->verts.ensure((size_t)3 * d->mesh.n_verts);
-        if (err == hipSuccess) err = o->tris.ensure((size_t)3 * d->mesh.n_tris);
-        if (err == hipSuccess && pm.closed) err = o->tri_flip.ensure((size_t)d->mesh.n_tris);
-        // (synchronous copies: the prepared triangle order and flip bits live in `pm`)
-        if (err == hipSuccess) err = hipMemcpy(o->verts.p, d->mesh.verts, sizeof(float) * 3 * d->mesh.n_verts, hipMemcpyHostToDevice);
-        if (err == hipSuccess) err = hipMemcpy(o->tris.p, pm.tris(d->mesh.tris), sizeof(int32_t) * 3 * d->mesh.n_tris, hipMemcpyHostToDevice);
-        if (err == hipSuccess && pm.closed) err = hipMemcpy(o->tri_flip.p, pm.flip.data(), (size_t)d->mesh.n_tris, hipMemcpyHostToDevice);
-        if (err != hipSuccess) { p = old; return fail(ROFT_ERR_DEVICE, std::string("mesh upload: ") + hipGetErrorString(err)); }
-        p.verts = o->verts.p; p.tris = o->tris.p;
-        p.tri_flip = pm.closed ? o->tri_flip.p : nullptr;
-        p.n_verts = d->mesh.n_verts; p.n_tris = d->mesh.n_tris;
-        *mesh_uploaded = true;
-    }
+    // The contract render leaves the triangles of a closed mesh that face away out (oracle/ro_render.c) and walks alike-facing ones
+    // together; the GL render mode draws every triangle and breaks depth ties on the caller's order: the mesh goes up as it is.
+    DeviceMesh fresh;
+    if (!keep_mesh) TRY(fresh.upload(d->mesh, e->cfg.render_mode == ROFT_RENDER_CONTRACT ? MeshLayout::kWalkOrder : MeshLayout::kAsItIs, s));
+    (keep_mesh ? o->mesh : fresh).describe(p);
     // initialization_step (ROFTFilter.cpp:216-237)
     init_state(*st);
     for (int i = 0; i < 6; ++i) { st->v_mean[i] = d->v_mean0[i]; st->v_cov[i * 6 + i] = d->v_cov0_diag[i]; }
@@ -685,9 +654,14 @@ static int apply_object_desc(roft_engine* e, int id, HostObject* o, const roft_o
     st->belief[B_LIN0] = b;       // p_corr_belief_
     st->belief[B_LIN1] = b;       // buffered_belief_ = p_corr_belief_ at initialization (ROFTFilter.cpp:231)
     st->belief[B_PRED] = st->belief[B_PRED + 1] = b;
-    hipError_t err = hipMemcpyAsync(e->arr.params.p + id, &p, sizeof(p), hipMemcpyHostToDevice, s);
+    ObjParams& live = e->h_params[id];   // (what the copy reads until the caller has synchronised s)
+    const ObjParams old = live;
+    live = p;
+    hipError_t err = hipMemcpyAsync(e->arr.params.p + id, &live, sizeof(live), hipMemcpyHostToDevice, s);
     if (err == hipSuccess) err = hipMemcpyAsync(e->arr.state.p + id, st, sizeof(ObjState), hipMemcpyHostToDevice, s);
-    if (err != hipSuccess) return fail(ROFT_ERR_DEVICE, std::string("state upload: ") + hipGetErrorString(err));
+    if (err != hipSuccess) { live = old; return fail(ROFT_ERR_DEVICE, std::string("state upload: ") + hipGetErrorString(err)); }
+    if (!keep_mesh) o->mesh = std::move(fresh);
+    *mesh_uploaded = !keep_mesh && has_mesh(o->mesh);
     for (int i = 0; i < 7; ++i) o->pose0[i] = d->p_mean0[6 + i];
     return ROFT_OK;
 }
@@ -764,7 +738,7 @@ int roft_objects_restart(roft_engine* e, const int* obj_ids, const roft_object_d
     {
         std::vector<int> has_mesh((size_t)n_obj), enrolled((size_t)n_obj);
         for (int id = 0; id < n_obj; ++id) {
-            has_mesh[id] = e->h_params[id].n_verts > 0 && e->h_params[id].n_tris > 0;
+            has_mesh[id] = roft::has_mesh(e->h_params[id]);
             enrolled[id] = e->objs[id]->pose_masks;
         }
         TRY(check_restart_args(e->cfg, n_obj, has_mesh.data(), enrolled.data(), e->pose_masks.enabled, e->pose_masks.all, obj_ids, descs, n, flags));

@@ -12,6 +12,8 @@
 //   engine_ops.hip      the operator-level entry points (one-object context: roft_flow_measurement ... roft_outlier_test, roft_pose_errors)
 //   engine_quality.hip  track quality: roft_engine_enable_quality / _get_quality, roft_track_quality, the batch's quality launch
 //   engine_debug.hip    roft_debug_* (diagnostics and experiments)
+//   scene.hip           the scene renderer: roft_scene_renderer_*, roft_render_scene
+//   mesh_class.h        a caller's mesh on the host: has_mesh, the array check, classification, the three upload layouts (host-only C++)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -23,7 +25,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <deque>
 #include <map>
 #include <mutex>
 #include <string>
@@ -31,6 +32,7 @@
 
 #include "roft_device.h"
 #include "mesh_class.h"
+#include "scene.h"
 #include "batch_plan.h"
 #include "pose_mask_gate.h"
 #include "opticalflow.h"
@@ -59,6 +61,10 @@ template <class T>
 struct DevBuf {
     T* p = nullptr;
     size_t n = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept { swap(o); }   // (move-only: one owner frees the memory; what `this` held goes with `o`)
+    DevBuf& operator=(DevBuf&& o) noexcept { swap(o); return *this; }
+    void swap(DevBuf& o) { std::swap(p, o.p); std::swap(n, o.n); }
     ~DevBuf() { release(); }
     void release()
     {
@@ -75,6 +81,69 @@ struct DevBuf {
         n = count;
         if (zero) e = hipMemset(p, 0, std::max<size_t>(count, 1) * sizeof(T));
         return e;
+    }
+};
+
+// The one refusal (ROFT_ERR_INVALID, before any device is looked for) of a caller's mesh at every site that draws one; `what` names it
+// in the text ("mesh 3").  The site's policy: may the mesh be absent; tri_index_bits > 0: n_tris must stay below 2^bits.
+inline int check_mesh(const roft_mesh& m, const std::string& what, bool may_be_absent, int tri_index_bits = 0)
+{
+    if (!has_mesh(m)) return may_be_absent ? ROFT_OK : fail(ROFT_ERR_INVALID, what + ": no vertices or no triangles");
+    if (tri_index_bits > 0 && m.n_tris >= (1 << tri_index_bits))
+        return fail(ROFT_ERR_INVALID, what + ": 2^" + std::to_string(tri_index_bits) + " triangles or more (a triangle's index is kept in that many bits)");
+    const MeshFault f = check_mesh_arrays(m.verts, m.n_verts, m.tris, m.n_tris);
+    if (f.kind == MeshFault::kNullArray) return fail(ROFT_ERR_INVALID, what + ": null vertex or triangle array");
+    if (f.kind == MeshFault::kBadIndex)
+        return fail(ROFT_ERR_INVALID, what + ": triangle " + std::to_string(f.triangle) + " refers to vertex " + std::to_string(f.vertex) + " of " +
+                                          std::to_string(m.n_verts));
+    return ROFT_OK;
+}
+
+// ... and the one resident copy.  "No mesh" until a mesh that has_mesh has gone up; the buffers grow on demand and are kept, so a
+// context uploads one mesh after the other into the same DeviceMesh.
+struct DeviceMesh {
+    DevBuf<float> verts;
+    DevBuf<int32_t> tris;
+    DevBuf<uint8_t> flip;
+    int n_verts = 0, n_tris = 0;
+    bool closed = false;   // the current upload was of a closed mesh in a layout with flip bits: `flip` holds them
+
+    // `m` (which has passed check_mesh) in `layout` (mesh_class.h), copied on stream s.  Returns only when the copies have read
+    // their host arrays: the prepared triangle order and flip bits live in this call.  An absent mesh, or a failed upload, leaves
+    // "no mesh"; an absent mesh makes no device call.
+    int upload(const roft_mesh& m, MeshLayout layout, hipStream_t s)
+    {
+        n_verts = n_tris = 0;
+        closed = false;
+        if (!has_mesh(m)) return ROFT_OK;
+        PreparedMesh pm;
+        prepare_mesh(m.verts, m.n_verts, m.tris, m.n_tris, layout, pm);
+        HIP_TRY(verts.ensure((size_t)3 * m.n_verts));
+        HIP_TRY(tris.ensure((size_t)3 * m.n_tris));
+        HIP_TRY(hipMemcpyAsync(verts.p, m.verts, sizeof(float) * 3 * m.n_verts, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(tris.p, pm.tris(m.tris), sizeof(int32_t) * 3 * m.n_tris, hipMemcpyHostToDevice, s));
+        if (pm.closed) {
+            HIP_TRY(flip.ensure((size_t)m.n_tris));
+            HIP_TRY(hipMemcpyAsync(flip.p, pm.flip.data(), (size_t)m.n_tris, hipMemcpyHostToDevice, s));
+        }
+        HIP_TRY(hipStreamSynchronize(s));
+        n_verts = m.n_verts;
+        n_tris = m.n_tris;
+        closed = pm.closed;
+        return ROFT_OK;
+    }
+
+    // what a kernel is given: null pointers without a mesh, and no flip bits unless THIS upload made them
+    SceneMesh scene_mesh() const
+    {
+        const bool has = has_mesh(*this);
+        return SceneMesh{has ? verts.p : nullptr, has ? tris.p : nullptr, closed ? flip.p : nullptr, n_verts, n_tris};
+    }
+    void describe(ObjParams& p) const   // (the five mesh fields of an object's parameter block)
+    {
+        const SceneMesh m = scene_mesh();
+        p.verts = m.verts; p.tris = m.tris; p.tri_flip = m.flip;
+        p.n_verts = m.n_verts; p.n_tris = m.n_tris;
     }
 };
 
@@ -288,9 +357,7 @@ struct HostObject {
     const void* stepped_flow = nullptr;       // the flow produced for the last stepped frame (roft_engine_get_flow), or null
     const float* stepped_depth = nullptr;     // the depth of the last stepped frame (roft_engine_get_depth reads it on a raw-depth engine)
     std::vector<OwnedFlow*> owned;   // engine copies of flows that outlived the zero-copy retention window
-    DevBuf<float> verts;
-    DevBuf<int32_t> tris;
-    DevBuf<uint8_t> tri_flip;   // closed meshes only (mesh_class.h)
+    DeviceMesh mesh;   // what ObjParams of the object names (absent: the object was described without one)
     // masks from poses (roft_engine_enable_pose_masks): the object is enrolled; the pose of roft_object_desc::p_mean0 (x, q = w x y z),
     // which stands in for a first frame that brings none
     bool pose_masks = false;

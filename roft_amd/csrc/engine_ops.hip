@@ -12,7 +12,8 @@ struct OpCtx {
     hipStream_t stream = nullptr;
     Arrays arr;
     int W = 0, H = 0, ftype = 0, fgrid = 0, radius = 0;
-    DevBuf<unsigned char> b0, b1, b2, b3, b4, b5, bflip;  // generic scratch
+    DevBuf<unsigned char> b0, b1, b2, b3, b4, b5;  // generic scratch
+    DeviceMesh mesh;                               // the mesh of the last outlier test / depth render
     bool ready = false;
 
     int prepare(const roft_camera& cam, int ftype_, int fgrid_, float fscale, int radius_)
@@ -397,14 +398,7 @@ static int pose_silhouettes(const char* what, const roft_camera* cam, const roft
     if (n < 1 || n > ROFT_SCENE_MAX_INSTANCES) return fail(ROFT_ERR_INVALID, std::string(what) + ": n must be 1 .. ROFT_SCENE_MAX_INSTANCES");
     if (bands < 0) return fail(ROFT_ERR_INVALID, "bands must be >= 0 (0: the library's choice)");
     if (vertex_cache != 0 && vertex_cache != 1) return fail(ROFT_ERR_INVALID, "vertex_cache must be 0 or 1");
-    auto has_mesh = [&](int k) { return meshes[k].n_verts > 0 && meshes[k].n_tris > 0; };
-    for (int k = 0; k < n; ++k) {
-        if (!has_mesh(k)) continue;
-        const roft_mesh& m = meshes[k];
-        if (!m.verts || !m.tris) return fail(ROFT_ERR_INVALID, "mesh: null vertex or triangle array");
-        for (size_t i = 0; i < (size_t)3 * m.n_tris; ++i)
-            if (m.tris[i] < 0 || m.tris[i] >= m.n_verts) return fail(ROFT_ERR_INVALID, "mesh: a triangle refers to a vertex outside the vertex array");
-    }
+    for (int k = 0; k < n; ++k) TRY(check_mesh(meshes[k], n > 1 ? "mesh " + std::to_string(k) : "mesh", true));
     if (roft_device_count() <= 0) return fail(ROFT_ERR_DEVICE, "no HIP device (libroft_hip has no CPU path)");
     if (int rc = check_geometry(cam->width, cam->height)) return rc;
     OpCtx& c = op();
@@ -414,7 +408,7 @@ static int pose_silhouettes(const char* what, const roft_camera* cam, const roft
     if (!c.stream) HIP_TRY(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
     const DevCamera dc = make_cam(*cam);
     const size_t npix = (size_t)cam->width * cam->height, plane_words = (size_t)dc.wpr * dc.H;
-    std::vector<DevBuf<unsigned char>> d_verts((size_t)n), d_tris((size_t)n), d_flip((size_t)n);
+    std::vector<DeviceMesh> d_meshes((size_t)n);
     DevBuf<unsigned char> d_mask;
     DevBuf<uint32_t> d_planes;
     DevBuf<MaskRec> d_rec;
@@ -431,22 +425,9 @@ static int pose_silhouettes(const char* what, const roft_camera* cam, const roft
     std::memset(prm.data(), 0, sizeof(ObjParams) * prm.size());
     int max_verts = 0;
     for (int k = 0; k < n; ++k) {
-        if (has_mesh(k)) {
-            const roft_mesh& m = meshes[k];
-            PreparedMesh pm;
-            prepare_mesh(m.verts, m.n_verts, m.tris, m.n_tris, pm);
-            if (int rc = to_dev(d_verts[k], m.verts, (size_t)3 * m.n_verts, c.stream)) return rc;
-            if (int rc = to_dev(d_tris[k], pm.tris(m.tris), (size_t)3 * m.n_tris, c.stream)) return rc;
-            if (pm.closed)
-                if (int rc = to_dev(d_flip[k], pm.flip.data(), (size_t)m.n_tris, c.stream)) return rc;
-            HIP_TRY(hipStreamSynchronize(c.stream));   // (pm lives in this iteration)
-            prm[k].verts = reinterpret_cast<const float*>(d_verts[k].p);
-            prm[k].tris = reinterpret_cast<const int32_t*>(d_tris[k].p);
-            prm[k].tri_flip = pm.closed ? reinterpret_cast<const uint8_t*>(d_flip[k].p) : nullptr;
-            prm[k].n_verts = m.n_verts;
-            prm[k].n_tris = m.n_tris;
-            max_verts = std::max(max_verts, m.n_verts);
-        }
+        TRY(d_meshes[k].upload(meshes[k], MeshLayout::kWalkOrder, c.stream));
+        d_meshes[k].describe(prm[k]);
+        max_verts = std::max(max_verts, d_meshes[k].n_verts);
         clear_ctrl(fc[k]);
         fc[k].has_new_mask = 1;
         fc[k].label_type = kMaskFromPose;
@@ -643,6 +624,7 @@ static int op_outlier(const roft_camera* cam, int divider, const float* depth, c
                       const double* x2 /*2x3*/, const double* q2 /*2x4*/, const OutlierLaunchOpts& o_in, double L_out[2],
                       long samples_out[2], int* selected_out, float* tiles_out)
 {
+    TRY(check_mesh(*mesh, "mesh", false));
     OpCtx& c = op();
     std::lock_guard<std::mutex> lk(c.mu);
     if (int rc = c.prepare(*cam, ROFT_FLOW_F32C2, 1, 1.0f, 35)) return rc;
@@ -658,21 +640,11 @@ static int op_outlier(const roft_camera* cam, int divider, const float* depth, c
         a.tile_h = cam->height / a.cam.divider;
         a.max_verts = a.max_tris = 0;
     };
-    for (size_t i = 0; i < (size_t)3 * mesh->n_tris; ++i)
-        if (mesh->tris[i] < 0 || mesh->tris[i] >= mesh->n_verts) return fail(ROFT_ERR_INVALID, "mesh: a triangle refers to a vertex outside the vertex array");
-    PreparedMesh pm;   // (GL render mode: the caller's triangles as they are, every one drawn -- roft_object_add does the same)
-    if (o_in.render_mode == ROFT_RENDER_CONTRACT) prepare_mesh(mesh->verts, mesh->n_verts, mesh->tris, mesh->n_tris, pm);
-    if (int rc = to_dev(c.b0, mesh->verts, (size_t)3 * mesh->n_verts, c.stream)) return rc;
-    if (int rc = to_dev(c.b1, pm.tris(mesh->tris), (size_t)3 * mesh->n_tris, c.stream)) return rc;
-    if (pm.closed)
-        if (int rc = to_dev(c.bflip, pm.flip.data(), (size_t)mesh->n_tris, c.stream)) return rc;
+    // (GL render mode: the caller's triangles as they are, every one drawn -- roft_object_add does the same)
+    TRY(c.mesh.upload(*mesh, o_in.render_mode == ROFT_RENDER_CONTRACT ? MeshLayout::kWalkOrder : MeshLayout::kAsItIs, c.stream));
     ObjParams prm;
     std::memset(&prm, 0, sizeof(prm));
-    prm.verts = reinterpret_cast<const float*>(c.b0.p);
-    prm.tris = reinterpret_cast<const int32_t*>(c.b1.p);
-    prm.tri_flip = pm.closed ? reinterpret_cast<const uint8_t*>(c.bflip.p) : nullptr;
-    prm.n_verts = mesh->n_verts;
-    prm.n_tris = mesh->n_tris;
+    c.mesh.describe(prm);
     a.max_verts = mesh->n_verts;
     a.max_tris = mesh->n_tris;
     FrameCtrl fc;
@@ -740,7 +712,7 @@ static int op_outlier(const roft_camera* cam, int divider, const float* depth, c
 
 int roft_mesh_classify(const roft_mesh* mesh, uint8_t* flip_out, int* closed_out)
 {
-    if (!mesh || !mesh->verts || !mesh->tris || mesh->n_verts <= 0 || mesh->n_tris <= 0 || !closed_out) return fail(ROFT_ERR_INVALID, "bad argument");
+    if (!mesh || !mesh->verts || !mesh->tris || !has_mesh(*mesh) || !closed_out) return fail(ROFT_ERR_INVALID, "bad argument");
     std::vector<uint8_t> flip;
     *closed_out = classify_mesh(mesh->verts, mesh->n_verts, mesh->tris, mesh->n_tris, flip) ? 1 : 0;
     if (flip_out) std::memcpy(flip_out, flip.data(), (size_t)mesh->n_tris);
@@ -756,8 +728,7 @@ int roft_render_depth(const roft_mesh* mesh, const double x[3], const double q[4
 int roft_render_depth_mode(const roft_mesh* mesh, const double x[3], const double q[4], const roft_camera* cam, int divider, int mode,
                            float* tile)
 {
-    if (!mesh || !mesh->verts || !mesh->tris || mesh->n_verts <= 0 || mesh->n_tris <= 0 || !x || !q || !cam || !tile || divider <= 0)
-        return fail(ROFT_ERR_INVALID, "bad argument");
+    if (!mesh || !x || !q || !cam || !tile || divider <= 0) return fail(ROFT_ERR_INVALID, "bad argument");
     if (mode != ROFT_RENDER_CONTRACT && mode != ROFT_RENDER_GL) return fail(ROFT_ERR_INVALID, "bad render mode");
     const size_t tpix = (size_t)(cam->width / divider) * (cam->height / divider);
     std::vector<float> tiles(2 * tpix);
@@ -774,9 +745,6 @@ int roft_outlier_test(const roft_camera* cam, int divider, const float* depth, c
                       const double x[6], const double q[8], int bands, int vertex_cache, int window_pixels, double L_out[2],
                       long samples_out[2], int* selected_out, float* tiles_out)
 {
-    if (!cam || !depth || !mask || !mesh || !mesh->verts || !mesh->tris || mesh->n_verts <= 0 || mesh->n_tris <= 0 || !x || !q ||
-        divider <= 0 || bands < 0 || bands > kMaxOutlierParts || window_pixels < 0)
-        return fail(ROFT_ERR_INVALID, "bad argument");
     return roft_outlier_test_split(cam, divider, depth, mask, mesh, x, q, bands, vertex_cache, window_pixels, -1, L_out, samples_out, selected_out, tiles_out);
 }
 
@@ -792,8 +760,7 @@ int roft_outlier_test_mode(const roft_camera* cam, int divider, const float* dep
                            const double x[6], const double q[8], int bands, int vertex_cache, int window_pixels, int split, int mode,
                            double L_out[2], long samples_out[2], int* selected_out, float* tiles_out)
 {
-    if (!cam || !depth || !mask || !mesh || !mesh->verts || !mesh->tris || mesh->n_verts <= 0 || mesh->n_tris <= 0 || !x || !q ||
-        divider <= 0 || bands < 0 || bands > kMaxOutlierParts || window_pixels < 0)
+    if (!cam || !depth || !mask || !mesh || !x || !q || divider <= 0 || bands < 0 || bands > kMaxOutlierParts || window_pixels < 0)
         return fail(ROFT_ERR_INVALID, "bad argument");
     if (mode != ROFT_RENDER_CONTRACT && mode != ROFT_RENDER_GL) return fail(ROFT_ERR_INVALID, "bad render mode");
     OutlierLaunchOpts o;

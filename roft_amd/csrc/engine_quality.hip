@@ -128,7 +128,9 @@ struct QualityOp {
     Arrays arr;
     int W = 0, H = 0;
     bool ready = false;
-    DevBuf<unsigned char> verts, tris, flip, mask, depth;
+    DeviceMesh mesh;
+    DevBuf<unsigned char> mask;
+    DevBuf<float> depth;
     DevBuf<QualityRaw> rec;
 };
 
@@ -148,11 +150,7 @@ extern "C" int roft_track_quality(const roft_camera* cam, int divider, const flo
     if (divider <= 0) return fail(ROFT_ERR_INVALID, "divider must be > 0");
     if (!(depth_tolerance >= 0.0f)) return fail(ROFT_ERR_INVALID, "depth_tolerance must be >= 0");
     if (window_pixels < 0) return fail(ROFT_ERR_INVALID, "window_pixels must be >= 0");
-    const bool has_mesh = mesh->n_verts > 0 && mesh->n_tris > 0;
-    if (has_mesh && (!mesh->verts || !mesh->tris)) return fail(ROFT_ERR_INVALID, "mesh: null vertex or triangle array");
-    if (has_mesh)
-        for (size_t i = 0; i < (size_t)3 * mesh->n_tris; ++i)
-            if (mesh->tris[i] < 0 || mesh->tris[i] >= mesh->n_verts) return fail(ROFT_ERR_INVALID, "mesh: a triangle refers to a vertex outside the vertex array");
+    TRY(check_mesh(*mesh, "mesh", true));   // (no mesh: nothing is rendered, the record counts the mask alone)
     if (roft_device_count() <= 0) return fail(ROFT_ERR_DEVICE, "no HIP device (libroft_hip has no CPU path)");
     if (int rc = check_geometry(cam->width, cam->height)) return rc;
     if (cam->width / divider <= 0 || cam->height / divider <= 0) return fail(ROFT_ERR_INVALID, "divider larger than the image");
@@ -180,32 +178,17 @@ extern "C" int roft_track_quality(const roft_camera* cam, int divider, const flo
     a.T = 1;
     a.out_log = c.arr.log.p;
     a.log_cap = 1;
-    a.max_verts = has_mesh ? mesh->n_verts : 0;
-    a.max_tris = has_mesh ? mesh->n_tris : 0;
+    a.max_verts = has_mesh(*mesh) ? mesh->n_verts : 0;
+    a.max_tris = has_mesh(*mesh) ? mesh->n_tris : 0;
     if (!quality_fits(a)) return fail(ROFT_ERR_INVALID, "track quality: the render target is too wide for the kernel's depth window");
     const size_t npix = (size_t)cam->width * cam->height;
     hipStream_t s = c.stream;
     ObjParams prm;
     std::memset(&prm, 0, sizeof(prm));
-    PreparedMesh pm;
-    if (has_mesh) {
-        prepare_mesh(mesh->verts, mesh->n_verts, mesh->tris, mesh->n_tris, pm);
-        HIP_TRY(c.verts.ensure(sizeof(float) * 3 * mesh->n_verts));
-        HIP_TRY(c.tris.ensure(sizeof(int32_t) * 3 * mesh->n_tris));
-        HIP_TRY(hipMemcpyAsync(c.verts.p, mesh->verts, sizeof(float) * 3 * mesh->n_verts, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(c.tris.p, pm.tris(mesh->tris), sizeof(int32_t) * 3 * mesh->n_tris, hipMemcpyHostToDevice, s));
-        if (pm.closed) {
-            HIP_TRY(c.flip.ensure((size_t)mesh->n_tris));
-            HIP_TRY(hipMemcpyAsync(c.flip.p, pm.flip.data(), (size_t)mesh->n_tris, hipMemcpyHostToDevice, s));
-        }
-        prm.verts = reinterpret_cast<const float*>(c.verts.p);
-        prm.tris = reinterpret_cast<const int32_t*>(c.tris.p);
-        prm.tri_flip = pm.closed ? reinterpret_cast<const uint8_t*>(c.flip.p) : nullptr;
-        prm.n_verts = mesh->n_verts;
-        prm.n_tris = mesh->n_tris;
-    }
+    TRY(c.mesh.upload(*mesh, MeshLayout::kWalkOrder, s));
+    c.mesh.describe(prm);
     HIP_TRY(c.mask.ensure(npix));
-    HIP_TRY(c.depth.ensure(npix * sizeof(float)));
+    HIP_TRY(c.depth.ensure(npix));
     HIP_TRY(hipMemcpyAsync(c.mask.p, mask, npix, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(c.depth.p, depth, npix * sizeof(float), hipMemcpyHostToDevice, s));
     FrameCtrl fc;
@@ -213,7 +196,7 @@ extern "C" int roft_track_quality(const roft_camera* cam, int divider, const flo
     fc.has_new_mask = 1;
     fc.new_mask = c.mask.p;
     fc.slot_cur = kSlotNew;   // (the ingest leaves the planes of the delivered mask in the slot the kernel is told to read)
-    fc.depth_cur = reinterpret_cast<const float*>(c.depth.p);
+    fc.depth_cur = c.depth.p;
     fc.frame_idx = 0;
     roft_object_output row;
     std::memset(&row, 0, sizeof(row));

@@ -104,7 +104,7 @@ int roft_engine_score_log(roft_engine* e, int kind, int obj_id, int first_frame,
     if (!e->arr.a.out_log) return fail(ROFT_ERR_INVALID, "log not enabled");
     if (n_frames < 0 || first_frame < 0) return fail(ROFT_ERR_INVALID, "bad frame range");
     const int n_verts = e->h_params[obj_id].n_verts;
-    if (!points && n_verts <= 0) return fail(ROFT_ERR_INVALID, "the object was added without a mesh: pass points");
+    if (!points && !has_mesh(e->h_params[obj_id])) return fail(ROFT_ERR_INVALID, "the object was added without a mesh: pass points");
     HIP_TRY(hipSetDevice(e->cfg.device));
     if (int rc = roft_sync(e)) return rc;
     const int cap = e->arr.a.log_cap, stepped = e->frame_counter;

@@ -499,7 +499,7 @@ static int schedule_mask_source(roft_engine* e, const FrameJob& j, const ImageSi
     // the silhouette of the delivered pose -- on the first frame of its track (Sched::track_frames), without one, of the pose it was
     // added or restarted with
     const EnginePoseMasks& pm = e->pose_masks;
-    const bool enrolled = pm.enabled && (ho.pose_masks || (pm.all && e->h_params[j.id].n_verts > 0 && e->h_params[j.id].n_tris > 0));
+    const bool enrolled = pm.enabled && (ho.pose_masks || (pm.all && has_mesh(e->h_params[j.id])));
     const bool from_pose = enrolled && !d.mask && !d.labels && (j.in.pose_valid || o.track_frames == 0);
     const bool has_mask = d.mask || d.labels || from_pose;
     c.has_new_mask = has_mask ? 1 : 0;
@@ -888,7 +888,7 @@ int roft_engine_enable_pose_masks(roft_engine* e, const int* obj_ids, int n_ids)
     for (int i = 0; i < n_ids; ++i) {
         const int id = obj_ids[i];
         if (id < 0 || id >= (int)e->objs.size()) return fail(ROFT_ERR_INVALID, "pose masks: " + std::to_string(id) + " is not an object of the engine");
-        if (e->h_params[id].n_verts <= 0 || e->h_params[id].n_tris <= 0)
+        if (!has_mesh(e->h_params[id]))
             return fail(ROFT_ERR_INVALID, "pose masks: object " + std::to_string(id) + " was added without a mesh");
     }
     if (e->cfg.cam.width / 32 > kSilhouetteWindowWords) return fail(ROFT_ERR_INVALID, "pose masks: an image row is wider than the kernel's bit window");
@@ -929,7 +929,7 @@ int roft_engine_enable_pose_mask_occlusion(roft_engine* e, const int* obj_ids, c
     if (e->frame_counter > 0 || e->submitted) return fail(ROFT_ERR_STATE, "roft_engine_enable_pose_mask_occlusion must precede the first frame");
     EnginePoseMasks& pm = e->pose_masks;
     if (!pm.enabled) return fail(ROFT_ERR_STATE, "pose mask occlusion: roft_engine_enable_pose_masks comes first");
-    auto enrolled = [&](int id) { return e->objs[id]->pose_masks || (pm.all && e->h_params[id].n_verts > 0 && e->h_params[id].n_tris > 0); };
+    auto enrolled = [&](int id) { return e->objs[id]->pose_masks || (pm.all && has_mesh(e->h_params[id])); };
     for (int i = 0; i < n_ids; ++i) {
         const int id = obj_ids[i];
         if (id < 0 || id >= (int)e->objs.size()) return fail(ROFT_ERR_INVALID, "pose mask occlusion: " + std::to_string(id) + " is not an object of the engine");

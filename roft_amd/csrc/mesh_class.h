@@ -1,11 +1,26 @@
-// mesh_class.h -- host side: is an object's mesh a closed orientable surface, which triangles are wound inwards, and the order
-// in which the rasteriser walks the triangles (mesh_class.hip).
+// mesh_class.h -- host side, no device code: does a caller's mesh exist and do its triangles name vertices it has, is it a closed
+// orientable surface, which triangles are wound inwards, and the arrays in which it goes up to the device (mesh_class.hip).
 #pragma once
 
 #include <cstdint>
 #include <vector>
 
 namespace roft {
+
+// "The object has a mesh": both counts positive.  Anything with n_verts / n_tris will do (roft_mesh, ObjParams).
+inline bool has_mesh(int n_verts, int n_tris) { return n_verts > 0 && n_tris > 0; }
+template <class M>
+inline bool has_mesh(const M& m) { return has_mesh(m.n_verts, m.n_tris); }
+
+// What is wrong with the arrays of a mesh that has_mesh: nothing, a null array, or the first triangle corner that is no vertex of
+// the mesh (the rasteriser indexes the vertex array with these).  The caller words the refusal ("mesh 3: ...").
+struct MeshFault {
+    enum Kind { kFine, kNullArray, kBadIndex } kind = kFine;
+    long long triangle = 0;   // kBadIndex: the triangle ...
+    int32_t vertex = 0;       // ... and the vertex it refers to
+    explicit operator bool() const { return kind != kFine; }
+};
+MeshFault check_mesh_arrays(const float* verts, int n_verts, const int32_t* tris, int n_tris);
 
 // The render contract's classification (oracle/ro_meshclass.c states the rules; this is the engine's own implementation of
 // them): true and flip[t] = 1 for every triangle wound clockwise seen from outside when the mesh is a closed orientable
@@ -20,13 +35,18 @@ bool classify_mesh(const float* verts, int n_verts, const int32_t* tris, int n_t
 // triangle walked k-th.
 void facing_coherent_order(const float* verts, const int32_t* tris, int n_tris, const std::vector<uint8_t>& flip, std::vector<int32_t>& order);
 
-// What roft_object_add uploads: closed -> the reordered triangles + their flip bits, else the caller's triangles as they are.
+// The three layouts in which a mesh goes up.  A mesh that is not closed goes up as the caller's triangles, without flip bits, in all three.
+enum class MeshLayout {
+    kWalkOrder,     // closed: the triangles in the facing-coherent order, flip bits in that order (the engine's contract render, the operators)
+    kCallersOrder,  // closed: the caller's triangles, flip bits in the caller's order (the scene renderer: a key's triangle index is the caller's)
+    kAsItIs,        // never classified: the caller's triangles, no flip bits (the GL render mode draws every triangle, ties by the caller's order)
+};
 struct PreparedMesh {
     bool closed = false;
-    std::vector<int32_t> reordered;   // 3 x n_tris, closed meshes only
-    std::vector<uint8_t> flip;        // n_tris, in the reordered order
-    const int32_t* tris(const int32_t* callers) const { return closed ? reordered.data() : callers; }
+    std::vector<int32_t> reordered;   // 3 x n_tris: closed meshes in walk order only
+    std::vector<uint8_t> flip;        // n_tris: closed meshes only, in the order of tris()
+    const int32_t* tris(const int32_t* callers) const { return reordered.empty() ? callers : reordered.data(); }
 };
-void prepare_mesh(const float* verts, int n_verts, const int32_t* tris, int n_tris, PreparedMesh& out);
+void prepare_mesh(const float* verts, int n_verts, const int32_t* tris, int n_tris, MeshLayout layout, PreparedMesh& out);
 
 }  // namespace roft

@@ -1,4 +1,5 @@
-// mesh_class.hip -- closed-surface classification of an object's mesh and the walk order of its triangles (host code only).
+// mesh_class.hip -- the check of a caller's mesh arrays, closed-surface classification of an object's mesh, the walk order of its
+// triangles and the three layouts in which a mesh goes up (host code only).
 //
 // Reference: the reference draws every triangle of the mesh with the depth test LESS and no culling (SICAD.cpp:271-272), so the
 // rendered value is the nearest surface along a pixel's ray.  Seen from outside, the nearest surface of a closed mesh faces the
@@ -15,10 +16,18 @@
 
 namespace roft {
 
+MeshFault check_mesh_arrays(const float* verts, int n_verts, const int32_t* tris, int n_tris)
+{
+    if (!verts || !tris) return {MeshFault::kNullArray, 0, 0};
+    for (size_t i = 0; i < (size_t)3 * n_tris; ++i)
+        if (tris[i] < 0 || tris[i] >= n_verts) return {MeshFault::kBadIndex, (long long)(i / 3), tris[i]};
+    return {};
+}
+
 bool classify_mesh(const float* verts, int n_verts, const int32_t* tris, int n_tris, std::vector<uint8_t>& flip)
 {
     flip.assign((size_t)std::max(n_tris, 0), 0);
-    if (n_verts <= 0 || n_tris <= 0) return false;
+    if (!has_mesh(n_verts, n_tris)) return false;
     // 1. weld vertices with equal coordinates (-0 == +0) to the smallest index of their group
     struct P { float x, y, z; };
     std::vector<P> pos((size_t)n_verts);
@@ -131,13 +140,16 @@ void facing_coherent_order(const float* verts, const int32_t* tris, int n_tris, 
     std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return key[a] < key[b]; });
 }
 
-void prepare_mesh(const float* verts, int n_verts, const int32_t* tris, int n_tris, PreparedMesh& out)
+void prepare_mesh(const float* verts, int n_verts, const int32_t* tris, int n_tris, MeshLayout layout, PreparedMesh& out)
 {
-    std::vector<uint8_t> flip;
-    out.closed = classify_mesh(verts, n_verts, tris, n_tris, flip);
+    out.closed = false;
     out.reordered.clear();
     out.flip.clear();
+    if (layout == MeshLayout::kAsItIs) return;
+    std::vector<uint8_t> flip;
+    out.closed = classify_mesh(verts, n_verts, tris, n_tris, flip);
     if (!out.closed) return;
+    if (layout == MeshLayout::kCallersOrder) { out.flip.swap(flip); return; }
     std::vector<int32_t> order;
     facing_coherent_order(verts, tris, n_tris, flip, order);
     out.reordered.resize((size_t)3 * n_tris);

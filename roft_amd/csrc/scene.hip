@@ -10,9 +10,7 @@ struct roft_scene_renderer {
     hipStream_t stream = nullptr;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     bool timed = false;
-    std::deque<DevBuf<float>> verts;
-    std::deque<DevBuf<int32_t>> tris;
-    std::deque<DevBuf<uint8_t>> flips;
+    std::vector<DeviceMesh> resident;   // the meshes the table below names
     DevBuf<SceneMesh> meshes;
     DevBuf<uint64_t> keys;
     DevBuf<ScenePose> pose_table;
@@ -43,15 +41,7 @@ int check_camera(const roft_camera* cam)
 int check_meshes(const roft_mesh* meshes, int n_meshes)
 {
     if (n_meshes < 0 || (n_meshes > 0 && !meshes)) return fail(ROFT_ERR_INVALID, "null mesh array");
-    for (int k = 0; k < n_meshes; ++k) {
-        const roft_mesh& m = meshes[k];
-        const std::string which = "mesh " + std::to_string(k);
-        if (!m.verts || !m.tris || m.n_verts <= 0 || m.n_tris <= 0) return fail(ROFT_ERR_INVALID, which + ": null or empty vertex or triangle array");
-        if (m.n_tris >= (1 << 24)) return fail(ROFT_ERR_INVALID, which + ": 2^24 triangles or more (a pixel's key holds 24 bits of triangle index)");
-        for (size_t i = 0; i < (size_t)3 * m.n_tris; ++i)
-            if (m.tris[i] < 0 || m.tris[i] >= m.n_verts)
-                return fail(ROFT_ERR_INVALID, which + ": triangle " + std::to_string(i / 3) + " refers to vertex " + std::to_string(m.tris[i]) + " outside the vertex array");
-    }
+    for (int k = 0; k < n_meshes; ++k) TRY(check_mesh(meshes[k], "mesh " + std::to_string(k), false, 24));   // (a pixel's key holds 24 bits of triangle index)
     return ROFT_OK;
 }
 
@@ -193,25 +183,15 @@ int roft_scene_renderer_create(const roft_camera* cam, const roft_mesh* meshes, 
     hipError_t e = hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking);
     for (int k = 0; k < 3 && e == hipSuccess; ++k) e = hipEventCreate(&r->ev[k]);
     if (e != hipSuccess) return bail(ROFT_ERR_DEVICE, std::string("stream creation: ") + hipGetErrorString(e));
-    r->verts.resize((size_t)n_meshes);
-    r->tris.resize((size_t)n_meshes);
-    r->flips.resize((size_t)n_meshes);
+    r->resident = std::vector<DeviceMesh>((size_t)n_meshes);
     std::vector<SceneMesh> table((size_t)n_meshes);
-    for (int k = 0; k < n_meshes && e == hipSuccess; ++k) {
-        const roft_mesh& m = meshes[k];
+    for (int k = 0; k < n_meshes; ++k) {
         // the caller's triangles as they are (a key's triangle index is the caller's); closed meshes get their flip bits
-        std::vector<uint8_t> flip;
-        const bool closed = classify_mesh(m.verts, m.n_verts, m.tris, m.n_tris, flip);
-        e = r->verts[k].ensure((size_t)3 * m.n_verts);
-        if (e == hipSuccess) e = hipMemcpy(r->verts[k].p, m.verts, sizeof(float) * 3 * m.n_verts, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = r->tris[k].ensure((size_t)3 * m.n_tris);
-        if (e == hipSuccess) e = hipMemcpy(r->tris[k].p, m.tris, sizeof(int32_t) * 3 * m.n_tris, hipMemcpyHostToDevice);
-        if (closed && e == hipSuccess) e = r->flips[k].ensure((size_t)m.n_tris);
-        if (closed && e == hipSuccess) e = hipMemcpy(r->flips[k].p, flip.data(), (size_t)m.n_tris, hipMemcpyHostToDevice);
-        table[k] = SceneMesh{r->verts[k].p, r->tris[k].p, closed ? r->flips[k].p : nullptr, m.n_verts, m.n_tris};
-        r->max_verts = std::max(r->max_verts, m.n_verts);
+        if (const int rc = r->resident[k].upload(meshes[k], MeshLayout::kCallersOrder, r->stream)) return bail(rc, std::string(last_error()));
+        table[k] = r->resident[k].scene_mesh();
+        r->max_verts = std::max(r->max_verts, meshes[k].n_verts);
     }
-    if (e == hipSuccess) e = r->meshes.ensure((size_t)n_meshes);
+    e = r->meshes.ensure((size_t)n_meshes);
     if (e == hipSuccess && n_meshes) e = hipMemcpy(r->meshes.p, table.data(), sizeof(SceneMesh) * n_meshes, hipMemcpyHostToDevice);
     const size_t WH = (size_t)r->W * r->H;
     if (e == hipSuccess) e = r->keys.ensure((WH * max_frames_per_call + kResolvePixels - 1) / kResolvePixels * kResolvePixels);

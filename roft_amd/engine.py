@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from .ops import mesh_of
 
 
 def default_config(width, height, flow_type=L.FLOW_F32C2, max_objects=64, device=0, max_batch_frames=1, render_mode=L.RENDER_CONTRACT):
@@ -151,9 +152,7 @@ class ROFTFilterBatch:
         self.W, self.H = cfg.cam.width, cfg.cam.height
 
     def add_object(self, desc, verts, tris):
-        verts = np.ascontiguousarray(verts, np.float32)
-        tris = np.ascontiguousarray(tris, np.int32)
-        desc.mesh = L.Mesh(verts.ctypes.data, verts.shape[0], tris.ctypes.data, tris.shape[0])
+        desc.mesh, (verts, tris) = mesh_of(verts, tris)
         oid = C.c_int(-1)
         L.check(L.lib().roft_object_add(self._h, C.byref(desc), C.byref(oid)))
         self.n_objects += 1
@@ -178,10 +177,8 @@ class ROFTFilterBatch:
                 descs[i].mesh = L.Mesh(None, 0, None, 0)
                 keep.append(None)
             else:
-                v = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
-                t = np.ascontiguousarray(tris, np.int32).reshape(-1, 3)
-                descs[i].mesh = L.Mesh(v.ctypes.data, v.shape[0], t.ctypes.data, t.shape[0])
-                keep.append((v, t))
+                descs[i].mesh, arrays = mesh_of(verts, tris)
+                keep.append(arrays)
         L.check(L.lib().roft_objects_restart(self._h, ids, descs, n, L.RESTART_KEEP_MESH if keep_mesh else 0))
         meshes = getattr(self, "_meshes", [])
         for (oid, _, _, _), m in zip(items, keep):

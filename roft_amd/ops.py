@@ -29,6 +29,22 @@ def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def mesh_of(verts, tris):
+    """Arrays of any layout or dtype -> (L.Mesh, the C-contiguous (verts [n, 3] float32, tris [m, 3] int32) it points into: keep them)."""
+    verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
+    tris = np.ascontiguousarray(tris, np.int32).reshape(-1, 3)
+    return L.Mesh(verts.ctypes.data, verts.shape[0], tris.ctypes.data, tris.shape[0]), (verts, tris)
+
+
+def _mesh_array(meshes):
+    """[(verts, tris), ...] -> (Mesh array, the arrays it points into)."""
+    keep, arr = [], (L.Mesh * max(len(meshes), 1))()
+    for k, (v, t) in enumerate(meshes):
+        arr[k], arrays = mesh_of(v, t)
+        keep.append(arrays)
+    return arr, keep
+
+
 def make_flow(arr, width):
     assert arr.flags["C_CONTIGUOUS"] and arr.ndim == 3 and arr.shape[2] == 2
     if arr.dtype == np.int16:
@@ -125,9 +141,7 @@ def pose_silhouette(cam, mesh, x, q, bands=0, vertex_cache=True):
     L.require_device()
     x, q = _f64(np.asarray(x).reshape(3)), _f64(np.asarray(q).reshape(4))
     if not isinstance(mesh, L.Mesh):
-        verts = np.ascontiguousarray(mesh[0], np.float32).reshape(-1, 3)
-        tris = np.ascontiguousarray(mesh[1], np.int32).reshape(-1, 3)
-        mesh = L.Mesh(verts.ctypes.data, verts.shape[0], tris.ctypes.data, tris.shape[0])
+        mesh, keep = mesh_of(*mesh)
     mask = np.zeros((cam.height, cam.width), np.uint8)
     count = C.c_int(0)
     L.check(L.lib().roft_pose_silhouette(C.byref(cam), C.byref(mesh), _p(x), _p(q), int(bands), 1 if vertex_cache else 0, _p(mask), C.byref(count)))
@@ -142,12 +156,7 @@ def pose_silhouettes_occluded(cam, meshes, xs, qs, bands=0, vertex_cache=True):
     L.require_device()
     n = len(meshes)
     xs, qs = _f64(np.asarray(xs).reshape(n, 3)), _f64(np.asarray(qs).reshape(n, 4))
-    keep, arr = [], (L.Mesh * max(n, 1))()
-    for k, m in enumerate(meshes):
-        verts = np.ascontiguousarray(m[0], np.float32).reshape(-1, 3)
-        tris = np.ascontiguousarray(m[1], np.int32).reshape(-1, 3)
-        keep.append((verts, tris))
-        arr[k] = L.Mesh(verts.ctypes.data, verts.shape[0], tris.ctypes.data, tris.shape[0])
+    arr, keep = _mesh_array(meshes)
     masks = np.zeros((n, cam.height, cam.width), np.uint8)
     counts = np.zeros(n, np.int32)
     L.check(L.lib().roft_pose_silhouettes_occluded(C.byref(cam), arr, n, _p(xs), _p(qs), int(bands), 1 if vertex_cache else 0, _p(masks),
@@ -166,12 +175,7 @@ def pose_silhouettes_gated(cam, meshes, xs, qs, depth, front_tolerance=0.02, beh
     depth = np.ascontiguousarray(depth, np.float32)
     if depth.shape != (cam.height, cam.width):
         raise ValueError("depth is an H x W image of the camera's size")
-    keep, arr = [], (L.Mesh * max(n, 1))()
-    for k, m in enumerate(meshes):
-        verts = np.ascontiguousarray(m[0], np.float32).reshape(-1, 3)
-        tris = np.ascontiguousarray(m[1], np.int32).reshape(-1, 3)
-        keep.append((verts, tris))
-        arr[k] = L.Mesh(verts.ctypes.data, verts.shape[0], tris.ctypes.data, tris.shape[0])
+    arr, keep = _mesh_array(meshes)
     masks = np.zeros((n, cam.height, cam.width), np.uint8)
     counts = np.zeros(n, np.int32)
     removed = np.zeros((n, 2), np.int32)
@@ -207,10 +211,8 @@ def ukf_correct(mean, P, mtype, meas, rdiag, ut=(1.0, 2.0, 0.0)):
 
 
 def make_mesh(verts, tris):
-    verts = np.ascontiguousarray(verts, np.float32)
-    tris = np.ascontiguousarray(tris, np.int32)
-    m = L.Mesh(verts.ctypes.data, verts.shape[0], tris.ctypes.data, tris.shape[0])
-    m._keep = (verts, tris)
+    m, keep = mesh_of(verts, tris)
+    m._keep = keep
     return m
 
 
@@ -442,15 +444,6 @@ class FlowProducer:
 
 # ---- scene renderer (roft_scene_renderer_*, roft_render_scene) --------------------------------------------------
 SCENE_OUTPUTS = ("rgb", "depth", "instance", "triangle")
-
-
-def _mesh_array(meshes):
-    """[(verts, tris), ...] -> (Mesh array, the arrays it points into)."""
-    keep = [(np.ascontiguousarray(v, np.float32).reshape(-1, 3), np.ascontiguousarray(t, np.int32).reshape(-1, 3)) for v, t in meshes]
-    arr = (L.Mesh * max(len(keep), 1))()
-    for k, (v, t) in enumerate(keep):
-        arr[k] = L.Mesh(v.ctypes.data, v.shape[0], t.ctypes.data, t.shape[0])
-    return arr, keep
 
 
 def _scene_desc(width, height, mesh_index, poses, valid, background, gray_background, styles, window_pixels):

@@ -5,6 +5,9 @@ multi-component and non-orientable meshes; and the oracle's render of a closed m
 render with them (the nearest surface of a closed mesh seen from outside faces the camera; reference: depth test LESS, no
 culling, src/roft-lib/src/SICAD.cpp:271-272)."""
 
+import os
+import subprocess
+
 import numpy as np
 import pytest
 
@@ -13,6 +16,19 @@ import util
 from oracle import binding as ob
 from roft_amd import io, ops, synth
 
+
+
+def test_the_array_check_and_the_three_upload_layouts(tmp_path):
+    """tests/cpp/mesh_check.cpp against mesh_class.hip ALONE, as plain C++ without a HIP include path: the array check reports null
+    arrays and the triangle and vertex of a bad index; walk order is a permutation of the caller's triangles with the flips
+    following it, the caller's order keeps the caller's pointer with classify_mesh's flips, "as it is" is never classified."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, "roft_amd", "csrc")
+    exe = str(tmp_path / "mesh_check")
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-I", csrc, os.path.join(root, "tests", "cpp", "mesh_check.cpp"),
+                           "-x", "c++", os.path.join(csrc, "mesh_class.hip"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and r.stdout.strip() == "mesh_check ok", r.stderr
 
 
 @pytest.mark.parametrize("name", sorted(mesh_zoo.zoo()))
