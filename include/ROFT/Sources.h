@@ -194,8 +194,12 @@ public:
         // a buffer of its own for every frame (the pool recycles blocks by size): a consumer that still holds the last frame's
         // cv::Mat -- the filter keeps flows referenced for as long as a mask can be chased through them -- keeps its content
         flow_ = cv::Mat(h_ / (int)get_grid_size(), w_ / (int)get_grid_size(), get_matrix_type());
-        compat::throw_if(roft_optical_flow(last_.data(), gray, w_, h_, &prm_, get_matrix_type() == CV_16SC2 ? ROFT_FLOW_S16C2 : ROFT_FLOW_F32C2,
-                                           flow_.data), "ImageOpticalFlowHIP::step_frame");
+        if (check_)
+            compat::throw_if(roft_optical_flow_checked(last_.data(), gray, w_, h_, &prm_, &tol_, reinterpret_cast<float*>(flow_.data)),
+                             "ImageOpticalFlowHIP::step_frame");
+        else
+            compat::throw_if(roft_optical_flow(last_.data(), gray, w_, h_, &prm_, get_matrix_type() == CV_16SC2 ? ROFT_FLOW_S16C2 : ROFT_FLOW_F32C2,
+                                               flow_.data), "ImageOpticalFlowHIP::step_frame");
         last_.assign(gray, gray + n);
         flow_in_ = true;
         return true;
@@ -208,6 +212,22 @@ public:
     int get_matrix_type() const override { return product_ == Product::NVOF_1_0 ? CV_16SC2 : CV_32FC2; }
     bool flow_buffers_are_immutable() const override { return true; }   // (step_frame allocates)
     roft_of_params& parameters() { return prm_; }
+    // the forward-backward check of roft_engine.h section 3f for every later frame: occluded pixels of the flow are NaN, which
+    // the consumers skip (OpticalFlowUtilities.h:19-22).  nullptr: off again.  The CV_32FC2 product only (CV_16SC2 cannot say "invalid").
+    void set_consistency(const roft_of_consistency* c)
+    {
+        if (c && product_ != Product::NVOF_2_0) throw std::runtime_error("ImageOpticalFlowHIP::set_consistency: the check needs the CV_32FC2 product");
+        if (c && !(c->tolerance_abs >= 0.0f && c->tolerance_abs <= 3.402823466e38f && c->tolerance_rel >= 0.0f && c->tolerance_rel <= 3.402823466e38f))
+            throw std::runtime_error("ImageOpticalFlowHIP::set_consistency: tolerances must be finite and >= 0");
+        check_ = c != nullptr;
+        if (c) tol_ = *c;
+    }
+    void set_consistency(bool on)   // the default tolerances
+    {
+        roft_of_consistency c;
+        compat::throw_if(roft_default_of_consistency(&c), "ImageOpticalFlowHIP::set_consistency");
+        set_consistency(on ? &c : nullptr);
+    }
 
 private:
     void init()
@@ -230,6 +250,8 @@ private:
     int w_ = 0, h_ = 0;
     Product product_;
     roft_of_params prm_{};
+    bool check_ = false;
+    roft_of_consistency tol_{};
     std::vector<std::uint8_t> last_, pending_;
     cv::Mat flow_;
     bool flow_in_ = false;

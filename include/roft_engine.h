@@ -595,6 +595,50 @@ int roft_engine_get_flow_stats(roft_engine* e, roft_engine_flow_stats* out);
 /* Stand-alone operator (tests, tools): the gray image (W x H bytes) of a HOST image, any W, H >= 1, by the device's conversion. */
 int roft_image_to_gray(const void* image, int image_type, int W, int H, uint8_t* gray_out);
 
+/* ---- (3f) forward-backward check: occluded pixels of a produced flow are marked invalid --------------------------------- *
+ * Dense Lucas-Kanade returns a vector for every pixel, also where frame k covers or uncovers something and no correspondence
+ * exists.  With the check on, the producer also computes the flow of the swapped pair and keeps a vector only where the two
+ * agree.  An invalid vector is what the consumers already skip (OpticalFlowUtilities.h:19-22: NaN, or magnitude >= 1e9): the flow
+ * measurement draws no sample from it and the mask chain drops a pixel whose chase meets it.  Opt-in: a producer or an engine
+ * that does not enable the check produces what it did before, bit for bit.
+ *
+ * The check, operation by operation (float; every product and sum one rounded operation, no fused multiply-add):
+ *   F = the level-0 field of (prev, cur), H x W x 2: roft_optical_flow's CV_32FC2 product;  B = that of (cur, prev), same parameters
+ *   for pixel (x, y), (fx, fy) = F[y][x]:
+ *     xf = (float)x + fx;  yf = (float)y + fy
+ *     inside = xf >= 0 && xf <= (float)(W-1) && yf >= 0 && yf <= (float)(H-1)          (false for a flow that is not finite)
+ *     x0 = floorf(xf), ax = xf - x0, x1 = min((int)x0 + 1, W-1);  y0, ay, y1 likewise
+ *     per component c of B:  top = (1 - ax) * B[y0][x0] + ax * B[y0][x1]
+ *                            bot = (1 - ax) * B[y1][x0] + ax * B[y1][x1]
+ *                            b_c = (1 - ay) * top + ay * bot
+ *     ex = fx + bx;  ey = fy + by;  e2 = ex*ex + ey*ey;  m2 = (fx*fx + fy*fy) + (bx*bx + by*by)
+ *     valid = inside && e2 <= tolerance_rel * m2 + tolerance_abs                       (multiply, then add)
+ *   A valid pixel keeps its two floats untouched; an invalid one gets the bit pattern 0x7FC00000 (a quiet NaN) in both.  A
+ *   pixel whose target leaves the image cannot be checked and is invalid.
+ * Defaults: tolerance_abs 0.5, tolerance_rel 0.01 -- the customary values of the large-displacement-flow literature (Sundaram,
+ * Brox, Keutzer, ECCV 2010).  NOBODY HAS TUNED THEM FOR THIS TRACKER.
+ * CV_32FC2 only: CV_16SC2 has no representation of "invalid", so every entry point below refuses an S16C2 product with
+ * ROFT_ERR_INVALID.  Tolerances must be finite and >= 0 (ROFT_ERR_INVALID). */
+typedef struct {
+    float tolerance_abs, tolerance_rel;
+} roft_of_consistency;
+int roft_default_of_consistency(roft_of_consistency* c);
+/* host buffers, like roft_optical_flow with out_type ROFT_FLOW_F32C2; c NULL: the defaults.  Bad arguments (a null pointer,
+ * parameters outside roft_flow_producer_create's ranges, bad tolerances) are refused before a device is looked for. */
+int roft_optical_flow_checked(const uint8_t* prev_gray, const uint8_t* cur_gray, int W, int H, const roft_of_params* p,
+                              const roft_of_consistency* c, float* flow_out);
+/* Every later roft_flow_producer_run checks its products; c NULL turns the check off again (today's product, bit for bit).
+ * Allocates the backward workspace on first use.  max_pairs keeps its meaning: pairs per call, not Lucas-Kanade problems.
+ * ROFT_ERR_INVALID on an S16C2 producer or for bad tolerances; the producer is then as before the call. */
+int roft_flow_producer_set_consistency(roft_flow_producer* fp, const roft_of_consistency* c);
+/* The engine's own flows (section 3a) are checked: an object whose entries carry images behaves, bit for bit, as if inputs[].flow
+ * of frame k had been a HOST buffer holding roft_optical_flow_checked(G_{k-1}, G_k, W, H, p, c).  roft_engine_get_flow returns
+ * the checked field; roft_engine_flow_stats::pairs still counts flows produced, not Lucas-Kanade problems; a flow an object
+ * hands in directly is never checked.  After roft_engine_enable_flow and before the first frame (ROFT_ERR_STATE otherwise);
+ * c NULL: the defaults.  ROFT_ERR_INVALID when roft_config::flow_type is S16C2 or the tolerances are bad.  A refused call
+ * leaves the engine as if it had not been made.  (roft_engine_enable_flow called again starts from "off".) */
+int roft_engine_enable_flow_consistency(roft_engine* e, const roft_of_consistency* c);
+
 /* ---- (3c) raw sensor depth on the engine -------------------------------------------------------------------------- *
  * No sensor delivers H x W floats in metres registered to the colour camera.  The reference's capture tool reads Z16 frames,
  * registers them to the colour stream with rs2::align and calls convertTo(CV_32FC1, 0.001) on every frame, on the host

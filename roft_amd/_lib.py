@@ -45,6 +45,10 @@ class OFParams(C.Structure):
     _fields_ = [("levels", C.c_int), ("radius", C.c_int), ("iterations", C.c_int), ("det_min", C.c_float)]
 
 
+class OFConsistency(C.Structure):
+    _fields_ = [("tolerance_abs", C.c_float), ("tolerance_rel", C.c_float)]
+
+
 class Mesh(C.Structure):
     _fields_ = [("verts", C.c_void_p), ("n_verts", C.c_int), ("tris", C.c_void_p), ("n_tris", C.c_int)]
 
@@ -191,6 +195,7 @@ ABI_SYMBOLS = [
     "roft_engine_enable_pose_mask_occlusion", "roft_engine_get_pose_mask_occlusion_stats", "roft_pose_silhouettes_occluded",
     "roft_objects_restart", "roft_engine_get_restart_stats", "roft_debug_restart_check",
     "roft_default_pose_mask_gate", "roft_engine_enable_pose_mask_depth_gate", "roft_engine_get_pose_mask_gate_stats", "roft_pose_silhouettes_gated",
+    "roft_default_of_consistency", "roft_optical_flow_checked", "roft_flow_producer_set_consistency", "roft_engine_enable_flow_consistency",
 ]
 POSE_ERROR_ADD, POSE_ERROR_ADDS = 0, 1   # ROFT_POSE_ERROR_*
 # entry points younger than ABI version 2 itself: a library built before them still loads through ROFT_LIB_SO
@@ -203,7 +208,9 @@ NEWER_SYMBOLS = ("roft_pose_errors", "roft_engine_score_log", "roft_scene_render
                  "roft_engine_enable_pose_mask_occlusion", "roft_engine_get_pose_mask_occlusion_stats", "roft_pose_silhouettes_occluded",
                  "roft_objects_restart", "roft_engine_get_restart_stats",
                  "roft_default_pose_mask_gate", "roft_engine_enable_pose_mask_depth_gate", "roft_engine_get_pose_mask_gate_stats",
-                 "roft_pose_silhouettes_gated")
+                 "roft_pose_silhouettes_gated",
+                 "roft_default_of_consistency", "roft_optical_flow_checked", "roft_flow_producer_set_consistency",
+                 "roft_engine_enable_flow_consistency")
 
 
 def build(force=False):
@@ -337,6 +344,11 @@ def lib():
         L.roft_engine_enable_pose_mask_occlusion.argtypes = [vp, ip, ip, C.c_int]
         L.roft_engine_get_pose_mask_occlusion_stats.argtypes = [vp, C.POINTER(EnginePoseMaskOcclusionStats)]
         L.roft_pose_silhouettes_occluded.argtypes = [C.POINTER(Camera), C.POINTER(Mesh), C.c_int, vp, vp, C.c_int, C.c_int, vp, ip]
+    if hasattr(L, "roft_optical_flow_checked"):
+        L.roft_default_of_consistency.argtypes = [C.POINTER(OFConsistency)]
+        L.roft_optical_flow_checked.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(OFParams), C.POINTER(OFConsistency), vp]
+        L.roft_flow_producer_set_consistency.argtypes = [vp, C.POINTER(OFConsistency)]
+        L.roft_engine_enable_flow_consistency.argtypes = [vp, C.POINTER(OFConsistency)]
     if hasattr(L, "roft_objects_restart"):
         L.roft_objects_restart.argtypes = [vp, ip, C.POINTER(ObjectDesc), C.c_int, C.c_int]
         L.roft_engine_get_restart_stats.argtypes = [vp, C.POINTER(EngineRestartStats)]

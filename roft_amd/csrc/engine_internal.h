@@ -393,6 +393,11 @@ struct EngineFlow {
     // grows to the largest number of distinct images a frame ever brought.
     std::vector<std::vector<DevBuf<float>*>> pyr;
     DevBuf<float> coarse, field;        // workspace of ONE chunk of kOfChunk pairs, reused chunk after chunk in stream order
+    // the forward-backward check (roft_engine_enable_flow_consistency): a chunk is then kOfCheckChunk pairs, whose backward problems
+    // take the upper half of `coarse` and the level-0 fields of `back`
+    bool check = false;
+    roft_of_consistency tol{};
+    DevBuf<float> back;                 // [kOfCheckChunk][H * W * 2]
     roft_engine_flow_stats stats{};
     ~EngineFlow() { for (auto& g : pyr) for (auto* b : g) delete b; }
 };

@@ -254,7 +254,10 @@ static int stage_host_runs(roft_engine* e, const roft_frame_input* inputs, int n
     return ROFT_OK;
 }
 
-namespace roft { int of_check_params(int W, int H, const roft_of_params* p); }   // flow_producer.hip
+namespace roft {   // flow_producer.hip
+int of_check_params(int W, int H, const roft_of_params* p);
+int of_check_consistency(const roft_of_consistency* c);
+}
 
 static size_t image_bytes(int type, size_t npix) { return type == ROFT_IMAGE_GRAY8 ? npix : 3 * npix; }
 
@@ -281,9 +284,25 @@ static int enqueue_flow_production(roft_engine* e, int T)
     }
     if (im.n) launch_of_pyramids(f.geom, im, e->up_stream);
     OfPairs pr{};
+    OfCheck ck{};
+    ck.tol_abs = f.tol.tolerance_abs; ck.tol_rel = f.tol.tolerance_rel;
+    auto launch_checked = [&]() {
+        of_check_close(pr);
+        launch_of_pairs(f.geom, pr, e->up_stream);
+        launch_of_check(f.geom, ck, e->up_stream);
+        pr.n = ck.n = 0;
+    };
     for (int t = 0; t < T; ++t) {
         const int gen = (e->frame_counter + t) % G, gen_prev = (e->frame_counter + t + G - 1) % G;
         for (const FlowPairJob& pj : jobs[t].pairs) {
+            if (f.check) {   // (CV_32FC2 only: the product's place is the forward field)
+                const int k = pr.n;
+                of_check_put(pr, ck, f.pyr[gen_prev][pj.pyr0]->p, f.pyr[gen][pj.pyr1]->p, reinterpret_cast<float*>(pj.out),
+                             f.coarse.p + (size_t)k * f.geom.flow_stride, f.coarse.p + (size_t)(kOfCheckChunk + k) * f.geom.flow_stride,
+                             f.back.p + (size_t)k * field_floats);
+                if (pr.n == kOfCheckChunk) launch_checked();
+                continue;
+            }
             const int k = pr.n++;
             pr.pyr0[k] = f.pyr[gen_prev][pj.pyr0]->p;
             pr.pyr1[k] = f.pyr[gen][pj.pyr1]->p;
@@ -293,6 +312,7 @@ static int enqueue_flow_production(roft_engine* e, int T)
             if (pr.n == kOfChunk) { launch_of_pairs(f.geom, pr, e->up_stream); pr.n = 0; }
         }
     }
+    if (pr.n && f.check) launch_checked();
     if (pr.n) launch_of_pairs(f.geom, pr, e->up_stream);
     if (hipError_t le = hipGetLastError()) return fail(ROFT_ERR_DEVICE, std::string("flow production: ") + hipGetErrorString(le));
     for (int t = 0; t < T; ++t)
@@ -854,6 +874,26 @@ int roft_engine_enable_flow(roft_engine* e, const roft_of_params* p)
     f.pyr.assign((size_t)e->T_max + 1, std::vector<DevBuf<float>*>());
     f.prm = prm;
     f.enabled = true;
+    f.check = false;   // (enabled again: the check is asked for again, behind this call)
+    return ROFT_OK;
+}
+
+// include/roft_engine.h section 3f
+int roft_engine_enable_flow_consistency(roft_engine* e, const roft_of_consistency* c)
+{
+    if (!e) return fail(ROFT_ERR_INVALID, "null engine");
+    if (!e->flow.enabled) return fail(ROFT_ERR_STATE, "roft_engine_enable_flow_consistency follows roft_engine_enable_flow");
+    if (e->frame_counter > 0 || e->submitted) return fail(ROFT_ERR_STATE, "roft_engine_enable_flow_consistency must precede the first frame");
+    if (e->cfg.flow_type != ROFT_FLOW_F32C2)
+        return fail(ROFT_ERR_INVALID, "flow consistency: CV_16SC2 has no representation of an invalid vector, the check serves a CV_32FC2 engine only");
+    roft_of_consistency tol;
+    if (c) tol = *c; else (void)roft_default_of_consistency(&tol);
+    if (int rc = roft::of_check_consistency(&tol)) return rc;
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    EngineFlow& f = e->flow;
+    HIP_TRY(f.back.ensure((size_t)kOfCheckChunk * 2 * e->cfg.cam.width * e->cfg.cam.height));
+    f.tol = tol;
+    f.check = true;
     return ROFT_OK;
 }
 

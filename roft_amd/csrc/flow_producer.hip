@@ -13,7 +13,11 @@
 using namespace roft;
 
 extern "C" const char* roft_last_error_string(void);
-namespace roft { int set_last_error(int code, const std::string& msg); int of_check_params(int W, int H, const roft_of_params* p); }
+namespace roft {
+int set_last_error(int code, const std::string& msg);
+int of_check_params(int W, int H, const roft_of_params* p);
+int of_check_consistency(const roft_of_consistency* c);
+}
 
 #define OF_TRY(expr)                                                                                       \
     do {                                                                                                   \
@@ -29,7 +33,20 @@ struct roft_flow_producer {
     float* pyr = nullptr;               // [2 * max_pairs][pyr_stride]: one pyramid per DISTINCT image of a call
     float* coarse = nullptr;            // [max_pairs][flow_stride]
     float* field = nullptr;             // [max_pairs][H*W*2] level-0 fields when the product is CV_16SC2
+    // the forward-backward check (roft_flow_producer_set_consistency): the backward problems' coarse workspace and level-0 fields
+    bool check = false;
+    roft_of_consistency tol{};
+    float* coarse_b = nullptr;          // [max_pairs][flow_stride]
+    float* field_b = nullptr;           // [max_pairs][H*W*2]
 };
+
+// finite and >= 0 (a NaN fails both comparisons' complement)
+int roft::of_check_consistency(const roft_of_consistency* c)
+{
+    if (!(c->tolerance_abs >= 0.0f && c->tolerance_abs <= 3.402823466e38f && c->tolerance_rel >= 0.0f && c->tolerance_rel <= 3.402823466e38f))
+        return roft::set_last_error(ROFT_ERR_INVALID, "flow consistency: tolerance_abs and tolerance_rel must be finite and >= 0");
+    return ROFT_OK;
+}
 
 // the ranges roft_flow_producer_create accepts (roft_engine_enable_flow asks the same question)
 int roft::of_check_params(int W, int H, const roft_of_params* p)
@@ -75,6 +92,29 @@ int roft_flow_producer_create(int W, int H, int max_pairs, const roft_of_params*
     return ROFT_OK;
 }
 
+int roft_default_of_consistency(roft_of_consistency* c)
+{
+    if (!c) return roft::set_last_error(ROFT_ERR_INVALID, "null consistency");
+    c->tolerance_abs = 0.5f;
+    c->tolerance_rel = 0.01f;
+    return ROFT_OK;
+}
+
+int roft_flow_producer_set_consistency(roft_flow_producer* fp, const roft_of_consistency* c)
+{
+    if (!fp) return roft::set_last_error(ROFT_ERR_INVALID, "null producer");
+    if (!c) { fp->check = false; return ROFT_OK; }   // (the workspace stays: the check may come back)
+    if (fp->out_type != ROFT_FLOW_F32C2)
+        return roft::set_last_error(ROFT_ERR_INVALID, "flow consistency: CV_16SC2 has no representation of an invalid vector, the check serves the CV_32FC2 product only");
+    if (int rc = roft::of_check_consistency(c)) return rc;
+    OF_TRY(hipSetDevice(fp->device));
+    if (!fp->coarse_b) OF_TRY(hipMalloc(reinterpret_cast<void**>(&fp->coarse_b), sizeof(float) * fp->geom.flow_stride * fp->max_pairs));
+    if (!fp->field_b) OF_TRY(hipMalloc(reinterpret_cast<void**>(&fp->field_b), sizeof(float) * 2 * fp->W * fp->H * fp->max_pairs));
+    fp->tol = *c;
+    fp->check = true;
+    return ROFT_OK;
+}
+
 int roft_flow_producer_destroy(roft_flow_producer* fp)
 {
     if (!fp) return ROFT_OK;
@@ -83,6 +123,8 @@ int roft_flow_producer_destroy(roft_flow_producer* fp)
     if (fp->pyr) (void)hipFree(fp->pyr);
     if (fp->coarse) (void)hipFree(fp->coarse);
     if (fp->field) (void)hipFree(fp->field);
+    if (fp->coarse_b) (void)hipFree(fp->coarse_b);
+    if (fp->field_b) (void)hipFree(fp->field_b);
     if (fp->stream) (void)hipStreamDestroy(fp->stream);
     delete fp;
     return ROFT_OK;
@@ -105,9 +147,19 @@ int roft_flow_producer_run(roft_flow_producer* fp, const uint8_t* const* prev, c
         if (k == images.size()) images.push_back(img);
         return fp->pyr + k * g.pyr_stride;
     };
-    std::vector<OfPairs> chunks((size_t)(n + kOfChunk - 1) / kOfChunk, OfPairs{});
+    // with the check a chunk serves kOfCheckChunk pairs: the forward and the backward problem of each (opticalflow.h)
+    const int per = fp->check ? kOfCheckChunk : kOfChunk;
+    std::vector<OfPairs> chunks((size_t)(n + per - 1) / per, OfPairs{});
+    std::vector<OfCheck> checks(fp->check ? chunks.size() : 0, OfCheck{});
     for (int i = 0; i < n; ++i) {
-        OfPairs& c = chunks[(size_t)i / kOfChunk];
+        OfPairs& c = chunks[(size_t)i / per];
+        if (fp->check) {
+            float* prev_pyr = pyramid_of(prev[i]);
+            float* cur_pyr = pyramid_of(cur[i]);
+            of_check_put(c, checks[(size_t)i / per], prev_pyr, cur_pyr, static_cast<float*>(out[i]), fp->coarse + (size_t)i * g.flow_stride,
+                         fp->coarse_b + (size_t)i * g.flow_stride, fp->field_b + (size_t)i * 2 * fp->W * fp->H);
+            continue;
+        }
         const int k = c.n++;
         c.pyr0[k] = pyramid_of(prev[i]);
         c.pyr1[k] = pyramid_of(cur[i]);
@@ -123,7 +175,14 @@ int roft_flow_producer_run(roft_flow_producer* fp, const uint8_t* const* prev, c
         }
         launch_of_pyramids(g, im, fp->stream);
     }
-    for (const OfPairs& c : chunks) launch_of_pairs(g, c, fp->stream);
+    for (size_t i = 0; i < chunks.size(); ++i) {
+        if (fp->check) of_check_close(chunks[i]);
+        launch_of_pairs(g, chunks[i], fp->stream);
+        if (fp->check) {
+            checks[i].tol_abs = fp->tol.tolerance_abs; checks[i].tol_rel = fp->tol.tolerance_rel;
+            launch_of_check(g, checks[i], fp->stream);
+        }
+    }
     OF_TRY(hipGetLastError());
     return ROFT_OK;
 }
@@ -138,11 +197,19 @@ int roft_flow_producer_sync(roft_flow_producer* fp)
 
 void* roft_flow_producer_stream(roft_flow_producer* fp) { return fp ? (void*)fp->stream : nullptr; }
 
-int roft_optical_flow(const uint8_t* prev, const uint8_t* cur, int W, int H, const roft_of_params* p, int out_type, void* flow_out)
+static int optical_flow_host(const uint8_t* prev, const uint8_t* cur, int W, int H, const roft_of_params* p, int out_type,
+                             const roft_of_consistency* check, void* flow_out)
 {
     if (!prev || !cur || !p || !flow_out) return roft::set_last_error(ROFT_ERR_INVALID, "null argument");
+    if (check) {
+        // decided before any device is touched
+        if (int rc = roft::of_check_params(W, H, p)) return rc;
+        if (int rc = roft::of_check_consistency(check)) return rc;
+    }
     roft_flow_producer* fp = nullptr;
     if (int rc = roft_flow_producer_create(W, H, 1, p, out_type, 0, &fp)) return rc;
+    if (check)
+        if (int rc = roft_flow_producer_set_consistency(fp, check)) { roft_flow_producer_destroy(fp); return rc; }
     const size_t npix = (size_t)W * H;
     const size_t obytes = (out_type == ROFT_FLOW_F32C2) ? npix * 8 : (npix / 16) * 4;
     uint8_t *d0 = nullptr, *d1 = nullptr;
@@ -167,6 +234,19 @@ int roft_optical_flow(const uint8_t* prev, const uint8_t* cur, int W, int H, con
     roft_flow_producer_destroy(fp);
     if (e != hipSuccess) return roft::set_last_error(ROFT_ERR_DEVICE, hipGetErrorString(e));
     return rc;
+}
+
+int roft_optical_flow(const uint8_t* prev, const uint8_t* cur, int W, int H, const roft_of_params* p, int out_type, void* flow_out)
+{
+    return optical_flow_host(prev, cur, W, H, p, out_type, nullptr, flow_out);
+}
+
+int roft_optical_flow_checked(const uint8_t* prev, const uint8_t* cur, int W, int H, const roft_of_params* p, const roft_of_consistency* c,
+                              float* flow_out)
+{
+    roft_of_consistency tol;
+    if (c) tol = *c; else (void)roft_default_of_consistency(&tol);
+    return optical_flow_host(prev, cur, W, H, p, ROFT_FLOW_F32C2, &tol, flow_out);
 }
 
 int roft_image_to_gray(const void* image, int image_type, int W, int H, uint8_t* gray_out)

@@ -195,6 +195,46 @@ __global__ __launch_bounds__(256) void of_quantise_kernel(OfPairs pr, int W, int
     reinterpret_cast<short2*>(pr.out_s16[pair])[i] = make_short2((short)qx, (short)qy);
 }
 
+// The forward-backward check of a chunk's pairs (include/roft_engine.h section 3f states it operation by operation; the library is
+// built without contraction, so every product and sum below is one rounded operation).  One pixel per thread: the forward vector
+// is one coalesced 8-byte load, the four backward taps are 8-byte gathers around the pixel's target (neighbouring pixels have
+// neighbouring targets wherever the flow is smooth), and ONLY an invalid pixel is stored -- a valid one keeps its bits because
+// nothing writes them.  A pixel whose target is outside the image (or not finite: every comparison fails) reads nothing.
+__global__ __launch_bounds__(256) void of_check_kernel(OfCheck ck, int W, int H)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= W * H) return;
+    float2* F = reinterpret_cast<float2*>(ck.fwd[blockIdx.y]);
+    const float2* B = reinterpret_cast<const float2*>(ck.bwd[blockIdx.y]);
+    const int y = i / W, x = i - y * W;
+    const float2 f = F[i];
+    const float xf = (float)x + f.x, yf = (float)y + f.y;
+    bool valid = xf >= 0.0f && xf <= (float)(W - 1) && yf >= 0.0f && yf <= (float)(H - 1);
+    if (valid) {
+        const float x0f = floorf(xf), y0f = floorf(yf);
+        const float ax = xf - x0f, ay = yf - y0f;
+        const int x0 = (int)x0f, y0 = (int)y0f;
+        const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
+        const float2 b00 = B[(size_t)y0 * W + x0], b01 = B[(size_t)y0 * W + x1];
+        const float2 b10 = B[(size_t)y1 * W + x0], b11 = B[(size_t)y1 * W + x1];
+        const float sx = 1.0f - ax, sy = 1.0f - ay;
+        const float topx = sx * b00.x + ax * b01.x, botx = sx * b10.x + ax * b11.x;
+        const float topy = sx * b00.y + ax * b01.y, boty = sx * b10.y + ax * b11.y;
+        const float bx = sy * topx + ay * botx, by = sy * topy + ay * boty;
+        const float ex = f.x + bx, ey = f.y + by;
+        const float e2 = ex * ex + ey * ey;
+        const float m2 = (f.x * f.x + f.y * f.y) + (bx * bx + by * by);
+        valid = e2 <= ck.tol_rel * m2 + ck.tol_abs;
+    }
+    if (!valid) reinterpret_cast<uint2*>(F)[i] = make_uint2(0x7FC00000u, 0x7FC00000u);
+}
+
+void launch_of_check(const OfGeom& a, const OfCheck& ck, hipStream_t s)
+{
+    const int W = a.lv[0].w, H = a.lv[0].h;
+    hipLaunchKernelGGL(of_check_kernel, dim3((W * H + 255) / 256, ck.n), dim3(256), 0, s, ck, W, H);
+}
+
 void launch_of_pyramids(const OfGeom& a, const OfImages& im, hipStream_t s)
 {
     const int n4 = a.lv[0].w * a.lv[0].h / 4;

@@ -254,12 +254,23 @@ class ROFTFilterBatch:
     def submit_batch_raw(self, arr, T, labels=None, images=None):
         self._submit(arr, T, labels, images)
 
-    def enable_flow(self, **of_params):
+    def enable_flow(self, consistency=None, **of_params):
         """Camera images instead of flow frames (frame key `image`): the engine computes the optical flow itself, with the
-        parameters of ops.of_params (levels, radius, iterations, det_min).  Before the first frame."""
-        from .ops import of_params as make
+        parameters of ops.of_params (levels, radius, iterations, det_min).  consistency: None, True or (tolerance_abs,
+        tolerance_rel) -- the forward-backward check of ops.optical_flow on every produced flow (CV_32FC2 engines).  Before the
+        first frame."""
+        from .ops import of_consistency, of_params as make
         p = make(**of_params)
+        c = of_consistency(consistency)
         L.check(L.lib().roft_engine_enable_flow(self._h, C.byref(p)))
+        if c is not None:
+            self.enable_flow_consistency(c)
+
+    def enable_flow_consistency(self, consistency=True):
+        """roft_engine_enable_flow_consistency: behind enable_flow, before the first frame.  True: the default tolerances."""
+        from .ops import of_consistency
+        c = consistency if isinstance(consistency, L.OFConsistency) else of_consistency(consistency)
+        L.check(L.lib().roft_engine_enable_flow_consistency(self._h, None if c is None else C.byref(c)))
 
     def flow_stats(self):
         """images / image_bytes taken in, pyramids built, pairs (flows) produced since the engine was created."""

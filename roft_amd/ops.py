@@ -336,9 +336,25 @@ def of_params(levels=3, radius=3, iterations=3, det_min=100.0):
     return p
 
 
-def optical_flow(prev_gray, cur_gray, flow_type=L.FLOW_F32C2, **kw):
+def of_consistency(consistency):
+    """The forward-backward check's tolerances (L.OFConsistency) of a `consistency` argument: None / False -> None (no check),
+    True -> the library's defaults, (tolerance_abs, tolerance_rel) -> those."""
+    if consistency is None or consistency is False:
+        return None
+    c = L.OFConsistency()
+    if not hasattr(L.lib(), "roft_optical_flow_checked"):
+        raise L.RoftError("this libroft_hip.so has no forward-backward check (roft_optical_flow_checked)")
+    L.check(L.lib().roft_default_of_consistency(C.byref(c)))
+    if consistency is not True:
+        c.tolerance_abs, c.tolerance_rel = (float(v) for v in consistency)
+    return c
+
+
+def optical_flow(prev_gray, cur_gray, flow_type=L.FLOW_F32C2, consistency=None, **kw):
     """Forward flow of `prev_gray` pixels towards `cur_gray` (u8, H x W).  CV_32FC2: float (H, W, 2); CV_16SC2: int16
-    (H/4, W/4, 2) S10.5 -- the two products of ImageOpticalFlowNVOF.cpp:19-80."""
+    (H/4, W/4, 2) S10.5 -- the two products of ImageOpticalFlowNVOF.cpp:19-80.  consistency: None, True (default tolerances) or
+    (tolerance_abs, tolerance_rel) -- the forward-backward check of include/roft_engine.h section 3f, whose invalid pixels are NaN
+    (CV_32FC2 only)."""
     prev = np.ascontiguousarray(prev_gray, np.uint8)
     cur = np.ascontiguousarray(cur_gray, np.uint8)
     if prev.shape != cur.shape or prev.ndim != 2:
@@ -346,7 +362,13 @@ def optical_flow(prev_gray, cur_gray, flow_type=L.FLOW_F32C2, **kw):
     H, W = prev.shape
     out = np.zeros((H, W, 2), np.float32) if flow_type == L.FLOW_F32C2 else np.zeros((H // 4, W // 4, 2), np.int16)
     p = of_params(**kw)
-    L.check(L.lib().roft_optical_flow(_p(prev), _p(cur), W, H, C.byref(p), flow_type, _p(out)))
+    c = of_consistency(consistency)
+    if c is None:
+        L.check(L.lib().roft_optical_flow(_p(prev), _p(cur), W, H, C.byref(p), flow_type, _p(out)))
+    elif flow_type != L.FLOW_F32C2:
+        raise ValueError("consistency needs flow_type FLOW_F32C2: CV_16SC2 has no representation of an invalid vector")
+    else:
+        L.check(L.lib().roft_optical_flow_checked(_p(prev), _p(cur), W, H, C.byref(p), C.byref(c), _p(out)))
     return out
 
 
@@ -412,11 +434,22 @@ def depth_align(raw, depth_cam, colour_cam, scale=0.001, R=None, t=None):
 class FlowProducer:
     """Batched device-resident producer (roft_flow_producer_*): `run` takes lists of device pointers."""
 
-    def __init__(self, width, height, max_pairs, flow_type=L.FLOW_F32C2, device=0, **kw):
+    def __init__(self, width, height, max_pairs, flow_type=L.FLOW_F32C2, device=0, consistency=None, **kw):
         self._h = C.c_void_p()
         self.width, self.height, self.max_pairs, self.flow_type = width, height, max_pairs, flow_type
         p = of_params(**kw)
         L.check(L.lib().roft_flow_producer_create(width, height, max_pairs, C.byref(p), flow_type, device, C.byref(self._h)))
+        if consistency is not None and consistency is not False:
+            try:
+                self.set_consistency(consistency)
+            except L.RoftError:
+                self.close()
+                raise
+
+    def set_consistency(self, consistency):
+        """The forward-backward check for every later run (ops.optical_flow's `consistency`); None turns it off again."""
+        c = of_consistency(consistency)
+        L.check(L.lib().roft_flow_producer_set_consistency(self._h, None if c is None else C.byref(c)))
 
     def run(self, prev_ptrs, cur_ptrs, out_ptrs):
         n = len(prev_ptrs)

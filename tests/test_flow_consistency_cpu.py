@@ -1,0 +1,182 @@
+"""The forward-backward check without a device (include/roft_engine.h section 3f): the header declares the five names next to an
+unchanged ABI; the numpy restatement of the check (flow_consistency_ref.py), run over the CPU oracle's flows of both directions
+(oracle/ro_opticalflow.c, the backward flow being the same oracle with the images swapped), does on the fixtures what the check
+is for; and the entry points refuse bad arguments before they look for a device."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from roft_amd import _lib as L
+
+import flow_consistency_cases as cases
+import flow_consistency_ref as ref
+from oracle import binding as ob
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = ("roft_default_of_consistency", "roft_optical_flow_checked", "roft_flow_producer_set_consistency",
+         "roft_engine_enable_flow_consistency")
+SEEDS = (1, 2, 3)
+_checked = {}
+
+
+def _code():
+    text = open(os.path.join(ROOT, "include", "roft_engine.h")).read()
+    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+
+
+def _oracle_pair(kind, seed=None):
+    """(F, B) of a fixture by the oracle, levels 3 / radius 3 / iterations 3 / det_min 100: computed once, never modified"""
+    key = (kind, seed)
+    if key not in _checked:
+        a, b = cases.rolled() if kind == "rolled" else getattr(cases, kind)(seed)
+        F, B = ob.optical_flow(a, b, 3, 3, 3, 100.0), ob.optical_flow(b, a, 3, 3, 3, 100.0)
+        F.setflags(write=False)
+        B.setflags(write=False)
+        _checked[key] = (F, B)
+    return _checked[key]
+
+
+# ---- the interface -------------------------------------------------------------------------------------------------------
+def test_header_declares_the_five_names():
+    code = _code()
+    m = re.search(r"typedef\s+struct\s*\{([^}]*)\}\s*roft_of_consistency\s*;", code)
+    assert m, "roft_of_consistency is not declared"
+    assert re.findall(r"(\w+)\s*[,;]", m.group(1)) == ["tolerance_abs", "tolerance_rel"] == [f for f, _ in L.OFConsistency._fields_]
+    for name in NAMES:
+        assert re.search(r"\bint\s+%s\s*\(" % name, code), name + " is not declared"
+        assert name in L.ABI_SYMBOLS and hasattr(L.lib(), name), name
+
+
+def test_abi_version_and_existing_structs_are_unchanged(tmp_path):
+    assert re.search(r"#define\s+ROFT_ABI_VERSION\s+2\b", _code())
+    assert L.ABI_VERSION == 2 and L.lib().roft_abi_version() == 2
+    src = ('#include <stdio.h>\n#include "roft_engine.h"\nint main(){printf("%zu %zu %zu\\n", sizeof(roft_of_params), '
+           'sizeof(roft_engine_flow_stats), sizeof(roft_of_consistency));return 0;}')
+    (tmp_path / "s.c").write_text(src)
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(tmp_path / "s.c"), "-o", str(tmp_path / "s")])
+    got = [int(x) for x in subprocess.check_output([str(tmp_path / "s")]).split()]
+    assert got == [16, 32, 8]      # four 4-byte fields; four long long; two floats
+    assert got == [C.sizeof(L.OFParams), C.sizeof(L.EngineFlowStats), C.sizeof(L.OFConsistency)]
+
+
+def test_defaults():
+    c = L.OFConsistency()
+    assert L.lib().roft_default_of_consistency(C.byref(c)) == 0
+    assert (c.tolerance_abs, c.tolerance_rel) == (0.5, np.float32(0.01))
+    assert L.lib().roft_default_of_consistency(None) == -1
+
+
+# ---- what the check does, on the oracle's flows --------------------------------------------------------------------------
+@pytest.mark.parametrize("seed", SEEDS)
+def test_plain_pair_loses_rim_pixels_only(seed):
+    F, B = _oracle_pair("plain", seed)
+    inv = ref.invalid(ref.check(F, B))
+    box = cases.box_mask()
+    union = box | cases.box_mask(cases.SHIFT)
+    assert inv[cases.erode(box, 6)].sum() == 0, "an interior pixel was invalidated"
+    assert inv[~cases.dilate(union, 8)].sum() == 0, "a far background pixel was invalidated"
+    assert inv.sum() >= 1
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_occluded_object_pixels_are_invalid(seed):
+    F, B = _oracle_pair("occluded", seed)
+    inv = ref.invalid(ref.check(F, B))
+    cov = cases.covered_object_pixels()
+    assert cov.sum() == 6 * 8       # the occluder's core, 2 px inside its 10 x 12
+    assert inv[cov].mean() >= 0.5, inv[cov].mean()
+
+
+def test_rolled_pair_uses_every_rule():
+    F, B = _oracle_pair("rolled")
+    inside, valid, _ = ref.parts(F, B)
+    assert (~inside).sum() >= 1 and (inside & ~valid).sum() >= 1 and valid.sum() >= 1
+    out = ref.check(F, B)
+    assert np.array_equal(ref.invalid(out), ~valid)
+    assert np.array_equal(out.view(np.uint32)[valid], F.view(np.uint32)[valid])      # a valid pixel keeps its bits
+
+
+@pytest.mark.parametrize("kind,seed", [("plain", 1), ("occluded", 2), ("rolled", None)])
+def test_tolerance_extremes(kind, seed):
+    F, B = _oracle_pair(kind, seed)
+    inside, valid0, e2 = ref.parts(F, B, 0.0, 0.0)
+    assert np.array_equal(valid0, inside & (e2 == 0))           # (0, 0): exactly the pixels without any error
+    if kind != "rolled":
+        assert valid0.sum() >= 1                                # the static far background
+    _, valid_inf, _ = ref.parts(F, B, 1e30, 0.0)
+    assert np.array_equal(valid_inf, inside)                    # a huge tol_abs: exactly the `inside` rule
+    assert np.array_equal(ref.invalid(ref.check(F, B, 1e30, 0.0)), ~inside)
+
+
+def test_reference_marks_a_non_finite_flow_invalid():
+    F = np.zeros((8, 8, 2), np.float32)
+    B = np.zeros((8, 8, 2), np.float32)
+    F[2, 3] = (np.nan, 0.0)
+    F[4, 4] = (np.inf, 0.0)
+    F[5, 5] = (0.0, 2.5)      # leaves the image: row 7.5 > H - 1
+    F[1, 1] = (1.0, 0.0)
+    B[1, 2] = (-1.0, 0.0)     # its exact answer
+    F[6, 1] = (1.0, 0.0)      # ... and one whose backward flow disagrees: e2 = 1 > 0.01 * 1 + 0.5
+    inv = ref.invalid(ref.check(F, B))
+    want = np.zeros((8, 8), bool)
+    want[2, 3] = want[4, 4] = want[5, 5] = want[6, 1] = True
+    want[1, 2] = True         # (the answering pixel itself: its own forward flow is 0, its backward flow -1)
+    assert np.array_equal(inv, want)
+
+
+# ---- refusals decided before any device is touched ------------------------------------------------------------------------
+def _call(prm, tol, out=True, W=96, H=64):
+    a = np.zeros((H, W), np.uint8)
+    flow = np.zeros((H, W, 2), np.float32)
+    c = None
+    if tol is not None:
+        c = L.OFConsistency(*tol)
+    return L.lib().roft_optical_flow_checked(a.ctypes.data, a.ctypes.data, W, H, C.byref(prm), None if c is None else C.byref(c),
+                                             flow.ctypes.data if out else None)
+
+
+def test_operator_refuses_bad_arguments_before_it_needs_a_device():
+    lib = L.lib()
+    good = L.OFParams(3, 3, 3, 100.0)
+    for tol in ((np.nan, 0.01), (0.5, np.nan), (-0.5, 0.01), (0.5, -1e-6), (np.inf, 0.01), (0.5, np.inf)):
+        assert _call(good, tol) == -1, tol
+        assert b"tolerance" in lib.roft_last_error_string()
+    assert _call(good, (0.5, 0.01), out=False) == -1
+    for bad in (L.OFParams(0, 3, 3, 100.0), L.OFParams(7, 3, 3, 100.0), L.OFParams(3, 0, 3, 100.0), L.OFParams(3, 8, 3, 100.0),
+                L.OFParams(3, 3, -1, 100.0)):
+        assert _call(bad, (0.5, 0.01)) == -1
+        assert _call(bad, None) == -1
+    assert _call(good, (0.5, 0.01), W=100) == -1          # 100 is no multiple of 4 * 4
+    assert lib.roft_flow_producer_set_consistency(None, None) == -1
+    assert lib.roft_engine_enable_flow_consistency(None, None) == -1
+    if lib.roft_device_count() <= 0:
+        assert _call(good, (0.5, 0.01)) == -2             # ROFT_ERR_DEVICE: everything else was in order, there is no CPU path
+        assert _call(good, (0.0, 0.0)) == -2
+        assert _call(good, None) == -2
+
+
+def test_python_refuses_the_s16_product():
+    from roft_amd import ops
+    a = np.zeros((64, 96), np.uint8)
+    with pytest.raises(ValueError, match="CV_16SC2"):
+        ops.optical_flow(a, a, flow_type=L.FLOW_S16C2, consistency=True)
+
+
+# ---- the slots of a checked chunk, host only --------------------------------------------------------------------------------
+def test_checked_chunk_layout(tmp_path):
+    """tests/cpp/of_check_plan_check.cpp over roft_amd/csrc/opticalflow_args.h ALONE (no HIP include path), under the address and
+    undefined-behaviour sanitizers, as a program of its own."""
+    csrc = os.path.join(ROOT, "roft_amd", "csrc")
+    text = open(os.path.join(csrc, "opticalflow_args.h")).read()
+    includes = [line.split()[1] for line in text.splitlines() if line.startswith("#include")]
+    assert includes and all(i.startswith("<c") for i in includes), includes
+    exe = str(tmp_path / "of_check_plan_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I", csrc, os.path.join(ROOT, "tests", "cpp", "of_check_plan_check.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    assert int(r.stdout) > 500

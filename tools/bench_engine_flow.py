@@ -29,6 +29,119 @@ sys.path.insert(0, ROOT)
 import numpy as np   # noqa: E402
 
 
+def consistency_legs(args, default_out):
+    """Images on the engine, check on / off alternated args.windows times: n_obj objects of ONE scene in batches of T frames at
+    640 x 480 (object-frames/s), and one object fed frame by frame at 1280 x 720 (submit + step + state, microseconds)."""
+    import torch
+    from roft_amd import _lib as L
+    from roft_amd import engine as E
+    from roft_amd import synth
+
+    L.require_device()
+    dev = torch.device("cuda", 0)
+    n_obj, T = args.objects, max(1, min(args.batch, L.MAX_BATCH_FRAMES))
+
+    def engine(st, cam, n, t, on):
+        cfg = E.default_config(cam.width, cam.height, L.FLOW_F32C2, max_objects=n, max_batch_frames=t)
+        cfg.cam.fx, cfg.cam.fy, cfg.cam.cx, cfg.cam.cy = cam.fx, cam.fy, cam.cx, cam.cy
+        cfg.flow_grid, cfg.flow_scale = st.flow_grid, st.flow_scale
+        eng = E.ROFTFilterBatch(cfg)
+        m0 = synth.initial_pose_from_stream(st)
+        for _ in range(n):
+            d = E.default_object()
+            for i in range(13):
+                d.p_mean0[i] = m0[i]
+            eng.add_object(d, *st.mesh)
+        eng.enable_flow(consistency=True if on else None)
+        return eng
+
+    def scaled(cam):
+        return cam.scaled(args.scale) if args.scale > 1 else cam
+
+    # ---- shared scene, batches -------------------------------------------------------------------------------------------
+    cam = scaled(synth.Camera.shape_a())
+    n_run = T + args.frames
+    st = synth.make_stream(4100, n_run, cam, flow_type=L.FLOW_F32C2, device=dev, with_gray=True)
+    depth, gray = st.depth[:n_run].cpu().pin_memory(), st.gray[:n_run].cpu().pin_memory()
+    masks = st.mask_gt.cpu().pin_memory()
+
+    def leg(on):
+        eng = engine(st, cam, n_obj, T, on)
+        batches = []
+        for k0 in range(0, n_run, T):
+            fl = []
+            for k in range(k0, min(n_run, k0 + T)):
+                pose = (st.pose_meas[k, :3], st.pose_meas[k, 3:]) if st.pose_valid[k] else None
+                mi = int(st.mask_delivery[k])
+                fl.append([dict(depth=depth[k].data_ptr(), mask=masks[mi].data_ptr() if mi >= 0 else None, pose=pose, dt=st.dt, mem_kind=L.MEM_HOST,
+                                image=gray[k].data_ptr(), image_type=L.IMAGE_GRAY8) for _ in range(n_obj)])
+            arr, keep, t_ = eng.build_batch(fl)
+            batches.append((arr, keep, t_, eng.batch_labels(keep), eng.batch_images(keep)))
+        eng.submit_batch_raw(*[batches[0][i] for i in (0, 2, 3, 4)])
+        eng.step()
+        eng.sync()
+        f0 = eng.stats()["frames"]
+        t1 = time.perf_counter()
+        for arr, _keep, t, lab, img in batches[1:]:
+            eng.submit_batch_raw(arr, t, lab, img)
+            eng.step()
+        eng.sync()
+        dt = time.perf_counter() - t1
+        frames = eng.stats()["frames"] - f0
+        pairs = eng.flow_stats()["pairs"]
+        eng.close()
+        return n_obj * frames / dt, 1e3 * dt / frames, pairs
+
+    shared = dict(off=[], on=[])
+    for _ in range(args.windows):
+        for name in ("off", "on"):
+            shared[name].append(leg(name == "on"))
+
+    # ---- live, frame by frame ----------------------------------------------------------------------------------------------
+    camb = scaled(synth.Camera.shape_b())
+    n_live = args.live_frames
+    sb = synth.make_stream(4200, n_live, camb, flow_type=L.FLOW_F32C2, device=dev, with_gray=True)
+    depth_b, gray_b, masks_b = sb.depth.cpu().numpy(), sb.gray.cpu().numpy(), sb.mask_gt.cpu().numpy()
+
+    def live(on):
+        eng = engine(sb, camb, 1, 1, on)
+        lat = []
+        for k in range(n_live):
+            mi = int(sb.mask_delivery[k])
+            pose = (sb.pose_meas[k, :3], sb.pose_meas[k, 3:]) if sb.pose_valid[k] else None
+            f = dict(depth=depth_b[k], mask=masks_b[mi] if mi >= 0 else None, pose=pose, dt=sb.dt, image=gray_b[k])
+            t0 = time.perf_counter()
+            eng.submit([f])
+            eng.step()
+            eng.state(0)
+            lat.append(1e6 * (time.perf_counter() - t0))
+        eng.close()
+        return float(np.median(lat[2:]))
+
+    lives = dict(off=[], on=[])
+    for rnd in range(args.windows + 1):      # (round 0 warms allocations)
+        for name in ("off", "on"):
+            v = live(name == "on")
+            if rnd:
+                lives[name].append(v)
+
+    med = lambda v: float(sorted(v)[len(v) // 2])
+    result = dict(
+        shared_scene=dict(config=dict(objects=n_obj, width=cam.width, height=cam.height, batch=T, timed_frames=args.frames, windows=args.windows),
+                          object_frames_per_s_off=med([r[0] for r in shared["off"]]), object_frames_per_s_on=med([r[0] for r in shared["on"]]),
+                          ms_per_step_off=med([r[1] for r in shared["off"]]), ms_per_step_on=med([r[1] for r in shared["on"]]),
+                          windows_off=[r[0] for r in shared["off"]], windows_on=[r[0] for r in shared["on"]],
+                          pairs_off=shared["off"][0][2], pairs_on=shared["on"][0][2]),
+        live_latency=dict(config=dict(width=camb.width, height=camb.height, flow="CV_32FC2", objects=1, frames=n_live - 2, rounds=args.windows),
+                          median_us_off=med(lives["off"]), median_us_on=med(lives["on"]), rounds_off=lives["off"], rounds_on=lives["on"]))
+    print(json.dumps(result))
+    if args.out != default_out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--objects", type=int, default=64)
@@ -38,7 +151,13 @@ def main():
     p.add_argument("--scale", type=int, default=1, help="divide the cameras (a quick look on a small shape)")
     p.add_argument("--live-frames", type=int, default=40)
     p.add_argument("--out", default=os.path.join(ROOT, "profiles", "r11_engine_flow.json"))
+    p.add_argument("--consistency", action="store_true",
+                   help="instead of flows against images: images with the forward-backward check (roft_engine_enable_flow_consistency) "
+                        "ON against OFF, CV_32FC2, alternated in one process -- the shared-scene throughput leg and the live leg; "
+                        "prints one JSON line (and writes --out when it is given explicitly)")
     args = p.parse_args()
+    if args.consistency:
+        return consistency_legs(args, p.get_default("out"))
 
     import torch
     from roft_amd import _lib as L

@@ -3,6 +3,10 @@
 
 usage: python tools/bench_flow_producer.py [--pairs 64] [--shape A|B] [--flow f32|s16] [--reps 10]
 Prints one JSON line: pairs/s, ms per batch, arithmetic of the Lucas-Kanade level-0..L-1 kernels.
+
+--consistency [--rounds 5]: the forward-backward check (include/roft_engine.h section 3f) on and off ALTERNATED on one producer
+in one process, `rounds` windows of `reps` batches each; the JSON line then carries the median flow frames/s of both and the
+ratio (f32 only).
 """
 import argparse
 import json
@@ -28,7 +32,11 @@ def main():
     ap.add_argument("--levels", type=int, default=3)
     ap.add_argument("--radius", type=int, default=3)
     ap.add_argument("--iterations", type=int, default=3)
+    ap.add_argument("--consistency", action="store_true")
+    ap.add_argument("--rounds", type=int, default=5)
     args = ap.parse_args()
+    if args.consistency and args.flow != "f32":
+        ap.error("--consistency needs --flow f32")
     L.require_device()
     cam = synth.Camera.shape_a() if args.shape == "A" else synth.Camera.shape_b()
     W, H = cam.width, cam.height
@@ -43,6 +51,26 @@ def main():
     torch.cuda.synchronize()
     fp = ops.FlowProducer(W, H, n, ft, levels=args.levels, radius=args.radius, iterations=args.iterations)
     pp, cc, oo = [t.data_ptr() for t in prev], [t.data_ptr() for t in cur], [t.data_ptr() for t in out]
+    if args.consistency:
+        windows = dict(off=[], on=[])
+        for rnd in range(args.rounds + 1):           # (round 0 warms both variants up)
+            for name in ("off", "on"):
+                fp.set_consistency(True if name == "on" else None)
+                fp.run(pp, cc, oo)
+                fp.sync()
+                t0 = time.perf_counter()
+                for _ in range(args.reps):
+                    fp.run(pp, cc, oo)
+                fp.sync()
+                if rnd:
+                    windows[name].append(n * args.reps / (time.perf_counter() - t0))
+        fp.close()
+        med = {k: sorted(v)[len(v) // 2] for k, v in windows.items()}
+        print(json.dumps(dict(workload="%dx%d, %d pairs, f32, L%d r%d it%d, forward-backward check on / off alternated"
+                                       % (W, H, n, args.levels, args.radius, args.iterations),
+                              flows_per_s_off=med["off"], flows_per_s_on=med["on"], on_over_off_time=med["off"] / med["on"],
+                              windows_off=windows["off"], windows_on=windows["on"], reps=args.reps, rounds=args.rounds)))
+        return
     for _ in range(2):
         fp.run(pp, cc, oo)
     fp.sync()

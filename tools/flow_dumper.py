@@ -3,7 +3,7 @@
 (tools/nvof/dumper/src/main.cpp:40-146) with the same synopsis and the same output files.
 
   flow_dumper.py <dataset_path> <data_format> <rgb_format> <heading_zeros> <index_offset> <camera_width>
-                 <camera_height> <nvof_version> <output_path>
+                 <camera_height> <nvof_version> <output_path> [--consistency [ABS REL]]
 
 Frames `%0<heading_zeros>d.<rgb_format>` are read from <dataset_path>/rgb/ starting at index <index_offset>; their
 number is the number of rows of <dataset_path>/data.<data_format> (RobotsIO::Camera log).  For every frame but the
@@ -11,6 +11,9 @@ first, the forward flow from the previous frame is written to <output_path>/<ind
 OpticalFlowUtilities.cpp:77-136:  nvof1 -> CV_16SC2 (S10.5) at grid 4, nvof2 -> CV_32FC2 at grid 1
 (ImageOpticalFlowNVOF.cpp:19-80).  The flow itself comes from the HIP pyramidal Lucas-Kanade producer
 (roft_flow_producer_*); there is no CPU path.
+
+--consistency (not in the reference's tool; nvof2 only): the forward-backward check of include/roft_engine.h section 3f, with
+the default tolerances or ABS REL.  Occluded pixels are written as NaN, which every reader of the file treats as invalid.
 """
 import os
 import sys
@@ -29,7 +32,25 @@ def synopsis():
     return 1
 
 
+def take_consistency(argv):
+    """(argv without the option, None | True | (abs, rel)); raises ValueError for a malformed option"""
+    if "--consistency" not in argv:
+        return argv, None
+    i = argv.index("--consistency")
+    tail = argv[i + 1:]
+    if len(tail) == 0:
+        return argv[:i], True
+    if len(tail) == 2:
+        return argv[:i], (float(tail[0]), float(tail[1]))
+    raise ValueError
+
+
 def main(argv):
+    try:
+        argv, consistency = take_consistency(list(argv))
+    except ValueError:
+        sys.stderr.write("--consistency takes no value or two numbers (ABS REL) and comes last\n")
+        return 1
     if len(argv) != 10:
         return synopsis()
     dataset_path, data_format, rgb_format = argv[1], argv[2], argv[3]
@@ -47,6 +68,9 @@ def main(argv):
     nvof = argv[8]
     if nvof not in ("nvof1", "nvof2"):
         sys.stderr.write("Invalid <nvof_version> \"%s\"\n" % nvof)
+        return 1
+    if consistency is not None and nvof != "nvof2":
+        sys.stderr.write("--consistency needs nvof2: CV_16SC2 has no representation of an invalid vector\n")
         return 1
     output_path = argv[9]
     if rgb_format != "png":
@@ -76,7 +100,7 @@ def main(argv):
             raise ValueError("frame %d is %s, expected %d x %d" % (i, g.shape[::-1], width, height))
         return torch.from_numpy(np.ascontiguousarray(g)).cuda()
 
-    fp = ops.FlowProducer(width, height, BATCH, ft)
+    fp = ops.FlowProducer(width, height, BATCH, ft, consistency=consistency)
     oshape = (height, width, 2) if ft == L.FLOW_F32C2 else (height // 4, width // 4, 2)
     out = torch.zeros((BATCH,) + oshape, dtype=torch.float32 if ft == L.FLOW_F32C2 else torch.int16, device="cuda")
     last = load(index_offset) if n_frames > 0 else None

@@ -57,6 +57,9 @@ def main(argv=None):
     ap.add_argument("--compute-flow", choices=["nvof1", "nvof2"], default=None)
     ap.add_argument("--flow-on-engine", choices=["nvof1", "nvof2"], default=None,
                     help="hand the camera frames rgb/<i>.png to the engine, which computes the flow (nvof1: CV_16SC2 grid 4, nvof2: CV_32FC2)")
+    ap.add_argument("--flow-consistency", action="store_true",
+                    help="forward-backward check of the computed flow (include/roft_engine.h section 3f): occluded pixels become "
+                         "invalid; with --compute-flow nvof2 or --flow-on-engine nvof2")
     ap.add_argument("--raw-depth", type=float, default=None, metavar="SCALE",
                     help="read depth/<i>.png (16-bit gray, SCALE metres per unit) and let the engine convert it on the device")
     ap.add_argument("--no-delay", action="store_true")
@@ -95,13 +98,15 @@ def main(argv=None):
         if len(gate) not in (1, 2):
             ap.error("--pose-mask-depth-gate takes FRONT or FRONT,BEHIND (metres)")
         gate = (gate + [0.0])[:2]
+    if args.flow_consistency and "nvof2" not in (args.compute_flow, args.flow_on_engine):
+        ap.error("--flow-consistency needs --compute-flow nvof2 or --flow-on-engine nvof2 (CV_16SC2 has no invalid vector)")
     L.require_device()
     cam = json.load(open(os.path.join(args.root, "cam_K.json")))
     W, H = int(cam["width"]), int(cam["height"])
     if args.compute_flow:
         out = os.path.join(args.root, "optical_flow", args.flow_set)
         rc = subprocess.call([sys.executable, os.path.join(ROOT, "tools", "flow_dumper.py"), args.root, "txt", "png", "1", "0",
-                              str(W), str(H), args.compute_flow, out])
+                              str(W), str(H), args.compute_flow, out] + (["--consistency"] if args.flow_consistency else []))
         if rc != 0:
             return rc
     start = 0
@@ -169,7 +174,7 @@ def main(argv=None):
     if args.quality:
         eng.enable_quality()
     if args.flow_on_engine:
-        eng.enable_flow()
+        eng.enable_flow(consistency=True if args.flow_consistency else None)
     if args.raw_depth is not None:
         eng.enable_raw_depth(args.raw_depth)
     if args.masks_from_pose:
