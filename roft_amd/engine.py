@@ -185,11 +185,15 @@ class ROFTFilterBatch:
             if m is not None and 0 <= int(oid) < len(meshes):
                 meshes[int(oid)] = m
 
+    def _read_stats(self, call, struct):
+        """one roft_engine_get_*_stats call -> the fields of its struct as a dict"""
+        st = struct()
+        L.check(call(self._h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in struct._fields_}
+
     def restart_stats(self):
         """calls / objects restarted / meshes replaced by restart_objects since the engine was created."""
-        st = L.EngineRestartStats()
-        L.check(L.lib().roft_engine_get_restart_stats(self._h, C.byref(st)))
-        return {k: getattr(st, k) for k, _ in L.EngineRestartStats._fields_}
+        return self._read_stats(L.lib().roft_engine_get_restart_stats, L.EngineRestartStats)
 
     def submit(self, frames):
         """frames: one dict per object with keys depth, flow, mask, pose (None or (x, q)), dt,
@@ -274,9 +278,7 @@ class ROFTFilterBatch:
 
     def flow_stats(self):
         """images / image_bytes taken in, pyramids built, pairs (flows) produced since the engine was created."""
-        st = L.EngineFlowStats()
-        L.check(L.lib().roft_engine_get_flow_stats(self._h, C.byref(st)))
-        return {k: getattr(st, k) for k, _ in L.EngineFlowStats._fields_}
+        return self._read_stats(L.lib().roft_engine_get_flow_stats, L.EngineFlowStats)
 
     def produced_flow(self, obj):
         """The flow the engine produced for object `obj`'s last stepped frame, in the engine's flow type: float32 [H, W, 2] or
@@ -304,9 +306,7 @@ class ROFTFilterBatch:
 
     def depth_stats(self):
         """distinct raw images / their uploaded image_bytes taken in, float products made since the engine was created."""
-        st = L.EngineDepthStats()
-        L.check(L.lib().roft_engine_get_depth_stats(self._h, C.byref(st)))
-        return {k: getattr(st, k) for k, _ in L.EngineDepthStats._fields_}
+        return self._read_stats(L.lib().roft_engine_get_depth_stats, L.EngineDepthStats)
 
     def depth_kernel_ms(self):
         """Device time (ms, HIP events) of the depth kernels of the last submit call."""
@@ -345,9 +345,7 @@ class ROFTFilterBatch:
 
     def pose_mask_stats(self):
         """silhouettes drawn / frames that had any since the engine was created."""
-        st = L.EnginePoseMaskStats()
-        L.check(L.lib().roft_engine_get_pose_mask_stats(self._h, C.byref(st)))
-        return {k: getattr(st, k) for k, _ in L.EnginePoseMaskStats._fields_}
+        return self._read_stats(L.lib().roft_engine_get_pose_mask_stats, L.EnginePoseMaskStats)
 
     def enable_pose_mask_occlusion(self, scene_of=None):
         """Enrolled objects of one scene hide each other's silhouettes (roft_engine_enable_pose_mask_occlusion): each keeps the
@@ -374,15 +372,11 @@ class ROFTFilterBatch:
 
     def pose_mask_gate_stats(self):
         """dict(gated, emptied, pixels_front, pixels_behind); waits for the batches stepped so far"""
-        st = L.EnginePoseMaskGateStats()
-        L.check(L.lib().roft_engine_get_pose_mask_gate_stats(self._h, C.byref(st)))
-        return {k: getattr(st, k) for k, _ in L.EnginePoseMaskGateStats._fields_}
+        return self._read_stats(L.lib().roft_engine_get_pose_mask_gate_stats, L.EnginePoseMaskGateStats)
 
     def pose_mask_occlusion_stats(self):
         """silhouettes resolved / of those hidden entirely / pixels removed, since the engine was created (waits for the device)."""
-        st = L.EnginePoseMaskOcclusionStats()
-        L.check(L.lib().roft_engine_get_pose_mask_occlusion_stats(self._h, C.byref(st)))
-        return {k: getattr(st, k) for k, _ in L.EnginePoseMaskOcclusionStats._fields_}
+        return self._read_stats(L.lib().roft_engine_get_pose_mask_occlusion_stats, L.EnginePoseMaskOcclusionStats)
 
     def pose_mask_kernel_ms(self):
         """Device time (ms, HIP events on its dispatch) of the last silhouette launch."""
@@ -394,9 +388,7 @@ class ROFTFilterBatch:
         return L.lib().roft_engine_retain_frames(self._h)
 
     def stats(self):
-        st = L.EngineStats()
-        L.check(L.lib().roft_engine_get_stats(self._h, C.byref(st)))
-        return {k: getattr(st, k) for k, _ in L.EngineStats._fields_}
+        return self._read_stats(L.lib().roft_engine_get_stats, L.EngineStats)
 
     def batch_trace(self, n=64):
         """The engine's record of its last (at most 64) batches, oldest first: scheduling decisions and host times

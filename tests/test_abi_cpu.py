@@ -1,5 +1,6 @@
-"""The C-ABI shared library: loads, exports every symbol include/roft_engine.h declares, and has no
-CPU fallback (compute entry points fail loudly without a HIP device)."""
+"""The C-ABI shared library and its ctypes binding: every struct, function and integer constant include/roft_engine.h declares
+(tests/abi_header.py reads them) has its mirror, its row and its name in roft_amd/_lib.py, and they agree; the library exports
+every symbol and has no CPU fallback (compute entry points fail loudly without a HIP device)."""
 import ctypes as C
 import os
 import re
@@ -7,48 +8,83 @@ import re
 import numpy as np
 import pytest
 
+import abi_header
 from roft_amd import _lib as L
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def declared_symbols():
-    text = open(os.path.join(ROOT, "include", "roft_engine.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(roft_[a-z_0-9]+)\s*\(", text)))
+def _mirrors():
+    """{C struct name: [its ctypes mirrors]}: every Structure of the binding, paired by the C type it names"""
+    out = {}
+    for cls in vars(L).values():
+        if isinstance(cls, type) and issubclass(cls, C.Structure) and cls is not C.Structure:
+            out.setdefault(getattr(cls, "_c_name_", "(no _c_name_: %s)" % cls.__name__), []).append(cls)
+    return out
+
+
+def test_every_struct_has_one_mirror_with_the_layout_gcc_gives_it(tmp_path):
+    """Field names and order, every offset, every field's size and the struct's size, for every struct typedef of the header."""
+    structs, layouts, mirrors = abi_header.structs(), abi_header.layouts(tmp_path), _mirrors()
+    assert len(structs) >= 26
+    assert sorted(mirrors) == sorted(s.name for s in structs), "a struct without a mirror, or a mirror of no struct"
+    for s in structs:
+        assert len(mirrors[s.name]) == 1, s.name
+        mirror, (size, fields) = mirrors[s.name][0], layouts[s.name]
+        assert [f for f, _ in mirror._fields_] == s.fields, s.name
+        assert {f: (getattr(mirror, f).offset, getattr(mirror, f).size) for f in s.fields} == fields, s.name
+        assert C.sizeof(mirror) == size, s.name
+
+
+SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "uint8_t": C.c_uint8, "uint16_t": C.c_uint16, "long": C.c_long, "long long": C.c_longlong,
+           "unsigned long long": C.c_ulonglong, "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double, "char": C.c_char,
+           "void": None}
+# struct pointers the binding hands over as plain addresses (numpy buffers of records), as it always has
+STRUCTS_AS_ADDRESSES = {("roft_engine_get_quality", "out")}
+
+
+def _accepted(function, param, ctype, mirrors):
+    """the ctypes a row may use for one C parameter (param None: the return value)"""
+    base, depth = ctype
+    if base in abi_header.opaque_handles():          # a handle is an address, an out-parameter for one a pointer to an address
+        return {1: {C.c_void_p}, 2: {C.POINTER(C.c_void_p)}}[depth]
+    if base in mirrors:                              # structs are passed by pointer only
+        assert depth == 1, (function, param)
+        return {C.c_void_p} if (function, param) in STRUCTS_AS_ADDRESSES else {C.POINTER(mirrors[base][0])}
+    if depth == 0:
+        return {SCALARS[base]}
+    inner = _accepted(function, param, abi_header.CType(base, depth - 1), mirrors) - {None}
+    return {C.c_void_p} | {C.POINTER(t) for t in inner} | ({C.c_char_p} if (base, depth) == ("char", 1) else set())
 
 
 def test_library_builds_and_exports_every_declared_symbol():
+    """... and every prototype has exactly one row of L.ABI, whose restype and argtypes agree with it, parameter by parameter."""
     L.build()
     lib = L.lib()
-    decl = declared_symbols()
-    assert len(decl) >= 25
-    for name in decl:
-        assert hasattr(lib, name), "libroft_hip.so does not export %s" % name
-    assert sorted(L.ABI_SYMBOLS) == decl
+    protos, mirrors = abi_header.prototypes(), _mirrors()
+    assert len(protos) >= 99
+    # (the parser misses nothing that looks like a call of a roft_ name)
+    assert sorted(p.name for p in protos) == sorted(set(re.findall(r"\b(roft_[a-z_0-9]+)\s*\(", abi_header.code())))
+    assert sorted(L.ABI_SYMBOLS) == sorted(p.name for p in protos) and len(set(L.ABI_SYMBOLS)) == len(L.ABI)
+    rows = {f.name: f for f in L.ABI}
+    for p in protos:
+        assert hasattr(lib, p.name), "libroft_hip.so does not export %s" % p.name
+        row, fn = rows[p.name], getattr(lib, p.name)
+        assert (fn.restype, list(fn.argtypes)) == (row.restype, list(row.argtypes)), p.name + ": lib() did not apply the row"
+        assert row.restype in _accepted(p.name, None, p.ret, mirrors), p.name
+        assert len(row.argtypes) == len(p.params), p.name
+        for got, (param, ctype) in zip(row.argtypes, p.params):
+            assert got in _accepted(p.name, param, ctype, mirrors), (p.name, param, got)
+        assert row.optional == (p.name.startswith("roft_debug_") or p.name in L.NEWER_SYMBOLS), p.name
+    assert not any(f.optional for f in L.ABI if f.name in ("roft_abi_version", "roft_last_error_string", "roft_device_count"))
 
 
-def test_struct_layouts_match_header_sizes():
-    # sizes the C compiler gives the ABI structs (guards the ctypes mirrors)
-    import subprocess
-    import tempfile
-    src = '#include <stdio.h>\n#include "roft_engine.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(roft_camera), sizeof(roft_flow), sizeof(roft_config), sizeof(roft_object_desc), sizeof(roft_frame_input), sizeof(roft_object_output), sizeof(roft_batch_trace), sizeof(roft_engine_stats));return 0;}'
-    with tempfile.TemporaryDirectory() as d:
-        open(os.path.join(d, "s.c"), "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "s.c"), "-o", os.path.join(d, "s")])
-        sizes = [int(x) for x in subprocess.check_output([os.path.join(d, "s")]).split()]
-    assert sizes == [C.sizeof(L.Camera), C.sizeof(L.Flow), C.sizeof(L.Config), C.sizeof(L.ObjectDesc),
-                     C.sizeof(L.FrameInput), C.sizeof(L.ObjectOutput), C.sizeof(L.BatchTrace), C.sizeof(L.EngineStats)]
-    # (the trailing ints of roft_config share one alignment slot: a field missing from the mirror would not change the size)
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "roft_engine.h"\nint main(){printf("%zu %zu %zu %zu\\n", offsetof(roft_config, device), '
-           'offsetof(roft_config, max_batch_frames), offsetof(roft_config, mask_workgroups_per_object), '
-           'offsetof(roft_config, outlier_bands_per_alternative));return 0;}')
-    with tempfile.TemporaryDirectory() as d:
-        open(os.path.join(d, "o.c"), "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "o.c"), "-o", os.path.join(d, "o")])
-        offs = [int(x) for x in subprocess.check_output([os.path.join(d, "o")]).split()]
-    assert offs == [L.Config.device.offset, L.Config.max_batch_frames.offset, L.Config.mask_workgroups_per_object.offset,
-                    L.Config.outlier_bands_per_alternative.offset]
+def test_every_integer_define_has_its_constant():
+    values, others = abi_header.defines()
+    assert len(values) >= 30
+    assert others == ["ROFT_ENGINE_H"], "the include guard is the only define without an integer value"
+    for name, value in values.items():
+        assert getattr(L, name[len("ROFT_"):], None) == value, name
 
 
 def test_defaults_follow_the_reference_config():
@@ -101,7 +137,6 @@ def _plan(cfg, pose_valid):
     pv = (C.c_int * n)(*[int(v) for v in pose_valid])
     ns, nc, out = (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
     slots = (C.c_int * (n * 10))()
-    lib.roft_debug_plan.argtypes = [C.POINTER(L.Config), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     assert lib.roft_debug_plan(C.byref(cfg), pv, n, ns, nc, out, slots) == 0
     return list(ns), list(nc), list(out), np.array(list(slots)).reshape(n, 10)
 

@@ -5,7 +5,6 @@ tables (tests/pose_mask_gate_cases.py) and the conditions of the engine tests on
 the operator that need no device."""
 import ctypes as C
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -16,8 +15,6 @@ from roft_amd import _lib as L
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "roft_amd", "csrc")
-CALLS = ("roft_default_pose_mask_gate", "roft_engine_enable_pose_mask_depth_gate", "roft_engine_get_pose_mask_gate_stats",
-         "roft_pose_silhouettes_gated")
 
 
 def test_gate_frame_rule_follows_the_reference_flow_buffer(tmp_path):
@@ -76,22 +73,10 @@ def test_conditions_of_the_engine_tests_hold_on_the_reference():
     assert min(sizes) > 1000 and min(removed) > 300
 
 
-def test_library_exports_the_symbols_and_the_structs_have_gccs_size(tmp_path):
+def test_library_exports_the_symbols_and_the_structs_have_gccs_size():
+    """(exports, rows, prototypes and struct layouts: tests/test_abi_cpu.py, for every name of the header)"""
     lib = L.lib()
-    for call in CALLS:
-        assert hasattr(lib, call), "libroft_hip.so does not export " + call
-        assert call in L.ABI_SYMBOLS
     assert lib.roft_abi_version() == 2
-    header = open(os.path.join(ROOT, "include", "roft_engine.h")).read()
-    assert re.search(r"#define\s+ROFT_ABI_VERSION\s+2\b", header)
-    for call in CALLS:
-        assert re.search(r"\bint\s+%s\(" % call, header), call
-    src = ('#include <stdio.h>\n#include "roft_engine.h"\nint main(){printf("%zu %zu\\n", sizeof(roft_pose_mask_gate), '
-           'sizeof(roft_engine_pose_mask_gate_stats));return 0;}')
-    (tmp_path / "s.c").write_text(src)
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(tmp_path / "s.c"), "-o", str(tmp_path / "s")])
-    sizes = [int(x) for x in subprocess.check_output([str(tmp_path / "s")]).split()]
-    assert sizes == [C.sizeof(L.PoseMaskGate), C.sizeof(L.EnginePoseMaskGateStats)] == [8, 32]
     g = L.PoseMaskGate(-1.0, -1.0)
     assert lib.roft_default_pose_mask_gate(C.byref(g)) == 0 and (g.front_tolerance, g.behind_tolerance) == (np.float32(0.02), 0.0)
     assert lib.roft_default_pose_mask_gate(None) == -1

@@ -1,75 +1,37 @@
-"""Raw sensor depth without a device (include/roft_engine.h section 3c): the header declares the calls, structs and constants next
-to an unchanged ABI, the ctypes mirrors have the header's sizes and offsets, the library exports the symbols, the stand-alone
+"""Raw sensor depth without a device (include/roft_engine.h section 3c): the ABI version and roft_frame_input are unchanged, the stand-alone
 operators refuse bad arguments before they look for a device -- and the numpy restatement the GPU tests compare against
 (tests/depth_ref.py) has the properties the contract promises, on inputs that take every one of its branches.  Last: 16-bit gray
 PNGs, the form YCB-Video and HO-3D ship depth in."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_header
 from roft_amd import _lib as L
 from roft_amd import io
 
 import depth_ref as D
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = ("roft_engine_enable_raw_depth", "roft_engine_get_depth", "roft_engine_get_depth_stats", "roft_depth_convert", "roft_depth_align",
-         "roft_debug_depth_kernel_ms")
-
-
-def _code():
-    text = open(os.path.join(ROOT, "include", "roft_engine.h")).read()
-    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-
-
-def _fields(code, struct):
-    m = re.search(r"typedef\s+struct\s*\{([^}]*)\}\s*%s\s*;" % struct, code)
-    assert m, struct + " is not declared"
-    return [f for decl in m.group(1).split(";") for f in re.findall(r"(\w+)(?:\[\d+\])?\s*(?:,|$)", decl.strip())]
 
 
 # ---- ABI ------------------------------------------------------------------------------------------------------------------------
 def test_header_declares_the_calls_structs_and_constants():
-    code = _code()
-    for name in NAMES:
-        assert re.search(r"\bint\s+%s\s*\(" % name, code), name + " is not declared"
-    assert _fields(code, "roft_depth_source") == ["type", "scale", "align", "cam", "R", "t"] == [f for f, _ in L.DepthSource._fields_]
-    assert _fields(code, "roft_engine_depth_stats") == ["images", "image_bytes", "products"] == [f for f, _ in L.EngineDepthStats._fields_]
-    assert re.search(r"#define\s+ROFT_DEPTH_Z16\s+1\b", code) and L.DEPTH_Z16 == 1
-    assert re.search(r"#define\s+ROFT_DEPTH_ALIGN_MAX_SPAN\s+16\b", code) and L.DEPTH_ALIGN_MAX_SPAN == 16 == D.MAX_SPAN
+    """(calls, structs and the constants' values: tests/test_abi_cpu.py, for every name of the header)"""
+    assert L.DEPTH_ALIGN_MAX_SPAN == D.MAX_SPAN, "the numpy restatement clips footprints where the contract does"
 
 
 def test_abi_version_and_frame_input_are_unchanged():
-    code = _code()
+    code = abi_header.code()
     assert re.search(r"#define\s+ROFT_ABI_VERSION\s+2\b", code)
     assert L.ABI_VERSION == 2 and L.lib().roft_abi_version() == 2
     m = re.search(r"typedef\s+struct\s*\{([^}]*)\}\s*roft_frame_input\s*;", code)
     assert re.findall(r"(\w+)(?:\[\d+\])?\s*;", m.group(1)) == ["dt", "depth", "flow", "mask", "pose_valid", "pose_x", "pose_q", "mem_kind", "stamp",
                                                                  "mask_stamp"] == [f for f, _ in L.FrameInput._fields_]
     assert not re.search(r"\bint\s+roft_frames_submit_\w*depth", code), "no new submit call: the raw frame travels in inputs[].depth"
-
-
-def test_struct_layouts_match_the_header(tmp_path):
-    fields = ["type", "scale", "align", "cam", "R", "t"]
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "roft_engine.h"\nint main(){printf("%zu %zu %zu %zu", sizeof(roft_depth_source), '
-           'sizeof(roft_engine_depth_stats), offsetof(roft_engine_depth_stats, products), sizeof(roft_frame_input));\n'
-           + "".join('printf(" %%zu", offsetof(roft_depth_source, %s));' % f for f in fields) + 'printf("\\n");return 0;}')
-    (tmp_path / "s.c").write_text(src)
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(tmp_path / "s.c"), "-o", str(tmp_path / "s")])
-    got = [int(x) for x in subprocess.check_output([str(tmp_path / "s")]).split()]
-    assert got == [C.sizeof(L.DepthSource), C.sizeof(L.EngineDepthStats), L.EngineDepthStats.products.offset, C.sizeof(L.FrameInput)] + \
-        [getattr(L.DepthSource, f).offset for f in fields]
-
-
-def test_library_exports_the_symbols():
-    lib = L.lib()
-    for name in NAMES:
-        assert hasattr(lib, name), "libroft_hip.so does not export " + name
-        assert name in L.ABI_SYMBOLS
 
 
 def _source(**over):

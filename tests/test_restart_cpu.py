@@ -1,52 +1,27 @@
-"""roft_objects_restart without a GPU: the header declares the entry points and the flag next to an unchanged ABI, the ctypes
-binding knows them, every ROFT_ERR_INVALID refusal comes before a device is looked for, the C++ facade's restart_objects compiles,
-and ROFT-tracker-batch explains --slots."""
+"""roft_objects_restart without a GPU: the header declares the entry points next to an unchanged ABI, every ROFT_ERR_INVALID
+refusal comes before a device is looked for, the C++ facade's restart_objects compiles, and ROFT-tracker-batch explains --slots."""
 import ctypes as C
 import os
-import re
 import subprocess
 
 import numpy as np
 
+import abi_header
 from roft_amd import _lib as L
 from roft_amd import engine as E
 from roft_amd import synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "roft_engine.h")
 CSRC = os.path.join(ROOT, "roft_amd", "csrc")
 
 
-def _code():
-    return re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
-
-
 def test_header_declares_the_calls_and_the_flag_next_to_abi_version_2():
-    code = _code()
-    assert re.search(r"\bint\s+roft_objects_restart\s*\(\s*roft_engine\s*\*\s*\w+\s*,\s*const\s+int\s*\*\s*\w+\s*,\s*const\s+roft_object_desc\s*\*\s*\w+\s*,"
-                     r"\s*int\s+\w+\s*,\s*int\s+\w+\s*\)\s*;", code)
-    assert re.search(r"\bint\s+roft_engine_get_restart_stats\s*\(\s*roft_engine\s*\*\s*\w+\s*,\s*roft_engine_restart_stats\s*\*\s*\w+\s*\)\s*;", code)
-    assert re.search(r"#define\s+ROFT_RESTART_KEEP_MESH\s+1\b", code) and L.RESTART_KEEP_MESH == 1
-    assert re.search(r"#define\s+ROFT_ABI_VERSION\s+2\b", code) and L.ABI_VERSION == 2 and L.lib().roft_abi_version() == 2
-    m = re.search(r"typedef\s+struct\s*\{([^}]*)\}\s*roft_engine_restart_stats\s*;", code)
-    assert m and re.findall(r"(\w+)\s*[,;]", m.group(1)) == [f for f, _ in L.EngineRestartStats._fields_] == ["calls", "objects", "meshes_replaced"]
+    """(prototypes, struct, flag and argtypes: tests/test_abi_cpu.py checks them with every other name of the header)"""
+    code = abi_header.code()
+    assert L.ABI_VERSION == 2 and L.lib().roft_abi_version() == 2
     # the section follows roft_object_add, as the issue of this feature places it
     assert code.index("roft_object_add(") < code.index("roft_objects_restart(") < code.index("roft_frame_submit(")
-
-
-def test_binding_has_the_argtypes(tmp_path):
-    lib = L.lib()
-    vp, ip = C.c_void_p, C.POINTER(C.c_int)
-    assert lib.roft_objects_restart.argtypes == [vp, ip, C.POINTER(L.ObjectDesc), C.c_int, C.c_int]
-    assert lib.roft_engine_get_restart_stats.argtypes == [vp, C.POINTER(L.EngineRestartStats)]
-    assert lib.roft_objects_restart.restype == C.c_int and lib.roft_engine_get_restart_stats.restype == C.c_int
-    for name in ("roft_objects_restart", "roft_engine_get_restart_stats", "roft_debug_restart_check"):
-        assert name in L.ABI_SYMBOLS
     assert hasattr(E.ROFTFilterBatch, "restart_objects") and hasattr(E.ROFTFilterBatch, "restart_stats")
-    src = '#include <stdio.h>\n#include "roft_engine.h"\nint main(){printf("%zu\\n", sizeof(roft_engine_restart_stats));return 0;}'
-    (tmp_path / "s.c").write_text(src)
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(tmp_path / "s.c"), "-o", str(tmp_path / "s")])
-    assert int(subprocess.check_output([str(tmp_path / "s")])) == C.sizeof(L.EngineRestartStats) == 24
 
 
 def test_every_invalid_refusal_comes_before_the_device():
