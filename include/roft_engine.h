@@ -188,7 +188,8 @@ int roft_depth_likelihood(const roft_camera* cam, const float* depth, const uint
  * alternatives x[0..2] q[0..3] (pose + velocity correction) and x[3..5] q[4..7] (velocity only) are rendered at
  * (W/divider) x (H/divider) and scored against every second mask pixel with 0 < depth < 2 (:553-577), and the decision
  * L_0 > 2 L_1 -> 1 (:581-583) is taken.  bands: workgroups one alternative is split over, 1..8 (0: by the CUs to spare, as
- * the engine does); vertex_cache 0: project the vertices per triangle instead of once into LDS; window_pixels > 0 caps
+ * the engine does); vertex_cache 0: project the vertices per triangle instead of once into LDS (the GL render mode only:
+ * the contract render walks the mesh in clusters of 64 triangles and keeps no projected vertices); window_pixels > 0 caps
  * the LDS depth window (a larger window is rendered in strips).  None of the three changes a bit of the depths.
  * tiles_out (optional): 2 x (H/divider) x (W/divider) floats, the renders as the kernel drew them, 0 = background.
  * L_out: DBL_MAX when an alternative has no sample. */

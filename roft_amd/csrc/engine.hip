@@ -643,7 +643,7 @@ static int apply_object_desc(roft_engine* e, int id, HostObject* o, const roft_o
     // The contract render leaves the triangles of a closed mesh that face away out (oracle/ro_render.c) and walks alike-facing ones
     // together; the GL render mode draws every triangle and breaks depth ties on the caller's order: the mesh goes up as it is.
     DeviceMesh fresh;
-    if (!keep_mesh) TRY(fresh.upload(d->mesh, e->cfg.render_mode == ROFT_RENDER_CONTRACT ? MeshLayout::kWalkOrder : MeshLayout::kAsItIs, s));
+    if (!keep_mesh) TRY(fresh.upload(d->mesh, e->cfg.render_mode == ROFT_RENDER_CONTRACT ? MeshLayout::kWalkClusters : MeshLayout::kAsItIs, s));
     (keep_mesh ? o->mesh : fresh).describe(p);
     // initialization_step (ROFTFilter.cpp:216-237)
     init_state(*st);
@@ -670,7 +670,9 @@ static int apply_object_desc(roft_engine* e, int id, HostObject* o, const roft_o
 static void update_mesh_maxima(roft_engine* e, int n_objs)
 {
     e->arr.a.max_tris = e->arr.a.max_verts = 0;
+    e->arr.a.meshes_without_clusters = 0;
     for (int id = 0; id < n_objs; ++id) {
+        if (e->h_params[id].n_tris > 0 && e->h_params[id].n_clusters <= 0) ++e->arr.a.meshes_without_clusters;
         e->arr.a.max_tris = std::max(e->arr.a.max_tris, e->h_params[id].n_tris);
         e->arr.a.max_verts = std::max(e->arr.a.max_verts, e->h_params[id].n_verts);
     }

@@ -14,6 +14,7 @@
 //   engine_debug.hip    roft_debug_* (diagnostics and experiments)
 //   scene.hip           the scene renderer: roft_scene_renderer_*, roft_render_scene
 //   mesh_class.h        a caller's mesh on the host: has_mesh, the array check, classification, the three upload layouts (host-only C++)
+//   mesh_clusters.h     the walk-order triangles cut into clusters of 64 for the outlier test's contract render (host-only C++ + the cone test)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -32,6 +33,7 @@
 
 #include "roft_device.h"
 #include "mesh_class.h"
+#include "mesh_clusters.h"
 #include "scene.h"
 #include "batch_plan.h"
 #include "pose_mask_gate.h"
@@ -105,15 +107,18 @@ struct DeviceMesh {
     DevBuf<float> verts;
     DevBuf<int32_t> tris;
     DevBuf<uint8_t> flip;
-    int n_verts = 0, n_tris = 0;
+    DevBuf<uint32_t> cl_headers, cl_words;   // the triangles as clusters (mesh_clusters.h): uploads that ask for them
+    DevBuf<float> cl_slots, box_corners;
+    int n_verts = 0, n_tris = 0, n_clusters = 0;
     bool closed = false;   // the current upload was of a closed mesh in a layout with flip bits: `flip` holds them
 
     // `m` (which has passed check_mesh) in `layout` (mesh_class.h), copied on stream s.  Returns only when the copies have read
     // their host arrays: the prepared triangle order and flip bits live in this call.  An absent mesh, or a failed upload, leaves
-    // "no mesh"; an absent mesh makes no device call.
+    // "no mesh"; an absent mesh makes no device call.  MeshLayout::kWalkClusters: the triangles go up as clusters as well.
     int upload(const roft_mesh& m, MeshLayout layout, hipStream_t s)
     {
-        n_verts = n_tris = 0;
+        const bool clusters = layout == MeshLayout::kWalkClusters;
+        n_verts = n_tris = n_clusters = 0;
         closed = false;
         if (!has_mesh(m)) return ROFT_OK;
         PreparedMesh pm;
@@ -126,9 +131,23 @@ struct DeviceMesh {
             HIP_TRY(flip.ensure((size_t)m.n_tris));
             HIP_TRY(hipMemcpyAsync(flip.p, pm.flip.data(), (size_t)m.n_tris, hipMemcpyHostToDevice, s));
         }
+        MeshClusters mc;
+        if (clusters) {
+            build_clusters(m.verts, m.n_verts, pm.tris(m.tris), m.n_tris, pm.closed ? pm.flip.data() : nullptr,
+                           pm.bucket.empty() ? nullptr : pm.bucket.data(), mc);
+            HIP_TRY(cl_headers.ensure(mc.headers.size()));
+            HIP_TRY(cl_slots.ensure(mc.slots.size()));
+            HIP_TRY(cl_words.ensure(mc.words.size()));
+            HIP_TRY(box_corners.ensure(24));
+            HIP_TRY(hipMemcpyAsync(cl_headers.p, mc.headers.data(), sizeof(uint32_t) * mc.headers.size(), hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(cl_slots.p, mc.slots.data(), sizeof(float) * mc.slots.size(), hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(cl_words.p, mc.words.data(), sizeof(uint32_t) * mc.words.size(), hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(box_corners.p, &mc.box[0][0], sizeof(float) * 24, hipMemcpyHostToDevice, s));
+        }
         HIP_TRY(hipStreamSynchronize(s));
         n_verts = m.n_verts;
         n_tris = m.n_tris;
+        n_clusters = mc.n_clusters;
         closed = pm.closed;
         return ROFT_OK;
     }
@@ -139,11 +158,14 @@ struct DeviceMesh {
         const bool has = has_mesh(*this);
         return SceneMesh{has ? verts.p : nullptr, has ? tris.p : nullptr, closed ? flip.p : nullptr, n_verts, n_tris};
     }
-    void describe(ObjParams& p) const   // (the five mesh fields of an object's parameter block)
+    void describe(ObjParams& p) const   // (the mesh fields of an object's parameter block)
     {
         const SceneMesh m = scene_mesh();
         p.verts = m.verts; p.tris = m.tris; p.tri_flip = m.flip;
         p.n_verts = m.n_verts; p.n_tris = m.n_tris;
+        const bool cl = has_mesh(*this) && n_clusters > 0;
+        p.cl_headers = cl ? cl_headers.p : nullptr; p.cl_slots = cl ? cl_slots.p : nullptr; p.cl_words = cl ? cl_words.p : nullptr;
+        p.box_corners = cl ? box_corners.p : nullptr; p.n_clusters = cl ? n_clusters : 0;
     }
 };
 
@@ -248,6 +270,7 @@ struct Arrays {
         a.log_cap = 0;
         a.max_tris = 0;
         a.max_verts = 0;
+        a.meshes_without_clusters = 0;
         a.ukf_chol_guard = 0.0;
         a.ukf_chol_guard_bil = 0.0;
         a.mask_wgs = 0;

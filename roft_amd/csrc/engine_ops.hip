@@ -639,14 +639,16 @@ static int op_outlier(const roft_camera* cam, int divider, const float* depth, c
         a.tile_w = cam->width / a.cam.divider;
         a.tile_h = cam->height / a.cam.divider;
         a.max_verts = a.max_tris = 0;
+        a.meshes_without_clusters = 0;
     };
     // (GL render mode: the caller's triangles as they are, every one drawn -- roft_object_add does the same)
-    TRY(c.mesh.upload(*mesh, o_in.render_mode == ROFT_RENDER_CONTRACT ? MeshLayout::kWalkOrder : MeshLayout::kAsItIs, c.stream));
+    TRY(c.mesh.upload(*mesh, o_in.render_mode == ROFT_RENDER_CONTRACT ? MeshLayout::kWalkClusters : MeshLayout::kAsItIs, c.stream));
     ObjParams prm;
     std::memset(&prm, 0, sizeof(prm));
     c.mesh.describe(prm);
     a.max_verts = mesh->n_verts;
     a.max_tris = mesh->n_tris;
+    a.meshes_without_clusters = (prm.n_tris > 0 && prm.n_clusters <= 0) ? 1 : 0;
     FrameCtrl fc;
     clear_ctrl(fc);
     fc.n_steps = 1;        // (walked already: the segment below only decides)
@@ -690,7 +692,7 @@ static int op_outlier(const roft_camera* cam, int divider, const float* depth, c
         launch_mask_ingest(a, 0, c.stream);
         launch_features(a, c.stream);
     }
-    launch_outlier(a, 0, c.stream, nullptr, &o);
+    TRY(launch_outlier(a, 0, c.stream, nullptr, &o));
     roft_ut_params ut{1.0, 2.0, 0.0};
     launch_ukf_chain(a, ut, false, 0, c.stream);   // decision (ROFTFilter.cpp:581-583) as the engine's next segment takes it
     err = hipMemcpyAsync(st, c.arr.state.p, sizeof(ObjState), hipMemcpyDeviceToHost, c.stream);

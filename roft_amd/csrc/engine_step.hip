@@ -360,7 +360,7 @@ static int enqueue_lane(Enqueue& q, int lin)
         tmark(e, "ukf_chain", which);
         if (last) break;
         if (seg == 0 && lp.wait_prev_vel) TRY(q.wait(sp, e->slot_of(e->batch_counter - 1).ev_vel));
-        launch_outlier(q.a, lin, sp, nullptr, &oo);
+        TRY(launch_outlier(q.a, lin, sp, nullptr, &oo));
         ++q.launches;
         CHECK_LAUNCH("outlier rejection");
         tmark(e, "outlier_render_likelihood", which);

@@ -18,11 +18,15 @@
 //    ~N_mask/2 samples and the frame itself need not be retained.
 #include <algorithm>
 #include <atomic>
+#include <string>
 
+#include "mesh_clusters.h"
 #include "plane_rank.h"
 #include "raster.h"
 
 namespace roft {
+
+namespace host { int fail(int code, const std::string& msg); }   // (engine.hip: sets the thread's error string, returns `code`)
 
 constexpr int kFeatThreads = 1024;
 
@@ -338,14 +342,25 @@ __global__ __launch_bounds__(kOutlierThreads) void outlier_kernel(EngineArrays a
 
 // ---- the engine's outlier test: depth render + likelihood of ONE alternative per workgroup, all in LDS ------------------
 // The render is only ever sampled at the buffered feature pixels, and the object covers a small window of the render
-// target (about 70 x 90 of 320 x 240 pixels at the metric shape).  So: the mesh vertices are projected once per
-// alternative into LDS (a vertex is shared by six triangles), their pixel bounding box is the z window -- also in LDS,
+// target (about 70 x 90 of 320 x 240 pixels at the metric shape).  So: the pixel box of the mesh is the z window -- in LDS,
 // resolved with LDS atomicMin, +inf = empty --, and the likelihood reads it in place.  No z-buffer in HBM, no clear
-// pass, no global atomics, one launch instead of three.  A window that does not fit the LDS next to the vertices is
-// rendered in horizontal strips (every strip walks all triangles and all features); a mesh whose vertices do not fit is
-// projected per triangle.  The per-pixel arithmetic is raster_projected's, whatever the strips, bands and the vertex cache: the depths are bit-identical
-// to oracle/ro_render.c in every configuration (tests/test_parity_gpu.py drives this kernel through roft_render_depth and
-// roft_outlier_test).
+// pass, no global atomics, one launch instead of three.  A window that does not fit the LDS is rendered in horizontal strips
+// (every strip walks all triangles and all features).  The per-pixel arithmetic is raster_projected's, whatever the strips and
+// bands: the depths are bit-identical to oracle/ro_render.c in every configuration (tests/test_parity_gpu.py and
+// tests/test_outlier_clusters_gpu.py drive this kernel through roft_render_depth and roft_outlier_test).
+// The contract render (GL = false) has no vertex pass: the mesh goes up cut into clusters of at most 64 triangles over at most 64
+// vertices (mesh_clusters.h), and a wave projects and draws one cluster at a time.  Before, every workgroup of an alternative
+// projected ALL vertices into a 98 KB LDS cache in a phase of its own in front of everything else (7 of 37 us at 64 objects),
+// and every triangle fetched three 32-bit indices and gathered nine floats from that cache.  Why the bits stay what they were:
+//   * every triangle the walk over `tris` drew is drawn, with the same corner coordinates -- a slot holds the bits of the mesh's
+//     vertex and goes through the same project_vertex -- in the triangle's own corner order and with the same cull code; the
+//     clusters the cone test skips hold only triangles raster_projected's sign-of-area rule culls (cluster_faces_away);
+//   * every window pixel is an order-free atomicMin, so it does not matter which wave draws a triangle, or when;
+//   * the window box from the corners of the mesh's box CONTAINS the vertices' box (corner_box_settles, raster.h): the same
+//     depths at the same pixels, the added pixels stay empty, and an empty pixel is neither dumped nor sampled; `behind` is
+//     the vertices' own flag (settled by the corners only with a tenfold margin, else by the vertex pass);
+//   * the band sums are exact integers (LikelihoodSum): rows may fall to other bands or strips than before.
+// The GL render mode keeps the vertex pass and its cache (project_mesh / fetch_triangle, as the other rasteriser kernels).
 // With CUs to spare an alternative is shared by `parts` workgroups, as R bands of the window's rows x G groups of its
 // triangles (round 4; R G = parts, R = the fewest bands that fit the LDS in one piece -- 1 for most objects).  The G workgroups of
 // a band each draw THEIR triangles (runs of 64, dealt out in turn) into a window of their own, write it through to a slab in
@@ -356,7 +371,7 @@ __global__ __launch_bounds__(kOutlierThreads) void outlier_kernel(EngineArrays a
 // when the slabs do not cover objects x parts, roft_debug_outlier_split(0) forces it.)  The launch lasts as long as its slowest
 // workgroup, which in the row split is the middle band of the largest object (49 - 56 us of triangles at 8 and 16 objects against
 // 25 - 30 with the triangles dealt out: 60 - 66 -> 45 - 46 us per launch).
-// grid: (2 alternatives x parts, n_obj).  dynamic LDS: [3 * vcache_cap floats] | [win_cap z values]
+// grid: (2 alternatives x parts, n_obj).  dynamic LDS: [win_cap z values]; GL: [3 * vcache_cap floats] | [win_cap keys]
 // GL = true: render mode ROFT_RENDER_GL (raster_projected_gl).  The window is then a visibility buffer: a pixel holds the 64-bit key
 // (quantised window z << 32 | triangle index in the caller's order) resolved with LDS atomicMin -- the nearest fragment, the first
 // drawn among equal depths, whatever order the threads draw in --, and the depth of the winning triangle is evaluated again where it
@@ -380,8 +395,9 @@ __global__ __launch_bounds__(kFusedThreads) void outlier_fused_kernel(EngineArra
     __shared__ int s_box[4];
     __shared__ int s_behind;
     __shared__ int s_last;
+    __shared__ int s_settled;
     // Workgroups are handed to the XCDs round robin by their linear index; the 2 x parts workgroups of an object read the
-    // same mesh (186 KB of indices + 98 KB of vertices at the bench's 15.5 k triangles): with the grid laid out as
+    // same mesh (246 clusters of 1 KB at the bench's 15.5 k triangles): with the grid laid out as
     // [group of 8 objects][workgroup of the object][object within the group] they share one XCD and one L2.
     const int per = 2 * parts, lin_id = (int)blockIdx.x;
     const int obj = (lin_id / (8 * per)) * 8 + (lin_id & 7), bx = (lin_id >> 3) % per;
@@ -397,9 +413,10 @@ __global__ __launch_bounds__(kFusedThreads) void outlier_fused_kernel(EngineArra
     const int d = a.cam.divider, tw = a.tile_w, th = a.tile_h;
     const float fx = (float)(a.cam.fx / d), fy = (float)(a.cam.fy / d), cx = (float)(a.cam.cx / d), cy = (float)(a.cam.cy / d);
     const int nv = prm.n_verts, nt = prm.n_tris;
-    const bool cached = nv <= vcache_cap;
+    // (the contract render keeps no projected vertices: its dynamic LDS is the window alone)
+    const bool cached = GL && nv <= vcache_cap;
     float* s_v = reinterpret_cast<float*>(smem);
-    uint32_t* s_z = reinterpret_cast<uint32_t*>(smem + vertex_cache_bytes(vcache_cap));
+    uint32_t* s_z = reinterpret_cast<uint32_t*>(smem + (GL ? vertex_cache_bytes(vcache_cap) : 0));
     uint64_t* s_k = reinterpret_cast<uint64_t*>(s_z);   // (GL: the visibility buffer, win_cap keys)
     if (tid < 4) s_box[tid] = (tid < 2) ? INT32_MAX : -1;
     if (tid == 0) s_behind = 0;
@@ -412,9 +429,31 @@ __global__ __launch_bounds__(kFusedThreads) void outlier_fused_kernel(EngineArra
         if constexpr (GL) project_vertex_gl(v, P, fx, fy, cx, cy, sx, sy, z);
         else project_vertex(v, P, fx, fy, cx, cy, sx, sy, z);
     };
-    // vertices -> screen and the pixel box of everything that can be drawn (raster.h), four vertices per thread fetched together
-    project_mesh<kFusedThreads, 4>(prm.verts, nv, cached, s_v, tw, th, s_box, &s_behind, project);
-    __syncthreads();
+    if constexpr (GL) {
+        // vertices -> screen and the pixel box of everything that can be drawn (raster.h), four vertices per thread fetched together
+        project_mesh<kFusedThreads, 4>(prm.verts, nv, cached, s_v, tw, th, s_box, &s_behind, project);
+        __syncthreads();
+    } else {
+        // The window box and the `behind` flag from the eight corners of the mesh's box, by the whole first wave (lane l takes corner
+        // l & 7: corner_box_settles votes and reduces across the wave); the vertex pass only where the corners do not settle them.
+        if (tid < 64 && prm.n_clusters > 0) {
+            const int k = tid & 7;
+            const float vc[3] = {prm.box_corners[3 * k], prm.box_corners[3 * k + 1], prm.box_corners[3 * k + 2]};
+            int box[4];
+            const bool settled = corner_box_settles(vc, P, fx, fy, cx, cy, tw, th, box);
+            if (tid == 0) {
+                s_settled = settled ? 1 : 0;
+                if (settled) { s_box[0] = box[0]; s_box[1] = box[1]; s_box[2] = box[2]; s_box[3] = box[3]; }
+            }
+        } else if (tid == 0) {
+            s_settled = 1;   // (no mesh: the empty box)
+        }
+        __syncthreads();
+        if (!s_settled) {
+            project_mesh<kFusedThreads, 4>(prm.verts, nv, false, s_v, tw, th, s_box, &s_behind, project);
+            __syncthreads();
+        }
+    }
     UTICK(0);
     const int i0 = min(s_box[0], tw - 1), i1 = s_box[2];
     // The `parts` workgroups of the alternative share its work as R bands of the window's rows x G groups of its triangles
@@ -473,38 +512,81 @@ __global__ __launch_bounds__(kFusedThreads) void outlier_fused_kernel(EngineArra
             auto store_key = [zk, i0, js, win_w](int i, int j, uint64_t key) {
                 (void)__hip_atomic_fetch_min(zk + ((j - js) * win_w + (i - i0)), key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             };
-            constexpr int kTB = 8;   // triangles per thread whose vertex indices are fetched together
-            const uint8_t* const flips = (!GL && nv < (1 << 30)) ? cull_table(prm.tri_flip, s_behind) : nullptr;   // (the cull code rides in an index's top bits)
-            // (split: the triangles are dealt out to the workgroups of the alternative in runs of 64 -- one run per wave and
-            //  fetch, so the index loads stay coalesced and neighbouring runs, which cost alike, go to different workgroups)
-            const int stride = G, first = grp;
-            auto tri_of = [=](int slot) { return ((slot >> 6) * stride + first) * 64 + (slot & 63); };   // slot: this workgroup's own numbering
-            const int n_slots = split ? ((nt + 63) / 64 + stride - 1 - first) / stride * 64 : nt;        // (its runs; the last one may be short)
-            for (int tb = tid; tb < n_slots; tb += kTB * kFusedThreads) {
-              int idx[kTB][3];   // (idx[k][0] carries the triangle's cull code in its two top bits: no registers of its own)
+            if constexpr (GL) {
+                // every triangle in the caller's order (tris are uploaded unsorted in this mode; the key's low word is that index),
+                // kTB per thread whose vertex indices are fetched together
+                constexpr int kTB = 8;
+                for (int tb = tid; tb < nt; tb += kTB * kFusedThreads) {
+                    int idx[kTB][3];
 #pragma unroll
-              for (int k = 0; k < kTB; ++k) {
-                  const int t = min(tri_of(min(tb + k * kFusedThreads, n_slots - 1)), nt - 1);
-                  const int32_t* tri = prm.tris + (size_t)3 * t;
-                  idx[k][0] = tri[0]; idx[k][1] = tri[1]; idx[k][2] = tri[2];
-                  if (flips) idx[k][0] |= cull_code(flips, t) << 30;
-              }
+                    for (int k = 0; k < kTB; ++k) {
+                        const int32_t* tri = prm.tris + (size_t)3 * min(tb + k * kFusedThreads, nt - 1);
+                        idx[k][0] = tri[0]; idx[k][1] = tri[1]; idx[k][2] = tri[2];
+                    }
 #pragma unroll
-              for (int k = 0; k < kTB; ++k) {
-                if (tb + k * kFusedThreads >= n_slots || tri_of(tb + k * kFusedThreads) >= nt) break;
-                const int cull_k = (int)((unsigned)idx[k][0] >> 30);
-                const int v0 = idx[k][0] & 0x3FFFFFFF, v1 = idx[k][1], v2 = idx[k][2];
-                float x0, y0, z0, x1, y1, z1, x2, y2, z2;
-                fetch_triangle(s_v, cached, prm.verts, v0, v1, v2, project, x0, y0, z0, x1, y1, z1, x2, y2, z2);
-                if constexpr (GL) {
-                    // the key's low word: the triangle's index in the caller's order (tris are uploaded unsorted in this mode)
-                    const uint64_t t = (uint32_t)tri_of(tb + k * kFusedThreads);
-                    raster_projected_gl(x0, y0, z0, x1, y1, z1, x2, y2, z2, tw, th, js, je,
-                                        [&](int i, int j, uint32_t qz) { store_key(i, j, ((uint64_t)qz << 32) | t); });
-                } else {
-                    raster_projected(x0, y0, z0, x1, y1, z1, x2, y2, z2, tw, th, js, je, cull_k, store);
+                    for (int k = 0; k < kTB; ++k) {
+                        if (tb + k * kFusedThreads >= nt) break;
+                        float x0, y0, z0, x1, y1, z1, x2, y2, z2;
+                        fetch_triangle(s_v, cached, prm.verts, idx[k][0], idx[k][1], idx[k][2], project, x0, y0, z0, x1, y1, z1, x2, y2, z2);
+                        const uint64_t t = (uint32_t)(tb + k * kFusedThreads);
+                        raster_projected_gl(x0, y0, z0, x1, y1, z1, x2, y2, z2, tw, th, js, je,
+                                            [&](int i, int j, uint32_t qz) { store_key(i, j, ((uint64_t)qz << 32) | t); });
+                    }
                 }
-              }
+            } else {
+                // One wave, one cluster at a time (mesh_clusters.h).  The clusters are dealt out in turn to the G workgroups that share
+                // the band's triangles and to their waves -- neighbouring clusters, which cost alike, go to different workgroups.
+                // First every lane looks at ONE cluster of the wave's list: while the back-face rule is on it reads the cluster's
+                // header and asks its cone whether all of it faces away (cluster_faces_away: only clusters of which raster_projected
+                // would cull every triangle) -- such a cluster is neither fetched, projected nor drawn.  Then the wave walks the
+                // clusters that are left: lane v projects vertex slot v, lane t takes the corners of triangle t from the lanes that
+                // own them and draws it, with the next cluster's slots and words (coalesced loads, no address depends on a header) in
+                // flight meanwhile.  A spare word names slot 0 three times: zero area, nothing drawn.
+                const bool rule_on = cull_table(prm.tri_flip, s_behind) != nullptr;
+                const bool cones = rule_on && fx > 0.0f && fy > 0.0f && pose_is_rotation(P.R);   // (a quaternion as given may not be a unit one)
+                const float f_lo = fminf(fx, fy), f_hi = fmaxf(fx, fy), c_abs = fabsf(cx) + fabsf(cy);
+                const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+                const int nc = prm.n_clusters, n_waves = kFusedThreads / 64;
+                auto cluster_of = [=](int i) { return (i * n_waves + wave) * G + grp; };   // the wave's i-th cluster
+                auto fetch = [&](int c, float (&v)[3], uint32_t& w) {
+                    const float* sl = prm.cl_slots + (size_t)c * 3 * kClusterSize + lane;
+                    v[0] = sl[0]; v[1] = sl[kClusterSize]; v[2] = sl[2 * kClusterSize];
+                    w = prm.cl_words[(size_t)c * kClusterSize + lane];
+                };
+                for (int base = 0; cluster_of(base) < nc; base += 64) {
+                    const int mine = cluster_of(base + lane);
+                    bool live = mine < nc;
+                    if (live && cones) {
+                        const uint4* hp = reinterpret_cast<const uint4*>(prm.cl_headers + (size_t)mine * kClusterWords);
+                        const uint4 h0 = hp[0], h1 = hp[1], h2 = hp[2], h3 = hp[3];
+                        static_assert(kCwCone == 2 && kCwAxis == 4 && kCwCos == 7 && kCwSin == 8 && kCwCenter == 9 && kCwRadius == 12 &&
+                                      kCwAreaMin == 13 && kCwEdgeMax == 14, "the header words as they are unpacked here");
+                        if (h0.z && cluster_faces_away(__uint_as_float(h1.x), __uint_as_float(h1.y), __uint_as_float(h1.z), __uint_as_float(h1.w),
+                                                       __uint_as_float(h2.x), __uint_as_float(h2.y), __uint_as_float(h2.z), __uint_as_float(h2.w),
+                                                       __uint_as_float(h3.x), __uint_as_float(h3.y), __uint_as_float(h3.z), P.R, P.t, f_lo, f_hi, c_abs))
+                            live = false;
+                    }
+                    unsigned long long todo = __ballot(live);
+                    if (!todo) continue;
+                    float v[3];
+                    uint32_t w;
+                    fetch(cluster_of(base + (int)__builtin_ctzll(todo)), v, w);
+                    while (todo) {
+                        todo &= todo - 1;
+                        float v_n[3] = {v[0], v[1], v[2]};
+                        uint32_t w_n = w;
+                        if (todo) fetch(cluster_of(base + (int)__builtin_ctzll(todo)), v_n, w_n);
+                        float sx, sy, z;
+                        project_vertex(v, P, fx, fy, cx, cy, sx, sy, z);
+                        const int a0 = (int)(w & 63u), a1 = (int)((w >> 6) & 63u), a2 = (int)((w >> 12) & 63u);
+                        const float x0 = __shfl(sx, a0, 64), y0 = __shfl(sy, a0, 64), z0 = __shfl(z, a0, 64);
+                        const float x1 = __shfl(sx, a1, 64), y1 = __shfl(sy, a1, 64), z1 = __shfl(z, a1, 64);
+                        const float x2 = __shfl(sx, a2, 64), y2 = __shfl(sy, a2, 64), z2 = __shfl(z, a2, 64);
+                        raster_projected(x0, y0, z0, x1, y1, z1, x2, y2, z2, tw, th, js, je, rule_on ? 1 + (int)((w >> 18) & 1u) : 0, store);
+                        v[0] = v_n[0]; v[1] = v_n[1]; v[2] = v_n[2];
+                        w = w_n;
+                    }
+                }
             }
             __syncthreads();
             UTICK(2);
@@ -657,8 +739,11 @@ __global__ __launch_bounds__(kFusedThreads) void outlier_fused_kernel(EngineArra
 static std::atomic<int> g_outlier_split{-1};   // roft_debug_outlier_split
 void set_outlier_split(int mode) { g_outlier_split.store(mode < 0 ? -1 : (mode ? 1 : 0), std::memory_order_relaxed); }
 
-void launch_outlier(const EngineArrays& a, int lin, hipStream_t s, hipEvent_t stop, const OutlierLaunchOpts* opts)
+int launch_outlier(const EngineArrays& a, int lin, hipStream_t s, hipEvent_t stop, const OutlierLaunchOpts* opts)
 {
+    // (the contract kernel walks clusters only: a mesh without them would be drawn as nothing, silently)
+    if (!(opts && opts->render_mode == ROFT_RENDER_GL) && a.meshes_without_clusters > 0)
+        return host::fail(ROFT_ERR_STATE, "outlier test: a mesh went up without clusters (MeshLayout::kWalkClusters)");
     // objects that do not test this frame return immediately; the decision (ROFTFilter.cpp:581-583) is taken by the
     // pose chain segment that follows (ukf_chain_kernel)
     const size_t lds_total = kRasterLdsBudget;
@@ -666,10 +751,11 @@ void launch_outlier(const EngineArrays& a, int lin, hipStream_t s, hipEvent_t st
     // render mode: the GL numerics keep an 8-byte key per window pixel (outlier_fused_kernel<true>), the contract a 4-byte depth
     const bool gl = opts && opts->render_mode == ROFT_RENDER_GL;
     const size_t zb = gl ? 8 : 4;
-    // cache the projected vertices when they leave room for a window of 8 k pixels (a window that large or larger is
-    // rendered in strips) and for the widest row of the target
+    // GL: cache the projected vertices when they leave room for a window of 8 k pixels (a window that large or larger is
+    // rendered in strips) and for the widest row of the target.  The contract render walks clusters and caches nothing: its
+    // LDS is the window alone.
     const size_t min_win = zb * std::max(8192, a.tile_w);
-    const bool cache = vbytes + min_win <= lds_total && !(opts && opts->no_vertex_cache);
+    const bool cache = gl && vbytes + min_win <= lds_total && !(opts && opts->no_vertex_cache);
     const int vcache_cap = cache ? a.max_verts : 0;
     int win_cap = (int)((lds_total - (cache ? vbytes : 0)) / zb);
     (void)set_max_dynamic_lds(gl ? reinterpret_cast<const void*>(outlier_fused_kernel<true>) : reinterpret_cast<const void*>(outlier_fused_kernel<false>),
@@ -699,6 +785,7 @@ void launch_outlier(const EngineArrays& a, int lin, hipStream_t s, hipEvent_t st
     else
         hipExtLaunchKernelGGL(outlier_fused_kernel<false>, dim3(2 * parts * ((a.n_obj + 7) / 8) * 8), dim3(kFusedThreads), (uint32_t)lds, s, nullptr, stop, 0, a,
                               lin, vcache_cap, win_cap, parts, split, opts ? opts->tile_dump : nullptr);
+    return ROFT_OK;
 }
 
 void launch_outlier_only(const EngineArrays& a, hipStream_t s)

@@ -32,12 +32,15 @@ bool classify_mesh(const float* verts, int n_verts, const int32_t* tris, int n_t
 // arithmetic depends on it), reordered so that triangles whose outward normals point alike are neighbours (24 direction
 // buckets: cube face x 2 x 2).  The render's result does not depend on the order (nearest depth per pixel); the order decides
 // which triangles share a wave, and a wave whose 64 triangles all face away is skipped whole.  order[k] = index of the
-// triangle walked k-th.
-void facing_coherent_order(const float* verts, const int32_t* tris, int n_tris, const std::vector<uint8_t>& flip, std::vector<int32_t>& order);
+// triangle walked k-th; bucket_of (optional): the direction bucket, 0 .. 23, of every triangle in the CALLER's order.
+void facing_coherent_order(const float* verts, const int32_t* tris, int n_tris, const std::vector<uint8_t>& flip, std::vector<int32_t>& order,
+                           std::vector<uint8_t>* bucket_of = nullptr);
 
-// The three layouts in which a mesh goes up.  A mesh that is not closed goes up as the caller's triangles, without flip bits, in all three.
+// The layouts in which a mesh goes up.  A mesh that is not closed goes up as the caller's triangles, without flip bits, in all of them.
 enum class MeshLayout {
-    kWalkOrder,     // closed: the triangles in the facing-coherent order, flip bits in that order (the engine's contract render, the operators)
+    kWalkOrder,     // closed: the triangles in the facing-coherent order, flip bits in that order (the operators that walk `tris`)
+    kWalkClusters,  // kWalkOrder, and the device copy also holds those triangles as clusters (mesh_clusters.h): every mesh the contract
+                    // render of the outlier test draws -- that kernel walks the clusters and nothing else
     kCallersOrder,  // closed: the caller's triangles, flip bits in the caller's order (the scene renderer: a key's triangle index is the caller's)
     kAsItIs,        // never classified: the caller's triangles, no flip bits (the GL render mode draws every triangle, ties by the caller's order)
 };
@@ -45,6 +48,7 @@ struct PreparedMesh {
     bool closed = false;
     std::vector<int32_t> reordered;   // 3 x n_tris: closed meshes in walk order only
     std::vector<uint8_t> flip;        // n_tris: closed meshes only, in the order of tris()
+    std::vector<uint8_t> bucket;      // n_tris: closed meshes in walk order only, the direction bucket of every triangle of tris() (mesh_clusters.h)
     const int32_t* tris(const int32_t* callers) const { return reordered.empty() ? callers : reordered.data(); }
 };
 void prepare_mesh(const float* verts, int n_verts, const int32_t* tris, int n_tris, MeshLayout layout, PreparedMesh& out);

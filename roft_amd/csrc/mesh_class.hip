@@ -118,7 +118,8 @@ bool classify_mesh(const float* verts, int n_verts, const int32_t* tris, int n_t
     return true;
 }
 
-void facing_coherent_order(const float* verts, const int32_t* tris, int n_tris, const std::vector<uint8_t>& flip, std::vector<int32_t>& order)
+void facing_coherent_order(const float* verts, const int32_t* tris, int n_tris, const std::vector<uint8_t>& flip, std::vector<int32_t>& order,
+                           std::vector<uint8_t>* bucket_of)
 {
     order.resize((size_t)std::max(n_tris, 0));
     std::vector<int> key((size_t)std::max(n_tris, 0));
@@ -138,6 +139,7 @@ void facing_coherent_order(const float* verts, const int32_t* tris, int n_tris, 
         order[t] = t;
     }
     std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return key[a] < key[b]; });
+    if (bucket_of) bucket_of->assign(key.begin(), key.end());
 }
 
 void prepare_mesh(const float* verts, int n_verts, const int32_t* tris, int n_tris, MeshLayout layout, PreparedMesh& out)
@@ -145,19 +147,23 @@ void prepare_mesh(const float* verts, int n_verts, const int32_t* tris, int n_tr
     out.closed = false;
     out.reordered.clear();
     out.flip.clear();
+    out.bucket.clear();
     if (layout == MeshLayout::kAsItIs) return;
     std::vector<uint8_t> flip;
     out.closed = classify_mesh(verts, n_verts, tris, n_tris, flip);
     if (!out.closed) return;
     if (layout == MeshLayout::kCallersOrder) { out.flip.swap(flip); return; }
     std::vector<int32_t> order;
-    facing_coherent_order(verts, tris, n_tris, flip, order);
+    std::vector<uint8_t> bucket_of;
+    facing_coherent_order(verts, tris, n_tris, flip, order, &bucket_of);
     out.reordered.resize((size_t)3 * n_tris);
     out.flip.resize((size_t)n_tris);
+    out.bucket.resize((size_t)n_tris);
     for (int k = 0; k < n_tris; ++k) {
         const int32_t t = order[k];
         for (int q = 0; q < 3; ++q) out.reordered[(size_t)3 * k + q] = tris[(size_t)3 * t + q];
         out.flip[k] = flip[t];
+        out.bucket[k] = bucket_of[t];
     }
 }
 

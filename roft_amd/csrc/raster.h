@@ -170,6 +170,50 @@ __device__ __forceinline__ void project_mesh(const float* verts, int nv, bool ca
     }
 }
 
+// project_mesh's two results -- the box and `behind` -- from the eight corners of the mesh's axis-aligned box instead of all its
+// vertices.  Called by a whole wave; every lane holds corner (lane & 7) in `corner`.  True: no vertex of the mesh is behind the
+// near plane (the caller leaves *s_behind 0) and box = {i0, j0, i1, j1}, in project_mesh's format, CONTAINS the box project_mesh
+// would have found: the same triangles then leave the same depths at the same pixels, and the pixels this box adds stay empty.
+// False: the corners do not settle it, the caller runs project_mesh.
+// Why.  A vertex is a convex combination of the corners.  Its exact depth is affine in it, so at least the smallest exact corner
+// depth; with all depths positive its exact screen coordinates lie between the corners' extremes (a perspective projection maps
+// the box onto the convex hull of its projected corners).  The float values differ from the exact ones by rounding: the three-term
+// sums of project_vertex err by less than 4e-7 x the sum of their terms' magnitudes, which for a vertex is at most the largest
+// such sum `mag` among the corners (a sum of absolute values of affine functions is convex).  Hence
+//   * behind: every float corner depth > 0.01 -- ten times the near plane -- and above 0.001 by more than 1e-6 mag (2 x 4e-7, rounded
+//     up; far beyond 0.009 only for coordinates of tens of kilometres) => every float vertex depth > 0.001;
+//   * box: a screen coordinate s = (f X) (1 / z) + c errs by less than px_err = 1e-6 (f (mag / z) (1 + mag / z) + |c|) (seven roundings,
+//     each relative 6e-8, on X, z, the reciprocal, two products and the sum).  While px_err < 1/4 a vertex' float coordinate is no more
+//     than half a pixel outside the float corners' range, and ceil(s - 1/2) / floor(s - 1/2) move by at most one: the corners'
+//     bounds widened by one pixel, then clamped to the target as project_mesh clamps.
+__device__ __forceinline__ bool corner_box_settles(const float* corner, const RenderPose& P, float fx, float fy, float cx, float cy, int w,
+                                                   int h, int* box)
+{
+    float sx, sy, z;
+    project_vertex(corner, P, fx, fy, cx, cy, sx, sy, z);
+    float mag = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+        mag = fmaxf(mag, ((fabsf(P.R[3 * r] * corner[0]) + fabsf(P.R[3 * r + 1] * corner[1])) + fabsf(P.R[3 * r + 2] * corner[2])) + fabsf(P.t[r]));
+    float mag_max = mag, z_min = z;   // (fminf / fmaxf drop a NaN: the lane that holds it fails its own test below)
+    for (int off = 1; off < 8; off <<= 1) {
+        mag_max = fmaxf(mag_max, __shfl_xor(mag_max, off, 64));
+        z_min = fminf(z_min, __shfl_xor(z_min, off, 64));
+    }
+    const float q = mag_max / z_min;
+    const float px_err = 1e-6f * (fmaxf(fabsf(fx), fabsf(fy)) * q * (1.0f + q) + (fabsf(cx) + fabsf(cy)));
+    const bool good = z > 0.01f && (z - 0.001f) > 1e-6f * mag_max && px_err < 0.25f && (mag == mag);
+    if (!__all(good)) return false;
+    int bi0 = (int)fminf(fmaxf(ceilf(sx - 0.5f) - 1.0f, 0.0f), (float)w), bi1 = (int)fminf(fmaxf(floorf(sx - 0.5f) + 1.0f, -1.0f), (float)(w - 1));
+    int bj0 = (int)fminf(fmaxf(ceilf(sy - 0.5f) - 1.0f, 0.0f), (float)h), bj1 = (int)fminf(fmaxf(floorf(sy - 0.5f) + 1.0f, -1.0f), (float)(h - 1));
+    for (int off = 1; off < 8; off <<= 1) {
+        bi0 = min(bi0, __shfl_xor(bi0, off, 64)); bi1 = max(bi1, __shfl_xor(bi1, off, 64));
+        bj0 = min(bj0, __shfl_xor(bj0, off, 64)); bj1 = max(bj1, __shfl_xor(bj1, off, 64));
+    }
+    box[0] = bi0; box[1] = bj0; box[2] = bi1; box[3] = bj1;
+    return true;
+}
+
 // The projected corners of a triangle: from the cache project_mesh filled, else through `project` again.
 // (Callers read cull_code BEFORE the fetch, so that the flip table's load is in flight with the corners': read behind the fetch it
 //  cost quality_kernel and pose_silhouette_kernel 3 us of 135 per launch, docs/notebook.md.)

@@ -72,6 +72,14 @@ struct ObjParams {
     // from outside; null: the mesh is not a closed orientable surface and every triangle is drawn.  (`tris` of a closed mesh is
     // in the facing-coherent walk order, tri_flip follows it.)
     const uint8_t* tri_flip;
+    // the same triangles as clusters of one wave's work (mesh_clusters.h; the contract render of the outlier test walks these and
+    // none of the arrays above): headers (16 words each), vertex slots (x[64] | y[64] | z[64] each), triangle words (64 each), and
+    // the eight corners of the mesh's axis-aligned box.  n_clusters = 0: the upload made none (no outlier test draws this mesh).
+    const uint32_t* cl_headers;
+    const float* cl_slots;
+    const uint32_t* cl_words;
+    const float* box_corners;
+    int n_clusters;
 };
 
 // compact flow measurement record (what the SKF kernel consumes)
@@ -234,6 +242,7 @@ struct EngineArrays {
     size_t plane_words;      // wpr*H
     int tile_w, tile_h;
     int max_tris, max_verts; // largest mesh among the objects
+    int meshes_without_clusters;   // objects whose mesh went up without clusters (MeshLayout::kWalkClusters): the contract render of the outlier test refuses to run
     double ukf_chol_guard;      // roft_config::ukf_cholesky_guard (0: always the eigen-decomposition)
     double ukf_chol_guard_bil;  // roft_config::ukf_cholesky_guard_bilinear
     roft_object_output* out_log;  // [log_cap][n_obj] per-frame outputs, or null
@@ -484,14 +493,15 @@ void launch_features(const EngineArrays& a, hipStream_t s, hipEvent_t stop = nul
 // the engine's kernel through every configuration); the engine passes none.
 struct OutlierLaunchOpts {
     int parts = 0;            // horizontal bands per alternative (0: by the CUs to spare, -d: that count / d)
-    int no_vertex_cache = 0;  // project the vertices per triangle instead of once into LDS
+    int no_vertex_cache = 0;  // GL render mode: project the vertices per triangle instead of once into LDS (the contract render has no cache)
     int window_pixels = 0;    // cap of the LDS depth window in pixels (> 0: forces the strip path for larger windows)
     float* tile_dump = nullptr;   // [2][tile_h][tile_w], zero-filled: receives the rendered window of both alternatives
     int split = -1;           // several workgroups per alternative share its TRIANGLES (1) or only its window's rows (0); -1: the default (triangles)
     int render_mode = ROFT_RENDER_CONTRACT;   // ROFT_RENDER_GL: the reference's GL numerics, every triangle drawn in `tris` order (rows split only)
 };
 // render + likelihood of the pending tests of a lane (the decision is the first thing the next pose chain segment does)
-void launch_outlier(const EngineArrays& a, int lin, hipStream_t s, hipEvent_t stop = nullptr, const OutlierLaunchOpts* opts = nullptr);
+// (ROFT_ERR_STATE, nothing launched: the contract render was asked to draw a mesh that went up without clusters)
+int launch_outlier(const EngineArrays& a, int lin, hipStream_t s, hipEvent_t stop = nullptr, const OutlierLaunchOpts* opts = nullptr);
 void set_outlier_split(int mode);   // process-wide override of OutlierLaunchOpts::split (-1: none)
 void launch_outlier_only(const EngineArrays& a, hipStream_t s);  // operator level: likelihood + decision on filled z-buffers
 
