@@ -21,7 +21,8 @@ TWIST_TOL = 1e-6  # m/s, rad/s
 LIK_ENGINE_RTOL = 1e-9
 
 
-def make_engine(streams, **over):
+def make_engine(streams, descs=None, **over):
+    """descs: per object a dict of roft_object_desc fields other than the defaults (tests/filter_time_cases.py), or None"""
     st0 = streams[0]
     cfg = E.default_config(st0.camera.width, st0.camera.height, st0.flow_type, max_objects=len(streams))
     c = st0.camera
@@ -30,11 +31,16 @@ def make_engine(streams, **over):
     for k, v in over.items():
         setattr(cfg, k, v)
     eng = E.ROFTFilterBatch(cfg)
-    for st in streams:
+    for o, st in enumerate(streams):
         d = E.default_object()
         m0 = synth.initial_pose_from_stream(st)
         for i in range(13):
             d.p_mean0[i] = m0[i]
+        for name, v in ((descs[o] if descs else None) or {}).items():
+            a = getattr(d, name)
+            assert len(a) == len(v), name
+            for i, x in enumerate(v):
+                a[i] = x
         eng.add_object(d, *st.mesh)
     return eng
 
@@ -43,16 +49,30 @@ def rot_err(qa, qb):
     return 2.0 * np.arccos(min(1.0, abs(float(np.dot(qa, qb)))))
 
 
-def compare(streams, n_frames, check_masks=True, **over):
+def compare(streams, n_frames, check_masks=True, descs=None, dts=None, withheld=None, report=None, **over):
+    """descs: per object a dict of roft_object_desc fields, given to the engine's object and to that object's oracle tracker.
+    dts[frame, object]: the time steps the engine is fed (<= 0: the oracle is fed sample_time, as roft_frame_input::dt says).
+    withheld: the (frame, object) pairs whose pose neither side is handed.  report: a dict that receives the largest deviations seen
+    (pos, rot, twist, lik) and the oracle's rows (ref)."""
     from oracle import binding as ob
-    ref = [util.run_oracle_tracker(ob, st, n_frames, **over) for st in streams]
-    eng = make_engine(streams, **over)
+    if descs is None and dts is None and withheld is None:
+        ref = [util.run_oracle_tracker(ob, st, n_frames, **over) for st in streams]
+    else:
+        import filter_time_cases as ftc
+        sample_time = over.get("sample_time", E.default_config(320, 240).sample_time)
+        ref = [ftc.run_oracle(ob, st, n_frames, descs[o] if descs else None, None if dts is None else ftc.oracle_dt(dts[:, o], sample_time),
+                              [k for k, oo in (withheld or ()) if oo == o], **over) for o, st in enumerate(streams)]
+    eng = make_engine(streams, descs, **over)
     n_tests = 0
+    dev = report if report is not None else {}
+    dev.update(pos=0.0, rot=0.0, twist=0.0, lik=0.0, ref=ref)
     for k in range(n_frames):
         frames = []
-        for st in streams:
+        for o, st in enumerate(streams):
             depth, flow, mask, pose = util.frame_inputs(st, k)
-            frames.append(dict(depth=depth, flow=flow, mask=mask, pose=pose, dt=st.dt))
+            if withheld and (k, o) in withheld:
+                pose = None
+            frames.append(dict(depth=depth, flow=flow, mask=mask, pose=pose, dt=st.dt if dts is None else float(dts[k, o])))
         eng.submit(frames)
         eng.step()
         outs = eng.outputs()
@@ -63,8 +83,12 @@ def compare(streams, n_frames, check_masks=True, **over):
             assert got.outlier_selected == exp["sel"], (k, o, list(got.outlier_L), exp["L"])
             if exp["sel"] >= 0:
                 n_tests += 1
+                dev["lik"] = max(dev["lik"], float(np.abs(np.array(got.outlier_L) / exp["L"] - 1.0).max()) if np.all(exp["L"] != 0) else 0.0)
                 np.testing.assert_allclose(np.array(got.outlier_L), exp["L"], rtol=LIK_ENGINE_RTOL)
             pose = np.array(got.pose)
+            dev["pos"] = max(dev["pos"], float(np.abs(pose[:9] - exp["pose"][:9]).max()))
+            dev["rot"] = max(dev["rot"], rot_err(pose[9:], exp["pose"][9:]))
+            dev["twist"] = max(dev["twist"], float(np.abs(np.array(got.twist) - exp["twist"]).max()))
             np.testing.assert_allclose(pose[:9], exp["pose"][:9], rtol=0, atol=POS_TOL, err_msg="frame %d obj %d" % (k, o))
             assert rot_err(pose[9:], exp["pose"][9:]) < ROT_TOL, (k, o)
             np.testing.assert_allclose(np.array(got.twist), exp["twist"], rtol=0, atol=TWIST_TOL)

@@ -97,13 +97,16 @@ def to_device(st):
 
 
 def device_frame(st, k):
-    """roft_frame_input of frame k for a stream returned by to_device()."""
+    """roft_frame_input of frame k for a stream returned by to_device().  A stream that carries `dt_frames` (one time step per
+    frame: tests/filter_time_cases.py) hands those instead of its constant dt."""
     from roft_amd import _lib as L
     mi = st.mask_delivery[k]
     pose = (st.pose_meas[k, :3], st.pose_meas[k, 3:]) if st.pose_valid[k] else None
     i = st.image(k)
+    dts = getattr(st, "dt_frames", None)
     return dict(depth=st.depth[i].data_ptr(), flow=st.flow[i].data_ptr() if st.flow_valid[k] else None,
-                mask=st.mask_gt[mi].data_ptr() if mi >= 0 else None, pose=pose, dt=st.dt, mem_kind=L.MEM_DEVICE)
+                mask=st.mask_gt[mi].data_ptr() if mi >= 0 else None, pose=pose, dt=st.dt if dts is None else float(dts[k]),
+                mem_kind=L.MEM_DEVICE)
 
 
 def run_engine_logged(make_engine, streams, n, T=1, splits=None, **over):
