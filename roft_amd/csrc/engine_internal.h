@@ -9,8 +9,10 @@
 //                       from counters before anything is enqueued (host-only C++, tested without a GPU)
 //   engine_step.hip     roft_step / roft_sync: step_batch enqueues a BatchPlan on the engine's four streams; the timing marks
 //   engine_results.hip  state, outputs, log, masks, timing and batch-trace readers
-//   engine_ops.hip      the operator-level entry points (one-object context: roft_flow_measurement ... roft_outlier_test, roft_pose_errors)
-//   engine_quality.hip  track quality: roft_engine_enable_quality / _get_quality, roft_track_quality, the batch's quality launch
+//   op_context.h        the ONE context of the operator-level entry points: it owns device memory, a stream and a mutex, never settings --
+//                       the entry (lock, device, stream), the one-object arrays derived by value, typed scratch, the state's landing block
+//   engine_ops.hip      the operator-level entry points on that context (roft_flow_measurement ... roft_outlier_test, roft_pose_errors)
+//   engine_quality.hip  track quality: roft_engine_enable_quality / _get_quality, the batch's quality launch; roft_track_quality (on op_context.h)
 //   engine_debug.hip    roft_debug_* (diagnostics and experiments)
 //   scene.hip           the scene renderer: roft_scene_renderer_*, roft_render_scene
 //   mesh_class.h        a caller's mesh on the host: has_mesh, the array check, classification, the three upload layouts (host-only C++)

@@ -1,71 +1,15 @@
-// engine_ops.hip -- the operator-level entry points of include/roft_engine.h (section 1): each runs the engine's own kernels on a
-// private one-object context on device 0.
-#include "engine_internal.h"
+// engine_ops.hip -- the operator-level entry points of include/roft_engine.h (section 1): each runs the engine's own kernels on the
+// one-object context of op_context.h.  An entry point checks its arguments, enters the context once, derives its arrays by value and
+// leaves nothing behind.
+#include "op_context.h"
 
-// =================================================================================================
-// operator level: one-object context on device 0
-// =================================================================================================
-namespace {
-
-struct OpCtx {
-    std::mutex mu;
-    hipStream_t stream = nullptr;
-    Arrays arr;
-    int W = 0, H = 0, ftype = 0, fgrid = 0, radius = 0;
-    DevBuf<unsigned char> b0, b1, b2, b3, b4, b5;  // generic scratch
-    DeviceMesh mesh;                               // the mesh of the last outlier test / depth render
-    bool ready = false;
-
-    int prepare(const roft_camera& cam, int ftype_, int fgrid_, float fscale, int radius_)
-    {
-        if (roft_device_count() <= 0) return fail(ROFT_ERR_DEVICE, "no HIP device (libroft_hip has no CPU path)");
-        if (int rc = check_geometry(cam.width, cam.height)) return rc;
-        HIP_TRY(hipSetDevice(0));
-        (void)hipGetLastError();   // a stale error of another library on this thread is not this call's
-        if (!stream) HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        DevFlowFmt ff;
-        ff.type = ftype_;
-        ff.grid = std::max(fgrid_, 1);
-        ff.cols = cam.width / ff.grid;
-        ff.rows = cam.height / ff.grid;
-        ff.scale = fscale;
-        if (!ready || W != cam.width || H != cam.height || radius != radius_) {
-            if (int rc = arr.alloc(1, 1, make_cam(cam), ff, std::max(radius_, 1))) return rc;
-            W = cam.width; H = cam.height; radius = radius_;
-            ready = true;
-        }
-        arr.a.cam = make_cam(cam);
-        arr.a.ffmt = ff;
-        arr.a.n_obj = 1;
-        arr.a.T = 1;
-        ObjState st;
-        init_state(st);
-        HIP_TRY(hipMemcpyAsync(arr.state.p, &st, sizeof(st), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        return ROFT_OK;
-    }
-};
-
-OpCtx& op()
+OpContext& roft::host::op_context()
 {
-    static OpCtx c;
+    static OpContext c;
     return c;
 }
 
-int upload_ctrl(OpCtx& c, const FrameCtrl& fc)
-{
-    HIP_TRY(hipMemcpyAsync(c.arr.ctrl.p, &fc, sizeof(fc), hipMemcpyHostToDevice, c.stream));
-    HIP_TRY(hipStreamSynchronize(c.stream));  // fc lives on the caller's stack
-    return ROFT_OK;
-}
-
-template <class T>
-int to_dev(DevBuf<unsigned char>& b, const T* src, size_t count, hipStream_t s)
-{
-    HIP_TRY(b.ensure(std::max<size_t>(count * sizeof(T), 16)));
-    if (count) HIP_TRY(hipMemcpyAsync(b.p, src, count * sizeof(T), hipMemcpyHostToDevice, s));
-    return ROFT_OK;
-}
+namespace {
 
 // ROFT_POSE_ERRORS_FMA=0: the nearest-neighbour search squares and adds in the oracle's operation order (9 fp64 operations per
 // pair instead of 7); read once per process
@@ -112,11 +56,33 @@ int roft::host::pose_errors_run(PoseErrorScratch& sc, int kind, const double* d_
 }
 
 namespace {
-PoseErrorScratch& op_pose_scratch()
+
+// The velocity filter's operators on plain arrays: x, P and the operator's diagonal go up as one block, `launch(c, in, out)` uploads
+// what else it needs and launches, x, P and the status come back.
+struct KfBlock { double x[6], P[36], diag[6]; int status; };
+
+template <class Launch>
+int op_kf(const double x[6], const double P[36], const double* diag, int n_diag, double x_out[6], double P_out[36], int* status_out, Launch&& launch)
 {
-    static PoseErrorScratch sc;
-    return sc;
+    OpContext& c = op_context();
+    std::unique_lock<std::mutex> lk;
+    TRY(c.enter(lk));
+    KfBlock h{}, *in, *out;
+    std::memcpy(h.x, x, sizeof(h.x));
+    std::memcpy(h.P, P, sizeof(h.P));
+    std::memcpy(h.diag, diag, sizeof(double) * n_diag);
+    TRY(c.upload(0, &h, 1, &in));
+    TRY(c.room(1, 1, &out));
+    TRY(launch(c, in, out));
+    HIP_TRY(hipMemcpyAsync(&h, out, sizeof(h), hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));   // (also keeps what `launch` uploaded alive until it has been read)
+    HIP_TRY(hipGetLastError());
+    std::memcpy(x_out, h.x, sizeof(h.x));
+    std::memcpy(P_out, h.P, sizeof(h.P));
+    if (status_out) *status_out = h.status;
+    return ROFT_OK;
 }
+
 }  // namespace
 
 extern "C" {
@@ -126,113 +92,77 @@ int roft_flow_measurement(const roft_camera* cam, const uint8_t* prev_mask, cons
                           int32_t* uv, double* y, double* H, int* n_out)
 {
     if (!cam || !prev_mask || !prev_depth || !flow || !flow->data || !n_out) return fail(ROFT_ERR_INVALID, "null argument");
-    OpCtx& c = op();
-    std::lock_guard<std::mutex> lk(c.mu);
     const int r = (int)(size_t)radius;
     if (r <= 0) return fail(ROFT_ERR_INVALID, "radius must be >= 1");
-    if (int rc = c.prepare(*cam, flow->type, flow->grid, flow->scale, r)) return rc;
+    OpContext& c = op_context();
+    std::unique_lock<std::mutex> lk;
+    TRY(c.enter(lk));
+    EngineArrays a;
+    TRY(c.one_object(*cam, flow, r, 0, &a));
     const size_t npix = (size_t)cam->width * cam->height;
-    if (int rc = to_dev(c.b0, prev_mask, npix, c.stream)) return rc;
-    if (int rc = to_dev(c.b1, prev_depth, npix, c.stream)) return rc;
-    if (int rc = to_dev(c.b2, (const unsigned char*)flow->data, flow_bytes(c.arr.a.ffmt), c.stream)) return rc;
+    uint8_t* d_mask;
+    float* d_depth;
+    unsigned char* d_flow;
+    TRY(c.upload(0, prev_mask, npix, &d_mask));
+    TRY(c.upload(1, prev_depth, npix, &d_depth));
+    TRY(c.upload(2, static_cast<const unsigned char*>(flow->data), flow_bytes(a.ffmt), &d_flow));
     FrameCtrl fc;
     clear_ctrl(fc);
     fc.dt = dt;
     fc.has_new_mask = 1;
-    fc.new_mask = c.b0.p;
+    fc.new_mask = d_mask;
     fc.slot_prev = kSlotNew;  // the ingested planes are "the previous frame's mask"
     fc.slot_cur = 0;
-    fc.depth_prev = reinterpret_cast<const float*>(c.b1.p);
-    fc.flow[0] = c.b2.p;
+    fc.depth_prev = d_depth;
+    fc.flow[0] = d_flow;
     fc.vel_stage = 1;
-    if (int rc = upload_ctrl(c, fc)) return rc;
-    launch_mask_ingest(c.arr.a, 0, c.stream);
-    launch_flow_measure(c.arr.a, depth_max, r, c.stream);
+    init_state(c.st);
+    TRY(c.begin_object(a, nullptr, fc));
+    launch_mask_ingest(a, 0, c.stream);
+    launch_flow_measure(a, depth_max, r, c.stream);
     int n = 0;
-    HIP_TRY(hipMemcpyAsync(&n, c.arr.a.npts, sizeof(int), hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipMemcpyAsync(&n, a.npts, sizeof(int), hipMemcpyDeviceToHost, c.stream));
     HIP_TRY(hipStreamSynchronize(c.stream));
     HIP_TRY(hipGetLastError());
     *n_out = n;
     if (n > capacity) return fail(ROFT_ERR_CAPACITY, "more flow points than the caller's capacity");
     if (n > 0 && uv && y && H) {
-        HIP_TRY(c.b3.ensure(sizeof(int32_t) * 2 * n));
-        HIP_TRY(c.b4.ensure(sizeof(double) * 2 * n));
-        HIP_TRY(c.b5.ensure(sizeof(double) * 12 * n));
-        launch_expand_yh(c.arr.a.recs, c.arr.a.npts, c.arr.a.cam, dt, reinterpret_cast<int32_t*>(c.b3.p),
-                         reinterpret_cast<double*>(c.b4.p), reinterpret_cast<double*>(c.b5.p), n, c.stream);
-        HIP_TRY(hipMemcpyAsync(uv, c.b3.p, sizeof(int32_t) * 2 * n, hipMemcpyDeviceToHost, c.stream));
-        HIP_TRY(hipMemcpyAsync(y, c.b4.p, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, c.stream));
-        HIP_TRY(hipMemcpyAsync(H, c.b5.p, sizeof(double) * 12 * n, hipMemcpyDeviceToHost, c.stream));
+        int32_t* d_uv;
+        double *d_y, *d_H;
+        TRY(c.room(3, (size_t)2 * n, &d_uv));
+        TRY(c.room(4, (size_t)2 * n, &d_y));
+        TRY(c.room(5, (size_t)12 * n, &d_H));
+        launch_expand_yh(a.recs, a.npts, a.cam, dt, d_uv, d_y, d_H, n, c.stream);
+        HIP_TRY(hipMemcpyAsync(uv, d_uv, sizeof(int32_t) * 2 * n, hipMemcpyDeviceToHost, c.stream));
+        HIP_TRY(hipMemcpyAsync(y, d_y, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, c.stream));
+        HIP_TRY(hipMemcpyAsync(H, d_H, sizeof(double) * 12 * n, hipMemcpyDeviceToHost, c.stream));
         HIP_TRY(hipStreamSynchronize(c.stream));
     }
-    // leave the one-object context clean for the next call
-    ObjState st;
-    init_state(st);
-    HIP_TRY(hipMemcpy(c.arr.state.p, &st, sizeof(st), hipMemcpyHostToDevice));
-    return ROFT_OK;
-}
-
-static int op_simple_prepare(OpCtx& c)
-{
-    if (roft_device_count() <= 0) return fail(ROFT_ERR_DEVICE, "no HIP device (libroft_hip has no CPU path)");
-    HIP_TRY(hipSetDevice(0));
-    (void)hipGetLastError();   // a stale error of another library on this thread is not this call's
-    if (!c.stream) HIP_TRY(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
     return ROFT_OK;
 }
 
 int roft_kf_predict(const double x[6], const double P[36], const double Qdiag[6], double x_out[6], double P_out[36])
 {
     if (!x || !P || !Qdiag || !x_out || !P_out) return fail(ROFT_ERR_INVALID, "null argument");
-    OpCtx& c = op();
-    std::lock_guard<std::mutex> lk(c.mu);
-    if (int rc = op_simple_prepare(c)) return rc;
-    double in[48];
-    std::memcpy(in, x, 48);
-    std::memcpy(in + 6, P, 288);
-    std::memcpy(in + 42, Qdiag, 48);
-    if (int rc = to_dev(c.b0, in, 48, c.stream)) return rc;
-    HIP_TRY(c.b1.ensure(sizeof(double) * 42));
-    double* d = reinterpret_cast<double*>(c.b0.p);
-    double* o = reinterpret_cast<double*>(c.b1.p);
-    launch_kf_predict(d, d + 6, d + 42, o, o + 6, c.stream);
-    double out[42];
-    HIP_TRY(hipMemcpyAsync(out, o, sizeof(out), hipMemcpyDeviceToHost, c.stream));
-    HIP_TRY(hipStreamSynchronize(c.stream));
-    std::memcpy(x_out, out, 48);
-    std::memcpy(P_out, out + 6, 288);
-    return ROFT_OK;
+    return op_kf(x, P, Qdiag, 6, x_out, P_out, nullptr, [&](OpContext& c, KfBlock* in, KfBlock* out) -> int {
+        launch_kf_predict(in->x, in->P, in->diag, out->x, out->P, c.stream);
+        return ROFT_OK;
+    });
 }
 
 int roft_skf_correct(const double x_pred[6], const double P_pred[36], int N, const double* y, const double* H,
                      const double Rdiag[2], int reweight, double x_out[6], double P_out[36], int* status_out)
 {
     if (!x_pred || !P_pred || !Rdiag || !x_out || !P_out || (N > 0 && (!y || !H))) return fail(ROFT_ERR_INVALID, "null argument");
-    OpCtx& c = op();
-    std::lock_guard<std::mutex> lk(c.mu);
-    if (int rc = op_simple_prepare(c)) return rc;
-    double in[44];
-    std::memcpy(in, x_pred, 48);
-    std::memcpy(in + 6, P_pred, 288);
-    in[42] = Rdiag[0]; in[43] = Rdiag[1];
-    if (int rc = to_dev(c.b0, in, 44, c.stream)) return rc;
-    const int n = std::max(N, 0);
-    if (int rc = to_dev(c.b1, y, (size_t)2 * n, c.stream)) return rc;
-    if (int rc = to_dev(c.b2, H, (size_t)12 * n, c.stream)) return rc;
-    HIP_TRY(c.b3.ensure(sizeof(double) * 3 * std::max(n, 1)));
-    HIP_TRY(c.b4.ensure(sizeof(double) * 44));
-    double* d = reinterpret_cast<double*>(c.b0.p);
-    double* o = reinterpret_cast<double*>(c.b4.p);
-    launch_skf_arrays(d, d + 6, N, reinterpret_cast<double*>(c.b1.p), reinterpret_cast<double*>(c.b2.p), d + 42, reweight,
-                      reinterpret_cast<double*>(c.b3.p), o, o + 6, reinterpret_cast<int*>(o + 42), c.stream);
-    double out[44];
-    HIP_TRY(hipMemcpyAsync(out, o, sizeof(out), hipMemcpyDeviceToHost, c.stream));
-    HIP_TRY(hipStreamSynchronize(c.stream));
-    HIP_TRY(hipGetLastError());
-    std::memcpy(x_out, out, 48);
-    std::memcpy(P_out, out + 6, 288);
-    if (status_out) std::memcpy(status_out, out + 42, sizeof(int));
-    return ROFT_OK;
+    const size_t n = (size_t)std::max(N, 0);
+    return op_kf(x_pred, P_pred, Rdiag, 2, x_out, P_out, status_out, [&](OpContext& c, KfBlock* in, KfBlock* out) -> int {
+        double *d_y, *d_H, *d_norms;
+        TRY(c.upload(2, y, 2 * n, &d_y));
+        TRY(c.upload(3, H, 12 * n, &d_H));
+        TRY(c.room(4, 3 * std::max<size_t>(n, 1), &d_norms));
+        launch_skf_arrays(in->x, in->P, N, d_y, d_H, in->diag, reweight, d_norms, out->x, out->P, &out->status, c.stream);
+        return ROFT_OK;
+    });
 }
 
 int roft_skf_correct_points(const roft_camera* cam, double dt, const double x_pred[6], const double P_pred[36], int N,
@@ -241,32 +171,16 @@ int roft_skf_correct_points(const roft_camera* cam, double dt, const double x_pr
 {
     if (!cam || !x_pred || !P_pred || !Rdiag || !x_out || !P_out || (N > 0 && (!uv || !z || !flow_xy)))
         return fail(ROFT_ERR_INVALID, "null argument");
-    OpCtx& c = op();
-    std::lock_guard<std::mutex> lk(c.mu);
-    if (int rc = op_simple_prepare(c)) return rc;
-    double in[44];
-    std::memcpy(in, x_pred, 48);
-    std::memcpy(in + 6, P_pred, 288);
-    in[42] = Rdiag[0]; in[43] = Rdiag[1];
-    if (int rc = to_dev(c.b0, in, 44, c.stream)) return rc;
-    const int n = std::max(N, 0);
-    std::vector<FlowRec> recs(n);
-    for (int i = 0; i < n; ++i) recs[i] = FlowRec{uv[2 * i], uv[2 * i + 1], z[i], flow_xy[2 * i], flow_xy[2 * i + 1]};
-    if (int rc = to_dev(c.b1, recs.data(), (size_t)n, c.stream)) return rc;
-    HIP_TRY(c.b3.ensure(sizeof(double) * 3 * std::max(n, 1)));
-    HIP_TRY(c.b4.ensure(sizeof(double) * 44));
-    double* d = reinterpret_cast<double*>(c.b0.p);
-    double* o = reinterpret_cast<double*>(c.b4.p);
-    launch_skf_records(d, d + 6, N, reinterpret_cast<const FlowRec*>(c.b1.p), make_cam(*cam), dt, d + 42, reweight,
-                       reinterpret_cast<double*>(c.b3.p), o, o + 6, reinterpret_cast<int*>(o + 42), c.stream);
-    double out[44];
-    HIP_TRY(hipMemcpyAsync(out, o, sizeof(out), hipMemcpyDeviceToHost, c.stream));
-    HIP_TRY(hipStreamSynchronize(c.stream));   // (also keeps `recs` alive until its upload has been read)
-    HIP_TRY(hipGetLastError());
-    std::memcpy(x_out, out, 48);
-    std::memcpy(P_out, out + 6, 288);
-    if (status_out) std::memcpy(status_out, out + 42, sizeof(int));
-    return ROFT_OK;
+    std::vector<FlowRec> recs((size_t)std::max(N, 0));
+    for (size_t i = 0; i < recs.size(); ++i) recs[i] = FlowRec{uv[2 * i], uv[2 * i + 1], z[i], flow_xy[2 * i], flow_xy[2 * i + 1]};
+    return op_kf(x_pred, P_pred, Rdiag, 2, x_out, P_out, status_out, [&](OpContext& c, KfBlock* in, KfBlock* out) -> int {
+        FlowRec* d_recs;
+        double* d_norms;
+        TRY(c.upload(2, recs.data(), recs.size(), &d_recs));
+        TRY(c.room(4, 3 * std::max<size_t>(recs.size(), 1), &d_norms));
+        launch_skf_records(in->x, in->P, N, d_recs, make_cam(*cam), dt, in->diag, reweight, d_norms, out->x, out->P, &out->status, c.stream);
+        return ROFT_OK;
+    });
 }
 
 int roft_mask_propagate(uint8_t* mask, int W, int H, const roft_flow* flows, int n_flows, int frames_between)
@@ -276,26 +190,30 @@ int roft_mask_propagate(uint8_t* mask, int W, int H, const roft_flow* flows, int
     if (frames_between > 0) start = std::max(0, n_flows - frames_between);
     const int used = n_flows - start;
     if (used > kMaxFlowHist) return fail(ROFT_ERR_INVALID, "more than ROFT_MAX_FLOW_CHASE flow frames per propagation are not supported");
-    OpCtx& c = op();
-    std::lock_guard<std::mutex> lk(c.mu);
-    roft_camera cam{W, H, 1.0, 1.0, 0.0, 0.0};
+    OpContext& c = op_context();
+    std::unique_lock<std::mutex> lk;
+    TRY(c.enter(lk));
+    const roft_camera cam{W, H, 1.0, 1.0, 0.0, 0.0};
     const roft_flow* f0 = used > 0 ? &flows[start] : nullptr;
-    if (int rc = c.prepare(cam, f0 ? f0->type : ROFT_FLOW_F32C2, f0 ? f0->grid : 1, f0 ? f0->scale : 1.0f, 35)) return rc;
+    EngineArrays a;
+    TRY(c.one_object(cam, f0, 35, 0, &a));
     const size_t npix = (size_t)W * H;
-    const size_t fb = flow_bytes(c.arr.a.ffmt);
-    if (int rc = to_dev(c.b0, mask, npix, c.stream)) return rc;
-    HIP_TRY(c.b1.ensure(fb * std::max(used, 1)));
+    const size_t fb = flow_bytes(a.ffmt);
+    uint8_t *d_mask, *d_out;
+    unsigned char* d_flows;
+    TRY(c.upload(0, mask, npix, &d_mask));
+    TRY(c.room(1, fb * std::max(used, 1), &d_flows));
     FrameCtrl fc;
     clear_ctrl(fc);
     for (int j = 0; j < used; ++j) {
         const roft_flow& f = flows[start + j];
         if (f.type != f0->type || f.cols != f0->cols || f.rows != f0->rows || !f.data)
             return fail(ROFT_ERR_INVALID, "all flow frames must share one format");
-        HIP_TRY(hipMemcpyAsync(c.b1.p + fb * j, f.data, fb, hipMemcpyHostToDevice, c.stream));
-        fc.flow[used - 1 - j] = c.b1.p + fb * j;  // [0] = newest
+        HIP_TRY(hipMemcpyAsync(d_flows + fb * j, f.data, fb, hipMemcpyHostToDevice, c.stream));
+        fc.flow[used - 1 - j] = d_flows + fb * j;  // [0] = newest
     }
     fc.has_new_mask = 1;
-    fc.new_mask = c.b0.p;
+    fc.new_mask = d_mask;
     fc.force_mode = 3;
     fc.n_hist = used;
     fc.slot_prev = 1;
@@ -305,18 +223,18 @@ int roft_mask_propagate(uint8_t* mask, int W, int H, const roft_flow* flows, int
     MaskRec rec0[2];
     std::memset(rec0, 0, sizeof(rec0));
     rec0[0].fbuf_n = used;
-    HIP_TRY(hipMemcpyAsync(c.arr.mrec.p, rec0, sizeof(rec0), hipMemcpyHostToDevice, c.stream));
+    HIP_TRY(hipMemcpyAsync(a.mrec, rec0, sizeof(rec0), hipMemcpyHostToDevice, c.stream));
+    a.mrec_carry = a.mrec;   // row 0: rec0[0]
     // the chain kernel ORs into a zeroed destination (inside the engine the frame before leaves it zeroed)
-    HIP_TRY(hipMemsetAsync(c.arr.a.planes + plane_offset(c.arr.a, 0, 0, 0), 0, sizeof(uint32_t) * 2 * c.arr.a.plane_words, c.stream));
-    if (int rc = upload_ctrl(c, fc)) return rc;
-    c.arr.a.mrec_carry = c.arr.mrec.p;   // row 0: rec0[0]
-    launch_mask_reset(c.arr.a, c.stream);
-    launch_mask_ingest(c.arr.a, 0, c.stream);
-    launch_mask_chain(c.arr.a, frames_between, 1, 1u, c.stream);
-    HIP_TRY(c.b2.ensure(npix));
-    launch_planes_to_mask(c.arr.a.planes + plane_offset(c.arr.a, 0, 0, 0), c.arr.a.planes + plane_offset(c.arr.a, 0, 0, 1),
-                          (int)npix, c.b2.p, c.stream);
-    HIP_TRY(hipMemcpyAsync(mask, c.b2.p, npix, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipMemsetAsync(a.planes + plane_offset(a, 0, 0, 0), 0, sizeof(uint32_t) * 2 * a.plane_words, c.stream));
+    init_state(c.st);
+    TRY(c.begin_object(a, nullptr, fc));
+    launch_mask_reset(a, c.stream);
+    launch_mask_ingest(a, 0, c.stream);
+    launch_mask_chain(a, frames_between, 1, 1u, c.stream);
+    TRY(c.room(2, npix, &d_out));
+    launch_planes_to_mask(a.planes + plane_offset(a, 0, 0, 0), a.planes + plane_offset(a, 0, 0, 1), (int)npix, d_out, c.stream);
+    HIP_TRY(hipMemcpyAsync(mask, d_out, npix, hipMemcpyDeviceToHost, c.stream));
     HIP_TRY(hipStreamSynchronize(c.stream));
     HIP_TRY(hipGetLastError());
     return ROFT_OK;
@@ -329,55 +247,49 @@ int roft_labels_to_masks(const void* labels, int label_type, int W, int H, const
     for (int i = 0; i < n; ++i)
         if (values[i] <= 0 || values[i] > (label_type == ROFT_LABEL_U8 ? 255 : 65535))
             return fail(ROFT_ERR_INVALID, "label " + std::to_string(values[i]) + ": 0 is the background, and the value must fit the label type");
-    if (roft_device_count() <= 0) return fail(ROFT_ERR_DEVICE, "no HIP device (libroft_hip has no CPU path)");
-    if (int rc = check_geometry(W, H)) return rc;
-    OpCtx& c = op();
-    std::lock_guard<std::mutex> lk(c.mu);
-    HIP_TRY(hipSetDevice(0));
-    (void)hipGetLastError();
-    if (!c.stream) HIP_TRY(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
+    OpContext& c = op_context();
+    std::unique_lock<std::mutex> lk;
+    TRY(c.enter(lk));
+    TRY(check_geometry(W, H));
     const size_t npix = (size_t)W * H, plane_words = npix / 32;
     // the engine's kernel on a compact layout: object i = value i, one ingest slot, one set
-    DevBuf<unsigned char> d_img, d_tab, d_masks;
-    DevBuf<uint32_t> d_planes;
-    DevBuf<MaskRec> d_rec;
-    HIP_TRY(d_img.ensure(npix * (label_type == ROFT_LABEL_U8 ? 1 : 2)));
-    HIP_TRY(hipMemcpyAsync(d_img.p, labels, npix * (label_type == ROFT_LABEL_U8 ? 1 : 2), hipMemcpyHostToDevice, c.stream));
-    std::vector<unsigned char> tab(sizeof(LabelSet) + sizeof(LabelMember) * (size_t)n);
+    unsigned char *d_img, *d_masks;
+    LabelSet* d_set;
+    LabelMember* d_members;
+    uint32_t* d_planes;
+    MaskRec* d_rec;
+    TRY(c.upload(0, static_cast<const unsigned char*>(labels), npix * (label_type == ROFT_LABEL_U8 ? 1 : 2), &d_img));
     LabelSet set{};
-    set.img = d_img.p; set.type = label_type; set.t = 0; set.first = 0; set.n = n;
-    std::memcpy(tab.data(), &set, sizeof(set));
-    for (int i = 0; i < n; ++i) {
-        const LabelMember m{i, values[i]};
-        std::memcpy(tab.data() + sizeof(LabelSet) + sizeof(LabelMember) * (size_t)i, &m, sizeof(m));
-    }
-    HIP_TRY(d_tab.ensure(tab.size()));
-    HIP_TRY(hipMemcpyAsync(d_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice, c.stream));
-    HIP_TRY(d_planes.ensure((size_t)n * 2 * plane_words));
-    HIP_TRY(d_rec.ensure((size_t)2 * n));
-    HIP_TRY(hipMemsetAsync(d_rec.p, 0, sizeof(MaskRec) * 2 * (size_t)n, c.stream));
+    set.img = d_img; set.type = label_type; set.t = 0; set.first = 0; set.n = n;
+    std::vector<LabelMember> members((size_t)n);
+    for (int i = 0; i < n; ++i) members[i] = LabelMember{i, values[i]};
+    std::vector<MaskRec> rec((size_t)2 * n);
+    TRY(c.upload(1, &set, 1, &d_set));
+    TRY(c.upload(2, members.data(), members.size(), &d_members));
+    TRY(c.room(3, (size_t)n * 2 * plane_words, &d_planes));
+    TRY(c.room(4, rec.size(), &d_rec));
+    HIP_TRY(hipMemsetAsync(d_rec, 0, sizeof(MaskRec) * rec.size(), c.stream));
     LabelIngestArgs la;
-    la.sets = reinterpret_cast<const LabelSet*>(d_tab.p);
-    la.members = reinterpret_cast<const LabelMember*>(d_tab.p + sizeof(LabelSet));
-    la.planes = d_planes.p;
+    la.sets = d_set;
+    la.members = d_members;
+    la.planes = d_planes;
     la.plane_words = plane_words;
     la.obj_stride = 2 * plane_words;
     la.slot0 = 0;
-    la.mrec = d_rec.p;
+    la.mrec = d_rec;
     la.n_obj = n;
     la.n_grp = (int)(npix / 64);
     launch_label_ingest(la, 1, c.stream);
     HIP_TRY(hipGetLastError());
     if (masks_out) {
-        HIP_TRY(d_masks.ensure(npix * (size_t)n));
+        TRY(c.room(5, npix * (size_t)n, &d_masks));
         for (int i = 0; i < n; ++i)
-            launch_planes_to_mask(d_planes.p + (size_t)i * 2 * plane_words, d_planes.p + (size_t)i * 2 * plane_words + plane_words, (int)npix,
-                                  d_masks.p + npix * (size_t)i, c.stream);
-        HIP_TRY(hipMemcpyAsync(masks_out, d_masks.p, npix * (size_t)n, hipMemcpyDeviceToHost, c.stream));
+            launch_planes_to_mask(d_planes + (size_t)i * 2 * plane_words, d_planes + (size_t)i * 2 * plane_words + plane_words, (int)npix,
+                                  d_masks + npix * (size_t)i, c.stream);
+        HIP_TRY(hipMemcpyAsync(masks_out, d_masks, npix * (size_t)n, hipMemcpyDeviceToHost, c.stream));
     }
-    std::vector<MaskRec> rec((size_t)2 * n);
-    HIP_TRY(hipMemcpyAsync(rec.data(), d_rec.p, sizeof(MaskRec) * 2 * (size_t)n, hipMemcpyDeviceToHost, c.stream));
-    HIP_TRY(hipStreamSynchronize(c.stream));
+    HIP_TRY(hipMemcpyAsync(rec.data(), d_rec, sizeof(MaskRec) * rec.size(), hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));   // (set, members and rec live in this call)
     HIP_TRY(hipGetLastError());
     if (counts_out)
         for (int i = 0; i < n; ++i) counts_out[i] = rec[(size_t)n + i].new_count;   // (row t + 1 = 1)
@@ -399,99 +311,90 @@ static int pose_silhouettes(const char* what, const roft_camera* cam, const roft
     if (bands < 0) return fail(ROFT_ERR_INVALID, "bands must be >= 0 (0: the library's choice)");
     if (vertex_cache != 0 && vertex_cache != 1) return fail(ROFT_ERR_INVALID, "vertex_cache must be 0 or 1");
     for (int k = 0; k < n; ++k) TRY(check_mesh(meshes[k], n > 1 ? "mesh " + std::to_string(k) : "mesh", true));
-    if (roft_device_count() <= 0) return fail(ROFT_ERR_DEVICE, "no HIP device (libroft_hip has no CPU path)");
-    if (int rc = check_geometry(cam->width, cam->height)) return rc;
-    OpCtx& c = op();
-    std::lock_guard<std::mutex> lk(c.mu);
-    HIP_TRY(hipSetDevice(0));
-    (void)hipGetLastError();
-    if (!c.stream) HIP_TRY(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
+    OpContext& c = op_context();
+    std::unique_lock<std::mutex> lk;
+    TRY(c.enter(lk));
+    TRY(check_geometry(cam->width, cam->height));
     const DevCamera dc = make_cam(*cam);
     const size_t npix = (size_t)cam->width * cam->height, plane_words = (size_t)dc.wpr * dc.H;
-    std::vector<DeviceMesh> d_meshes((size_t)n);
-    DevBuf<unsigned char> d_mask;
-    DevBuf<uint32_t> d_planes;
-    DevBuf<MaskRec> d_rec;
-    DevBuf<FrameCtrl> d_ctrl;
-    DevBuf<ObjParams> d_prm;
-    DevBuf<unsigned long long> d_zbuf, d_zstats;
-    DevBuf<SilhouettePair> d_zpairs;
-    DevBuf<unsigned char> d_depth;
-    DevBuf<int> d_removed;
-    if (gated)
-        if (int rc = to_dev(d_depth, depth, npix, c.stream)) return rc;
+    if (c.meshes.size() < (size_t)n) c.meshes.resize((size_t)n);
+    float* d_depth = nullptr;
+    FrameCtrl* d_ctrl;
+    ObjParams* d_prm;
+    uint32_t* d_planes;
+    MaskRec* d_rec;
+    if (gated) TRY(c.upload(0, depth, npix, &d_depth));
     std::vector<ObjParams> prm((size_t)n);
     std::vector<FrameCtrl> fc((size_t)n);
+    std::vector<MaskRec> rec((size_t)2 * n);
     std::memset(prm.data(), 0, sizeof(ObjParams) * prm.size());
     int max_verts = 0;
     for (int k = 0; k < n; ++k) {
-        TRY(d_meshes[k].upload(meshes[k], MeshLayout::kWalkOrder, c.stream));
-        d_meshes[k].describe(prm[k]);
-        max_verts = std::max(max_verts, d_meshes[k].n_verts);
+        TRY(c.meshes[k].upload(meshes[k], MeshLayout::kWalkOrder, c.stream));
+        c.meshes[k].describe(prm[k]);
+        max_verts = std::max(max_verts, c.meshes[k].n_verts);
         clear_ctrl(fc[k]);
         fc[k].has_new_mask = 1;
         fc[k].label_type = kMaskFromPose;
         fc[k].label = n > 1 ? 1 : 0;   // (z-buffer 0 of the frame)
-        fc[k].gate_depth = gated ? reinterpret_cast<const float*>(d_depth.p) : nullptr;
+        fc[k].gate_depth = d_depth;
         for (int i = 0; i < 3; ++i) fc[k].pose_x[i] = x[3 * k + i];
         for (int i = 0; i < 4; ++i) fc[k].pose_q[i] = q[4 * k + i];
     }
-    HIP_TRY(d_ctrl.ensure((size_t)n));
-    HIP_TRY(d_prm.ensure((size_t)n));
-    HIP_TRY(d_planes.ensure((size_t)n * 2 * plane_words));
-    HIP_TRY(d_rec.ensure((size_t)2 * n));
-    HIP_TRY(hipMemcpyAsync(d_ctrl.p, fc.data(), sizeof(FrameCtrl) * n, hipMemcpyHostToDevice, c.stream));
-    HIP_TRY(hipMemcpyAsync(d_prm.p, prm.data(), sizeof(ObjParams) * n, hipMemcpyHostToDevice, c.stream));
-    HIP_TRY(hipMemsetAsync(d_planes.p, 0xA5, sizeof(uint32_t) * (size_t)n * 2 * plane_words, c.stream));   // (stale words, as an engine's ingest slot holds)
-    HIP_TRY(hipMemsetAsync(d_rec.p, 0, sizeof(MaskRec) * 2 * n, c.stream));
+    TRY(c.upload(1, fc.data(), fc.size(), &d_ctrl));
+    TRY(c.upload(2, prm.data(), prm.size(), &d_prm));
+    TRY(c.room(3, (size_t)n * 2 * plane_words, &d_planes));
+    TRY(c.room(4, rec.size(), &d_rec));
+    HIP_TRY(hipMemsetAsync(d_planes, 0xA5, sizeof(uint32_t) * (size_t)n * 2 * plane_words, c.stream));   // (stale words, as an engine's ingest slot holds)
+    HIP_TRY(hipMemsetAsync(d_rec, 0, sizeof(MaskRec) * rec.size(), c.stream));
     SilhouetteArgs sa{};
-    sa.ctrl = d_ctrl.p;
-    sa.params = d_prm.p;
-    sa.planes = d_planes.p;
+    sa.ctrl = d_ctrl;
+    sa.params = d_prm;
+    sa.planes = d_planes;
     sa.plane_words = plane_words;
     sa.obj_stride = 2 * plane_words;
     sa.slot0 = 0;
-    sa.mrec = d_rec.p;
+    sa.mrec = d_rec;
     sa.n_obj = n;
     sa.W = dc.W; sa.H = dc.H; sa.wpr = dc.wpr;
     sa.fx = (float)dc.fx; sa.fy = (float)dc.fy; sa.cx = (float)dc.cx; sa.cy = (float)dc.cy;   // (divider 1: the camera as it is)
     sa.frames_packed = 0u;
+    unsigned long long* d_zstats = nullptr;
+    int* d_removed = nullptr;
     if (n > 1 || gated) {
-        HIP_TRY(d_zpairs.ensure((size_t)n));
-        HIP_TRY(d_zstats.ensure(2 + 3));   // (the occlusion counters, then the gate's)
-        HIP_TRY(hipMemsetAsync(d_zpairs.p, 0, sizeof(SilhouettePair) * n, c.stream));
-        HIP_TRY(hipMemsetAsync(d_zstats.p, 0, sizeof(unsigned long long) * 5, c.stream));
-        sa.zpairs = d_zpairs.p;
+        TRY(c.room(5, (size_t)n, &sa.zpairs));
+        TRY(c.room(6, 2 + 3, &d_zstats));   // (the occlusion counters, then the gate's)
+        HIP_TRY(hipMemsetAsync(sa.zpairs, 0, sizeof(SilhouettePair) * n, c.stream));
+        HIP_TRY(hipMemsetAsync(d_zstats, 0, sizeof(unsigned long long) * 5, c.stream));
     }
     if (n > 1) {
-        HIP_TRY(d_zbuf.ensure(npix));
-        sa.zbuf = d_zbuf.p;
+        TRY(c.room(7, npix, &sa.zbuf));
         sa.n_zscenes = 1;
-        sa.zstats = d_zstats.p;
+        sa.zstats = d_zstats;
     }
     if (gated) {
-        HIP_TRY(d_removed.ensure((size_t)2 * n));
-        HIP_TRY(hipMemsetAsync(d_removed.p, 0, sizeof(int) * 2 * n, c.stream));   // (an object without a mesh is drawn, and removes nothing)
+        TRY(c.room(8, (size_t)2 * n, &d_removed));
+        HIP_TRY(hipMemsetAsync(d_removed, 0, sizeof(int) * 2 * n, c.stream));   // (an object without a mesh is drawn, and removes nothing)
         sa.gate = 1;
         sa.gate_tf = gate->front_tolerance;
         sa.gate_tb = gate->behind_tolerance;
-        sa.gstats = d_zstats.p + 2;
-        sa.gremoved = d_removed.p;
+        sa.gstats = d_zstats + 2;
+        sa.gremoved = d_removed;
     }
     if (!launch_pose_silhouette(sa, 1, max_verts, bands, vertex_cache, c.stream))
         return fail(ROFT_ERR_INVALID, "pose silhouette: an image row is wider than the kernel's bit window");
     HIP_TRY(hipGetLastError());
     if (masks_out) {
-        HIP_TRY(d_mask.ensure(npix * n));
+        uint8_t* d_mask;
+        TRY(c.room(9, npix * n, &d_mask));
         for (int k = 0; k < n; ++k) {
-            const uint32_t* nz = d_planes.p + (size_t)k * 2 * plane_words;
-            launch_planes_to_mask(nz, nz + plane_words, (int)npix, d_mask.p + (size_t)k * npix, c.stream);
+            const uint32_t* nz = d_planes + (size_t)k * 2 * plane_words;
+            launch_planes_to_mask(nz, nz + plane_words, (int)npix, d_mask + (size_t)k * npix, c.stream);
         }
-        HIP_TRY(hipMemcpyAsync(masks_out, d_mask.p, npix * n, hipMemcpyDeviceToHost, c.stream));
+        HIP_TRY(hipMemcpyAsync(masks_out, d_mask, npix * n, hipMemcpyDeviceToHost, c.stream));
     }
-    std::vector<MaskRec> rec((size_t)2 * n);
-    HIP_TRY(hipMemcpyAsync(rec.data(), d_rec.p, sizeof(MaskRec) * rec.size(), hipMemcpyDeviceToHost, c.stream));
-    if (gated && removed_out) HIP_TRY(hipMemcpyAsync(removed_out, d_removed.p, sizeof(int) * 2 * n, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipMemcpyAsync(rec.data(), d_rec, sizeof(MaskRec) * rec.size(), hipMemcpyDeviceToHost, c.stream));
+    if (gated && removed_out) HIP_TRY(hipMemcpyAsync(removed_out, d_removed, sizeof(int) * 2 * n, hipMemcpyDeviceToHost, c.stream));
     HIP_TRY(hipStreamSynchronize(c.stream));   // (fc, prm and rec live in this call)
     HIP_TRY(hipGetLastError());
     if (counts_out)
@@ -535,15 +438,15 @@ int roft_pose_process_noise(const double psd[3], const double sig_w[3], double T
 static int op_ukf(const double mean[13], const double P[144], const double* Q81, double T, int type, const double* meas,
                   const double* Rdiag, const roft_ut_params* ut, double mean_out[13], double P_out[144], int* status)
 {
-    OpCtx& c = op();
-    std::lock_guard<std::mutex> lk(c.mu);
-    roft_camera cam{64, 64, 1.0, 1.0, 0.0, 0.0};
-    if (!c.ready) { if (int rc = c.prepare(cam, ROFT_FLOW_F32C2, 1, 1.0f, 35)) return rc; }
-    else { if (int rc = op_simple_prepare(c)) return rc; }
-    ObjState* st = new ObjState();
-    init_state(*st);
-    std::memcpy(st->belief[B_CORR].mean, mean, sizeof(double) * 13);
-    std::memcpy(st->belief[B_CORR].cov, P, sizeof(double) * 144);
+    OpContext& c = op_context();
+    std::unique_lock<std::mutex> lk;
+    TRY(c.enter(lk));
+    EngineArrays a;
+    TRY(c.one_object(&a));
+    ObjState& st = c.st;
+    init_state(st);
+    std::memcpy(st.belief[B_CORR].mean, mean, sizeof(double) * 13);
+    std::memcpy(st.belief[B_CORR].cov, P, sizeof(double) * 144);
     ObjParams prm;
     std::memset(&prm, 0, sizeof(prm));
     FrameCtrl fc;
@@ -554,8 +457,9 @@ static int op_ukf(const double mean[13], const double P[144], const double* Q81,
     sd.op = 1;
     sd.src = B_CORR;
     if (Q81) {
-        if (int rc = to_dev(c.b0, Q81, 81, c.stream)) { delete st; return rc; }
-        prm.q_override = reinterpret_cast<const double*>(c.b0.p);
+        double* d_q;
+        TRY(c.upload(0, Q81, 81, &d_q));
+        prm.q_override = d_q;
         sd.do_predict = 1;
         sd.n_corr = 0;
         sd.dst[0] = B_SPARE;
@@ -569,7 +473,7 @@ static int op_ukf(const double mean[13], const double P[144], const double* Q81,
         const bool has_vel = (type == ROFT_MEAS_VELOCITY || type == ROFT_MEAS_POSE_VELOCITY);
         const bool has_pose = (type == ROFT_MEAS_POSE || type == ROFT_MEAS_POSE_VELOCITY);
         if (has_vel) {
-            for (int i = 0; i < 6; ++i) st->twist_hist[0][i] = meas[i];
+            for (int i = 0; i < 6; ++i) st.twist_hist[0][i] = meas[i];
             for (int i = 0; i < 3; ++i) prm.R_v[i] = Rdiag[k++];
             for (int i = 0; i < 3; ++i) prm.R_w[i] = Rdiag[k++];
         }
@@ -581,23 +485,12 @@ static int op_ukf(const double mean[13], const double P[144], const double* Q81,
             for (int i = 0; i < 3; ++i) prm.R_q[i] = Rdiag[k++];
         }
     }
-    hipError_t err = hipMemcpyAsync(c.arr.state.p, st, sizeof(ObjState), hipMemcpyHostToDevice, c.stream);
-    if (err == hipSuccess) err = hipMemcpyAsync(c.arr.params.p, &prm, sizeof(prm), hipMemcpyHostToDevice, c.stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(c.stream);
-    if (err != hipSuccess) { delete st; HIP_TRY(err); }
-    c.arr.a.n_obj = 1;
-    if (int rc = upload_ctrl(c, fc)) { delete st; return rc; }
-    launch_ukf_chain(c.arr.a, *ut, true, 0, c.stream);
-    err = hipMemcpyAsync(st, c.arr.state.p, sizeof(ObjState), hipMemcpyDeviceToHost, c.stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(c.stream);
-    if (err == hipSuccess) err = hipGetLastError();
-    if (err == hipSuccess) {
-        std::memcpy(mean_out, st->belief[B_SPARE].mean, sizeof(double) * 13);
-        std::memcpy(P_out, st->belief[B_SPARE].cov, sizeof(double) * 144);
-        if (status) *status = st->lane[0].ukf_status & 0xF;
-    }
-    delete st;
-    HIP_TRY(err);
+    TRY(c.begin_object(a, &prm, fc));
+    launch_ukf_chain(a, *ut, true, 0, c.stream);
+    TRY(c.read_state(a));
+    std::memcpy(mean_out, st.belief[B_SPARE].mean, sizeof(double) * 13);
+    std::memcpy(P_out, st.belief[B_SPARE].cov, sizeof(double) * 144);
+    if (status) *status = st.lane[0].ukf_status & 0xF;
     return ROFT_OK;
 }
 
@@ -617,7 +510,7 @@ int roft_ukf_correct(const double mean[13], const double P[144], int type, const
     return op_ukf(mean, P, nullptr, 0.0, type, meas, Rdiag, ut, mean_out, P_out, status_out);
 }
 
-// The engine's outlier test on a one-object context: features of (depth, mask) buffered by features_kernel, both
+// The engine's outlier test on the one object: features of (depth, mask) buffered by features_kernel, both
 // alternatives rendered and scored by outlier_fused_kernel, the decision taken by the pose chain segment that follows -- the
 // three launches roft_step enqueues at a pose arrival.  depth / mask may be null (render only: no samples).
 static int op_outlier(const roft_camera* cam, int divider, const float* depth, const uint8_t* mask, const roft_mesh* mesh,
@@ -625,22 +518,12 @@ static int op_outlier(const roft_camera* cam, int divider, const float* depth, c
                       long samples_out[2], int* selected_out, float* tiles_out)
 {
     TRY(check_mesh(*mesh, "mesh", false));
-    OpCtx& c = op();
-    std::lock_guard<std::mutex> lk(c.mu);
-    if (int rc = c.prepare(*cam, ROFT_FLOW_F32C2, 1, 1.0f, 35)) return rc;
-    EngineArrays& a = c.arr.a;
-    a.cam.divider = divider;
-    a.tile_w = cam->width / divider;
-    a.tile_h = cam->height / divider;
+    OpContext& c = op_context();
+    std::unique_lock<std::mutex> lk;
+    TRY(c.enter(lk));
+    EngineArrays a;
+    TRY(c.one_object(*cam, nullptr, 35, divider, &a));
     const size_t npix = (size_t)cam->width * cam->height, tpix = (size_t)a.tile_w * a.tile_h;
-    if (int rc = c.arr.ensure_zmerge(1, tpix)) return rc;
-    auto restore = [&]() {   // default tile geometry of this context
-        a.cam = make_cam(*cam);
-        a.tile_w = cam->width / a.cam.divider;
-        a.tile_h = cam->height / a.cam.divider;
-        a.max_verts = a.max_tris = 0;
-        a.meshes_without_clusters = 0;
-    };
     // (GL render mode: the caller's triangles as they are, every one drawn -- roft_object_add does the same)
     TRY(c.mesh.upload(*mesh, o_in.render_mode == ROFT_RENDER_CONTRACT ? MeshLayout::kWalkClusters : MeshLayout::kAsItIs, c.stream));
     ObjParams prm;
@@ -657,36 +540,31 @@ static int op_outlier(const roft_camera* cam, int divider, const float* depth, c
     fc.lane = 0;
     fc.feat_read = 0;
     if (depth && mask) {
-        std::vector<uint8_t> zero;
-        if (int rc = to_dev(c.b2, mask, npix, c.stream)) return rc;
-        if (int rc = to_dev(c.b3, depth, npix, c.stream)) return rc;
+        uint8_t* d_mask;
+        float* d_depth;
+        TRY(c.upload(0, mask, npix, &d_mask));
+        TRY(c.upload(1, depth, npix, &d_depth));
         fc.has_new_mask = 1;
-        fc.new_mask = c.b2.p;
+        fc.new_mask = d_mask;
         fc.slot_cur = kSlotNew;
-        fc.depth_cur = reinterpret_cast<const float*>(c.b3.p);
+        fc.depth_cur = d_depth;
         fc.feat_write = 0;
     }
-    ObjState* st = new ObjState();
-    init_state(*st);
-    st->lane[0].pending_frame = 0;
-    st->lane[0].pc_frame = 0;
-    st->lane[0].pc_step = 1;
+    ObjState& st = c.st;
+    init_state(st);
+    st.lane[0].pending_frame = 0;
+    st.lane[0].pc_frame = 0;
+    st.lane[0].pc_step = 1;
     for (int k = 0; k < 2; ++k) {
-        PoseBelief& b = st->belief[b_alt(0, k)];
+        PoseBelief& b = st.belief[b_alt(0, k)];
         for (int i = 0; i < 3; ++i) b.mean[6 + i] = x2[3 * k + i];
         for (int i = 0; i < 4; ++i) b.mean[9 + i] = q2[4 * k + i];
     }
-    hipError_t err = hipMemcpyAsync(c.arr.state.p, st, sizeof(ObjState), hipMemcpyHostToDevice, c.stream);
-    if (err == hipSuccess) err = hipMemcpyAsync(c.arr.params.p, &prm, sizeof(prm), hipMemcpyHostToDevice, c.stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(c.stream);
-    if (err != hipSuccess) { delete st; restore(); HIP_TRY(err); }
-    if (int rc = upload_ctrl(c, fc)) { delete st; restore(); return rc; }
+    TRY(c.begin_object(a, &prm, fc));
     OutlierLaunchOpts o = o_in;
     if (tiles_out) {
-        err = c.b4.ensure(sizeof(float) * 2 * tpix);
-        if (err == hipSuccess) err = hipMemsetAsync(c.b4.p, 0, sizeof(float) * 2 * tpix, c.stream);
-        if (err != hipSuccess) { delete st; restore(); HIP_TRY(err); }
-        o.tile_dump = reinterpret_cast<float*>(c.b4.p);
+        TRY(c.room(2, 2 * tpix, &o.tile_dump));
+        HIP_TRY(hipMemsetAsync(o.tile_dump, 0, sizeof(float) * 2 * tpix, c.stream));
     }
     if (depth && mask) {
         launch_mask_ingest(a, 0, c.stream);
@@ -695,20 +573,13 @@ static int op_outlier(const roft_camera* cam, int divider, const float* depth, c
     TRY(launch_outlier(a, 0, c.stream, nullptr, &o));
     roft_ut_params ut{1.0, 2.0, 0.0};
     launch_ukf_chain(a, ut, false, 0, c.stream);   // decision (ROFTFilter.cpp:581-583) as the engine's next segment takes it
-    err = hipMemcpyAsync(st, c.arr.state.p, sizeof(ObjState), hipMemcpyDeviceToHost, c.stream);
-    if (err == hipSuccess && tiles_out) err = hipMemcpyAsync(tiles_out, c.b4.p, sizeof(float) * 2 * tpix, hipMemcpyDeviceToHost, c.stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(c.stream);
-    if (err == hipSuccess) err = hipGetLastError();
-    if (err == hipSuccess) {
-        for (int k = 0; k < 2; ++k) {
-            if (L_out) L_out[k] = st->lane[0].outlier_L[k];
-            if (samples_out) samples_out[k] = (long)st->lane[0].outlier_cnt[k];
-        }
-        if (selected_out) *selected_out = st->lane[0].outlier_selected;
+    if (tiles_out) HIP_TRY(hipMemcpyAsync(tiles_out, o.tile_dump, sizeof(float) * 2 * tpix, hipMemcpyDeviceToHost, c.stream));
+    TRY(c.read_state(a));
+    for (int k = 0; k < 2; ++k) {
+        if (L_out) L_out[k] = st.lane[0].outlier_L[k];
+        if (samples_out) samples_out[k] = (long)st.lane[0].outlier_cnt[k];
     }
-    delete st;
-    restore();
-    HIP_TRY(err);
+    if (selected_out) *selected_out = st.lane[0].outlier_selected;
     return ROFT_OK;
 }
 
@@ -778,18 +649,16 @@ int roft_depth_likelihood(const roft_camera* cam, const float* depth, const uint
                           double* L_out, long* samples_out)
 {
     if (!cam || !depth || !mask || !tile || !L_out || divider <= 0) return fail(ROFT_ERR_INVALID, "bad argument");
-    OpCtx& c = op();
-    std::lock_guard<std::mutex> lk(c.mu);
-    if (int rc = c.prepare(*cam, ROFT_FLOW_F32C2, 1, 1.0f, 35)) return rc;
-    c.arr.a.cam.divider = divider;
-    c.arr.a.tile_w = cam->width / divider;
-    c.arr.a.tile_h = cam->height / divider;
-    const size_t npix = (size_t)cam->width * cam->height;
-    const size_t tpix = (size_t)c.arr.a.tile_w * c.arr.a.tile_h;
-    if (tpix * 2 > c.arr.zbuf.n) HIP_TRY(c.arr.zbuf.ensure(tpix * 2));
-    c.arr.a.zbuf = c.arr.zbuf.p;
-    if (int rc = to_dev(c.b0, mask, npix, c.stream)) return rc;
-    if (int rc = to_dev(c.b1, depth, npix, c.stream)) return rc;
+    OpContext& c = op_context();
+    std::unique_lock<std::mutex> lk;
+    TRY(c.enter(lk));
+    EngineArrays a;
+    TRY(c.one_object(*cam, nullptr, 35, divider, &a));
+    const size_t npix = (size_t)cam->width * cam->height, tpix = (size_t)a.tile_w * a.tile_h;
+    uint8_t* d_mask;
+    float* d_depth;
+    TRY(c.upload(0, mask, npix, &d_mask));
+    TRY(c.upload(1, depth, npix, &d_depth));
     // tile -> z-buffer bit pattern (0 = background -> +inf), used for both alternatives
     std::vector<uint32_t> zb(tpix * 2);
     for (size_t i = 0; i < tpix; ++i) {
@@ -799,43 +668,25 @@ int roft_depth_likelihood(const roft_camera* cam, const float* depth, const uint
         zb[i] = bits;
         zb[tpix + i] = bits;
     }
-    HIP_TRY(hipMemcpyAsync(c.arr.zbuf.p, zb.data(), zb.size() * 4, hipMemcpyHostToDevice, c.stream));
+    HIP_TRY(hipMemcpyAsync(a.zbuf, zb.data(), zb.size() * 4, hipMemcpyHostToDevice, c.stream));
     FrameCtrl fc;
     clear_ctrl(fc);
     fc.has_new_mask = 1;
-    fc.new_mask = c.b0.p;
+    fc.new_mask = d_mask;
     fc.slot_cur = kSlotNew;
-    fc.depth_cur = reinterpret_cast<const float*>(c.b1.p);
+    fc.depth_cur = d_depth;
     fc.feat_write = 0;
     fc.feat_read = 0;
     fc.outlier_step = 0;
-    if (int rc = upload_ctrl(c, fc)) return rc;
-    {
-        ObjState st0;
-        init_state(st0);
-        st0.lane[0].pending_frame = 0;   // the test of frame 0 is pending
-        HIP_TRY(hipMemcpyAsync(c.arr.state.p, &st0, sizeof(st0), hipMemcpyHostToDevice, c.stream));
-        HIP_TRY(hipStreamSynchronize(c.stream));
-    }
-    launch_mask_ingest(c.arr.a, 0, c.stream);
-    launch_features(c.arr.a, c.stream);
-    // likelihood only (the z-buffers are already filled)
-    launch_outlier_only(c.arr.a, c.stream);
-    ObjState* st = new ObjState();
-    hipError_t err = hipMemcpyAsync(st, c.arr.state.p, sizeof(ObjState), hipMemcpyDeviceToHost, c.stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(c.stream);
-    if (err == hipSuccess) err = hipGetLastError();
-    if (err == hipSuccess) {
-        *L_out = st->lane[0].outlier_L[0];
-        if (samples_out) *samples_out = (long)st->lane[0].outlier_cnt[0];
-    }
-    delete st;
-    // restore the default tile geometry of this context
-    c.arr.a.cam = make_cam(*cam);
-    c.arr.a.tile_w = cam->width / c.arr.a.cam.divider;
-    c.arr.a.tile_h = cam->height / c.arr.a.cam.divider;
-    c.ready = false;  // zbuf may have been re-sized: force a clean re-allocation next time
-    HIP_TRY(err);
+    init_state(c.st);
+    c.st.lane[0].pending_frame = 0;   // the test of frame 0 is pending
+    TRY(c.begin_object(a, nullptr, fc));
+    launch_mask_ingest(a, 0, c.stream);
+    launch_features(a, c.stream);
+    launch_outlier_only(a, c.stream);   // likelihood only (the z-buffers are already filled)
+    TRY(c.read_state(a));
+    *L_out = c.st.lane[0].outlier_L[0];
+    if (samples_out) *samples_out = (long)c.st.lane[0].outlier_cnt[0];
     return ROFT_OK;
 }
 
@@ -845,10 +696,10 @@ int roft_pose_errors(int kind, const double* points, int n_points, const double*
     if (!points || !est || !ref || !out) return fail(ROFT_ERR_INVALID, "null argument");
     if (n_points <= 0 || n_poses < 0) return fail(ROFT_ERR_INVALID, "n_points must be > 0 and n_poses >= 0");
     if (n_poses == 0) return ROFT_OK;
-    OpCtx& c = op();
-    std::lock_guard<std::mutex> lk(c.mu);
-    if (int rc = op_simple_prepare(c)) return rc;
-    PoseErrorScratch& sc = op_pose_scratch();
+    OpContext& c = op_context();
+    std::unique_lock<std::mutex> lk;
+    TRY(c.enter(lk));
+    PoseErrorScratch& sc = c.pose_errors;
     HIP_TRY(sc.pts.ensure((size_t)3 * n_points));
     HIP_TRY(hipMemcpyAsync(sc.pts.p, points, sizeof(double) * 3 * n_points, hipMemcpyHostToDevice, c.stream));
     return pose_errors_run(sc, kind, sc.pts.p, n_points, est, PoseView{}, ref, n_poses, out, c.stream);
@@ -857,9 +708,9 @@ int roft_pose_errors(int kind, const double* points, int n_points, const double*
 int roft_debug_pose_errors_kernel_ms(double* ms_out)
 {
     if (!ms_out) return fail(ROFT_ERR_INVALID, "null argument");
-    OpCtx& c = op();
+    OpContext& c = op_context();
     std::lock_guard<std::mutex> lk(c.mu);
-    PoseErrorScratch& sc = op_pose_scratch();
+    PoseErrorScratch& sc = c.pose_errors;
     if (!sc.timed) return fail(ROFT_ERR_STATE, "no roft_pose_errors call to report");
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, sc.ev0, sc.ev1));

@@ -1,6 +1,6 @@
 // engine_quality.hip -- track quality (include/roft_engine.h, section 3d): enabling it on an engine, reading the records, the
 // operator-level entry point on host buffers, the kernel's time.  The launch itself is part of a batch's plan: engine_step.hip.
-#include "engine_internal.h"
+#include "op_context.h"
 
 static_assert(roft_engine::kBatchRing == 8, "EngineQuality keeps one event pair per slot of the batch ring");
 static_assert(sizeof(roft_quality_record) == 40, "roft_quality_record is 40 bytes");
@@ -119,29 +119,7 @@ int roft_debug_quality_kernel_ms(roft_engine* e, double* ms_out)
 
 }  // extern "C"
 
-// ---- operator level: the engine's kernel on host buffers, one object, device 0 -----------------------------------------------
-namespace {
-
-struct QualityOp {
-    std::mutex mu;
-    hipStream_t stream = nullptr;
-    Arrays arr;
-    int W = 0, H = 0;
-    bool ready = false;
-    DeviceMesh mesh;
-    DevBuf<unsigned char> mask;
-    DevBuf<float> depth;
-    DevBuf<QualityRaw> rec;
-};
-
-QualityOp& quality_op()
-{
-    static QualityOp c;
-    return c;
-}
-
-}  // namespace
-
+// ---- operator level: the engine's kernel on host buffers, on the one-object context (op_context.h) ---------------------------------
 extern "C" int roft_track_quality(const roft_camera* cam, int divider, const float* depth, const uint8_t* mask, const roft_mesh* mesh,
                                   const double x[3], const double q[4], float depth_tolerance, double depth_maximum, int window_pixels,
                                   roft_quality_record* out)
@@ -151,31 +129,12 @@ extern "C" int roft_track_quality(const roft_camera* cam, int divider, const flo
     if (!(depth_tolerance >= 0.0f)) return fail(ROFT_ERR_INVALID, "depth_tolerance must be >= 0");
     if (window_pixels < 0) return fail(ROFT_ERR_INVALID, "window_pixels must be >= 0");
     TRY(check_mesh(*mesh, "mesh", true));   // (no mesh: nothing is rendered, the record counts the mask alone)
-    if (roft_device_count() <= 0) return fail(ROFT_ERR_DEVICE, "no HIP device (libroft_hip has no CPU path)");
-    if (int rc = check_geometry(cam->width, cam->height)) return rc;
-    if (cam->width / divider <= 0 || cam->height / divider <= 0) return fail(ROFT_ERR_INVALID, "divider larger than the image");
-    QualityOp& c = quality_op();
-    std::lock_guard<std::mutex> lk(c.mu);
-    HIP_TRY(hipSetDevice(0));
-    (void)hipGetLastError();
-    if (!c.stream) HIP_TRY(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
-    if (!c.ready || c.W != cam->width || c.H != cam->height) {
-        DevFlowFmt ff;
-        ff.type = ROFT_FLOW_F32C2; ff.grid = 1; ff.cols = cam->width; ff.rows = cam->height; ff.scale = 1.0f;
-        c.ready = false;
-        if (int rc = c.arr.alloc(1, 1, make_cam(*cam), ff, 35)) return rc;
-        HIP_TRY(c.arr.log.ensure(1, true));
-        HIP_TRY(c.rec.ensure(1));
-        c.W = cam->width; c.H = cam->height;
-        c.ready = true;
-    }
-    EngineArrays a = c.arr.a;
-    a.cam = make_cam(*cam);
-    a.cam.divider = divider;
-    a.tile_w = cam->width / divider;
-    a.tile_h = cam->height / divider;
-    a.n_obj = 1;
-    a.T = 1;
+    OpContext& c = op_context();
+    std::unique_lock<std::mutex> lk;
+    TRY(c.enter(lk));
+    EngineArrays a;
+    TRY(c.one_object(*cam, nullptr, 35, divider, &a));
+    if (a.tile_w <= 0 || a.tile_h <= 0) return fail(ROFT_ERR_INVALID, "divider larger than the image");
     a.out_log = c.arr.log.p;
     a.log_cap = 1;
     a.max_verts = has_mesh(*mesh) ? mesh->n_verts : 0;
@@ -187,31 +146,31 @@ extern "C" int roft_track_quality(const roft_camera* cam, int divider, const flo
     std::memset(&prm, 0, sizeof(prm));
     TRY(c.mesh.upload(*mesh, MeshLayout::kWalkOrder, s));
     c.mesh.describe(prm);
-    HIP_TRY(c.mask.ensure(npix));
-    HIP_TRY(c.depth.ensure(npix));
-    HIP_TRY(hipMemcpyAsync(c.mask.p, mask, npix, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(c.depth.p, depth, npix * sizeof(float), hipMemcpyHostToDevice, s));
+    uint8_t* d_mask;
+    float* d_depth;
+    TRY(c.upload(0, mask, npix, &d_mask));
+    TRY(c.upload(1, depth, npix, &d_depth));
     FrameCtrl fc;
     clear_ctrl(fc);
     fc.has_new_mask = 1;
-    fc.new_mask = c.mask.p;
+    fc.new_mask = d_mask;
     fc.slot_cur = kSlotNew;   // (the ingest leaves the planes of the delivered mask in the slot the kernel is told to read)
-    fc.depth_cur = c.depth.p;
+    fc.depth_cur = d_depth;
     fc.frame_idx = 0;
     roft_object_output row;
     std::memset(&row, 0, sizeof(row));
     for (int i = 0; i < 3; ++i) row.pose[6 + i] = x[i];
     for (int i = 0; i < 4; ++i) row.pose[9 + i] = q[i];
-    HIP_TRY(hipMemcpyAsync(a.ctrl, &fc, sizeof(fc), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(a.out_log, &row, sizeof(row), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(a.params, &prm, sizeof(prm), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(c.rec.p, 0xFF, sizeof(QualityRaw), s));
+    HIP_TRY(hipMemsetAsync(c.quality.p, 0xFF, sizeof(QualityRaw), s));
+    init_state(c.st);
+    TRY(c.begin_object(a, &prm, fc));   // (row lives on this stack as well)
     launch_mask_reset(a, s);   // (the ingest adds its pixel counts to the context's mask table)
     launch_mask_ingest(a, 0, s);
-    launch_quality(a, c.rec.p, 1, 0u, 1, depth_tolerance, depth_maximum, window_pixels, s);
+    launch_quality(a, c.quality.p, 1, 0u, 1, depth_tolerance, depth_maximum, window_pixels, s);
     QualityRaw raw;
-    HIP_TRY(hipMemcpyAsync(&raw, c.rec.p, sizeof(raw), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));   // (fc, row, prm and raw live on this stack)
+    HIP_TRY(hipMemcpyAsync(&raw, c.quality.p, sizeof(raw), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     HIP_TRY(hipGetLastError());
     if (raw.frame != 0) return fail(ROFT_ERR_DEVICE, "track quality: the kernel left no record");
     *out = quality_record(raw);
