@@ -28,9 +28,6 @@ int fail(int code, const std::string& msg)
 const std::string& last_error() { return g_last_error; }
 
 namespace roft {
-// shared with flow_producer.hip
-int set_last_error(int code, const std::string& msg) { return fail(code, msg); }
-
 int device_cu_count()
 {
     static std::mutex mu;
@@ -102,7 +99,7 @@ __global__ __launch_bounds__(1024) void probe_sectors_kernel(const unsigned* buf
 // would hold
 int check_dev_error(roft_engine* e)
 {
-    const int code = e->dev_error ? *reinterpret_cast<volatile int*>(e->dev_error) : 0;
+    const int code = e->dev_error.p ? *reinterpret_cast<volatile int*>(e->dev_error.p) : 0;
     if (code == 0) return ROFT_OK;
     if (code == ROFT_DEV_ERROR_TWIST_WAIT)
         return fail(ROFT_ERR_DEVICE, "a pose lane waited two seconds for a twist of the velocity filter it runs next to and gave up "
@@ -343,12 +340,15 @@ static int create_stream_set(int device, bool priorities, StreamSet** out)
     int pr[5] = {normal, normal, greatest, least, normal};
     if (const char* pe = getenv("ROFT_PRIO"))
         for (int i = 0; i < 5 && pe[i]; ++i) pr[i] = pe[i] == 'h' ? greatest : (pe[i] == 'l' ? least : normal);
-    hipError_t err = hipSuccess;
-    for (int l = 0; l < kNumLin && err == hipSuccess; ++l) err = hipStreamCreateWithPriority(&s->pose[l], hipStreamNonBlocking, pr[l]);
-    if (err == hipSuccess) err = hipStreamCreateWithPriority(&s->vel, hipStreamNonBlocking, pr[2]);
-    if (err == hipSuccess) err = hipStreamCreateWithPriority(&s->mask, hipStreamNonBlocking, pr[3]);
-    if (err == hipSuccess) err = hipStreamCreateWithPriority(&s->up, hipStreamNonBlocking, pr[4]);
-    if (err != hipSuccess) { delete s; return fail(ROFT_ERR_DEVICE, std::string("stream creation: ") + hipGetErrorString(err)); }
+    hipStream_t* const made[5] = {&s->pose[0], &s->pose[1], &s->vel, &s->mask, &s->up};
+    static_assert(kNumLin == 2, "pr[] and made[] name two pose lanes");
+    for (int i = 0; i < 5; ++i) {
+        const hipError_t err = hipStreamCreateWithPriority(made[i], hipStreamNonBlocking, pr[i]);
+        if (err == hipSuccess) continue;
+        while (i-- > 0) (void)hipStreamDestroy(*made[i]);   // (the set never reached the pool: nothing else knows these streams)
+        delete s;
+        return fail(ROFT_ERR_DEVICE, std::string("stream creation: ") + hipGetErrorString(err));
+    }
     *out = s;
     return ROFT_OK;
 }
@@ -455,10 +455,8 @@ static int engine_setup(roft_engine* e, const roft_config* cfg)
     }
     for (BatchSlot& b : e->ring) {
         HIP_TRY(b.dctrl.ensure(ctrl_block_count((size_t)cfg->max_objects * e->T_max), true));
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&b.stage), sizeof(FrameCtrl) * ctrl_block_count((size_t)cfg->max_objects * e->T_max)));
-        hipError_t err = hipSuccess;
-        b.each_event([&](hipEvent_t& ev) { if (err == hipSuccess) err = hipEventCreateWithFlags(&ev, hipEventDisableTiming); });
-        HIP_TRY(err);
+        HIP_TRY(b.stage.ensure(ctrl_block_count((size_t)cfg->max_objects * e->T_max)));
+        HIP_TRY(b.create_events());
     }
     DevFlowFmt ff;
     ff.type = cfg->flow_type;
@@ -469,11 +467,11 @@ static int engine_setup(roft_engine* e, const roft_config* cfg)
     const int radius = (int)(size_t)cfg->subsampling_radius;
     if (int rc = e->arr.alloc(cfg->max_objects, e->T_max, make_cam(cfg->cam), ff, radius)) return rc;
     e->arr.a.n_obj = 0;
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->dev_error), sizeof(int), hipHostMallocMapped));
-    *e->dev_error = 0;
+    HIP_TRY(e->dev_error.ensure(1, hipHostMallocMapped));
+    *e->dev_error.p = 0;
     {
         void* dp = nullptr;
-        HIP_TRY(hipHostGetDevicePointer(&dp, e->dev_error, 0));
+        HIP_TRY(hipHostGetDevicePointer(&dp, e->dev_error.p, 0));
         e->arr.a.dev_error = static_cast<int*>(dp);
     }
     e->arr.a.mask_wgs = cfg->mask_workgroups_per_object;
@@ -527,7 +525,7 @@ static int engine_setup(roft_engine* e, const roft_config* cfg)
 int roft_engine_create(const roft_config* cfg, roft_engine** out)
 {
     if (!cfg || !out) return fail(ROFT_ERR_INVALID, "null argument");
-    if (roft_device_count() <= cfg->device) return fail(ROFT_ERR_DEVICE, "no such HIP device (the engine has no CPU path)");
+    TRY(require_device(cfg->device, "no such HIP device (the engine has no CPU path)"));
     if (int rc = check_geometry(cfg->cam.width, cfg->cam.height)) return rc;
     if (cfg->max_objects <= 0) return fail(ROFT_ERR_INVALID, "max_objects must be positive");
     if (cfg->flow_type != ROFT_FLOW_S16C2 && cfg->flow_type != ROFT_FLOW_F32C2)
@@ -566,9 +564,8 @@ int roft_engine_create(const roft_config* cfg, roft_engine** out)
     else e->hist_cap = (cfg->mask_frames_between > 0) ? cfg->mask_frames_between : kMaxFlowHist;
     e->retain = e->hist_cap + lead * T + 2;
     if (const int rc = engine_setup(e, cfg)) {
-        const std::string msg = g_last_error;
-        (void)roft_engine_destroy(e);
-        return fail(rc, msg);
+        (void)roft_engine_destroy(e);   // (it refuses nothing: the error string stays engine_setup's)
+        return rc;
     }
     *out = e;
     return ROFT_OK;
@@ -585,17 +582,8 @@ int roft_engine_destroy(roft_engine* e)
     }
     for (hipStream_t s : {e->stream, e->vel_stream, e->pose_stream[0], e->pose_stream[1], e->up_stream})
         if (s) (void)hipStreamSynchronize(s);
-    for (BatchSlot& b : e->ring) {
-        b.each_event([](hipEvent_t& ev) { if (ev) (void)hipEventDestroy(ev); });
-        if (b.stage) (void)hipHostFree(b.stage);
-        if (b.gather_tab) (void)hipHostFree(b.gather_tab);
-    }
     release_streams(e->streams);   // (idle: synchronised above)
-    for (auto* o : e->objs) delete o;
-    if (e->state_host) (void)hipHostFree(e->state_host);
-    if (e->dev_error) (void)hipHostFree(e->dev_error);
-    for (auto ev : e->tev) (void)hipEventDestroy(ev);
-    delete e;
+    delete e;   // (everything the engine owns -- device and pinned memory, events, objects -- goes here, behind the synchronise, on its device)
     return ROFT_OK;
 }
 
@@ -686,14 +674,12 @@ int roft_object_add(roft_engine* e, const roft_object_desc* d, int* obj_id)
     HIP_TRY(hipSetDevice(e->cfg.device));
     const int id = (int)e->objs.size();
     TRY(check_object_desc(e->cfg, *d, false, false));
-    HostObject* o = new HostObject();
-    ObjState* st = new ObjState();
+    auto o = std::make_unique<HostObject>();
+    auto st = std::make_unique<ObjState>();   // (too large for the stack)
     bool mesh_uploaded = false;
-    int rc = apply_object_desc(e, id, o, d, false, st, e->stream, &mesh_uploaded);
-    if (rc == ROFT_OK && hipStreamSynchronize(e->stream) != hipSuccess) rc = fail(ROFT_ERR_DEVICE, "state upload failed");
-    delete st;
-    if (rc != ROFT_OK) { delete o; return rc; }
-    e->objs.push_back(o);
+    TRY(apply_object_desc(e, id, o.get(), d, false, st.get(), e->stream, &mesh_uploaded));
+    if (hipStreamSynchronize(e->stream) != hipSuccess) return fail(ROFT_ERR_DEVICE, "state upload failed");
+    e->objs.push_back(std::move(o));
     e->arr.a.n_obj = (int)e->objs.size();
     update_mesh_maxima(e, e->arr.a.n_obj);
     if (obj_id) *obj_id = id;
@@ -764,7 +750,7 @@ int roft_objects_restart(roft_engine* e, const int* obj_ids, const roft_object_d
     long long meshes = 0;
     for (int i = 0; i < n; ++i) {
         const int id = obj_ids[i];
-        HostObject* o = e->objs[id];
+        HostObject* o = e->objs[id].get();
         if (running && o->s.track_frames > 0) {
             const ObjState& st = last[i];
             roft_object_output& out = o->last_out;
@@ -780,7 +766,6 @@ int roft_objects_restart(roft_engine* e, const int* obj_ids, const roft_object_d
         TRY(apply_object_desc(e, id, o, &descs[i], keep_mesh, &fresh[i], s, &mesh_uploaded));
         meshes += mesh_uploaded ? 1 : 0;
         // the schedule mirrors of a new object, on the ENGINE's frame numbering (Sched::frame_idx)
-        for (OwnedFlow* of : o->owned) delete of;
         o->owned.clear();
         o->s = Sched();
         o->s.frame_idx = e->frame_counter;

@@ -8,13 +8,10 @@ extern "C" int roft_debug_get_dbg(roft_engine* e, int id, long long out[32])
 {
     if (!e || id < 0 || id >= (int)e->objs.size()) return ROFT_ERR_INVALID;
     if (roft_sync(e) != ROFT_OK) return ROFT_ERR_DEVICE;
-    ObjState* st = new ObjState();
-    hipError_t err = hipMemcpy(st, e->arr.state.p + id, sizeof(ObjState), hipMemcpyDeviceToHost);
-    if (err == hipSuccess) std::memcpy(out, st->dbg, sizeof(long long) * 32);
-    delete st;
+    char* const dbg = reinterpret_cast<char*>(e->arr.state.p + id) + offsetof(ObjState, dbg);
+    if (hipMemcpy(out, dbg, sizeof(long long) * 32, hipMemcpyDeviceToHost) != hipSuccess) return ROFT_ERR_DEVICE;
     // (read and clear: the stamps of the frame kernels are maxima over their workgroups)
-    if (err == hipSuccess) err = hipMemset(reinterpret_cast<char*>(e->arr.state.p + id) + offsetof(ObjState, dbg), 0, sizeof(long long) * 32);
-    return err == hipSuccess ? ROFT_OK : ROFT_ERR_DEVICE;
+    return hipMemset(dbg, 0, sizeof(long long) * 32) == hipSuccess ? ROFT_OK : ROFT_ERR_DEVICE;
 }
 
 // Diagnostics: (100 MHz ticks, workgroups) the workgroups of each kernel spent resident since the last call -- ResidencyKernel
@@ -45,30 +42,24 @@ extern "C" int roft_debug_sector_rate(int device, double* sectors_per_second)
     if (!sectors_per_second) return fail(ROFT_ERR_INVALID, "null output");
     HIP_TRY(hipSetDevice(device));
     const size_t bytes = (size_t)2 << 30;
-    unsigned* buf = nullptr;
-    unsigned* sink = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&buf), bytes));
     const int grid = 2048;   // x 1024 threads x 8 loads = 16 M sectors
-    hipError_t err = hipMalloc(reinterpret_cast<void**>(&sink), (size_t)grid * 1024 * sizeof(unsigned));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (err == hipSuccess) err = hipMemset(buf, 0, bytes);
-    if (err == hipSuccess) err = hipEventCreate(&e0);
-    if (err == hipSuccess) err = hipEventCreate(&e1);
+    DevBuf<unsigned> buf, sink;
+    Event e0, e1;
+    HIP_TRY(buf.ensure(bytes / sizeof(unsigned), true));
+    HIP_TRY(sink.ensure((size_t)grid * 1024));
+    HIP_TRY(e0.create());
+    HIP_TRY(e1.create());
     float best_ms = 0.f;
-    for (int rep = 0; rep < 5 && err == hipSuccess; ++rep) {
+    for (int rep = 0; rep < 5; ++rep) {
         (void)hipEventRecord(e0, nullptr);
-        hipLaunchKernelGGL(probe_sectors_kernel, dim3(grid), dim3(1024), 0, nullptr, buf, (unsigned)(bytes / 64 - 1), 0x9e3779b9u * (unsigned)(rep + 1), sink);
+        hipLaunchKernelGGL(probe_sectors_kernel, dim3(grid), dim3(1024), 0, nullptr, buf.p, (unsigned)(bytes / 64 - 1), 0x9e3779b9u * (unsigned)(rep + 1), sink.p);
         (void)hipEventRecord(e1, nullptr);
-        err = hipEventSynchronize(e1);
+        HIP_TRY(hipEventSynchronize(e1));
         float ms = 0.f;
-        if (err == hipSuccess) err = hipEventElapsedTime(&ms, e0, e1);
+        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
         if (rep > 0 && (best_ms == 0.f || ms < best_ms)) best_ms = ms;   // (the first launch loads the code object)
     }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    (void)hipFree(sink);
-    (void)hipFree(buf);
-    if (err != hipSuccess || !(best_ms > 0.f)) return fail(ROFT_ERR_DEVICE, std::string("sector-rate probe: ") + hipGetErrorString(err));
+    if (!(best_ms > 0.f)) return fail(ROFT_ERR_DEVICE, std::string("sector-rate probe: ") + hipGetErrorString(hipSuccess));   // (no launch took time)
     *sectors_per_second = (double)grid * 1024.0 * 8.0 / ((double)best_ms * 1e-3);
     return ROFT_OK;
 }

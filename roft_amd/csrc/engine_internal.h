@@ -2,6 +2,8 @@
 // engine, the host-side mirrors of the reference's source / measurement state machines (Sched), the engine object itself and
 // the few functions that cross a file boundary.  Not installed, not part of the ABI (that is include/roft_engine.h).
 //
+//   device_owned.h      fail / HIP_TRY / TRY, "is the device there", and the owners of device memory (DevBuf), pinned host memory (PinnedBuf)
+//                       and events (Event): every allocation of the host side is a member of one of them (also flow_producer.hip, k_depth.hip)
 //   engine.hip          error string, pinned host pool, defaults, stream sets, roft_engine_create / destroy, roft_object_add,
 //                       roft_objects_restart
 //   engine_submit.hip   roft_frames_submit: the frame programs (build_pose_program), HOST staging, the control blocks of a batch
@@ -29,10 +31,12 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
 
+#include "device_owned.h"
 #include "roft_device.h"
 #include "mesh_class.h"
 #include "mesh_clusters.h"
@@ -48,45 +52,6 @@ static_assert(roft::host::kPlanLanes == roft::kNumLin, "batch_plan.h plans for t
 
 namespace roft {
 namespace host {
-
-// sets the calling thread's error string (roft_last_error_string) and returns `code` (engine.hip)
-int fail(int code, const std::string& msg);
-
-
-#define HIP_TRY(expr)                                                                                      \
-    do {                                                                                                   \
-        hipError_t _e = (expr);                                                                            \
-        if (_e != hipSuccess)                                                                              \
-            return fail(ROFT_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e));               \
-    } while (0)
-#define TRY(call) do { if (int _rc = (call)) return _rc; } while (0)   // (a call that has set the error string itself)
-
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    DevBuf() = default;
-    DevBuf(DevBuf&& o) noexcept { swap(o); }   // (move-only: one owner frees the memory; what `this` held goes with `o`)
-    DevBuf& operator=(DevBuf&& o) noexcept { swap(o); return *this; }
-    void swap(DevBuf& o) { std::swap(p, o.p); std::swap(n, o.n); }
-    ~DevBuf() { release(); }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-    hipError_t ensure(size_t count, bool zero = false)
-    {
-        if (count <= n && p) return hipSuccess;
-        release();
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(count, 1) * sizeof(T));
-        if (e != hipSuccess) { p = nullptr; return e; }
-        n = count;
-        if (zero) e = hipMemset(p, 0, std::max<size_t>(count, 1) * sizeof(T));
-        return e;
-    }
-};
 
 // The one refusal (ROFT_ERR_INVALID, before any device is looked for) of a caller's mesh at every site that draws one; `what` names it
 // in the text ("mesh 3").  The site's policy: may the mesh be absent; tri_index_bits > 0: n_tris must stay below 2^bits.
@@ -291,13 +256,8 @@ struct Arrays {
 // Device scratch of the pose-error metrics (roft_pose_errors / roft_engine_score_log): grows on demand, kept between calls.
 struct PoseErrorScratch {
     DevBuf<double> pts, est, ref, cloud, partial, out;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the kernels of the last call (roft_debug_pose_errors_kernel_ms)
+    Event ev0, ev1;   // around the kernels of the last call (roft_debug_pose_errors_kernel_ms)
     bool timed = false;
-    ~PoseErrorScratch()
-    {
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-    }
 };
 // ADD / ADD-S of n pose pairs on stream s (engine_ops.hip).  d_pts: P x 3 doubles on the device.  The estimates are est_host
 // (n x 7 host doubles, uploaded) or, when that is null, est_dev (already on the device).  ref_host: n x 7 host doubles;
@@ -381,7 +341,7 @@ struct HostObject {
     int stepped_slot = 0, stepped_lane = 0;   // slot holding p_corr_belief_ after the last stepped frame, and its lane
     const void* stepped_flow = nullptr;       // the flow produced for the last stepped frame (roft_engine_get_flow), or null
     const float* stepped_depth = nullptr;     // the depth of the last stepped frame (roft_engine_get_depth reads it on a raw-depth engine)
-    std::vector<OwnedFlow*> owned;   // engine copies of flows that outlived the zero-copy retention window
+    std::vector<OwnedFlow> owned;   // engine copies of flows that outlived the zero-copy retention window
     DeviceMesh mesh;   // what ObjParams of the object names (absent: the object was described without one)
     // masks from poses (roft_engine_enable_pose_masks): the object is enrolled; the pose of roft_object_desc::p_mean0 (x, q = w x y z),
     // which stands in for a first frame that brings none
@@ -393,7 +353,6 @@ struct HostObject {
     // roft_objects_restart: what roft_get_outputs showed for the track that ended, shown until the new track's first step
     roft_object_output last_out{};
     bool last_out_valid = false;
-    ~HostObject() { for (auto* o : owned) delete o; }
 };
 
 // Camera images on the engine (roft_engine_enable_flow): what a submit call enqueues on the upload stream, frame by frame, behind
@@ -416,7 +375,7 @@ struct EngineFlow {
     // generations indexed by frame, so that the pyramids of ALL frames of a batch are built in one go while the last one of the
     // batch before is still there (a later batch overwrites a generation behind its readers in stream order); a generation
     // grows to the largest number of distinct images a frame ever brought.
-    std::vector<std::vector<DevBuf<float>*>> pyr;
+    std::vector<std::vector<DevBuf<float>>> pyr;
     DevBuf<float> coarse, field;        // workspace of ONE chunk of kOfChunk pairs, reused chunk after chunk in stream order
     // the forward-backward check (roft_engine_enable_flow_consistency): a chunk is then kOfCheckChunk pairs, whose backward problems
     // take the upper half of `coarse` and the level-0 fields of `back`
@@ -424,7 +383,6 @@ struct EngineFlow {
     roft_of_consistency tol{};
     DevBuf<float> back;                 // [kOfCheckChunk][H * W * 2]
     roft_engine_flow_stats stats{};
-    ~EngineFlow() { for (auto& g : pyr) for (auto* b : g) delete b; }
 };
 
 // Raw sensor depth on the engine (roft_engine_enable_raw_depth): inputs[].depth carries the sensor's 16-bit frame; the float depth
@@ -439,13 +397,8 @@ struct EngineDepth {
     size_t raw_pixels = 0;            // readings per raw image (the depth source's size)
     DepthAlignGeom geom{};            // src.align != 0
     roft_engine_depth_stats stats{};
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the depth kernels of the last submit (roft_debug_depth_kernel_ms)
+    Event ev0, ev1;   // around the depth kernels of the last submit (roft_debug_depth_kernel_ms)
     bool timed = false;
-    ~EngineDepth()
-    {
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-    }
 };
 
 // Masks from poses on the engine (roft_engine_enable_pose_masks): enrolled objects take the silhouette of a delivered pose as the
@@ -456,7 +409,7 @@ struct EnginePoseMasks {
     bool enabled = false;
     bool all = false;                    // n_ids == 0: every object the engine has at its first frame (and a mesh)
     roft_engine_pose_mask_stats stats{};
-    hipEvent_t ev_start[8] = {}, ev_stop[8] = {};
+    Event ev_start[8], ev_stop[8];
     int last_slot = -1;                  // batch-ring slot of the last launch
     bool last_timed = false;             // ... and whether it ended with ev_stop of that slot
     // objects of one scene hide each other (roft_engine_enable_pose_mask_occlusion).  Allocated when the mode is enabled: z-buffers
@@ -473,11 +426,6 @@ struct EnginePoseMasks {
     roft_pose_mask_gate gate_prm{};
     roft_engine_pose_mask_gate_stats gate_stats{};   // (gated: counted by submit; the rest is read from gstats)
     DevBuf<unsigned long long> gstats;
-    ~EnginePoseMasks()
-    {
-        for (hipEvent_t ev : ev_start) if (ev) (void)hipEventDestroy(ev);
-        for (hipEvent_t ev : ev_stop) if (ev) (void)hipEventDestroy(ev);
-    }
 };
 
 // Track quality on the engine (roft_engine_enable_quality): one record per (frame, object) in a ring of the log's capacity, written by
@@ -488,13 +436,8 @@ struct EngineQuality {
     roft_quality_params prm{};
     DevBuf<QualityRaw> ring;             // [cap][objects]
     int cap = 0;
-    hipEvent_t ev_start[8] = {}, ev_done[8] = {};   // per batch-ring slot: bound to the launch's dispatch; ev_done is what the host waits for
+    Event ev_start[8], ev_done[8];   // per batch-ring slot: bound to the launch's dispatch; ev_done is what the host waits for
     int last_slot = -1;                  // batch-ring slot of the last launch
-    ~EngineQuality()
-    {
-        for (hipEvent_t ev : ev_start) if (ev) (void)hipEventDestroy(ev);
-        for (hipEvent_t ev : ev_done) if (ev) (void)hipEventDestroy(ev);
-    }
 };
 
 // Device copies of HOST inputs: a ring of `retain` frame slots, each a bump allocator over chunks of device memory that
@@ -502,13 +445,9 @@ struct EngineQuality {
 // their own 640x480 depth + CV_32FC2 flow + mask streams need 239 MB per slot, a shared scene 7 MB + the masks); identical
 // host pointers within a frame (a scene shared by several objects) share one upload.
 struct StageFrame {
-    std::vector<DevBuf<unsigned char>*> chunks;
+    std::vector<DevBuf<unsigned char>> chunks;
     size_t cur = 0, used = 0;   // bump pointer: chunk index, bytes used of it
     std::vector<std::pair<const void*, void*>> seen;
-    StageFrame() = default;
-    StageFrame(StageFrame&&) = default;
-    StageFrame(const StageFrame&) = delete;
-    ~StageFrame() { for (auto* c : chunks) delete c; }
 };
 constexpr size_t kStageChunk = (size_t)32 << 20;
 
@@ -594,20 +533,25 @@ struct SubmitSnapshot {
 
 // What one batch in flight owns: a slot of the batch ring.
 struct BatchSlot {
-    hipEvent_t ev_up = nullptr;     // uploads of the batch on the device, and the flows the submit produced from camera images behind them
-    hipEvent_t ev_host = nullptr;   // ... the copies alone, where production follows them: what the HOST waits for (its buffers are its own again)
-    hipEvent_t ev_ctrl = nullptr;   // FrameCtrl blocks of the batch on the device (and the mask chain of the batch before)
-    hipEvent_t ev_mask = nullptr;   // mask chain kernel of the batch complete
-    hipEvent_t ev_part = nullptr;   // the masks of the batch's frames 0 .. T - 2 complete (what its flow measurements read)
-    hipEvent_t ev_prep = nullptr;   // control blocks + ingested masks of the batch on the device (prepared on the upload stream)
-    hipEvent_t ev_feat = nullptr;   // features of the batch complete (a feature kernel on the mask stream)
-    hipEvent_t ev_vel = nullptr;    // the batch's velocity chain complete (velocity filter AND the feature kernel behind it)
-    hipEvent_t ev_skf = nullptr;    // twists of the batch complete (the velocity filter alone: what a pose lane waits for)
-    hipEvent_t ev_done[kNumLin] = {nullptr, nullptr};   // pose chain of the batch complete (per lane)
-    template <class F> void each_event(F&& f) { for (hipEvent_t* ev : {&ev_up, &ev_host, &ev_ctrl, &ev_mask, &ev_part, &ev_prep, &ev_feat, &ev_vel, &ev_skf, &ev_done[0], &ev_done[1]}) f(*ev); }
+    Event ev_up;                   // uploads of the batch on the device, and the flows the submit produced from camera images behind them
+    Event ev_host;                 // ... the copies alone, where production follows them: what the HOST waits for (its buffers are its own again)
+    Event ev_ctrl;                 // FrameCtrl blocks of the batch on the device (and the mask chain of the batch before)
+    Event ev_mask;                 // mask chain kernel of the batch complete
+    Event ev_part;                 // the masks of the batch's frames 0 .. T - 2 complete (what its flow measurements read)
+    Event ev_prep;                 // control blocks + ingested masks of the batch on the device (prepared on the upload stream)
+    Event ev_feat;                 // features of the batch complete (a feature kernel on the mask stream)
+    Event ev_vel;                  // the batch's velocity chain complete (velocity filter AND the feature kernel behind it)
+    Event ev_skf;                  // twists of the batch complete (the velocity filter alone: what a pose lane waits for)
+    Event ev_done[kNumLin];   // pose chain of the batch complete (per lane)
+    hipError_t create_events()   // (they order streams: none takes time stamps)
+    {
+        for (Event* ev : {&ev_up, &ev_host, &ev_ctrl, &ev_mask, &ev_part, &ev_prep, &ev_feat, &ev_vel, &ev_skf, &ev_done[0], &ev_done[1]})
+            if (const hipError_t err = ev->create(hipEventDisableTiming)) return err;
+        return hipSuccess;
+    }
     DevBuf<FrameCtrl> dctrl;             // control blocks on the device
-    FrameCtrl* stage = nullptr;          // ... and their pinned staging block
-    GatherItem* gather_tab = nullptr;    // pinned table gather_copy_kernel reads (kGatherCap entries; allocated on first use)
+    PinnedBuf<FrameCtrl> stage;          // ... and their pinned staging block
+    PinnedBuf<GatherItem> gather_tab;    // pinned table gather_copy_kernel reads (kGatherCap entries; allocated on first use)
     // written by step_batch for wait_batch: which of the events the batch signals
     bool done_used[kNumLin] = {false, false};   // the lane had work
     bool vel_used = false;               // the velocity chain ended with ev_vel
@@ -648,12 +592,12 @@ struct roft_engine {
     // ROFT_HOST_PROF=1: host time of the sections of the submit call / roft_step, printed by roft_engine_destroy
     double hp_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     long hp_batches = 0;
-    std::vector<HostObject*> objs;
+    std::vector<std::unique_ptr<HostObject>> objs;
     SubmitSnapshot snapshot;               // taken when a submit call starts
     std::vector<ObjParams> h_params;
     std::vector<StageFrame> staging;       // [retain]
-    ObjState* state_host = nullptr;   // pinned landing block of roft_get_state (velocity belief + corrected pose belief)
-    int* dev_error = nullptr;         // pinned word a kernel raises when it gives up (EngineArrays::dev_error)
+    PinnedBuf<ObjState> state_host;   // pinned landing block of roft_get_state (velocity belief + corrected pose belief)
+    PinnedBuf<int> dev_error;         // pinned word a kernel raises when it gives up (EngineArrays::dev_error)
     bool submitted = false;
     PendingBatch pending;                  // the submitted (or being submitted), not yet stepped batch
     EngineFlow flow;                       // camera images -> flows (roft_engine_enable_flow)
@@ -678,7 +622,7 @@ struct roft_engine {
     // timing
     bool timing = false;
     int timing_level = 2;   // 1: only flow_measure_kernel (two events per batch), 2: every launch group
-    std::vector<hipEvent_t> tev;
+    std::vector<Event> tev;
     std::vector<std::string> tnames_s;
     std::vector<const char*> tnames;
     std::vector<float> tms;

@@ -41,7 +41,7 @@ int roft::host::pose_errors_run(PoseErrorScratch& sc, int kind, const double* d_
     if (kind == ROFT_POSE_ERROR_ADDS) HIP_TRY(sc.cloud.ensure((size_t)chunk * P_pad * 3));
     HIP_TRY(sc.partial.ensure((size_t)chunk * waves));
     HIP_TRY(sc.out.ensure((size_t)n));
-    if (!sc.ev0) { HIP_TRY(hipEventCreate(&sc.ev0)); HIP_TRY(hipEventCreate(&sc.ev1)); }
+    if (!sc.ev0) { HIP_TRY(sc.ev0.create()); HIP_TRY(sc.ev1.create()); }
     const PoseView ref_dev{sc.ref.p, 7, 0, 0};
     HIP_TRY(hipEventRecord(sc.ev0, s));
     for (int f0 = 0; f0 < n; f0 += chunk)   // (in order on one stream: a launch re-uses the scratch of the one before)

@@ -56,8 +56,8 @@ int roft_engine_enable_quality(roft_engine* e, const roft_quality_params* p)
     // nothing of the launch may happen for the first time inside a caller's timed region (engine_setup): each event pair has
     // completed one dispatch on the stream that will carry it
     for (int i = 0; i < roft_engine::kBatchRing; ++i) {
-        if (!q.ev_start[i]) HIP_TRY(hipEventCreate(&q.ev_start[i]));
-        if (!q.ev_done[i]) HIP_TRY(hipEventCreate(&q.ev_done[i]));
+        HIP_TRY(q.ev_start[i].create());
+        HIP_TRY(q.ev_done[i].create());
         hipExtLaunchKernelGGL(probe_tiny_kernel, dim3(1), dim3(64), 0, e->pose_stream[kNumLin - 1], q.ev_start[i], q.ev_done[i], 0,
                               reinterpret_cast<int*>(q.ring.p));
     }

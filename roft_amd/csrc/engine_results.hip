@@ -19,12 +19,12 @@ int roft_get_state(roft_engine* e, int id, double pose13[13], double P12[144], d
     // last writer of what is returned), then the other chains are waited for as roft_sync does
     static_assert(B_LIN0 == 0 && B_LIN1 == 1 && offsetof(ObjState, v_mean) == 0, "roft_get_state copies the head of ObjState");
     constexpr size_t kHead = offsetof(ObjState, belief) + kNumLin * sizeof(PoseBelief);
-    if (!e->state_host) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->state_host), sizeof(ObjState)));
+    HIP_TRY(e->state_host.ensure(1));   // (allocated by the first call)
     const int lin = e->objs[id]->stepped_slot;
     hipStream_t last = e->multi() ? e->pose_stream[e->objs[id]->stepped_lane] : e->stream;
-    HIP_TRY(hipMemcpyAsync(e->state_host, e->arr.state.p + id, kHead, hipMemcpyDeviceToHost, last));
+    HIP_TRY(hipMemcpyAsync(e->state_host.p, e->arr.state.p + id, kHead, hipMemcpyDeviceToHost, last));
     if (int rc = roft_sync(e)) return rc;
-    const ObjState* st = e->state_host;
+    const ObjState* st = e->state_host.p;
     if (pose13) std::memcpy(pose13, st->belief[B_LIN0 + lin].mean, sizeof(double) * 13);
     if (P12) std::memcpy(P12, st->belief[B_LIN0 + lin].cov, sizeof(double) * 144);
     if (twist6) std::memcpy(twist6, st->v_mean, sizeof(double) * 6);
@@ -157,10 +157,11 @@ int roft_engine_enable_timing(roft_engine* e, int enable)
         // before it, and the velocity stream has carried a dispatch with a start / stop event pair (the first such dispatch
         // switches the queue's profiling on -- a host call of its own kind; one bench run in twenty spent 1.3 ms of a 1.4 ms
         // window on the host side of its launches).
+        e->tev.reserve(256);
         while (e->tev.size() < 64) {
-            hipEvent_t ev;
-            HIP_TRY(hipEventCreate(&ev));
-            e->tev.push_back(ev);
+            Event ev;
+            HIP_TRY(ev.create());
+            e->tev.push_back(std::move(ev));
         }
         e->tmark.reserve(256);
         e->tstream.reserve(256);

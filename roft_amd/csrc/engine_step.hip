@@ -61,9 +61,8 @@ static hipEvent_t push_mark(roft_engine* e, const char* name, int which)
 {
     const size_t idx = e->tmark.size();
     while (e->tev.size() <= idx) {
-        hipEvent_t ev;
-        (void)hipEventCreate(&ev);
-        e->tev.push_back(ev);
+        e->tev.emplace_back();
+        (void)e->tev.back().create();   // (a creation that fails leaves a null event: the mark is not recorded and roft_engine_get_timing reports it)
     }
     int id = -1;
     if (name) {
@@ -219,14 +218,14 @@ static int enqueue_preparation(Enqueue& q)
         if (!p.prep) tmark(e, "pose_silhouettes", 0);
         return ROFT_OK;
     };
-    if (p.try_fused && launch_ctrl_ingest(q.cur.stage, a, n16, pb.facts.plain_mask_frames, sp, ctrl_stop)) {
+    if (p.try_fused && launch_ctrl_ingest(q.cur.stage.p, a, n16, pb.facts.plain_mask_frames, sp, ctrl_stop)) {
         ++q.launches;
         CHECK_LAUNCH("FrameCtrl upload + mask ingest");
         if (p.label_ingest) TRY(label_ingest());
         return p.pose_silhouettes ? pose_silhouettes() : ROFT_OK;
     }
     hipExtLaunchKernelGGL(ctrl_upload_kernel, dim3((unsigned)std::min<size_t>((n16 + 255) / 256, 64)), dim3(256), 0, sp, nullptr, ctrl_stop, 0,
-                          reinterpret_cast<const uint4*>(q.cur.stage), a, n16, 1);
+                          reinterpret_cast<const uint4*>(q.cur.stage.p), a, n16, 1);
     ++q.launches;
     CHECK_LAUNCH("FrameCtrl upload");
     int last = -1;
@@ -500,7 +499,7 @@ int roft_step(roft_engine* e)
         roft_batch_trace& tr = e->trace[e->batch_counter % roft_engine::kTraceRing];
         if (tr.batch == e->batch_counter) tr.step_us = host_now_us() - t_step0;
     }
-    for (HostObject* ho : e->objs) { ho->stepped_slot = ho->s.cur_slot; ho->stepped_lane = ho->s.own[ho->s.cur_slot]; ho->stepped_flow = ho->s.flow_made; ho->stepped_depth = ho->s.depth_prev; ho->last_out_valid = false; }
+    for (const auto& ho : e->objs) { ho->stepped_slot = ho->s.cur_slot; ho->stepped_lane = ho->s.own[ho->s.cur_slot]; ho->stepped_flow = ho->s.flow_made; ho->stepped_depth = ho->s.depth_prev; ho->last_out_valid = false; }
     // (a failed step leaves the engine consistent as far as the host can tell: the batch counts as enqueued)
     const int T = e->pending.facts.T;
     e->frame_counter += T;

@@ -124,15 +124,15 @@ static int stage_alloc(roft_engine* e, int frame, size_t bytes, unsigned char** 
 {
     StageFrame& sf = e->staging[frame % e->retain];
     const size_t need = (bytes + 255) & ~(size_t)255;
-    while (sf.cur < sf.chunks.size() && sf.used + need > sf.chunks[sf.cur]->n) { ++sf.cur; sf.used = 0; }
+    while (sf.cur < sf.chunks.size() && sf.used + need > sf.chunks[sf.cur].n) { ++sf.cur; sf.used = 0; }
     if (sf.cur == sf.chunks.size()) {
-        auto* c = new DevBuf<unsigned char>();
-        const hipError_t err = c->ensure(std::max(need, kStageChunk));
-        if (err != hipSuccess) { delete c; return fail(ROFT_ERR_DEVICE, std::string("HOST staging memory: ") + hipGetErrorString(err)); }
-        sf.chunks.push_back(c);
+        DevBuf<unsigned char> c;
+        const hipError_t err = c.ensure(std::max(need, kStageChunk));
+        if (err != hipSuccess) return fail(ROFT_ERR_DEVICE, std::string("HOST staging memory: ") + hipGetErrorString(err));
+        sf.chunks.push_back(std::move(c));
         sf.used = 0;
     }
-    *out = sf.chunks[sf.cur]->p + sf.used;
+    *out = sf.chunks[sf.cur].p + sf.used;
     sf.used += need;
     return ROFT_OK;
 }
@@ -155,14 +155,14 @@ static int flush_gather(roft_engine* e)
 {
     std::vector<GatherItem>& gather = e->pending.gather;
     if (gather.empty()) return ROFT_OK;
-    GatherItem*& tab = e->slot_of(e->batch_counter).gather_tab;
-    if (!tab) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&tab), sizeof(GatherItem) * kGatherCap, hipHostMallocMapped));
+    PinnedBuf<GatherItem>& tab = e->slot_of(e->batch_counter).gather_tab;
+    HIP_TRY(tab.ensure(kGatherCap, hipHostMallocMapped));   // (allocated on the slot's first use)
     const size_t n = gather.size();
-    std::memcpy(tab, gather.data(), sizeof(GatherItem) * n);
+    std::memcpy(tab.p, gather.data(), sizeof(GatherItem) * n);
     size_t largest = 0;
     for (const GatherItem& g : gather) largest = std::max(largest, g.bytes);
     const unsigned gx = (unsigned)std::max<size_t>(1, std::min<size_t>(32, (largest / 16 + 2047) / 2048));   // ~8 units per thread
-    hipLaunchKernelGGL(gather_copy_kernel, dim3(gx, (unsigned)n), dim3(256), 0, e->up_stream, tab);
+    hipLaunchKernelGGL(gather_copy_kernel, dim3(gx, (unsigned)n), dim3(256), 0, e->up_stream, tab.p);
     gather.clear();
     if (hipError_t le = hipGetLastError()) return fail(ROFT_ERR_DEVICE, std::string("gather copy of HOST inputs: ") + hipGetErrorString(le));
     e->stats.h2d_copies++;
@@ -278,7 +278,7 @@ static int enqueue_flow_production(roft_engine* e, int T)
         const int gen = (e->frame_counter + t) % G;
         for (size_t i = 0; i < jobs[t].images.size(); ++i) {
             const int k = im.n++;
-            im.type[k] = jobs[t].images[i].type; im.src[k] = jobs[t].images[i].dev; im.pyr[k] = f.pyr[gen][i]->p;
+            im.type[k] = jobs[t].images[i].type; im.src[k] = jobs[t].images[i].dev; im.pyr[k] = f.pyr[gen][i].p;
             if (im.n == kOfChunk) { launch_of_pyramids(f.geom, im, e->up_stream); im.n = 0; }
         }
     }
@@ -297,15 +297,15 @@ static int enqueue_flow_production(roft_engine* e, int T)
         for (const FlowPairJob& pj : jobs[t].pairs) {
             if (f.check) {   // (CV_32FC2 only: the product's place is the forward field)
                 const int k = pr.n;
-                of_check_put(pr, ck, f.pyr[gen_prev][pj.pyr0]->p, f.pyr[gen][pj.pyr1]->p, reinterpret_cast<float*>(pj.out),
+                of_check_put(pr, ck, f.pyr[gen_prev][pj.pyr0].p, f.pyr[gen][pj.pyr1].p, reinterpret_cast<float*>(pj.out),
                              f.coarse.p + (size_t)k * f.geom.flow_stride, f.coarse.p + (size_t)(kOfCheckChunk + k) * f.geom.flow_stride,
                              f.back.p + (size_t)k * field_floats);
                 if (pr.n == kOfCheckChunk) launch_checked();
                 continue;
             }
             const int k = pr.n++;
-            pr.pyr0[k] = f.pyr[gen_prev][pj.pyr0]->p;
-            pr.pyr1[k] = f.pyr[gen][pj.pyr1]->p;
+            pr.pyr0[k] = f.pyr[gen_prev][pj.pyr0].p;
+            pr.pyr1[k] = f.pyr[gen][pj.pyr1].p;
             pr.coarse[k] = f.coarse.p + (size_t)k * f.geom.flow_stride;
             pr.field[k] = s16 ? f.field.p + (size_t)k * field_floats : reinterpret_cast<float*>(pj.out);
             pr.out_s16[k] = s16 ? reinterpret_cast<int16_t*>(pj.out) : nullptr;
@@ -326,7 +326,7 @@ static int enqueue_depth_production(roft_engine* e)
 {
     EngineDepth& d = e->depth;
     const size_t npix = (size_t)e->cfg.cam.width * e->cfg.cam.height;
-    if (!d.ev0) { HIP_TRY(hipEventCreate(&d.ev0)); HIP_TRY(hipEventCreate(&d.ev1)); }
+    if (!d.ev0) { HIP_TRY(d.ev0.create()); HIP_TRY(d.ev1.create()); }
     HIP_TRY(hipEventRecord(d.ev0, e->up_stream));
     DepthJobs jobs{};
     auto launch = [&]() {
@@ -477,11 +477,11 @@ static int plan_flow_product(roft_engine* e, const FrameJob& j, const ImageSizes
         if (pyr_cur < 0) {
             pyr_cur = (int)fj.images.size();
             fj.images.push_back(FlowImageJob{d.image, j.fim->image_type});
-            std::vector<DevBuf<float>*>& gen = f.pyr[(size_t)j.frame % f.pyr.size()];
+            std::vector<DevBuf<float>>& gen = f.pyr[(size_t)j.frame % f.pyr.size()];
             if ((int)gen.size() <= pyr_cur) {
-                auto* pb = new DevBuf<float>();
-                gen.push_back(pb);
-                HIP_TRY(pb->ensure(f.geom.pyr_stride));
+                DevBuf<float> pb;
+                HIP_TRY(pb.ensure(f.geom.pyr_stride));
+                gen.push_back(std::move(pb));
             }
             f.stats.images++;
             f.stats.pyramids++;
@@ -567,28 +567,28 @@ static int schedule_mask_source(roft_engine* e, const FrameJob& j, const ImageSi
         if (fe.owned >= 0 || o.frame_idx - fe.frame < e->hist_cap) continue;
         int k = -1;
         for (size_t q = 0; q < ho.owned.size(); ++q) {
-            bool referenced = ho.owned[q]->last_ref_frame >= e->completed_frames;
+            bool referenced = ho.owned[q].last_ref_frame >= e->completed_frames;
             for (int j2 = 0; j2 < o.n_hist && !referenced; ++j2) referenced = o.hist[j2].owned == (int)q;
             if (!referenced) { k = (int)q; break; }
         }
-        if (k < 0) { ho.owned.push_back(new OwnedFlow()); k = (int)ho.owned.size() - 1; }
-        HIP_TRY(ho.owned[k]->buf.ensure(sz.flow));
+        if (k < 0) { ho.owned.emplace_back(); k = (int)ho.owned.size() - 1; }
+        HIP_TRY(ho.owned[k].buf.ensure(sz.flow));
         if (pm.gate && fe.depth_before) {
             // the depth gate: the image the chase from this flow starts on ages out one frame BEFORE its flow; it is older than
             // anything this submit uploads or produces, so the copy needs no place behind the batch's production
-            HIP_TRY(ho.owned[k]->depth.ensure(sz.npix));   // (the float image, also where the caller's frames are the sensor's)
-            HIP_TRY(hipMemcpyAsync(ho.owned[k]->depth.p, fe.depth_before, sz.npix * sizeof(float), hipMemcpyDeviceToDevice, e->up_stream));
-            fe.depth_before = ho.owned[k]->depth.p;
+            HIP_TRY(ho.owned[k].depth.ensure(sz.npix));   // (the float image, also where the caller's frames are the sensor's)
+            HIP_TRY(hipMemcpyAsync(ho.owned[k].depth.p, fe.depth_before, sz.npix * sizeof(float), hipMemcpyDeviceToDevice, e->up_stream));
+            fe.depth_before = ho.owned[k].depth.p;
         }
         if (e->flow.enabled) {
             // (the flow may be one this very submit produces: the copy goes behind that production, in stream order)
-            pb.flow_jobs[j.t].clones.push_back(FlowCloneJob{ho.owned[k]->buf.p, fe.ptr});
+            pb.flow_jobs[j.t].clones.push_back(FlowCloneJob{ho.owned[k].buf.p, fe.ptr});
             pb.facts.produced_flows = true;
         } else {
-            HIP_TRY(hipMemcpyAsync(ho.owned[k]->buf.p, fe.ptr, sz.flow, hipMemcpyDeviceToDevice, e->up_stream));
+            HIP_TRY(hipMemcpyAsync(ho.owned[k].buf.p, fe.ptr, sz.flow, hipMemcpyDeviceToDevice, e->up_stream));
             pb.facts.had_uploads = true;
         }
-        fe.ptr = ho.owned[k]->buf.p;
+        fe.ptr = ho.owned[k].buf.p;
         fe.owned = k;
     }
     c.flow_valid = valid_flow ? 1 : 0;
@@ -620,7 +620,7 @@ static int schedule_mask_source(roft_engine* e, const FrameJob& j, const ImageSi
     c.n_hist = o.n_hist;
     for (int k = 0; k < o.n_hist; ++k) {
         c.flow[k] = o.hist[k].ptr;
-        if (o.hist[k].owned >= 0) ho.owned[o.hist[k].owned]->last_ref_frame = j.frame;
+        if (o.hist[k].owned >= 0) ho.owned[o.hist[k].owned].last_ref_frame = j.frame;
     }
     return ROFT_OK;
 }
@@ -676,7 +676,7 @@ static int submit_frames(roft_engine* e, const roft_frame_input* inputs, const r
     const roft_config& cfg = e->cfg;
     const ImageSizes sz(e);
     PendingBatch& pb = e->pending;
-    FrameCtrl* blk = e->slot_of(e->batch_counter).stage;
+    FrameCtrl* blk = e->slot_of(e->batch_counter).stage.p;
     {
         // Balance of the two pose chain lanes.  A lane's launch lasts as long as its busiest object, so the lanes only
         // overlap if, in every batch, the re-sync replays of all objects are on ONE lane and the ordinary steps in
@@ -870,8 +870,8 @@ int roft_engine_enable_flow(roft_engine* e, const roft_of_params* p)
     of_geometry(f.geom, cfg.cam.width, cfg.cam.height, prm.levels, prm.radius, prm.iterations, prm.det_min);
     HIP_TRY(f.coarse.ensure((size_t)kOfChunk * f.geom.flow_stride));
     if (cfg.flow_type == ROFT_FLOW_S16C2) HIP_TRY(f.field.ensure((size_t)kOfChunk * 2 * cfg.cam.width * cfg.cam.height));
-    for (auto& g : f.pyr) for (auto* b : g) delete b;   // (enabled again with other levels: another pyramid size)
-    f.pyr.assign((size_t)e->T_max + 1, std::vector<DevBuf<float>*>());
+    f.pyr.clear();   // (enabled again with other levels: another pyramid size)
+    f.pyr.resize((size_t)e->T_max + 1);
     f.prm = prm;
     f.enabled = true;
     f.check = false;   // (enabled again: the check is asked for again, behind this call)
@@ -937,8 +937,8 @@ int roft_engine_enable_pose_masks(roft_engine* e, const int* obj_ids, int n_ids)
     // nothing of the launch may happen for the first time inside a caller's timed region (engine_setup): each event pair has completed
     // one dispatch on the streams that will carry it
     for (int i = 0; i < roft_engine::kBatchRing; ++i) {
-        if (!pm.ev_start[i]) HIP_TRY(hipEventCreate(&pm.ev_start[i]));
-        if (!pm.ev_stop[i]) HIP_TRY(hipEventCreate(&pm.ev_stop[i]));
+        HIP_TRY(pm.ev_start[i].create());
+        HIP_TRY(pm.ev_stop[i].create());
         hipExtLaunchKernelGGL(probe_tiny_kernel, dim3(1), dim3(64), 0, (i & 1) ? e->up_stream : e->stream, pm.ev_start[i], pm.ev_stop[i], 0,
                               reinterpret_cast<int*>(e->arr.a.mask_general));
     }

@@ -10,11 +10,12 @@
 #include <cmath>
 #include <string>
 
+#include "device_owned.h"
 #include "depth.h"
 
 namespace roft {
 
-int set_last_error(int code, const std::string& msg);   // engine.hip
+using host::fail;
 
 typedef unsigned u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));   // 16 bytes behind a 4-byte aligned address
 
@@ -121,26 +122,26 @@ void launch_depth_align(const DepthJobs& jobs, const DepthAlignGeom& g, hipStrea
 // ---- host-side checks (before a device is looked for) -------------------------------------------------------------------------
 int depth_check_scale(float scale)
 {
-    if (!std::isfinite(scale) || !(scale > 0.0f)) return set_last_error(ROFT_ERR_INVALID, "the depth scale (metres per unit) must be finite and > 0");
+    if (!std::isfinite(scale) || !(scale > 0.0f)) return fail(ROFT_ERR_INVALID, "the depth scale (metres per unit) must be finite and > 0");
     return ROFT_OK;
 }
 
 int depth_check_camera(const roft_camera& cam, const char* which)
 {
     const std::string w(which);
-    if (cam.width < 1 || cam.height < 1) return set_last_error(ROFT_ERR_INVALID, "the " + w + " camera's width and height must be at least 1");
+    if (cam.width < 1 || cam.height < 1) return fail(ROFT_ERR_INVALID, "the " + w + " camera's width and height must be at least 1");
     if ((size_t)cam.width * (size_t)cam.height >= ((size_t)1 << 24))
-        return set_last_error(ROFT_ERR_INVALID, "the " + w + " camera's width * height must be < 2^24");
+        return fail(ROFT_ERR_INVALID, "the " + w + " camera's width * height must be < 2^24");
     if (!std::isfinite(cam.fx) || !std::isfinite(cam.fy) || !(cam.fx > 0.0) || !(cam.fy > 0.0))
-        return set_last_error(ROFT_ERR_INVALID, "the " + w + " camera's focal lengths must be finite and > 0");
-    if (!std::isfinite(cam.cx) || !std::isfinite(cam.cy)) return set_last_error(ROFT_ERR_INVALID, "the " + w + " camera's principal point must be finite");
+        return fail(ROFT_ERR_INVALID, "the " + w + " camera's focal lengths must be finite and > 0");
+    if (!std::isfinite(cam.cx) || !std::isfinite(cam.cy)) return fail(ROFT_ERR_INVALID, "the " + w + " camera's principal point must be finite");
     return ROFT_OK;
 }
 
 int depth_check_transform(const roft_depth_source& src)
 {
-    for (float r : src.R) if (!std::isfinite(r)) return set_last_error(ROFT_ERR_INVALID, "the depth source's R must be finite");
-    for (float t : src.t) if (!std::isfinite(t)) return set_last_error(ROFT_ERR_INVALID, "the depth source's t must be finite");
+    for (float r : src.R) if (!std::isfinite(r)) return fail(ROFT_ERR_INVALID, "the depth source's R must be finite");
+    for (float t : src.t) if (!std::isfinite(t)) return fail(ROFT_ERR_INVALID, "the depth source's t must be finite");
     return ROFT_OK;
 }
 
@@ -159,33 +160,14 @@ void depth_align_geometry(DepthAlignGeom& g, const roft_depth_source& src, const
 // ---- the stand-alone operators: HOST buffers, device 0 -------------------------------------------------------------------------
 namespace {
 
-bool have_device()
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return false; }
-    return true;
-}
+using namespace roft::host;
 
-// raw (HOST, raw_bytes) -> device; `run` enqueues on the null stream; the product (out_bytes) -> out (HOST)
-template <class F>
-int run_on_host_buffers(const uint16_t* raw, size_t raw_bytes, float* out, size_t out_bytes, F&& run)
+// the one job of a round trip (device_owned.h, host_round_trip): the raw frame that went up, the product's place
+roft::DepthJobs one_job(const DevBuf<unsigned char>* in, void* out)
 {
-    uint16_t* d_raw = nullptr;
-    float* d_out = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_raw), raw_bytes);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_out), out_bytes);
-    if (e == hipSuccess) e = hipMemcpy(d_raw, raw, raw_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        roft::DepthJobs jobs{};
-        jobs.n = 1; jobs.raw[0] = d_raw; jobs.out[0] = d_out;
-        run(jobs);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost);
-    if (d_raw) (void)hipFree(d_raw);
-    if (d_out) (void)hipFree(d_out);
-    if (e != hipSuccess) return roft::set_last_error(ROFT_ERR_DEVICE, hipGetErrorString(e));
-    return ROFT_OK;
+    roft::DepthJobs jobs{};
+    jobs.n = 1; jobs.raw[0] = reinterpret_cast<const uint16_t*>(in[0].p); jobs.out[0] = static_cast<float*>(out);
+    return jobs;
 }
 
 }  // namespace
@@ -194,28 +176,33 @@ extern "C" {
 
 int roft_depth_convert(const uint16_t* raw, int W, int H, float scale, float* out)
 {
-    if (!raw || !out) return roft::set_last_error(ROFT_ERR_INVALID, "null argument");
-    if (W < 1 || H < 1) return roft::set_last_error(ROFT_ERR_INVALID, "width and height must be at least 1");
+    if (!raw || !out) return fail(ROFT_ERR_INVALID, "null argument");
+    if (W < 1 || H < 1) return fail(ROFT_ERR_INVALID, "width and height must be at least 1");
     if (int rc = roft::depth_check_scale(scale)) return rc;
-    if (!have_device()) return roft::set_last_error(ROFT_ERR_DEVICE, "no HIP device (the depth conversion has no CPU path)");
+    TRY(require_device(0, "no HIP device (the depth conversion has no CPU path)"));
     const size_t npix = (size_t)W * H;
-    return run_on_host_buffers(raw, npix * sizeof(uint16_t), out, npix * sizeof(float),
-                               [&](const roft::DepthJobs& jobs) { roft::launch_depth_convert(jobs, npix, scale, nullptr); });
+    return host_round_trip({{raw, npix * sizeof(uint16_t)}}, out, npix * sizeof(float), [&](const DevBuf<unsigned char>* in, void* d_out) -> int {
+        roft::launch_depth_convert(one_job(in, d_out), npix, scale, nullptr);
+        return ROFT_OK;
+    });
 }
 
 int roft_depth_align(const uint16_t* raw, const roft_depth_source* src, const roft_camera* colour, float* out)
 {
-    if (!raw || !src || !colour || !out) return roft::set_last_error(ROFT_ERR_INVALID, "null argument");
-    if (src->type != ROFT_DEPTH_Z16) return roft::set_last_error(ROFT_ERR_INVALID, "the depth source's type must be ROFT_DEPTH_Z16");
+    if (!raw || !src || !colour || !out) return fail(ROFT_ERR_INVALID, "null argument");
+    if (src->type != ROFT_DEPTH_Z16) return fail(ROFT_ERR_INVALID, "the depth source's type must be ROFT_DEPTH_Z16");
     if (int rc = roft::depth_check_scale(src->scale)) return rc;
     if (int rc = roft::depth_check_camera(src->cam, "depth")) return rc;
     if (int rc = roft::depth_check_camera(*colour, "colour")) return rc;
     if (int rc = roft::depth_check_transform(*src)) return rc;
-    if (!have_device()) return roft::set_last_error(ROFT_ERR_DEVICE, "no HIP device (the depth alignment has no CPU path)");
+    TRY(require_device(0, "no HIP device (the depth alignment has no CPU path)"));
     roft::DepthAlignGeom g{};
     roft::depth_align_geometry(g, *src, *colour);
-    return run_on_host_buffers(raw, (size_t)g.Wd * g.Hd * sizeof(uint16_t), out, (size_t)g.Wc * g.Hc * sizeof(float),
-                               [&](const roft::DepthJobs& jobs) { roft::launch_depth_align(jobs, g, nullptr); });
+    return host_round_trip({{raw, (size_t)g.Wd * g.Hd * sizeof(uint16_t)}}, out, (size_t)g.Wc * g.Hc * sizeof(float),
+                           [&](const DevBuf<unsigned char>* in, void* d_out) -> int {
+                               roft::launch_depth_align(one_job(in, d_out), g, nullptr);
+                               return ROFT_OK;
+                           });
 }
 
 }  // extern "C"

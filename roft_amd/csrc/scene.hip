@@ -8,7 +8,7 @@ struct roft_scene_renderer {
     int W = 0, H = 0, device = 0, max_frames = 0, n_meshes = 0, max_verts = 0;
     float fx = 0, fy = 0, cx = 0, cy = 0;
     hipStream_t stream = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    Event ev[3];
     bool timed = false;
     std::vector<DeviceMesh> resident;   // the meshes the table below names
     DevBuf<SceneMesh> meshes;
@@ -172,22 +172,23 @@ int roft_scene_renderer_create(const roft_camera* cam, const roft_mesh* meshes, 
     if (int rc = check_meshes(meshes, n_meshes)) return rc;
     if (max_frames_per_call < 1 || max_frames_per_call > 65536) return fail(ROFT_ERR_INVALID, "max_frames_per_call must be 1 .. 65536");
     if (device < 0) return fail(ROFT_ERR_INVALID, "device must be >= 0");
-    if (roft_device_count() <= device) return fail(ROFT_ERR_DEVICE, "no such HIP device (the scene renderer has no CPU path)");
+    TRY(require_device(device, "no such HIP device (the scene renderer has no CPU path)"));
     HIP_TRY(hipSetDevice(device));
     (void)hipGetLastError();
-    roft_scene_renderer* r = new roft_scene_renderer();
-    auto bail = [&](int code, const std::string& msg) { roft_scene_renderer_destroy(r); return fail(code, msg); };
+    // (destroyed on every way out but the last)
+    struct Destroy { void operator()(roft_scene_renderer* p) const { (void)roft_scene_renderer_destroy(p); } };
+    std::unique_ptr<roft_scene_renderer, Destroy> r(new roft_scene_renderer());
     r->W = cam->width; r->H = cam->height; r->device = device; r->max_frames = max_frames_per_call; r->n_meshes = n_meshes;
     // the contract's intrinsics at divider 1 (oracle/ro_render.c: (float)(fx / divider))
     r->fx = (float)cam->fx; r->fy = (float)cam->fy; r->cx = (float)cam->cx; r->cy = (float)cam->cy;
     hipError_t e = hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking);
-    for (int k = 0; k < 3 && e == hipSuccess; ++k) e = hipEventCreate(&r->ev[k]);
-    if (e != hipSuccess) return bail(ROFT_ERR_DEVICE, std::string("stream creation: ") + hipGetErrorString(e));
+    for (int k = 0; k < 3 && e == hipSuccess; ++k) e = r->ev[k].create();
+    if (e != hipSuccess) return fail(ROFT_ERR_DEVICE, std::string("stream creation: ") + hipGetErrorString(e));
     r->resident = std::vector<DeviceMesh>((size_t)n_meshes);
     std::vector<SceneMesh> table((size_t)n_meshes);
     for (int k = 0; k < n_meshes; ++k) {
         // the caller's triangles as they are (a key's triangle index is the caller's); closed meshes get their flip bits
-        if (const int rc = r->resident[k].upload(meshes[k], MeshLayout::kCallersOrder, r->stream)) return bail(rc, std::string(last_error()));
+        TRY(r->resident[k].upload(meshes[k], MeshLayout::kCallersOrder, r->stream));
         table[k] = r->resident[k].scene_mesh();
         r->max_verts = std::max(r->max_verts, meshes[k].n_verts);
     }
@@ -195,8 +196,8 @@ int roft_scene_renderer_create(const roft_camera* cam, const roft_mesh* meshes, 
     if (e == hipSuccess && n_meshes) e = hipMemcpy(r->meshes.p, table.data(), sizeof(SceneMesh) * n_meshes, hipMemcpyHostToDevice);
     const size_t WH = (size_t)r->W * r->H;
     if (e == hipSuccess) e = r->keys.ensure((WH * max_frames_per_call + kResolvePixels - 1) / kResolvePixels * kResolvePixels);
-    if (e != hipSuccess) return bail(ROFT_ERR_DEVICE, std::string("mesh upload: ") + hipGetErrorString(e));
-    *out = r;
+    if (e != hipSuccess) return fail(ROFT_ERR_DEVICE, std::string("mesh upload: ") + hipGetErrorString(e));
+    *out = r.release();
     return ROFT_OK;
 }
 
@@ -205,10 +206,8 @@ int roft_scene_renderer_destroy(roft_scene_renderer* r)
     if (!r) return ROFT_OK;
     (void)hipSetDevice(r->device);
     if (r->stream) (void)hipStreamSynchronize(r->stream);
-    for (int k = 0; k < 3; ++k)
-        if (r->ev[k]) (void)hipEventDestroy(r->ev[k]);
     if (r->stream) (void)hipStreamDestroy(r->stream);
-    delete r;   // (the device buffers free themselves)
+    delete r;   // (the device buffers and the events free themselves)
     return ROFT_OK;
 }
 
