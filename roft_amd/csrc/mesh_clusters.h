@@ -1,5 +1,5 @@
 // mesh_clusters.h -- the triangles of a mesh cut into clusters of at most 64 triangles over at most 64 distinct vertices: what one
-// wave of the outlier test (outlier_fused_kernel<false>, k_render.hip) projects and draws at a time.  Host side except for
+// wave of the outlier test (outlier_fused_kernel<false>, draw_clusters of k_render.hip) projects and draws at a time.  Host side except for
 // cluster_faces_away, which the kernel shares with the CPU test (tests/cpp/cluster_check.cpp compiles this header without HIP).
 //
 // A cluster is grown inside one of the 24 normal-direction buckets of a closed mesh's walk order (mesh_class.h) -- it never crosses

@@ -2,7 +2,8 @@
 // projection, scan conversion of one projected triangle -- and the mesh walk around it: the vertex pass (project_mesh), the corner
 // fetch (fetch_triangle), the back-face rule's guard (cull_table / cull_code) and the LDS arithmetic of a launcher.  Shared by the
 // outlier test (k_render.hip), track quality (k_quality.hip), masks from poses (k_silhouette.hip) and the scene renderer
-// (k_scene.hip); every translation unit that includes it is built with -ffp-contract=off.
+// (k_scene.hip); every translation unit that includes it is built with -ffp-contract=off.  The numerics of the outlier test's other
+// render mode, ROFT_RENDER_GL, stand next to it in raster_gl.h.
 #pragma once
 
 #include "roft_device.h"

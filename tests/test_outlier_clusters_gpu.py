@@ -105,6 +105,9 @@ def test_render_depth_of_every_mesh_and_pose(oracle, refs, name, div):
 
 SHAPES = [dict(bands=b, forced=f) for b in (1, 2, 3, 8) for f in (0, 1)] + [dict(bands=0, forced=-1), dict(bands=1, window_pixels=TW, forced=-1),
                                                                             dict(bands=8, window_pixels=TW, forced=1), dict(bands=2, window_pixels=3 * TW, forced=0)]
+# The slab merge has a branch per number of other slabs (G - 1): bands 2, 3 and 8 above reach 1, 2 and 7, bands 6 and 7 the shared
+# branch of five and six real slabs with the spare pointers repeated.
+SHAPES += [dict(bands=6, forced=1), dict(bands=7, forced=1)]
 
 
 @pytest.mark.parametrize("div", [1, 2])
@@ -114,8 +117,8 @@ SHAPES = [dict(bands=b, forced=f) for b in (1, 2, 3, 8) for f in (0, 1)] + [dict
                                          ("box", ("q 2 % off unit length", "in view")), ("box_reversed", ("in view", "half off the target")),
                                          ("box_open", ("in view", "camera inside")), ("one_triangle", ("in view", "in view, close"))])
 def test_outlier_test_in_every_launch_shape(oracle, refs, name, labels, div):
-    """parts 1, 2, 3 and 8 with roft_debug_outlier_split 0 and 1, the library's own choice, and windows forced down to one row and to
-    three (strips); alternative k is the pose `labels[k]`, the scene shows the mesh at the first pose of the list."""
+    """parts 1, 2, 3 and 8 with roft_debug_outlier_split 0 and 1, parts 6 and 7 with 1, the library's own choice, and windows forced down
+    to one row and to three (strips); alternative k is the pose `labels[k]`, the scene shows the mesh at the first pose of the list."""
     v, t, _ = _meshes()[name]
     cam = _camera(div)
     ocam = util.oracle_camera(oracle, cam)
