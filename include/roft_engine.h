@@ -674,7 +674,8 @@ int roft_engine_enable_flow_consistency(roft_engine* e, const roft_of_consistenc
  * Deviation from librealsense, on purpose: rs2::align rounds both corners to nearest and fills inclusively, which takes a 2 x 2
  * minimum even under identity and drops footprints that are partly outside the image; this contract uses centres in a half-open
  * footprint and clips.  (librealsense was not at hand when this was written: that description of it is RECALLED, not read.)
- * Not modelled: lens distortion, colour aligned to depth, per-object depth formats.
+ * Not modelled: a distorted depth camera of its own (section 3g rectifies what is in the colour camera), colour aligned to depth,
+ * per-object depth formats.
  *
  * Refusals, all on the host before anything is enqueued, nothing consumed.  ROFT_ERR_STATE: enabling after the first frame.
  * ROFT_ERR_INVALID: a NULL argument; an unknown type; a scale that is not finite or not > 0; align == 0 with a size other than
@@ -686,14 +687,14 @@ typedef struct {
     int   type;        /* ROFT_DEPTH_* */
     float scale;       /* metres per unit (RealSense: 0.001f); finite, > 0 */
     int   align;       /* 0: the frame is already in the engine's camera (size must equal roft_config::cam; cam/R/t ignored) */
-    roft_camera cam;   /* align != 0: the DEPTH camera, any width, height >= 1, pinhole, no distortion */
+    roft_camera cam;   /* align != 0: the DEPTH camera, any width, height >= 1, pinhole (its own lens distortion is not modelled) */
     float R[9];        /* row-major; P_colour = R * P_depth + t */
     float t[3];        /* metres */
 } roft_depth_source;
 /* before the first frame */
 int roft_engine_enable_raw_depth(roft_engine* e, const roft_depth_source* src);
 /* the float depth (roft_config::cam: H x W) the engine made for obj's last stepped frame -> host buffer; syncs; ROFT_ERR_STATE on an
- * engine without raw depth or before the first step */
+ * engine that makes no depth (neither raw depth nor the rectification of section 3g) or before the first step */
 int roft_engine_get_depth(roft_engine* e, int obj_id, float* depth_out);
 typedef struct {
     long long images;       /* distinct raw images taken in */
@@ -705,6 +706,94 @@ int roft_engine_get_depth_stats(roft_engine* e, roft_engine_depth_stats* out);
  * camera's size; src->align is not looked at, src->cam / R / t always are).  Any W, H >= 1. */
 int roft_depth_convert(const uint16_t* raw, int W, int H, float scale, float* out);
 int roft_depth_align(const uint16_t* raw, const roft_depth_source* src, const roft_camera* colour, float* out);
+
+/* ---- (3g) lens distortion: frames rectified into the pinhole camera on the device ------------------------------------- *
+ * A real colour camera has Brown-Conrady coefficients; ignored, pixels near the border move by whole pixels, which biases the
+ * flow-to-twist Jacobian ((u - cx) / fx), the depth back-projection and every render-against-depth comparison.  On an engine with
+ * roft_engine_enable_rectification the caller hands over the DISTORTED frames as the sensor delivers them and the engine resamples
+ * them into its pinhole camera roft_config::cam on the device, once per distinct image, before anything else reads them.
+ *
+ * MODEL.  OpenCV's Brown-Conrady model with identity rectification rotation (the float counterpart of initUndistortRectifyMap).
+ * A roft_lens holds the SOURCE (sensor) camera and k1, k2, p1, p2, k3; the target is a pinhole roft_camera.  All doubles are
+ * converted to float once; everything below is float, one rounded operation per written operation, nothing contracted.
+ *
+ * MAP.  For target pixel (u, v), with (fx, fy, cx, cy) the target's and (fx_s, fy_s, cx_s, cy_s) the source's intrinsics:
+ *     x = ((float)u - cx) / fx;  y = ((float)v - cy) / fy
+ *     xx = x*x;  yy = y*y;  xy = x*y;  r2 = xx + yy
+ *     rad = 1 + r2*(k1 + r2*(k2 + r2*k3))                     the innermost product first
+ *     tx  = (2*p1)*xy + p2*(r2 + 2*xx)
+ *     ty  = p1*(r2 + 2*yy) + (2*p2)*xy
+ *     xd  = x*rad + tx;  yd = y*rad + ty
+ *     sx  = xd*fx_s + cx_s;  sy = yd*fy_s + cy_s
+ * roft_rectify_map writes (sx, sy).  The float map's distance from the same formula evaluated in double, with the lens of the
+ * engine test (k1 -0.05, k2 0.01, p1 0.001, p2 0.0005, k3 0; source focal lengths x 1.02 / x 0.99, principal point moved by
+ * (0.7, -0.4)) and a target focal length of 0.95 x the width: at most 5.6e-6 px at 64 x 48, 9.7e-5 px at 640 x 480, 1.9e-4 px at
+ * 1280 x 720 and 2.5e-4 px at 1920 x 1080 -- the rounding of coordinates of that magnitude (recorded, not asserted).
+ *
+ * NEAREST (depth as Z16 or float, masks, label images; W_s x H_s the source size):
+ *     jx = floorf(sx + 0.5f);  jy = floorf(sy + 0.5f)
+ *     inside = jx >= 0 && jx <= (float)(W_s-1) && jy >= 0 && jy <= (float)(H_s-1)      in float, before any conversion to an
+ *                                                                                      integer: false for anything not finite
+ *     out = inside ? src[jy][jx] : 0                          zero is already "no reading" and "background"
+ *
+ * BILINEAR (8-bit images):
+ *     sx or sy not finite: out = 0.  Otherwise x0 = floorf(sx), ax = sx - x0, and the taps are the columns
+ *     clamp(x0, 0, W_s-1) and clamp(x0 + 1, 0, W_s-1), clamped in float and then converted; rows likewise (edge-extended, like the
+ *     flow producer's images);  top = (1-ax)*p00 + ax*p01,  bot = (1-ax)*p10 + ax*p11,  val = (1-ay)*top + ay*bot,
+ *     out = (uint8)fminf(rintf(val), 255).  A colour image rectifies its three channels independently.
+ *
+ * THE ENGINE.  roft_engine_enable_rectification(e, lens): before the first frame (ROFT_ERR_STATE afterwards), in any order with
+ * the other roft_engine_enable_* calls.  The source size must equal roft_config::cam's (ROFT_ERR_INVALID otherwise); the
+ * intrinsics may differ.  Equivalence that defines the feature: the engine behaves, bit for bit, as if every frame image it is
+ * handed had been replaced by a HOST image holding the operator's product --
+ *   - inputs[].depth, float: roft_rectify(ROFT_RECTIFY_F32);
+ *   - inputs[].depth on a raw-depth engine with align == 0: the Z16 frame rectified (ROFT_RECTIFY_U16), then converted.  With
+ *     align != 0 the depth is NOT touched: the alignment already lands in the pinhole colour camera.  A distorted depth camera of
+ *     its own stays unmodelled;
+ *   - inputs[].mask: ROFT_RECTIFY_U8; label images: ROFT_RECTIFY_U8 / ROFT_RECTIFY_U16;
+ *   - camera images: G_k = roft_rectify(ROFT_RECTIFY_GRAY8) of the gray image of section 3a (the colour conversion is integer
+ *     arithmetic, fused into the taps); the flow producer sees a GRAY8 image;
+ *   - silhouettes of pose masks are drawn in the pinhole camera and are unaffected; their depth gate, track quality and the outlier
+ *     test read the rectified products because they read the frame's depth.  roft_engine_get_depth returns the frame's depth as the
+ *     kernels read it on a rectifying engine too.
+ * One product is made per distinct pointer, kind and frame however many objects name it, and it lives where, and as long as, a
+ * staged HOST image of that frame would (as the raw-depth product does).  HOST images are uploaded once as before, DEVICE images
+ * are read in place during the submit call's own enqueued work.  Production goes on the upload stream in front of the depth and the
+ * flow production: ONE launch per chunk of ROFT_RECTIFY_CHUNK jobs, every thread evaluating the map once for its four pixels and
+ * serving its jobs of the chunk from it (all of them at large images; at small ones the grid deals the jobs out in slices).  An entry that carries inputs[].flow on such an engine is refused with ROFT_ERR_INVALID,
+ * nothing consumed: a flow computed between distorted images cannot be rectified, the caller hands the image instead.
+ * An engine that does not enable the feature enqueues exactly what it did before.
+ *
+ * Not modelled: a distorted depth camera of its own (align != 0), the inverse Brown-Conrady form (coefficients that map distorted
+ * to ideal points), fisheye and rational models, a source of another size than roft_config::cam on the engine (the stand-alone
+ * operators take any), the C++ facade.
+ *
+ * Refusals of the stand-alone operators, all before a device is looked for (ROFT_ERR_INVALID): a NULL pointer, an unknown kind, a
+ * coefficient or intrinsic that is not finite, a focal length <= 0, width or height < 1, width * height >= 2^24 on either side. */
+#define ROFT_RECTIFY_GRAY8 1   /* H x W bytes, bilinear */
+#define ROFT_RECTIFY_RGB8  2   /* H x W x 3 bytes (any channel order), bilinear per channel */
+#define ROFT_RECTIFY_U8    3   /* H x W bytes, nearest: masks, 8-bit label images */
+#define ROFT_RECTIFY_U16   4   /* H x W uint16, nearest: Z16 depth, 16-bit label images */
+#define ROFT_RECTIFY_F32   5   /* H x W floats, nearest: depth in metres */
+#define ROFT_RECTIFY_CHUNK 32  /* jobs one launch of the engine serves */
+typedef struct {
+    roft_camera cam;           /* the SOURCE (sensor) camera: the size of the distorted frames and their intrinsics */
+    double k1, k2, p1, p2, k3; /* OpenCV's order of distCoeffs */
+} roft_lens;
+/* the source camera = `target`, all coefficients 0: rectifies every image onto itself */
+int roft_default_lens(roft_lens* lens, const roft_camera* target);
+/* map_out: target H x W x 2 floats (sx, sy).  HOST buffer, device 0. */
+int roft_rectify_map(const roft_lens* lens, const roft_camera* target, float* map_out);
+/* src: one image of the lens' source size in the layout of `kind` (ROFT_RECTIFY_*); out: the same layout at the target's size.
+ * HOST buffers, device 0. */
+int roft_rectify(const void* src, int kind, const roft_lens* lens, const roft_camera* target, void* out);
+int roft_engine_enable_rectification(roft_engine* e, const roft_lens* lens);
+typedef struct {
+    long long sources;    /* distinct images taken in (per frame) */
+    long long products;   /* rectified images made: one per distinct (image, kind) of a frame */
+    long long bytes;      /* source bytes + product bytes of those products */
+} roft_engine_rectify_stats;   /* since roft_engine_create */
+int roft_engine_get_rectify_stats(roft_engine* e, roft_engine_rectify_stats* out);
 
 /* ---- (3d) track quality: silhouette overlap and depth residual of every estimate --------------------------------------- *
  * The outlier test scores two alternatives, on frames where a delayed pose arrives, against features buffered earlier.  Track
@@ -1048,6 +1137,9 @@ int roft_debug_scene_kernel_ms(roft_scene_renderer* r, double ms_out[2]);
 /* device time in milliseconds (HIP events) of the raw-depth kernels the engine's last submit call enqueued (section 3c), without its
  * copies; waits for them.  ROFT_ERR_STATE when that call made no depth product. */
 int roft_debug_depth_kernel_ms(roft_engine* e, double* ms_out);
+/* device time in milliseconds (HIP events) of the rectification launches the engine's last submit call enqueued (section 3g), without
+ * its copies; waits for them.  ROFT_ERR_STATE when that call made no rectified product. */
+int roft_debug_rectify_kernel_ms(roft_engine* e, double* ms_out);
 /* device time in milliseconds (the HIP events bound to its dispatch) of the engine's last quality launch (section 3d); waits for it.
  * ROFT_ERR_STATE when there was none. */
 int roft_debug_quality_kernel_ms(roft_engine* e, double* ms_out);

@@ -32,6 +32,8 @@ LABEL_U8, LABEL_U16 = 1, 2          # ROFT_LABEL_*
 IMAGE_GRAY8, IMAGE_BGR8, IMAGE_RGB8 = 1, 2, 3   # ROFT_IMAGE_*
 DEPTH_Z16 = 1                       # ROFT_DEPTH_*
 DEPTH_ALIGN_MAX_SPAN = 16           # ROFT_DEPTH_ALIGN_MAX_SPAN
+RECTIFY_GRAY8, RECTIFY_RGB8, RECTIFY_U8, RECTIFY_U16, RECTIFY_F32 = 1, 2, 3, 4, 5   # ROFT_RECTIFY_*: bilinear, bilinear, nearest x 3
+RECTIFY_CHUNK = 32                  # ROFT_RECTIFY_CHUNK
 SCENE_MAX_INSTANCES = 256   # ROFT_SCENE_MAX_INSTANCES
 
 
@@ -124,6 +126,16 @@ class DepthSource(C.Structure):
 class EngineDepthStats(C.Structure):
     _c_name_ = "roft_engine_depth_stats"
     _fields_ = [("images", C.c_longlong), ("image_bytes", C.c_longlong), ("products", C.c_longlong)]
+
+
+class Lens(C.Structure):
+    _c_name_ = "roft_lens"
+    _fields_ = [("cam", Camera), ("k1", C.c_double), ("k2", C.c_double), ("p1", C.c_double), ("p2", C.c_double), ("k3", C.c_double)]
+
+
+class EngineRectifyStats(C.Structure):
+    _c_name_ = "roft_engine_rectify_stats"
+    _fields_ = [("sources", C.c_longlong), ("products", C.c_longlong), ("bytes", C.c_longlong)]
 
 
 class QualityRecord(C.Structure):
@@ -279,6 +291,12 @@ ABI = (
     Fn("roft_engine_get_depth_stats", _int, [_vp, _P(EngineDepthStats)], _OPTIONAL),
     Fn("roft_depth_convert", _int, [_vp, _int, _int, C.c_float, _vp], _OPTIONAL),
     Fn("roft_depth_align", _int, [_vp, _P(DepthSource), _P(Camera), _vp], _OPTIONAL),
+    # (3g) lens distortion
+    Fn("roft_default_lens", _int, [_P(Lens), _P(Camera)], _OPTIONAL),
+    Fn("roft_rectify_map", _int, [_P(Lens), _P(Camera), _vp], _OPTIONAL),
+    Fn("roft_rectify", _int, [_vp, _int, _P(Lens), _P(Camera), _vp], _OPTIONAL),
+    Fn("roft_engine_enable_rectification", _int, [_vp, _P(Lens)], _OPTIONAL),
+    Fn("roft_engine_get_rectify_stats", _int, [_vp, _P(EngineRectifyStats)], _OPTIONAL),
     # (3d) track quality
     Fn("roft_default_quality_params", _int, [_P(QualityParams)], _OPTIONAL),
     Fn("roft_engine_enable_quality", _int, [_vp, _P(QualityParams)], _OPTIONAL),
@@ -310,6 +328,7 @@ ABI = (
     Fn("roft_debug_pose_errors_kernel_ms", _int, [_dp], _OPTIONAL),
     Fn("roft_debug_scene_kernel_ms", _int, [_vp, _dp], _OPTIONAL),
     Fn("roft_debug_depth_kernel_ms", _int, [_vp, _dp], _OPTIONAL),
+    Fn("roft_debug_rectify_kernel_ms", _int, [_vp, _dp], _OPTIONAL),
     Fn("roft_debug_quality_kernel_ms", _int, [_vp, _dp], _OPTIONAL),
     Fn("roft_debug_pose_mask_kernel_ms", _int, [_vp, _dp], _OPTIONAL),
     Fn("roft_debug_get_dbg", _int, [_vp, _int, _P(C.c_longlong)], _OPTIONAL),

@@ -45,6 +45,7 @@
 #include "pose_mask_gate.h"
 #include "opticalflow.h"
 #include "depth.h"
+#include "rectify.h"
 #include "quality.h"
 
 static_assert(roft::host::kPlanLanes == roft::kNumLin, "batch_plan.h plans for the engine's pose lanes");
@@ -401,6 +402,21 @@ struct EngineDepth {
     bool timed = false;
 };
 
+// Lens distortion on the engine (roft_engine_enable_rectification, include/roft_engine.h section 3g): every frame image the caller
+// hands over is the sensor's distorted one; its rectified product is made on the upload stream behind the copies and in front of the
+// depth and the flow production, where a staged HOST image of the frame would have been copied (stage_alloc: it lives exactly as
+// long as one).  Planned by submit_frames on the host only (PendingBatch::rect_jobs) and enqueued when the whole batch has been
+// accepted: a refused submit leaves the device untouched.
+struct RectJob { int t; const void* src; int kind; void* out; };   // a distinct (image, kind) of frame t of the batch and its product's place
+struct EngineRectify {
+    bool enabled = false;
+    roft_lens lens{};
+    RectGeom geom{};
+    roft_engine_rectify_stats stats{};
+    Event ev0, ev1;   // around the rectification launches of the last submit (roft_debug_rectify_kernel_ms)
+    bool timed = false;
+};
+
 // Masks from poses on the engine (roft_engine_enable_pose_masks): enrolled objects take the silhouette of a delivered pose as the
 // frame's mask where no mask and no label image arrives.  One launch per delivering batch, part of its preparation (engine_step.hip).
 // The launch's events live here, one pair per slot of the batch ring; where the plan ends the preparation with the launch's stop
@@ -499,6 +515,7 @@ struct PendingBatch {
     int gated_pairs = 0;               // ... and the pairs among them that are compared with a depth image (the depth gate)
     std::vector<FlowFrameJobs> flow_jobs;   // [T] camera images: what enqueue_flow_production enqueues, frame by frame
     std::vector<DepthJob> depth_jobs;       // raw depth: what enqueue_depth_production enqueues
+    std::vector<RectJob> rect_jobs;         // lens distortion: what enqueue_rectification enqueues, in front of the two above
     // Small HOST images in PINNED memory (the per-object masks of a delivery: 64 buffers of 300 KB) are not copied one
     // hipMemcpyAsync each but fetched by ONE kernel over the bus (engine_submit.hip, gather_copy_kernel): what to fetch
     std::vector<GatherItem> gather;         // collected by stage_host, launched by flush_gather
@@ -516,19 +533,21 @@ struct PendingBatch {
         label_table_bytes = 0;
         flow_jobs.assign((size_t)T, FlowFrameJobs{});
         depth_jobs.clear();
+        rect_jobs.clear();
         gather.clear();
         lane_tests.assign((size_t)n_obj * kNumLin, -1);
     }
 };
 
 // "A refused submit consumes nothing": what roft_frames_submit_images puts back when it fails.  The schedule mirrors of every object
-// and the counters of the two producers; NOT roft_engine_stats::h2d_bytes / h2d_copies, which count what crossed the bus -- a refused
+// and the counters of the producers (flow, depth, rectification); NOT roft_engine_stats::h2d_bytes / h2d_copies, which count what crossed the bus -- a refused
 // call's copies did.  (What else a submit writes is either the PendingBatch, which the next call resets, or staging memory of the
 // batch's own frames, which the next call recycles.)
 struct SubmitSnapshot {
     std::vector<Sched> sched;
     roft_engine_flow_stats flow{};
     roft_engine_depth_stats depth{};
+    roft_engine_rectify_stats rectify{};
 };
 
 // What one batch in flight owns: a slot of the batch ring.
@@ -602,6 +621,7 @@ struct roft_engine {
     PendingBatch pending;                  // the submitted (or being submitted), not yet stepped batch
     EngineFlow flow;                       // camera images -> flows (roft_engine_enable_flow)
     EngineDepth depth;                     // raw sensor depth -> float depth (roft_engine_enable_raw_depth); its products ride on SubmitFacts::produced_flows
+    EngineRectify rectify;                 // distorted frames -> the pinhole camera (roft_engine_enable_rectification); rides on produced_flows like the depth products
     EngineQuality quality;                 // track quality (roft_engine_enable_quality)
     EnginePoseMasks pose_masks;            // masks from poses (roft_engine_enable_pose_masks)
     int prev_T = 0;                 // frames of the batch stepped before

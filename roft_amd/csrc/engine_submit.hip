@@ -345,6 +345,25 @@ static int enqueue_depth_production(roft_engine* e)
     return ROFT_OK;
 }
 
+// The rectified products of the accepted batch -> upload stream, behind the copies and in front of the depth and the flow production
+// (both read them): all distinct (image, kind) pairs of the batch in one launch per chunk of kRectChunk, pointers in the kernel arguments.
+static int enqueue_rectification(roft_engine* e)
+{
+    EngineRectify& r = e->rectify;
+    if (!r.ev0) { HIP_TRY(r.ev0.create()); HIP_TRY(r.ev1.create()); }
+    HIP_TRY(hipEventRecord(r.ev0, e->up_stream));
+    RectJobs jobs{};
+    for (const RectJob& j : e->pending.rect_jobs) {
+        jobs.src[jobs.n] = j.src; jobs.dst[jobs.n] = j.out; jobs.kind[jobs.n] = (unsigned char)j.kind;
+        if (++jobs.n == kRectChunk) { launch_rectify(jobs, r.geom, e->up_stream); jobs.n = 0; }
+    }
+    if (jobs.n) launch_rectify(jobs, r.geom, e->up_stream);
+    if (hipError_t le = hipGetLastError()) return fail(ROFT_ERR_DEVICE, std::string("rectification: ") + hipGetErrorString(le));
+    HIP_TRY(hipEventRecord(r.ev1, e->up_stream));
+    r.timed = true;
+    return ROFT_OK;
+}
+
 // ---- submit_frames: one object's frame of the batch at a time, through the stages below in their order --------------------------------
 
 struct ImageSizes {
@@ -365,7 +384,8 @@ struct FrameJob {
 };
 
 // the frame's inputs in device memory (depth: floats, or on a raw-depth engine the 16-bit frame until plan_depth_product; mask: bytes)
-struct DevInputs { const void *depth = nullptr, *flow = nullptr, *mask = nullptr, *labels = nullptr, *image = nullptr; };
+// (image_type: the camera image's as the flow producer will see it -- GRAY8 once plan_rectified_products has replaced the image)
+struct DevInputs { const void *depth = nullptr, *flow = nullptr, *mask = nullptr, *labels = nullptr, *image = nullptr; int image_type = 0; };
 
 // device or managed memory, or host memory the GPU can address as it is (hipHostMalloc / hipHostRegister: pinned and mapped --
 // zero-copy over the bus); unregistered pageable memory is what is refused
@@ -380,6 +400,9 @@ static int check_frame_forms(const roft_engine* e, const FrameJob& j)
 {
     auto obj = [&] { return "object " + std::to_string(j.id); };
     if (!j.in.depth) return fail(ROFT_ERR_INVALID, "cannot continue without a continuous depth stream (ROFTFilter.cpp:261-266)");
+    if (e->rectify.enabled && j.in.flow)
+        return fail(ROFT_ERR_INVALID, obj() + ": a flow on an engine with roft_engine_enable_rectification (a flow computed between distorted "
+                                              "images cannot be rectified: hand the camera image instead)");
     if (const roft_label_mask* lm = j.lm) {
         if (j.in.mask) return fail(ROFT_ERR_INVALID, obj() + ": a label image AND a mask for one frame (one of the two)");
         if (lm->label_type != ROFT_LABEL_U8 && lm->label_type != ROFT_LABEL_U16)
@@ -441,6 +464,40 @@ static int resolve_inputs(roft_engine* e, const FrameJob& j, const ImageSizes& s
     return ROFT_OK;
 }
 
+// Lens distortion: every image of the frame is the sensor's distorted one so far.  Each is replaced by its rectified product, which
+// goes where a staged HOST image of the frame would have been copied, one per distinct (image, kind) and frame however many objects
+// name it.  The depth of a raw-depth engine that aligns on the device is not touched: the alignment lands in the pinhole camera.
+static int plan_rectified_products(roft_engine* e, const FrameJob& j, const ImageSizes& sz, DevInputs& d)
+{
+    std::vector<RectJob>& jobs = e->pending.rect_jobs;
+    auto product = [&](const void*& img, int kind) -> int {
+        bool source_known = false;
+        for (size_t i = jobs.size(); i-- > 0 && jobs[i].t == j.t;) {
+            if (jobs[i].src != img) continue;
+            if (jobs[i].kind == kind) { img = jobs[i].out; return ROFT_OK; }
+            source_known = true;
+        }
+        unsigned char* out = nullptr;
+        TRY(stage_alloc(e, j.frame, sz.npix * rect_dst_pixel_bytes(kind), &out));
+        jobs.push_back(RectJob{j.t, img, kind, out});
+        roft_engine_rectify_stats& st = e->rectify.stats;
+        if (!source_known) st.sources++;
+        st.products++;
+        st.bytes += (long long)(sz.npix * (rect_src_pixel_bytes(kind) + rect_dst_pixel_bytes(kind)));
+        e->pending.facts.produced_flows = true;   // (production behind the copies: ev_up is recorded behind it)
+        img = out;
+        return ROFT_OK;
+    };
+    if (!(e->depth.enabled && e->depth.src.align)) TRY(product(d.depth, e->depth.enabled ? ROFT_RECTIFY_U16 : ROFT_RECTIFY_F32));
+    if (d.mask) TRY(product(d.mask, ROFT_RECTIFY_U8));
+    if (d.labels) TRY(product(d.labels, j.lm->label_type == ROFT_LABEL_U8 ? ROFT_RECTIFY_U8 : ROFT_RECTIFY_U16));
+    if (d.image) {
+        TRY(product(d.image, d.image_type == ROFT_IMAGE_GRAY8 ? ROFT_RECTIFY_GRAY8 : d.image_type == ROFT_IMAGE_BGR8 ? kRectGrayOfBgr8 : kRectGrayOfRgb8));
+        d.image_type = ROFT_IMAGE_GRAY8;
+    }
+    return ROFT_OK;
+}
+
 // Raw depth: d.depth is the device address of the 16-bit frame so far.  Its float product goes where a staged HOST depth of the frame
 // would have been copied, one per distinct raw image and frame however many objects name it.
 static int plan_depth_product(roft_engine* e, const FrameJob& j, const ImageSizes& sz, DevInputs& d)
@@ -473,10 +530,10 @@ static int plan_flow_product(roft_engine* e, const FrameJob& j, const ImageSizes
         EngineFlow& f = e->flow;
         FlowFrameJobs& fj = e->pending.flow_jobs[j.t];
         for (size_t i = 0; i < fj.images.size() && pyr_cur < 0; ++i)
-            if (fj.images[i].dev == d.image && fj.images[i].type == j.fim->image_type) pyr_cur = (int)i;
+            if (fj.images[i].dev == d.image && fj.images[i].type == d.image_type) pyr_cur = (int)i;
         if (pyr_cur < 0) {
             pyr_cur = (int)fj.images.size();
-            fj.images.push_back(FlowImageJob{d.image, j.fim->image_type});
+            fj.images.push_back(FlowImageJob{d.image, d.image_type});
             std::vector<DevBuf<float>>& gen = f.pyr[(size_t)j.frame % f.pyr.size()];
             if ((int)gen.size() <= pyr_cur) {
                 DevBuf<float> pb;
@@ -714,6 +771,8 @@ static int submit_frames(roft_engine* e, const roft_frame_input* inputs, const r
             TRY(check_frame_forms(e, j));
             j.c.dt = (j.in.dt > 0.0) ? j.in.dt : cfg.sample_time;
             TRY(resolve_inputs(e, j, sz, d));
+            if (j.fim) d.image_type = j.fim->image_type;
+            if (e->rectify.enabled) TRY(plan_rectified_products(e, j, sz, d));
             if (e->depth.enabled) TRY(plan_depth_product(e, j, sz, d));
             TRY(plan_flow_product(e, j, sz, d));
             TRY(schedule_mask_source(e, j, sz, d));
@@ -801,8 +860,10 @@ int roft_frames_submit_images(roft_engine* e, const roft_frame_input* inputs, co
     for (size_t i = 0; i < e->objs.size(); ++i) snap.sched[i] = e->objs[i]->s;
     snap.flow = e->flow.stats;
     snap.depth = e->depth.stats;
+    snap.rectify = e->rectify.stats;
     pb.reset(n_objects, n_frames);
     e->depth.timed = false;
+    e->rectify.timed = false;
     int rc = submit_frames(e, inputs, labels, images, n_objects, n_frames);
     if (rc == ROFT_OK) rc = flush_gather(e);
     HP_MARK(e, 1, hp_t);
@@ -814,7 +875,8 @@ int roft_frames_submit_images(roft_engine* e, const roft_frame_input* inputs, co
         // production; the host for ev_host, recorded behind the copies alone -- and for nothing when nothing was copied.
         hipError_t err = hipSuccess;
         if (pb.facts.had_uploads) { err = hipEventRecord(bs.ev_host, e->up_stream); ev_wait = bs.ev_host; }
-        if (err == hipSuccess && !pb.depth_jobs.empty()) rc = enqueue_depth_production(e);
+        if (err == hipSuccess && !pb.rect_jobs.empty()) rc = enqueue_rectification(e);
+        if (err == hipSuccess && rc == ROFT_OK && !pb.depth_jobs.empty()) rc = enqueue_depth_production(e);
         if (err == hipSuccess && rc == ROFT_OK && e->flow.enabled) rc = enqueue_flow_production(e, n_frames);
         if (err == hipSuccess && rc == ROFT_OK) err = hipEventRecord(bs.ev_up, e->up_stream);
         if (err != hipSuccess) rc2 = fail(ROFT_ERR_DEVICE, std::string("flow production: ") + hipGetErrorString(err));
@@ -834,6 +896,7 @@ int roft_frames_submit_images(roft_engine* e, const roft_frame_input* inputs, co
         for (size_t i = 0; i < e->objs.size(); ++i) e->objs[i]->s = snap.sched[i];
         e->flow.stats = snap.flow;
         e->depth.stats = snap.depth;
+        e->rectify.stats = snap.rectify;
         return fail(rc != ROFT_OK ? rc : rc2, msg);
     }
     e->submitted = true;
@@ -1114,7 +1177,8 @@ int roft_engine_get_depth(roft_engine* e, int obj_id, float* depth_out)
 {
     if (!e || !depth_out) return fail(ROFT_ERR_INVALID, "null argument");
     if (obj_id < 0 || obj_id >= (int)e->objs.size()) return fail(ROFT_ERR_INVALID, "bad obj_id");
-    if (!e->depth.enabled) return fail(ROFT_ERR_STATE, "the engine makes no depth: roft_engine_enable_raw_depth was not called");
+    if (!e->depth.enabled && !e->rectify.enabled)
+        return fail(ROFT_ERR_STATE, "the engine makes no depth: neither roft_engine_enable_raw_depth nor roft_engine_enable_rectification was called");
     const float* src = e->objs[obj_id]->stepped_depth;
     if (!src) return fail(ROFT_ERR_STATE, "no frame stepped yet");
     if (int rc = roft_sync(e)) return rc;
@@ -1137,6 +1201,42 @@ int roft_debug_depth_kernel_ms(roft_engine* e, double* ms_out)
     HIP_TRY(hipEventSynchronize(e->depth.ev1));
     float ms = 0.0f;
     HIP_TRY(hipEventElapsedTime(&ms, e->depth.ev0, e->depth.ev1));
+    *ms_out = (double)ms;
+    return ROFT_OK;
+}
+
+// ---- lens distortion (include/roft_engine.h section 3g) ---------------------------------------------------------------------------
+int roft_engine_enable_rectification(roft_engine* e, const roft_lens* lens)
+{
+    if (!e || !lens) return fail(ROFT_ERR_INVALID, "null argument");
+    if (e->frame_counter > 0 || e->submitted) return fail(ROFT_ERR_STATE, "roft_engine_enable_rectification must precede the first frame");
+    if (int rc = rect_check_lens(*lens)) return rc;
+    const roft_camera& cam = e->cfg.cam;
+    if (lens->cam.width != cam.width || lens->cam.height != cam.height)
+        return fail(ROFT_ERR_INVALID, "the lens' source camera must have the size of roft_config::cam (its intrinsics may differ)");
+    if (int rc = rect_check_camera(cam, "target")) return rc;
+    EngineRectify& r = e->rectify;
+    rect_geometry(r.geom, *lens, cam);
+    r.lens = *lens;
+    r.enabled = true;
+    return ROFT_OK;
+}
+
+int roft_engine_get_rectify_stats(roft_engine* e, roft_engine_rectify_stats* out)
+{
+    if (!e || !out) return fail(ROFT_ERR_INVALID, "null argument");
+    *out = e->rectify.stats;
+    return ROFT_OK;
+}
+
+int roft_debug_rectify_kernel_ms(roft_engine* e, double* ms_out)
+{
+    if (!e || !ms_out) return fail(ROFT_ERR_INVALID, "null argument");
+    if (!e->rectify.timed) return fail(ROFT_ERR_STATE, "the engine's last submit call made no rectified product");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(hipEventSynchronize(e->rectify.ev1));
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, e->rectify.ev0, e->rectify.ev1));
     *ms_out = (double)ms;
     return ROFT_OK;
 }

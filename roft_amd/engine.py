@@ -314,6 +314,26 @@ class ROFTFilterBatch:
         L.check(L.lib().roft_debug_depth_kernel_ms(self._h, C.byref(ms)))
         return ms.value
 
+    def enable_rectification(self, dist, cam=None):
+        """Lens distortion (roft_engine_enable_rectification, include/roft_engine.h section 3g): from now on every frame image --
+        depth, mask, label image, camera image -- is the sensor's DISTORTED one and is resampled into the engine's pinhole camera on
+        the device.  dist: (k1, k2, p1, p2, k3) in OpenCV's order, or a lens (ops.lens); cam: the sensor's camera (same size as the
+        engine's, its intrinsics may differ; None: the engine's).  Frames then bring no `flow` (hand the `image`).  Before the
+        first frame."""
+        from .ops import lens
+        ln = lens(dist) if hasattr(dist, "k1") else lens(self.cfg.cam if cam is None else cam, dist)   # (a lens: L.Lens, or shaped like one)
+        L.check(L.lib().roft_engine_enable_rectification(self._h, C.byref(ln)))
+
+    def rectify_stats(self):
+        """distinct sources taken in, products made, bytes (sources read + products written) since the engine was created."""
+        return self._read_stats(L.lib().roft_engine_get_rectify_stats, L.EngineRectifyStats)
+
+    def rectify_kernel_ms(self):
+        """Device time (ms, HIP events) of the rectification launches of the last submit call."""
+        ms = C.c_double(0.0)
+        L.check(L.lib().roft_debug_rectify_kernel_ms(self._h, C.byref(ms)))
+        return ms.value
+
     def enable_quality(self, every=1, depth_tolerance=0.01):
         """Track quality (roft_engine_enable_quality): from now on every frame with frame % every == 0 leaves one record per object
         -- silhouette overlap and depth residual of its final estimate against its own mask and depth.  After enable_log (whose

@@ -431,6 +431,60 @@ def depth_align(raw, depth_cam, colour_cam, scale=0.001, R=None, t=None):
     return out
 
 
+def _camera(cam):
+    return L.Camera(int(cam.width), int(cam.height), float(cam.fx), float(cam.fy), float(cam.cx), float(cam.cy))
+
+
+def lens(cam, dist=(0.0, 0.0, 0.0, 0.0, 0.0)):
+    """L.Lens of a sensor: cam is the SOURCE camera (L.Camera, or anything with width, height, fx, fy, cx, cy), dist its
+    Brown-Conrady coefficients (k1, k2, p1, p2, k3) in OpenCV's order."""
+    if isinstance(cam, L.Lens):
+        return cam
+    if hasattr(cam, "cam") and hasattr(cam, "k1"):     # anything shaped like a lens: cam, k1, k2, p1, p2, k3
+        cam, dist = cam.cam, (cam.k1, cam.k2, cam.p1, cam.p2, cam.k3)
+    k1, k2, p1, p2, k3 = (float(v) for v in dist)
+    return L.Lens(_camera(cam), k1, k2, p1, p2, k3)
+
+
+# the kind of an image by its dtype and shape, for ops.rectify: 8-bit images are resampled bilinearly unless nearest is asked for
+def _rectify_kind(img, nearest):
+    if img.dtype == np.uint8 and img.ndim == 3 and img.shape[2] == 3 and not nearest:
+        return L.RECTIFY_RGB8
+    if img.ndim != 2:
+        raise TypeError("an image to rectify is [H, W] uint8 / uint16 / float32 or [H, W, 3] uint8")
+    if img.dtype == np.uint8:
+        return L.RECTIFY_U8 if nearest else L.RECTIFY_GRAY8
+    if img.dtype == np.uint16:
+        return L.RECTIFY_U16
+    if img.dtype == np.float32:
+        return L.RECTIFY_F32
+    raise TypeError("an image to rectify is uint8, uint16 or float32, not %s" % img.dtype)
+
+
+def rectify_map(source_lens, target_cam):
+    """The map of roft_rectify_map (include/roft_engine.h section 3g): [H, W, 2] float32 (sx, sy), where in the distorted source
+    image each pixel of the pinhole camera `target_cam` reads.  source_lens: ops.lens(...)."""
+    ln, tgt = lens(source_lens), _camera(target_cam)
+    out = np.zeros((tgt.height, tgt.width, 2), np.float32)
+    L.check(L.lib().roft_rectify_map(C.byref(ln), C.byref(tgt), _p(out)))
+    return out
+
+
+def rectify(image, source_lens, target_cam, nearest=None, kind=None):
+    """The distorted image of the sensor `source_lens` (ops.lens) resampled into the pinhole camera `target_cam` by the device
+    (roft_rectify).  uint16 and float32 images (depth, labels) are sampled NEAREST; uint8 [H, W] images bilinearly unless
+    nearest=True (masks, label images); [H, W, 3] uint8 bilinearly per channel.  kind: an L.RECTIFY_* value instead."""
+    img = np.ascontiguousarray(image)
+    ln, tgt = lens(source_lens), _camera(target_cam)
+    if kind is None:
+        kind = _rectify_kind(img, bool(nearest))
+    if img.shape[:2] != (ln.cam.height, ln.cam.width):
+        raise ValueError("the image does not have the source camera's size")
+    out = np.zeros((tgt.height, tgt.width) + img.shape[2:], img.dtype)
+    L.check(L.lib().roft_rectify(_p(img), int(kind), C.byref(ln), C.byref(tgt), _p(out)))
+    return out
+
+
 class FlowProducer:
     """Batched device-resident producer (roft_flow_producer_*): `run` takes lists of device pointers."""
 

@@ -5,7 +5,7 @@
 
   render_results.py --root SEQ --mesh model.obj --poses FILE [--mesh OBJ --poses FILE ...] --out DIR
                     [--frames i,j,k] [--crop x0 y0 x1 y1] [--thumbnail FILE] [--ids DIR] [--first-frame N]
-                    [--frames-per-call 16] [--color] [--dry-run]
+                    [--frames-per-call 16] [--color] [--dry-run] [--lens k1,k2,p1,p2,k3 [--lens-camera fx,fy,cx,cy]]
 
 SEQ holds rgb/<i>.png and cam_K.json.  Every --mesh / --poses pair is one pose source: FILE is a `pose_estimate` log of this
 project or of the reference (13 columns, the pose in the last seven) or a `poses.txt` (7 columns), rows `x y z axis angle`.  Row k
@@ -18,6 +18,10 @@ over the frame as it is) and written to DIR/<i>.png.
                (that source alone) under it, 10-pixel white borders.  (The reference's sheet has one spare blank row at the bottom,
                `1 + len(paths)` rows with the RGB path already among the paths; this one has not.)
   --ids        instance maps as 8-bit PNGs DIR/<i>.png: the index of the pose source per pixel, 255 = background
+  --lens       rgb/<i>.png are the sensor's DISTORTED frames with these Brown-Conrady coefficients (--lens-camera: the sensor's
+               intrinsics where they differ from cam_K.json's): every background frame is rectified into the pinhole camera of
+               cam_K.json with the 3-channel operator (roft_rectify; include/roft_engine.h section 3g), so the overlays line up
+               (a list that starts with a minus sign is written --lens=-0.05,0.01,...)
   --dry-run    reads the poses, prints the plan as one JSON line and renders nothing (needs no GPU)
 
 An invalid pose (x = y = z = 0: the reference's spelling of "no detection") repeats the last valid pose of its source, as
@@ -118,7 +122,20 @@ def main(argv=None):
     ap.add_argument("--frames-per-call", type=int, default=16)
     ap.add_argument("--color", action="store_true")
     ap.add_argument("--dry-run", action="store_true")
+    ap.add_argument("--lens", default=None, metavar="K1,K2,P1,P2,K3")
+    ap.add_argument("--lens-camera", default=None, metavar="FX,FY,CX,CY")
     args = ap.parse_args(argv)
+    dist = sensor = None
+    if args.lens_camera is not None and args.lens is None:
+        raise SystemExit("--lens-camera needs --lens")
+    if args.lens is not None:
+        try:
+            dist = [float(v) for v in args.lens.split(",")]
+            sensor = [float(v) for v in args.lens_camera.split(",")] if args.lens_camera else None
+        except ValueError:
+            dist = []
+        if len(dist) != 5 or (sensor is not None and len(sensor) != 4):
+            raise SystemExit("--lens takes k1,k2,p1,p2,k3 and --lens-camera fx,fy,cx,cy")
     sources, frames = plan(args)
     cam_k = json.load(open(os.path.join(args.root, "cam_K.json")))
     W, H = int(cam_k["width"]), int(cam_k["height"])
@@ -126,6 +143,8 @@ def main(argv=None):
         raise SystemExit("--crop must lie inside the %d x %d image" % (W, H))
     report = dict(frames=frames, sources=len(sources), chunks=len(chunks(frames, args.frames_per_call)), width=W, height=H,
                   background_only=[[i for i in frames if not drawn[i - args.first_frame]] for _, drawn in sources])
+    if dist:
+        report["lens"] = dist
     if args.dry_run:
         print(json.dumps(report))
         return 0
@@ -141,6 +160,7 @@ def main(argv=None):
         if d:
             os.makedirs(d, exist_ok=True)
     renderer = ops.SceneRenderer(cam, meshes, max_frames_per_call=args.frames_per_call)
+    lens = ops.lens(L.Camera(W, H, *sensor) if sensor else cam, dist) if dist else None
     n_src = len(sources)
     sheet_rows = [[] for _ in range(1 + n_src)] if args.thumbnail else None
     for chunk in chunks(frames, args.frames_per_call):
@@ -149,6 +169,8 @@ def main(argv=None):
         if bg.ndim == 3:
             bg = np.repeat(bg[..., None], 3, axis=3)
         bg = np.ascontiguousarray(bg[..., :3])
+        if lens is not None:
+            bg = np.stack([ops.rectify(b, lens, cam, kind=L.RECTIFY_RGB8) for b in bg])
         poses = np.stack([p[rows] for p, _ in sources], 1)        # [chunk, source, 7]
         valid = np.stack([d[rows] for _, d in sources], 1)
         if args.out or args.ids:

@@ -6,7 +6,7 @@ files (`pose_estimate`, `velocity_estimate`, ROFTFilter.cpp:386-394) -- what `te
                   [--pose-set dope] [--out PREFIX] [--compute-flow nvof1|nvof2 | --flow-on-engine nvof1|nvof2] [--no-delay]
                   [--init-pose x y z qw qx qy qz] [--raw-depth SCALE]
                   [--start-at-first-detection] [--score-on-device] [--render-overlay DIR] [--quality FILE] [--masks-from-pose]
-                  [--pose-mask-depth-gate FRONT[,BEHIND]]
+                  [--pose-mask-depth-gate FRONT[,BEHIND]] [--lens k1,k2,p1,p2,k3 [--lens-camera fx,fy,cx,cy]]
                   [--from config_fast_ycb.cfg [--group::key value ...]]
 
 --from reads the filter parameters from one of the reference's configuration files (config/config_fast_ycb.cfg,
@@ -31,7 +31,11 @@ initial pose when it brings none).  The pose source's delay is the mask's delay 
 pose_frames_between.  --pose-mask-depth-gate FRONT[,BEHIND] (with --masks-from-pose) compares every silhouette with the depth of
 the image its pose was computed on (roft_engine_enable_pose_mask_depth_gate): pixels where the sensor saw something more than
 FRONT metres nearer than the mesh -- a hand, clutter -- are left out, and with BEHIND > 0 those where it saw something more than
-BEHIND metres farther; the report carries the gate's counts.
+BEHIND metres farther; the report carries the gate's counts.  --lens k1,k2,p1,p2,k3 (with --flow-on-engine) says that the
+directory holds the sensor's DISTORTED frames, with those Brown-Conrady coefficients (OpenCV's order): the engine rectifies depth,
+masks and camera frames into the pinhole camera of cam_K.json on the device (roft_engine_enable_rectification; include/roft_engine.h
+section 3g).  --lens-camera fx,fy,cx,cy gives the sensor's own intrinsics where they differ from cam_K.json's; the report carries
+the rectification's counts.  (A list that starts with a minus sign is written --lens=-0.05,0.01,...)
 """
 import argparse
 import json
@@ -78,6 +82,10 @@ def main(argv=None):
                     help="no segmentation masks: the engine draws the silhouette of every delivered pose on the device and tracks with it")
     ap.add_argument("--pose-mask-depth-gate", default=None, metavar="FRONT[,BEHIND]",
                     help="with --masks-from-pose: gate the silhouettes against the depth of the pose's own frame (tolerances in metres; BEHIND 0: off)")
+    ap.add_argument("--lens", default=None, metavar="K1,K2,P1,P2,K3",
+                    help="with --flow-on-engine: the frames are the sensor's distorted ones; the engine rectifies them on the device")
+    ap.add_argument("--lens-camera", default=None, metavar="FX,FY,CX,CY",
+                    help="with --lens: the sensor's intrinsics (default: those of cam_K.json)")
     ap.add_argument("--from", dest="cfg_file", default=None, help="ROFT configuration file (libconfig), overrides as --a::b::c value")
     args, overrides = ap.parse_known_args(argv)
 
@@ -98,6 +106,18 @@ def main(argv=None):
         if len(gate) not in (1, 2):
             ap.error("--pose-mask-depth-gate takes FRONT or FRONT,BEHIND (metres)")
         gate = (gate + [0.0])[:2]
+    lens = None
+    if args.lens_camera is not None and args.lens is None:
+        ap.error("--lens-camera needs --lens")
+    if args.lens is not None:
+        if not args.flow_on_engine:
+            ap.error("--lens needs --flow-on-engine (a flow computed between distorted frames cannot be rectified)")
+        try:
+            lens = [float(v) for v in args.lens.split(",")], [float(v) for v in args.lens_camera.split(",")] if args.lens_camera else None
+        except ValueError:
+            lens = [], None
+        if len(lens[0]) != 5 or (lens[1] is not None and len(lens[1]) != 4):
+            ap.error("--lens takes k1,k2,p1,p2,k3 and --lens-camera fx,fy,cx,cy")
     if args.flow_consistency and "nvof2" not in (args.compute_flow, args.flow_on_engine):
         ap.error("--flow-consistency needs --compute-flow nvof2 or --flow-on-engine nvof2 (CV_16SC2 has no invalid vector)")
     L.require_device()
@@ -177,6 +197,9 @@ def main(argv=None):
         eng.enable_flow(consistency=True if args.flow_consistency else None)
     if args.raw_depth is not None:
         eng.enable_raw_depth(args.raw_depth)
+    if lens:
+        fx, fy, cx, cy = lens[1] if lens[1] else (cfg.cam.fx, cfg.cam.fy, cfg.cam.cx, cfg.cam.cy)
+        eng.enable_rectification(lens[0], cam=L.Camera(W, H, fx, fy, cx, cy))
     if args.masks_from_pose:
         if cfg.mask_frames_between != cfg.pose_frames_between:
             sys.stderr.write("note: mask_frames_between %d != pose_frames_between %d: a silhouette is as old as its pose\n" %
@@ -208,6 +231,7 @@ def main(argv=None):
                                                               r["n_front"], r["n_behind"], r["depth_err"], o))
     pose_mask_stats = eng.pose_mask_stats() if args.masks_from_pose else None
     gate_stats = dict(eng.pose_mask_gate_stats(), front_tolerance=gate[0], behind_tolerance=gate[1]) if gate else None
+    rectify_stats = eng.rectify_stats() if lens else None
     eng.close()
     prefix = args.out if args.out is not None else os.path.join(args.root, "roft_mi355x_")
     io.write_estimate_logs(prefix, pose[:, 0], twist[:, 0])
@@ -229,7 +253,8 @@ def main(argv=None):
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import render_results
         rc = render_results.main(["--root", args.root, "--mesh", args.mesh, "--poses", prefix + "pose_estimate", "--out", args.render_overlay,
-                                  "--first-frame", str(start)])
+                                  "--first-frame", str(start)] + (["--lens=" + args.lens] if lens else []) +
+                                 (["--lens-camera=" + args.lens_camera] if lens and args.lens_camera else []))
         if rc != 0:
             return rc
         report["overlay"] = args.render_overlay
@@ -239,6 +264,8 @@ def main(argv=None):
         report["pose_masks"] = pose_mask_stats
     if gate_stats:
         report["pose_mask_gate"] = gate_stats
+    if rectify_stats:
+        report["rectification"] = rectify_stats
     print(json.dumps(report))
     return 0
 
