@@ -379,6 +379,7 @@ int roft_object_add(roft_engine* e, const roft_object_desc* desc, int* obj_id);
  *    are a burst again): restart the slots that are due in ONE call.  Restarts are served on an idle engine by plain copies; the
  *    launch graph of a batch does not know about them.
  *  - ROFT_RESTART_KEEP_MESH: descs[i].mesh is not looked at; the slot keeps its resident mesh (no upload, no classification).
+ *    A symmetry group (section 3h) goes with the mesh: the slot keeps it under KEEP_MESH and loses it when the mesh is replaced.
  *  - Refusals, all on the host before anything changes and before any wait, with the reason in roft_last_error_string.
  *    ROFT_ERR_INVALID, checked before a device is looked for: a NULL engine; n < 0, or n > 0 with a NULL array; an id outside the
  *    engine's objects; an id named twice; unknown flag bits; every check roft_object_add makes on a description; a description
@@ -1095,6 +1096,79 @@ int roft_scene_render(roft_scene_renderer* r, const roft_scene_desc* desc, uint8
 /* create + render + destroy on device 0 */
 int roft_render_scene(const roft_camera* cam, const roft_mesh* meshes, int n_meshes, const roft_scene_desc* desc, uint8_t* rgb_out,
                       float* depth_out, int32_t* instance_out, int32_t* triangle_out);
+
+/* ---- (3h) symmetric objects: equivalent poses in the pose UKF, MSSD / MSPD scores ------------------------------------------------- *
+ * A pose source returns, for a box or a can, any of the object's equivalent orientations, and which one changes from delivery to
+ * delivery.  Taken as given, a delivery that is the same pose up to a half turn of the object enters the UKF as a half-turn
+ * innovation, and the outlier test cannot reject it: the alternative renders the same depth.  An object may therefore be given its
+ * discrete symmetry group; the filter then replaces a delivered pose by its equivalent nearest to the belief it corrects, and the
+ * evaluation has BOP's MSSD and MSPD next to ADD / ADD-S.  Opt-in: an engine that never names a group enqueues and computes exactly
+ * what it did before.
+ *
+ * THE GROUP.  n elements, each a rigid transform of the object frame as 7 doubles `x y z, w x y z` (the row layout of
+ * roft_pose_errors).  If (x, q) is a pose of the object, so is (x + R(q) t_g, q (x) g).  Host checks, ROFT_ERR_INVALID with the reason
+ * in roft_last_error_string, made before a device is looked for: 1 <= n <= ROFT_MAX_SYMMETRIES for the filter and the selection
+ * operator, 1 <= n <= ROFT_MAX_SCORE_SYMMETRIES for scoring; element 0 exactly the identity 0 0 0 1 0 0 0; every component finite;
+ * | |q_g|^2 - 1 | <= 1e-6 for every element.  Closure is not checked.
+ *
+ * THE SELECTION RULE (roft_amd/csrc/symmetry.h: the kernel and the operator compile the same text).  Double precision, every product
+ * and every sum one rounded operation, no fused multiply-add.  For a belief quaternion qh, a measurement (x, m), quaternions w x y z:
+ *   p_g = m (x) g, the Hamilton product, the four terms of a component summed left to right:
+ *       p.w = m.w g.w - m.x g.x - m.y g.y - m.z g.z        p.x = m.w g.x + m.x g.w + m.y g.z - m.z g.y
+ *       p.y = m.w g.y - m.x g.z + m.y g.w + m.z g.x        p.z = m.w g.z + m.x g.y - m.y g.x + m.z g.w
+ *   c_g = | qh.w p.w + qh.x p.x + qh.y p.y + qh.z p.z |, summed left to right; a c_g that is NaN counts as -1.
+ *   g* = the element with the largest c_g, the lowest index among equal ones: the identity wins a tie.
+ *   g* = 0: the measurement is returned BIT FOR BIT AS GIVEN -- no product, no sign change (a measurement in the opposite hemisphere
+ *       of qh stays there, as it does without a group).
+ *   otherwise m' = p_g*, negated in all four components when qh . m' < 0 (the same four-term sum), and
+ *       x' = x + R(m) t_g*:  x'_i = x_i + (R_i0 t_0 + R_i1 t_1 + R_i2 t_2), R(m) in the operation order of roft_pose_errors' matrices:
+ *       R00 = 1 - 2 (yy + zz)  R01 = 2 (xy - wz)      R02 = 2 (xz + wy)
+ *       R10 = 2 (xy + wz)      R11 = 1 - 2 (xx + zz)  R12 = 2 (yz - wx)
+ *       R20 = 2 (xz - wy)      R21 = 2 (yz + wx)      R22 = 1 - 2 (xx + yy)        (m as given, not normalised)
+ * roft_pose_nearest_equivalent is that rule as a stand-alone operator in HOST arithmetic: it needs no device and looks for none.
+ * index_out (may be NULL) receives g*.  x_out / q_out may alias x / q.
+ *
+ * THE ENGINE.  roft_object_set_symmetry gives object obj_id the group sym[n_sym][7]; n_sym 0 or 1: none (sym may be NULL for 0).
+ *  - Callable before the first frame and later.  On a running engine it WAITS for every stepped batch exactly as roft_sync does and
+ *    is served by plain copies on the idle engine, as roft_objects_restart is; the launch graph of a batch does not know about it.
+ *    It takes effect from the next submitted frame.  (A call that sets none on an object that has none returns at once.)
+ *  - ROFT_ERR_INVALID, before a device is looked for: NULL engine, a bad group, n_sym < 0, an id outside the engine's objects.
+ *    ROFT_ERR_STATE: a submitted batch that has not been stepped.  A refused call changes nothing.
+ *  - roft_object_desc and ROFT_ABI_VERSION are unchanged: the group has an entry point, not a field.
+ *  - roft_objects_restart DROPS a slot's group when it replaces the mesh (the group describes the mesh) and KEEPS it with
+ *    ROFT_RESTART_KEEP_MESH.
+ *  - In the step: when the object has a group of more than one element and one of a UKF step's corrections carries the pose
+ *    (type & ROFT_MEAS_POSE), the rule runs once, after the step's prediction and before its corrections, with qh = the quaternion of
+ *    the belief the correction is applied to -- the buffered belief in a re-synchronisation step, the prediction otherwise.  Both
+ *    corrections of an outlier-rejection step see the same rewritten measurement.
+ *  - What does not change: pose masks draw the silhouette of the pose AS DELIVERED (an equivalent pose has the same silhouette);
+ *    quality records and the log's columns.  No counter is added: a pose step can be executed by more than one lane and lineage, so
+ *    a per-object "remapped" count needs a design of its own.  The C++ class facade (include/ROFT) gets no switch for it.
+ *
+ * SCORES.  roft_pose_errors_sym: for n_poses pose pairs over one point set, on the device, in double precision,
+ *   p' = R_g p_i + t_g,  a = R_r p' + t_r,  b = R_e p_i + t_e     each row R_i0 p_0 + R_i1 p_1 + R_i2 p_2 + t_i, left to right, the matrices
+ *                                                                 as above, quaternions as given
+ *   ROFT_POSE_ERROR_MSSD  sqrt( min_g max_i ( (b-a)_x^2 + (b-a)_y^2 + (b-a)_z^2 ) )                    metres
+ *   ROFT_POSE_ERROR_MSPD  the same over u = fx X / Z + cx, v = fy Y / Z + cy of a and b ((du)^2 + (dv)^2)   pixels; needs cam
+ * MSPD: a pose pair that puts any point at Z <= 0 on either side, under any element, gives +inf.  A non-finite pose gives a
+ * non-finite result and changes no other entry.  Determinism: the contract of roft_pose_errors -- out[f] is a function of (kind,
+ * points, group, camera, pose pair f) alone; max and min are exact, there are no atomics.
+ * ROFT_ERR_INVALID before a device is looked for: unknown kind, NULL pointer, n_points <= 0, n_poses < 0, a bad group, MSPD without
+ * a camera (or with non-finite intrinsics; width and height are not read).  n_poses == 0 is ROFT_OK and touches nothing.
+ * roft_engine_score_log_sym: the same for the poses of one object in the log, read in place, with the contract, the frame-range rules
+ * and the points == NULL case (the slot's current mesh) of roft_engine_score_log; MSPD projects with the engine's camera.  Equal, bit
+ * for bit, to roft_pose_errors_sym on the rows roft_engine_get_log_rows returns. */
+#define ROFT_MAX_SYMMETRIES 16
+#define ROFT_MAX_SCORE_SYMMETRIES 256
+#define ROFT_POSE_ERROR_MSSD 2   /* metres */
+#define ROFT_POSE_ERROR_MSPD 3   /* pixels; needs cam */
+int roft_pose_nearest_equivalent(const double* sym, int n_sym, const double qh[4], const double x[3], const double q[4], double x_out[3],
+                                 double q_out[4], int* index_out);
+int roft_object_set_symmetry(roft_engine* e, int obj_id, const double* sym, int n_sym);
+int roft_pose_errors_sym(int kind, const double* points, int n_points, const double* est, const double* ref, int n_poses, const double* sym,
+                         int n_sym, const roft_camera* cam, double* out);
+int roft_engine_score_log_sym(roft_engine* e, int kind, int obj_id, int first_frame, int n_frames, const double* points, int n_points,
+                              const double* ref, const double* sym, int n_sym, double* out);
 
 /* ---- (4) diagnostics (tests and profiling tools; not needed by an integration) --------------------------------- */
 /* The per-frame program builder without a device: the host-side mirror of CartesianQuaternionMeasurement::freeze's

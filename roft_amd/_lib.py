@@ -35,6 +35,8 @@ DEPTH_ALIGN_MAX_SPAN = 16           # ROFT_DEPTH_ALIGN_MAX_SPAN
 RECTIFY_GRAY8, RECTIFY_RGB8, RECTIFY_U8, RECTIFY_U16, RECTIFY_F32 = 1, 2, 3, 4, 5   # ROFT_RECTIFY_*: bilinear, bilinear, nearest x 3
 RECTIFY_CHUNK = 32                  # ROFT_RECTIFY_CHUNK
 SCENE_MAX_INSTANCES = 256   # ROFT_SCENE_MAX_INSTANCES
+MAX_SYMMETRIES, MAX_SCORE_SYMMETRIES = 16, 256   # ROFT_MAX_SYMMETRIES, ROFT_MAX_SCORE_SYMMETRIES
+POSE_ERROR_MSSD, POSE_ERROR_MSPD = 2, 3          # ROFT_POSE_ERROR_* of roft_pose_errors_sym
 
 
 class RoftError(RuntimeError):
@@ -318,6 +320,11 @@ ABI = (
     Fn("roft_scene_renderer_destroy", _int, [_vp], _OPTIONAL),
     Fn("roft_scene_render", _int, [_vp, _P(SceneDesc), _vp, _vp, _vp, _vp], _OPTIONAL),
     Fn("roft_render_scene", _int, [_P(Camera), _P(Mesh), _int, _P(SceneDesc), _vp, _vp, _vp, _vp], _OPTIONAL),
+    # (3h) symmetric objects
+    Fn("roft_pose_nearest_equivalent", _int, [_vp, _int, _vp, _vp, _vp, _vp, _vp, _ip], _OPTIONAL),
+    Fn("roft_object_set_symmetry", _int, [_vp, _int, _vp, _int], _OPTIONAL),
+    Fn("roft_pose_errors_sym", _int, [_int, _vp, _int, _vp, _vp, _int, _vp, _int, _P(Camera), _vp], _OPTIONAL),
+    Fn("roft_engine_score_log_sym", _int, [_vp, _int, _int, _int, _int, _vp, _int, _vp, _vp, _int, _vp], _OPTIONAL),
     # (4) diagnostics
     Fn("roft_debug_plan", _int, [_P(Config), _vp, _int, _vp, _vp, _vp, _vp], _OPTIONAL),
     Fn("roft_debug_restart_check", _int, [_P(Config), _int, _ip, _ip, _int, _ip, _P(ObjectDesc), _int, _int], _OPTIONAL),

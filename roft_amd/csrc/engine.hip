@@ -633,6 +633,8 @@ static int apply_object_desc(roft_engine* e, int id, HostObject* o, const roft_o
     DeviceMesh fresh;
     if (!keep_mesh) TRY(fresh.upload(d->mesh, e->cfg.render_mode == ROFT_RENDER_CONTRACT ? MeshLayout::kWalkClusters : MeshLayout::kAsItIs, s));
     (keep_mesh ? o->mesh : fresh).describe(p);
+    // the symmetry group describes the mesh: it stays with a mesh that stays and goes with one that is replaced
+    if (keep_mesh && o->n_sym > 1) { p.sym = o->sym.p; p.n_sym = o->n_sym; }
     // initialization_step (ROFTFilter.cpp:216-237)
     init_state(*st);
     for (int i = 0; i < 6; ++i) { st->v_mean[i] = d->v_mean0[i]; st->v_cov[i * 6 + i] = d->v_cov0_diag[i]; }
@@ -648,7 +650,7 @@ static int apply_object_desc(roft_engine* e, int id, HostObject* o, const roft_o
     hipError_t err = hipMemcpyAsync(e->arr.params.p + id, &live, sizeof(live), hipMemcpyHostToDevice, s);
     if (err == hipSuccess) err = hipMemcpyAsync(e->arr.state.p + id, st, sizeof(ObjState), hipMemcpyHostToDevice, s);
     if (err != hipSuccess) { live = old; return fail(ROFT_ERR_DEVICE, std::string("state upload: ") + hipGetErrorString(err)); }
-    if (!keep_mesh) o->mesh = std::move(fresh);
+    if (!keep_mesh) { o->mesh = std::move(fresh); o->n_sym = 0; }
     *mesh_uploaded = !keep_mesh && has_mesh(o->mesh);
     for (int i = 0; i < 7; ++i) o->pose0[i] = d->p_mean0[6 + i];
     return ROFT_OK;
@@ -792,5 +794,35 @@ int roft_engine_get_restart_stats(roft_engine* e, roft_engine_restart_stats* out
 {
     if (!e || !out) return fail(ROFT_ERR_INVALID, "null argument");
     *out = e->restart_stats;
+    return ROFT_OK;
+}
+
+// ---- roft_object_set_symmetry (include/roft_engine.h section 3h) --------------------------------------------------------------------
+
+int roft_object_set_symmetry(roft_engine* e, int obj_id, const double* sym, int n_sym)
+{
+    if (!e) return fail(ROFT_ERR_INVALID, "null engine");
+    if (n_sym < 0) return fail(ROFT_ERR_INVALID, "symmetry group: n_sym must be >= 0");
+    if (n_sym > 0)
+        if (const char* why = roft::sym::check(sym, n_sym, ROFT_MAX_SYMMETRIES)) return fail(ROFT_ERR_INVALID, why);
+    if (obj_id < 0 || obj_id >= (int)e->objs.size()) return fail(ROFT_ERR_INVALID, "symmetry group: bad object id");
+    if (e->submitted) return fail(ROFT_ERR_STATE, "symmetry group: a submitted batch has not been stepped (roft_step comes first)");
+    HostObject* o = e->objs[obj_id].get();
+    if (n_sym <= 1 && o->n_sym <= 1) return ROFT_OK;   // (none before, none now: nothing to copy and nothing to wait for)
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    TRY(roft_sync(e));   // every stepped batch has ended: no step reads the group or the parameter block that follow
+    hipStream_t s = e->stream;
+    if (n_sym > 1) {
+        HIP_TRY(o->sym.ensure((size_t)roft::sym::kElement * ROFT_MAX_SYMMETRIES));
+        HIP_TRY(hipMemcpyAsync(o->sym.p, sym, sizeof(double) * roft::sym::kElement * n_sym, hipMemcpyHostToDevice, s));
+    }
+    ObjParams& live = e->h_params[obj_id];
+    const ObjParams old = live;
+    live.sym = n_sym > 1 ? o->sym.p : nullptr;
+    live.n_sym = n_sym > 1 ? n_sym : 0;
+    hipError_t err = hipMemcpyAsync(e->arr.params.p + obj_id, &live, sizeof(live), hipMemcpyHostToDevice, s);
+    if (err == hipSuccess) err = hipStreamSynchronize(s);
+    if (err != hipSuccess) { live = old; return fail(ROFT_ERR_DEVICE, std::string("symmetry group upload: ") + hipGetErrorString(err)); }
+    o->n_sym = live.n_sym;
     return ROFT_OK;
 }

@@ -47,6 +47,7 @@
 #include "depth.h"
 #include "rectify.h"
 #include "quality.h"
+#include "symmetry.h"
 
 static_assert(roft::host::kPlanLanes == roft::kNumLin, "batch_plan.h plans for the engine's pose lanes");
 
@@ -256,7 +257,7 @@ struct Arrays {
 
 // Device scratch of the pose-error metrics (roft_pose_errors / roft_engine_score_log): grows on demand, kept between calls.
 struct PoseErrorScratch {
-    DevBuf<double> pts, est, ref, cloud, partial, out;
+    DevBuf<double> pts, est, ref, cloud, partial, out, sym;
     Event ev0, ev1;   // around the kernels of the last call (roft_debug_pose_errors_kernel_ms)
     bool timed = false;
 };
@@ -265,6 +266,13 @@ struct PoseErrorScratch {
 // out_host: n doubles.  Returns when the results are in out_host.
 int pose_errors_run(PoseErrorScratch& sc, int kind, const double* d_pts, int P, const double* est_host, PoseView est_dev,
                     const double* ref_host, int n, double* out_host, hipStream_t s);
+// MSSD / MSPD under a symmetry group (roft_pose_errors_sym / roft_engine_score_log_sym).  check_pose_errors_sym: the refusals the
+// two share -- unknown kind, a bad group (cap ROFT_MAX_SCORE_SYMMETRIES), MSPD without a usable camera -- on the host, no device.
+// pose_errors_sym_run: as pose_errors_run; sym_host: n_sym x 7 host doubles, cam: read for MSPD only.
+int check_pose_errors_sym(int kind, const double* sym, int n_sym, const roft_camera* cam);
+int pose_errors_sym_run(PoseErrorScratch& sc, int kind, const double* d_pts, int P, const double* est_host, PoseView est_dev,
+                        const double* ref_host, int n, const double* sym_host, int n_sym, const roft_camera* cam, double* out_host,
+                        hipStream_t s);
 
 inline void init_state(ObjState& st)
 {
@@ -344,6 +352,10 @@ struct HostObject {
     const float* stepped_depth = nullptr;     // the depth of the last stepped frame (roft_engine_get_depth reads it on a raw-depth engine)
     std::vector<OwnedFlow> owned;   // engine copies of flows that outlived the zero-copy retention window
     DeviceMesh mesh;   // what ObjParams of the object names (absent: the object was described without one)
+    // roft_object_set_symmetry: the device copy of the object's group (16 elements: allocated once, at the first group), which
+    // ObjParams::sym names while n_sym > 1.  Goes with the mesh: a restart that replaces the mesh drops it.
+    DevBuf<double> sym;
+    int n_sym = 0;
     // masks from poses (roft_engine_enable_pose_masks): the object is enrolled; the pose of roft_object_desc::p_mean0 (x, q = w x y z),
     // which stands in for a first frame that brings none
     bool pose_masks = false;

@@ -55,6 +55,47 @@ int roft::host::pose_errors_run(PoseErrorScratch& sc, int kind, const double* d_
     return ROFT_OK;
 }
 
+int roft::host::check_pose_errors_sym(int kind, const double* sym, int n_sym, const roft_camera* cam)
+{
+    if (kind != ROFT_POSE_ERROR_MSSD && kind != ROFT_POSE_ERROR_MSPD) return fail(ROFT_ERR_INVALID, "unknown symmetry-aware pose error kind");
+    if (const char* why = roft::sym::check(sym, n_sym, ROFT_MAX_SCORE_SYMMETRIES)) return fail(ROFT_ERR_INVALID, why);
+    if (kind == ROFT_POSE_ERROR_MSPD) {
+        if (!cam) return fail(ROFT_ERR_INVALID, "MSPD needs a camera");
+        if (!std::isfinite(cam->fx) || !std::isfinite(cam->fy) || !std::isfinite(cam->cx) || !std::isfinite(cam->cy))
+            return fail(ROFT_ERR_INVALID, "MSPD: the camera's intrinsics are not finite");
+    }
+    return ROFT_OK;
+}
+
+int roft::host::pose_errors_sym_run(PoseErrorScratch& sc, int kind, const double* d_pts, int P, const double* est_host, PoseView est_dev,
+                                    const double* ref_host, int n, const double* sym_host, int n_sym, const roft_camera* cam,
+                                    double* out_host, hipStream_t s)
+{
+    if (est_host) {
+        HIP_TRY(sc.est.ensure((size_t)7 * n));
+        HIP_TRY(hipMemcpyAsync(sc.est.p, est_host, sizeof(double) * 7 * n, hipMemcpyHostToDevice, s));
+        est_dev = PoseView{sc.est.p, 7, 0, 0};
+    }
+    HIP_TRY(sc.ref.ensure((size_t)7 * n));
+    HIP_TRY(hipMemcpyAsync(sc.ref.p, ref_host, sizeof(double) * 7 * n, hipMemcpyHostToDevice, s));
+    HIP_TRY(sc.sym.ensure((size_t)roft::sym::kElement * n_sym));
+    HIP_TRY(hipMemcpyAsync(sc.sym.p, sym_host, sizeof(double) * roft::sym::kElement * n_sym, hipMemcpyHostToDevice, s));
+    HIP_TRY(sc.out.ensure((size_t)n));
+    if (!sc.ev0) { HIP_TRY(sc.ev0.create()); HIP_TRY(sc.ev1.create()); }
+    const PoseView ref_dev{sc.ref.p, 7, 0, 0};
+    const SymCamera dc = cam ? SymCamera{cam->fx, cam->fy, cam->cx, cam->cy} : SymCamera{0.0, 0.0, 0.0, 0.0};
+    constexpr int kPerLaunch = 1 << 20;   // (one workgroup per pair: well inside the grid's x extent)
+    HIP_TRY(hipEventRecord(sc.ev0, s));
+    for (int f0 = 0; f0 < n; f0 += kPerLaunch)
+        launch_pose_errors_sym(kind, d_pts, P, est_dev, ref_dev, f0, std::min(kPerLaunch, n - f0), sc.sym.p, n_sym, dc, sc.out.p, s);
+    HIP_TRY(hipEventRecord(sc.ev1, s));
+    sc.timed = true;
+    HIP_TRY(hipMemcpyAsync(out_host, sc.out.p, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipGetLastError());
+    return ROFT_OK;
+}
+
 namespace {
 
 // The velocity filter's operators on plain arrays: x, P and the operator's diagonal go up as one block, `launch(c, in, out)` uploads
@@ -703,6 +744,42 @@ int roft_pose_errors(int kind, const double* points, int n_points, const double*
     HIP_TRY(sc.pts.ensure((size_t)3 * n_points));
     HIP_TRY(hipMemcpyAsync(sc.pts.p, points, sizeof(double) * 3 * n_points, hipMemcpyHostToDevice, c.stream));
     return pose_errors_run(sc, kind, sc.pts.p, n_points, est, PoseView{}, ref, n_poses, out, c.stream);
+}
+
+int roft_pose_errors_sym(int kind, const double* points, int n_points, const double* est, const double* ref, int n_poses, const double* sym,
+                         int n_sym, const roft_camera* cam, double* out)
+{
+    if (!points || !est || !ref || !out || !sym) return fail(ROFT_ERR_INVALID, "null argument");
+    if (n_points <= 0 || n_poses < 0) return fail(ROFT_ERR_INVALID, "n_points must be > 0 and n_poses >= 0");
+    TRY(check_pose_errors_sym(kind, sym, n_sym, cam));
+    if (n_poses == 0) return ROFT_OK;
+    OpContext& c = op_context();
+    std::unique_lock<std::mutex> lk;
+    TRY(c.enter(lk));
+    PoseErrorScratch& sc = c.pose_errors;
+    HIP_TRY(sc.pts.ensure((size_t)3 * n_points));
+    HIP_TRY(hipMemcpyAsync(sc.pts.p, points, sizeof(double) * 3 * n_points, hipMemcpyHostToDevice, c.stream));
+    return pose_errors_sym_run(sc, kind, sc.pts.p, n_points, est, PoseView{}, ref, n_poses, sym, n_sym, cam, out, c.stream);
+}
+
+// host arithmetic alone (symmetry.h): no device is looked for
+int roft_pose_nearest_equivalent(const double* sym, int n_sym, const double qh[4], const double x[3], const double q[4], double x_out[3],
+                                 double q_out[4], int* index_out)
+{
+    if (!qh || !x || !q || !x_out || !q_out) return fail(ROFT_ERR_INVALID, "null argument");
+    if (const char* why = roft::sym::check(sym, n_sym, ROFT_MAX_SYMMETRIES)) return fail(ROFT_ERR_INVALID, why);
+    const int g = roft::sym::select(sym, n_sym, qh, q);
+    if (g == 0) {   // the measurement as it was given, bit for bit
+        std::memmove(x_out, x, sizeof(double) * 3);
+        std::memmove(q_out, q, sizeof(double) * 4);
+    } else {
+        double xq[7];
+        roft::sym::apply(qh, x, q, sym + roft::sym::kElement * g, xq);
+        std::memcpy(x_out, xq, sizeof(double) * 3);
+        std::memcpy(q_out, xq + 3, sizeof(double) * 4);
+    }
+    if (index_out) *index_out = g;
+    return ROFT_OK;
 }
 
 int roft_debug_pose_errors_kernel_ms(double* ms_out)

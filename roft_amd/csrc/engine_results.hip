@@ -123,6 +123,34 @@ int roft_engine_score_log(roft_engine* e, int kind, int obj_id, int first_frame,
     return pose_errors_run(sc, kind, sc.pts.p, P, nullptr, est, ref, n_frames, out, e->stream);
 }
 
+int roft_engine_score_log_sym(roft_engine* e, int kind, int obj_id, int first_frame, int n_frames, const double* points, int n_points,
+                              const double* ref, const double* sym, int n_sym, double* out)
+{
+    if (!e) return fail(ROFT_ERR_INVALID, "null engine");
+    if (!ref || !out || !sym) return fail(ROFT_ERR_INVALID, "null argument");
+    TRY(check_pose_errors_sym(kind, sym, n_sym, &e->cfg.cam));
+    if (points && n_points <= 0) return fail(ROFT_ERR_INVALID, "n_points must be > 0");
+    if (obj_id < 0 || obj_id >= (int)e->objs.size()) return fail(ROFT_ERR_INVALID, "bad object id");
+    if (!e->arr.a.out_log) return fail(ROFT_ERR_INVALID, "log not enabled");
+    if (n_frames < 0 || first_frame < 0) return fail(ROFT_ERR_INVALID, "bad frame range");
+    const int n_verts = e->h_params[obj_id].n_verts;
+    if (!points && !has_mesh(e->h_params[obj_id])) return fail(ROFT_ERR_INVALID, "the object was added without a mesh: pass points");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    if (int rc = roft_sync(e)) return rc;
+    const int cap = e->arr.a.log_cap, stepped = e->frame_counter;
+    if (n_frames > cap || (long)first_frame + n_frames > stepped || first_frame < stepped - cap)
+        return fail(ROFT_ERR_INVALID, "frame range is not (or no longer) in the log");
+    if (n_frames == 0) return ROFT_OK;
+    PoseErrorScratch& sc = e->score;
+    const int P = points ? n_points : n_verts;
+    HIP_TRY(sc.pts.ensure((size_t)3 * P));
+    if (points) HIP_TRY(hipMemcpyAsync(sc.pts.p, points, sizeof(double) * 3 * P, hipMemcpyHostToDevice, e->stream));
+    else launch_float_to_double(e->h_params[obj_id].verts, 3 * P, sc.pts.p, e->stream);
+    const PoseView est{reinterpret_cast<const double*>(e->arr.a.out_log + obj_id) + 6,
+                       (long)(sizeof(roft_object_output) / sizeof(double)) * e->arr.a.n_obj, first_frame, cap};
+    return pose_errors_sym_run(sc, kind, sc.pts.p, P, nullptr, est, ref, n_frames, sym, n_sym, &e->cfg.cam, out, e->stream);
+}
+
 int roft_get_mask(roft_engine* e, int id, uint8_t* mask_out)
 {
     if (!e || !mask_out || id < 0 || id >= (int)e->objs.size()) return fail(ROFT_ERR_INVALID, "bad arguments");

@@ -22,7 +22,10 @@
 //
 // The poses are read through PoseView: rows of 7 doubles (x y z, q = w x y z) at a stride, optionally in a ring -- the host
 // arrays of roft_pose_errors and the records of the engine's log (roft_engine_score_log) go through the same kernels.
+//
+// MSSD and MSPD of the same pose pairs under a symmetry group have a kernel of their own further down (pose_error_sym_kernel).
 #include "roft_device.h"
+#include "symmetry.h"
 
 namespace roft {
 
@@ -141,6 +144,95 @@ __global__ __launch_bounds__(256) void pose_error_finish_kernel(const double* __
     double s = 0.0;
     for (int w = 0; w < waves_per_pose; ++w) s += partial[(size_t)f * waves_per_pose + w];
     out[f] = s / (double)P;
+}
+
+// ---- MSSD / MSPD (BOP: maximum symmetry-aware surface / projection distance; include/roft_engine.h section 3h) --------------------
+//   p' = R_g p_i + t_g,  a = R_r p' + t_r,  b = R_e p_i + t_e                       (pose_transform's order, load_pose's matrices)
+//   MSSD[f] = sqrt( min_g max_i |b - a|^2 ),   MSPD[f] = the same over the pixels (fx X / Z + cx, fy Y / Z + cy) of a and b
+// One workgroup of 4 waves per pose pair.  kSymBatch elements at a time: their transforms are the same for every lane (uniform
+// loads), a lane walks the points tid, tid + 256, ... once per batch and keeps one running maximum per element of the batch in
+// registers; a shuffle tree gives the maximum of a wave, the LDS that of the workgroup, and every thread folds the batch into its
+// running minimum.  A batch that the group does not fill repeats the last element (a duplicate changes no minimum).
+// Max and min are exact and keep a NaN once they have seen one (nan_max / nan_min: fmax would drop it), so out[f] is a function
+// of (kind, points, group, camera, pose pair f) and of nothing else, and a non-finite pose gives a non-finite result.
+// MSPD: a point with Z <= 0 (or NaN) under either pose, for any element, makes the pair's result +inf.
+constexpr int kSymBatch = 4;
+constexpr int kSymThreads = 64 * kPoseWaves;
+
+__device__ inline double nan_max(double a, double b) { return (b > a || b != b) ? b : a; }
+__device__ inline double nan_min(double a, double b) { return (b < a || b != b) ? b : a; }
+
+template <int KIND>
+__global__ __launch_bounds__(kSymThreads) void pose_error_sym_kernel(const double* __restrict__ pts, int P, PoseView est, PoseView ref, int f0,
+                                                                     const double* __restrict__ elems, int n_sym, SymCamera cam,
+                                                                     double* __restrict__ out)
+{
+    __shared__ double s_max[kPoseWaves][kSymBatch];
+    const int f = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const RigidPose ge = load_pose(est, f0 + f), gr = load_pose(ref, f0 + f);
+    double best = INFINITY;
+    int bad = 0;
+    for (int g0 = 0; g0 < n_sym; g0 += kSymBatch) {
+        RigidPose gs[kSymBatch];
+#pragma unroll
+        for (int k = 0; k < kSymBatch; ++k) {
+            const double* el = elems + sym::kElement * min(g0 + k, n_sym - 1);   // uniform over the workgroup
+            sym::quat_to_rot(el[3], el[4], el[5], el[6], gs[k].R);
+            gs[k].t[0] = el[0]; gs[k].t[1] = el[1]; gs[k].t[2] = el[2];
+        }
+        double m[kSymBatch];
+#pragma unroll
+        for (int k = 0; k < kSymBatch; ++k) m[k] = 0.0;
+        for (int i = tid; i < P; i += kSymThreads) {
+            const double* p = pts + 3 * (size_t)i;
+            double b[3], ub = 0.0, vb = 0.0;
+            pose_transform(ge, p, b);
+            if (KIND == ROFT_POSE_ERROR_MSPD) {
+                bad |= !(b[2] > 0.0);
+                ub = cam.fx * b[0] / b[2] + cam.cx;
+                vb = cam.fy * b[1] / b[2] + cam.cy;
+            }
+#pragma unroll
+            for (int k = 0; k < kSymBatch; ++k) {
+                double ps[3], a[3], d;
+                pose_transform(gs[k], p, ps);
+                pose_transform(gr, ps, a);
+                if (KIND == ROFT_POSE_ERROR_MSPD) {
+                    bad |= !(a[2] > 0.0);
+                    const double du = ub - (cam.fx * a[0] / a[2] + cam.cx), dv = vb - (cam.fy * a[1] / a[2] + cam.cy);
+                    d = du * du + dv * dv;
+                } else {
+                    const double dx = b[0] - a[0], dy = b[1] - a[1], dz = b[2] - a[2];
+                    d = dx * dx + dy * dy + dz * dz;
+                }
+                m[k] = nan_max(m[k], d);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kSymBatch; ++k) {
+            for (int o = 32; o > 0; o >>= 1) m[k] = nan_max(m[k], __shfl_xor(m[k], o, 64));
+            if (lane == 0) s_max[wave][k] = m[k];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < kSymBatch; ++k) {
+            double v = s_max[0][k];
+            for (int w = 1; w < kPoseWaves; ++w) v = nan_max(v, s_max[w][k]);
+            best = nan_min(best, v);
+        }
+        __syncthreads();   // (the next batch overwrites s_max)
+    }
+    if (KIND == ROFT_POSE_ERROR_MSPD) bad = __syncthreads_or(bad);
+    if (tid == 0) out[f0 + f] = bad ? INFINITY : sqrt(best);
+}
+
+void launch_pose_errors_sym(int kind, const double* pts, int P, const PoseView& est, const PoseView& ref, int f0, int n, const double* elems,
+                            int n_sym, const SymCamera& cam, double* out, hipStream_t s)
+{
+    if (kind == ROFT_POSE_ERROR_MSPD)
+        hipLaunchKernelGGL((pose_error_sym_kernel<ROFT_POSE_ERROR_MSPD>), dim3(n), dim3(kSymThreads), 0, s, pts, P, est, ref, f0, elems, n_sym, cam, out);
+    else
+        hipLaunchKernelGGL((pose_error_sym_kernel<ROFT_POSE_ERROR_MSSD>), dim3(n), dim3(kSymThreads), 0, s, pts, P, est, ref, f0, elems, n_sym, cam, out);
 }
 
 __global__ __launch_bounds__(256) void float_to_double_kernel(const float* __restrict__ in, int n, double* __restrict__ out)

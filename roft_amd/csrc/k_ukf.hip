@@ -22,6 +22,7 @@
 // outlier-rejection step needs two corrections of the same prediction they share one
 // decomposition.  Products this small (12x12x49) do not fill an MFMA tile batch; plain fp64 FMA.
 #include "roft_device.h"
+#include "symmetry.h"
 
 // Nothing in this file is compared bit for bit with the oracle (the UKF agrees with it to rounding, not exactly),
 // so fused multiply-adds are welcome here although the build default is -ffp-contract=off.
@@ -1122,6 +1123,8 @@ __device__ bool ukf_one_step(const EngineArrays& a, const FrameCtrl& c, int obj,
     const ObjParams& prm = a.params[obj];
     const int lane = threadIdx.x;
     const int lin = c.lane, cur = c.cur_slot;
+    const int n_sym = prm.n_sym;               // (uniform loads, in flight while the belief is staged)
+    const double* sym_elems = prm.sym;
 
 #ifdef ROFT_UKF_PROFILE
     if (lane < 32) L.dbg[lane] = 0;
@@ -1179,6 +1182,34 @@ __device__ bool ukf_one_step(const EngineArrays& a, const FrameCtrl& c, int obj,
         if (roft_object_output* row = log_row(a, c, obj))
             if (lane < 13 && sd.dst0 == cur) row->pose[lane] = L.mean[lane];
         return true;
+    }
+    // Symmetric object (symmetry.h; include/roft_engine.h section 3h): the delivered pose is replaced by its equivalent nearest to
+    // the belief the correction is applied to -- L.mean here: the buffered belief of a re-synchronisation step, the prediction
+    // otherwise -- once per step, so both corrections of an outlier-rejection step see the same measurement.  Uniform over the
+    // workgroup; without a group this is the test of one count.  Lane g of wave 0 forms c_g, a shuffle tree over the 16 lanes
+    // a group can fill finds the largest (lowest index among equals), lane 0 rewrites L.meas[6..12] unless the identity won.
+    if (n_sym > 1 && ((sd.type0 | (sd.n_corr > 1 ? sd.type1 : 0)) & ROFT_MEAS_POSE)) {
+        if (lane < 64) {
+            double cg = -2.0;
+            int ig = lane;
+            if (lane < n_sym) cg = sym::closeness(L.mean + 9, L.meas + 9, sym_elems + sym::kElement * lane + 3);
+            static_assert(sym::kMaxFilter == 16, "the tree below spans 16 lanes");
+            for (int o = 8; o > 0; o >>= 1) {
+                const double oc = __shfl_xor(cg, o, 64);
+                const int oi = __shfl_xor(ig, o, 64);
+                if (sym::better(oc, oi, cg, ig)) { cg = oc; ig = oi; }
+            }
+            if (lane == 0 && ig != 0) {
+                const double* el = sym_elems + sym::kElement * ig;
+                const double qh[4] = {L.mean[9], L.mean[10], L.mean[11], L.mean[12]};
+                const double xm[7] = {L.meas[6], L.meas[7], L.meas[8], L.meas[9], L.meas[10], L.meas[11], L.meas[12]};
+                const double e7[7] = {el[0], el[1], el[2], el[3], el[4], el[5], el[6]};
+                double xq[7];
+                sym::apply(qh, xm, xm + 3, e7, xq);
+                for (int i = 0; i < 7; ++i) L.meas[6 + i] = xq[i];
+            }
+        }
+        __syncthreads();
     }
     TICK(L, 6);
     // square root of the predicted covariance, shared by both corrections of an outlier-rejection step

@@ -80,6 +80,10 @@ struct ObjParams {
     const uint32_t* cl_words;
     const float* box_corners;
     int n_clusters;
+    // the object's discrete symmetry group (symmetry.h; roft_object_set_symmetry): n_sym elements of 7 doubles, element 0 the
+    // identity.  n_sym <= 1: none (sym may be null) -- the pose UKF takes a delivered pose as it is given.
+    const double* sym;
+    int n_sym;
 };
 
 // compact flow measurement record (what the SKF kernel consumes)
@@ -530,5 +534,10 @@ void launch_float_to_double(const float* in, int n, double* out, hipStream_t s);
 // cloud: n x padded_points x 3 doubles (ADD-S only), partial: n x waves doubles.  fma: 7 instead of 9 operations per pair (ADD-S).
 void launch_pose_errors(int kind, const double* pts, int P, const PoseView& est, const PoseView& ref, int f0, int n, double* cloud,
                         double* partial, double* out, bool fma, hipStream_t s);
+// MSSD / MSPD (kind: ROFT_POSE_ERROR_MSSD / _MSPD) of the pose pairs f0 .. f0 + n - 1 under the group elems[n_sym][7] (device;
+// n_sym >= 1, element 0 the identity) -> out[f0 + ..]; one workgroup per pair, no scratch.  cam: read by MSPD only.
+struct SymCamera { double fx, fy, cx, cy; };
+void launch_pose_errors_sym(int kind, const double* pts, int P, const PoseView& est, const PoseView& ref, int f0, int n, const double* elems,
+                            int n_sym, const SymCamera& cam, double* out, hipStream_t s);
 
 }  // namespace roft

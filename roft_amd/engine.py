@@ -185,6 +185,16 @@ class ROFTFilterBatch:
             if m is not None and 0 <= int(oid) < len(meshes):
                 meshes[int(oid)] = m
 
+    def set_symmetry(self, obj, elements):
+        """The discrete symmetry group of object `obj` (roft_object_set_symmetry): elements [n, 7] rows x y z, q = (w, x, y, z),
+        element 0 the identity, n <= L.MAX_SYMMETRIES; None or a single element: none.  From the next submitted frame on, a
+        delivered pose is replaced by its equivalent nearest to the belief it corrects.  Waits for every stepped batch like sync()."""
+        if elements is None:
+            L.check(L.lib().roft_object_set_symmetry(self._h, int(obj), None, 0))
+            return
+        sym = np.ascontiguousarray(elements, np.float64).reshape(-1, 7)
+        L.check(L.lib().roft_object_set_symmetry(self._h, int(obj), sym.ctypes.data, sym.shape[0]))
+
     def _read_stats(self, call, struct):
         """one roft_engine_get_*_stats call -> the fields of its struct as a dict"""
         st = struct()
@@ -464,16 +474,26 @@ class ROFTFilterBatch:
         L.check(L.lib().roft_engine_get_log_rows(self._h, first, n, rows.ctypes.data))
         return rows
 
-    def score_log(self, kind, obj, first, n, ref, points=None):
+    def score_log(self, kind, obj, first, n, ref, points=None, symmetries=None):
         """ADD ('add') / ADD-S ('adi') of object `obj` over the logged frames first .. first + n - 1 against ref [n, 7] (x y z,
         q wxyz), on the device: the estimates are read from the log in place (roft_engine_score_log).  points [P, 3]; None:
-        every vertex of the mesh the object was added with.  Returns ndarray[n] (metres)."""
-        from .ops import pose_error_kind
+        every vertex of the mesh the object was added with.  Returns ndarray[n] (metres).
+        kind 'mssd' (metres) / 'mspd' (pixels, the engine's camera): the symmetry-aware scores under the group `symmetries`
+        [n_sym, 7] (None: the identity alone), roft_engine_score_log_sym."""
+        from .ops import pose_error_kind, symmetry_elements
         ref = np.ascontiguousarray(ref, np.float64).reshape(-1, 7)
         if ref.shape[0] != n:
             raise ValueError("ref must hold one pose per scored frame")
         out = np.zeros(n)
         pts = None if points is None else np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+        if pose_error_kind(kind) in (L.POSE_ERROR_MSSD, L.POSE_ERROR_MSPD):
+            sym = symmetry_elements(symmetries)
+            L.check(L.lib().roft_engine_score_log_sym(self._h, pose_error_kind(kind), obj, first, n, None if pts is None else pts.ctypes.data,
+                                                      0 if pts is None else pts.shape[0], ref.ctypes.data, sym.ctypes.data, sym.shape[0],
+                                                      out.ctypes.data))
+            return out
+        if symmetries is not None:
+            raise ValueError("symmetries are read by kind 'mssd' / 'mspd' only")
         L.check(L.lib().roft_engine_score_log(self._h, pose_error_kind(kind), obj, first, n, None if pts is None else pts.ctypes.data,
                                               0 if pts is None else pts.shape[0], ref.ctypes.data, out.ctypes.data))
         return out

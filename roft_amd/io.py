@@ -476,3 +476,64 @@ def write_sequence(root, st, object_name, mask_set="gt", pose_set="dope", flow_s
     mesh = os.path.join(root, "model.obj")
     write_obj(mesh, *st.mesh)
     return mesh
+
+
+# ---- symmetry groups (BOP models_info.json) ------------------------------------------------------------------------
+def rot_to_quat(R):
+    """3 x 3 rotation matrix -> unit quaternion (w, x, y, z), w >= 0 (the branch with the largest pivot, so no small divisor)."""
+    R = np.asarray(R, float).reshape(3, 3)
+    t = np.trace(R)
+    if t > 0.0:
+        s = 2.0 * np.sqrt(1.0 + t)
+        q = np.array([0.25 * s, (R[2, 1] - R[1, 2]) / s, (R[0, 2] - R[2, 0]) / s, (R[1, 0] - R[0, 1]) / s])
+    else:
+        i = int(np.argmax(np.diag(R)))
+        j, k = (i + 1) % 3, (i + 2) % 3
+        s = 2.0 * np.sqrt(1.0 + R[i, i] - R[j, j] - R[k, k])
+        q = np.zeros(4)
+        q[0] = (R[k, j] - R[j, k]) / s
+        q[1 + i] = 0.25 * s
+        q[1 + j] = (R[j, i] + R[i, j]) / s
+        q[1 + k] = (R[k, i] + R[i, k]) / s
+    q /= np.linalg.norm(q)
+    return -q if q[0] < 0.0 else q
+
+
+IDENTITY_ELEMENT = (0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0)
+
+
+def discretise_axis(axis, offset, n):
+    """A continuous symmetry about `axis` through the point `offset` (model units already scaled), sampled at n rotations
+    2 pi k / n, k = 0 .. n - 1 -> [n, 7] rows x y z, q = (w, x, y, z); row 0 is exactly the identity.  A rotation R about an axis
+    through c is p -> R p + (c - R c)."""
+    from .metrics import quat_to_rot
+    if n < 1:
+        raise ValueError("n must be >= 1")
+    c = np.asarray(offset, float).reshape(3)
+    out = np.zeros((n, 7))
+    out[0] = IDENTITY_ELEMENT
+    for k in range(1, n):
+        q = axis_angle_to_quat(axis, 2.0 * np.pi * k / n)
+        out[k, :3] = c - quat_to_rot(q) @ c
+        out[k, 3:] = q
+    return out
+
+
+def read_bop_symmetries(path, obj_id, unit_scale=0.001):
+    """The discrete symmetry group of object `obj_id` of a BOP models_info.json as the engine takes it: [n, 7] rows x y z (scaled by
+    unit_scale: BOP models are usually in millimetres), q = (w, x, y, z), with the identity prepended as row 0 (BOP lists only the
+    others).  An object without `symmetries_discrete` has the identity alone.  `symmetries_continuous` is refused: sample it with
+    discretise_axis(axis, offset, n) at the resolution the evaluation wants."""
+    with open(path) as f:
+        info = json.load(f)
+    key = str(obj_id)
+    if key not in info:
+        raise KeyError("%s has no object %s" % (path, key))
+    entry = info[key]
+    if entry.get("symmetries_continuous"):
+        raise ValueError("object %s has symmetries_continuous: sample them with discretise_axis(axis, offset, n)" % key)
+    rows = [IDENTITY_ELEMENT]
+    for m in entry.get("symmetries_discrete", []):
+        T = np.asarray(m, float).reshape(4, 4)   # 16 floats, row-major 4 x 4
+        rows.append(np.concatenate([T[:3, 3] * unit_scale, rot_to_quat(T[:3, :3])]))
+    return np.array(rows, float)

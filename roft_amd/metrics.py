@@ -76,6 +76,70 @@ def trajectory_add(pose_est, pose_ref, pts, backend="cpu"):
     return _trajectory("add", pose_est, pose_ref, pts, backend)
 
 
+# ---- BOP's symmetry-aware distances: MSSD and MSPD (include/roft_engine.h section 3h) -----------------------
+def _rigid(row):
+    """row x y z, q (w x y z) -> (the 9 entries of quat_to_rot(q) in row-major order, t)"""
+    return quat_to_rot(row[3:7]).reshape(9), row[:3]
+
+
+def _move(R, t, p):
+    """R p + t for points p = (px, py, pz) as three arrays: each row R_i0 p_0 + R_i1 p_1 + R_i2 p_2 + t_i, left to right"""
+    return [R[3 * i] * p[0] + R[3 * i + 1] * p[1] + R[3 * i + 2] * p[2] + t[i] for i in range(3)]
+
+
+def max_symmetric_distance(kind, est, ref, pts, symmetries, cam=None):
+    """MSSD ('mssd') or MSPD ('mspd', cam = (fx, fy, cx, cy)) of ONE pose pair est / ref (rows x y z, q wxyz) under the group
+    symmetries [n, 7], in numpy, in the operation order the header states: a = R_r (R_g p + t_g) + t_r, b = R_e p + t_e,
+    sqrt(min_g max_i |b - a|^2); MSPD over the pixels fx X / Z + cx, fy Y / Z + cy, +inf when any point has Z <= 0."""
+    p = np.asarray(pts, float).reshape(-1, 3).T
+    Re, te = _rigid(np.asarray(est, float))
+    Rr, tr = _rigid(np.asarray(ref, float))
+    b = _move(Re, te, p)
+    if kind == "mspd":
+        fx, fy, cx, cy = cam
+        bad = not np.all(b[2] > 0.0)
+        with np.errstate(all="ignore"):
+            ub, vb = fx * b[0] / b[2] + cx, fy * b[1] / b[2] + cy
+    best = np.inf
+    for el in np.asarray(symmetries, float).reshape(-1, 7):
+        Rg, tg = _rigid(el)
+        a = _move(Rr, tr, _move(Rg, tg, p))
+        with np.errstate(all="ignore"):
+            if kind == "mspd":
+                bad = bad or not np.all(a[2] > 0.0)
+                du, dv = ub - (fx * a[0] / a[2] + cx), vb - (fy * a[1] / a[2] + cy)
+                d = du * du + dv * dv
+            else:
+                dx, dy, dz = b[0] - a[0], b[1] - a[1], b[2] - a[2]
+                d = dx * dx + dy * dy + dz * dz
+        best = np.minimum(best, np.max(d))   # (np.max and np.minimum keep a NaN, as the kernel does)
+    if kind == "mspd" and bad:
+        return np.inf
+    return float(np.sqrt(best))
+
+
+def _trajectory_sym(kind, pose_est, pose_ref, pts, symmetries, cam, backend):
+    if backend not in ("numpy", "hip"):
+        raise ValueError("backend must be 'numpy' or 'hip'")
+    pose_est, pose_ref = np.asarray(pose_est, float).reshape(-1, 7), np.asarray(pose_ref, float).reshape(-1, 7)
+    sym = np.array([[0.0, 0, 0, 1, 0, 0, 0]]) if symmetries is None else np.asarray(symmetries, float).reshape(-1, 7)
+    if backend == "hip":
+        from . import ops
+        return ops.pose_errors_sym(kind, pts, pose_est, pose_ref, sym, cam)
+    return np.array([max_symmetric_distance(kind, pose_est[k], pose_ref[k], pts, sym, cam) for k in range(len(pose_est))])
+
+
+def trajectory_mssd(pose_est, pose_ref, pts, symmetries=None, backend="numpy"):
+    """pose_*: [F, 7] (x, q wxyz); symmetries [n, 7], element 0 the identity.  Per-frame MSSD in metres.  backend 'numpy' or
+    'hip' (ops.pose_errors_sym; no CPU fallback)."""
+    return _trajectory_sym("mssd", pose_est, pose_ref, pts, symmetries, None, backend)
+
+
+def trajectory_mspd(pose_est, pose_ref, pts, cam, symmetries=None, backend="numpy"):
+    """... MSPD in pixels; cam = (fx, fy, cx, cy)."""
+    return _trajectory_sym("mspd", pose_est, pose_ref, pts, symmetries, cam, backend)
+
+
 # ---- RMSE metrics of evaluation/metrics.py (the step right after the filtering path) -----------------------
 def _rot_angle_deg(q_ref, q_sig):
     """Geodesic angle of R_ref R_sig^T in degrees (metrics.py:114-144)."""

@@ -301,7 +301,8 @@ def track_quality(cam, divider, depth, mask, mesh, x, q, depth_tolerance=0.01, d
     return np.frombuffer(bytes(rec), QUALITY_DTYPE)[0].copy()
 
 
-POSE_ERROR_KINDS = {"add": L.POSE_ERROR_ADD, "adi": L.POSE_ERROR_ADDS, "adds": L.POSE_ERROR_ADDS}
+POSE_ERROR_KINDS = {"add": L.POSE_ERROR_ADD, "adi": L.POSE_ERROR_ADDS, "adds": L.POSE_ERROR_ADDS,
+                    "mssd": L.POSE_ERROR_MSSD, "mspd": L.POSE_ERROR_MSPD}
 
 
 def pose_error_kind(kind):
@@ -319,6 +320,42 @@ def pose_errors(kind, points, est, ref):
         raise ValueError("est and ref must hold the same number of poses")
     out = np.zeros(est.shape[0])
     L.check(L.lib().roft_pose_errors(pose_error_kind(kind), _p(points), points.shape[0], _p(est), _p(ref), est.shape[0], _p(out)))
+    return out
+
+
+def symmetry_elements(symmetries):
+    """A symmetry group as the ABI takes it: [n, 7] float64 rows x y z, q = (w, x, y, z), element 0 the identity.  None: the
+    identity alone."""
+    if symmetries is None:
+        return np.array([[0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0]])
+    return _f64(symmetries).reshape(-1, 7)
+
+
+def pose_nearest_equivalent(symmetries, qh, x, q):
+    """The pose equivalent to (x, q) under the object's symmetry group that is nearest to the belief quaternion qh
+    (roft_pose_nearest_equivalent: the rule of the pose UKF in host arithmetic -- no device is needed).
+    Returns (x' [3], q' [4], index of the chosen element); index 0 returns the input's bits."""
+    sym = symmetry_elements(symmetries)
+    qh, x, q = _f64(qh).reshape(4), _f64(x).reshape(3), _f64(q).reshape(4)
+    x_out, q_out, index = np.zeros(3), np.zeros(4), C.c_int(-1)
+    L.check(L.lib().roft_pose_nearest_equivalent(_p(sym), sym.shape[0], _p(qh), _p(x), _p(q), _p(x_out), _p(q_out), C.byref(index)))
+    return x_out, q_out, index.value
+
+
+def pose_errors_sym(kind, points, est, ref, symmetries=None, cam=None):
+    """MSSD ('mssd', metres) or MSPD ('mspd', pixels; cam = L.Camera or (fx, fy, cx, cy)) of F pose pairs over one point set under
+    a symmetry group [n, 7], on the device (roft_pose_errors_sym).  Shapes as pose_errors.  Returns ndarray[F]."""
+    points = _f64(points).reshape(-1, 3)
+    est, ref = _f64(est).reshape(-1, 7), _f64(ref).reshape(-1, 7)
+    if est.shape != ref.shape:
+        raise ValueError("est and ref must hold the same number of poses")
+    sym = symmetry_elements(symmetries)
+    if cam is not None and not isinstance(cam, L.Camera):
+        fx, fy, cx, cy = (float(v) for v in cam)
+        cam = L.Camera(0, 0, fx, fy, cx, cy)
+    out = np.zeros(est.shape[0])
+    L.check(L.lib().roft_pose_errors_sym(pose_error_kind(kind), _p(points), points.shape[0], _p(est), _p(ref), est.shape[0], _p(sym),
+                                         sym.shape[0], None if cam is None else C.byref(cam), _p(out)))
     return out
 
 

@@ -61,8 +61,47 @@ def time_device(pts, est, ref, repeats):
     return float(np.median(wall)), float(np.median(kern)), out
 
 
+def symmetry_cases(cpu_poses, repeats):
+    """MSSD and MSPD under a box's four-element group at the same point x pose sizes: the numpy path (metrics.trajectory_mssd /
+    trajectory_mspd, one core, timed on cpu_poses poses and scaled) against ops.pose_errors_sym end to end and kernel only."""
+    group = np.array([[0, 0, 0, 1, 0, 0, 0], [0, 0, 0, 0, 1, 0, 0], [0, 0, 0, 0, 0, 1, 0], [0, 0, 0, 0, 0, 0, 1]], float)   # identity, three half turns
+    cam = (614.7142806307731, 614.7142806307731, 320.0, 240.0)
+    est_all, ref_all = poses(48000)
+    est_all[:, 2] += 2.0   # (in front of the camera: MSPD of a pose behind it is +inf)
+    ref_all[:, 2] += 2.0
+    out = []
+    for name, pts in clouds():
+        for kind in ("mssd", "mspd"):
+            c = cam if kind == "mspd" else None
+            t0 = time.perf_counter()
+            if kind == "mssd":
+                cpu = metrics.trajectory_mssd(est_all[:cpu_poses], ref_all[:cpu_poses], pts, group)
+            else:
+                cpu = metrics.trajectory_mspd(est_all[:cpu_poses], ref_all[:cpu_poses], pts, cam, group)
+            cpu_ms_per_pose = 1e3 * (time.perf_counter() - t0) / cpu_poses
+            for F in (1000, 48000):
+                est, ref = est_all[:F], ref_all[:F]
+                ops.pose_errors_sym(kind, pts, est, ref, group, c)
+                wall, kern = [], []
+                for _ in range(repeats):
+                    t0 = time.perf_counter()
+                    got = ops.pose_errors_sym(kind, pts, est, ref, group, c)
+                    wall.append(time.perf_counter() - t0)
+                    kern.append(ops.pose_errors_kernel_ms() * 1e-3)
+                n_cmp = min(F, cpu_poses)
+                case = dict(kind=kind, points=len(pts), cloud=name, poses=F, elements=len(group), numpy_ms_per_pose=cpu_ms_per_pose,
+                            numpy_poses_timed=cpu_poses, numpy_s=cpu_ms_per_pose * 1e-3 * F, device_s=float(np.median(wall)),
+                            device_kernel_s=float(np.median(kern)), speedup=cpu_ms_per_pose * 1e-3 * F / float(np.median(wall)),
+                            max_abs_diff_vs_numpy=float(np.abs(got[:n_cmp] - cpu[:n_cmp]).max()))
+                out.append(case)
+                print(json.dumps(case), flush=True)
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--symmetry-only", action="store_true",
+                    help="only the MSSD / MSPD lines (roft_pose_errors_sym under a four-element group, against the numpy path): {symmetry_cases: [...]} -> --out")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r08_pose_errors.json"))
     ap.add_argument("--commit", default=None)
     ap.add_argument("--cpu-poses", type=int, default=1000)
@@ -84,6 +123,17 @@ def main(argv=None):
             commit = subprocess.check_output(["git", "-C", ROOT, "rev-parse", "HEAD"], text=True, stderr=subprocess.DEVNULL).strip()
         except Exception:
             commit = "unknown"
+    if args.symmetry_only:
+        record = dict(commit=commit, device_count=int(L.lib().roft_device_count()), kind="MSSD / MSPD (roft_pose_errors_sym)",
+                      numpy_path="metrics.trajectory_mssd / trajectory_mspd backend='numpy' (one core); timed on numpy_poses_timed poses, scaled to F",
+                      device_path="ops.pose_errors_sym end to end (upload, kernel, read-back): median of %d calls after one warm-up" % args.repeats,
+                      symmetry_cases=symmetry_cases(min(args.cpu_poses, 200), args.repeats))
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(record, f, indent=1)
+            f.write("\n")
+        print("wrote", args.out)
+        return 0
     cases = []
     all_faster = True
     est_all, ref_all = poses(48000)   # every case scores the leading rows of the same trajectory

@@ -3,7 +3,7 @@
 reference computes for its 'ours' entries -- per object and pooled over ALL -- printed as a Markdown table.
 
   evaluate_results.py --results DIR --dataset DIR [--objects NAME ...] [--points DIR] [--metrics m1,m2,...] [--of-ms 0]
-                      [--device] [--all-points]
+                      [--device] [--all-points] [--symmetry models_info.json --symmetry-ids NAME=ID ... [--mssd] [--mspd]]
 
 DIR/<object>/{pose_estimate[_ycb].txt, velocity_estimate.txt, execution_times.txt} are the log files ROFT-tracker (or
 ROFT-tracker-batch, or tools/run_sequence.py with --out DIR/<object>/) leaves; dataset/<object>/gt/poses.txt holds the ground-truth
@@ -11,6 +11,8 @@ poses (x y z axis angle) and, optionally, gt/velocities.txt the ground-truth vel
 when --points is given (the reference's YCB_Video_Models layout), else every k-th vertex of dataset/<object>/model.obj (about 500;
 --all-points: every vertex).  --device computes the ADD / ADD-S distances on the GPU (roft_pose_errors: brute force in double
 precision, the same numbers to 1e-12 m), once per object: the ALL row pools them instead of computing them again.
+--mssd / --mspd add the mean of BOP's symmetry-aware distances (mm / px) under the objects' discrete symmetry groups of --symmetry
+(metrics.trajectory_mssd / trajectory_mspd: numpy, or the device with --device); MSPD projects with dataset/<object>/cam_K.json.
 As in evaluate.py: the leading six velocity columns of the pose log are dropped (data_loader.py:238-241), the estimates are compared
 with as many ground-truth rows as there are estimates (from the row the run started at: --first-frame), the linear velocity is
 moved from the camera origin to the object position before it is compared (v = v_O + w x r, evaluate.py:514-521), and --of-ms is
@@ -29,7 +31,8 @@ from roft_amd import io, metrics  # noqa: E402
 
 DEFAULT = "rmse_cartesian_3d,rmse_angular,add,adi,rmse_linear_velocity,rmse_angular_velocity,time,excess_33_ms"
 UNITS = dict(rmse_cartesian_3d="cm", rmse_cartesian_x="cm", rmse_cartesian_y="cm", rmse_cartesian_z="cm", rmse_angular="deg", add="AUC %", adi="AUC %",
-             rmse_linear_velocity="cm/s", rmse_angular_velocity="deg/s", max_linear_velocity="m/s", max_angular_velocity="deg/s", time="ms", excess_33_ms="frames")
+             rmse_linear_velocity="cm/s", rmse_angular_velocity="deg/s", max_linear_velocity="m/s", max_angular_velocity="deg/s", time="ms", excess_33_ms="frames",
+             mssd="mean mm", mspd="mean px")
 
 
 def first_existing(*paths):
@@ -75,7 +78,15 @@ def main(argv=None):
     ap.add_argument("--json", default=None, help="also write the numbers to this file")
     ap.add_argument("--device", action="store_true", help="ADD / ADD-S distances on the GPU (no CPU fallback)")
     ap.add_argument("--all-points", action="store_true", help="ADD / ADD-S on every vertex of model.obj instead of about 500")
+    ap.add_argument("--symmetry", default=None, metavar="FILE", help="BOP models_info.json with the objects' discrete symmetry groups (for --mssd / --mspd)")
+    ap.add_argument("--symmetry-ids", nargs="*", default=[], metavar="NAME=ID", help="an object's id in --symmetry (an object not named here: the identity alone)")
+    ap.add_argument("--symmetry-unit-scale", type=float, default=0.001, help="model units of --symmetry in metres (BOP: millimetres)")
+    ap.add_argument("--mssd", action="store_true", help="a column with the mean MSSD (mm) under the groups of --symmetry")
+    ap.add_argument("--mspd", action="store_true", help="a column with the mean MSPD (px; the camera is dataset/<object>/cam_K.json, or --camera)")
+    ap.add_argument("--camera", default=None, metavar="FX,FY,CX,CY", help="the intrinsics --mspd projects with, for every object")
     args = ap.parse_args(argv)
+    if (args.mssd or args.mspd) and not args.symmetry:
+        ap.error("--mssd / --mspd need --symmetry FILE")
     names = args.objects or sorted(n for n in os.listdir(args.results) if os.path.isdir(os.path.join(args.results, n)))
     data = {n: load_object(args.results, args.dataset, n, args.first_frame, args.of_ms) for n in names}
     points = {}
@@ -110,6 +121,33 @@ def main(argv=None):
             ref, sig = (pick("gt_vel"), pick("vel")) if vel_metric else (pick("gt_pose"), pick("pose"))
             row["ALL"] = metric.evaluate("ALL", ref, sig, {n: data[n]["time"] for n in have} if all("time" in data[n] for n in have) else None)
         table[m] = row
+    # the symmetry-aware distances: per object the mean over its frames, ALL the mean over the pooled frames
+    ids = dict(item.split("=", 1) for item in args.symmetry_ids)
+    for m, on in (("mssd", args.mssd), ("mspd", args.mspd)):
+        if not on:
+            continue
+        dist = {}
+        for n in (n for n in names if n in points):
+            sym = io.read_bop_symmetries(args.symmetry, int(ids[n]), args.symmetry_unit_scale) if n in ids else None
+            est, ref = metrics.Metric._poses(data[n]["pose"]), metrics.Metric._poses(data[n]["gt_pose"])
+            k = min(len(est), len(ref))
+            backend = "hip" if args.device else "numpy"
+            if m == "mssd":
+                dist[n] = 1e3 * metrics.trajectory_mssd(est[:k], ref[:k], points[n], sym, backend)
+            else:
+                cam_path = os.path.join(args.dataset, n, "cam_K.json")
+                if args.camera:
+                    cam4 = tuple(float(v) for v in args.camera.split(","))
+                elif os.path.exists(cam_path):
+                    cam = json.load(open(cam_path))
+                    cam4 = (cam["fx"], cam["fy"], cam["cx"], cam["cy"])
+                else:
+                    ap.error("--mspd: no %s; give --camera=FX,FY,CX,CY" % cam_path)
+                dist[n] = metrics.trajectory_mspd(est[:k], ref[:k], points[n], cam4, sym, backend)
+        table[m] = {n: float(d.mean()) for n, d in dist.items()}
+        if dist:
+            table[m]["ALL"] = float(np.concatenate(list(dist.values())).mean())
+        wanted.append(m)
     cols = [m for m in wanted if table[m]]
     print("| object | " + " | ".join("%s (%s)" % (m, UNITS[m]) for m in cols) + " |")
     print("|---|" + "---|" * len(cols))

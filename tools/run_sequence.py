@@ -86,6 +86,11 @@ def main(argv=None):
                     help="with --flow-on-engine: the frames are the sensor's distorted ones; the engine rectifies them on the device")
     ap.add_argument("--lens-camera", default=None, metavar="FX,FY,CX,CY",
                     help="with --lens: the sensor's intrinsics (default: those of cam_K.json)")
+    ap.add_argument("--symmetry", default=None, metavar="FILE",
+                    help="BOP models_info.json: the object's discrete symmetry group goes to the engine (a delivered pose is replaced by its "
+                         "equivalent nearest to the belief) and the report gains MSSD / MSPD; needs --symmetry-id")
+    ap.add_argument("--symmetry-id", type=int, default=None, metavar="N", help="the object's id in --symmetry")
+    ap.add_argument("--symmetry-unit-scale", type=float, default=0.001, help="model units of --symmetry in metres (BOP: millimetres)")
     ap.add_argument("--from", dest="cfg_file", default=None, help="ROFT configuration file (libconfig), overrides as --a::b::c value")
     args, overrides = ap.parse_known_args(argv)
 
@@ -186,6 +191,12 @@ def main(argv=None):
         for i in range(7):
             d.p_mean0[6 + i] = init[i]
     eng.add_object(d, verts, tris)
+    symmetries = None
+    if args.symmetry:
+        if args.symmetry_id is None:
+            ap.error("--symmetry needs --symmetry-id")
+        symmetries = io.read_bop_symmetries(args.symmetry, args.symmetry_id, args.symmetry_unit_scale)
+        eng.set_symmetry(0, symmetries)
     n = len(seq) - start
     if n <= 0:
         sys.stderr.write("the first detection arrives after the last frame\n")
@@ -220,6 +231,9 @@ def main(argv=None):
         g = io.read_poses(gt_path)[0][start + 12:start + n]
         for kind in ("adi", "add"):
             device_scores[kind] = eng.score_log(kind, 0, 12, len(g), g)
+        if symmetries is not None:
+            for kind in ("mssd", "mspd"):
+                device_scores[kind] = eng.score_log(kind, 0, 12, len(g), g, symmetries=symmetries)
     if args.quality:
         from roft_amd.ops import quality_overlap
         rec = eng.quality(0, n)[:, 0]
@@ -245,6 +259,14 @@ def main(argv=None):
         report.update(adds_mm_mean=1e3 * float(dist.mean()), adds_auc=metrics.auc(dist),
                       rmse_position_cm=metrics.rmse_cartesian_3d(g[:, :3], est[12:, :3]),
                       rmse_orientation_deg=metrics.rmse_angular(g[:, 3:], est[12:, 3:]))
+        if symmetries is not None:
+            cam4 = (cfg.cam.fx, cfg.cam.fy, cfg.cam.cx, cfg.cam.cy)
+            report.update(symmetry_elements=int(len(symmetries)),
+                          mssd_mm_mean=1e3 * float(metrics.trajectory_mssd(est[12:], g, pts, symmetries).mean()),
+                          mspd_px_mean=float(metrics.trajectory_mspd(est[12:], g, pts, cam4, symmetries).mean()))
+            if "mssd" in device_scores:
+                report.update(mssd_full_mesh_mm_mean=1e3 * float(device_scores["mssd"].mean()),
+                              mspd_full_mesh_px_mean=float(device_scores["mspd"].mean()))
         if device_scores:
             report.update(full_mesh_points=int(len(verts)), adds_full_mesh_mm_mean=1e3 * float(device_scores["adi"].mean()),
                           adds_full_mesh_auc=metrics.auc(device_scores["adi"]), add_full_mesh_mm_mean=1e3 * float(device_scores["add"].mean()),
