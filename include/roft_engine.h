@@ -1170,6 +1170,62 @@ int roft_pose_errors_sym(int kind, const double* points, int n_points, const dou
 int roft_engine_score_log_sym(roft_engine* e, int kind, int obj_id, int first_frame, int n_frames, const double* points, int n_points,
                               const double* ref, const double* sym, int n_sym, double* out);
 
+/* ---- (3i) VSD scores: BOP's third pose error, against the sensor's depth image ------------------------------------------------------ *
+ * BOP scores a 6D pose method by the mean of three recalls: MSSD and MSPD (section 3h) and VSD, the Visible Surface Discrepancy --
+ * the only one that looks at the depth image: an estimate hidden behind a hand is not punished for what nobody could see, and
+ * symmetric views need no symmetry group.  roft_pose_errors_vsd computes it for n_poses pose pairs of one mesh on the device: two
+ * depth renders per pair, which never leave the chip, and one pass over the pair's depth image.
+ *
+ * Inputs.  est / ref: rows of 7 doubles x y z, w x y z; the quaternion is used as given.  depth: [n_depth][height][width] floats,
+ * metres, HOST memory, 0 = no measurement; n_depth = n_poses (image f belongs to pair f) or 1 (one image under every pair).
+ *
+ * For pose pair f, with D_t its depth image:
+ *  - Renders.  D_e and D_g are what roft_render_depth(mesh, x, q, cam, 1, ..) draws for the estimated and the reference pose: the
+ *    render contract, back-face rule included, 0 = background (at ANY width >= 1, as the scene renderer draws; roft_render_depth
+ *    itself wants a multiple of 32).  A pose with a non-finite component draws nothing, as in the scene renderer.
+ *  - Distance images (BOP's depth_im_to_dist_im_fast), in double, every operation rounded once, no contraction: for pixel (i, j) --
+ *    column i, row j -- and depth d (float, promoted)
+ *        a = (i - cx) / fx,  b = (j - cy) / fy,  dist = sqrt(((a d)^2 + (b d)^2) + d^2)
+ *    give T, G and E from D_t, D_g and D_e.
+ *  - Visibility (BOP's mode `bop19`).  For a model image M in {G, E}: diff = (float)M - (float)T, in float;
+ *        vis(M) = (T > 0 && M > 0 && diff <= delta) || (T == 0 && M > 0);    V_g = vis(G);    V_e = vis(E) || (V_g && E > 0).
+ *    A NaN depth pixel is neither a measurement nor a hole: it fails every comparison, and hides nothing and shows nothing.  The
+ *    distance of a NEGATIVE depth is that of its magnitude (the squares), so the formulas take such a pixel for a measurement, as BOP's
+ *    code does; a caller who means "no measurement" writes 0.
+ *  - Counts.  n_union = |V_g u V_e|, n_inter = |V_g n V_e|, n_gt = |V_g|, n_est = |V_e|, fail[k] = the pixels of V_g n V_e with
+ *    c >= taus[k] in double, c = |G - E| / diameter when diameter > 0, else c = |G - E| undivided.
+ *  - Errors (BOP's cost `step`).  errors_out[f][k] = (double)(fail[k] + n_union - n_inter) / (double)n_union; 1.0 for every k when
+ *    n_union == 0.  counts_out (optional) row f: n_union, n_inter, n_gt, n_est, fail[0 .. n_taus).
+ *
+ * Determinism: the contract of roft_pose_errors.  Row f is a function of the camera, the mesh, the parameters, pose pair f and its
+ * depth image alone -- not of n_poses, the pair's position in the call, n_depth, window_pixels, strips or the run: every figure is a
+ * sum of integers.
+ *
+ * ROFT_ERR_INVALID, the reason in roft_last_error_string, before a device is looked for: a NULL pointer other than counts_out;
+ * n_poses < 0; n_depth neither 1 nor n_poses when n_poses > 0; n_taus outside 1 .. ROFT_VSD_MAX_TAUS; a tau that is not finite or not
+ * > 0; delta or diameter negative or not finite; window_pixels < 0; a mesh the other operators refuse (no vertices or triangles, a
+ * NULL array, an index out of range); width * height outside what the scene renderer accepts (each >= 1, the product < 2^24); an
+ * image row wider than the kernel's two on-chip depth windows (about 19 000 pixels).  n_poses == 0 is ROFT_OK and touches nothing.
+ * Without a device a well-formed call returns ROFT_ERR_DEVICE: there is no CPU path.
+ *
+ * Not in scope: BOP's cost `tlinear` and its visibility mode `bop18`; a roft_engine_score_log form (the engine does not keep a
+ * sequence's depth frames); several objects in one VSD render (the other objects of a scene enter through the depth image only); the
+ * C++ class facade (include/ROFT). */
+#define ROFT_VSD_MAX_TAUS 16
+typedef struct {
+    float  delta;          /* metres; tolerance of the visibility test (BOP19: 0.015) */
+    int    n_taus;         /* 1 .. ROFT_VSD_MAX_TAUS */
+    double taus[ROFT_VSD_MAX_TAUS];  /* misalignment tolerances; in units of `diameter` when it is > 0, else metres */
+    double diameter;       /* metres; 0: distances are not normalised */
+    int    window_pixels;  /* 0: the library's choice; > 0: at most this many pixels per on-chip window (tests: forces strips). Changes no bit. */
+} roft_vsd_params;
+/* 0.015f, the ten BOP19 taus 0.05 k (k = 1 .. 10, each the double nearest to k * 0.05), diameter 0, window_pixels 0 */
+int roft_default_vsd_params(roft_vsd_params* p);
+int roft_pose_errors_vsd(const roft_camera* cam, const roft_mesh* mesh, const double* est, const double* ref, int n_poses,
+                         const float* depth, int n_depth /* n_poses, or 1: one image under every pair */,
+                         const roft_vsd_params* p, double* errors_out /* [n_poses][n_taus] */,
+                         int32_t* counts_out /* [n_poses][4 + n_taus], may be NULL */);
+
 /* ---- (4) diagnostics (tests and profiling tools; not needed by an integration) --------------------------------- */
 /* The per-frame program builder without a device: the host-side mirror of CartesianQuaternionMeasurement::freeze's
  * Standard / PopBufferedMeasurement / RepeatOnlyVelocity state machine (cpp:92-348) and of the re-sync loop of

@@ -37,6 +37,7 @@ RECTIFY_CHUNK = 32                  # ROFT_RECTIFY_CHUNK
 SCENE_MAX_INSTANCES = 256   # ROFT_SCENE_MAX_INSTANCES
 MAX_SYMMETRIES, MAX_SCORE_SYMMETRIES = 16, 256   # ROFT_MAX_SYMMETRIES, ROFT_MAX_SCORE_SYMMETRIES
 POSE_ERROR_MSSD, POSE_ERROR_MSPD = 2, 3          # ROFT_POSE_ERROR_* of roft_pose_errors_sym
+VSD_MAX_TAUS = 16                                # ROFT_VSD_MAX_TAUS
 
 
 class RoftError(RuntimeError):
@@ -208,6 +209,12 @@ class SceneDesc(C.Structure):
                 ("styles", C.c_void_p), ("window_pixels", C.c_int)]
 
 
+class VsdParams(C.Structure):
+    _c_name_ = "roft_vsd_params"
+    _fields_ = [("delta", C.c_float), ("n_taus", C.c_int), ("taus", C.c_double * VSD_MAX_TAUS), ("diameter", C.c_double),
+                ("window_pixels", C.c_int)]
+
+
 # ---- every function include/roft_engine.h declares, in the header's order: one row each --------------------------------------
 # optional: a library loaded through ROFT_LIB_SO (an older build, for an A/B run) may lack the symbol -- the diagnostics and the
 # entry points younger than ABI version 2 itself; tests/test_abi_cpu.py checks that the in-tree library has them all.
@@ -325,6 +332,9 @@ ABI = (
     Fn("roft_object_set_symmetry", _int, [_vp, _int, _vp, _int], _OPTIONAL),
     Fn("roft_pose_errors_sym", _int, [_int, _vp, _int, _vp, _vp, _int, _vp, _int, _P(Camera), _vp], _OPTIONAL),
     Fn("roft_engine_score_log_sym", _int, [_vp, _int, _int, _int, _int, _vp, _int, _vp, _vp, _int, _vp], _OPTIONAL),
+    # (3i) VSD scores
+    Fn("roft_default_vsd_params", _int, [_P(VsdParams)], _OPTIONAL),
+    Fn("roft_pose_errors_vsd", _int, [_P(Camera), _P(Mesh), _vp, _vp, _int, _vp, _int, _P(VsdParams), _vp, _vp], _OPTIONAL),
     # (4) diagnostics
     Fn("roft_debug_plan", _int, [_P(Config), _vp, _int, _vp, _vp, _vp, _vp], _OPTIONAL),
     Fn("roft_debug_restart_check", _int, [_P(Config), _int, _ip, _ip, _int, _ip, _P(ObjectDesc), _int, _int], _OPTIONAL),

@@ -13,7 +13,8 @@
 //   engine_results.hip  state, outputs, log, masks, timing and batch-trace readers
 //   op_context.h        the ONE context of the operator-level entry points: it owns device memory, a stream and a mutex, never settings --
 //                       the entry (lock, device, stream), the one-object arrays derived by value, typed scratch, the state's landing block
-//   engine_ops.hip      the operator-level entry points on that context (roft_flow_measurement ... roft_outlier_test, roft_pose_errors)
+//   engine_ops.hip      the operator-level entry points on that context (roft_flow_measurement ... roft_outlier_test, roft_pose_errors,
+//                       roft_pose_errors_vsd)
 //   engine_quality.hip  track quality: roft_engine_enable_quality / _get_quality, the batch's quality launch; roft_track_quality (on op_context.h)
 //   engine_debug.hip    roft_debug_* (diagnostics and experiments)
 //   scene.hip           the scene renderer: roft_scene_renderer_*, roft_render_scene
@@ -48,6 +49,7 @@
 #include "rectify.h"
 #include "quality.h"
 #include "symmetry.h"
+#include "vsd.h"
 
 static_assert(roft::host::kPlanLanes == roft::kNumLin, "batch_plan.h plans for the engine's pose lanes");
 
@@ -273,6 +275,14 @@ int check_pose_errors_sym(int kind, const double* sym, int n_sym, const roft_cam
 int pose_errors_sym_run(PoseErrorScratch& sc, int kind, const double* d_pts, int P, const double* est_host, PoseView est_dev,
                         const double* ref_host, int n, const double* sym_host, int n_sym, const roft_camera* cam, double* out_host,
                         hipStream_t s);
+
+// Device scratch of the VSD score (roft_pose_errors_vsd): grows on demand, kept between calls.  depth: the images of one chunk of
+// pairs, or the one image under every pair.
+struct VsdScratch {
+    DevBuf<double> est, ref, out;
+    DevBuf<float> depth;
+    DevBuf<int32_t> counts, rows;
+};
 
 inline void init_state(ObjState& st)
 {

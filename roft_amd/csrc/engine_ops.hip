@@ -762,6 +762,92 @@ int roft_pose_errors_sym(int kind, const double* points, int n_points, const dou
     return pose_errors_sym_run(sc, kind, sc.pts.p, n_points, est, PoseView{}, ref, n_poses, sym, n_sym, cam, out, c.stream);
 }
 
+int roft_default_vsd_params(roft_vsd_params* p)
+{
+    if (!p) return fail(ROFT_ERR_INVALID, "null argument");
+    std::memset(p, 0, sizeof(*p));
+    p->delta = 0.015f;
+    p->n_taus = 10;
+    for (int k = 1; k <= 10; ++k) p->taus[k - 1] = (double)k / 20.0;   // (the double nearest to k * 0.05: one rounding)
+    p->diameter = 0.0;
+    p->window_pixels = 0;
+    return ROFT_OK;
+}
+
+// VSD (section 3i).  The mesh goes up once, the poses once; the depth images go up in chunks of at most kVsdChunk pairs, so that
+// the resident depth stays modest whatever n_poses is -- or once, when one image lies under every pair.  Every chunk's workgroups add
+// to their pairs' integer rows; one finish launch divides.
+int roft_pose_errors_vsd(const roft_camera* cam, const roft_mesh* mesh, const double* est, const double* ref, int n_poses, const float* depth,
+                         int n_depth, const roft_vsd_params* p, double* errors_out, int32_t* counts_out)
+{
+    if (!cam || !mesh || !est || !ref || !depth || !p || !errors_out) return fail(ROFT_ERR_INVALID, "null argument");
+    if (n_poses < 0) return fail(ROFT_ERR_INVALID, "n_poses must be >= 0");
+    if (n_poses > 0 && n_depth != 1 && n_depth != n_poses) return fail(ROFT_ERR_INVALID, "n_depth must be n_poses or 1");
+    if (p->n_taus < 1 || p->n_taus > ROFT_VSD_MAX_TAUS) return fail(ROFT_ERR_INVALID, "n_taus must be 1 .. ROFT_VSD_MAX_TAUS");
+    for (int k = 0; k < p->n_taus; ++k)
+        if (!(std::isfinite(p->taus[k]) && p->taus[k] > 0.0)) return fail(ROFT_ERR_INVALID, "tau " + std::to_string(k) + " must be finite and > 0");
+    if (!(std::isfinite(p->delta) && p->delta >= 0.0f)) return fail(ROFT_ERR_INVALID, "delta must be finite and >= 0");
+    if (!(std::isfinite(p->diameter) && p->diameter >= 0.0)) return fail(ROFT_ERR_INVALID, "diameter must be finite and >= 0 (0: not normalised)");
+    if (p->window_pixels < 0) return fail(ROFT_ERR_INVALID, "window_pixels must be >= 0 (0: the library's choice)");
+    TRY(check_mesh(*mesh, "mesh", false));
+    if (cam->width < 1 || cam->height < 1) return fail(ROFT_ERR_INVALID, "width and height must be >= 1");
+    if ((long long)cam->width * cam->height >= (1ll << 24)) return fail(ROFT_ERR_INVALID, "width * height must be < 2^24");
+    VsdArgs a;
+    std::memset(&a, 0, sizeof(a));
+    size_t lds = 0;
+    if (!vsd_shape(mesh->n_verts, cam->width, p->window_pixels, a.vcache_cap, a.win_alloc, a.win_cap, lds))
+        return fail(ROFT_ERR_INVALID, "VSD: an image row is wider than the kernel's two depth windows");
+    if (n_poses == 0) return ROFT_OK;
+    OpContext& c = op_context();
+    std::unique_lock<std::mutex> lk;
+    TRY(c.enter(lk));
+    VsdScratch& sc = c.vsd;
+    hipStream_t s = c.stream;
+    TRY(c.mesh.upload(*mesh, MeshLayout::kWalkOrder, s));
+    const size_t n = (size_t)n_poses, npix = (size_t)cam->width * cam->height;
+    const int T = p->n_taus;
+    const bool shared = n_depth == 1;
+    constexpr int kVsdChunk = 64, kVsdSharedChunk = 32768;   // pairs per launch: with their own images / under one image
+    const int chunk = std::min(n_poses, shared ? kVsdSharedChunk : kVsdChunk);
+    HIP_TRY(sc.est.ensure(7 * n));
+    HIP_TRY(sc.ref.ensure(7 * n));
+    HIP_TRY(sc.depth.ensure(npix * (shared ? 1 : (size_t)chunk)));
+    HIP_TRY(sc.counts.ensure(n * kVsdCounts));
+    HIP_TRY(sc.out.ensure(n * T));
+    HIP_TRY(sc.rows.ensure(n * (4 + T)));
+    HIP_TRY(hipMemcpyAsync(sc.est.p, est, sizeof(double) * 7 * n, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(sc.ref.p, ref, sizeof(double) * 7 * n, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(sc.counts.p, 0, sizeof(int32_t) * n * kVsdCounts, s));
+    if (shared) HIP_TRY(hipMemcpyAsync(sc.depth.p, depth, sizeof(float) * npix, hipMemcpyHostToDevice, s));
+    a.mesh = c.mesh.scene_mesh();
+    a.depth = sc.depth.p;
+    a.depth_stride = shared ? 0 : npix;
+    a.W = cam->width; a.H = cam->height;
+    a.fx = (float)cam->fx; a.fy = (float)cam->fy; a.cx = (float)cam->cx; a.cy = (float)cam->cy;   // (divider 1: the camera as it is)
+    a.dfx = cam->fx; a.dfy = cam->fy; a.dcx = cam->cx; a.dcy = cam->cy;
+    a.delta = p->delta;
+    a.n_taus = T;
+    for (int k = 0; k < T; ++k) a.taus[k] = p->taus[k];
+    a.diameter = p->diameter;
+    for (int f0 = 0; f0 < n_poses; f0 += chunk) {   // (in order on one stream: a chunk re-uses the depth buffer of the one before)
+        const int m = std::min(chunk, n_poses - f0);
+        if (!shared) HIP_TRY(hipMemcpyAsync(sc.depth.p, depth + npix * (size_t)f0, sizeof(float) * npix * m, hipMemcpyHostToDevice, s));
+        a.est = sc.est.p + (size_t)7 * f0;
+        a.ref = sc.ref.p + (size_t)7 * f0;
+        a.counts = sc.counts.p + (size_t)kVsdCounts * f0;
+        // workgroups per pair: enough of them to fill the chip when the launch is small
+        a.parts = (int)std::max<size_t>(1, std::min<size_t>(32, (size_t)2 * device_cu_count() / (size_t)m));
+        launch_vsd(a, m, lds, s);
+        HIP_TRY(hipGetLastError());
+    }
+    launch_vsd_finish(sc.counts.p, n_poses, T, sc.out.p, sc.rows.p, s);
+    HIP_TRY(hipMemcpyAsync(errors_out, sc.out.p, sizeof(double) * n * T, hipMemcpyDeviceToHost, s));
+    if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, sc.rows.p, sizeof(int32_t) * n * (4 + T), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipGetLastError());
+    return ROFT_OK;
+}
+
 // host arithmetic alone (symmetry.h): no device is looked for
 int roft_pose_nearest_equivalent(const double* sym, int n_sym, const double qh[4], const double x[3], const double q[4], double x_out[3],
                                  double q_out[4], int* index_out)

@@ -22,6 +22,7 @@ struct OpContext {
     DeviceMesh mesh;                     // the mesh of the one-mesh calls ...
     std::vector<DeviceMesh> meshes;      // ... and those of the n-mesh silhouette calls (grows, never shrinks)
     PoseErrorScratch pose_errors;
+    VsdScratch vsd;
     DevBuf<unsigned char> slot[kSlots];  // scratch, typed where it is handed out: room / upload.  A call numbers its slots as it likes
     ObjState st;                         // host landing block of the state's upload (begin_object) and read-back (read_state)
 

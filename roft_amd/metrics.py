@@ -140,6 +140,83 @@ def trajectory_mspd(pose_est, pose_ref, pts, cam, symmetries=None, backend="nump
     return _trajectory_sym("mspd", pose_est, pose_ref, pts, symmetries, cam, backend)
 
 
+# ---- BOP's Visible Surface Discrepancy and average recall (include/roft_engine.h section 3i) -----------------
+BOP_VSD_TAUS = np.arange(0.05, 0.51, 0.05)           # misalignment tolerances, in object diameters
+BOP_THRESHOLDS = np.arange(0.05, 0.51, 0.05)         # correctness thresholds of VSD, and of MSSD in object diameters
+BOP_MSPD_THRESHOLDS = np.arange(5, 51, 5)            # ... of MSPD, in pixels of a 640-wide image
+
+
+def _distance_image(depth, cam):
+    """BOP's depth_im_to_dist_im_fast: the distance to the camera centre of every pixel's point; cam = (fx, fy, cx, cy)."""
+    fx, fy, cx, cy = (float(v) for v in cam)
+    d = np.asarray(depth, np.float32).astype(np.float64)
+    a = ((np.arange(d.shape[1], dtype=np.float64) - cx) / fx)[None, :]
+    b = ((np.arange(d.shape[0], dtype=np.float64) - cy) / fy)[:, None]
+    return np.sqrt(((a * d) ** 2 + (b * d) ** 2) + d ** 2)
+
+
+def _visible(model, test, delta):
+    """BOP's visibility mask (mode bop19) of a model distance image against the measured one"""
+    with np.errstate(invalid="ignore"):
+        diff = model.astype(np.float32) - test.astype(np.float32)
+        return ((test > 0) & (model > 0) & (diff <= np.float32(delta))) | ((test == 0) & (model > 0))
+
+
+def vsd_from_depths(depth_est, depth_gt, depth_test, cam, delta=0.015, taus=None, diameter=None, counts=False):
+    """VSD (BOP19: visibility mode bop19, cost `step`) of ONE pose pair from its two depth renders and the sensor's depth image,
+    [H, W] float32 metres, 0 = nothing.  cam = (fx, fy, cx, cy); taus in object diameters when `diameter` is given (> 0), else
+    metres; None: BOP_VSD_TAUS.  Returns errors [n_taus], with counts=True also the integer row n_union, n_inter, n_gt, n_est,
+    fail[0 .. n_taus) -- what ops.pose_errors_vsd computes on the device from the poses."""
+    taus = BOP_VSD_TAUS if taus is None else np.asarray(taus, np.float64).reshape(-1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        T, G, E = (_distance_image(d, cam) for d in (depth_test, depth_gt, depth_est))
+        vg = _visible(G, T, delta)
+        ve = _visible(E, T, delta) | (vg & (E > 0))
+        inter, union = vg & ve, vg | ve
+        c = np.abs(G[inter] - E[inter])
+        if diameter is not None and diameter > 0:
+            c = c / float(diameter)
+        fail = np.array([int(np.count_nonzero(c >= t)) for t in taus], np.int64)
+    n_union, n_inter = int(np.count_nonzero(union)), int(np.count_nonzero(inter))
+    errors = (fail + n_union - n_inter).astype(np.float64) / np.float64(n_union) if n_union > 0 else np.ones(len(taus))
+    if counts:
+        return errors, np.concatenate([[n_union, n_inter, int(np.count_nonzero(vg)), int(np.count_nonzero(ve))], fail]).astype(np.int32)
+    return errors
+
+
+def model_diameter(points, chunk=2048):
+    """The largest distance between two of the points [P, 3] (BOP's object diameter over the model's vertices), chunked: no more
+    than chunk x P distances at a time."""
+    p = np.asarray(points, np.float64).reshape(-1, 3)
+    best = 0.0
+    for k in range(0, len(p), chunk):
+        d = p[k:k + chunk, None, :] - p[None, :, :]
+        best = max(best, float(np.sqrt((d * d).sum(axis=2).max())))
+    return best
+
+
+def bop_recall(errors, thresholds):
+    """The mean over `thresholds` of the fraction of entries of `errors` (any shape) that are < the threshold: BOP's average
+    recall of one pose-error function.  0 when there are no errors."""
+    e = np.asarray(errors, np.float64).reshape(-1)
+    th = np.asarray(thresholds, np.float64).reshape(-1)
+    if e.size == 0:
+        return 0.0
+    return float(np.mean([np.count_nonzero(e < t) / e.size for t in th]))
+
+
+def bop_average_recall(vsd, mssd, mspd, diameter, width):
+    """BOP19's scores of one object's estimates: vsd [F, n_taus] (errors per tau), mssd [F] metres, mspd [F] pixels, the object's
+    diameter (metres) and the image width.  VSD is correct when e < theta, theta in BOP_THRESHOLDS, averaged over taus x theta; MSSD
+    when e < theta x diameter; MSPD when e < theta x width / 640, theta in BOP_MSPD_THRESHOLDS.
+    Returns {"AR_VSD", "AR_MSSD", "AR_MSPD", "AR"}: AR the mean of the three."""
+    out = {"AR_VSD": bop_recall(vsd, BOP_THRESHOLDS),
+           "AR_MSSD": bop_recall(mssd, BOP_THRESHOLDS * float(diameter)),
+           "AR_MSPD": bop_recall(mspd, BOP_MSPD_THRESHOLDS * (float(width) / 640.0))}
+    out["AR"] = (out["AR_VSD"] + out["AR_MSSD"] + out["AR_MSPD"]) / 3.0
+    return out
+
+
 # ---- RMSE metrics of evaluation/metrics.py (the step right after the filtering path) -----------------------
 def _rot_angle_deg(q_ref, q_sig):
     """Geodesic angle of R_ref R_sig^T in degrees (metrics.py:114-144)."""

@@ -359,6 +359,44 @@ def pose_errors_sym(kind, points, est, ref, symmetries=None, cam=None):
     return out
 
 
+def vsd_params(delta=0.015, taus=None, diameter=None, window_pixels=0):
+    """roft_vsd_params: taus None -> np.arange(0.05, 0.51, 0.05); diameter None -> 0 (distances are not normalised)."""
+    taus = np.arange(0.05, 0.51, 0.05) if taus is None else _f64(taus).reshape(-1)
+    if len(taus) > L.VSD_MAX_TAUS:
+        raise ValueError("at most %d taus" % L.VSD_MAX_TAUS)
+    p = L.VsdParams()
+    p.delta, p.n_taus = float(delta), len(taus)
+    for k, t in enumerate(taus):
+        p.taus[k] = float(t)
+    p.diameter = 0.0 if diameter is None else float(diameter)
+    p.window_pixels = int(window_pixels)
+    return p
+
+
+def pose_errors_vsd(cam, mesh, est, ref, depth, delta=0.015, taus=None, diameter=None, window_pixels=0, counts=False):
+    """BOP's Visible Surface Discrepancy of F pose pairs of one mesh against depth images, on the device (roft_pose_errors_vsd; the
+    contract: include/roft_engine.h, section 3i).  cam: L.Camera; mesh: make_mesh(verts, tris); est, ref [F, 7] rows x y z,
+    q = (w, x, y, z); depth [F, H, W] float32 metres (0: no measurement), or [H, W] / [1, H, W]: one image under every pair.
+    taus in object diameters when `diameter` is given, else in metres.  window_pixels > 0 caps the kernel's LDS depth windows
+    (strips; no bit changes).  Returns errors [F, n_taus]; with counts=True also int32 [F, 4 + n_taus]: n_union, n_inter, n_gt,
+    n_est, fail[0 .. n_taus)."""
+    est, ref = _f64(est).reshape(-1, 7), _f64(ref).reshape(-1, 7)
+    if est.shape != ref.shape:
+        raise ValueError("est and ref must hold the same number of poses")
+    depth = np.ascontiguousarray(depth, np.float32)
+    if depth.ndim == 2:
+        depth = depth[None]
+    if depth.ndim != 3 or depth.shape[1:] != (cam.height, cam.width):
+        raise ValueError("depth must be [F, H, W] or [H, W] of the camera's size")
+    p = vsd_params(delta, taus, diameter, window_pixels)
+    n = est.shape[0]
+    errors = np.zeros((n, p.n_taus))
+    rows = np.zeros((n, 4 + p.n_taus), np.int32) if counts else None
+    L.check(L.lib().roft_pose_errors_vsd(C.byref(cam), C.byref(mesh), _p(est), _p(ref), n, _p(depth), depth.shape[0], C.byref(p),
+                                         _p(errors), _p(rows) if counts else None))
+    return (errors, rows) if counts else errors
+
+
 def pose_errors_kernel_ms():
     """Device time (ms, HIP events) of the kernels of the last pose_errors call, without its copies."""
     ms = C.c_double(0.0)
