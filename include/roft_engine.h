@@ -1226,6 +1226,54 @@ int roft_pose_errors_vsd(const roft_camera* cam, const roft_mesh* mesh, const do
                          const roft_vsd_params* p, double* errors_out /* [n_poses][n_taus] */,
                          int32_t* counts_out /* [n_poses][4 + n_taus], may be NULL */);
 
+/* ---- (3j) pose hypotheses: many candidate poses of one object scored against one frame in one launch ---------------------------------- *
+ * Track quality (section 3d) says that an estimate is bad; it does not say where the object is instead.  A caller with several
+ * candidate poses for one object and one frame -- a detector's N-best list, the equivalent orientations a detector does not
+ * disambiguate, a neighbourhood of a drifting estimate -- scores all of them here in one call: the mask, the depth and the mesh are
+ * uploaded once (on an engine: not at all, they are resident), one launch draws and scores every pose, and one record of section 3d
+ * comes back per pose.  What the caller does with the records -- pick one, search (roft_amd/relocalise.py is a host-side compass
+ * search over this call; its step sizes are those of one CPU experiment and nobody has tuned them), restart the track with
+ * roft_objects_restart -- is the caller's.
+ *
+ * roft_pose_hypotheses_score: HOST buffers, device 0.  poses: n rows of 7 doubles x y z, q = w x y z, the quaternion used as given.
+ * Operation by operation, by reference to section 3d:
+ *   out[i]    bit for bit what roft_track_quality(cam, divider, depth, mask, mesh, poses[i], poses[i] + 3, depth_tolerance,
+ *             depth_maximum, window_pixels, ..) returns -- M, D, d, w, h, R, every count, S and depth_err as defined there --,
+ *             frame = 0 included
+ *   out[i]    is a function of pose i and the shared inputs alone: not of n, of the pose's position in the call, of the other poses,
+ *             of window_pixels (which caps the LDS depth window as in 3d: strips, no bit changes), of how the launch maps poses to
+ *             workgroups, or of the run -- every figure is a sum of integers
+ *   non-finite  a pose with a NaN or infinite component draws nothing: n_mask as for every other pose, all other counts 0, depth_err
+ *             DBL_MAX; it changes no other entry.  (Such a pose is not part of the equivalence with roft_track_quality.)
+ *   n == 0    ROFT_OK, nothing is touched.  Any n up to 2^20 is accepted; a call is scored in chunks of 65 536 poses.
+ * ROFT_ERR_INVALID, the reason in roft_last_error_string, before a device is looked for: a NULL pointer (with n > 0); n < 0 or
+ * n > 2^20; divider <= 0; a negative or NaN depth_tolerance; window_pixels < 0; a mesh the other operators refuse (a NULL array, an
+ * index out of range; a mesh of 0 triangles is accepted and draws nothing, as in 3d).  Without a device a well-formed call returns
+ * ROFT_ERR_DEVICE: there is no CPU path.
+ *
+ * roft_engine_score_hypotheses: the same launch on what the engine holds of object obj_id's LAST STEPPED FRAME; syncs like
+ * roft_get_mask.  M is what roft_get_mask returns; D is the float depth of that frame as the kernels read it (with raw depth or
+ * rectification enabled: the product roft_engine_get_depth returns; else the caller's image -- with DEVICE inputs the caller's buffer
+ * must still hold it, as the next frame's velocity stage requires anyway); the mesh is the slot's resident mesh, an object without one
+ * has R = 0; d is the engine's render divider; depth_maximum is roft_config::depth_maximum.  out[i] equals
+ * roft_pose_hypotheses_score on those images bit for bit, except `frame`, which is the engine frame counter of the scored frame.
+ * With track quality enabled, the record of the frame's own estimate (pose[6..12] of its log row) is the engine's
+ * roft_quality_record of that frame when depth_tolerance is the one quality was enabled with.
+ * The call reads engine state and writes only its own buffers: every later output of the engine is what it would have been without
+ * it.  It needs neither the log nor track quality enabled.
+ * ROFT_ERR_STATE: no stepped frame for the slot -- also a restarted slot before its next step: exactly where roft_get_mask
+ * refuses --, or a submitted batch that has not been stepped.  ROFT_ERR_INVALID: a bad obj_id; the argument checks above; an engine
+ * with render_mode == ROFT_RENDER_GL (the reason of section 3d); a render target too wide for the kernel's depth window.
+ *
+ * Not in scope: a search loop on the device; hypotheses for several objects in one call; ROFT_RENDER_GL; the C++ class facade
+ * (include/ROFT). */
+int roft_pose_hypotheses_score(const roft_camera* cam, int divider, const float* depth, const uint8_t* mask,
+                               const roft_mesh* mesh, const double* poses /* n x 7: x y z, q = w x y z */, int n,
+                               float depth_tolerance, double depth_maximum, int window_pixels,
+                               roft_quality_record* out /* n */);
+int roft_engine_score_hypotheses(roft_engine* e, int obj_id, const double* poses, int n, float depth_tolerance,
+                                 roft_quality_record* out /* n */);
+
 /* ---- (4) diagnostics (tests and profiling tools; not needed by an integration) --------------------------------- */
 /* The per-frame program builder without a device: the host-side mirror of CartesianQuaternionMeasurement::freeze's
  * Standard / PopBufferedMeasurement / RepeatOnlyVelocity state machine (cpp:92-348) and of the re-sync loop of

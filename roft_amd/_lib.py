@@ -335,6 +335,9 @@ ABI = (
     # (3i) VSD scores
     Fn("roft_default_vsd_params", _int, [_P(VsdParams)], _OPTIONAL),
     Fn("roft_pose_errors_vsd", _int, [_P(Camera), _P(Mesh), _vp, _vp, _int, _vp, _int, _P(VsdParams), _vp, _vp], _OPTIONAL),
+    # (3j) pose hypotheses
+    Fn("roft_pose_hypotheses_score", _int, [_P(Camera), _int, _vp, _vp, _P(Mesh), _vp, _int, C.c_float, C.c_double, _int, _P(QualityRecord)], _OPTIONAL),
+    Fn("roft_engine_score_hypotheses", _int, [_vp, _int, _vp, _int, C.c_float, _P(QualityRecord)], _OPTIONAL),
     # (4) diagnostics
     Fn("roft_debug_plan", _int, [_P(Config), _vp, _int, _vp, _vp, _vp, _vp], _OPTIONAL),
     Fn("roft_debug_restart_check", _int, [_P(Config), _int, _ip, _ip, _int, _ip, _P(ObjectDesc), _int, _int], _OPTIONAL),

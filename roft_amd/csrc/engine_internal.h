@@ -16,6 +16,7 @@
 //   engine_ops.hip      the operator-level entry points on that context (roft_flow_measurement ... roft_outlier_test, roft_pose_errors,
 //                       roft_pose_errors_vsd)
 //   engine_quality.hip  track quality: roft_engine_enable_quality / _get_quality, the batch's quality launch; roft_track_quality (on op_context.h)
+//   engine_hypotheses.hip  pose hypotheses: roft_pose_hypotheses_score (on op_context.h) and roft_engine_score_hypotheses, one launcher
 //   engine_debug.hip    roft_debug_* (diagnostics and experiments)
 //   scene.hip           the scene renderer: roft_scene_renderer_*, roft_render_scene
 //   mesh_class.h        a caller's mesh on the host: has_mesh, the array check, classification, the three upload layouts (host-only C++)
@@ -50,6 +51,7 @@
 #include "quality.h"
 #include "symmetry.h"
 #include "vsd.h"
+#include "hypotheses.h"
 
 static_assert(roft::host::kPlanLanes == roft::kNumLin, "batch_plan.h plans for the engine's pose lanes");
 
@@ -478,6 +480,14 @@ struct EngineQuality {
     int last_slot = -1;                  // batch-ring slot of the last launch
 };
 
+// Pose hypotheses (roft_pose_hypotheses_score, roft_engine_score_hypotheses): what a call owns on the device -- one chunk of poses, its
+// records, the plane's bit count.  Grows to the largest chunk it has held (at most kHypothesesChunk poses), never shrinks.
+struct HypothesesScratch {
+    DevBuf<double> poses;          // [chunk][7]
+    DevBuf<QualityRaw> records;    // [chunk]
+    DevBuf<int> n_mask;            // one word
+};
+
 // Device copies of HOST inputs: a ring of `retain` frame slots, each a bump allocator over chunks of device memory that
 // are allocated when a frame first needs them and kept (a slot grows to the largest frame it ever held: 64 objects with
 // their own 640x480 depth + CV_32FC2 flow + mask streams need 239 MB per slot, a shared scene 7 MB + the masks); identical
@@ -645,6 +655,7 @@ struct roft_engine {
     EngineDepth depth;                     // raw sensor depth -> float depth (roft_engine_enable_raw_depth); its products ride on SubmitFacts::produced_flows
     EngineRectify rectify;                 // distorted frames -> the pinhole camera (roft_engine_enable_rectification); rides on produced_flows like the depth products
     EngineQuality quality;                 // track quality (roft_engine_enable_quality)
+    HypothesesScratch hypotheses;          // roft_engine_score_hypotheses: the call's own buffers
     EnginePoseMasks pose_masks;            // masks from poses (roft_engine_enable_pose_masks)
     int prev_T = 0;                 // frames of the batch stepped before
     int batch_counter = 0, frame_counter = 0;

@@ -1,4 +1,5 @@
-// op_context.h -- the one context of the operator-level entry points (engine_ops.hip, roft_track_quality in engine_quality.hip): the
+// op_context.h -- the one context of the operator-level entry points (engine_ops.hip, roft_track_quality in engine_quality.hip,
+// roft_pose_hypotheses_score in engine_hypotheses.hip): the
 // engine's own kernels on one object and one frame, on device 0.
 //
 // THE RULE: the context owns device memory, a stream and a mutex.  It never holds configuration.  Every call derives the EngineArrays
@@ -19,6 +20,7 @@ struct OpContext {
     Arrays arr;                          // one object, one frame, with the one-row log.  arr.a is written by Arrays::alloc / ensure_zmerge and nobody else
     int W = 0, H = 0, radius = 0;        // what arr is allocated for (0: nothing yet)
     DevBuf<QualityRaw> quality;          // the record of roft_track_quality
+    HypothesesScratch hypotheses;        // the poses and records of roft_pose_hypotheses_score (grow with the call's chunk)
     DeviceMesh mesh;                     // the mesh of the one-mesh calls ...
     std::vector<DeviceMesh> meshes;      // ... and those of the n-mesh silhouette calls (grows, never shrinks)
     PoseErrorScratch pose_errors;

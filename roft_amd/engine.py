@@ -365,6 +365,25 @@ class ROFTFilterBatch:
         L.check(L.lib().roft_debug_quality_kernel_ms(self._h, C.byref(ms)))
         return ms.value
 
+    def score_hypotheses(self, obj, poses, depth_tolerance=0.01):
+        """The track-quality record of each of n candidate poses [n, 7] (x y z, q = w x y z) of object `obj` against its last
+        stepped frame -- the mask mask(obj) returns, that frame's float depth, the slot's resident mesh -- in one launch on the
+        resident images (roft_engine_score_hypotheses; include/roft_engine.h, section 3j).  Reads engine state, changes none.
+        Returns ops.QUALITY_DTYPE[n]; `frame` is the scored frame.  Syncs."""
+        from .ops import QUALITY_DTYPE, hypothesis_poses
+        poses = hypothesis_poses(poses)
+        out = np.zeros(poses.shape[0], QUALITY_DTYPE)
+        L.check(L.lib().roft_engine_score_hypotheses(self._h, obj, poses.ctypes.data, poses.shape[0], float(depth_tolerance),
+                                                     out.ctypes.data_as(C.POINTER(L.QualityRecord))))
+        return out
+
+    def relocalise(self, obj, x, q, depth_tolerance=0.01, **kw):
+        """Where is object `obj` instead?  relocalise.compass_search from the pose (x, q) over score_hypotheses on the last stepped
+        frame; **kw: its t_step, r_step, rounds, max_halvings.  Returns (x, q, trace).  What to do with the pose is the caller's --
+        restart(...) with it is one option."""
+        from .relocalise import compass_search
+        return compass_search(lambda poses: self.score_hypotheses(obj, poses, depth_tolerance), x, q, **kw)
+
     def enable_pose_masks(self, obj_ids=None):
         """Masks from poses (roft_engine_enable_pose_masks): the listed objects (None: every object the engine has at its first
         frame) take the silhouette of a delivered pose as the frame's mask wherever the frame brings neither `mask` nor `labels`

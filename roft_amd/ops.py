@@ -301,6 +301,29 @@ def track_quality(cam, divider, depth, mask, mesh, x, q, depth_tolerance=0.01, d
     return np.frombuffer(bytes(rec), QUALITY_DTYPE)[0].copy()
 
 
+def hypothesis_poses(poses):
+    """Candidate poses as the ABI takes them: [n, 7] float64 rows x y z, q = (w, x, y, z)."""
+    poses = np.asarray(poses, np.float64)
+    if poses.size % 7:
+        raise ValueError("poses must hold 7 numbers per pose: x y z, q = (w, x, y, z)")
+    return np.ascontiguousarray(poses.reshape(-1, 7))
+
+
+def pose_hypotheses_score(cam, divider, depth, mask, mesh, poses, depth_tolerance=0.01, depth_maximum=2.0, window_pixels=0):
+    """The track-quality record of each of n candidate poses [n, 7] (x y z, q = w x y z) of `mesh` against one mask and one depth
+    image, in one launch (roft_pose_hypotheses_score; the contract: include/roft_engine.h, section 3j): entry i is, bit for bit,
+    track_quality(..., poses[i, :3], poses[i, 3:], ...).  A pose with a non-finite component draws nothing.  Returns
+    QUALITY_DTYPE[n]."""
+    depth = np.ascontiguousarray(depth, np.float32)
+    mask = np.ascontiguousarray(mask, np.uint8)
+    poses = hypothesis_poses(poses)
+    n = poses.shape[0]
+    out = np.zeros(n, QUALITY_DTYPE)
+    L.check(L.lib().roft_pose_hypotheses_score(C.byref(cam), divider, _p(depth), _p(mask), C.byref(mesh), _p(poses), n, float(depth_tolerance),
+                                               float(depth_maximum), window_pixels, out.ctypes.data_as(C.POINTER(L.QualityRecord))))
+    return out
+
+
 POSE_ERROR_KINDS = {"add": L.POSE_ERROR_ADD, "adi": L.POSE_ERROR_ADDS, "adds": L.POSE_ERROR_ADDS,
                     "mssd": L.POSE_ERROR_MSSD, "mspd": L.POSE_ERROR_MSPD}
 
