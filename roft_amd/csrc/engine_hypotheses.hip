@@ -59,8 +59,8 @@ extern "C" int roft_pose_hypotheses_score(const roft_camera* cam, int divider, c
     if (a.tile_w <= 0 || a.tile_h <= 0) return fail(ROFT_ERR_INVALID, "divider larger than the image");
     HypothesesArgs ha;
     std::memset(&ha, 0, sizeof(ha));
-    size_t lds = 0;
-    if (!quality_window_shape(has_mesh(*mesh) ? mesh->n_verts : 0, a.tile_w, window_pixels, ha.vcache_cap, ha.win_cap, lds))
+    const RasterShape sh = quality_window_shape(has_mesh(*mesh) ? mesh->n_verts : 0, a.tile_w, window_pixels);
+    if (!sh.ok)
         return fail(ROFT_ERR_INVALID, "track quality: the render target is too wide for the kernel's depth window");
     const size_t npix = (size_t)cam->width * cam->height;
     hipStream_t s = c.stream;
@@ -84,14 +84,16 @@ extern "C" int roft_pose_hypotheses_score(const roft_camera* cam, int divider, c
     ha.plane = a.planes + plane_offset(a, 0, kSlotNew, 1);
     ha.plane_words = a.plane_words;
     ha.depth = d_depth;
-    ha.mesh = c.mesh.scene_mesh();
+    ha.mesh = c.mesh.view();
+    ha.vcache_cap = sh.vcache_cap;
+    ha.win_cap = sh.win_cap;
     ha.cam = a.cam;
     ha.tile_w = a.tile_w;
     ha.tile_h = a.tile_h;
     ha.frame = 0;
     ha.depth_tolerance = depth_tolerance;
     ha.depth_maximum = depth_maximum;
-    return score_in_chunks(ha, c.hypotheses, lds, poses, n, s, out);
+    return score_in_chunks(ha, c.hypotheses, sh.lds, poses, n, s, out);
 }
 
 extern "C" int roft_engine_score_hypotheses(roft_engine* e, int obj_id, const double* poses, int n, float depth_tolerance,
@@ -115,18 +117,20 @@ extern "C" int roft_engine_score_hypotheses(roft_engine* e, int obj_id, const do
     const bool mesh = has_mesh(prm);
     HypothesesArgs ha;
     std::memset(&ha, 0, sizeof(ha));
-    size_t lds = 0;
-    if (!quality_window_shape(mesh ? prm.n_verts : 0, a.tile_w, 0, ha.vcache_cap, ha.win_cap, lds))
+    const RasterShape sh = quality_window_shape(mesh ? prm.n_verts : 0, a.tile_w, 0);
+    if (!sh.ok)
         return fail(ROFT_ERR_INVALID, "track quality: the render target is too wide for the kernel's depth window");
     ha.plane = a.planes + plane_offset(a, obj_id, (o.frame_idx - 1) % kPlaneSlots, 1);   // (the slot roft_get_mask reads)
     ha.plane_words = a.plane_words;
     ha.depth = ho.stepped_depth;
-    if (mesh) ha.mesh = SceneMesh{prm.verts, prm.tris, prm.tri_flip, prm.n_verts, prm.n_tris};
+    if (mesh) ha.mesh = mesh_view(prm);
+    ha.vcache_cap = sh.vcache_cap;
+    ha.win_cap = sh.win_cap;
     ha.cam = a.cam;
     ha.tile_w = a.tile_w;
     ha.tile_h = a.tile_h;
     ha.frame = o.frame_idx - 1;
     ha.depth_tolerance = depth_tolerance;
     ha.depth_maximum = e->cfg.depth_maximum;
-    return score_in_chunks(ha, e->hypotheses, lds, poses, n, e->stream, out);
+    return score_in_chunks(ha, e->hypotheses, sh.lds, poses, n, e->stream, out);
 }

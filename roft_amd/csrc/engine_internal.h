@@ -126,14 +126,14 @@ struct DeviceMesh {
     }
 
     // what a kernel is given: null pointers without a mesh, and no flip bits unless THIS upload made them
-    SceneMesh scene_mesh() const
+    MeshView view() const
     {
         const bool has = has_mesh(*this);
-        return SceneMesh{has ? verts.p : nullptr, has ? tris.p : nullptr, closed ? flip.p : nullptr, n_verts, n_tris};
+        return MeshView{has ? verts.p : nullptr, has ? tris.p : nullptr, closed ? flip.p : nullptr, n_verts, n_tris};
     }
     void describe(ObjParams& p) const   // (the mesh fields of an object's parameter block)
     {
-        const SceneMesh m = scene_mesh();
+        const MeshView m = view();
         p.verts = m.verts; p.tris = m.tris; p.tri_flip = m.flip;
         p.n_verts = m.n_verts; p.n_tris = m.n_tris;
         const bool cl = has_mesh(*this) && n_clusters > 0;

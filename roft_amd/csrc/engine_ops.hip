@@ -794,9 +794,9 @@ int roft_pose_errors_vsd(const roft_camera* cam, const roft_mesh* mesh, const do
     if ((long long)cam->width * cam->height >= (1ll << 24)) return fail(ROFT_ERR_INVALID, "width * height must be < 2^24");
     VsdArgs a;
     std::memset(&a, 0, sizeof(a));
-    size_t lds = 0;
-    if (!vsd_shape(mesh->n_verts, cam->width, p->window_pixels, a.vcache_cap, a.win_alloc, a.win_cap, lds))
-        return fail(ROFT_ERR_INVALID, "VSD: an image row is wider than the kernel's two depth windows");
+    const RasterShape sh = vsd_shape(mesh->n_verts, cam->width, p->window_pixels);
+    if (!sh.ok) return fail(ROFT_ERR_INVALID, "VSD: an image row is wider than the kernel's two depth windows");
+    a.vcache_cap = sh.vcache_cap; a.win_alloc = sh.win_alloc; a.win_cap = sh.win_cap;
     if (n_poses == 0) return ROFT_OK;
     OpContext& c = op_context();
     std::unique_lock<std::mutex> lk;
@@ -819,7 +819,7 @@ int roft_pose_errors_vsd(const roft_camera* cam, const roft_mesh* mesh, const do
     HIP_TRY(hipMemcpyAsync(sc.ref.p, ref, sizeof(double) * 7 * n, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(sc.counts.p, 0, sizeof(int32_t) * n * kVsdCounts, s));
     if (shared) HIP_TRY(hipMemcpyAsync(sc.depth.p, depth, sizeof(float) * npix, hipMemcpyHostToDevice, s));
-    a.mesh = c.mesh.scene_mesh();
+    a.mesh = c.mesh.view();
     a.depth = sc.depth.p;
     a.depth_stride = shared ? 0 : npix;
     a.W = cam->width; a.H = cam->height;
@@ -837,7 +837,7 @@ int roft_pose_errors_vsd(const roft_camera* cam, const roft_mesh* mesh, const do
         a.counts = sc.counts.p + (size_t)kVsdCounts * f0;
         // workgroups per pair: enough of them to fill the chip when the launch is small
         a.parts = (int)std::max<size_t>(1, std::min<size_t>(32, (size_t)2 * device_cu_count() / (size_t)m));
-        launch_vsd(a, m, lds, s);
+        launch_vsd(a, m, sh.lds, s);
         HIP_TRY(hipGetLastError());
     }
     launch_vsd_finish(sc.counts.p, n_poses, T, sc.out.p, sc.rows.p, s);

@@ -4,7 +4,7 @@
 #pragma once
 
 #include "quality.h"
-#include "scene.h"
+#include "raster.h"
 
 namespace roft {
 
@@ -15,7 +15,7 @@ struct HypothesesArgs {
     const uint32_t* plane;   // the object plane M (wpr words per row, plane_words in all)
     size_t plane_words;
     const float* depth;      // D
-    SceneMesh mesh;          // as ObjParams describes it: walk order, flip bits of a closed mesh (n_tris == 0: nothing is drawn)
+    MeshView mesh;           // as ObjParams describes it: walk order, flip bits of a closed mesh (n_tris == 0: nothing is drawn)
     DevCamera cam;           // with the divider the records are made under
     int tile_w, tile_h;
     const double* poses;     // [n][7] x y z, w x y z of the launch's hypotheses
@@ -29,7 +29,7 @@ struct HypothesesArgs {
 };
 
 // n hypotheses (n <= kHypothesesChunk): the plane's bit count once, then one workgroup per hypothesis.  a.vcache_cap / win_cap and lds
-// from quality_window_shape (quality.h): the two kernels of quality_body.h share the shape and refuse the same targets.
+// from quality_window_shape (raster_shape.h): the two kernels of quality_body.h share the shape and refuse the same targets.
 void launch_hypotheses(const HypothesesArgs& a, int n, size_t lds, hipStream_t s);
 
 }  // namespace roft

@@ -5,15 +5,13 @@
 // workgroup per hypothesis runs quality_body.h -- the body quality_kernel runs for the engine's estimate -- on its own pose, against
 // the plane, the depth and the mesh all hypotheses share.  n_mask is the same for every pose: plane_count_kernel counts the plane's
 // bits once, ahead of the hypotheses on the same stream, and every record copies the word.  A pose with a non-finite component
-// draws nothing.  The kernel takes a plain argument block (hypotheses.h), no engine structure: the operator (on the one-object
+// draws nothing (pose_is_finite).  The kernel takes a plain argument block (hypotheses.h), no engine structure: the operator (on the one-object
 // context) and the engine entry (on the idle engine's own stream) use the same launcher.
 //
 // Workgroup shape: 1024 threads with quality_kernel's LDS (the vertex cache and a 16 k-pixel window), one workgroup per CU.  256-thread
 // workgroups with a quarter of the LDS -- four hypotheses per CU, a large mesh projected per triangle -- were measured and lost
 // (docs/notebook.md); no bit would depend on the shape.
 // Built with -ffp-contract=off like every user of raster.h.
-#include <algorithm>
-
 #include "hypotheses.h"
 #include "quality_body.h"
 
@@ -23,17 +21,11 @@ constexpr int kHypothesesThreads = 1024;
 
 __global__ __launch_bounds__(1024) void plane_count_kernel(const uint32_t* plane, size_t plane_words, int* n_mask)
 {
-    __shared__ int s_n[1024 / 64];
-    const int tid = threadIdx.x;
-    int n = plane_bits_share(plane, plane_words, tid, 1024);
-    for (int off = 32; off > 0; off >>= 1) n += __shfl_down(n, off, 64);
-    if ((tid & 63) == 0) s_n[tid >> 6] = n;
+    __shared__ int s_n[1024 / 64][1];
+    int n[1] = {plane_bits_share(plane, plane_words, threadIdx.x, 1024)};
+    wave_sums_to_rows(n, s_n);
     __syncthreads();
-    if (tid == 0) {
-        int tot = 0;
-        for (int w = 0; w < 1024 / 64; ++w) tot += s_n[w];
-        *n_mask = tot;
-    }
+    if (threadIdx.x == 0) *n_mask = rows_total<1024>(s_n, 0);
 }
 
 __global__ __launch_bounds__(kHypothesesThreads) void hypotheses_kernel(HypothesesArgs a)
@@ -41,17 +33,13 @@ __global__ __launch_bounds__(kHypothesesThreads) void hypotheses_kernel(Hypothes
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int h = blockIdx.x, tid = threadIdx.x;
     const double* pose = a.poses + (size_t)7 * h;
-    bool finite = true;
-#pragma unroll
-    for (int i = 0; i < 7; ++i) finite = finite && isfinite(pose[i]);
     QualitySums tot;
-    if (finite) {   // (uniform over the workgroup: the body's barriers are met by all or by none)
+    if (pose_is_finite(pose)) {   // (uniform over the workgroup: the body's barriers are met by all or by none)
         const int d = a.cam.divider;
         QualityScene sc;
         sc.plane = a.plane;
         sc.depth = a.depth;
-        sc.verts = a.mesh.verts; sc.tris = a.mesh.tris; sc.tri_flip = a.mesh.flip;
-        sc.n_verts = a.mesh.n_verts; sc.n_tris = a.mesh.n_tris;
+        sc.mesh = a.mesh;
         sc.d = d; sc.tw = a.tile_w; sc.th = a.tile_h; sc.W = a.cam.W; sc.wpr = a.cam.wpr;
         sc.fx = (float)(a.cam.fx / d); sc.fy = (float)(a.cam.fy / d); sc.cx = (float)(a.cam.cx / d); sc.cy = (float)(a.cam.cy / d);
         sc.depth_tolerance = a.depth_tolerance;

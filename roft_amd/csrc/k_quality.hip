@@ -2,12 +2,8 @@
 // own mask and depth (include/roft_engine.h, section 3d).
 //
 // One workgroup per (object, frame) pair that gets a record.  It counts the bits of the whole object plane and hands the pose the
-// step left in the log row to quality_body.h, which projects the mesh, draws it into an LDS depth window exactly as the outlier
-// test does, walks the image pixels under it and adds the counts as integers and |e| as a LikelihoodSum: every figure is a sum of
-// integers, so no record depends on strips, threads or waves.  (The same body scores pose hypotheses: k_hypotheses.hip.)
-// Built with -ffp-contract=off like every user of raster.h.
-#include <algorithm>
-
+// step left in the log row to quality_body.h, which draws the mesh and makes the record's sums.  (The same body scores pose
+// hypotheses: k_hypotheses.hip.)  Built with -ffp-contract=off like every user of raster.h.
 #include "quality.h"
 #include "quality_body.h"
 
@@ -28,8 +24,7 @@ __global__ __launch_bounds__(kQualityThreads) void quality_kernel(EngineArrays a
     QualityScene sc;
     sc.plane = a.planes + plane_offset(a, obj, c.slot_cur, 1);
     sc.depth = c.depth_cur;
-    sc.verts = prm.verts; sc.tris = prm.tris; sc.tri_flip = prm.tri_flip;
-    sc.n_verts = prm.n_verts; sc.n_tris = prm.n_tris;
+    sc.mesh = mesh_view(prm);
     sc.d = d; sc.tw = a.tile_w; sc.th = a.tile_h; sc.W = a.cam.W; sc.wpr = a.cam.wpr;
     sc.fx = (float)(a.cam.fx / d); sc.fy = (float)(a.cam.fy / d); sc.cx = (float)(a.cam.cx / d); sc.cy = (float)(a.cam.cy / d);
     sc.depth_tolerance = qa.depth_tolerance;
@@ -51,35 +46,7 @@ __global__ __launch_bounds__(kQualityThreads) void quality_kernel(EngineArrays a
     }
 }
 
-// LDS of a workgroup: the projected vertices of the largest mesh where they leave room for a window, and a window of 16 k pixels
-// (an object's window is about 70 x 90 of 320 x 240 at the metric shape; a larger one is drawn in strips) -- not the whole LDS, so
-// that workgroups of the chains the launch runs next to still find a place on the CU.
-bool quality_window_shape(int max_verts, int tile_w, int window_pixels, int& vcache_cap, int& win_cap, size_t& lds)
-{
-    const size_t lds_total = kRasterLdsBudget;
-    const size_t vbytes = vertex_cache_bytes(max_verts);
-    const size_t min_win = 4 * (size_t)std::max(8192, tile_w);
-    const bool cache = vbytes + min_win <= lds_total;
-    vcache_cap = cache ? max_verts : 0;
-    const size_t room = (lds_total - (cache ? vbytes : 0)) / 4;
-    if ((size_t)tile_w > room) return false;   // not even one row of the target
-    win_cap = (int)std::min<size_t>(room, (size_t)std::max(16384, tile_w));
-    lds = (cache ? vbytes : 0) + 4 * (size_t)win_cap;
-    if (window_pixels > 0) win_cap = std::max(tile_w, std::min(win_cap, window_pixels));
-    return true;
-}
-
-static bool quality_shape(const EngineArrays& a, int window_pixels, int& vcache_cap, int& win_cap, size_t& lds)
-{
-    return quality_window_shape(a.max_verts, a.tile_w, window_pixels, vcache_cap, win_cap, lds);
-}
-
-bool quality_fits(const EngineArrays& a)
-{
-    int vc, wc;
-    size_t lds;
-    return quality_shape(a, 0, vc, wc, lds);
-}
+bool quality_fits(const EngineArrays& a) { return quality_window_shape(a.max_verts, a.tile_w, 0).ok; }
 
 void launch_quality(const EngineArrays& a, QualityRaw* ring, int cap, unsigned frames_packed, int n_frames, float depth_tolerance,
                     double depth_maximum, int window_pixels, hipStream_t s, hipEvent_t start, hipEvent_t stop)
@@ -90,10 +57,12 @@ void launch_quality(const EngineArrays& a, QualityRaw* ring, int cap, unsigned f
     qa.frames_packed = frames_packed;
     qa.depth_tolerance = depth_tolerance;
     qa.depth_maximum = depth_maximum;
-    size_t lds = 0;
-    if (!quality_shape(a, window_pixels, qa.vcache_cap, qa.win_cap, lds)) return;   // (callers ask quality_fits first)
+    const RasterShape sh = quality_window_shape(a.max_verts, a.tile_w, window_pixels);
+    if (!sh.ok) return;   // (callers ask quality_fits first)
+    qa.vcache_cap = sh.vcache_cap;
+    qa.win_cap = sh.win_cap;
     (void)set_max_dynamic_lds(reinterpret_cast<const void*>(quality_kernel), (int)kRasterLdsBudget);
-    hipExtLaunchKernelGGL(quality_kernel, dim3(a.n_obj, n_frames), dim3(kQualityThreads), (uint32_t)lds, s, start, stop, 0, a, qa);
+    hipExtLaunchKernelGGL(quality_kernel, dim3(a.n_obj, n_frames), dim3(kQualityThreads), (uint32_t)sh.lds, s, start, stop, 0, a, qa);
 }
 
 }  // namespace roft

@@ -8,17 +8,15 @@
 //                                               src/roft-lib/shader/shader_model.frag:30-52
 //
 // What is here.
-//  * outlier_fused_kernel<GL>, the engine's test: one launch renders an alternative into a window in LDS -- the pixel box of the
-//    mesh, resolved with LDS atomicMin, so the window is bit-identical from run to run -- and sums the likelihood over the buffered
-//    features (k_features.hip) where the window lies.  No OpenGL, no z-buffer in memory.  An alternative is shared by `parts`
-//    workgroups as bands of the window's rows x groups of its triangles; a window that does not fit the LDS is drawn in strips.
-//    The kernel is a list of stages (job, window box, band split; per strip clear, draw, merge, dump, score; band sums), and the
-//    two render modes differ in three of them and in the window's type:
-//      - the contract (GL = false, the hot path): raster.h's arithmetic, IEEE float in the operation order of oracle/ro_render.c
-//        (this file is built with -ffp-contract=off); a wave projects and draws one 64-triangle cluster at a time
-//        (mesh_clusters.h), the box comes from the corners of the mesh's box, the window holds depths (DepthWindow);
+//  * outlier_fused_kernel<GL>, the engine's test: one launch draws an alternative into an LDS window by the pieces of raster.h's
+//    draw contract (the box, the strips, DepthWindow) and sums the likelihood over the buffered features (k_features.hip) where
+//    the window lies.  No OpenGL, no z-buffer in memory.  What this file adds: an alternative is shared by `parts` workgroups as
+//    bands of the box's rows x groups of its triangles (band_split, merge_slabs), and each render mode walks the triangles its way:
+//      - the contract (GL = false, the hot path): a wave projects and draws one 64-triangle cluster at a time (draw_clusters over
+//        mesh_clusters.h), and the box comes from the corners of the mesh's box (box_from_corners) instead of a vertex pass;
 //      - ROFT_RENDER_GL (GL = true, opt-in, twice the time): raster_gl.h's arithmetic, every triangle of `tris` in the caller's
-//        order over a vertex cache in LDS, the window holds (depth, triangle) keys (GlWindow).
+//        order over a vertex cache in LDS (draw_triangles_gl), the window holds (depth, triangle) keys (GlWindow).
+//    The stages: job, window box, band split; per strip clear, draw, merge, dump, score; band sums.
 //  * launch_outlier: the launch shape (OutlierShape) and the split override.
 //  * outlier_kernel, the operator-level likelihood and decision over z-buffers in memory (roft_depth_likelihood).
 #include <algorithm>
@@ -202,34 +200,9 @@ __device__ __forceinline__ bool fused_job(const EngineArrays& a, int lin, int pa
     return true;
 }
 
-// One strip of the window: columns i0 .. i1 (win_w of them), rows js .. je of the render target, npx pixels, row-major.
-struct Strip {
-    int i0, i1, js, je, win_w, npx;
-};
-
 // The window of a render mode, in dynamic LDS: what a pixel holds, what "empty" is, how the rasteriser stores into it and how a
-// depth is read back.  Pixel i of a strip is (i0 + i % win_w, js + i / win_w).  clear / the stores / the reads each need a barrier
-// between them; the stages below say which.
-
-// The contract's window: a pixel is the IEEE bits of its (positive) eye-space depth, kDepthEmpty where nothing was drawn.
-struct DepthWindow {
-    uint32_t* z;   // [win_cap]
-    __device__ __forceinline__ void clear(int npx) const
-    {
-        for (int i = threadIdx.x; i < npx; i += kFusedThreads) z[i] = kDepthEmpty;
-    }
-    // raster_projected's `store(i, j, z)`: order-free minimum of the depth bits
-    __device__ __forceinline__ auto store(const Strip& s) const
-    {
-        ROFT_LDS uint32_t* const zw = pin_lds(z);
-        const int i0 = s.i0, js = s.js, win_w = s.win_w;
-        return [zw, i0, js, win_w](int i, int j, float depth) {
-            (void)__hip_atomic_fetch_min(zw + ((j - js) * win_w + (i - i0)), __float_as_uint(depth), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        };
-    }
-    __device__ __forceinline__ bool covered(int i) const { return z[i] != kDepthEmpty; }
-    __device__ __forceinline__ float depth(int i, int, int) const { return __uint_as_float(z[i]); }
-};
+// depth is read back, strip by strip (Strip, raster.h).  clear / the stores / the reads each need a barrier between them; the
+// stages below say which.  The contract's window is raster.h's DepthWindow.
 
 // project_mesh's / fetch_triangle's `project` under the GL numerics
 struct GlProject {
@@ -247,10 +220,7 @@ struct GlWindow {
     float* s_v;      // [3 * vcache_cap] projected vertices (box_from_vertices fills them when `cached`)
     bool cached;
     const FusedJob& job;
-    __device__ __forceinline__ void clear(int npx) const
-    {
-        for (int i = threadIdx.x; i < npx; i += kFusedThreads) k[i] = kGlKeyClear;
-    }
+    __device__ __forceinline__ void clear(int npx, int threads) const { for (int i = threadIdx.x; i < npx; i += threads) k[i] = kGlKeyClear; }
     // `store(i, j, key)`: the nearest fragment, the first drawn among equal depths, whatever order the threads draw in
     __device__ __forceinline__ auto store(const Strip& s) const
     {
@@ -287,17 +257,16 @@ __device__ __forceinline__ auto open_window(unsigned char* smem, int vcache_cap,
         return DepthWindow{reinterpret_cast<uint32_t*>(smem)};
 }
 
-// window box, both modes: leave s_box = {i0, j0, i1, j1} and *s_behind in project_mesh's format (raster.h), behind a barrier of
-// their own.  They write shared memory first: the caller has no other use of s_box / s_behind / s_settled in flight.
+// window box, both modes: leave `sh` as project_mesh does (raster.h), behind a barrier of their own.  They write shared memory
+// first: the caller has no other use of sh / s_settled in flight.
 
 // window box, contract.  The box and the `behind` flag from the eight corners of the mesh's box, by the whole first wave (lane l
 // takes corner l & 7: corner_box_settles votes and reduces across the wave); the vertex pass only where the corners do not settle them.
-__device__ __forceinline__ void box_from_corners(const FusedJob& job, int* s_box, int* s_behind, int* s_settled)
+__device__ __forceinline__ void box_from_corners(const FusedJob& job, MeshBoxShared& sh, int* s_settled)
 {
     const int tid = threadIdx.x;
     const ObjParams& prm = *job.prm;
-    if (tid < 4) s_box[tid] = (tid < 2) ? INT32_MAX : -1;
-    if (tid == 0) *s_behind = 0;
+    box_reset(sh);
     __syncthreads();
     if (tid < 64 && prm.n_clusters > 0) {
         const int k = tid & 7;
@@ -306,7 +275,7 @@ __device__ __forceinline__ void box_from_corners(const FusedJob& job, int* s_box
         const bool settled = corner_box_settles(vc, job.P, job.fx, job.fy, job.cx, job.cy, job.tw, job.th, box);
         if (tid == 0) {
             *s_settled = settled ? 1 : 0;
-            if (settled) { s_box[0] = box[0]; s_box[1] = box[1]; s_box[2] = box[2]; s_box[3] = box[3]; }
+            if (settled) { sh.box[0] = box[0]; sh.box[1] = box[1]; sh.box[2] = box[2]; sh.box[3] = box[3]; }
         }
     } else if (tid == 0) {
         *s_settled = 1;   // (no mesh: the empty box)
@@ -314,20 +283,18 @@ __device__ __forceinline__ void box_from_corners(const FusedJob& job, int* s_box
     __syncthreads();
     if (!*s_settled) {
         auto project = [&](const float* v, float& sx, float& sy, float& z) { project_vertex(v, job.P, job.fx, job.fy, job.cx, job.cy, sx, sy, z); };
-        project_mesh<kFusedThreads, 4>(prm.verts, prm.n_verts, false, nullptr, job.tw, job.th, s_box, s_behind, project);
+        project_mesh<kFusedThreads, 4>(prm.verts, prm.n_verts, false, nullptr, job.tw, job.th, sh.box, &sh.behind, project);
         __syncthreads();
     }
 }
 
 // window box, GL.  vertices -> screen and the pixel box of everything that can be drawn (raster.h), four vertices per thread fetched
 // together; the projected vertices stay in the window's cache when they fit it.
-__device__ __forceinline__ void box_from_vertices(const FusedJob& job, const GlWindow& win, int* s_box, int* s_behind)
+__device__ __forceinline__ void box_from_vertices(const FusedJob& job, const GlWindow& win, MeshBoxShared& sh)
 {
-    const int tid = threadIdx.x;
-    if (tid < 4) s_box[tid] = (tid < 2) ? INT32_MAX : -1;
-    if (tid == 0) *s_behind = 0;
+    box_reset(sh);
     __syncthreads();
-    project_mesh<kFusedThreads, 4>(job.prm->verts, job.prm->n_verts, win.cached, win.s_v, job.tw, job.th, s_box, s_behind, GlProject{job});
+    project_mesh<kFusedThreads, 4>(job.prm->verts, job.prm->n_verts, win.cached, win.s_v, job.tw, job.th, sh.box, &sh.behind, GlProject{job});
     __syncthreads();
 }
 
@@ -337,34 +304,29 @@ __device__ __forceinline__ void box_from_vertices(const FusedJob& job, const GlW
 // merged in memory and the workgroup that arrives last scores the band: R is the smallest divisor of `parts` whose bands
 // fit the LDS in one piece (1 for most objects: set-up and walk are divided by `parts`, nothing is done twice but the
 // projection).  This is a pure function of its arguments, the same in every workgroup of the alternative but for `part`: every
-// workgroup sees the same box and decides alike.  Reads s_box behind the box stage's barrier.
+// workgroup sees the same box and decides alike.  `all`: box_read behind the box stage's barrier.
 struct BandSplit {
-    int R, G, band, grp;        // this workgroup: band `band` of R, triangle group `grp` of G
-    int i0, i1, j0, j1, win_w;  // the band's columns and rows (nothing to draw: see drawable)
-    __device__ __forceinline__ bool drawable() const { return win_w > 0 && j1 >= j0 && i0 >= 0 && j0 >= 0; }
+    int R, G, band, grp;   // this workgroup: band `band` of R, triangle group `grp` of G
+    MeshBox box;           // the band's columns and rows (nothing to draw: not drawable())
 };
-__device__ __forceinline__ BandSplit band_split(int parts, int split_tris, int part, const int* box, int tw, int th, int win_cap)
+__device__ __forceinline__ BandSplit band_split(int parts, int split_tris, int part, const MeshBox& all, int win_cap)
 {
     BandSplit b;
-    b.i0 = min(box[0], tw - 1);
-    b.i1 = box[2];
-    b.j0 = min(box[1], th - 1);
-    b.j1 = box[3];
+    b.box = all;
     b.R = parts;
-    if (split_tris && parts > 1 && b.i1 >= b.i0 && b.j1 >= b.j0 && b.i0 >= 0 && b.j0 >= 0) {
-        const long long w_all = b.i1 - b.i0 + 1, rows_all = b.j1 - b.j0 + 1;
+    if (split_tris && parts > 1 && all.drawable()) {
+        const long long w_all = all.width(), rows_all = all.j1 - all.j0 + 1;
         for (b.R = 1; b.R < parts; ++b.R)
             if (parts % b.R == 0 && ((rows_all + b.R - 1) / b.R) * w_all <= (long long)win_cap) break;
     }
     b.G = parts / b.R;
     b.band = part / b.G;
     b.grp = part % b.G;
-    if (b.j1 >= b.j0 && b.R > 1) {
-        const int j0 = b.j0, rows_all = b.j1 - j0 + 1;
-        b.j0 = j0 + (int)((long long)rows_all * b.band / b.R);
-        b.j1 = j0 + (int)((long long)rows_all * (b.band + 1) / b.R) - 1;
+    if (all.j1 >= all.j0 && b.R > 1) {
+        const int rows_all = all.j1 - all.j0 + 1;
+        b.box.j0 = all.j0 + (int)((long long)rows_all * b.band / b.R);
+        b.box.j1 = all.j0 + (int)((long long)rows_all * (b.band + 1) / b.R) - 1;
     }
-    b.win_w = b.i1 - b.i0 + 1;
     return b;
 }
 
@@ -638,8 +600,7 @@ __global__ __launch_bounds__(kFusedThreads) void outlier_fused_kernel(EngineArra
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ long long s_hi[kFusedThreads / 64], s_lo[kFusedThreads / 64];
     __shared__ int s_cnt[kFusedThreads / 64];
-    __shared__ int s_box[4];
-    __shared__ int s_behind;
+    __shared__ MeshBoxShared s_mb;
     __shared__ int s_last;
     __shared__ int s_settled;
     FusedJob job;
@@ -649,23 +610,22 @@ __global__ __launch_bounds__(kFusedThreads) void outlier_fused_kernel(EngineArra
     if (threadIdx.x < 8 && job.bx < 4) job.st->dbg[job.bx * 8 + threadIdx.x] = 0;
 #endif
     const auto win = open_window<GL>(smem, vcache_cap, job);
-    if constexpr (GL) box_from_vertices(job, win, s_box, &s_behind);
-    else box_from_corners(job, s_box, &s_behind, &s_settled);
+    if constexpr (GL) box_from_vertices(job, win, s_mb);
+    else box_from_corners(job, s_mb, &s_settled);
     UTICK(0);
-    const BandSplit bs = band_split(parts, GL ? 0 : split_tris, job.part, s_box, job.tw, job.th, win_cap);
+    const BandSplit bs = band_split(parts, GL ? 0 : split_tris, job.part, box_read(s_mb, job.tw, job.th), win_cap);
     const FeatureList ft = pending_features(a, job);
     LikelihoodSum err;
     int cnt = 0;
-    if (bs.drawable()) {
-        const int rows = max(1, win_cap / bs.win_w);   // (win_cap >= the target's width: a strip holds at least one row)
-        for (int js = bs.j0; js <= bs.j1; js += rows) {
-            const int je = min(bs.j1, js + rows - 1);
-            const Strip s = {bs.i0, bs.i1, js, je, bs.win_w, bs.win_w * (je - js + 1)};
-            win.clear(s.npx);
+    if (bs.box.drawable()) {
+        const int rows = strip_rows(win_cap, bs.box.width());   // (win_cap >= the target's width: a strip holds at least one row)
+        for (int js = bs.box.j0; js <= bs.box.j1; js += rows) {
+            const Strip s = strip_from(bs.box, js, rows);
+            win.clear(s.npx, kFusedThreads);
             __syncthreads();
             UTICK(1);
             if constexpr (GL) draw_triangles_gl(job, win, s);
-            else draw_clusters(job, win, s, bs.G, bs.grp, s_behind);
+            else draw_clusters(job, win, s, bs.G, bs.grp, s_mb.behind);
             __syncthreads();
             UTICK(2);
             if constexpr (!GL)
@@ -676,8 +636,8 @@ __global__ __launch_bounds__(kFusedThreads) void outlier_fused_kernel(EngineArra
             UTICK(3);
 #ifdef ROFT_FUSED_PROFILE
             if (threadIdx.x == 0 && job.bx < 4) job.st->dbg[job.bx * 8 + 4] += 1;
-            if (threadIdx.x == 0 && job.bx < 4) job.st->dbg[job.bx * 8 + 5] = (long long)bs.win_w * 100;
-            if (threadIdx.x == 0 && job.bx < 4) job.st->dbg[job.bx * 8 + 6] = (long long)(bs.j1 - bs.j0 + 1) * 100;
+            if (threadIdx.x == 0 && job.bx < 4) job.st->dbg[job.bx * 8 + 5] = (long long)bs.box.width() * 100;
+            if (threadIdx.x == 0 && job.bx < 4) job.st->dbg[job.bx * 8 + 6] = (long long)(bs.box.j1 - bs.box.j0 + 1) * 100;
 #endif
         }
     }

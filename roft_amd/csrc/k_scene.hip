@@ -5,11 +5,11 @@
 // renderer they call, tools/object_renderer/src/renderer.cpp (the mesh at every estimated pose over the grayed camera frame).
 //
 // Two passes over a visibility buffer of 64-bit keys, one buffer per frame of the call (scene.h states the contract):
-//   scene_visibility_kernel   one workgroup per (frame, instance, part).  It projects the instance's vertices (kept in LDS
-//       when they fit), takes their pixel bounding box as the instance's window, and walks the window in strips of at most
-//       win_cap pixels: a strip is a window of keys in LDS, every thread draws triangles into it with raster_projected and an
-//       LDS 64-bit min, and the keys that were drawn are merged into the frame's buffer in memory with a 64-bit atomic min
-//       (global_atomic_umin_x2, a vector instruction).  The `parts` workgroups of an instance deal the strips out in turn.
+//   scene_visibility_kernel   one workgroup per (frame, instance, part).  It draws the instance by raster.h's draw contract into
+//       a window of KEYS in LDS (an LDS 64-bit min; draw_triangles hands the store the triangle's index), in strips of at most
+//       win_cap pixels -- whole rows while a row fits, else a row is cut into column runs as well --, and merges the keys that were
+//       drawn into the frame's buffer in memory with a 64-bit atomic min (global_atomic_umin_x2, a vector instruction).  The
+//       `parts` workgroups of an instance deal the strips out in turn.
 //   scene_resolve_kernel      streams the keys once, four pixels per thread, and writes the outputs that were asked for:
 //       16-byte stores for the maps, three dwords of RGB.  A covered pixel is shaded from its key: the winning triangle's
 //       corners are transformed again with the float pose the visibility pass left in the pose table.
@@ -34,62 +34,49 @@ __device__ __forceinline__ void eye_vertex(const float* v, const ScenePose& P, f
 __global__ __launch_bounds__(kSceneThreads) void scene_visibility_kernel(SceneArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    __shared__ int s_box[4];
-    __shared__ int s_behind;
+    __shared__ MeshBoxShared s_mb;
     const int tid = threadIdx.x;
     const int part = (int)(blockIdx.x % (unsigned)a.parts), fi = (int)(blockIdx.x / (unsigned)a.parts);   // fi = frame * n_instances + instance
     const int inst = fi % a.n_instances, frame = fi / a.n_instances;
     if (a.valid && !a.valid[fi]) return;
     const double* pose = a.poses + (size_t)fi * 7;
-    bool finite = true;
-    for (int i = 0; i < 7; ++i) finite = finite && (fabs(pose[i]) < INFINITY);   // (uniform over the workgroup)
-    if (!finite) return;   // draws nothing; its triangles would fail raster_projected's own tests one by one
+    if (!pose_is_finite(pose)) return;   // (uniform over the workgroup) draws nothing
     const RenderPose P = make_pose(pose, pose + 3);
     if (part == 0 && tid == 0) {
         ScenePose& o = a.pose_table[fi];
         for (int i = 0; i < 9; ++i) o.R[i] = P.R[i];
         for (int i = 0; i < 3; ++i) o.t[i] = P.t[i];
     }
-    const SceneMesh m = a.meshes[a.mesh_index[inst]];
-    const int nv = m.n_verts, nt = m.n_tris, W = a.W, H = a.H;
-    const bool cached = nv <= a.vcache_cap;
+    const MeshView m = a.meshes[a.mesh_index[inst]];
+    const int W = a.W, H = a.H;
+    const bool cached = m.n_verts <= a.vcache_cap;
     float* s_v = reinterpret_cast<float*>(smem);
     uint64_t* s_k = reinterpret_cast<uint64_t*>(smem + vertex_cache_bytes(a.vcache_cap));
-    if (tid < 4) s_box[tid] = (tid < 2) ? INT32_MAX : -1;
-    if (tid == 0) s_behind = 0;
+    box_reset(s_mb);
     __syncthreads();
-    // vertices -> screen and the pixel box of everything that can be drawn (raster.h)
     auto project = [&](const float* v, float& sx, float& sy, float& z) { project_vertex(v, P, a.fx, a.fy, a.cx, a.cy, sx, sy, z); };
-    project_mesh<kSceneThreads, 1>(m.verts, nv, cached, s_v, W, H, s_box, &s_behind, project);
+    project_mesh<kSceneThreads, 1>(m.verts, m.n_verts, cached, s_v, W, H, s_mb.box, &s_mb.behind, project);
     __syncthreads();
-    const int i0 = min(s_box[0], W - 1), i1 = s_box[2], j0 = min(s_box[1], H - 1), j1 = s_box[3];
-    if (i1 < i0 || j1 < j0 || i0 < 0 || j0 < 0) return;   // nothing on the screen
+    const MeshBox box = box_read(s_mb, W, H);
+    if (!box.drawable()) return;   // nothing on the screen
     // strips of the window: whole rows while a row fits the LDS window, else a row is cut into column runs as well
-    const int win_w = i1 - i0 + 1, cw = min(win_w, a.win_cap), rows = max(1, a.win_cap / cw);
-    const int n_cols = (win_w + cw - 1) / cw, n_rows = (j1 - j0 + rows) / rows;
-    const uint8_t* const flips = cull_table(m.flip, s_behind);
+    const int win_w = box.width(), cw = min(win_w, a.win_cap), rows = strip_rows(a.win_cap, cw);
+    const int n_cols = (win_w + cw - 1) / cw, n_rows = (box.j1 - box.j0 + rows) / rows;
+    const uint8_t* const flips = cull_table(m.flip, s_mb.behind);
     ROFT_LDS uint64_t* const zk = (ROFT_LDS uint64_t*)pin_lds(reinterpret_cast<uint32_t*>(s_k));
     uint64_t* const keys = a.keys + (size_t)frame * W * H;
     for (int strip = part; strip < n_cols * n_rows; strip += a.parts) {
-        const int is = i0 + (strip % n_cols) * cw, ie = min(i1, is + cw - 1);
-        const int js = j0 + (strip / n_cols) * rows, je = min(j1, js + rows - 1);
-        const int sw = ie - is + 1, npx = sw * (je - js + 1);   // <= win_cap
+        const Strip st = strip_at(box, cw, rows, n_cols, strip);   // (st.npx <= win_cap)
+        const int is = st.i0, js = st.js, je = st.je, sw = st.win_w, npx = st.npx;
         for (int i = tid; i < npx; i += kSceneThreads) s_k[i] = kSceneKeyEmpty;
         __syncthreads();
-        for (int t = tid; t < nt; t += kSceneThreads) {
-            const int32_t* tri = m.tris + (size_t)3 * t;
-            const int v0 = tri[0], v1 = tri[1], v2 = tri[2];
-            const int cull = cull_code(flips, t);
-            float x0, y0, z0, x1, y1, z1, x2, y2, z2;
-            fetch_triangle(s_v, cached, m.verts, v0, v1, v2, project, x0, y0, z0, x1, y1, z1, x2, y2, z2);
+        draw_triangles<kSceneThreads>(m, s_v, cached, flips, project, W, H, js, je, [zk, is, js, sw, inst](int i, int j, float z, int t) {
+            const unsigned ci = (unsigned)(i - is);   // (the strip's column run)
             const uint64_t low = ((uint64_t)(uint32_t)inst << 24) | (uint32_t)t;
-            raster_projected(x0, y0, z0, x1, y1, z1, x2, y2, z2, W, H, js, je, cull, [zk, is, js, sw, low](int i, int j, float z) {
-                const unsigned ci = (unsigned)(i - is);
-                if (ci < (unsigned)sw)
-                    (void)__hip_atomic_fetch_min(zk + ((j - js) * sw + (int)ci), ((uint64_t)__float_as_uint(z) << 32) | low, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_WORKGROUP);
-            });
-        }
+            if (ci < (unsigned)sw)
+                (void)__hip_atomic_fetch_min(zk + ((j - js) * sw + (int)ci), ((uint64_t)__float_as_uint(z) << 32) | low, __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_WORKGROUP);
+        });
         __syncthreads();
         // the strip's drawn keys -> the frame's buffer (other instances and other strips of this one merge into the same buffer)
         for (int i = tid; i < npx; i += kSceneThreads) {
@@ -104,7 +91,7 @@ __global__ __launch_bounds__(kSceneThreads) void scene_visibility_kernel(SceneAr
 // shade of the key's triangle: scene.h, operation by operation
 __device__ __forceinline__ float scene_shade(const SceneArgs& a, int frame, int inst, int tri_id)
 {
-    const SceneMesh& m = a.meshes[a.mesh_index[inst]];
+    const MeshView& m = a.meshes[a.mesh_index[inst]];
     const ScenePose& P = a.pose_table[(size_t)frame * a.n_instances + inst];
     const int32_t* tri = m.tris + (size_t)3 * tri_id;
     float p[3][3];

@@ -2,18 +2,17 @@
 // bit planes a delivered mask would have been ingested into (include/roft_engine.h, section 3e).
 //
 // The mask is M(p) = roft_render_depth(mesh, pose_x, pose_q, cam, 1)(p) > 0 ? 255 : 0: the render contract at full resolution
-// (raster.h: make_pose / project_vertex / raster_projected unchanged, the back-face rule for closed meshes as k_quality.hip and
-// outlier_fused_kernel apply it), of which only "some triangle covers the pixel with z > 0" is kept -- one bit.  So the store of
-// the rasteriser is an LDS atomicOr, the result is an order-free OR, and no band count, strip height or triangle order changes it.
+// (raster.h's draw contract), of which only "some triangle covers the pixel with z > 0" is kept -- one bit.  So the store of the
+// rasteriser is an LDS atomicOr, the result is an order-free OR, and no band count, strip height or triangle order changes it.
 //
 // One workgroup = one band of image rows of one (delivering frame, enrolled object) pair; ONE launch covers every pair of a batch
 // (grid z: the batch's delivering frames, four bits each in frames_packed; a pair that is not enrolled, or whose mask arrived
-// another way, leaves at once).  The workgroup projects the vertices once -- into LDS where the mesh fits, else again per triangle --
-// and takes the row box of everything that can be drawn from them; it clears a bit window of its rows in LDS, walks the triangles
-// over [j_lo, j_hi] = band x box (a band the box misses walks none), and flushes the window: EVERY word of BOTH planes of slot
-// slot0 + t is written, zeros included (the slot holds stale words; a silhouette has no pixel of value 1: nz == obj, new_ones
-// stays 0), consecutive threads consecutive words, and the population count goes to mrec[t + 1][obj].new_count behind a wave
-// reduction, as label_ingest_kernel does.  A band taller than the window is drawn in strips.
+// another way, leaves at once).  What the kernel does with raster.h's draw contract: its window holds BITS, wpr words per image
+// row, and it uses only the ROWS of the box (project_mesh's kRowsOnly, read as the pass left them: a box nothing widened meets no
+// band), drawing over [j_lo, j_hi] = band x box.  Its triangle loop is draw_triangles' spelled out (measured: docs/notebook.md).
+// The flush writes EVERY word of BOTH planes of slot slot0 + t, zeros included (the slot holds stale words; a silhouette has no
+// pixel of value 1: nz == obj, new_ones stays 0), consecutive threads consecutive words, and the population count goes to
+// mrec[t + 1][obj].new_count behind a wave reduction, as label_ingest_kernel does.
 // Built with -ffp-contract=off like every user of raster.h.
 //
 // THE DEPTH GATE (kGate; section 3e, "gated against the depth of the pose's own frame").  With R(p) the rendered depth -- the
@@ -58,8 +57,7 @@ template <bool kZ, bool kGate>
 __global__ __launch_bounds__(kSilhouetteThreads) void pose_silhouette_kernel(SilhouetteArgs sa)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    __shared__ int s_box[4];   // (of which the rows are used: the first and last image row anything can be drawn in)
-    __shared__ int s_behind;
+    __shared__ MeshBoxShared s_mb;   // (of which the rows are used: the first and last image row anything can be drawn in)
     const int obj = blockIdx.y, tid = threadIdx.x;
     const int t = (int)((sa.frames_packed >> (4 * blockIdx.z)) & 15u);
     const FrameCtrl& c = sa.ctrl[(size_t)t * sa.n_obj + obj];
@@ -72,19 +70,18 @@ __global__ __launch_bounds__(kSilhouetteThreads) void pose_silhouette_kernel(Sil
     const bool cached = nv <= sa.vcache_cap;
     float* s_v = reinterpret_cast<float*>(smem);
     uint32_t* s_win = reinterpret_cast<uint32_t*>(smem + vertex_cache_bytes(sa.vcache_cap));
-    if (tid < 4) s_box[tid] = (tid < 2) ? INT32_MAX : -1;
-    if (tid == 0) s_behind = 0;
+    box_reset(s_mb);
     __syncthreads();
 
     // vertices -> screen and the rows of everything that can be drawn (raster.h; rows only: the columns, which nothing here reads,
     // were measured at 1 - 2 % of the launch, docs/notebook.md)
     auto project = [&](const float* v, float& sx, float& sy, float& z) { project_vertex(v, P, fx, fy, cx, cy, sx, sy, z); };
-    project_mesh<kSilhouetteThreads, 1, true>(prm.verts, nv, cached, s_v, W, H, s_box, &s_behind, project);
+    project_mesh<kSilhouetteThreads, 1, true>(prm.verts, nv, cached, s_v, W, H, s_mb.box, &s_mb.behind, project);
     __syncthreads();
-    const int box0 = s_box[1], box1 = s_box[3];
+    const int box0 = s_mb.box[1], box1 = s_mb.box[3];
     const bool to_z = kZ && c.label > 0;   // (workgroup-uniform)
     unsigned long long* const zb = to_z ? sa.zbuf + ((size_t)blockIdx.z * sa.n_zscenes + (c.label - 1)) * ((size_t)W * H) : nullptr;
-    const uint8_t* const flips = cull_table(prm.tri_flip, s_behind);
+    const uint8_t* const flips = cull_table(prm.tri_flip, s_mb.behind);
 
     // the band's rows, strip by strip
     const int bands = (int)gridDim.x, band = (int)blockIdx.x;
@@ -121,6 +118,7 @@ __global__ __launch_bounds__(kSilhouetteThreads) void pose_silhouette_kernel(Sil
                     if (tb > 0.0f && D > hi) (void)__hip_atomic_fetch_or(win + (2 * win_words + wi), bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
             };
+            // (raster.h's draw_triangles, kept inline: through the shared loop the launch took 142.0 us for 138.0, docs/notebook.md)
             for (int k = tid; k < nt; k += kSilhouetteThreads) {
                 const int32_t* tri = prm.tris + (size_t)3 * k;
                 const int v0 = tri[0], v1 = tri[1], v2 = tri[2];

@@ -1,18 +1,13 @@
 // k_vsd.hip -- BOP's Visible Surface Discrepancy of pose pairs against depth images (gfx950; include/roft_engine.h, section 3i).
 //
-// One workgroup per (pose pair, part).  It projects the mesh at both poses for their pixel boxes, takes the boxes' union -- outside
-// it both visibility masks are empty -- and cuts the union into strips of rows that fit two LDS depth windows.  Per strip it draws the
-// estimated pose into one window and the reference pose into the other exactly as quality_kernel draws its one: raster_projected of
-// raster.h, the back-face rule for closed meshes, atomicMin on the float bits -- so the windows hold, bit for bit, what
-// roft_render_depth(.., divider 1) returns under the strip.  The rendered depths never leave the CU.  The projected vertices are kept
-// in ONE LDS cache where the mesh fits: a strip draws first the pose the cache holds, then refills it for the other one (one vertex
-// pass per strip), else every triangle projects its own corners.  Then the strip's pixels are walked row by row (consecutive lanes,
-// consecutive pixels: the reads of the depth image are coalesced), only where something was drawn: distance images, the two masks
-// and the 4 + n_taus counts in registers, reduced wave -> workgroup -> one integer atomic add per count into the pair's row.
-// vsd_finish_kernel divides.  Every figure is a sum of integers: no row depends on strips, parts, threads or the launch.
-// Built with -ffp-contract=off like every user of raster.h; the distance images are specified operation by operation in double.
-#include <algorithm>
-
+// One workgroup per (pose pair, part).  It projects the mesh at both poses, takes the union of their pixel boxes -- outside it both
+// visibility masks are empty -- and per strip of the union draws the estimate into one LDS DepthWindow and the reference into another
+// by raster.h's draw contract: the windows hold, bit for bit, what roft_render_depth(.., divider 1) returns, and never leave the CU.
+// ONE LDS cache holds the projected vertices where the mesh fits: a strip draws first the pose the cache holds, then refills it for
+// the other (one vertex pass per strip).  Then the strip's pixels are walked row by row (coalesced reads of the depth image), only
+// where something was drawn: distance images, the two masks and the 4 + n_taus counts in registers, reduced wave -> workgroup -> one
+// integer atomic add per count into the pair's row.  vsd_finish_kernel divides.  Every figure is a sum of integers: no row depends on
+// strips, parts, threads or the launch.  Built with -ffp-contract=off; the distance images are specified in double.
 #include "raster.h"
 #include "vsd.h"
 
@@ -38,60 +33,48 @@ __global__ __launch_bounds__(kVsdThreads) void vsd_kernel(VsdArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ int s_cnt[kVsdThreads / 64][kVsdCounts];
-    __shared__ int s_box[2][4];
-    __shared__ int s_behind[2];
+    __shared__ MeshBoxShared s_mb[2];   // 0: the estimate, 1: the reference
     const int tid = threadIdx.x;
     const int part = (int)(blockIdx.x % (unsigned)a.parts), pair = (int)(blockIdx.x / (unsigned)a.parts);
-    const int W = a.W, H = a.H, nv = a.mesh.n_verts, nt = a.mesh.n_tris;
+    const MeshView& mesh = a.mesh;
+    const int W = a.W, H = a.H, nv = mesh.n_verts;
     const bool cached = nv <= a.vcache_cap;
     float* s_v = reinterpret_cast<float*>(smem);
-    uint32_t* const s_ze = reinterpret_cast<uint32_t*>(smem + vertex_cache_bytes(a.vcache_cap));   // the estimate's window
-    uint32_t* const s_zg = s_ze + a.win_alloc;                                                     // the reference's
+    const DepthWindow win_e{reinterpret_cast<uint32_t*>(smem + vertex_cache_bytes(a.vcache_cap))}, win_g{win_e.z + a.win_alloc};
     const double* const pose_e = a.est + (size_t)pair * 7;
     const double* const pose_g = a.ref + (size_t)pair * 7;
-    bool finite_e = true, finite_g = true;   // (uniform over the workgroup) a pose with a non-finite component draws nothing, as in the scene renderer
-    for (int i = 0; i < 7; ++i) {
-        finite_e = finite_e && (fabs(pose_e[i]) < INFINITY);
-        finite_g = finite_g && (fabs(pose_g[i]) < INFINITY);
-    }
+    const bool finite_e = pose_is_finite(pose_e), finite_g = pose_is_finite(pose_g);   // (uniform over the workgroup)
     const RenderPose Pe = make_pose(pose_e, pose_e + 3), Pg = make_pose(pose_g, pose_g + 3);   // (not used when not finite)
-    if (tid < 8) s_box[tid >> 2][tid & 3] = ((tid & 3) < 2) ? INT32_MAX : -1;
-    if (tid < 2) s_behind[tid] = 0;
+    box_reset(s_mb[0]);
+    box_reset(s_mb[1]);
     __syncthreads();
 
     // vertices -> screen: the pixel box of everything either pose can draw; the cache is left with the estimate's vertices
     auto project_e = [&](const float* v, float& sx, float& sy, float& z) { project_vertex(v, Pe, a.fx, a.fy, a.cx, a.cy, sx, sy, z); };
     auto project_g = [&](const float* v, float& sx, float& sy, float& z) { project_vertex(v, Pg, a.fx, a.fy, a.cx, a.cy, sx, sy, z); };
-    if (finite_g) project_mesh<kVsdThreads, 1>(a.mesh.verts, nv, false, s_v, W, H, s_box[1], &s_behind[1], project_g);
-    if (finite_e) project_mesh<kVsdThreads, 1>(a.mesh.verts, nv, cached, s_v, W, H, s_box[0], &s_behind[0], project_e);
+    if (finite_g) project_mesh<kVsdThreads, 1>(mesh.verts, nv, false, s_v, W, H, s_mb[1].box, &s_mb[1].behind, project_g);
+    if (finite_e) project_mesh<kVsdThreads, 1>(mesh.verts, nv, cached, s_v, W, H, s_mb[0].box, &s_mb[0].behind, project_e);
     __syncthreads();
     int holds = finite_e ? 0 : -1;   // the pose whose vertices the cache holds: 0 the estimate, 1 the reference
-    int i0 = INT32_MAX, j0 = INT32_MAX, i1 = -1, j1 = -1;
-    bool drawn_e, drawn_g;   // the pose can draw something on the target
-    {
-        const int bi0 = min(s_box[0][0], W - 1), bi1 = s_box[0][2], bj0 = min(s_box[0][1], H - 1), bj1 = s_box[0][3];
-        drawn_e = finite_e && bi1 >= bi0 && bj1 >= bj0 && bi0 >= 0 && bj0 >= 0;
-        if (drawn_e) { i0 = bi0; i1 = bi1; j0 = bj0; j1 = bj1; }
-    }
-    {
-        const int bi0 = min(s_box[1][0], W - 1), bi1 = s_box[1][2], bj0 = min(s_box[1][1], H - 1), bj1 = s_box[1][3];
-        drawn_g = finite_g && bi1 >= bi0 && bj1 >= bj0 && bi0 >= 0 && bj0 >= 0;
-        if (drawn_g) { i0 = min(i0, bi0); i1 = max(i1, bi1); j0 = min(j0, bj0); j1 = max(j1, bj1); }
-    }
-    const uint8_t* const flips_e = cull_table(a.mesh.flip, s_behind[0]);
-    const uint8_t* const flips_g = cull_table(a.mesh.flip, s_behind[1]);
+    const MeshBox box_e = box_read(s_mb[0], W, H), box_g = box_read(s_mb[1], W, H);
+    const bool drawn_e = finite_e && box_e.drawable(), drawn_g = finite_g && box_g.drawable();   // the pose can draw something on the target
+    MeshBox box = {INT32_MAX, INT32_MAX, -1, -1};   // the union
+    if (drawn_e) box = box_e;
+    if (drawn_g) box = MeshBox{min(box.i0, box_g.i0), min(box.j0, box_g.j0), max(box.i1, box_g.i1), max(box.j1, box_g.j1)};
+    const uint8_t* const flips_e = cull_table(mesh.flip, s_mb[0].behind);
+    const uint8_t* const flips_g = cull_table(mesh.flip, s_mb[1].behind);
 
     int cnt[kVsdCounts];
 #pragma unroll
     for (int k = 0; k < kVsdCounts; ++k) cnt[k] = 0;
 
     if (drawn_e || drawn_g) {
-        // (the launcher refuses targets wider than a window: a strip holds at least one row of any union)
-        const int win_w = i1 - i0 + 1, rows = max(1, a.win_cap / win_w), n_strips = (j1 - j0 + rows) / rows;
+        const int rows = strip_rows(a.win_cap, box.width()), n_strips = (box.j1 - box.j0 + rows) / rows;
         const float* depth = a.depth + (size_t)pair * a.depth_stride;
         for (int strip = part; strip < n_strips; strip += a.parts) {
-            const int js = j0 + strip * rows, je = min(j1, js + rows - 1), npx = win_w * (je - js + 1);
-            for (int i = tid; i < npx; i += kVsdThreads) { s_ze[i] = kDepthEmpty; s_zg[i] = kDepthEmpty; }
+            const Strip s = strip_from(box, box.j0 + strip * rows, rows);
+            win_e.clear(s.npx, kVsdThreads);
+            win_g.clear(s.npx, kVsdThreads);
             __syncthreads();
             const int first = (cached && holds == 1) ? 1 : 0;
             for (int pass = 0; pass < 2; ++pass) {
@@ -102,37 +85,25 @@ __global__ __launch_bounds__(kVsdThreads) void vsd_kernel(VsdArgs a)
                     __syncthreads();   // the other pose's triangles have read the cache
                     for (int v = tid; v < nv; v += kVsdThreads) {
                         float sx, sy, z;
-                        project_vertex(a.mesh.verts + (size_t)3 * v, Pw, a.fx, a.fy, a.cx, a.cy, sx, sy, z);
+                        project_vertex(mesh.verts + (size_t)3 * v, Pw, a.fx, a.fy, a.cx, a.cy, sx, sy, z);
                         s_v[3 * v] = sx; s_v[3 * v + 1] = sy; s_v[3 * v + 2] = z;
                     }
                     holds = w;
                     __syncthreads();
                 }
-                ROFT_LDS uint32_t* const zw = pin_lds(w ? s_zg : s_ze);
-                auto store = [zw, i0, js, win_w](int i, int j, float z) {
-                    (void)__hip_atomic_fetch_min(zw + ((j - js) * win_w + (i - i0)), __float_as_uint(z), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                };
                 auto project = [&](const float* v, float& sx, float& sy, float& z) { project_vertex(v, Pw, a.fx, a.fy, a.cx, a.cy, sx, sy, z); };
-                const uint8_t* const fl = w ? flips_g : flips_e;
-                for (int t = tid; t < nt; t += kVsdThreads) {
-                    const int32_t* tri = a.mesh.tris + (size_t)3 * t;
-                    const int v0 = tri[0], v1 = tri[1], v2 = tri[2];
-                    const int cull = cull_code(fl, t);
-                    float x0, y0, z0, x1, y1, z1, x2, y2, z2;
-                    fetch_triangle(s_v, cached, a.mesh.verts, v0, v1, v2, project, x0, y0, z0, x1, y1, z1, x2, y2, z2);
-                    raster_projected(x0, y0, z0, x1, y1, z1, x2, y2, z2, W, H, js, je, cull, store);
-                }
+                draw_triangles<kVsdThreads>(mesh, s_v, cached, w ? flips_g : flips_e, project, W, H, s.js, s.je, (w ? win_g : win_e).store(s));
             }
             __syncthreads();
             // the strip's pixels, row by row; a pixel neither pose drew is in neither mask
-            for (int idx = tid; idx < npx; idx += kVsdThreads) {
-                const uint32_t be = s_ze[idx], bg = s_zg[idx];
-                if (be == kDepthEmpty && bg == kDepthEmpty) continue;
-                const int jj = idx / win_w, i = i0 + (idx - jj * win_w), j = js + jj;
+            for (int idx = tid; idx < s.npx; idx += kVsdThreads) {
+                const bool has_e = win_e.covered(idx), has_g = win_g.covered(idx);
+                if (!has_e && !has_g) continue;
+                const int jj = idx / s.win_w, i = s.i0 + (idx - jj * s.win_w), j = s.js + jj;
                 const double ca = ((double)i - a.dcx) / a.dfx, cb = ((double)j - a.dcy) / a.dfy;   // once per pixel, for T, G and E
                 const double T = vsd_dist(ca, cb, depth[(size_t)j * W + i]);
-                const double G = bg == kDepthEmpty ? 0.0 : vsd_dist(ca, cb, __uint_as_float(bg));
-                const double E = be == kDepthEmpty ? 0.0 : vsd_dist(ca, cb, __uint_as_float(be));
+                const double G = has_g ? vsd_dist(ca, cb, win_g.depth(idx, i, j)) : 0.0;
+                const double E = has_e ? vsd_dist(ca, cb, win_e.depth(idx, i, j)) : 0.0;
                 const bool vg = G > 0.0 && vsd_visible(G, T, a.delta);
                 const bool ve = E > 0.0 && (vsd_visible(E, T, a.delta) || vg);
                 if (!(vg || ve)) continue;
@@ -152,18 +123,10 @@ __global__ __launch_bounds__(kVsdThreads) void vsd_kernel(VsdArgs a)
     }
 
     // wave -> workgroup -> the pair's row
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < kVsdCounts; ++k) cnt[k] += __shfl_down(cnt[k], off, 64);
-    }
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < kVsdCounts; ++k) s_cnt[tid >> 6][k] = cnt[k];
-    }
+    wave_sums_to_rows(cnt, s_cnt);
     __syncthreads();
     if (tid < kVsdCounts) {
-        int tot = 0;
-        for (int w = 0; w < kVsdThreads / 64; ++w) tot += s_cnt[w][tid];
+        const int tot = rows_total<kVsdThreads>(s_cnt, tid);
         if (tot) atomicAdd(&a.counts[(size_t)pair * kVsdCounts + tid], tot);
     }
 }
@@ -181,23 +144,6 @@ __global__ void vsd_finish_kernel(const int32_t* counts, int n, int n_taus, doub
         row[4 + k] = c[4 + k];
         errors[(size_t)f * n_taus + k] = n_union > 0 ? (double)(c[4 + k] + n_union - n_inter) / (double)n_union : 1.0;
     }
-}
-
-// LDS of a workgroup: the projected vertices where they leave room for two windows of 4 k pixels, and two windows of at most 16 k
-// pixels (an object of a tracked sequence covers a few tens of thousands of pixels at 640 x 480: a handful of strips).
-bool vsd_shape(int n_verts, int width, int window_pixels, int& vcache_cap, int& win_alloc, int& win_cap, size_t& lds)
-{
-    const size_t budget = kRasterLdsBudget, vbytes = vertex_cache_bytes(n_verts);
-    const bool cache = vbytes + 8 * (size_t)std::max(4096, width) <= budget;
-    vcache_cap = cache ? n_verts : 0;
-    const size_t room = (budget - (cache ? vbytes : 0)) / 8;   // pixels per window
-    if ((size_t)width > room) return false;                    // not even one row of the target
-    win_cap = (int)std::min<size_t>(room, (size_t)std::max(16384, width));
-    lds = (cache ? vbytes : 0) + 8 * (size_t)win_cap;
-    // (a smaller cap uses less of the same allocation: a strip of one row is at most `width` <= the allocation wide)
-    win_alloc = win_cap;
-    if (window_pixels > 0) win_cap = std::min(win_cap, window_pixels);
-    return true;
 }
 
 void launch_vsd(const VsdArgs& a, int n, size_t lds, hipStream_t s)

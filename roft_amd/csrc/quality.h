@@ -3,6 +3,7 @@
 // writes only its own records.
 #pragma once
 
+#include "raster_shape.h"
 #include "roft_device.h"
 
 namespace roft {
@@ -31,10 +32,7 @@ void launch_quality(const EngineArrays& a, QualityRaw* ring, int cap, unsigned f
 
 // false: the render target is wider than the LDS window can be (nothing is launched then)
 bool quality_fits(const EngineArrays& a);
-// The LDS of a workgroup that runs quality_body.h for meshes of up to max_verts vertices on a target tile_w wide: the vertex cache
-// where it leaves room for a window, the window's pixels, the bytes to ask for.  false as quality_fits.  window_pixels > 0 caps
-// win_cap (a strip still holds at least one row).  Shared with the pose hypotheses' launcher (hypotheses.h).
-bool quality_window_shape(int max_verts, int tile_w, int window_pixels, int& vcache_cap, int& win_cap, size_t& lds);
+// (The LDS of a workgroup that runs quality_body.h: quality_window_shape, raster_shape.h; shared with the pose hypotheses' launcher.)
 
 inline roft_quality_record quality_record(const QualityRaw& r)
 {

@@ -1,11 +1,9 @@
 // quality_body.h -- the body of a track-quality record (include/roft_engine.h, section 3d), between "project the mesh" and "the
-// record": ONE pose of one mesh against one object plane and one depth image, by one workgroup.  It projects the mesh and draws it
-// into an LDS depth window exactly as the outlier test does -- the vertices projected once into LDS where they fit, else per
-// triangle; raster_projected of raster.h, the back-face rule for closed meshes; strips when the window exceeds its LDS share -- so
-// the window holds, bit for bit, the tile roft_render_depth returns.  Then it walks the image pixels under the strip row by row
-// (consecutive threads, consecutive pixels: the plane words and the depth gathers are row-coalesced), reads the depth only where
-// mask and render meet, and adds the counts as integers and |e| as a LikelihoodSum: every figure is a sum of integers, so no record
-// depends on strips, threads or waves.
+// record": ONE pose of one mesh against one object plane and one depth image, by one workgroup.  It draws the mesh into an LDS
+// DepthWindow by raster.h's draw contract, so the window holds, bit for bit, the tile roft_render_depth returns.  Then it walks the
+// image pixels under the strip row by row (consecutive threads, consecutive pixels: the plane words and the depth gathers are
+// row-coalesced), reads the depth only where mask and render meet, and adds the counts as integers and |e| as a LikelihoodSum:
+// every figure is a sum of integers, so no record depends on strips, threads or waves.
 // Two kernels include it: quality_kernel (k_quality.hip: the engine's estimate of a frame) and hypotheses_kernel (k_hypotheses.hip:
 // n candidate poses against one frame, section 3j).  Both are built with -ffp-contract=off like every user of raster.h.
 #pragma once
@@ -20,10 +18,7 @@ constexpr int kQualityCounts = 6;   // n_mask, n_render, n_both, n_depth, n_fron
 struct QualityScene {
     const uint32_t* plane;   // the object plane M: wpr words per image row
     const float* depth;      // D, W floats per row
-    const float* verts;      // the mesh as ObjParams describes it (walk order and flip bits of a closed mesh)
-    const int32_t* tris;
-    const uint8_t* tri_flip;
-    int n_verts, n_tris;
+    MeshView mesh;           // as ObjParams describes it (walk order and flip bits of a closed mesh)
     int d, tw, th, W, wpr;   // divider, render target, image width, plane words per row
     float fx, fy, cx, cy;    // the camera over the divider, as the render contract rounds it
     float depth_tolerance;
@@ -47,64 +42,49 @@ __device__ __forceinline__ void quality_body(const QualityScene& sc, const Rende
 {
     __shared__ long long s_hi[kThreads / 64], s_lo[kThreads / 64];
     __shared__ int s_cnt[kThreads / 64][kQualityCounts];
-    __shared__ int s_box[4];
-    __shared__ int s_behind;
+    __shared__ MeshBoxShared s_mb;
     const int tid = threadIdx.x;
     const float* depth = sc.depth;
     const uint32_t* plane = sc.plane;
+    const MeshView& mesh = sc.mesh;
     const int d = sc.d, tw = sc.tw, th = sc.th, W = sc.W, wpr = sc.wpr;
     const float fx = sc.fx, fy = sc.fy, cx = sc.cx, cy = sc.cy;
-    const int nv = sc.n_verts, nt = sc.n_tris;
-    const bool cached = nv <= sc.vcache_cap;
+    const bool cached = mesh.n_verts <= sc.vcache_cap;
     float* s_v = reinterpret_cast<float*>(smem);
-    uint32_t* s_z = reinterpret_cast<uint32_t*>(smem + vertex_cache_bytes(sc.vcache_cap));
-    if (tid < 4) s_box[tid] = (tid < 2) ? INT32_MAX : -1;
-    if (tid == 0) s_behind = 0;
+    const DepthWindow win{reinterpret_cast<uint32_t*>(smem + vertex_cache_bytes(sc.vcache_cap))};
+    box_reset(s_mb);
     __syncthreads();
     int n_render = 0, n_both = 0, n_depth = 0, n_front = 0, n_behind = 0;
 
-    // vertices -> screen and the pixel box of everything that can be drawn (raster.h)
     auto project = [&](const float* v, float& sx, float& sy, float& z) { project_vertex(v, P, fx, fy, cx, cy, sx, sy, z); };
-    project_mesh<kThreads, 1>(sc.verts, nv, cached, s_v, tw, th, s_box, &s_behind, project);
+    project_mesh<kThreads, 1>(mesh.verts, mesh.n_verts, cached, s_v, tw, th, s_mb.box, &s_mb.behind, project);
     __syncthreads();
-    const int i0 = min(s_box[0], tw - 1), i1 = s_box[2], j0 = min(s_box[1], th - 1), j1 = s_box[3];
-    const int win_w = i1 - i0 + 1;
+    const MeshBox box = box_read(s_mb, tw, th);
     LikelihoodSum err;
-    if (win_w > 0 && win_w <= sc.win_cap && j1 >= j0 && i0 >= 0 && j0 >= 0) {
-        const int rows = max(1, sc.win_cap / win_w);
-        const uint8_t* const flips = cull_table(sc.tri_flip, s_behind);
-        for (int js = j0; js <= j1; js += rows) {
-            const int je = min(j1, js + rows - 1), npx = win_w * (je - js + 1);
-            for (int i = tid; i < npx; i += kThreads) s_z[i] = kDepthEmpty;
+    if (box.drawable() && box.width() <= sc.win_cap) {
+        const int rows = strip_rows(sc.win_cap, box.width());
+        const uint8_t* const flips = cull_table(mesh.flip, s_mb.behind);
+        for (int js = box.j0; js <= box.j1; js += rows) {
+            const Strip s = strip_from(box, js, rows);
+            win.clear(s.npx, kThreads);
             __syncthreads();
-            ROFT_LDS uint32_t* const zw = pin_lds(s_z);
-            auto store = [zw, i0, js, win_w](int i, int j, float z) {
-                (void)__hip_atomic_fetch_min(zw + ((j - js) * win_w + (i - i0)), __float_as_uint(z), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            };
-            for (int t = tid; t < nt; t += kThreads) {
-                const int32_t* tri = sc.tris + (size_t)3 * t;
-                const int v0 = tri[0], v1 = tri[1], v2 = tri[2];
-                const int cull = cull_code(flips, t);
-                float x0, y0, z0, x1, y1, z1, x2, y2, z2;
-                fetch_triangle(s_v, cached, sc.verts, v0, v1, v2, project, x0, y0, z0, x1, y1, z1, x2, y2, z2);
-                raster_projected(x0, y0, z0, x1, y1, z1, x2, y2, z2, tw, th, js, je, cull, store);
-            }
+            draw_triangles<kThreads>(mesh, s_v, cached, flips, project, tw, th, s.js, s.je, win.store(s));
             __syncthreads();
             // the image pixels under the strip: (u, v) with u / d in [i0, i1], v / d in [js, je] -- all inside the image, since
             // tw d <= W and th d <= H
-            const int rw = win_w * d, n_img = rw * (je - js + 1) * d;
+            const int rw = s.win_w * d, n_img = rw * (s.je - s.js + 1) * d;
             for (int idx = tid; idx < n_img; idx += kThreads) {
                 const int vv = idx / rw, uu = idx - vv * rw;
-                const uint32_t b = s_z[(vv / d) * win_w + uu / d];
-                if (b == kDepthEmpty) continue;
+                const int px = (vv / d) * s.win_w + uu / d;
+                if (!win.covered(px)) continue;
                 n_render += 1;
-                const int u = i0 * d + uu, v = js * d + vv;
+                const int u = s.i0 * d + uu, v = s.js * d + vv;
                 if (!((plane[(size_t)v * wpr + (u >> 5)] >> (u & 31)) & 1u)) continue;
                 n_both += 1;
                 const float D = depth[(size_t)v * W + u];
                 if (!(D > 0.0f && (double)D < sc.depth_maximum)) continue;   // (NaN fails both)
                 n_depth += 1;
-                const float e = D - __uint_as_float(b);
+                const float e = D - win.depth(px, u / d, v / d);
                 if (e < -sc.depth_tolerance) n_front += 1;
                 if (e > sc.depth_tolerance) n_behind += 1;
                 err.add(fabsf(e));
@@ -113,6 +93,7 @@ __device__ __forceinline__ void quality_body(const QualityScene& sc, const Rende
         }
     }
     int cnt[kQualityCounts] = {n_mask, n_render, n_both, n_depth, n_front, n_behind};
+    // (raster.h's wave_sums_to_rows / rows_total, kept fused with the LikelihoodSum's reduction: one shuffle loop, one serial add)
     for (int off = 32; off > 0; off >>= 1) {
         err.hi += __shfl_down(err.hi, off, 64);
         err.lo += __shfl_down(err.lo, off, 64);

@@ -1,20 +1,43 @@
-// raster.h -- the render contract's rasteriser (oracle/ro_render.c, operation by operation): pose -> float rotation, vertex
-// projection, scan conversion of one projected triangle -- and the mesh walk around it: the vertex pass (project_mesh), the corner
-// fetch (fetch_triangle), the back-face rule's guard (cull_table / cull_code) and the LDS arithmetic of a launcher.  Shared by the
-// outlier test (k_render.hip), track quality (k_quality.hip), masks from poses (k_silhouette.hip) and the scene renderer
-// (k_scene.hip); every translation unit that includes it is built with -ffp-contract=off.  The numerics of the outlier test's other
-// render mode, ROFT_RENDER_GL, stand next to it in raster_gl.h.
+// raster.h -- the render contract's rasteriser (oracle/ro_render.c, operation by operation) and the stage that draws a mesh with it
+// into an LDS window, in pieces.  Shared by the outlier test (k_render.hip), track quality and pose hypotheses (quality_body.h), VSD
+// (k_vsd.hip), masks from poses (k_silhouette.hip) and the scene renderer (k_scene.hip); every translation unit that includes it is
+// built with -ffp-contract=off.  The numerics of the outlier test's other render mode, ROFT_RENDER_GL, stand next to it in
+// raster_gl.h; the LDS arithmetic of a launcher in raster_shape.h.
+// THE DRAW CONTRACT, for a workgroup of kThreads threads whose threads all take every step:
+//   1. box_reset(sh); barrier.
+//   2. `project` = project_vertex with the pose and the intrinsics; project_mesh(.., sh.box, &sh.behind, project); barrier.
+//      (Several boxes may be reset behind one barrier and filled behind one more.)
+//   3. box = box_read(sh, w, h).  Nothing can be drawn unless box.drawable(): every vertex on one side of the target, or none in
+//      front of the near plane -- the box is then as box_reset left it.  flips = cull_table(mesh.flip, sh.behind).
+//   4. Per strip of the box's rows (strip_rows: as many as the window holds, at least one; the launcher refuses a target whose row
+//      does not fit): clear the window; barrier; draw_triangles(.., strip.js, strip.je, store); barrier; read the window; barrier
+//      before the next strip clears it.  The stores are order-free atomics, so a window's bits depend on the pose and the mesh only.
 #pragma once
 
+#include "raster_shape.h"
 #include "roft_device.h"
 
 namespace roft {
 
 constexpr uint32_t kDepthEmpty = 0x7F800000u;   // +inf: the pixel of a depth window nothing was drawn into
 
-// Dynamic LDS of a workgroup that draws a mesh: [the projected vertices, when they are cached] | [its window].
-constexpr size_t kRasterLdsBudget = 160 * 1024 - 4096;   // what such a kernel may ask for (the rest: its static LDS)
-__host__ __device__ constexpr size_t vertex_cache_bytes(int verts) { return ((size_t)verts * 12 + 15) & ~(size_t)15; }   // = the window's offset
+// The mesh a kernel draws: `tris` in the order the caller wants triangle indices in, `flip` the bits of a closed mesh (mesh_class.h:
+// 1 = wound clockwise seen from outside) or nullptr: every triangle is drawn.
+struct MeshView {
+    const float* verts;
+    const int32_t* tris;
+    const uint8_t* flip;
+    int n_verts, n_tris;
+};
+__host__ __device__ inline MeshView mesh_view(const ObjParams& p) { return MeshView{p.verts, p.tris, p.tri_flip, p.n_verts, p.n_tris}; }
+
+// x y z, w x y z: false = the pose draws nothing (its triangles would fail raster_projected's own tests one by one)
+__device__ __forceinline__ bool pose_is_finite(const double* pose7)
+{
+    bool finite = true;
+    for (int i = 0; i < 7; ++i) finite = finite && (fabs(pose7[i]) < INFINITY);
+    return finite;
+}
 
 struct RenderPose {
     float R[9];
@@ -115,9 +138,7 @@ __device__ __forceinline__ int cull_code(const uint8_t* flips, int t) { return f
 // s_v (3 floats per vertex) when `cached`, and widens s_box = {i0, j0, i1, j1}, the pixel box of everything that can be drawn;
 // *s_behind is set when some vertex is not in front of the near plane (cull_table).  kVB: vertices per thread whose coordinates are
 // fetched together.  kRowsOnly: the caller uses the rows of the box only (s_box[1], s_box[3]); the columns are left as it set them.
-// Contract: the caller sets s_box = {INT32_MAX, INT32_MAX, -1, -1} and *s_behind = 0 behind a barrier, and puts a barrier after
-// the call.  It then reads i0 = min(s_box[0], w - 1), i1 = s_box[2], j0 = min(s_box[1], h - 1), j1 = s_box[3]; nothing can be drawn
-// when i1 < i0 or j1 < j0 (every vertex on one side of the target, or none in front: the box is untouched).
+// s_box / s_behind: a MeshBoxShared's fields, reset and read as the draw contract above says (box_reset, box_read below).
 // Why the box of the VERTICES covers every triangle: raster_projected clips a triangle to ceil(min - 0.5) .. floor(max - 0.5)
 // of its corners' coordinates, clamped to the target; both bounds are monotone in the coordinates, so a triangle's range lies
 // between the smallest lower bound and the largest upper bound of its vertices, and only triangles with all three corners in
@@ -216,7 +237,7 @@ __device__ __forceinline__ bool corner_box_settles(const float* corner, const Re
 }
 
 // The projected corners of a triangle: from the cache project_mesh filled, else through `project` again.
-// (Callers read cull_code BEFORE the fetch, so that the flip table's load is in flight with the corners': read behind the fetch it
+// (draw_triangles reads cull_code BEFORE the fetch, so that the flip table's load is in flight with the corners': read behind the fetch it
 //  cost quality_kernel and pose_silhouette_kernel 3 us of 135 per launch, docs/notebook.md.)
 template <class Project>
 __device__ __forceinline__ void fetch_triangle(const float* s_v, bool cached, const float* verts, int v0, int v1, int v2, Project project,
@@ -232,6 +253,98 @@ __device__ __forceinline__ void fetch_triangle(const float* s_v, bool cached, co
         project(verts + (size_t)3 * v1, x1, y1, z1);
         project(verts + (size_t)3 * v2, x2, y2, z2);
     }
+}
+
+// ---- the box: what project_mesh leaves in LDS (the caller declares it __shared__), reset before and read behind the pass
+struct MeshBoxShared { int box[4], behind; };   // box = {i0, j0, i1, j1}
+__device__ __forceinline__ void box_reset(MeshBoxShared& sh)   // (the caller owes a barrier before project_mesh)
+{
+    if (threadIdx.x < 4) sh.box[threadIdx.x] = (threadIdx.x < 2) ? INT32_MAX : -1;
+    if (threadIdx.x == 0) sh.behind = 0;
+}
+// The pixel box of everything that can be drawn: columns i0 .. i1, rows j0 .. j1 of the target.
+struct MeshBox {
+    int i0, j0, i1, j1;
+    __device__ __forceinline__ int width() const { return i1 - i0 + 1; }
+    __device__ __forceinline__ bool drawable() const { return i1 >= i0 && j1 >= j0 && i0 >= 0 && j0 >= 0; }
+};
+// (behind the barrier after project_mesh; the min takes back the empty lower bound w / h of a vertex right of or below the target)
+__device__ __forceinline__ MeshBox box_read(const MeshBoxShared& sh, int w, int h)
+{
+    return MeshBox{min(sh.box[0], w - 1), min(sh.box[1], h - 1), sh.box[2], sh.box[3]};
+}
+
+// ---- the window.  One strip of a box: columns i0 .. i1 (win_w of them), rows js .. je, npx pixels, row-major: pixel i of the
+// strip is (i0 + i % win_w, js + i / win_w).
+struct Strip { int i0, i1, js, je, win_w, npx; };
+// rows of a strip when the window holds win_cap pixels and the box is win_w wide (win_cap >= win_w: the launcher's refusal)
+__device__ __forceinline__ int strip_rows(int win_cap, int win_w) { return max(1, win_cap / win_w); }
+// the strip of `rows` rows that begins at row js of the box
+__device__ __forceinline__ Strip strip_from(const MeshBox& b, int js, int rows)
+{
+    const int je = min(b.j1, js + rows - 1), win_w = b.width();
+    return Strip{b.i0, b.i1, js, je, win_w, win_w * (je - js + 1)};
+}
+// strip k of a box cut into runs of cw columns x strips of `rows` rows, n_cols runs side by side (a row wider than the window)
+__device__ __forceinline__ Strip strip_at(const MeshBox& b, int cw, int rows, int n_cols, int k)
+{
+    const int is = b.i0 + (k % n_cols) * cw, js = b.j0 + (k / n_cols) * rows;
+    return strip_from(MeshBox{is, js, min(b.i1, is + cw - 1), b.j1}, js, rows);
+}
+// The contract's window, in dynamic LDS: a pixel is the IEEE bits of its (positive) eye-space depth -- positive floats order like
+// their bits --, kDepthEmpty where nothing was drawn.  clear / the stores / the reads each need a barrier between them.
+struct DepthWindow {
+    uint32_t* z;   // [win_cap]
+    __device__ __forceinline__ void clear(int npx, int threads) const { for (int i = threadIdx.x; i < npx; i += threads) z[i] = kDepthEmpty; }
+    // order-free minimum of the depth bits: raster_projected's `store(i, j, z)` and, the index unused, draw_triangles' `store(i, j, z, t)`
+    __device__ __forceinline__ auto store(const Strip& s) const
+    {
+        ROFT_LDS uint32_t* const zw = pin_lds(z);
+        const int i0 = s.i0, js = s.js, win_w = s.win_w;
+        return [zw, i0, js, win_w](int i, int j, float depth, int /*t*/ = 0) {
+            (void)__hip_atomic_fetch_min(zw + ((j - js) * win_w + (i - i0)), __float_as_uint(depth), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        };
+    }
+    __device__ __forceinline__ bool covered(int i) const { return z[i] != kDepthEmpty; }
+    __device__ __forceinline__ float depth(int i, int, int) const { return __uint_as_float(z[i]); }
+};
+
+// ---- the triangles.  Every triangle of the mesh, thread-strided, onto rows j_lo .. j_hi of a w x h target: `store(i, j, z, t)`
+// receives every covered pixel with its eye-space depth and the triangle's index.  s_v / cached / project: as project_mesh left and took them; flips:
+// cull_table's.  Behind the barrier after the clear; the caller owes a barrier before anything reads what the stores wrote.
+template <int kThreads, class Project, class Store>
+__device__ __forceinline__ void draw_triangles(const MeshView& mesh, const float* s_v, bool cached, const uint8_t* flips, Project project,
+                                               int w, int h, int j_lo, int j_hi, Store store)
+{
+    for (int t = threadIdx.x; t < mesh.n_tris; t += kThreads) {
+        const int32_t* tri = mesh.tris + (size_t)3 * t;
+        const int v0 = tri[0], v1 = tri[1], v2 = tri[2];
+        const int cull = cull_code(flips, t);   // (before the fetch: see fetch_triangle)
+        float x0, y0, z0, x1, y1, z1, x2, y2, z2;
+        fetch_triangle(s_v, cached, mesh.verts, v0, v1, v2, project, x0, y0, z0, x1, y1, z1, x2, y2, z2);
+        raster_projected(x0, y0, z0, x1, y1, z1, x2, y2, z2, w, h, j_lo, j_hi, cull, [&store, t](int i, int j, float z) { store(i, j, z, t); });
+    }
+}
+
+// ---- the counts.  Integer counts of a workgroup's threads -> one LDS row per wave; behind a barrier of the caller's, rows_total
+// adds the rows of count k (exact, so no figure depends on threads or waves).
+template <int N>
+__device__ __forceinline__ void wave_sums_to_rows(int (&cnt)[N], int (*s_rows)[N])
+{
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) cnt[k] += __shfl_down(cnt[k], off, 64);
+    }
+#pragma unroll
+    for (int k = 0; k < N; ++k)
+        if ((threadIdx.x & 63) == 0) s_rows[threadIdx.x >> 6][k] = cnt[k];
+}
+template <int kThreads, int N>
+__device__ __forceinline__ int rows_total(const int (*s_rows)[N], int k)
+{
+    int tot = 0;
+    for (int w = 0; w < kThreads / 64; ++w) tot += s_rows[w][k];
+    return tot;
 }
 
 }  // namespace roft

@@ -12,7 +12,7 @@
 //   background   the camera image, or its gray (R 4899 + G 9617 + B 1868 + 8192) >> 14 in all three channels, or zeros.
 #pragma once
 
-#include "roft_device.h"
+#include "raster.h"
 
 namespace roft {
 
@@ -20,13 +20,6 @@ constexpr int kSceneThreads = 1024;            // visibility: one workgroup per 
 constexpr int kSceneMaxInstances = 256;        // 8 bits of the key
 constexpr uint64_t kSceneKeyEmpty = ~0ull;     // nothing drawn (a key's depth word is below 0x7F800000 when it is a surface)
 constexpr int kResolvePixels = 4;              // pixels per thread of the resolve pass: 12 bytes of RGB = three dwords
-
-struct SceneMesh {
-    const float* verts;
-    const int32_t* tris;      // the caller's order: a key's triangle index is the caller's
-    const uint8_t* flip;      // closed mesh: 1 = wound clockwise seen from outside; nullptr: every triangle is drawn
-    int n_verts, n_tris;
-};
 
 struct SceneStyle {
     float tint[3], opacity, ambient;
@@ -40,7 +33,7 @@ struct ScenePose {
 struct SceneArgs {
     int W, H, n_frames, n_instances;
     float fx, fy, cx, cy;
-    const SceneMesh* meshes;
+    const MeshView* meshes;        // tris in the caller's order: a key's triangle index is the caller's
     const int* mesh_index;         // [n_instances]
     const double* poses;           // [n_frames][n_instances][7]
     const uint8_t* valid;          // [n_frames][n_instances] or nullptr

@@ -11,7 +11,7 @@ struct roft_scene_renderer {
     Event ev[3];
     bool timed = false;
     std::vector<DeviceMesh> resident;   // the meshes the table below names
-    DevBuf<SceneMesh> meshes;
+    DevBuf<MeshView> meshes;
     DevBuf<uint64_t> keys;
     DevBuf<ScenePose> pose_table;
     DevBuf<double> poses;
@@ -131,21 +131,14 @@ int render(roft_scene_renderer* r, const roft_scene_desc* d, uint8_t* rgb_out, f
     if (depth_out) { HIP_TRY(r->depth.ensure(padded)); a.depth = r->depth.p; }
     if (instance_out) { HIP_TRY(r->instance.ensure(padded)); a.instance = r->instance.p; }
     if (triangle_out) { HIP_TRY(r->triangle.ensure(padded)); a.triangle = r->triangle.p; }
-    // The LDS of a visibility workgroup: the projected vertices when they leave room for a window of 8 k keys, and the window.
-    // 8 k keys = 64 KB: two workgroups share a CU.  (A larger window means fewer strips, each of which walks all triangles, but one
-    // workgroup per CU; the object of a tracked sequence covers a few tens of thousands of pixels, a handful of strips.)
-    const size_t budget = kRasterLdsBudget, vbytes = vertex_cache_bytes(r->max_verts);
-    size_t win = std::min<size_t>(WH, 8192);
-    const bool cache = vbytes + 8 * win <= budget;
-    if (d->window_pixels > 0) win = std::min<size_t>(win, (size_t)d->window_pixels);
-    a.vcache_cap = cache ? r->max_verts : 0;
-    a.win_cap = (int)win;
-    const size_t lds = (cache ? vbytes : 0) + 8 * win;
+    const RasterShape sh = scene_window_shape(r->max_verts, WH, d->window_pixels);   // the LDS of a visibility workgroup
+    a.vcache_cap = sh.vcache_cap;
+    a.win_cap = sh.win_cap;
     // workgroups per instance: enough of them to fill the chip when the call is small
     a.parts = (int)std::max<size_t>(1, std::min<size_t>(32, (size_t)2 * device_cu_count() / std::max<size_t>((size_t)F * I, 1)));
     HIP_TRY(hipEventRecord(r->ev[0], s));
     HIP_TRY(hipMemsetAsync(r->keys.p, 0xFF, padded * sizeof(uint64_t), s));   // kSceneKeyEmpty
-    if (I > 0) launch_scene_visibility(a, lds, s);
+    if (I > 0) launch_scene_visibility(a, sh.lds, s);
     HIP_TRY(hipEventRecord(r->ev[1], s));
     launch_scene_resolve(a, s);
     HIP_TRY(hipEventRecord(r->ev[2], s));
@@ -185,15 +178,15 @@ int roft_scene_renderer_create(const roft_camera* cam, const roft_mesh* meshes, 
     for (int k = 0; k < 3 && e == hipSuccess; ++k) e = r->ev[k].create();
     if (e != hipSuccess) return fail(ROFT_ERR_DEVICE, std::string("stream creation: ") + hipGetErrorString(e));
     r->resident = std::vector<DeviceMesh>((size_t)n_meshes);
-    std::vector<SceneMesh> table((size_t)n_meshes);
+    std::vector<MeshView> table((size_t)n_meshes);
     for (int k = 0; k < n_meshes; ++k) {
         // the caller's triangles as they are (a key's triangle index is the caller's); closed meshes get their flip bits
         TRY(r->resident[k].upload(meshes[k], MeshLayout::kCallersOrder, r->stream));
-        table[k] = r->resident[k].scene_mesh();
+        table[k] = r->resident[k].view();
         r->max_verts = std::max(r->max_verts, meshes[k].n_verts);
     }
     e = r->meshes.ensure((size_t)n_meshes);
-    if (e == hipSuccess && n_meshes) e = hipMemcpy(r->meshes.p, table.data(), sizeof(SceneMesh) * n_meshes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && n_meshes) e = hipMemcpy(r->meshes.p, table.data(), sizeof(MeshView) * n_meshes, hipMemcpyHostToDevice);
     const size_t WH = (size_t)r->W * r->H;
     if (e == hipSuccess) e = r->keys.ensure((WH * max_frames_per_call + kResolvePixels - 1) / kResolvePixels * kResolvePixels);
     if (e != hipSuccess) return fail(ROFT_ERR_DEVICE, std::string("mesh upload: ") + hipGetErrorString(e));

@@ -2,8 +2,7 @@
 // The kernel reads the mesh, the pose pairs and the depth images and adds only to the pairs' own integer rows.
 #pragma once
 
-#include "roft_device.h"
-#include "scene.h"
+#include "raster.h"
 
 namespace roft {
 
@@ -11,7 +10,7 @@ constexpr int kVsdMaxTaus = ROFT_VSD_MAX_TAUS;
 constexpr int kVsdCounts = 4 + kVsdMaxTaus;   // a pair's row: n_union, n_inter, n_gt, n_est, fail[0 .. 16)
 
 struct VsdArgs {
-    SceneMesh mesh;
+    MeshView mesh;
     const double* est;      // [n][7] x y z, w x y z of the launch's pairs
     const double* ref;
     const float* depth;     // the launch's depth images
@@ -30,11 +29,8 @@ struct VsdArgs {
     int parts;              // workgroups per pair: they deal the strips out in turn
 };
 
-// The LDS of a workgroup for a mesh of n_verts vertices on a target `width` wide: false when not even one row of the target fits
-// the two windows (nothing may be launched then).  window_pixels > 0 caps win_cap (a strip still holds at least one row).
-bool vsd_shape(int n_verts, int width, int window_pixels, int& vcache_cap, int& win_alloc, int& win_cap, size_t& lds);
-
-// n pairs (grid: n * a.parts workgroups) add their counts to a.counts; `lds` from vsd_shape
+// n pairs (grid: n * a.parts workgroups) add their counts to a.counts; a.vcache_cap / win_alloc / win_cap and `lds` from vsd_shape
+// (raster_shape.h), which refuses a target of which not even one row fits the two windows: nothing may be launched then
 void launch_vsd(const VsdArgs& a, int n, size_t lds, hipStream_t s);
 // counts[n][kVsdCounts] -> errors[n][n_taus] and rows[n][4 + n_taus]
 void launch_vsd_finish(const int32_t* counts, int n, int n_taus, double* errors, int32_t* rows, hipStream_t s);

@@ -100,6 +100,15 @@ def test_plan_adds_exactly_the_launch_and_its_event(tmp_path):
     assert int(r.stdout) > 10000
 
 
+def test_launcher_shapes_equal_the_recorded_ones(tmp_path):
+    """raster_shape.h's three launcher rules against tests/golden/raster_shapes.json, every field of every row"""
+    exe = str(tmp_path / "raster_shape_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC, os.path.join(ROOT, "tests", "cpp", "raster_shape_check.cpp"), "-o", exe])
+    r = subprocess.run([exe, os.path.join(ROOT, "tests", "golden", "raster_shapes.json")], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    assert int(r.stdout) == 3 * 224 + 224   # 8 meshes x 7 widths x 4 window_pixels, the scene's on two targets each
+
+
 # ---- the reference's own properties --------------------------------------------------------------------------------------
 
 def camera_of(oracle, W, H):

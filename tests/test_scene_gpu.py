@@ -3,6 +3,7 @@ and tests/scene_ref.py: single meshes, occlusion between instances, the determin
 from a tracked sequence to PNG files, and one large shape."""
 import functools
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -164,6 +165,41 @@ def test_nan_pose_and_invalid_flag_draw_nothing_and_disturb_nothing():
             assert not (out["instance"][1] == 1).any() and (clean["instance"][1] == 1).any()
     none = ops.render_scene(cam, [box, torus], [0, 1, 0], poses, valid=np.zeros((4, 3)), background=bg)
     assert (none["instance"] == -1).all() and (none["depth"] == 0).all() and np.array_equal(none["rgb"], bg)
+
+
+def _box_columns(tile):
+    cols = np.flatnonzero((tile > 0).any(axis=0))
+    return int(cols[-1] - cols[0] + 1)
+
+
+def test_column_runs_and_a_mesh_beyond_the_vertex_cache_at_64x48(tmp_path):
+    """The two strip shapes and the two projection paths of the visibility kernel, each against the oracle's tile bit for bit, on the
+    smallest target that reaches them.  window_pixels below the width of the object's box cuts its rows into column runs; two rows'
+    worth draws strips of whole rows.  A mesh of more vertices than the LDS holds next to a window of the whole 64 x 48 target is
+    projected per triangle: the launcher's own rule (scene_window_shape, roft_amd/csrc/raster_shape.h, through
+    tests/cpp/raster_shape_check.cpp) says which of the two meshes it caches."""
+    size = (64, 48)
+    c = su.cam(*size)
+    cam = su.lib_cam(c)
+    exe = str(tmp_path / "raster_shape_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "roft_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "raster_shape_check.cpp"), "-o", exe])
+    small, big = _box(), synth.box_mesh(synth.CRACKER_BOX_HALF_EXTENTS, n=43)
+
+    def vcache_cap(mesh, wp):
+        return int(subprocess.check_output([exe, str(mesh[0].shape[0]), str(size[0] * size[1]), str(wp)]))
+    p = su.pose([0.01, -0.01, 0.9], [1, 2, 3], 0.7)
+    for name, (v, t) in (("cached", small), ("per triangle", big)):
+        want = ob.render_depth(ob.make_mesh(v, t), p[:3], p[3:], su.oracle_cam(c), 1)
+        width = _box_columns(want)
+        assert 12 <= width < size[0] and (want > 0).any(axis=1).sum() >= 8, "several column runs and several strips of two rows"
+        whole = ops.render_scene(cam, [(v, t)], [0], p[None, None], outputs=("depth", "triangle"))
+        assert su.same_bits(whole["depth"][0], want), name
+        for wp in (0, width // 3, 2 * width + 1, 1):
+            assert vcache_cap((v, t), wp) == (v.shape[0] if name == "cached" else 0), "the launcher caches the small mesh only"
+        for wp in (width // 3, 2 * width + 1, 1):
+            out = ops.render_scene(cam, [(v, t)], [0], p[None, None], outputs=("depth", "triangle"), window_pixels=wp)
+            assert su.same_bits(out["depth"][0], want), (name, wp)
+            assert np.array_equal(out["triangle"][0], whole["triangle"][0]), (name, wp)
 
 
 def test_no_frames_each_output_alone_and_no_instances():

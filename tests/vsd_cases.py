@@ -21,7 +21,7 @@ ESTIMATES = {
     "off": scene_util.pose([0.4, 0.3, 0.45], [1, 2, 3], 0.7),   # off screen
 }
 CLOSE = scene_util.POSES[2]   # vertices behind the near plane: the back-face rule is off
-CACHE_VERTS = 10581           # the most vertices the kernel's LDS cache holds next to its two windows (k_vsd.hip, vsd_shape)
+CACHE_VERTS = 10581           # the most vertices the kernel's LDS cache holds next to its two windows (raster_shape.h, vsd_shape)
 
 
 @functools.lru_cache(maxsize=None)
